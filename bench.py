@@ -61,6 +61,37 @@ def loss_head(ret):
     return 1e3 * rgb + 1e2 * eik + dep
 
 
+DUMP_MAX_ELEMS = 1 << 20       # --dump-outputs: larger arrays are written as this many entries at fixed seeded positions
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs, modules):
+    """--dump-outputs: the step's outputs (`outputs`: name -> tensor) and every parameter gradient the step left on the
+    modules (`modules`: [(prefix, module)] -> 'grad.<prefix>.<parameter name>') as <out_dir>/<name>.npy, float64 stays
+    float64, everything else becomes float32.  An array of more than DUMP_MAX_ELEMS entries is flattened and sampled at
+    DUMP_MAX_ELEMS sorted positions drawn by numpy's default_rng(0) from its size alone, so two runs sample the same entries."""
+    import numpy as np
+    arrays = dict(outputs)
+    for prefix, mod in modules:
+        for name, p in mod.named_parameters():
+            if p.grad is not None:
+                arrays[f"grad.{prefix}.{name}"] = p.grad
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {out_dir}", file=sys.stderr)
+
+
 def host_threads(cap=32):
     """cores this process may actually run on (affinity mask and cgroup quota, not the machine's core count: sizing the
     OpenMP pool by os.cpu_count() inside a CPU-limited container oversubscribes spinning threads)"""
@@ -213,7 +244,13 @@ def main():
     ap.add_argument("--inference", action="store_true",
                     help="time the forward-only render under no_grad (the eval path: Camera.render_img_by_slices renders an image "
                          "in rand_rays chunks, pipelines/Camera.py:274-311) instead of the training step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the render outputs, the loss and every "
+                         "parameter gradient; inference: the render outputs) as DIR/<name>.npy, float32 / float64, rank 0 only; arrays "
+                         f"above {DUMP_MAX_ELEMS} elements as a fixed seeded sample of that many entries (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     preset = CONFIGS[args.config]
     args.rays = preset["rays"] if args.rays is None else args.rays
     args.samples = preset["samples"] if args.samples is None else args.samples
@@ -307,22 +344,34 @@ def main():
     depth_ref = torch.zeros(1, args.rays, device=dev)
     one = torch.ones((), device=dev)              # d loss / d loss (what loss.backward() would allocate and fill every step)
 
-    def render_step():
-        """Renderer.forward -> loss head -> backward: every parameter's .grad is (re)written"""
+    def render_step(keep=False):
+        """Renderer.forward -> loss head -> backward: every parameter's .grad is (re)written.  keep: -> what a caller of the
+        step receives, the render's result dict (+ 'loss'), detached (no autograd graph outlives the step)"""
         if sharded_opt is not None:
             sharded_opt.wait_params()       # the previous step's all-gathers (device-side wait) before the first parameter read
         if args.inference:
             with torch.no_grad():
-                return ren.forward(opt, center, ray, sdf, rad)["rgb"]
+                ret = ren.forward(opt, center, ray, sdf, rad)
+            return ret if keep else ret["rgb"]
         for p in params:
             p.grad = None
         if args.torch_loss:
-            loss = loss_head(ren.forward(opt, center, ray, sdf, rad))
+            ret = ren.forward(opt, center, ray, sdf, rad)
+            loss = loss_head(ret)
+            losses = None
         elif args.split_loss:           # Renderer.forward, then the loss head as its own two kernels
-            loss = head.terms(ren.forward(opt, center, ray, sdf, rad), rgb_gt, d_points=depth_ref)[1]
+            ret = ren.forward(opt, center, ray, sdf, rad)
+            terms, loss = head.terms(ret, rgb_gt, d_points=depth_ref)
+            losses = None
         else:                           # the loss head inside the render (forward epilogue / backward prologue)
-            loss = ren.forward_with_loss(opt, center, ray, sdf, rad, head, rgb_gt, d_points=depth_ref)[1]["all"]
+            ret, losses = ren.forward_with_loss(opt, center, ray, sdf, rad, head, rgb_gt, d_points=depth_ref)
+            loss = losses["all"]
         loss.backward(gradient=one)
+        if keep:
+            if args.split_loss:
+                losses = head.as_dict(terms, loss)
+            out = dict(ret, **{f"loss.{k}": v for k, v in (losses or {"all": loss}).items()})
+            return {k: v.detach() for k, v in out.items()}
         return loss
 
     mode = "graph" if args.graph else args.launch
@@ -344,21 +393,25 @@ def main():
     captured = None
     use_graph = False
 
-    def whole_step():
-        """what a graph captures: the render step and the gradient exchange behind it (sharded form: + the update)"""
-        render_step()
+    def whole_step(keep=True):
+        """what a graph captures: the render step and the gradient exchange behind it (sharded form: + the update).  A capture
+        keeps the step's outputs (every replay rewrites them in place); eager steps keep them only when asked"""
+        out = render_step(keep)
         if sharded_opt is not None:
             sharded_opt.step()
         if reducer is not None:
             reducer.all_reduce()
+        return out if keep else None
 
-    def step(eager=False):
+    def step(eager=False, keep=False):
+        """-> with `keep` (or as a graph replay): the step's outputs (render_step(keep=True))"""
         if use_graph and not eager:
-            captured.replay()
+            out = captured.replay()
         else:
-            whole_step()
+            out = whole_step(keep)
         if local_opt is not None:
             local_opt.step()
+        return out
 
     launch_probe = None
     if mode == "graph":
@@ -442,29 +495,21 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # timed region: EXACTLY K steps between barrier + synchronize on both sides.  That block is repeated until ~1 s of device
-    # time has been sampled (a driver run with --steps 20 would otherwise time 12 ms) and the MEDIAN block is reported; every
-    # block is a complete measurement under the contract, min / max are in the line.
-    def timed_block():
-        barrier()
-        t_start = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        barrier()
-        return time.perf_counter() - t_start
-    blocks = [timed_block()]
-    n_blocks = max(1, min(100, int(1.0 / max(blocks[0], 1e-4) + 0.999)))
-    if multi:                                # every rank must run the same number of blocks
-        nb = torch.tensor([n_blocks], device=dev)
-        dist.all_reduce(nb, op=dist.ReduceOp.MAX)
-        n_blocks = int(nb.item())
-    while len(blocks) < n_blocks:
-        blocks.append(timed_block())
-    if multi:                                # max over ranks, block by block
-        tb = torch.tensor(blocks, device=dev, dtype=torch.float64)
+    # timed region: EXACTLY K steps between barrier + synchronize on both sides, nothing else (the number of steps of a longer
+    # measurement is chosen from this line's ms_per_step).  The last step keeps its outputs for --dump-outputs.
+    last = args.steps - 1
+    barrier()
+    t_start = time.perf_counter()
+    for i in range(args.steps):
+        outputs = step(keep=i == last)
+    barrier()
+    dt = time.perf_counter() - t_start
+    if multi:                                # max over ranks
+        tb = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tb, op=dist.ReduceOp.MAX)
-        blocks = tb.tolist()
-    dt = sorted(blocks)[len(blocks) // 2]
+        dt = float(tb.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, [("sdf", sdf), ("rad", rad)])
     # N > 1: what the gradient exchange costs, measured outside the timed region -- the same K steps WITHOUT exchange and update
     # (compute only), so that a scaling run records exposed exchange time next to the bytes it moves.  Not
     # for the level-group overlap, whose reductions are issued from inside the backward.
@@ -572,7 +617,6 @@ def main():
     out = {
         "metric": "rendered rays/sec (forward only, no_grad)" if args.inference else "rendered rays/sec (fwd+bwd)", "value": value, "unit": "rays/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "timed_blocks": len(blocks), "ms_per_step_min": min(blocks) / args.steps * 1e3, "ms_per_step_max": max(blocks) / args.steps * 1e3,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "launch": ("hipGraph replay of the whole step" if use_graph else "eager") + (" (auto)" if mode == "auto" else ""),
         "eager_profiled_ms_per_step": dt_eager / args.steps * 1e3,

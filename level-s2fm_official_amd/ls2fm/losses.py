@@ -115,6 +115,7 @@ class RenderLossHead:
         """-> (terms [5] = rgb, eikonal, DC, mse, all ; all as its own 0-dim tensor: backward through it costs no
         select/zero-fill kernels)"""
         normals = ret["normals"]
+        _lib.require_device(normals)        # before _workspace() asks torch.cuda about the tensor's device
         n_rays = normals.numel() // (3 * normals.shape[-2])
         return _LossHead.apply(ret["rgb"], normals, ret["depth_mlp"], d_points, rgbs_gt, _mask(mask_eik, n_rays, rgbs_gt),
                                _mask(mask_finish, n_rays), _mask(mask_bg, n_rays, rgbs_gt), self.weights,

@@ -4,7 +4,7 @@ device tensors.  The figures of such a run mean nothing (both ranks share the GP
 is tested is the control flow the 2/4/8-GPU runs take: process-group set-up, sharded rays, the gradient exchange -- the default
 all-reduce (the metric's step: no optimizer inside; overlapped from inside the backward, or flat with --no-overlap) and (--shard) reduce-scatter -> sharded
 Adam -> all-gather (monolithic, or --shard-groups 2: pipelined by level group) --,
-barriers, the block-count and max-over-ranks reductions, ONE JSON line on rank 0."""
+barriers, the max-over-ranks reduction of the timed block, ONE JSON line on rank 0."""
 import json
 import os
 import socket

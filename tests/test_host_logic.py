@@ -302,6 +302,8 @@ def test_numa_binding_is_safe_without_a_gpu_topology(monkeypatch):
     node = numa.gpu_numa_node(0)
     if node is None:                                       # no KFD topology here: nothing is bound
         assert numa.bind_to_gpu_numa_node(0) is None and os.sched_getaffinity(0) == before
+    for var in ("ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):          # (read before HIP_VISIBLE_DEVICES: a GPU box may set them)
+        monkeypatch.delenv(var, raising=False)
     monkeypatch.setenv("HIP_VISIBLE_DEVICES", "GPU-deadbeef")            # a UUID form: not resolved, not an error
     assert numa.gpu_numa_node(0) is None
 
