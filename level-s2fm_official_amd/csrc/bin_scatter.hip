@@ -45,31 +45,11 @@ namespace {
 // and no overflow path (any item count is served).  Every item's slot is fixed once (rank = LDS atomic) and kept in registers;
 // a window pass re-derives the item's indices (eight hashes) and stages the items whose slot falls into the window.  The
 // run offsets (two dependent global loads per slab) are requested at the very top, ahead of the records.
-#ifndef LS2FM_FILL_NT
-#define LS2FM_FILL_NT 0
-#endif
-// how the accumulate pass stores the gradient tables: 1 = non-temporal (default: 100 MB that nothing reads before the optimizer --
-// kept out of the L2s they leave the table slices and item lists in place: slab_accumulate 84 -> 76 us and the NEXT step's gather
-// pass 104 -> 98 us at C2), 0 = plain, 2 = write-through (sc1: no gain).  The fill's item stores stay plain: as nt / sc1 stores of
-// 16-byte halves they cost 190 instead of 86 us.
-#ifndef LS2FM_ACC_NT_STORE
-#define LS2FM_ACC_NT_STORE 1
-#endif
-#ifndef LS2FM_FILL_PROBE
-#define LS2FM_FILL_PROBE 0
-#endif
-// Round 6: how the staged items leave the LDS.  0 = one ITEM per lane (rounds 1-5): a 32-byte item is two 16-byte stores whose lanes
-// are 32 bytes apart -- every store instruction touches 16 lines and fills half of each; a 20-byte item five dword stores 20 bytes
-// apart (10 lines, a fifth of each).  1 = FLAT: the staging area is walked in store-sized chunks, consecutive lanes write consecutive
-// 16-byte (dual) / 4-byte (single field) pieces of the sorted order, which is contiguous in memory inside a (workgroup, slab) run:
-// the same number of store instructions, each covering whole lines except at run boundaries.
-#ifndef LS2FM_FILL_FLAT
-#define LS2FM_FILL_FLAT 1
-#endif
-// LS2FM_FILL_REC_NT (round 6): the scatter records (read exactly once, here) as non-temporal loads
-#ifndef LS2FM_FILL_REC_NT
-#define LS2FM_FILL_REC_NT 0
-#endif
+// The accumulate pass stores the gradient tables non-temporally (nothing reads them before the optimizer; DESIGN.md section 4:
+// slab_accumulate and the next step's gather pass both gain); the fill's item stores stay plain (profiles/r05_scatter_notes.md section 4).
+// The staged items leave the LDS as a FLAT stream -- consecutive lanes write consecutive pieces of the sorted order, whole lines
+// per store instruction -- instead of one item per lane (profiles/r06_notes.md section 3a).  The records are read with plain
+// loads (non-temporal ones: section 16).
 #ifndef LS2FM_FILL_MINW
 #define LS2FM_FILL_MINW 5
 #endif
@@ -82,7 +62,7 @@ __global__ void __launch_bounds__(kFillThreads, LS2FM_FILL_MINW)
 scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, const float* __restrict__ ray, int64_t n_points,
                     int64_t p_pad, int sshift, const float* __restrict__ rpt, const float* __restrict__ rec1,
                     const float* __restrict__ rec2, const float* __restrict__ ray_bound, int64_t n_rays, int64_t r_pad,
-                    BinMeta bm, int level_base, int reverse, int n_explicit, SideJobs sj) {
+                    BinMeta bm, int level_base, int n_explicit, SideJobs sj) {
     typedef typename ItemOf<DUAL>::type ItemT;
     __shared__ int hist[kBins];          // items of this workgroup per slab, then running rank
     __shared__ int lds_off[kBins];       // first slot (in the workgroup's sorted order) of the slab's run
@@ -105,93 +85,51 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
         if (job < sj.dec_blocks + sj.l1_jobs + sj.n_red + kFinalizeTasks) side_job_run(sj, job, reinterpret_cast<float*>(s_raw), &s_total);
         return;
     }
-    // issue-priority experiment (round 6, profiles/r06_notes.md section 9): LS2FM_FILL_PRIO = 1: raised until the hash pass is done (a young
-    // workgroup's record loads go out first), 2: raised behind it (a workgroup that has its items staged leaves first).  Default 0.
-#ifndef LS2FM_FILL_PRIO
-#define LS2FM_FILL_PRIO 0
-#endif
-    if (LS2FM_FILL_PRIO == 1) __builtin_amdgcn_s_setprio(2);
+    // (no issue-priority hooks: raised through or behind the hash pass, or for the write-out, measured nothing; profiles/r06_notes.md section 9)
     ItemT* __restrict__ g_items = reinterpret_cast<ItemT*>(bm.items);
     // levels are walked last to first: the accumulate launch reads the lists first to last, i.e. most recently written first
+    // (slab_accumulate 101 -> 98 us at C2 against the fill's levels first to last)
     const int y_lv = (int)blockIdx.y - sj.rows, n_lv = (int)gridDim.y - sj.rows;
-    const int tid = threadIdx.x, lane = tid & 63, l = level_base + (reverse ? n_lv - 1 - y_lv : y_lv);
+    const int tid = threadIdx.x, lane = tid & 63, l = level_base + n_lv - 1 - y_lv;
     // Round 6: which TILE a workgroup fills.  Workgroup x of a row runs on XCD x % 8 (observed; the rows are multiples of 8 wide
     // whenever this mapping is used), and the runs of neighbouring tiles are neighbours in a slab's list: a run is ~8 items = 256 B
     // at a 32-byte granularity, so most runs end inside a cache line whose other part the NEXT tile's workgroup writes.  With
     // tile = x the two halves of such a line are written through two different XCD L2s (two partial-line write-backs); with the
     // XCDs walking contiguous tile ranges -- tile = (x % 8) (n_tiles / 8) + x / 8 -- they meet in one L2 a dispatch round apart.
-    // Any mapping gives the same items in the same places.  LS2FM_FILL_XCD_TILES=0: tile = x.
-#ifndef LS2FM_FILL_XCD_TILES
-#define LS2FM_FILL_XCD_TILES 1
-#endif
+    // Any mapping gives the same items in the same places (profiles/r06_notes.md section 3b).
     const int n_tiles_x = (int)gridDim.x;
-    const int tile_x = (LS2FM_FILL_XCD_TILES && (n_tiles_x & 7) == 0) ? ((int)blockIdx.x & 7) * (n_tiles_x >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+    const int tile_x = (n_tiles_x & 7) == 0 ? ((int)blockIdx.x & 7) * (n_tiles_x >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
     if (tile_x == 0 && y_lv == 0) {              // armed for the accumulate launch behind this one: unit counter, slab tickets
         if (tid == 0) *acc_claim(bm) = 0;
         for (int q = tid; q < LS2FM_MAX_LEVELS * kBins; q += kFillThreads) bm.part_ticket[q] = 0;
     }
     static_assert(kBins <= kFillThreads, "one thread per slab for the run offsets");
-    // Round 6: the workgroup's item count per slab is NOT counted again here (rounds 1-5: a pass over the pairs -- eight hashes and
-    // 4-8 LDS atomics per thread -- and two barriers): the gather pass counted exactly these items (same classification,
-    // bin_items.h) and the scans left, per (tile, slab), the number of items of the EARLIER tiles: the difference of two
-    // neighbouring rows is this tile's count (the last tile: against the slab's total).  Timing probes of this round (no item
-    // stores at all: 70 of 90 us) showed the kernel bound by its own instruction count, not by its stores.
-    // LS2FM_FILL_COUNT_{DUAL,SINGLE}: 1 (default) = counted here, in the ONE hash pass, with LDS atomics; 0 = taken from the scan
-    // results as described above (no atomics, one barrier fewer -- but the offsets' loads then have a consumer at the head of the
-    // workgroup's chain instead of at its staging).  Measured at C2 (profiles/r06_notes.md section 3, profiles/r06_raw/c16_*), rounds 1-5's separate counting
-    // pass | from the scan rows | counted in the hash pass:  dual field 87.0 | 84.3 | 81.2 us;  single field 64.0 | 66.8 | 63.7 us.
-#ifndef LS2FM_FILL_COUNT_DUAL
-#define LS2FM_FILL_COUNT_DUAL 1
-#endif
-#ifndef LS2FM_FILL_COUNT_SINGLE
-#define LS2FM_FILL_COUNT_SINGLE 1
-#endif
-    constexpr bool kCountHere = DUAL ? (LS2FM_FILL_COUNT_DUAL != 0) : (LS2FM_FILL_COUNT_SINGLE != 0);
-    int pre_base = 0, n_mine = 0;
+    // The workgroup's item count per slab is counted in the ONE hash pass below with LDS atomics (a separate counting pass, or the
+    // difference of two neighbouring scan rows, measured slower: profiles/r06_notes.md section 3c).
+    int pre_base = 0;
     if (tid < kBins) {
-        const int* row = bm.tile + ((int64_t)l * bm.n_tiles + tile_x) * kBins + tid;
-        const int before = row[0];
+        const int before = bm.tile[((int64_t)l * bm.n_tiles + tile_x) * kBins + tid];
         pre_base = bm.start[l * kBins + tid] + before;
-        if (!kCountHere) n_mine = (tile_x + 1 < bm.n_tiles ? row[kBins] : bm.count[l * kBins + tid]) - before;
     }
-    if (kCountHere) {
-        for (int b = tid; b < kBins; b += kFillThreads) hist[b] = 0;
-        __syncthreads();
-    }
+    for (int b = tid; b < kBins; b += kFillThreads) hist[b] = 0;
+    __syncthreads();
     const LevelC L = make_level_c(lv, l, sshift);
     const int64_t i = (int64_t)tile_x * kFillThreads + tid;
     const bool live = i < n_points;
     uint32_t g[3] = {0u, 0u, 0u};
     float w[3] = {0.f, 0.f, 0.f}, d0 = 0.f, d1 = 0.f, r0 = 0.f, r1 = 0.f, e0 = 0.f, e1 = 0.f, qd[3] = {0.f, 0.f, 0.f};
     if (live) {
-#if (LS2FM_FILL_PROBE & 2)
-        const float fi = (float)(i % 977) * 1.0e-3f;      // timing probe: no record loads
-        const float4 a = make_float4(fi, 0.5f * fi + 0.1f, 0.3f, 0.1f), c = make_float4(0.2f, 0.3f, 0.f, 0.f), b = make_float4(fi, fi, 0.1f, 0.2f);
-#else
         const float4 a = reinterpret_cast<const float4*>(rpt)[2 * i];
         const float4 c = reinterpret_cast<const float4*>(rpt)[2 * i + 1];
-#if LS2FM_FILL_REC_NT
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        const f32x4 bv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(rec1) + ((int64_t)l * p_pad + i));
-        const float4 b = make_float4(bv[0], bv[1], bv[2], bv[3]);
-#else
         const float4 b = reinterpret_cast<const float4*>(rec1)[(int64_t)l * p_pad + i];
-#endif
-#endif
         const float x[3] = {a.x, a.y, a.z};                 // the grid-normalised position the forward classified (same bits)
 #pragma unroll
         for (int q = 0; q < 3; ++q) pos_fract(x[q], L.scale, g[q], w[q]);
         d0 = b.x; d1 = b.y; r0 = b.z; r1 = b.w;
         qd[0] = L.scale * a.w; qd[1] = L.scale * c.x; qd[2] = L.scale * c.y;
         if (DUAL) {
-#if LS2FM_FILL_REC_NT
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            const f32x2 e = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(rec2) + ((int64_t)l * p_pad + i));
-            e0 = e[0]; e1 = e[1];
-#else
             const float2 e = reinterpret_cast<const float2*>(rec2)[(int64_t)l * p_pad + i];
             e0 = e.x; e1 = e.y;
-#endif
         }
     }
     // runs of consecutive points in one cell (bin_items.h): the same flags the counting pass derived
@@ -214,7 +152,7 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
         const uint32_t field = ((uint32_t)slab | ((first && i1 == 0xFFFFu) ? 0x80u : 0u)) << (8 * c);
         sb0 |= first ? field : 0u;
         sb1 |= first ? 0u : field;
-        if (kCountHere) atomicAdd(&hist[slab], 1);
+        atomicAdd(&hist[slab], 1);
     });
     // the items of pair c from the kept fields: f(slab, second half item?, ij word of the item)
     auto pair_items = [&](unsigned c, auto&& f) {
@@ -258,12 +196,10 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
 #pragma unroll
         for (unsigned c = 0; c < 4; ++c) pair_factors(c, fa[c], fb[c], fcc[c]);
     }
-    if (LS2FM_FILL_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-    if (LS2FM_FILL_PRIO == 2) __builtin_amdgcn_s_setprio(2);
-    // ---- the run lengths (counted above, or the first consumer of the loads issued at the top)
-    if (kCountHere) __syncthreads();
+    // ---- the run lengths (counted above)
+    __syncthreads();
     if (tid < kBins) {                   // (slab tid: this thread is its only reader and writer here)
-        run_len[tid] = kCountHere ? hist[tid] : n_mine;
+        run_len[tid] = hist[tid];
         base[tid] = pre_base;
         hist[tid] = 0;                   // running rank
     }
@@ -311,19 +247,13 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
         }
         __syncthreads();
         const int staged = s_total < kWin ? s_total : kWin;
-#if LS2FM_FILL_FLAT
-        {
-            static_assert(sizeof(ItemT) == 20, "five words per item");
-            const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(s_items);
-            uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(g_items);
-            for (int c = tid; c < 5 * staged; c += kFillThreads) {
-                const int q = (int)(((uint32_t)c * 52429u) >> 18);            // c / 5 for c < 2^16 (5 * kFillCap = 5440)
-                dst[5u * s_gidx[q] + (uint32_t)(c - 5 * q)] = src[c];
-            }
+        static_assert(sizeof(ItemT) == 20, "five words per item");
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(s_items);
+        uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(g_items);
+        for (int c = tid; c < 5 * staged; c += kFillThreads) {
+            const int q = (int)(((uint32_t)c * 52429u) >> 18);            // c / 5 for c < 2^16 (5 * kFillCap = 5440)
+            dst[5u * s_gidx[q] + (uint32_t)(c - 5 * q)] = src[c];
         }
-#else
-        for (int q = tid; q < staged; q += kFillThreads) g_items[s_gidx[q]] = s_items[q];
-#endif
     } else {
     // every item's slot in the workgroup's sorted order
     // (named scalars, 16 bits per slot: as arrays indexed by the lambda's pair number they went to scratch memory)
@@ -346,61 +276,15 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
     auto write_out = [&](int win) {
         // runs of one slab are contiguous in the sorted order and in memory: consecutive threads write consecutive items
         const int staged = total - win < kWin ? total - win : kWin;
-        if (LS2FM_FILL_PRIO == 3) __builtin_amdgcn_s_setprio(2);           // (3: raised for the write-out only)
-#if (LS2FM_FILL_PROBE & 1)
-        if (staged < 0)                    // timing probe: no item stores
-#endif
-#if LS2FM_FILL_FLAT
-#ifdef LS2FM_ITEM_PROBE24
-        for (int c = tid; c < 3 * staged; c += kFillThreads) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(2)));          // (8-byte chunks of a 24-byte item)
-            const int q = (int)(((uint32_t)c * 43691u) >> 17), hf = c - 3 * q;
-#else
         for (int c = tid; c < 2 * staged; c += kFillThreads) {
             typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             const int q = c >> 1, hf = c & 1;
-#endif
-#if (LS2FM_FILL_PROBE & 4)
-            const uint32_t gi = s_gidx[q] & 0x7FFFu;                                   // timing probe: every store inside a 1 MB window (cache-resident)
-#elif (LS2FM_FILL_PROBE & 8)
-            const uint32_t gi = (uint32_t)(((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * (kFillCap + 64) + win + q);     // timing probe: the workgroup's items CONTIGUOUS (streaming stores, no scatter)
-#else
             const uint32_t gi = s_gidx[q];
-#endif
             const u32x4 v = reinterpret_cast<const u32x4*>(s_items)[c];
             u32x4* dst = reinterpret_cast<u32x4*>(&g_items[gi]) + hf;
-#if LS2FM_FILL_NT
-            __builtin_nontemporal_store(v, dst);
-#else
             *dst = v;
-#endif
             if (DUAL && expl && hf == 0) bm.extra[gi] = s_extra[q];
         }
-#else
-        for (int q = tid; q < staged; q += kFillThreads) {
-            const uint32_t gi = s_gidx[q];
-#if LS2FM_FILL_NT
-            if constexpr (DUAL) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4* src = reinterpret_cast<const u32x4*>(&s_items[q]);
-                u32x4* dst = reinterpret_cast<u32x4*>(&g_items[gi]);
-#if LS2FM_FILL_NT == 2
-                const u32x4 h0 = src[0], h1 = src[1];
-                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc1" :: "v"(dst), "v"(h0), "v"(h1) : "memory");
-#elif LS2FM_FILL_NT == 3
-                const u32x4 h0 = src[0], h1 = src[1];
-                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc0 sc1" :: "v"(dst), "v"(h0), "v"(h1) : "memory");
-#else
-                __builtin_nontemporal_store(src[0], dst);
-                __builtin_nontemporal_store(src[1], dst + 1);
-#endif
-            } else
-#endif
-            g_items[gi] = s_items[q];
-            if (DUAL && expl) bm.extra[gi] = s_extra[q];
-        }
-#endif
-        if (LS2FM_FILL_PRIO == 3) __builtin_amdgcn_s_setprio(0);
     };
     if (!expl) {
         // ---- factored dual items (factors formed above, indices and slabs kept from the one hash pass)
@@ -417,9 +301,7 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
                         it.wx = w[0];
                         it.a0 = fa[c][0]; it.a1 = fa[c][1];
                         it.b0 = fb[c][0]; it.b1 = fb[c][1];
-#ifndef LS2FM_ITEM_PROBE24
                         it.c0 = fcc[c][0]; it.c1 = fcc[c][1];
-#endif
                         s_items[rel] = it;
                         s_gidx[rel] = (uint32_t)(base[slab] + (rel + win - lds_off[slab]));
                     });
@@ -486,29 +368,18 @@ struct SlabPlan {
     int n_explicit;                      // dual field: leading levels with explicit, run-merged items (bin_items.h)
 };
 
-// LS2FM_ACC_CVT: how a contribution becomes a 64-bit fixed-point integer.  0: __float2ll_rn(v * to_fixed) -- there is no f32 -> i64
-// instruction: the compiler's expansion is ~12 VALU instructions, eight times per item, half of this kernel's SIMD cycles.  1: through
-// the double's mantissa -- fma((double) v, to_fixed, 1.5 * 2^52) rounds v * to_fixed (exact in double) to the nearest integer, ties to
-// even, exactly as __float2ll_rn does, and leaves it in the low 52 bits of the result (two's complement, |.| < 2^51); what is above
-// them is the constant 0x4338 in the top 16 bits, whose low dword is zero: ONE 32-bit subtraction on the high dword.  Three
-// instructions (v_cvt_f64_f32, v_fma_f64, v_add_u32) and the same integers bit for bit, PROVIDED |v * to_fixed| < 2^51: a single
-// item is at most 64 contributions (a run merged inside a wave, bin_items.h: wave_runs), each < 2^(62 - headroom) -- make_plan
-// keeps headroom_bits >= 18 (it is 4 + log2(points): only batches under 16 384 points see the floor, as a 2^-44-of-the-bound
-// quantum instead of a finer one).
-// Round 6, same session, alternating libraries (profiles/r06_raw/c55_ab_cvt.txt): 1 380 -> 920 VALU instructions in the kernel; slab_accumulate
-// 69.1 / 69.3 / 68.8 -> 66.8 / 66.6 / 66.6 us (single field 46.0 -> 45.2, C3 399 -> 397, C5 243 -> 241); gradient digests identical.
-#ifndef LS2FM_ACC_CVT
-#define LS2FM_ACC_CVT 1
-#endif
-constexpr int kMinHeadroomBits = LS2FM_ACC_CVT ? 18 : 4;
+// A contribution becomes a 64-bit fixed-point integer through the double's mantissa: fma((double) v, to_fixed, 1.5 * 2^52) rounds
+// v * to_fixed (exact in double) to the nearest integer, ties to even, exactly as __float2ll_rn does, and leaves it in the low 52
+// bits of the result (two's complement, |.| < 2^51); what is above them is the constant 0x4338 in the top 16 bits, whose low dword
+// is zero: ONE 32-bit subtraction on the high dword.  Three instructions instead of __float2ll_rn's ~12 (profiles/r06_notes.md
+// section 10), PROVIDED |v * to_fixed| < 2^51: a single item is at most 64 contributions (a run merged inside a wave, bin_items.h:
+// wave_runs), each < 2^(62 - headroom) -- make_plan keeps headroom_bits >= 18 (it is 4 + log2(points): only batches under
+// 16 384 points see the floor, as a 2^-44-of-the-bound quantum instead of a finer one).
+constexpr int kMinHeadroomBits = 18;
 __device__ __forceinline__ void add_fixed(u64* slot, float v, float to_fixed) {
     // v * to_fixed is exact (power-of-two scale); |.| < 2^62 / worst-case hits by construction of the quantum
-#if LS2FM_ACC_CVT
     const double d = fma((double)v, (double)to_fixed, 6755399441055744.0);
     atomicAdd(slot, (u64)__double_as_longlong(d) - 0x4338000000000000ull);
-#else
-    atomicAdd(slot, (u64)__float2ll_rn(v * to_fixed));        // two's complement: integer sums are exact
-#endif
 }
 
 __device__ __forceinline__ void quantum_of(float bound, int headroom_bits, float& to_fixed, double& to_float) {
@@ -610,46 +481,12 @@ struct AccUnit {
     const void* list;
 };
 
-#ifndef LS2FM_ACC_NT
-#define LS2FM_ACC_NT 0
-#endif
-// an item of a slab's list (read exactly once, by one workgroup): optionally as non-temporal loads
-__device__ __forceinline__ Item load_item(const Item* p) {
-#if LS2FM_ACC_NT
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    union { u32x4 q[2]; Item it; } u;
-    u.q[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    u.q[1] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p) + 1);
-    return u.it;
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ ItemS load_item(const ItemS* p) {
-#if LS2FM_ACC_NT
-    union { uint32_t w[5]; ItemS it; } u;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) u.w[q] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p) + q);
-    return u.it;
-#else
-    return *p;
-#endif
-}
-
-// one entry of a gradient table, written once by its sole owner and not read again in this launch: plain, non-temporal (1) or
-// write-through (2) stores -- the table is the optimizer's input much later, keeping its lines in this XCD's L2 only evicts others
+// one entry of a gradient table, written once by its sole owner and not read again in this launch: a non-temporal store -- the
+// table is the optimizer's input much later, keeping its lines in this XCD's L2 only evicts others
 __device__ __forceinline__ void store_entry(float* d, const float2 v) {
-#if LS2FM_ACC_NT_STORE == 2
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const f32x2 r = {v.x, v.y};
-    asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(d), "v"(r) : "memory");
-#elif LS2FM_ACC_NT_STORE == 1
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 r = {v.x, v.y};
     __builtin_nontemporal_store(r, reinterpret_cast<f32x2*>(d));
-#else
-    *reinterpret_cast<float2*>(d) = v;
-#endif
 }
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -718,9 +555,6 @@ __device__ __forceinline__ AccUnit acc_unit_finish(const AccUnitRaw& r, const Bi
     return u;
 }
 
-#ifndef LS2FM_ACC_PROBE
-#define LS2FM_ACC_PROBE 0
-#endif
 #ifdef LS2FM_STAMPS
 #define PACC_STAMP(uid, k) do { if (threadIdx.x == 0 && (uid) < 4096) g_acc_stamps[8 * (uid) + (k)] = wall_clock64(); } while (0)
 #else
@@ -767,7 +601,7 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
 #pragma unroll
         for (int u = 0; u < kAccBatch; ++u) {
             const int j = cur.j_lo + tid + u * kAccThreads;
-            buf[u] = load_item(list + (j < cur.j_hi ? j : j_last));
+            buf[u] = list[j < cur.j_hi ? j : j_last];
             if (DUAL) bufx[u] = cur.expl ? bm.extra[cur.start + (j < cur.j_hi ? j : j_last)] : 0.f;
         }
     }
@@ -789,11 +623,7 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
         quantum_of(cur.bound1, plan.headroom_bits, to_fixed1, to_float1);
         quantum_of(cur.bound2, plan.headroom_bits, to_fixed2, to_float2);
         auto add_item = [&](const ItemT& it, float x9) {
-#if (LS2FM_FILL_PROBE & 12)
-            const uint32_t i0 = it.ij & 0xFFFu, i1 = (it.ij >> 16) & 0xFFFu;       // (the fill probes leave stale / foreign items in the lists: stay inside the slab)
-#else
             const uint32_t i0 = it.ij & 0xFFFFu, i1 = it.ij >> 16;
-#endif
             if constexpr (DUAL) {
                 if (cur.expl) {                // explicit item (bin_items.h: explicit_item): the corners' values as they are
                     if (i0 != 0xFFFFu) {
@@ -801,13 +631,13 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
                         add_fixed(slot, it.wx, to_fixed1);
                         add_fixed(slot + E, it.a0, to_fixed1);
                         add_fixed(slot + 2 * E, it.b1, to_fixed2);
-                        add_fixed(slot + 3 * E, LS2FM_ITEM_C0(it), to_fixed2);
+                        add_fixed(slot + 3 * E, it.c0, to_fixed2);
                     }
                     if (i1 != 0xFFFFu) {
                         u64* slot = acc + i1;
                         add_fixed(slot, it.a1, to_fixed1);
                         add_fixed(slot + E, it.b0, to_fixed1);
-                        add_fixed(slot + 2 * E, LS2FM_ITEM_C1(it), to_fixed2);
+                        add_fixed(slot + 2 * E, it.c1, to_fixed2);
                         add_fixed(slot + 3 * E, x9, to_fixed2);
                     }
                     return;
@@ -817,15 +647,15 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
                     u64* slot = acc + i0;
                     add_fixed(slot, fmaf(px0, it.a0, -it.b0), to_fixed1);
                     add_fixed(slot + E, fmaf(px0, it.a1, -it.b1), to_fixed1);
-                    add_fixed(slot + 2 * E, px0 * LS2FM_ITEM_C0(it), to_fixed2);
-                    add_fixed(slot + 3 * E, px0 * LS2FM_ITEM_C1(it), to_fixed2);
+                    add_fixed(slot + 2 * E, px0 * it.c0, to_fixed2);
+                    add_fixed(slot + 3 * E, px0 * it.c1, to_fixed2);
                 }
                 if (i1 != 0xFFFFu) {
                     u64* slot = acc + i1;
                     add_fixed(slot, fmaf(it.wx, it.a0, it.b0), to_fixed1);
                     add_fixed(slot + E, fmaf(it.wx, it.a1, it.b1), to_fixed1);
-                    add_fixed(slot + 2 * E, it.wx * LS2FM_ITEM_C0(it), to_fixed2);
-                    add_fixed(slot + 3 * E, it.wx * LS2FM_ITEM_C1(it), to_fixed2);
+                    add_fixed(slot + 2 * E, it.wx * it.c0, to_fixed2);
+                    add_fixed(slot + 3 * E, it.wx * it.c1, to_fixed2);
                 }
             } else {
                 if (i0 != 0xFFFFu) {
@@ -851,18 +681,13 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
             const int last_n = hi_n > lo_n ? hi_n - 1 : lo_n;
             const bool expl_n = DUAL && (more ? cur.expl : nxt.expl);    // (uniform)
             const float* __restrict__ extra_n = bm.extra + (more ? cur.start : nxt.start);
-            // (issue-priority experiment, round 6: LS2FM_ACC_PRIO = 1 raises a wave while it issues the next batch's loads.  Default 0.)
-#ifndef LS2FM_ACC_PRIO
-#define LS2FM_ACC_PRIO 0
-#endif
-            if (LS2FM_ACC_PRIO == 1) __builtin_amdgcn_s_setprio(2);
+            // (no issue-priority hooks: raised for the loads or for the adds measured nothing; profiles/r06_notes.md section 9)
 #pragma unroll
             for (int u = 0; u < kAccBatch; ++u) {                        // unconditional loads, masked where they are used
                 const int j = lo_n + tid + u * kAccThreads;
-                buf[u] = load_item(list_n + (j < hi_n ? j : last_n));
+                buf[u] = list_n[j < hi_n ? j : last_n];
                 if (DUAL) bufx[u] = expl_n ? extra_n[j < hi_n ? j : last_n] : 0.f;
             }
-            if (LS2FM_ACC_PRIO == 1) __builtin_amdgcn_s_setprio(0);
             // The claim: lane 0 of wave 0, issued WITHOUT waiting for the returned value (as a builtin under `if (tid == 0)` the
             // compiler waits for it at the end of the branch: one memory round trip per unit in front of wave 0's adds), BEHIND
             // the batch loads just issued: every vmcnt the compiler computes for loads older than the atomic is merely one too
@@ -875,14 +700,9 @@ slab_accumulate_persistent_kernel(LevelSet lv, SlabPlan plan, BinMeta bm, int ss
                              "s_mov_b64 exec, %1"
                              : "=&v"(claimed), "=&s"(saved) : "v"(0), "v"(1), "s"(claim) : "memory");
             }
-#if (LS2FM_ACC_PROBE & 1)
-            if (now[0].ij == 0x12345678u)        // timing probe: (almost) no LDS atomics
-#endif
-            if (LS2FM_ACC_PRIO == 2) __builtin_amdgcn_s_setprio(2);            // (2: raised for the adds)
 #pragma unroll
             for (int u = 0; u < kAccBatch; ++u)
                 if (b0 + tid + u * kAccThreads < cur.j_hi) add_item(now[u], DUAL ? nowx[u] : 0.f);
-            if (LS2FM_ACC_PRIO == 2) __builtin_amdgcn_s_setprio(0);
             b0 += BT;
         } while (b0 < cur.j_hi);
         PACC_STAMP(cur.uid, 1);
@@ -988,9 +808,7 @@ bool levels_fit(const ls2fm_grid_desc* grid, int sshift) {
 // floats of workspace the scatter needs: meta + worst case 8 items (4 pairs, each split) of 32 bytes per (point, level) + the
 // explicit dual items' ninth word
 int64_t ls2fm_bins_workspace_floats(int n_levels, int64_t n_points) {
-#ifndef LS2FM_ITEM_PROBE24
     static_assert(sizeof(Item) == 32 && sizeof(ItemS) == 20, "item layouts");
-#endif
     return meta_ints(n_points) + part_acc_floats(n_points) + extra_floats(n_points) + 8 * 8 * (int64_t)n_levels * n_points + 64;
 }
 
@@ -1025,8 +843,6 @@ int ls2fm_launch_scatter_fill(const ls2fm_grid_desc* grid, const FieldC& fc, con
     const LevelSet lv = make_level_set(grid);
     if (level_hi < 0) level_hi = grid->n_levels;
     if (level_hi <= level_lo) return LS2FM_OK;
-    // (most recently written lists are read first: slab_accumulate 101 -> 98 us at C2; LS2FM_FILL_REVERSE=0 for the A/B)
-    static const int reverse = [] { const char* e = getenv("LS2FM_FILL_REVERSE"); return e ? atoi(e) : 1; }();
     SideJobs sj{};
     if (side_jobs) {
         sj = *static_cast<const SideJobs*>(side_jobs);
@@ -1035,8 +851,8 @@ int ls2fm_launch_scatter_fill(const ls2fm_grid_desc* grid, const FieldC& fc, con
     }
     if (kFillThreads != kWmThreads && sj.rows > 0) return LS2FM_ERR_UNSUPPORTED;      // the side jobs are written for 256-thread workgroups
     const dim3 g((unsigned)bm.n_tiles, (unsigned)(level_hi - level_lo + sj.rows));
-    if (dual) scatter_fill_kernel<true><<<g, kFillThreads, 0, stream>>>(lv, fc, center, ray, n_points, p_pad, sshift, rpt, rec1, rec2, ray_bound, n_rays, r_pad, bm, level_lo, reverse, n_explicit, sj);
-    else      scatter_fill_kernel<false><<<g, kFillThreads, 0, stream>>>(lv, fc, center, ray, n_points, p_pad, sshift, rpt, rec1, nullptr, ray_bound, n_rays, r_pad, bm, level_lo, reverse, 0, sj);
+    if (dual) scatter_fill_kernel<true><<<g, kFillThreads, 0, stream>>>(lv, fc, center, ray, n_points, p_pad, sshift, rpt, rec1, rec2, ray_bound, n_rays, r_pad, bm, level_lo, n_explicit, sj);
+    else      scatter_fill_kernel<false><<<g, kFillThreads, 0, stream>>>(lv, fc, center, ray, n_points, p_pad, sshift, rpt, rec1, nullptr, ray_bound, n_rays, r_pad, bm, level_lo, 0, sj);
     return ls2fm_launch_status();
 }
 
@@ -1057,7 +873,7 @@ HostPlan make_plan(const ls2fm_grid_desc* grid, int64_t n_points, int sshift, in
         for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) h.plan.parts[l] = 1;
         h.plan.headroom_bits = 4;                // 8 corners per point (+1)
         while ((1ll << (h.plan.headroom_bits - 4)) < n_points) ++h.plan.headroom_bits;
-        if (h.plan.headroom_bits < kMinHeadroomBits) h.plan.headroom_bits = kMinHeadroomBits;        // (add_fixed, LS2FM_ACC_CVT)
+        if (h.plan.headroom_bits < kMinHeadroomBits) h.plan.headroom_bits = kMinHeadroomBits;        // (add_fixed)
         h.plan.n_explicit = n_explicit < LS2FM_MAX_LEVELS ? n_explicit : 0;        // (the kernels' flag is a dual-field one)
         h.zero_lo = h.zero_hi = -1;
         const int64_t target = 16384;            // items a workgroup should process (a hashed-level slab sees ~4P/slabs)

@@ -60,26 +60,6 @@ wgrad_tail_kernel(WgradParts wp, float* __restrict__ wg, FinalizeArgs fa, int n_
     }
 }
 
-// The upstream of the traced depth (loss head inside the render: the depth-consistency term) per ray -- exactly the lines of
-// shade_bwd's first part that form `d_depth_ref`, as a kernel of its own, so that the tracing's own backward (ls2fm_depth_backward: a
-// chain of five small launches over the track points) can start BESIDE shade_bwd instead of behind it.
-__global__ void __launch_bounds__(256)
-depth_upstream_kernel(LossUp lo, const float* __restrict__ rout_depth, int64_t n_rays) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rays) return;
-    float gt[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (lo.d_terms) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) gt[k] = lo.d_terms[k];
-    }
-    const float g_all = gt[4] + (lo.d_total ? lo.d_total[0] : 0.f);
-    const float gl_dc = lo.sums[5] > 0.0 ? fmaf(lo.weights[2], g_all, gt[2]) / (float)lo.sums[5] : 0.f;
-    float gd = 0.f;
-    if (lo.depth_ref != nullptr && (lo.mask_dc == nullptr || lo.mask_dc[r] != 0))
-        gd = gl_dc * ls2fm_smooth_l1_grad(lo.depth_ref[r] - rout_depth[r]);
-    lo.d_depth_ref[r] = gd;
-}
-
 }  // namespace
 
 // weight-norm backward of the SDF MLP alone (point queries, points.hip): tasks 0 and 1 of finalize_kernel
@@ -137,7 +117,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) lsc.s[l] = l < L1 ? sdf_grid->scale[l] : 0.f;
 
     SideCtx sc;
-    bool forked = false, joined = false;
     LS2FM_CHECK_ARG(((reinterpret_cast<uintptr_t>(grads->sdf_table) | (dual ? reinterpret_cast<uintptr_t>(grads->rad_table) : 0)) & 15u) == 0);
 
     Upstream up{d_rgb, d_sdfs_volume, d_normals, d_depth_mlp, d_normal_mlp, LossUp{}};
@@ -152,20 +131,25 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     // scans) are contracted by this call's SDF weight-gradient kernel as extra tiles (no second wgrad_mlp / reduction / weight-norm
     // backward -- whose 63 KB workgroups waited for a CU beside this call's), and its table gradient is ADDED into this call's table
     // behind the main accumulate (no second table, no final sum kernel).
-    // Round 5, measured and NOT taken (LS2FM_DEPTH_EARLY=1 enables it; results identical): the branch forked IN FRONT of shade_bwd --
-    // the depth's upstream from depth_upstream_kernel (the same arithmetic as shade_bwd's first part, which then leaves d_depth_ref
-    // alone) -- so that its five small launches run beside shade_bwd instead of beside the scatter, where they are stretched 3-5x and
-    // end the stage's backward 90 us behind the main accumulate.  shade_bwd is ONE round of workgroups that fills every slot of the
-    // chip: whatever runs beside it starts a second round -- stage step 0.808 - 0.820 -> 0.856 - 0.864 ms, loops +0.06 - 0.1 ms.
+    // (Beside the scatter its five small launches are stretched 3-5x and end the stage's backward 90 us behind the main accumulate;
+    // forking the branch IN FRONT of shade_bwd instead measured slower: shade_bwd is ONE round of workgroups that fills every slot of
+    // the chip, and whatever runs beside it starts a second round -- profiles/r05_scatter_notes.md section 10.)
     const ls2fm_depth_backward* db = (opts && loss && loss->d_depth_ref) ? opts->depth_bwd : nullptr;
-    static const int depth_early_env = [] { const char* e = getenv("LS2FM_DEPTH_EARLY"); return e ? atoi(e) : 0; }();
-    const bool depth_early = db != nullptr && depth_early_env != 0;
+    ls2fm_prof_begin(LS2FM_PROF_SHADE_BWD, s);
+    // (leading workgroups of this launch zero the weight-gradient accumulators and the atomically flushed table ranges)
+    // the MLPs' weight gradients are contracted inside shade_bwd (LS2FM_FUSED_WGRAD=0: round 4's separate wgrad_mlp launches,
+    // for A/B measurements)
+    // (one-sample rays share the workspace layout of free points, which has no per-ray partials: wgrad_mlp.hip serves them)
+    ls2fm_launch_shade_bwd(fc, lsc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, up, want_pose, sdf_grid, grads->sdf_table,
+                           dual ? grads->rad_table : nullptr, s, fused_wgrad);
+    ls2fm_prof_end(LS2FM_PROF_SHADE_BWD, s);
+    if (opts && opts->depth_grad_ready && hipEventRecord((hipEvent_t)opts->depth_grad_ready, s) != hipSuccess) return LS2FM_ERR_LAUNCH;
     SideCtx sc1, sc2;
     bool forked2 = false;
     Ls2fmWgradExtra extra{};
     int64_t n_track = 0;
     hipStream_t ds = s;
-    auto launch_depth_branch = [&]() -> int {
+    if (db) {
         LS2FM_CHECK_ARG(db->points && db->trips && db->gate && db->d_sdf && db->workspace && db->k_max >= 1);
         if (opts->n_level_groups > 1) return LS2FM_ERR_UNSUPPORTED;      // a group's slices would not be final at its event
         n_track = n_rays * (int64_t)db->k_max;
@@ -185,44 +169,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
             if (forked2) { (void)hipEventRecord(sc2.join, sc2.side); (void)hipStreamWaitEvent(s, sc2.join, 0); }
             return st;
         }
-        return LS2FM_OK;
-    };
-    if (depth_early) {
-        depth_upstream_kernel<<<(unsigned)((n_rays + 255) / 256), 256, 0, s>>>(up.loss, ws + w.rout + 3 * w.r_pad, n_rays);
-        if (opts->depth_grad_ready && hipEventRecord((hipEvent_t)opts->depth_grad_ready, s) != hipSuccess) return LS2FM_ERR_LAUNCH;
-        const int st = launch_depth_branch();
-        if (st != LS2FM_OK) return st;
-        up.loss.d_depth_ref = nullptr;                   // (shade_bwd leaves it alone: the branch is reading it)
-    }
-#ifdef LS2FM_DEBUG_PTRS
-    {   // (diagnosis, round 6: which of shade_bwd's pointers is not device memory?)
-        static int once = 0;
-        if (!once++) {
-            auto show = [](const char* name, const void* p) {
-                hipPointerAttribute_t a{};
-                if (!p) { fprintf(stderr, "[ptr] %-12s null\n", name); return; }
-                const hipError_t e = hipPointerGetAttributes(&a, p);
-                if (e != hipSuccess) (void)hipGetLastError();
-                fprintf(stderr, "[ptr] %-12s %p  err %d  type %d  device %d  managed %d\n", name, p, (int)e, (int)a.type, a.device, (int)a.isManaged);
-            };
-            show("center", center); show("ray", ray); show("ws", ws); show("pk", pk);
-            show("rgb_gt", up.loss.rgb_gt); show("depth_ref", up.loss.depth_ref); show("weights", up.loss.weights); show("sums", up.loss.sums);
-            show("d_terms", up.loss.d_terms); show("d_total", up.loss.d_total); show("d_depth_ref", up.loss.d_depth_ref);
-            show("sdf_table", grads->sdf_table); show("beta", grads->beta);
-        }
-    }
-#endif
-    ls2fm_prof_begin(LS2FM_PROF_SHADE_BWD, s);
-    // (leading workgroups of this launch zero the weight-gradient accumulators and the atomically flushed table ranges)
-    // the MLPs' weight gradients are contracted inside shade_bwd (LS2FM_FUSED_WGRAD=0: round 4's separate wgrad_mlp launches,
-    // for A/B measurements)
-    // (one-sample rays share the workspace layout of free points, which has no per-ray partials: wgrad_mlp.hip serves them)
-    ls2fm_launch_shade_bwd(fc, lsc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, up, want_pose, sdf_grid, grads->sdf_table,
-                           dual ? grads->rad_table : nullptr, s, fused_wgrad);
-    ls2fm_prof_end(LS2FM_PROF_SHADE_BWD, s);
-    if (!depth_early) {
-        if (opts && opts->depth_grad_ready && hipEventRecord((hipEvent_t)opts->depth_grad_ready, s) != hipSuccess) return LS2FM_ERR_LAUNCH;
-        if (db) { const int st = launch_depth_branch(); if (st != LS2FM_OK) return st; }
     }
     auto fail = [&](bool f1, const SideCtx& c1, int st) {       // error after the forks: every branch is joined back into `s`
         if (forked2) { (void)hipEventRecord(sc2.join, sc2.side); (void)hipStreamWaitEvent(s, sc2.join, 0); }
@@ -235,7 +181,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     }
 
     // the one fork of the backward: weight-gradient GEMMs -> reduce -> finalize run on the side stream, beside the table scatters
-    static const int probe_no_side = [] { const char* e = getenv("LS2FM_PROBE_NO_SIDE"); return e ? atoi(e) : 0; }();     // timing probe: wrong MLP gradients
     // Round 5: NO side stream in the render's backward when the MLPs' weight gradients were contracted by shade_bwd and no traced
     // depth rides along: what is left of the chain (decoder columns, level-1 sums, reduction rows, finalize tasks) runs as leading
     // workgroups of the scatter_fill launch (side_jobs.h) -- one chain on one queue.  LS2FM_SIDE_IN_FILL=0: the side stream of
@@ -248,7 +193,7 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     // rows and finalize tasks, ~180: side_jobs.h -- so that the producers they poll can never be kept off the chip by them)
     const int n_waiters = kRegsSdf + (dual ? kRegsGeo : 0) + kRegsDec + kFinalizeTasks;
     static const int64_t side_max_rays = [] { const char* e = getenv("LS2FM_SIDE_IN_FILL_MAX_RAYS"); return e ? atoll(e) : 4096ll; }();
-    const bool side_in_fill = side_in_fill_env && fused_wgrad && !db && !probe_no_side && w.p >= 32768 && n_rays <= side_max_rays &&
+    const bool side_in_fill = side_in_fill_env && fused_wgrad && !db && w.p >= 32768 && n_rays <= side_max_rays &&
                               ls2fm_device_cus() >= n_waiters;      // (>= 4 workgroups of this launch fit a CU: 4x the slots)
     SideJobs sj{};
     if (side_in_fill) {
@@ -265,34 +210,28 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
         sj.fa = FinalizeArgs{*params, *grads, 3 + 2 * L1, 3 + 2 * L2, rad_in, dual, pk, ws + w.wg, ws + w.dbeta, n_rays, 0};
         static_assert(kSideDecBlocks + kL1Seg * (kRegsSdf + kRegsGeo) + kRegsSdf + kRegsGeo + kRegsDec <= kSideFlagInts, "one flag per side job");
         sj.flags = reinterpret_cast<int*>(ws + w.wg + kWgFlagsAt);                  // (zeroed by shade_bwd's leading workgroups)
-        static const int side_probe = [] { const char* e = getenv("LS2FM_SIDE_PROBE"); return e ? atoi(e) : 0; }();
-        sj.probe = side_probe;
         sj.err = err_word;
     }
-    forked = !probe_no_side && !side_in_fill && ls2fm_side_stream(&sc, s) && hipEventRecord(sc.fork, s) == hipSuccess && hipStreamWaitEvent(sc.side, sc.fork, 0) == hipSuccess;
-    hipStream_t gs = forked ? sc.side : s;
-    // The side chain is enqueued IN FRONT of the scatter.  (Behind it -- LS2FM_SIDE_FIRST=0, tried in round 5 now that the chain is
-    // short: the scatter then keeps shade_bwd's hardware queue in a hipGraph replay -- measured 0.526 against 0.509 ms per step.)
-    static const int side_first = [] { const char* e = getenv("LS2FM_SIDE_FIRST"); return e ? atoi(e) : 1; }();
-    auto launch_side = [&]() -> int {
-    if (probe_no_side || side_in_fill) return LS2FM_OK;
-    Ls2fmWgradParts parts{};
-    if (ls2fm_launch_wgrad_mlp(fc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, gs, false, &parts, db ? &extra : nullptr,
-                               fused_wgrad) != LS2FM_OK)
-        return fail(forked, sc, LS2FM_ERR_LAUNCH);
-    ls2fm_prof_begin(LS2FM_PROF_FINALIZE, gs);
-    {   // sum of the partials + finalize tasks, one launch (the ticket word: slack of the reduced-gradient block, zeroed above)
-        static_assert(WgLayout::total % 64 != 0 && (WgLayout::total + 63) / 64 * 64 - WgLayout::total >= 1, "ticket word in the block's slack");
-        const int n_red = kRegsSdf + (dual ? kRegsGeo : 0) + kRegsDec;
-        const FinalizeArgs fa{*params, *grads, 3 + 2 * L1, 3 + 2 * L2, rad_in, dual, pk, ws + w.wg, ws + w.dbeta, n_rays, 0};
-        wgrad_tail_kernel<<<n_red + kFinalizeTasks, 256, 0, gs>>>(parts, ws + w.wg, fa, n_red,
-                                                                 reinterpret_cast<int*>(ws + w.wg + WgLayout::total), err_word);
+    const bool forked = !side_in_fill && ls2fm_side_stream(&sc, s) && hipEventRecord(sc.fork, s) == hipSuccess && hipStreamWaitEvent(sc.side, sc.fork, 0) == hipSuccess;
+    // The side chain is enqueued IN FRONT of the scatter (behind it, the scatter keeps shade_bwd's hardware queue in a hipGraph
+    // replay: measured slower, profiles/r05_scatter_notes.md section 4).
+    if (!side_in_fill) {
+        hipStream_t gs = forked ? sc.side : s;
+        Ls2fmWgradParts parts{};
+        if (ls2fm_launch_wgrad_mlp(fc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, gs, false, &parts, db ? &extra : nullptr,
+                                   fused_wgrad) != LS2FM_OK)
+            return fail(forked, sc, LS2FM_ERR_LAUNCH);
+        ls2fm_prof_begin(LS2FM_PROF_FINALIZE, gs);
+        {   // sum of the partials + finalize tasks, one launch (the ticket word: slack of the reduced-gradient block, zeroed above)
+            static_assert(WgLayout::total % 64 != 0 && (WgLayout::total + 63) / 64 * 64 - WgLayout::total >= 1, "ticket word in the block's slack");
+            const int n_red = kRegsSdf + (dual ? kRegsGeo : 0) + kRegsDec;
+            const FinalizeArgs fa{*params, *grads, 3 + 2 * L1, 3 + 2 * L2, rad_in, dual, pk, ws + w.wg, ws + w.dbeta, n_rays, 0};
+            wgrad_tail_kernel<<<n_red + kFinalizeTasks, 256, 0, gs>>>(parts, ws + w.wg, fa, n_red,
+                                                                     reinterpret_cast<int*>(ws + w.wg + WgLayout::total), err_word);
+        }
+        ls2fm_prof_end(LS2FM_PROF_FINALIZE, gs);
+        if (forked && hipEventRecord(sc.join, sc.side) != hipSuccess) return fail(forked, sc, LS2FM_ERR_LAUNCH);
     }
-    ls2fm_prof_end(LS2FM_PROF_FINALIZE, gs);
-    if (forked && hipEventRecord(sc.join, sc.side) != hipSuccess) return fail(forked, sc, LS2FM_ERR_LAUNCH);
-    return LS2FM_OK;
-    };
-    if (side_first) { const int st = launch_side(); if (st != LS2FM_OK) return st; }
 
     // hash-table gradients: payloads sorted by slab (scatter_fill), then one streaming pass per LDS-owned slab
     // (slab_accumulate; bin_scatter.hip); tables overwritten in full; dual field: both grids share geometry, hence items.
@@ -314,13 +253,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
                                                (side_in_fill && gi == 0) ? &sj : nullptr);
             ls2fm_prof_end(LS2FM_PROF_SCATTER_RAD, s);
             if (st != LS2FM_OK) return fail(forked, sc, st);
-            // LS2FM_JOIN_EARLY=1: the side chain is joined in FRONT of the (last) accumulate launch instead of at the end of the
-            // call: the call then ends on one queue
-            static const int join_early = [] { const char* e = getenv("LS2FM_JOIN_EARLY"); return e ? atoi(e) : 0; }();
-            if (join_early && side_first && forked && !joined && gi == groups - 1) {
-                if (hipStreamWaitEvent(s, sc.join, 0) != hipSuccess) return fail(forked, sc, LS2FM_ERR_LAUNCH);
-                joined = true;
-            }
             ls2fm_prof_begin(LS2FM_PROF_SCATTER_SDF, s);
             st = ls2fm_launch_slab_accumulate(sdf_grid, ws + w.bins, w.p, grads->sdf_table, dual ? grads->rad_table : nullptr, s, lo, hi,
                                               0, n_explicit, field->n_samples);
@@ -331,7 +263,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
                 return fail(forked, sc, LS2FM_ERR_LAUNCH);
         }
     }
-    if (!side_first) { const int st = launch_side(); if (st != LS2FM_OK) return st; }
     if (db) {
         // the tracing's table gradient, added into the table the scatter above has just written: behind it (an event when the
         // branch has a stream of its own)
@@ -342,6 +273,6 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
         if (forked2 && (hipEventRecord(sc2.join, sc2.side) != hipSuccess || hipStreamWaitEvent(s, sc2.join, 0) != hipSuccess))
             return ls2fm_join_on_error(forked, sc, s, LS2FM_ERR_LAUNCH);
     }
-    if (forked && !joined && hipStreamWaitEvent(s, sc.join, 0) != hipSuccess) return LS2FM_ERR_LAUNCH;       // join
+    if (forked && hipStreamWaitEvent(s, sc.join, 0) != hipSuccess) return LS2FM_ERR_LAUNCH;       // join
     return ls2fm_launch_status();
 }

@@ -8,8 +8,6 @@
 //   shade_fwd    : block per ray, lane per sample: SDF MLP + analytic normal + (second field) + collapsed
 //                  radiance + VolSDF sigma, then the front-to-back composite as a wave/block scan
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 
 #include "bin_items.h"
 
@@ -285,12 +283,6 @@ struct EncodeExtras {
     int n_explicit;           // dual field: leading levels whose scatter items are explicit and run-merged (bin_items.h)
     int n_prep_tasks;         // 3: both MLPs + the radiance chain (render); 1: the SDF MLP only (point queries)
     const float* pts;         // [n,3] free points instead of ray samples (point queries), or null
-    int probe;                // LS2FM_ENC_PROBE (measurements, round 6): 1 = walking order NOT pinned to XCDs (every XCD walks every
-                              // level over its eighth of the chunks: what a gather fused into the per-ray shading kernel would see;
-                              // same results); 2 = timing probe, WRONG results: a hashed level's corner loads restricted to one HALF
-                              // of its slice by entry index, lower half during the first half of an XCD's chunks of the level, upper
-                              // half during the second (one of the two passes an entry-range split between XCDs would make);
-                              // 3 = timing probe: every corner reads entry 0 of its level (no table traffic); 4 = timing probe: no stores
 };
 
 constexpr int kEncThreads = 512;             // sample points of one level per workgroup = kEncRows tiles of the scatter's counting sort
@@ -326,38 +318,11 @@ __device__ __forceinline__ void locate_sample(const FieldC& fc, const float* __r
 
 // INTERLEAVED: dual field with the entry-interleaved table copy (ls2fm_params.dual_table): one 16-byte gather per corner
 // serves both grids -- the gathers are bound by the L2 -> L1 line rate, not by bytes.
-// (the measurement probes are compiled in only with -DLS2FM_ENC_PROBES: inside the shipped kernel their branches cost 14 registers --
-// 70 -> 84, five instead of seven waves per SIMD)
-// Issue priority (round 6, profiles/r06_notes.md section 9).  LS2FM_ENC_PRIO_{PAIR,ONE} for the interleaved two-grid walk / the one-grid
-// walk: 1 = a wave runs at raised priority until its eight gathers are issued (young waves get their loads out before older ones
-// interpolate), 2 = the reverse: raised BEHIND the loads (a wave that has its data interpolates, stores and frees its slot first).
-// Two grids (16-byte gathers, 70 registers): 98 -> 111 / 105 us, left alone.  One grid (8-byte gathers, the reference's default
-// field): 77 -> 75.6 / 71.9 us at C2's shape -- 2 is its default.
-#ifndef LS2FM_ENC_PRIO_PAIR
-#define LS2FM_ENC_PRIO_PAIR 0
-#endif
-#ifndef LS2FM_ENC_PRIO_ONE
-#define LS2FM_ENC_PRIO_ONE 2
-#endif
-#define ENC_PRIO_MODE (INTERLEAVED ? LS2FM_ENC_PRIO_PAIR : LS2FM_ENC_PRIO_ONE)
-#define ENC_PRIO_HEAD(x) do { if (ENC_PRIO_MODE == 1) __builtin_amdgcn_s_setprio(x); } while (0)
-#define ENC_PRIO_TAIL(x) do { if (ENC_PRIO_MODE == 2) __builtin_amdgcn_s_setprio(x); } while (0)
-#ifdef LS2FM_ENC_PROBES
-#define ENC_PROBE(ex) ((ex).probe)
-#else
-#define ENC_PROBE(ex) 0
-#endif
+// Issue priority: the one-grid walk raises a wave's priority BEHIND its eight gathers (a wave that has its data interpolates,
+// stores and frees its slot first); the interleaved two-grid walk is left alone (profiles/r06_notes.md section 9).  Tables are
+// gathered and E / J stored through 64-bit addresses: the base + 32-bit offset form lost 20 % here (section 13).
 #ifndef LS2FM_ENC_MINW
 #define LS2FM_ENC_MINW 1
-#endif
-#ifndef LS2FM_ENC_OFF32
-#define LS2FM_ENC_OFF32 0
-#endif
-#ifndef LS2FM_ENC_OFF32_LD
-#define LS2FM_ENC_OFF32_LD LS2FM_ENC_OFF32
-#endif
-#ifndef LS2FM_ENC_OFF32_ST
-#define LS2FM_ENC_OFF32_ST LS2FM_ENC_OFF32
 #endif
 template <bool INTERLEAVED>
 __global__ void __launch_bounds__(kEncThreads, LS2FM_ENC_MINW)
@@ -373,16 +338,10 @@ ray_encode_kernel(LevelSet lv1, LevelSet lv2, FieldC fc, const float* __restrict
         if (blockIdx.x == 3 && tid == 0 && ex.scan_ticket) *ex.scan_ticket = 0;      // armed for the scans in the shade_fwd launch
         return;
     }
-    ENC_PRIO_HEAD(2);
     const int bx = (int)blockIdx.x - kEncReserved;
     const int xcd = bx & 7, j = bx >> 3;
-    int unit = plan.start[xcd] + j;
-    if (ENC_PROBE(ex) == 1) {                                 // (measurement) chunk-major: XCD x walks chunks x, x + 8, .. of EVERY pass-level
-        const int n_pl = plan.start[8] / n_chunks;
-        const int ck = (j / n_pl) * 8 + xcd;
-        if (ck >= n_chunks) return;
-        unit = (j % n_pl) * n_chunks + ck;
-    } else if (unit >= plan.start[xcd + 1]) return;
+    const int unit = plan.start[xcd] + j;
+    if (unit >= plan.start[xcd + 1]) return;
     const int pl = unit / n_chunks;                      // pass-level; two grids: (level 0, grid 1), (level 0, grid 2), (level 1, ..
     const int chunk = unit % n_chunks;
     const bool two = !INTERLEAVED && table2 != nullptr;
@@ -409,30 +368,13 @@ ray_encode_kernel(LevelSet lv1, LevelSet lv2, FieldC fc, const float* __restrict
         uint32_t g[3];
         Cell c;
         locate_sample(fc, center, ray, ex.pts, i, lv, g, c);
-        // row `row` of a [channel][p_pad] (k = 1) / [channel][p_pad][3] (k = 3) block, this thread's point: uniform base + 32-bit byte
-        // offset (LS2FM_ENC_OFF32: `global_store v_off, v, s[base]` instead of a 64-bit address per store; 32 rows x 2^23 points x 12 B < 2^32)
-        const uint32_t pp32 = (uint32_t)p_pad, i32 = (uint32_t)i;
-        auto enc_at = [=](float* __restrict__ base, int row, uint32_t k) -> float* {
-            return LS2FM_ENC_OFF32_ST ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + ((uint32_t)row * pp32 + i32) * (4u * k))
-                                   : base + ((int64_t)row * p_pad + i) * k;
-        };
+        // row `row` of a [channel][p_pad] (k = 1) / [channel][p_pad][3] (k = 3) block, this thread's point
+        auto enc_at = [=](float* __restrict__ base, int row, uint32_t k) -> float* { return base + ((int64_t)row * p_pad + i) * k; };
         if (INTERLEAVED) {
             const float4* __restrict__ table = reinterpret_cast<const float4*>(table1);
             float4 v[8];
-            if (ENC_PROBE(ex) == 3) {                         // (timing probe: wrong results) no table traffic: every corner reads the level's entry 0
 #pragma unroll
-                for (int k = 0; k < 8; ++k) c.idx[k] = lv.offset;
-            }
-            if (ENC_PROBE(ex) == 2 && lv.hashed) {            // (timing probe: wrong results) only the corners in one half of the slice
-                const uint32_t want = 2 * chunk >= n_chunks ? 1u : 0u, hb = lv.size >> 1;
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if ((((c.idx[k] - lv.offset) >= hb) ? 1u : 0u) != want) c.idx[k] = lv.offset + want * hb;
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                v[k] = LS2FM_ENC_OFF32_LD ? *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(table1) + c.idx[k] * 16u) : table[c.idx[k]];
-            ENC_PRIO_HEAD(0); ENC_PRIO_TAIL(2);
+            for (int k = 0; k < 8; ++k) v[k] = table[c.idx[k]];
             float y0 = 0.f, y1 = 0.f, y2 = 0.f, y3 = 0.f;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -442,13 +384,10 @@ ray_encode_kernel(LevelSet lv1, LevelSet lv2, FieldC fc, const float* __restrict
                 y2 = fmaf(wt, v[k].z, y2);
                 y3 = fmaf(wt, v[k].w, y3);
             }
-            const bool st = ENC_PROBE(ex) != 4 || y0 == 1234.5f;          // (probe 4, timing only: no value / Jacobian stores)
-            if (st) {
             __builtin_nontemporal_store(y0, enc_at(enc1, 2 * l + 0, 1u));
             __builtin_nontemporal_store(y1, enc_at(enc1, 2 * l + 1, 1u));
             __builtin_nontemporal_store(y2, enc_at(enc2, 2 * l + 0, 1u));
             __builtin_nontemporal_store(y3, enc_at(enc2, 2 * l + 1, 1u));
-            }
 #pragma unroll
             for (int gd = 0; gd < 3; ++gd) {
                 float g0 = 0.f, g1 = 0.f;
@@ -458,19 +397,15 @@ ray_encode_kernel(LevelSet lv1, LevelSet lv2, FieldC fc, const float* __restrict
                     g0 = fmaf(dw, v[k].x, g0);
                     g1 = fmaf(dw, v[k].y, g1);
                 }
-                if (st || g0 == 1234.5f) {
                 __builtin_nontemporal_store(lv.scale * g0, enc_at(jac, 2 * l + 0, 3u) + gd);      // [channel][point][3]
                 __builtin_nontemporal_store(lv.scale * g1, enc_at(jac, 2 * l + 1, 3u) + gd);
-                }
             }
         } else {
             const float* __restrict__ table = second ? table2 : table1;
             float2 v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
-                v[k] = LS2FM_ENC_OFF32_LD ? *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(table) + c.idx[k] * 8u)
-                                       : *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
-            ENC_PRIO_HEAD(0); ENC_PRIO_TAIL(2);
+            for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
+            __builtin_amdgcn_s_setprio(2);
             float y0 = 0.f, y1 = 0.f;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -584,16 +519,8 @@ static XcdPlan make_xcd_plan(const ls2fm_grid_desc* g1, int l1, const ls2fm_grid
     // ONE pass over the entry-interleaved table (16-byte gathers, a level slice is 8 MB: twice an XCD's L2): the coarse levels
     // are relatively cheaper than in the two-table pass -- measured 0.20-0.30 (dense), 0.61, 0.90, then 1.0 -- with the
     // two-table constants the XCD that owns them finished 21 us before the last one (86 vs 107 us).
-    static double cm2[6] = {0.27, 1.5, 1.1, 0.45, 0.45, 1.0};     // two tables:  dense, first_dense, first_hashed, slope, intercept, top
-    static double cmi[6] = {0.31, 1.0, 1.0, 1.0, -0.156, 1.0};    // interleaved
-    static const bool cm_env = [] {
-        const char* e = getenv("LS2FM_CM");                      // experiments: "dense,first_dense,first_hashed,slope,intercept"
-        if (e) sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf", &cm2[0], &cm2[1], &cm2[2], &cm2[3], &cm2[4], &cm2[5]);
-        const char* e2 = getenv("LS2FM_CMI");
-        if (e2) sscanf(e2, "%lf,%lf,%lf,%lf,%lf,%lf", &cmi[0], &cmi[1], &cmi[2], &cmi[3], &cmi[4], &cmi[5]);
-        return e != nullptr;
-    }();
-    (void)cm_env;
+    static constexpr double cm2[6] = {0.27, 1.5, 1.1, 0.45, 0.45, 1.0};     // two tables:  dense, first_dense, first_hashed, slope, intercept, top
+    static constexpr double cmi[6] = {0.31, 1.0, 1.0, 1.0, -0.156, 1.0};    // interleaved
     const double* cm = interleaved ? cmi : cm2;
     const int n_pl = l1 + l2;
     for (int pl = 0; pl < n_pl; ++pl) {
@@ -677,7 +604,6 @@ int ls2fm_launch_points_encode(const ls2fm_field_desc* field, const ls2fm_grid_d
     ex.n_explicit = 0;
     ex.n_prep_tasks = 1;
     ex.pts = pts;
-    ex.probe = 0;
     ray_encode_kernel<false><<<(unsigned)(kEncReserved + 8 * most), kEncThreads, 0, s>>>(
         make_level_set(grid), make_level_set(grid), fc, nullptr, nullptr, params->sdf_table, nullptr, w.p, w.p_pad, n_chunks, plan,
         ws + w.e1, nullptr, ws + w.j1, ex);
@@ -725,13 +651,6 @@ extern "C" int ls2fm_render_fwd(const ls2fm_field_desc* field, const ls2fm_grid_
     ex.tile_counts = nullptr; ex.scan_ticket = nullptr; ex.n_tiles = 0; ex.sshift = ls2fm_slab_shift(dual);
     ex.n_explicit = ls2fm_explicit_levels(sdf_grid, dual, field->n_samples);
     ex.n_prep_tasks = 3; ex.pts = nullptr;
-    static const int enc_probe = [] { const char* e = getenv("LS2FM_ENC_PROBE"); return e ? atoi(e) : 0; }();
-#ifdef LS2FM_ENC_PROBES
-    ex.probe = enc_probe;
-#else
-    ex.probe = 0; (void)enc_probe;
-#endif
-    if (ex.probe == 1) most = (n_chunks + 7) / 8 * (L1 + (pair ? L2 : 0));
     if (prepare_bwd) {
         const BinMeta bm = make_bin_meta(ws + w.bins, w.p);
         ex.tile_counts = bm.tile;

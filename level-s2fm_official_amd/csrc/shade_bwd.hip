@@ -28,34 +28,16 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Issue priority (round 6, profiles/r06_notes.md section 9).  The two waves of a SIMD belong to two rays that started together: left
+// Issue priority (profiles/r06_notes.md section 9).  The two waves of a SIMD belong to two rays that started together: left
 // alone they reach their MFMA clusters and their softplus / LDS parts at the same time and queue for the same pipe.  With the
 // priority raised around the MFMA clusters of the SDF field's hidden blocks and dropped for the VALU part between them, the wave
 // that gets to its MFMAs first keeps the matrix pipe and the other one's VALU work fills the gaps -- the pair falls out of step:
-// shade_bwd 111.4 -> 106.0 us at C2 (single field 72.8 -> 70.6, C3 832 -> 821), bit-identical.  LS2FM_BWD_PRIO: 0 = no s_setprio,
-// 1 = raised for the whole hidden-block loop (107 us at C2, but +1 % at C3), 2 = around the MFMA clusters (the default).  Measured
-// and not kept: a tile's operand loads at the highest priority (no change), the VALU position columns lowered (108), a constant
-// priority by the parity of the wave's slot (111: no gain), the same toggling in the second field's loop (no change), and the same
-// scheme in shade_fwd (four waves per SIMD there: 57 - 60 against 57.6 us); __builtin_amdgcn_iglp_opt(0 / 1) in the hidden-block loop (106).
-// LS2FM_BWD_PART_NT (round 6): the per-ray weight-gradient partials (39 KB per ray) leave with non-temporal stores: shade_bwd 105.6 -> 103.6 us,
-// the fill (whose leading rows read them) 79.9 -> 81.9, the step 0.4098 -> 0.4078 ms in three alternating pairs (profiles/r06_raw/c73_ab_part_nt.txt)
-#ifndef LS2FM_BWD_PART_NT
-#define LS2FM_BWD_PART_NT 1
-#endif
-#ifndef LS2FM_BWD_PRIO
-#define LS2FM_BWD_PRIO 2
-#endif
-#define BWD_PRIO_LOOP(x) do { if (LS2FM_BWD_PRIO == 1) __builtin_amdgcn_s_setprio(x); } while (0)
-#define BWD_PRIO_MFMA(x) do { if (LS2FM_BWD_PRIO == 2) __builtin_amdgcn_s_setprio(x); } while (0)
+// shade_bwd 111.4 -> 106.0 us at C2 (single field 72.8 -> 70.6, C3 832 -> 821), bit-identical.
+// The per-ray weight-gradient partials (39 KB per ray) leave with non-temporal stores (section 12).
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-#ifndef LS2FM_PROBE
-#define LS2FM_PROBE 0
-#endif
-constexpr bool kProbeNoContract = (LS2FM_PROBE & 1) != 0, kProbeNoTrans = (LS2FM_PROBE & 2) != 0, kProbeNC1 = (LS2FM_PROBE & 4) != 0;
-constexpr bool kProbeNoPos = (LS2FM_PROBE & 8) != 0, kProbeStage1 = (LS2FM_PROBE & 32) != 0;
 constexpr int kTLd = 20;       // floats per row of the wave-private transpose tile: 16 samples + 4 pad (16-B aligned rows)
 constexpr int kTRows = 48;     // da | gj | h of one hidden block (U / V: 36 rows, GF: 20)
 constexpr int kSwWg = kMfmaBwdSdfFloats - 4 * 4 * 64 + 64;       // WG: W1[0] as 64 floats instead of its operand-ordered 4 KB
@@ -70,40 +52,23 @@ constexpr int kSwWg = kMfmaBwdSdfFloats - 4 * 4 * 64 + 64;       // WG: W1[0] as
 #ifndef LS2FM_BWD_WAVES_WG
 #define LS2FM_BWD_WAVES_WG 2
 #endif
-template <bool WG> constexpr int bwd_nc() { return WG ? LS2FM_BWD_NC_WG : (kProbeNC1 ? 1 : 2); }
+template <bool WG> constexpr int bwd_nc() { return WG ? LS2FM_BWD_NC_WG : 2; }
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// the scatter's records: written once here, read once by scatter_fill (any XCD) -- optionally non-temporal (LS2FM_REC_NT)
-#ifndef LS2FM_REC_NT
-#define LS2FM_REC_NT 1
-#endif
+// the scatter's records: written once here, read once by scatter_fill (any XCD) -- non-temporal stores
 __device__ __forceinline__ void st4(float* p, const float4 v) {
-#if LS2FM_REC_NT
     const f32x4 r = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 __device__ __forceinline__ void st2(float* p, const float2 v) {
-#if LS2FM_REC_NT
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 r = {v.x, v.y};
     __builtin_nontemporal_store(r, reinterpret_cast<f32x2*>(p));
-#else
-    *reinterpret_cast<float2*>(p) = v;
-#endif
 }
-// LS2FM_BWD_OFF32 (round 6, as in shade_fwd.hip): per-sample rows are addressed as uniform base + 32-bit BYTE offset -- the offset is
-// formed in 32-bit arithmetic, so the access is `global_load v, v_off, s[base]` (one register, one add) instead of a 64-bit address per
-// lane (an element index scaled in 64 bits defeats that form).  LS2FM_MAX_RENDER_POINTS = 2^23 keeps 32 rows x p_pad x 12 bytes and 16
-// levels x p_pad x 16 bytes under 2^32.
-#ifndef LS2FM_BWD_EJ_NT
-#define LS2FM_BWD_EJ_NT 0
-#endif
-#ifndef LS2FM_BWD_OFF32
-#define LS2FM_BWD_OFF32 1
-#endif
+// Per-sample rows are addressed as uniform base + 32-bit BYTE offset -- the offset is formed in 32-bit arithmetic, so the access is
+// `global_load v, v_off, s[base]` (one register, one add) instead of a 64-bit address per lane (an element index scaled in 64 bits
+// defeats that form; profiles/r06_notes.md section 13).  LS2FM_MAX_RENDER_POINTS = 2^23 keeps 32 rows x p_pad x 12 bytes and 16
+// levels x p_pad x 16 bytes under 2^32.  E / J are read with plain loads (non-temporal ones: section 16).
 template <typename T> __device__ __forceinline__ const T* at_bytes(const float* base, uint32_t bytes) {
     return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + bytes);
 }
@@ -112,10 +77,10 @@ template <typename T> __device__ __forceinline__ T* at_bytes(float* base, uint32
 }
 // element `idx` of a float row block / the `idx`-th group of K floats
 __device__ __forceinline__ const float* elem(const float* base, uint32_t idx, uint32_t k = 1u) {
-    return LS2FM_BWD_OFF32 ? at_bytes<float>(base, idx * (4u * k)) : base + (int64_t)idx * k;
+    return at_bytes<float>(base, idx * (4u * k));
 }
 __device__ __forceinline__ float* elem(float* base, uint32_t idx, uint32_t k = 1u) {
-    return LS2FM_BWD_OFF32 ? at_bytes<float>(base, idx * (4u * k)) : base + (int64_t)idx * k;
+    return at_bytes<float>(base, idx * (4u * k));
 }
 // lane J of this lane's 16-lane row (DPP row_share: folds into the consuming VALU instruction)
 template <int J> __device__ __forceinline__ float row_bcast(float v) {
@@ -237,11 +202,7 @@ __device__ __forceinline__ void wg_flush(const f32x4 (&acc0)[4][2], const f32x4 
     }
     if (wave == 0) {
 #pragma unroll
-#if LS2FM_BWD_PART_NT
-        for (int q = 0; q < R; ++q) __builtin_nontemporal_store(regs[q], LS2FM_BWD_OFF32 ? at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u) : dst + lane + q * 64);
-#else
-        for (int q = 0; q < R; ++q) (dst + lane)[q * 64] = regs[q];
-#endif
+        for (int q = 0; q < R; ++q) __builtin_nontemporal_store(regs[q], at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u));
     }
 }
 
@@ -518,7 +479,6 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
     }
 
     // =========================================================================== 2. MFMA lanes
-    if (kProbeStage1) return;
     const float* __restrict__ s_w0a = s_w;                              // [m][t][lane]
     const float* __restrict__ s_w1ta = s_w + 4 * 9 * 64;                // [m][5][lane]
     const float* __restrict__ s_w0ta = s_w1ta + 4 * 5 * 64;             // [mk][m][r][lane]
@@ -596,7 +556,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             for (int cc = 0; cc < NC; ++cc) {
                 const int ch = 4 * t + g;
                 const bool on = ch < ch1;
-                ub[t][cc] = on ? (LS2FM_BWD_EJ_NT ? __builtin_nontemporal_load(elem(f_e1, (uint32_t)ch * P32 + is[cc])) : *elem(f_e1, (uint32_t)ch * P32 + is[cc])) : 0.f;
+                ub[t][cc] = on ? *elem(f_e1, (uint32_t)ch * P32 + is[cc]) : 0.f;
                 // J rows are [channel][point][3]: one 12-byte load per (channel, sample)
                 // (a 4-byte-aligned 3-vector, NOT a struct of float[3]: the conditionally assigned struct stayed an alloca, which the
                 // compiler promoted to LDS indexed by the FLAT work-item id -- and for that it read the workgroup's y / z sizes from the
@@ -604,8 +564,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                 typedef float f32x3 __attribute__((ext_vector_type(3)));
                 typedef f32x3 f32x3_a4 __attribute__((aligned(4)));
                 f32x3 jv = {0.f, 0.f, 0.f};
-                if (on) jv = LS2FM_BWD_EJ_NT ? __builtin_nontemporal_load(reinterpret_cast<const f32x3_a4*>(elem(f_j1, (uint32_t)ch * P32 + is[cc], 3u)))
-                                             : *reinterpret_cast<const f32x3_a4*>(elem(f_j1, (uint32_t)ch * P32 + is[cc], 3u));
+                if (on) jv = *reinterpret_cast<const f32x3_a4*>(elem(f_j1, (uint32_t)ch * P32 + is[cc], 3u));
                 float acc = fmaf(jv.x, gns[cc][0], 0.f);
                 acc = fmaf(jv.y, gns[cc][1], acc);
                 acc = fmaf(jv.z, gns[cc][2], acc);
@@ -663,11 +622,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         // (WG) U, V, GF of this tile as operands of the contraction over the samples: row jl (+ 16 mk), samples 4g .. 4g + 3.
         // A wave's DS operations execute in order: a tile's rows are rewritten right behind the reads of the previous rows.
         float4 b_u[NC][3], b_v[NC][3], a_gf[NC];
-        if (WG && kProbeNoTrans) {
-#pragma unroll
-            for (int cc = 0; cc < NC; ++cc) b_u[cc][0] = b_u[cc][1] = b_u[cc][2] = b_v[cc][0] = b_v[cc][1] = b_v[cc][2] = a_gf[cc] = make_float4(1.f, 2.f, 3.f, 4.f);
-        }
-        if (WG && !kProbeNoTrans) {
+        if (WG) {
             const int row2 = jl < 4 ? 32 + jl : 35;                  // rows 32..35 exist: lanes jl < 4 are the ones pos_col reads
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) {                        // (tile cc's own block of the wave's LDS area)
@@ -702,10 +657,9 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         for (int mk = 0; mk < 2; ++mk)
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) { de[mk][cc] = f32x4{0.f, 0.f, 0.f, 0.f}; rr[mk][cc] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        BWD_PRIO_LOOP(1);
 #pragma unroll kUnrollM
         for (int m = 0; m < 4; ++m) {
-            BWD_PRIO_MFMA(1);
+            __builtin_amdgcn_s_setprio(1);
             f32x4 aa[NC], qq[NC], tt[NC];
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) { aa[cc] = f32x4{0.f, 0.f, 0.f, 0.f}; qq[cc] = aa[cc]; tt[cc] = aa[cc]; }
@@ -725,7 +679,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                     for (int cc = 0; cc < NC; ++cc) tt[cc] = mfma4(a1, gfb[t][cc], tt[cc]);
                 }
             }
-            BWD_PRIO_MFMA(0);
+            __builtin_amdgcn_s_setprio(0);
             float da[NC][4], gj[NC][4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -736,7 +690,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                     softplus100(aa[cc][q], h, s1, s2);
                     da[cc][q] = fmaf(s1, tt[cc][q], s2 * w10 * qq[cc][q]);
                     gj[cc][q] = s1 * w10;
-                    if (WG && !kProbeNoTrans) {       // this hidden block's DA | GJ | H, [hidden unit 4g + q][sample jl]
+                    if (WG) {       // this hidden block's DA | GJ | H, [hidden unit 4g + q][sample jl]
                         float* __restrict__ xc = xt + cc * (kTRows * kTLd);
                         xc[(4 * g + q) * kTLd + jl] = da[cc][q];
                         xc[(16 + 4 * g + q) * kTLd + jl] = gj[cc][q];
@@ -748,7 +702,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                     }
                 }
             }
-            BWD_PRIO_MFMA(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int mk = 0; mk < 2; ++mk)
 #pragma unroll
@@ -768,7 +722,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                     for (int cc = 0; cc < NC; ++cc) dex[cc] = mfma4(at, da[cc][q], dex[cc]);
                 }
             }
-            if (WG && !kProbeNoContract) {
+            if (WG) {
                 // contraction over the tile's 16 samples: the lane supplies row jl, samples 4g .. 4g + 3 of every operand (the
                 // tile's trip through LDS was in flight during the DE / RR products above)
                 __builtin_amdgcn_wave_barrier();
@@ -792,19 +746,17 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                     c0 = mfma4(a_gj[cc].w, b_v[cc][0].w, c0); c1 = mfma4(a_gj[cc].w, b_v[cc][1].w, c1);
                 }
                 acc0[m][0] = c0; acc0[m][1] = c1; acc1[m] = c3;
-                if (!kProbeNoPos) {
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc) {
-                pacc[m][0] = pos_col<0, true>(pacc[m][0], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
-                pacc[m][1] = pos_col<1, true>(pacc[m][1], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
-                pacc[m][2] = pos_col<2, true>(pacc[m][2], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
-                pacc[m][3] = pos_col<3, false>(pacc[m][3], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);       // (V has no bias row)
-                }
+                    pacc[m][0] = pos_col<0, true>(pacc[m][0], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
+                    pacc[m][1] = pos_col<1, true>(pacc[m][1], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
+                    pacc[m][2] = pos_col<2, true>(pacc[m][2], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);
+                    pacc[m][3] = pos_col<3, false>(pacc[m][3], a_da[cc], a_gj[cc], b_u[cc][2], b_v[cc][2]);       // (V has no bias row)
                 }
                 __builtin_amdgcn_sched_barrier(0);       // (the unrolled hidden blocks are not interleaved: their temporaries would add up)
             }
         }
-        BWD_PRIO_LOOP(0); BWD_PRIO_MFMA(0);
+        __builtin_amdgcn_s_setprio(0);
         if (want_pose && g == 0) {
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc)
@@ -841,7 +793,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
 #pragma unroll
             for (int t = 0; t < 8; ++t)
 #pragma unroll
-                for (int cc = 0; cc < NC; ++cc) ub[t][cc] = (4 * t + g) < ch2 ? (LS2FM_BWD_EJ_NT ? __builtin_nontemporal_load(elem(f_e2, (uint32_t)(4 * t + g) * P32 + is[cc])) : *elem(f_e2, (uint32_t)(4 * t + g) * P32 + is[cc])) : 0.f;
+                for (int cc = 0; cc < NC; ++cc) ub[t][cc] = (4 * t + g) < ch2 ? *elem(f_e2, (uint32_t)(4 * t + g) * P32 + is[cc]) : 0.f;
 #pragma unroll
             for (int cc = 0; cc < NC; ++cc) {
 #pragma unroll
@@ -855,11 +807,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                 if (!WG && live_c[cc] && g == 0) o_gf2[is[cc]] = 0.f;
             }
             float4 b_u[NC][3], a_gf[NC];
-            if (WG && kProbeNoTrans) {
-#pragma unroll
-                for (int cc = 0; cc < NC; ++cc) b_u[cc][0] = b_u[cc][1] = b_u[cc][2] = a_gf[cc] = make_float4(1.f, 2.f, 3.f, 4.f);
-            }
-            if (WG && !kProbeNoTrans) {
+            if (WG) {
                 const int row2 = jl < 4 ? 32 + jl : 35;
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc) {
@@ -884,7 +832,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             for (int mk = 0; mk < 2; ++mk)
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc) de2[mk][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
-            BWD_PRIO_LOOP(1); BWD_PRIO_MFMA(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll kUnrollM
             for (int m = 0; m < 4; ++m) {
                 f32x4 aa[NC], tt[NC];
@@ -910,7 +858,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                         float h, s1, s2;
                         softplus100(aa[cc][q], h, s1, s2);
                         da[cc][q] = s1 * tt[cc][q];
-                        if (WG && !kProbeNoTrans) {
+                        if (WG) {
                             float* __restrict__ xc = xt + cc * (kTRows * kTLd);
                             xc[(4 * g + q) * kTLd + jl] = da[cc][q];
                             xc[(32 + 4 * g + q) * kTLd + jl] = h;
@@ -933,7 +881,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                         for (int cc = 0; cc < NC; ++cc) dex[cc] = mfma4(at, da[cc][q], dex[cc]);
                     }
                 }
-                if (WG && !kProbeNoContract) {
+                if (WG) {
                     __builtin_amdgcn_wave_barrier();
                     float4 a_da[NC], b_h[NC];
 #pragma unroll
@@ -951,19 +899,17 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
                         c0 = mfma4(a_da[cc].w, b_u[cc][0].w, c0); c1 = mfma4(a_da[cc].w, b_u[cc][1].w, c1); c3 = mfma4(a_gf[cc].w, b_h[cc].w, c3);
                     }
                     acc0[m][0] = c0; acc0[m][1] = c1; acc1[m] = c3;
-                    if (!kProbeNoPos) {
 #pragma unroll
                     for (int cc = 0; cc < NC; ++cc) {
-                    pacc[m][0] = pos_col<0, false>(pacc[m][0], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
-                    pacc[m][1] = pos_col<1, false>(pacc[m][1], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
-                    pacc[m][2] = pos_col<2, false>(pacc[m][2], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
-                    pacc[m][3] = pos_col<3, false>(pacc[m][3], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
-                    }
+                        pacc[m][0] = pos_col<0, false>(pacc[m][0], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
+                        pacc[m][1] = pos_col<1, false>(pacc[m][1], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
+                        pacc[m][2] = pos_col<2, false>(pacc[m][2], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
+                        pacc[m][3] = pos_col<3, false>(pacc[m][3], a_da[cc], a_da[cc], b_u[cc][2], b_u[cc][2]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            BWD_PRIO_LOOP(0); BWD_PRIO_MFMA(0);
+            __builtin_amdgcn_s_setprio(0);
             if (want_pose && g == 0) {
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc)

@@ -21,35 +21,10 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// issue-priority experiment (round 6, profiles/r06_notes.md section 9; shade_bwd.hip gains 5 % from it): LS2FM_FWD_PRIO = 1 raises a
-// wave's priority inside the hidden-block loop, 2 only around its MFMA clusters.  Four waves per SIMD here: 59.9 - 60.3 / 57.0 - 57.6
-// against 57.3 - 57.9 us -- default 0, no s_setprio.
-#ifndef LS2FM_FWD_PRIO
-#define LS2FM_FWD_PRIO 0
-#endif
-#define FWD_PRIO_LOOP(x) do { if (LS2FM_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(x); } while (0)
-#define FWD_PRIO_MFMA(x) do { if (LS2FM_FWD_PRIO == 2) __builtin_amdgcn_s_setprio(x); } while (0)
-// LS2FM_FWD_NT (round 6): the per-sample outputs (sdf, normal, colour, both feature blocks: what shade_bwd reads back ~100 us later, and the
-// caller's [R, N] tensors) leave with non-temporal stores: shade_fwd 57.7 -> 56.4 us at C2, 378 -> 372 at 8192 rays, shade_bwd unchanged
-// (profiles/r06_raw/c71_ab_fwd_nt.txt).
-#ifndef LS2FM_FWD_NT
-#define LS2FM_FWD_NT 1
-#endif
-#ifndef LS2FM_FWD_FULL
-#define LS2FM_FWD_FULL 1
-#endif
-#ifndef LS2FM_FWD_FULL_J
-#define LS2FM_FWD_FULL_J 0
-#endif
-#ifndef LS2FM_FWD_REPOS
-#define LS2FM_FWD_REPOS 1
-#endif
-#ifndef LS2FM_FWD_OFF32
-#define LS2FM_FWD_OFF32 1
-#endif
-#ifndef LS2FM_FWD_SCHED_BAR
-#define LS2FM_FWD_SCHED_BAR 0
-#endif
+// No issue-priority hooks here: with four waves per SIMD, raising a wave's priority inside the hidden-block loop or around its MFMA
+// clusters measured nothing or worse (profiles/r06_notes.md sections 9 and 13); neither did a scheduling barrier behind that loop.
+// The per-sample outputs (sdf, normal, colour, the CT = 2 feature blocks: what shade_bwd reads back ~100 us later, and the caller's
+// [R, N] tensors) leave with non-temporal stores (section 12).
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -124,9 +99,9 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
     struct Cols { float v[CT]; };
     const bool vec = FULL || (live_c[CT - 1] && ((is[0] & (CT - 1)) == 0));
     const int64_t i0 = is[0], i1 = is[1], i2 = is[CT - 2], i3 = is[CT - 1];
-    // LS2FM_FWD_OFF32 (round 6): the vector forms address uniform base + 32-bit byte offset (global_load ... v_off, s[base]) instead of a
-    // 64-bit address per lane: one register and one add per load instead of two and a 64-bit add chain (LS2FM_MAX_RENDER_POINTS = 2^23
-    // keeps 32 rows x p_pad x 12 bytes under 2^32)
+    // the vector forms address uniform base + 32-bit byte offset (global_load ... v_off, s[base]) instead of a 64-bit address per
+    // lane: one register and one add per load instead of two and a 64-bit add chain (LS2FM_MAX_RENDER_POINTS = 2^23 keeps 32 rows x
+    // p_pad x 12 bytes under 2^32; profiles/r06_notes.md section 13)
     const unsigned pp = (unsigned)p_pad, u0 = (unsigned)i0;
     auto loadv = [=](const float* __restrict__ base, int rowidx) -> Cols {        // by value: by-reference captures cost spilled registers
         Cols o;
@@ -135,13 +110,13 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
         const unsigned off = ((unsigned)rowidx * pp + u0) * 4u;
         if (CT == 4) {
             if (vec) {
-                const float4 t = LS2FM_FWD_OFF32 ? *reinterpret_cast<const float4*>(cb + off) : *reinterpret_cast<const float4*>(row + i0);
+                const float4 t = *reinterpret_cast<const float4*>(cb + off);
                 o.v[0] = t.x; o.v[1] = t.y; o.v[CT - 2] = t.z; o.v[CT - 1] = t.w;
             }
             else { o.v[0] = row[i0]; o.v[1] = row[i1]; o.v[CT - 2] = row[i2]; o.v[CT - 1] = row[i3]; }
         } else {
             if (vec) {
-                const float2 t = LS2FM_FWD_OFF32 ? *reinterpret_cast<const float2*>(cb + off) : *reinterpret_cast<const float2*>(row + i0);
+                const float2 t = *reinterpret_cast<const float2*>(cb + off);
                 o.v[0] = t.x; o.v[1] = t.y;
             }
             else { o.v[0] = row[i0]; o.v[1] = row[i1]; }
@@ -173,10 +148,8 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
 #pragma unroll
         for (int mk = 0; mk < 3; ++mk) racc[mk][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    FWD_PRIO_LOOP(1);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        FWD_PRIO_MFMA(1);
         f32x4 acc[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -186,7 +159,6 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
 #pragma unroll
             for (int c = 0; c < CT; ++c) acc[c] = mfma4(a, ub[t][c], acc[c]);
         }
-        FWD_PRIO_MFMA(0);
         float ga[CT][4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -200,7 +172,6 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
                 f0p[c] = fmaf(w10, h, f0p[c]);
             }
         }
-        FWD_PRIO_MFMA(1);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float a1 = s_w1a[(m * 4 + q) * 64 + lane];
@@ -217,10 +188,6 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
             }
     }
 
-    FWD_PRIO_LOOP(0); FWD_PRIO_MFMA(0);
-#if LS2FM_FWD_SCHED_BAR
-    __builtin_amdgcn_sched_barrier(0);       // the Jacobian loads (48 registers) stay behind the hidden-block loop
-#endif
     // sdf and the analytic normal  n = kappa (R_p / rescale + inv_ext . J^T R_enc)
     float sdf[CT], nrm[CT][3];
     float part[CT][3];
@@ -231,14 +198,14 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int ch = 16 * mk + 4 * g + q;
-            if (ch < (LS2FM_FWD_FULL_J ? ch1 : ch1_arg)) {
+            if (ch < ch1_arg) {          // (a run-time predicate even in FULL: compile-time, the Jacobian loads were hoisted; section 13)
                 // J rows are [channel][point][3]: the lane's CT consecutive samples are 3 CT consecutive floats
                 const float* __restrict__ jrow = J1 + (int64_t)ch * p_pad * 3;
                 const char* __restrict__ jb = reinterpret_cast<const char*>(J1) + ((unsigned)ch * (pp * 3u) + u0 * 3u) * 4u;
                 float jv[CT][3];
                 if (vec) {
                     if (CT == 4) {
-                        const float4* q4 = LS2FM_FWD_OFF32 ? reinterpret_cast<const float4*>(jb) : reinterpret_cast<const float4*>(jrow + i0 * 3);
+                        const float4* q4 = reinterpret_cast<const float4*>(jb);
                         const float4 x0 = q4[0], x1 = q4[1], x2 = q4[2];
                         const float f[12] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w, x2.x, x2.y, x2.z, x2.w};
 #pragma unroll
@@ -246,7 +213,7 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
 #pragma unroll
                             for (int a = 0; a < 3; ++a) jv[c][a] = f[3 * c + a];
                     } else {
-                        const float2* q2 = LS2FM_FWD_OFF32 ? reinterpret_cast<const float2*>(jb) : reinterpret_cast<const float2*>(jrow + i0 * 3);
+                        const float2* q2 = reinterpret_cast<const float2*>(jb);
                         const float2 x0 = q2[0], x1 = q2[1], x2 = q2[2];
                         const float f[6] = {x0.x, x0.y, x1.x, x1.y, x2.x, x2.y};
 #pragma unroll
@@ -285,8 +252,7 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
         const unsigned off = ((unsigned)rowidx * pp + u0) * 4u;
         if (CT == 4) {
             if (vec) {
-                if (LS2FM_FWD_OFF32) *reinterpret_cast<float4*>(cb + off) = make_float4(acc[0][q], acc[1][q], acc[CT - 2][q], acc[CT - 1][q]);
-                else *reinterpret_cast<float4*>(row + i0) = make_float4(acc[0][q], acc[1][q], acc[CT - 2][q], acc[CT - 1][q]);
+                *reinterpret_cast<float4*>(cb + off) = make_float4(acc[0][q], acc[1][q], acc[CT - 2][q], acc[CT - 1][q]);
             } else {
                 if (l0) row[i0] = acc[0][q];
                 if (l1) row[i1] = acc[1][q];
@@ -295,13 +261,9 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
             }
         } else {
             if (vec) {
-#if LS2FM_FWD_NT
-                { typedef float f32x2 __attribute__((ext_vector_type(2))); f32x2 v = {acc[0][q], acc[1][q]};
-                  __builtin_nontemporal_store(v, LS2FM_FWD_OFF32 ? reinterpret_cast<f32x2*>(cb + off) : reinterpret_cast<f32x2*>(row + i0)); }
-#else
-                if (LS2FM_FWD_OFF32) *reinterpret_cast<float2*>(cb + off) = make_float2(acc[0][q], acc[1][q]);
-                else *reinterpret_cast<float2*>(row + i0) = make_float2(acc[0][q], acc[1][q]);
-#endif
+                typedef float f32x2 __attribute__((ext_vector_type(2)));
+                const f32x2 v = {acc[0][q], acc[1][q]};
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x2*>(cb + off));
             } else {
                 if (l0) row[i0] = acc[0][q];
                 if (l1) row[i1] = acc[1][q];
@@ -364,9 +326,9 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
             wf[k][q] = pk->wc[k][33 + 4 * g + q];
             wf2[k][q] = DUAL ? pk->wc[k][49 + 4 * g + q] : 0.f;
         }
-#if LS2FM_FWD_REPOS
     // the sample positions are formed again for the decoder instead of being held across both MLP chains (six registers under a cap the
-    // kernel spills at; same operations, same bits -- the sample number goes through an empty asm so that the two evaluations stay apart)
+    // kernel spills at, profiles/r06_notes.md section 13; same operations, same bits -- the sample number goes through an empty asm so
+    // that the two evaluations stay apart)
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         int ns = 16 * CT * wave + CT * jl + c;
@@ -374,7 +336,6 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
         float x[3];
         sample_position(fc, gm, sample_depth(gm, (FULL || ns < N) ? ns : N - 1, N), pw[c], x);
     }
-#endif
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         float col[3];
@@ -413,24 +374,13 @@ shade_fwd_kernel(FieldC fc, int ch1_arg, int ch2_arg, const Packed* __restrict__
     const float col_n[3] = {s_x[nx][4], s_x[nx][5], s_x[nx][6]};
     const float sigma = sigma_of(sdf_n, pk->alpha, pk->beta);
     if (live) {
-#if LS2FM_FWD_NT
         __builtin_nontemporal_store(sdf_n, sdfs_out + i);
         __builtin_nontemporal_store(sdf_n, SDFV + i);
-#else
-        sdfs_out[i] = sdf_n;
-        SDFV[i] = sdf_n;
-#endif
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-#if LS2FM_FWD_NT
             __builtin_nontemporal_store(nrm_n[a], normals_out + i * 3 + a);
             __builtin_nontemporal_store(nrm_n[a], NRM + a * p_pad + i);
             __builtin_nontemporal_store(col_n[a], RGBS + a * p_pad + i);
-#else
-            normals_out[i * 3 + a] = nrm_n[a];
-            NRM[a * p_pad + i] = nrm_n[a];
-            RGBS[a * p_pad + i] = col_n[a];
-#endif
         }
     }
 
@@ -509,7 +459,7 @@ int ls2fm_launch_shade_fwd(const FieldC& fc, int dual, int ch1, int ch2, const P
     const int threads = (fc.n_samples + per_wave - 1) / per_wave * 64;
     ls2fm_loss_spec ls{};            // rgb_gt == null: plain render
     if (loss) ls = *loss;
-    const bool full = LS2FM_FWD_FULL && small && ch1 == 32 && (!dual || ch2 == 32) && fc.n_samples % 32 == 0;
+    const bool full = small && ch1 == 32 && (!dual || ch2 == 32) && fc.n_samples % 32 == 0;
 #define LS2FM_SHADE_FWD(DUAL, MAXS, CT, FULL)                                                                      \
     shade_fwd_kernel<DUAL, MAXS, CT, FULL><<<(unsigned)n_rays, threads, 0, s>>>(                                    \
         fc, ch1, ch2, pk, center, ray, w.p_pad, ws + w.e1, ws + w.j1, DUAL ? ws + w.e2 : nullptr, rgb, sdfs_volume, \

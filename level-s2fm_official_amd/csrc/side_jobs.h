@@ -3,7 +3,7 @@
 // With the MLPs' weight gradients contracted inside shade_bwd, what is left of the side chain of rounds 2-4 is small: the decoder
 // columns (dz x [p n f f2 1], 21 MB of operands), the level-1 sums of shade_bwd's per-ray partials (40 MB), the fixed-order reduction
 // and the seven finalize tasks -- 13 + 30 us as two launches on a side stream.  Having a side stream at all costs the step 26 - 28 us
-// (timing probe LS2FM_PROBE_NO_SIDE: 0.473 -> 0.445 ms replayed, 0.468 -> 0.443 eager): a cross-queue edge in front of scatter_fill,
+// (a round-5 timing probe without the side chain: 0.473 -> 0.445 ms replayed, 0.468 -> 0.443 eager): a cross-queue edge in front of scatter_fill,
 // a fork / join pair of barrier packets, a longer replay-to-replay gap (two queues to drain) and contention with the fill.  Here the
 // jobs are device functions over an LDS arena the host kernel lends, and scatter_fill runs them in LEADING rows of its grid
 // (bin_scatter.hip): the backward is then ONE chain on ONE queue.  Hand-offs between the jobs inside that launch: write-through
@@ -38,11 +38,7 @@ __device__ __forceinline__ float4 mask4(const float4 v, int64_t s, int64_t n, bo
 // adds row k of the rays [sg * per, (sg + 1) * per) -- wave v takes the rays v, v + 4, ... of the segment, eight loads in
 // flight, then the four waves' sums are added in order -- and leaves row k of segment sum sg.  The order of the additions is a
 // function of (n_rays, kL1Seg) alone: deterministic.
-// LS2FM_SIDE_PART_NT (round 6): the per-ray partials (written once by shade_bwd with non-temporal stores, read once here) as
-// non-temporal loads
-#ifndef LS2FM_SIDE_PART_NT
-#define LS2FM_SIDE_PART_NT 0
-#endif
+// The per-ray partials are read with plain loads (non-temporal ones: profiles/r06_notes.md section 16).
 struct L1Job { const float* slot_sdf; const float* slot_geo; float* l1_sdf; float* l1_geo; int n_slots, dual; };
 
 template <bool WT>
@@ -64,11 +60,11 @@ __device__ __forceinline__ void wgrad_l1_job_a(const L1Job& jb, int job, float* 
         float v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            v[u] = LS2FM_SIDE_PART_NT ? __builtin_nontemporal_load(&src[(int64_t)(b + u * kWmWaves) * (R * 64)]) : src[(int64_t)(b + u * kWmWaves) * (R * 64)];
+            v[u] = src[(int64_t)(b + u * kWmWaves) * (R * 64)];
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc += v[u];
     }
-    for (; b < hi; b += kWmWaves) acc += LS2FM_SIDE_PART_NT ? __builtin_nontemporal_load(&src[(int64_t)b * (R * 64)]) : src[(int64_t)b * (R * 64)];
+    for (; b < hi; b += kWmWaves) acc += src[(int64_t)b * (R * 64)];
     s_l1[wave][lane] = acc;
     __syncthreads();
     if (wave == 0) {
@@ -181,7 +177,6 @@ struct SideJobs {
     WgradParts parts;
     FinalizeArgs fa;
     int* flags;               // one word per job, zeroed by shade_bwd's zero job: [dec blocks | level-1 jobs | reduction rows]
-    int probe;                // timing probe (wrong results): 1 no finalize tasks, 2 no reduction rows either, 4 no decoder tiles
     int* err;                 // host-visible sticky error word (ls2fm_async_error) or null
 };
 
@@ -225,7 +220,7 @@ __device__ __forceinline__ void side_job_run(const SideJobs& sj, int job, float*
     int* const f_l1 = sj.flags + sj.dec_blocks;
     int* const f_red = f_l1 + sj.l1_jobs;
     if (job < sj.dec_blocks) {
-        if (!(sj.probe & 4)) wgrad_dec_block_a<true, 2>(sj.w, sj.dual, sj.n_rays, sj.ws, sj.part_dec, sj.dec_blocks, job, arena);
+        wgrad_dec_block_a<true, 2>(sj.w, sj.dual, sj.n_rays, sj.ws, sj.part_dec, sj.dec_blocks, job, arena);
         side_arrive(f_dec + job);
         return;
     }
@@ -237,7 +232,6 @@ __device__ __forceinline__ void side_job_run(const SideJobs& sj, int job, float*
     }
     job -= sj.l1_jobs;
     if (job < sj.n_red) {
-        if (sj.probe & 2) return;
         // row `job` of the reduction: rows [0, rows_mlp) sum the kL1Seg segment sums of THEIR row (level-1 job ids sg * rows_mlp + row),
         // the decoder's rows every decoder block
         const int rows_mlp = kRegsSdf + (sj.dual ? kRegsGeo : 0);
@@ -248,7 +242,6 @@ __device__ __forceinline__ void side_job_run(const SideJobs& sj, int job, float*
     }
     job -= sj.n_red;
     if (job < kFinalizeTasks) {
-        if (sj.probe & 3) return;
         const bool ok = side_wait(f_red, sj.n_red, 1, s_flag);
         finalize_task_a(sj.fa, job, arena);
         // Bounded waits.  HIP promises no dispatch order inside a launch, so the protocol must not need one: the only workgroups of

@@ -344,7 +344,7 @@ def test_hand_issued_loads_stay_untouched_until_their_wait():
 
 
 def test_fixed_point_conversion_through_the_doubles_mantissa_is_rint():
-    """`slab_accumulate`'s add_fixed (csrc/bin_scatter.hip, LS2FM_ACC_CVT): fma((double) v, 2^shift, 1.5 * 2^52), reinterpreted, minus
+    """`slab_accumulate`'s add_fixed (csrc/bin_scatter.hip, `add_fixed`): fma((double) v, 2^shift, 1.5 * 2^52), reinterpreted, minus
     0x4338 << 48 -- must be the round-to-nearest-even integer of v * 2^shift (what __float2ll_rn gave) whenever |v * 2^shift| < 2^51.
     The device code is three instructions; this restates its arithmetic in numpy (the product is exact in double: fma = multiply, add)."""
     rng = np.random.default_rng(5)
@@ -361,3 +361,23 @@ def test_fixed_point_conversion_through_the_doubles_mantissa_is_rint():
         want = np.rint(prod[keep]).astype(np.int64)
         assert np.array_equal(bits.view(np.int64), want)
         assert keep.sum() > 200000
+
+
+def _integration_switch_list(heading):
+    """The LS2FM_ names of one of INTEGRATION.md's two lists of the library's switches: the lines from `heading` to the next blank line."""
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    at = text.index(heading)
+    block = text[at:text.find("\n\n", at)]
+    return set(re.findall(r"LS2FM_[A-Z0-9_]+", block))
+
+
+def test_integration_lists_exactly_the_librarys_switches():
+    """Every environment switch the library reads and every build-time switch it tests is listed in INTEGRATION.md, and nothing
+    else is: the lists cannot keep a name the sources dropped, nor miss one they added."""
+    csrc = os.path.join(ROOT, "level-s2fm_official_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    env = set(re.findall(r'getenv\("(LS2FM_[A-Z0-9_]+)"\)', src))
+    build = set(re.findall(r"^\s*#\s*ifn?def\s+(LS2FM_[A-Z0-9_]+)", src, re.M))
+    assert env and build
+    assert _integration_switch_list("Library environment switches") == env
+    assert _integration_switch_list("Library build-time switches") == build
