@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LS2FM_ABI_VERSION 9
+#define LS2FM_ABI_VERSION 10
 #define LS2FM_MAX_LEVELS 16
 #define LS2FM_HIDDEN 64        /* SDF.arch.layers = [null, 64, 16]  (options/LevelS2fM.yaml:14) */
 #define LS2FM_FEAT 16
@@ -181,6 +181,30 @@ int ls2fm_sdf_eval(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, c
 int ls2fm_sdf_volume(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
                      int64_t n_side, int64_t first, int64_t count, int32_t ref_indexing, const double* step,
                      const double* origin, float* sdf, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Marching cubes over a dense volume: the mesh of the level set {v = level}.
+ * Replaces: skimage.measure.marching_cubes as called by convert_sigma_samples_to_ply (utils/util.py:345), reached from
+ *           extract_mesh (util.py:392-425) on the volume of ls2fm_sdf_volume.
+ * vol [nx,ny,nz] fp32, row-major (axis 2 fastest).  Corner values v < level (strict; a NaN is not) are BELOW; an edge
+ * crosses iff exactly one end is below.  Case table generated from one face rule (csrc/mc_tables.h, tools/gen_mc_tables.py):
+ * shared faces get the same segments, so the mesh has no cracks; an ambiguous face cuts each below corner off on its own
+ * (simpler than skimage's Lewiner tables: topology in ambiguous cells may differ).  Triangle normals (right-hand rule) point
+ * to increasing values (outward for an SDF).
+ * verts float [n_verts,3], one per crossing lattice edge, ordered by (lower end's linear index, axis 0 < 1 < 2):
+ *   t = (level - v0) / (v1 - v0),  pos[a] = (idx[a] + (a == axis ? t : 0)) * spacing[a] + origin[a]  (fp32, each op rounded);
+ * faces int32 [n_faces,3] vertex ids, ordered by (cell linear index, table order).  Output is deterministic.
+ * Refused (LS2FM_ERR_INVALID_ARGUMENT, nothing enqueued): any side < 2, or 3 nx ny nz >= 2^31 (vertex ids are int32).
+ * ls2fm_marching_cubes_workspace_bytes: bytes of workspace (~5 per point), or < 0 for refused sizes.
+ * ls2fm_marching_cubes_count: counts int64 [2] (device) = n_verts, n_faces; fills the workspace for the emit call.
+ * ls2fm_marching_cubes_emit: after count, with the same volume, level and workspace; verts / faces hold at least the counted
+ * rows (either may be NULL when its count is 0).  spacing, origin: 3 floats each in HOST memory.
+ */
+int64_t ls2fm_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int ls2fm_marching_cubes_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                               int64_t* counts, void* stream);
+int ls2fm_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, const float* spacing,
+                              const float* origin, void* workspace, float* verts, int32_t* faces, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Point queries WITH a graph: backward of  p -> (sdf, the 17 MLP outputs, the analytic normal d sdf / d p)  for n free points.

@@ -9,6 +9,6 @@ models/base.py, utils/custom_functions.py) so its pipelines can call it unchange
     from ls2fm.models.RadF import RadF
     from ls2fm.models.Renderer import Renderer
 """
-from . import _lib, hashgrid, ops, options  # noqa: F401
+from . import _lib, hashgrid, ops, mesh, options  # noqa: F401
 
-__all__ = ["_lib", "hashgrid", "ops", "options"]
+__all__ = ["_lib", "hashgrid", "ops", "mesh", "options"]

@@ -2,8 +2,9 @@
 
 `extract_mesh` (utils/util.py:392-425) evaluates `implicit_surface.infer_sdf` on an N^3 lattice in 16 k-point chunks
 (host numpy lattice -> device -> host per chunk) and hands the volume to skimage's marching cubes.  Here the sweep is ONE
-device call (`ls2fm_sdf_volume`: the lattice is generated in the kernel, the volume stays in HBM); marching cubes and the
-PLY writer are third-party packages (scikit-image, plyfile) that are used when installed -- they are not part of the path.
+device call (`ls2fm_sdf_volume`: the lattice is generated in the kernel, the volume stays in HBM).  Marching cubes and the
+PLY file come from scikit-image and plyfile when both are installed (the reference's own branch, kept byte for byte), and
+otherwise from the device (`ls2fm.mesh`: ls2fm_marching_cubes_* and a numpy PLY writer of the same layout).
 """
 import numpy as np
 import torch
@@ -52,18 +53,37 @@ def lattice_points(volume_size=2.0, N=512, bound_max=None, bound_min=None, first
 
 
 def extract_mesh(implicit_surface, log=None, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply",
-                 show_progress=True, chunk=16 * 1024, bound_max=None, bound_min=None, extra_info=None):
-    """utils/util.py:392-425.  `chunk` and `show_progress` are accepted and unused (one device call)."""
+                 show_progress=True, chunk=16 * 1024, bound_max=None, bound_min=None, extra_info=None, backend="auto"):
+    """utils/util.py:392-425.  `chunk` and `show_progress` are accepted and unused (one device call).
+    backend: "skimage" = the reference's scikit-image + plyfile branch (ImportError without them); "device" = ls2fm.mesh
+    (marching cubes on the GPU, numpy PLY writer); "auto" = "skimage" when both packages import, else "device".  Both apply
+    the reference's spacing size / N (the lattice step is size / (N - 1)) and origin to the vertices.  Returns the volume."""
+    if backend not in ("auto", "device", "skimage"):
+        raise ValueError(f"extract_mesh: backend must be 'auto', 'device' or 'skimage', got {backend!r}")
     if extra_info is not None:
         raise NotImplementedError("extract_mesh(extra_info=...): residual fields are outside the fused path")
     vol = sdf_volume(implicit_surface, volume_size, N, bound_max, bound_min)
     _, _, origin, sizes = _lattice(volume_size, N, bound_max, bound_min)
+    if backend == "auto":
+        try:
+            import skimage.measure  # noqa: F401
+            import plyfile  # noqa: F401
+            backend = "skimage"
+        except ImportError:
+            backend = "device"
+    if backend == "device":
+        from .. import mesh
+        verts, faces = mesh.marching_cubes(vol, level=level, spacing=[float(v) / N for v in sizes], origin=origin)
+        mesh.write_ply(filepath, verts, faces)
+        if log is not None:
+            log.info("saving mesh to %s" % str(filepath))
+        return vol
     try:
         import skimage.measure
         import plyfile
-    except ImportError as e:          # third-party, not vendored: the volume is the product of this path
-        raise ImportError("extract_mesh needs scikit-image and plyfile for marching cubes / PLY output; "
-                          "ls2fm.utils.util.sdf_volume returns the volume itself") from e
+    except ImportError as e:          # third-party, not vendored
+        raise ImportError("extract_mesh(backend='skimage') needs scikit-image and plyfile for marching cubes / PLY output; "
+                          "backend='device' extracts the mesh on the GPU") from e
     verts, faces, _, _ = skimage.measure.marching_cubes(vol.cpu().numpy(), level=level,
                                                         spacing=[float(v) / N for v in sizes])
     pts = verts + np.asarray(origin, dtype=verts.dtype)[None, :]
