@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Level-S2fM render hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]  (N > 1: launched by torch.distributed.run)
 
 One "step" = one pass of the hot path over one batch of synthetic rays, forward + backward (launched eagerly or as a
 hipGraph replay, see --launch):
@@ -10,7 +10,10 @@ RCCL all-reduce of the gradients.  Workload (BASELINE.json configs[1]): ETH3D bo
 inside = false), 1024 rays x 128 samples per GPU, full L16/F2/T19 hash grids, dual field (SDF + radiance grid),
 synthetic inputs per BASELINE.md section 3.  Weak scaling: every rank renders its own 1024 rays.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: the headline figure of the timed steps (`metric`, `value`, `unit`, `ms_per_step`, ...).  A plain run
+does nothing else: set-up, warm-up (with the --launch auto probe), the K timed steps, --dump-outputs.  --full adds what takes runs
+of its own after the timed steps: the per-kernel `roofline` (the K steps again, eager and profiled), `mirror_upkeep`, for N > 1 the
+compute-only steps of `exchange`, and for N = 1 the `cpu_baseline` leg.
 """
 from __future__ import annotations
 
@@ -208,8 +211,12 @@ def main():
     ap.add_argument("--samples", type=int, default=None)
     ap.add_argument("--dataset", default=None)
     ap.add_argument("--single-field", action="store_true", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # child process of the default run
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-kernel device times and "
+                         "the roofline (the K steps again, eager, profiled), the interleaved table copy's upkeep, N > 1 the "
+                         "compute-only steps, N = 1 the CPU baseline (a child process, up to 150 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # child process of a --full run
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N > 1 code path (process group, gradient all-reduce, barriers) even with one process")
     ap.add_argument("--launch", choices=("auto", "eager", "graph"), default="auto",
@@ -510,9 +517,9 @@ def main():
         dt = float(tb.item())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, outputs, [("sdf", sdf), ("rad", rad)])
-    # N > 1: what the gradient exchange costs, measured outside the timed region -- the same K steps WITHOUT exchange and update
-    # (compute only), so that a scaling run records exposed exchange time next to the bytes it moves.  Not
-    # for the level-group overlap, whose reductions are issued from inside the backward.
+    # N > 1: what the gradient exchange is and moves; with --full also what it costs, measured outside the timed region -- the same
+    # K steps WITHOUT exchange and update (compute only), so that a scaling run records exposed exchange time next to the bytes it
+    # moves.  Not for the level-group overlap, whose reductions are issued from inside the backward.
     exchange = None
     if multi and not args.inference:
         flat_bytes = 4 * sum((p.numel() + 3) // 4 * 4 for p in params)
@@ -525,7 +532,8 @@ def main():
                 exchange["form"] = (f"all-reduce inside the captured step, {args.overlap_groups} level groups on a second branch of the graph "
                                     "(beside the scatter of the later groups)" if args.capture_overlap and not args.no_overlap else
                                     "all-reduce of the flat gradient buffer inside the captured step")
-        # compute only = the same K steps of fwd + bwd with NO exchange and no update, launched eagerly, on EVERY N > 1 line
+    if exchange is not None and args.full:
+        # compute only = the same K steps of fwd + bwd with NO exchange and no update, launched eagerly, on EVERY N > 1 --full line
         # (the first real scaling run separates exchange from compute whatever form it times).  The level-group
         # reductions a backward would launch itself are switched off for these steps.
         tabs = [p for p in params if hasattr(p, "_ls2fm_overlap_groups")]
@@ -560,18 +568,19 @@ def main():
         exchange["compute_only_ms_per_step"] = float(t_compute.item()) * 1e3
         exchange["compute_only_launch"] = "eager" if compute_step is render_step else "hipGraph replay"
         exchange["exchange_and_update_ms_per_step"] = dt / args.steps * 1e3 - exchange["compute_only_ms_per_step"]
-    # per-kernel device times (roofline): the same K steps launched eagerly with the library's HIP-event profiler on
+    # per-kernel device times (roofline, --full): the same K steps launched eagerly with the library's HIP-event profiler on
     # (events cannot be read back from inside a graph replay); also gives the eager step time
-    lib.ls2fm_profile_reset()
-    lib.ls2fm_profile_enable(1)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(eager=True)
-    barrier()
-    dt_eager = time.perf_counter() - t1
-    lib.ls2fm_profile_enable(0)
-    has_prof = True
+    has_prof = args.full
+    if has_prof:
+        lib.ls2fm_profile_reset()
+        lib.ls2fm_profile_enable(1)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(eager=True)
+        barrier()
+        dt_eager = time.perf_counter() - t1
+        lib.ls2fm_profile_enable(0)
 
     ms_per_step = dt / args.steps * 1e3
     value = args.rays * world * args.steps / dt
@@ -619,30 +628,31 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "launch": ("hipGraph replay of the whole step" if use_graph else "eager") + (" (auto)" if mode == "auto" else ""),
-        "eager_profiled_ms_per_step": dt_eager / args.steps * 1e3,
         "launch_probe": launch_probe,           # untimed probe of both launch forms (auto mode): eager and hipGraph ms/step
         "config": {"workload": f"{args.config}: {args.dataset} bounds, {args.rays} rays x {args.samples} samples per GPU, "
                                f"{'dual' if dual else 'single'} field, L16/F2/T19 hash grid, fwd+loss+bwd"
                                + ((", RCCL reduce-scatter + sharded Adam + all-gather" if shard else ", RCCL grad all-reduce") if multi else ""),
                    "rays_per_gpu": args.rays, "samples_per_ray": args.samples, "dual_field": dual,
                    "parallelism": f"dp{world} (rays sharded by view)"},
-        "roofline": roofline,
         "host_numa_node": numa_node,         # the GPU's NUMA node this process was bound to before the runtime started (None: not bound)
     }
+    if has_prof:
+        out["eager_profiled_ms_per_step"] = dt_eager / args.steps * 1e3
+        out["roofline"] = roofline
     if exchange is not None:
         out["exchange"] = exchange
     # is an optimizer update part of the timed step?  (N > 1 with the sharded exchange: yes; N = 1: only with --with-update --
     # compare a scaling curve's points like for like)
     out["update_in_step"] = bool(shard or local_opt is not None)
-    if dual and not multi and not args.inference:
+    if args.full and dual and not multi and not args.inference:
         # The dual-field render reads the ENTRY-INTERLEAVED copy of the two tables, which FusedAdam keeps current inside its own
         # pass.  The default line times fwd + bwd only, so that upkeep is outside the timed region (with --with-update it is
-        # inside); its cost is measured here, after the timed region: the paired Adam job that also writes the copy against the
+        # inside); --full measures its cost here, after the timed region: the paired Adam job that also writes the copy against the
         # two plain jobs (learning rate 0: the weights do not move).
         out["mirror_upkeep"] = {"in_timed_region": local_opt is not None, "adam_pair_extra_us": mirror_upkeep_us(sdf, rad, dev)}
         # the training-relevant figure one field away: a step of a training loop also pays the copy's upkeep (in its optimizer pass)
         out["ms_per_step_incl_mirror_upkeep"] = ms_per_step + (0.0 if local_opt is not None else out["mirror_upkeep"]["adam_pair_extra_us"] * 1e-3)
-    if rank == 0:
+    if args.full and rank == 0:
         out["cpu_baseline"] = None
         if world == 1 and not args.no_cpu_baseline:
             # the CPU leg runs in a fresh process (clean OpenMP state, no GPU context) under a hard wall-clock bound, so a

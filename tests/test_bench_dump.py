@@ -49,6 +49,7 @@ def test_bench_dump_outputs_eager_equals_graph(tmp_path):
         assert out.returncode == 0, out.stderr[-2000:]
         line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
         assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert not {"roofline", "eager_profiled_ms_per_step", "mirror_upkeep", "cpu_baseline"} & set(line)    # --full only
         arrays = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
         assert {"rgb", "normals", "depth_mlp", "loss.all"} <= set(arrays)
         assert any(k.startswith("grad.sdf.") for k in arrays) and any(k.startswith("grad.rad.") for k in arrays)

@@ -45,22 +45,24 @@ def test_bench_two_ranks_one_gpu(extra):
 def test_bench_one_rank_rccl_default_form_is_the_metrics_step():
     """`--force-dist` (one-rank RCCL group: the collectives are identities, everything else is real): the default N > 1 form is
     fwd + bwd + all-reduce of the flat gradient buffer, launched like the N = 1 line -- also as ONE hipGraph replay with the
-    RCCL all-reduce recorded in it -- and carries no optimizer update"""
+    RCCL all-reduce recorded in it -- and carries no optimizer update; --full adds the compute-only steps beside it"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LS2FM_DIST_SINGLE="1", MASTER_PORT=str(_free_port()))
-    for launch in ("eager", "graph"):
+    for launch, full in (("eager", []), ("graph", []), ("graph", ["--full"])):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "2",
-                              "--rays", "256", "--samples", "32", "--no-cpu-baseline", "--launch", launch],
+                              "--rays", "256", "--samples", "32", "--no-cpu-baseline", "--launch", launch] + full,
                              cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
         assert d["update_in_step"] is False and "all-reduce" in d["exchange"]["form"]
         assert d["launch"].startswith("hipGraph" if launch == "graph" else "eager")
+        assert ("compute_only_ms_per_step" in d["exchange"]) == bool(full)
 
 
 def test_bench_c1_and_inference_lines():
-    """--config C1 (BASELINE.json configs[0] at its own shape) and the forward-only line: one JSON line each"""
+    """--config C1 (BASELINE.json configs[0] at its own shape) and the forward-only line: one JSON line each, with the roofline
+    of --full"""
     for extra, metric in ((["--config", "C1"], "rendered rays/sec (fwd+bwd)"), (["--inference", "--rays", "512", "--samples", "32"], "rendered rays/sec (forward only, no_grad)")):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline",
                               "--launch", "eager"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -10,7 +10,7 @@ for i in $(seq $N); do
   for v in "$@"; do
     LIB=""; ENVS=""
     for w in $v; do case $w in cur) ;; *.so) LIB=$ROOT/$w ;; *) ENVS="$ENVS $w" ;; esac; done
-    env ${LIB:+LS2FM_LIB=$LIB} $ENVS python bench.py --no-cpu-baseline --steps 300 --warmup 30 $ARGS 2>/dev/null | tail -1 | python -c "
+    env ${LIB:+LS2FM_LIB=$LIB} $ENVS python bench.py --full --no-cpu-baseline --steps 300 --warmup 30 $ARGS 2>/dev/null | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['roofline']['all_kernels_avg_us']

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""profiles/<tag>_pmc_traffic.json from the two PMC summaries tools/collect_round.sh leaves in gpurun_out/
-   (tools/pmc_summary.py output of the FETCH_SIZE and the WRITE_SIZE pass):   python tools/pmc_to_json.py r02 <git hash>"""
-import json, re, sys
+"""profiles/<tag>_pmc_traffic.json from the two PMC summaries tools/collect_round.sh leaves in its output directory
+   (tools/pmc_summary.py output of the FETCH_SIZE and the WRITE_SIZE pass):   python tools/pmc_to_json.py r02 <git hash> [<dir>]"""
+import json, os, re, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 commit = sys.argv[2] if len(sys.argv) > 2 else "unknown"
+src = sys.argv[3] if len(sys.argv) > 3 else "."
 SHORT = [("ray_encode", "ray_encode_pair"), ("slab_accumulate", "slab_accumulate"), ("slab_combine", "slab_combine"), ("scatter_fill", "scatter_fill"),
          ("shade_bwd", "shade_bwd"), ("shade_fwd", "shade_fwd"), ("wgrad_mlp_kernelILb0", "wgrad_mlp_sdf"),
          ("wgrad_mlp_kernelILb1", "wgrad_mlp_geo"), ("wgrad_mlp_kernel<false", "wgrad_mlp_sdf"), ("wgrad_mlp_kernel<true", "wgrad_mlp_geo"),
@@ -24,8 +25,8 @@ def read(path, counter):
     return out
 
 
-fetch = read(f"gpurun_out/{tag}_pmc_fetch.txt", "FETCH_SIZE")
-write = read(f"gpurun_out/{tag}_pmc_write.txt", "WRITE_SIZE")
+fetch = read(os.path.join(src, f"{tag}_pmc_fetch.txt"), "FETCH_SIZE")
+write = read(os.path.join(src, f"{tag}_pmc_write.txt"), "WRITE_SIZE")
 doc = {"_about": "HBM-side bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two separate passes with --kernel-trace "
                  "only, LS2FM_SERIAL=1, bench.py default workload C2), counter KB * 1024.  `fetch_raw` is the RAW counter; `fetch` "
                  "applies the guide's gfx950 correction for wide coalesced streaming reads (FETCH_SIZE reports half: "
