@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LS2FM_ABI_VERSION 10
+#define LS2FM_ABI_VERSION 11
 #define LS2FM_MAX_LEVELS 16
 #define LS2FM_HIDDEN 64        /* SDF.arch.layers = [null, 64, 16]  (options/LevelS2fM.yaml:14) */
 #define LS2FM_FEAT 16
@@ -462,13 +462,14 @@ int ls2fm_loss_terms_from_sums(const double* sums, const float* weights, float* 
 /* ---------------------------------------------------------------------------------------------
  * Fused Adam step over a list of fp32 tensors, one launch, one pass over memory.
  * Replaces: torch.optim.Adam.step() of the stage loops (Initialization.py:149-179, BA.py:117-182; amsgrad = False,
- * maximize = False), operation by operation:  g' = g + wd p;  m = lerp(m, g', 1 - beta1);
- * v = v beta2 + (1 - beta2) g' g';  p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps).
+ * maximize = False):  g' = g + wd p;  m = lerp(m, g', 1 - beta1);  v = v beta2 + ((1 - beta2) g') g';
+ * p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  lr, beta1 and beta2 are doubles (ABI 11), like torch's
+ * hyper-parameters: 1 - beta, beta^step, lr / bc1 and sqrt(bc2) are formed in double and each is rounded to fp32 once.
  * params / grads / exp_avg / exp_avg_sq: HOST arrays of n_tensors device pointers; numel: HOST array; step >= 1 is the
  * count AFTER this update (torch increments before use).  Updates params, exp_avg, exp_avg_sq in place.
  */
 int ls2fm_adam_step(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                    float* const* exp_avg_sq, const int64_t* numel, float lr, float beta1, float beta2, float eps,
+                    float* const* exp_avg_sq, const int64_t* numel, double lr, double beta1, double beta2, float eps,
                     float weight_decay, int64_t step, void* stream);
 
 /* The same update with the schedule RESIDENT ON THE DEVICE, for optimisation steps captured into a hipGraph (a replay cannot
@@ -479,7 +480,7 @@ int ls2fm_adam_step(int32_t n_tensors, float* const* params, const float* const*
  * in a one-thread kernel, then runs the update with those values.  Replaces torch.optim.Adam.step() + ExponentialLR.step().
  */
 int ls2fm_adam_step_scheduled(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                              float* const* exp_avg_sq, const int64_t* numel, void* sched_state, float beta1, float beta2,
+                              float* const* exp_avg_sq, const int64_t* numel, void* sched_state, double beta1, double beta2,
                               float eps, float weight_decay, void* stream);
 
 /* Either update above with a MIRROR list: mirrors[t] (HOST array of n_tensors device pointers, entries may be NULL; NULL array =
@@ -491,11 +492,11 @@ int ls2fm_adam_step_scheduled(int32_t n_tensors, float* const* params, const flo
  * form (lr and step ignored).  No reference counterpart: the reference's tcnn grids are separate.
  */
 int ls2fm_adam_step_mirrored(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                             float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, void* sched_state, float lr,
-                             float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
+                             float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, void* sched_state, double lr,
+                             double beta1, double beta2, float eps, float weight_decay, int64_t step, void* stream);
 
 /* The general form (the three above are special cases of it): every parameter GROUP of an optimizer in one call.  Per tensor t a
- * learning rate lrs[t] (HOST float array; with `step`, the unscheduled form) or a device-resident schedule sched_states[t] (HOST
+ * learning rate lrs[t] (HOST double array; with `step`, the unscheduled form) or a device-resident schedule sched_states[t] (HOST
  * array of DEVICE pointers, entries or the whole array may be NULL; every distinct schedule is advanced once per call);
  * mirrors as above or NULL.  Two tensors whose mirrors are the two halves of one interleaved copy (M and M + 2, equal length,
  * 16-byte aligned) -- the SDF table and the second field's table -- are updated by ONE job that also writes the copy as whole
@@ -503,8 +504,8 @@ int ls2fm_adam_step_mirrored(int32_t n_tensors, float* const* params, const floa
  * over `[{sdf_func.parameters(), lr_sdf}, {color_func.parameters(), lr_color}]` (BA.py:79-83) + ExponentialLR.step().
  */
 int ls2fm_adam_step_multi(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                          float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, const float* lrs,
-                          void* const* sched_states, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                          float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, const double* lrs,
+                          void* const* sched_states, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                           void* stream);
 
 /* ExponentialLR.step() for parameter groups that took NO Adam step this iteration (every tensor's grad is None): the device

@@ -1,9 +1,15 @@
 // Fused Adam step over a list of fp32 tensors (the stage loops update two 12 M-entry hash
 // tables and 26 small tensors with torch.optim.Adam: Initialization.py:149-179, BA.py:117-182).  One launch for the whole
 // list, one pass over memory: 16 B read + 12 B written per element (p, g, m, v -> p, m, v), HBM-bound.
-// Arithmetic follows torch.optim.Adam (amsgrad = False, maximize = False), operation by operation:
-//   g' = g + wd p ; m = lerp(m, g', 1 - b1) ; v = v b2 + (1 - b2) g' g' ;
+// Arithmetic follows torch.optim.Adam (amsgrad = False, maximize = False):
+//   g' = g + wd p ; m = lerp(m, g', 1 - b1) ; v = v b2 + ((1 - b2) g') g' ;
 //   p = p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// The scalars are formed as torch forms them from its Python doubles: lr, b1 and b2 arrive as doubles; 1 - b, b^t, lr / bc1 and
+// sqrt(bc2) are evaluated in double, and each is rounded to fp32 once.  (Rounding b2 to fp32 before forming 1 - b2 makes the
+// second moment's new-gradient weight 9.99987e-4 instead of 1e-3 at b2 = 0.999.)  The element arithmetic is fp32 and differs
+// from torch's only in rounding: weight decay is one fmaf, and (1 - b2) g' g' is multiplied in torch's order, so a g'^2 above
+// fp32's range does not overflow where the weighted term fits.  tests/test_hip_fused_adam.py holds every launch form to a
+// float64 Adam element by element.
 #include "ls2fm_device.h"
 
 namespace {
@@ -36,7 +42,7 @@ struct AdamHyper { float step_size, bc2_sqrt, w1, beta2, one_minus_beta2, eps, w
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
     if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
     m = h.w1 < 0.5f ? m + h.w1 * (g - m) : g - (g - m) * (1.0f - h.w1);       // torch lerp
-    v = v * h.beta2 + h.one_minus_beta2 * (g * g);
+    v = v * h.beta2 + (h.one_minus_beta2 * g) * g;
     const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
     p = p - h.step_size * (m / denom);
 }
@@ -161,19 +167,27 @@ adam_pair_kernel(AdamPair q, AdamHyper h) {
 // sched_states[t] -- each distinct schedule is advanced once), optional mirrors.  Two tensors whose mirrors are the two halves
 // of one interleaved copy (base and base + 2, same length) are updated by ONE paired job.
 extern "C" int ls2fm_adam_step_multi(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                                     float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, const float* lrs,
-                                     void* const* sched_states, float beta1, float beta2, float eps, float weight_decay,
+                                     float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, const double* lrs,
+                                     void* const* sched_states, double beta1, double beta2, float eps, float weight_decay,
                                      int64_t step, void* stream_) {
-    LS2FM_CHECK_ARG(n_tensors >= 0 && (n_tensors == 0 || (params && grads && exp_avg && exp_avg_sq && numel && (lrs || sched_states))));
-    LS2FM_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f);
+    LS2FM_CHECK_ARG(n_tensors >= 0 && n_tensors <= 4096);
+    LS2FM_CHECK_ARG(n_tensors == 0 || (params && grads && exp_avg && exp_avg_sq && numel && (lrs || sched_states)));
+    LS2FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
     static_assert(sizeof(AdamSched) == 32, "sched_state is 32 bytes {double step, lr, gamma; float[2]}");
+    // every argument is checked before anything is launched: a refused call leaves parameters and schedules as they were
+    for (int32_t t = 0; t < n_tensors; ++t) {
+        if (!(sched_states && sched_states[t])) LS2FM_CHECK_ARG(lrs && step >= 1);
+        if (numel[t] <= 0) continue;
+        LS2FM_CHECK_ARG(params[t] && grads[t] && exp_avg[t] && exp_avg_sq[t]);
+        if (mirrors && mirrors[t]) LS2FM_CHECK_ARG((reinterpret_cast<uintptr_t>(mirrors[t]) & 7u) == 0 && numel[t] % 2 == 0);
+    }
     hipStream_t stream = (hipStream_t)stream_;
     AdamHyper h;
     h.step_size = 0.f;
     h.bc2_sqrt = 1.f;
-    h.w1 = (float)(1.0 - (double)beta1);
-    h.beta2 = beta2;
-    h.one_minus_beta2 = (float)(1.0 - (double)beta2);
+    h.w1 = (float)(1.0 - beta1);
+    h.beta2 = (float)beta2;
+    h.one_minus_beta2 = (float)(1.0 - beta2);
     h.eps = eps;
     h.weight_decay = weight_decay;
     // every distinct device schedule advances once
@@ -181,25 +195,23 @@ extern "C" int ls2fm_adam_step_multi(int32_t n_tensors, float* const* params, co
     adv.count = 0;
     for (int32_t t = 0; t < n_tensors; ++t) {
         void* st = sched_states ? sched_states[t] : nullptr;
-        if (!st) { LS2FM_CHECK_ARG(lrs && step >= 1); continue; }
+        if (!st) continue;
         bool seen = false;
         for (int q = 0; q < adv.count; ++q) seen = seen || (adv.st[q] == (AdamSched*)st);
         if (seen) continue;
-        if (adv.count == 16) { adam_advance_kernel<<<1, 16, 0, stream>>>(adv, (double)beta1, (double)beta2); adv.count = 0; }
+        if (adv.count == 16) { adam_advance_kernel<<<1, 16, 0, stream>>>(adv, beta1, beta2); adv.count = 0; }
         adv.st[adv.count++] = (AdamSched*)st;
     }
-    if (adv.count) adam_advance_kernel<<<1, 16, 0, stream>>>(adv, (double)beta1, (double)beta2);
-    const double bc1 = step >= 1 ? 1.0 - pow((double)beta1, (double)step) : 1.0, bc2 = step >= 1 ? 1.0 - pow((double)beta2, (double)step) : 1.0;
-    auto host_step = [&](int32_t t) { return (sched_states && sched_states[t]) ? 0.f : (float)((double)lrs[t] / bc1); };
+    if (adv.count) adam_advance_kernel<<<1, 16, 0, stream>>>(adv, beta1, beta2);
+    const double bc1 = step >= 1 ? 1.0 - pow(beta1, (double)step) : 1.0, bc2 = step >= 1 ? 1.0 - pow(beta2, (double)step) : 1.0;
+    auto host_step = [&](int32_t t) { return (sched_states && sched_states[t]) ? 0.f : (float)(lrs[t] / bc1); };
     const float host_bc2 = (float)sqrt(bc2);
     bool done[4096];
-    LS2FM_CHECK_ARG(n_tensors <= 4096);
     for (int32_t t = 0; t < n_tensors; ++t) done[t] = numel[t] <= 0;
     // paired tables
     if (mirrors)
         for (int32_t t = 0; t < n_tensors; ++t) {
             if (done[t] || !mirrors[t]) continue;
-            LS2FM_CHECK_ARG((reinterpret_cast<uintptr_t>(mirrors[t]) & 7u) == 0 && numel[t] % 2 == 0);
             for (int32_t u = 0; u < n_tensors; ++u) {
                 if (u == t || done[u] || !mirrors[u] || numel[u] != numel[t] || mirrors[u] != mirrors[t] + 2) continue;
                 const uintptr_t all = reinterpret_cast<uintptr_t>(params[t]) | reinterpret_cast<uintptr_t>(params[u]) |
@@ -226,7 +238,6 @@ extern "C" int ls2fm_adam_step_multi(int32_t n_tensors, float* const* params, co
         int blocks = 0;
         for (; t < n_tensors && jobs.count < kAdamMaxTensors; ++t) {
             if (done[t]) continue;
-            LS2FM_CHECK_ARG(params[t] && grads[t] && exp_avg[t] && exp_avg_sq[t]);
             const int j = jobs.count++;
             jobs.p[j] = params[t]; jobs.g[j] = grads[t]; jobs.m[j] = exp_avg[t]; jobs.v[j] = exp_avg_sq[t]; jobs.n[j] = numel[t];
             jobs.mirror[j] = mirrors ? mirrors[t] : nullptr;
@@ -259,11 +270,11 @@ extern "C" int ls2fm_adam_sched_decay(int32_t n, void* const* sched_states, void
 }
 
 namespace {
-struct PtrList { void* v[4096]; float lr[4096]; };
+struct PtrList { void* v[4096]; double lr[4096]; };
 }
 
 extern "C" int ls2fm_adam_step(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                               float* const* exp_avg_sq, const int64_t* numel, float lr, float beta1, float beta2, float eps,
+                               float* const* exp_avg_sq, const int64_t* numel, double lr, double beta1, double beta2, float eps,
                                float weight_decay, int64_t step, void* stream) {
     LS2FM_CHECK_ARG(n_tensors >= 0 && n_tensors <= 4096 && step >= 1);
     static thread_local PtrList pl;
@@ -273,8 +284,8 @@ extern "C" int ls2fm_adam_step(int32_t n_tensors, float* const* params, const fl
 }
 
 extern "C" int ls2fm_adam_step_scheduled(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                                         float* const* exp_avg_sq, const int64_t* numel, void* sched_state, float beta1,
-                                         float beta2, float eps, float weight_decay, void* stream) {
+                                         float* const* exp_avg_sq, const int64_t* numel, void* sched_state, double beta1,
+                                         double beta2, float eps, float weight_decay, void* stream) {
     LS2FM_CHECK_ARG(n_tensors >= 0 && n_tensors <= 4096 && sched_state);
     static thread_local PtrList pl;
     for (int32_t t = 0; t < n_tensors; ++t) pl.v[t] = sched_state;
@@ -284,7 +295,7 @@ extern "C" int ls2fm_adam_step_scheduled(int32_t n_tensors, float* const* params
 
 extern "C" int ls2fm_adam_step_mirrored(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                                         float* const* exp_avg_sq, const int64_t* numel, float* const* mirrors, void* sched_state,
-                                        float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                        double lr, double beta1, double beta2, float eps, float weight_decay, int64_t step,
                                         void* stream) {
     LS2FM_CHECK_ARG(n_tensors >= 0 && n_tensors <= 4096 && (sched_state || step >= 1));
     static thread_local PtrList pl;

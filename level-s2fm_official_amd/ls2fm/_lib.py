@@ -8,14 +8,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
 
 import torch
 
 MAX_LEVELS = 16
 HIDDEN = 64
 FEAT = 16
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_RENDER_POINTS = 1 << 23     # LS2FM_MAX_RENDER_POINTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -146,10 +146,11 @@ _SIGNATURES = {
     "ls2fm_loss_head_fwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P]),
     "ls2fm_loss_head_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
                                       _P]),
-    "ls2fm_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
-    "ls2fm_adam_step_scheduled": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, _P]),
-    "ls2fm_adam_step_mirrored": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
-    "ls2fm_adam_step_multi": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int64, _P]),
+    "ls2fm_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_float, c_float, c_int64, _P]),
+    "ls2fm_adam_step_scheduled": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, c_double, c_double, c_float, c_float, _P]),
+    "ls2fm_adam_step_mirrored": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_float, c_float, c_int64,
+                                           _P]),
+    "ls2fm_adam_step_multi": (c_int32, [c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_float, c_float, c_int64, _P]),
     "ls2fm_adam_sched_decay": (c_int32, [c_int32, _P, _P]),
     "ls2fm_camera_rays": (c_int32, [_P, _P, POINTER(c_float), _P, _P, c_int32, c_int32, _P, c_int32, c_int64, _P, _P, _P, _P]),
     "ls2fm_se3_exp_fwd": (c_int32, [_P, c_int32, _P, _P]),

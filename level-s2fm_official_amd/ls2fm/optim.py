@@ -85,7 +85,7 @@ class FusedAdam(torch.optim.Optimizer):
                 n, ptrs([it[0] for it in items]), ptrs([it[1] for it in items]), ptrs([it[2]["exp_avg"] for it in items]),
                 ptrs([it[2]["exp_avg_sq"] for it in items]), (ctypes.c_int64 * n)(*[it[0].numel() for it in items]),
                 (ctypes.c_void_p * n)(*[m[1] for m in mirrors]) if any_mirror else None,
-                (ctypes.c_float * n)(*[it[3] for it in items]),
+                (ctypes.c_double * n)(*[it[3] for it in items]),
                 (ctypes.c_void_p * n)(*[None if it[4] is None else it[4].data_ptr() for it in items]) if step is None else None,
                 b1, b2, eps, wd, 0 if step is None else step, _lib.stream_ptr()), "ls2fm_adam_step_multi")
             for (p, _, _, _, _), (rec, _) in zip(items, mirrors):
