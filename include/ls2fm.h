@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LS2FM_ABI_VERSION 11
+#define LS2FM_ABI_VERSION 12
 #define LS2FM_MAX_LEVELS 16
 #define LS2FM_HIDDEN 64        /* SDF.arch.layers = [null, 64, 16]  (options/LevelS2fM.yaml:14) */
 #define LS2FM_FEAT 16
@@ -353,6 +353,29 @@ int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf_g
                      const float* d_normals, const float* d_depth_mlp, const float* d_normal_mlp,
                      const ls2fm_param_grads* grads, float* d_center, float* d_ray, void* workspace,
                      const ls2fm_render_opts* opts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Forward-only rendering of whole images (new, ABI 12).
+ * Replaces: Camera.render_img_by_slices (pipelines/Camera.py:274-311): get_center_and_ray for every pixel, then Renderer.forward
+ * over rand_rays slices and a concatenation.
+ * Every pixel's outputs are, bit for bit, what ls2fm_render_fwd returns for its ray -- the ray ls2fm_camera_rays forms for
+ * poses and pix = 0 .. H*W-1 with width W (centres x + 0.5, y + 0.5):
+ *   rgb [n_views,H*W,3] (background added), depth [n_views,H*W] (depth_mlp), normal [n_views,H*W,3] (normal_mlp),
+ *   opacity [n_views,H*W] or NULL (the sum of the composite's weights, prob.sum: Renderer.py:89-107).  Row-major pixels.
+ * poses [n_views,3,4] world-to-camera (DEVICE: read at run time, so a captured call follows poses updated in place);
+ * kinv_host: the 3 x 3 K^-1 as 9 HOST floats (as ls2fm_camera_rays).
+ * workspace: ls2fm_render_image_workspace_bytes(...) bytes: it depends on the field and the grids only, one call renders any
+ * image size and any number of views (the rays are walked in chunks inside; LS2FM_MAX_RENDER_POINTS does not apply).  No
+ * allocation, no host synchronisation, no stream fork: capturable.
+ * Refusals (before any device work): LS2FM_ERR_UNSUPPORTED for bg_sdf, dual grids of different geometry and more than 512
+ * samples per ray; LS2FM_ERR_INVALID_ARGUMENT for null inputs / outputs or non-positive sizes; LS2FM_ERR_WORKSPACE for a null
+ * workspace.  No gradients (the reference renders images under no_grad).
+ */
+int64_t ls2fm_render_image_workspace_bytes(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf_grid,
+                                           const ls2fm_grid_desc* rad_grid);
+int ls2fm_render_image(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf_grid, const ls2fm_grid_desc* rad_grid,
+                       const ls2fm_params* params, const float* poses, int32_t n_views, const float* kinv_host, int32_t height,
+                       int32_t width, float* rgb, float* depth, float* normal, float* opacity, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Bidirectional sphere tracing, the no-grad root-find loop.

@@ -12,18 +12,12 @@
 //     theta = sqrt(w0^2 + w1^2 + w2^2) ;  A, B, C = 11-term series  sum_i (-1)^i theta^(2i) / d_i  (left to right)
 //     W = skew(w) ; W2 = W W ;  R = (I + A W) + B W2 ;  V = (I + B W) + C W2 ;  t = V u                 (se3_to_SE3)
 //     in_cam = [x, y, 1] K^-T ;  c2w = [R^T | -(R^T t)] ;  center = c2w[:, 3] ;  ray = ([in_cam, 1] c2w^T) - center
-#include "ls2fm_device.h"
+#include "camera_ray.h"
 
 namespace {
 
 constexpr int kCrThreads = 256;
 constexpr int kTerms = 11;
-
-struct Kinv { float k[9]; };
-
-__device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
-    return fmaf(a2, b2, fmaf(a1, b1, a0 * b0));
-}
 
 // The three 11-term series A, B, C (and their term-by-term derivatives) of one view, by ONE WAVE: lane 11 s + i forms term i of
 // series s -- 33 powf calls side by side instead of one after the other in a single lane (15 us per call of the exponential, in

@@ -609,6 +609,42 @@ int ls2fm_launch_points_encode(const ls2fm_field_desc* field, const ls2fm_grid_d
         ws + w.e1, nullptr, ws + w.j1, ex);
     return ls2fm_launch_status();
 }
+// Gather pass of the image render (render_image.hip) over one chunk of its rays: the training forward's kernel and arguments,
+// without the scatter's item counts.  `packed` non-null: the weight prep rides in the leading workgroups (a call's first chunk).
+int ls2fm_launch_image_encode(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf_grid, const ls2fm_grid_desc* rad_grid,
+                              const ls2fm_params* params, const float* center, const float* ray, int64_t n_points, int64_t p_pad,
+                              float* e1, float* e2, float* j1, Packed* packed, hipStream_t s) {
+    const FieldC fc = make_field_c(field);
+    const int dual = field->dual_field ? 1 : 0;
+    const int L1 = sdf_grid->n_levels, L2 = dual ? rad_grid->n_levels : 0;
+    const int n_chunks = (int)((n_points + kEncThreads - 1) / kEncThreads);
+    const bool interleaved = dual && params->dual_table;
+    const bool pair = dual && !interleaved;
+    int most = 0;
+    const XcdPlan plan = make_xcd_plan(sdf_grid, L1, pair ? rad_grid : nullptr, pair ? L2 : 0, field->n_samples, n_chunks, false, &most,
+                                       interleaved);
+    EncodeExtras ex;
+    ex.params = *params;
+    ex.in_dim = 3 + 2 * L1; ex.in_dim2 = 3 + 2 * L2; ex.rad_in = 3 + 3 + kView + LS2FM_FEAT * (dual ? 2 : 1); ex.dual = dual;
+    ex.packed = packed;
+    ex.tile_counts = nullptr; ex.scan_ticket = nullptr; ex.n_tiles = 0; ex.sshift = ls2fm_slab_shift(dual);
+    ex.n_explicit = 0;
+    ex.n_prep_tasks = 3; ex.pts = nullptr;
+    const unsigned enc_blocks = (unsigned)(kEncReserved + 8 * most);
+    const int enc_span = dual ? LS2FM_PROF_ENCODE_PAIR : LS2FM_PROF_ENCODE_SDF;
+    ls2fm_prof_begin(enc_span, s);
+    if (interleaved)
+        ray_encode_kernel<true><<<enc_blocks, kEncThreads, 0, s>>>(
+            make_level_set(sdf_grid), make_level_set(sdf_grid), fc, center, ray, params->dual_table, nullptr, n_points, p_pad, n_chunks,
+            plan, e1, e2, j1, ex);
+    else
+        ray_encode_kernel<false><<<enc_blocks, kEncThreads, 0, s>>>(
+            make_level_set(sdf_grid), make_level_set(pair ? rad_grid : sdf_grid), fc, center, ray, params->sdf_table,
+            pair ? params->rad_table : nullptr, n_points, p_pad, n_chunks, plan, e1, pair ? e2 : nullptr, j1, ex);
+    ls2fm_prof_end(enc_span, s);
+    return ls2fm_launch_status();
+}
+
 int ls2fm_launch_post_shade(const ls2fm_loss_spec* loss, const float* ray_part, int64_t n_rays, int n_samples,
                             const ls2fm_grid_desc* scan_grid, int64_t n_points, float* bins_ws, hipStream_t stream);
 

@@ -15,7 +15,7 @@ import torch
 MAX_LEVELS = 16
 HIDDEN = 64
 FEAT = 16
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_RENDER_POINTS = 1 << 23     # LS2FM_MAX_RENDER_POINTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -129,6 +129,9 @@ _SIGNATURES = {
                                    c_int64, _P, _P, _P, _P, _P, _P, POINTER(RenderOpts), _P]),
     "ls2fm_render_bwd": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc), POINTER(Params), _P, _P,
                                    c_int64, _P, _P, _P, _P, _P, POINTER(ParamGrads), _P, _P, _P, POINTER(RenderOpts), _P]),
+    "ls2fm_render_image_workspace_bytes": (c_int64, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc)]),
+    "ls2fm_render_image": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc), POINTER(Params), _P, c_int32,
+                                     POINTER(c_float), c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "ls2fm_loss_terms_from_sums": (c_int32, [_P, _P, _P, _P]),
     "ls2fm_sphere_trace": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(Params), _P, _P, c_int64,
                                      c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -433,6 +433,24 @@ def _uniform_count_scale(fl) -> int:
     return 0
 
 
+def bind_params(lib, plan, ps):
+    """point the plan's ls2fm_params at the Parameters `ps` (= plan.ts) and make the dual field's interleaved table current"""
+    _, _, _, dual, beta_speed, _ = plan.cfg
+    pkey = tuple([p.data_ptr() for p in ps])
+    if plan.pkey != pkey:                   # pointers only change when a module is re-created / moved
+        for p in ps:
+            if not (p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda):
+                raise RuntimeError("ls2fm: fused render needs contiguous fp32 GPU parameters")
+        plan.pstruct = _params_struct(ps, dual, beta_speed)
+        plan.pkey = pkey
+        plan.dual_key = None
+    if dual and _DUAL_TABLE != "off":
+        _refresh_dual_table(lib, plan, ps[0], ps[_RAD_TABLE_AT])
+    elif plan.pstruct.dual_table:
+        plan.pstruct.dual_table = None      # mode switched off after use: gather from the two tables again
+        plan.dual_key = None
+
+
 class _Render(torch.autograd.Function):
     """Renderer.forward (and, with a FusedLoss, the loss head of the stage loops inside it) as ONE autograd node.
     outputs: rgb, sdfs_volume, normals, depth_mlp, normal_mlp [, terms (5), total]"""
@@ -449,19 +467,7 @@ class _Render(torch.autograd.Function):
         c = center.detach().reshape(-1, 3).float().contiguous()
         d = ray.detach().reshape(-1, 3).float().contiguous()
         ps = params                             # nn.Parameters: contiguous fp32 by construction (checked in the plan key)
-        pkey = tuple([p.data_ptr() for p in ps])
-        if plan.pkey != pkey:                   # pointers only change when a module is re-created / moved
-            for p in ps:
-                if not (p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda):
-                    raise RuntimeError("ls2fm: fused render needs contiguous fp32 GPU parameters")
-            plan.pstruct = _params_struct(ps, dual, beta_speed)
-            plan.pkey = pkey
-            plan.dual_key = None
-        if dual and _DUAL_TABLE != "off":
-            _refresh_dual_table(lib, plan, ps[0], ps[_RAD_TABLE_AT])
-        elif plan.pstruct.dual_table:
-            plan.pstruct.dual_table = None      # mode switched off after use: gather from the two tables again
-            plan.dual_key = None
+        bind_params(lib, plan, ps)
         ws_bytes = plan.ws_bytes.get(n_rays)
         if ws_bytes is None:
             ws_bytes = lib.ls2fm_render_workspace_bytes(ctypes.byref(fdesc), ctypes.byref(g1), n_rays)
