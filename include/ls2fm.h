@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LS2FM_ABI_VERSION 12
+#define LS2FM_ABI_VERSION 13
 #define LS2FM_MAX_LEVELS 16
 #define LS2FM_HIDDEN 64        /* SDF.arch.layers = [null, 64, 16]  (options/LevelS2fM.yaml:14) */
 #define LS2FM_FEAT 16
@@ -205,6 +205,40 @@ int ls2fm_marching_cubes_count(const float* vol, int64_t nx, int64_t ny, int64_t
                                int64_t* counts, void* stream);
 int ls2fm_marching_cubes_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, const float* spacing,
                               const float* origin, void* workspace, float* verts, int32_t* faces, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh components and the largest component by area (new, ABI 13).
+ * Replaces: trimesh.Trimesh.split(only_watertight=False), argmax over the components' `area` and the submesh it returns, as
+ *           get_surface_high_res_mesh calls them (utils/plots.py:163-166).
+ * verts fp32 [n_verts,3], faces int32 [n_faces,3], DEVICE.  Every index lies in [0, n_verts): the caller guarantees it (the
+ * library does not check; ls2fm.mesh checks with one device reduction before the call).
+ * Components: two faces are in one component when a chain of faces, each consecutive pair sharing a vertex INDEX, links them
+ * (trimesh joins through shared edges; on ls2fm_marching_cubes meshes the two agree).  The label of a vertex is the smallest
+ * vertex index of its component; a vertex no face uses is a component of its own.  Labels do not depend on the order of the
+ * unions: they are deterministic by definition.
+ * Area of a face: 0.5 |(b - a) x (c - a)| in double from the fp32 corners; of a component: the sum over its faces, formed in
+ * 64-bit fixed point (2^-s units, s from the largest face area and n_faces, so the total stays below 2^63): the sum does not
+ * depend on the order of the faces, two components with the same faces tie exactly, and every call gives the same bits.
+ * Largest component: the largest area; on a tie, the component that holds the lowest-numbered face (what np.argmax over
+ * trimesh's split list, ordered by lowest face, picks).  Extraction keeps its faces in their order and the vertices they use
+ * in index order, the faces renumbered to match (Trimesh.submesh).  Output is identical from call to call.
+ * ls2fm_mesh_components: labels int32 [n_verts].  n_faces = 0 writes labels[v] = v (one launch); n_verts = 0 enqueues nothing.
+ * ls2fm_mesh_components_workspace_bytes: workspace of the two calls below (~20 bytes per vertex), or < 0 for refused sizes.
+ * ls2fm_mesh_largest_component_count: counts int64 [2] (device) = kept vertices, kept faces; areas double [n_verts] or NULL:
+ *   areas[l] = the area of the component labelled l, 0 where l is no label.  Fills the workspace for the emit call.
+ * ls2fm_mesh_largest_component_emit: after count, with the same mesh and workspace; out_verts [counts[0],3] fp32, out_faces
+ *   [counts[1],3] int32.
+ * n_faces = 0: the result is empty; nothing is enqueued and counts are not written.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL buffer, a negative count, n_verts >= 2^31,
+ * n_faces >= 2^31 or faces without vertices; LS2FM_ERR_WORKSPACE for a NULL workspace or one below the queried size.
+ */
+int64_t ls2fm_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int ls2fm_mesh_components(const int32_t* faces, int64_t n_verts, int64_t n_faces, int32_t* labels, void* stream);
+int ls2fm_mesh_largest_component_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                                       void* workspace, int64_t workspace_bytes, int64_t* counts, double* areas, void* stream);
+int ls2fm_mesh_largest_component_emit(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                                      void* workspace, int64_t workspace_bytes, float* out_verts, int32_t* out_faces,
+                                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Point queries WITH a graph: backward of  p -> (sdf, the 17 MLP outputs, the analytic normal d sdf / d p)  for n free points.

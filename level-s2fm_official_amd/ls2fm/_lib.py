@@ -15,7 +15,7 @@ import torch
 MAX_LEVELS = 16
 HIDDEN = 64
 FEAT = 16
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_RENDER_POINTS = 1 << 23     # LS2FM_MAX_RENDER_POINTS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +118,10 @@ _SIGNATURES = {
     "ls2fm_marching_cubes_count": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, _P, _P, _P]),
     "ls2fm_marching_cubes_emit": (c_int32, [_P, c_int64, c_int64, c_int64, c_float, POINTER(c_float), POINTER(c_float), _P, _P,
                                             _P, _P]),
+    "ls2fm_mesh_components_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "ls2fm_mesh_components": (c_int32, [_P, c_int64, c_int64, _P, _P]),
+    "ls2fm_mesh_largest_component_count": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "ls2fm_mesh_largest_component_emit": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "ls2fm_sdf_points_workspace_bytes": (c_int64, [POINTER(FieldDesc), POINTER(GridDesc), c_int64]),
     "ls2fm_sdf_points_bwd": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(Params), _P, c_int64, _P, _P, _P,
                                        POINTER(ParamGrads), _P, _P, _P]),

@@ -1,12 +1,16 @@
-"""Mesh extraction on the device: marching cubes over a dense volume (ls2fm_marching_cubes_*) and a PLY writer.
+"""Mesh extraction on the device: marching cubes over a dense volume (ls2fm_marching_cubes_*), connected components and the
+largest one by area (ls2fm_mesh_*), area-weighted surface sampling and a PLY writer / reader (binary and ASCII).
 
 Replaces the third-party steps of the reference's extract_mesh (utils/util.py:392-425 -> convert_sigma_samples_to_ply,
-util.py:345): skimage.measure.marching_cubes and plyfile.  The case table is generated from one face rule
-(tools/gen_mc_tables.py; include/ls2fm.h documents the rule, the vertex arithmetic and the output order).
+util.py:345): skimage.measure.marching_cubes and plyfile; and of get_surface_high_res_mesh (utils/plots.py:140-222):
+trimesh's split / area / submesh, trimesh.sample.sample_surface and trimesh.exchange.ply.export_ply.  The case table is
+generated from one face rule (tools/gen_mc_tables.py; include/ls2fm.h documents the rule, the vertex arithmetic and the
+output order).
 """
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -45,6 +49,129 @@ def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 
     return verts, faces
 
 
+class Mesh(NamedTuple):
+    """a triangle mesh: vertices float32 [V, 3], faces int32 [F, 3]"""
+    vertices: torch.Tensor
+    faces: torch.Tensor
+
+
+def _check_mesh(verts, faces, what):
+    """device-only and [., 3] shapes"""
+    if not faces.is_cuda or (verts is not None and not verts.is_cuda):
+        raise RuntimeError(f"ls2fm.mesh.{what} runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be [F, 3], got shape {tuple(faces.shape)}")
+    if verts is not None and (verts.dim() != 2 or verts.shape[1] != 3):
+        raise ValueError(f"{what}: verts must be [V, 3], got shape {tuple(verts.shape)}")
+
+
+def _faces_i32(faces, n_verts, what):
+    """faces as contiguous int32, every index checked in [0, n_verts) (one device reduction, one host read)"""
+    f = faces if faces.dtype == torch.int32 and faces.is_contiguous() else faces.to(torch.int32).contiguous()
+    if f.numel():
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(faces.reshape(-1))).cpu())
+        if lo < 0 or hi >= n_verts:
+            raise ValueError(f"{what}: face indices span [{lo}, {hi}], outside [0, {n_verts})")
+    return f
+
+
+def connected_components(faces: torch.Tensor, n_verts: int) -> torch.Tensor:
+    """labels int32 [n_verts] on the faces' device: the smallest vertex index of each vertex's component, faces joined through
+    shared vertex indices (include/ls2fm.h); a vertex no face uses is its own component"""
+    lib = _lib.load()
+    _check_mesh(None, faces, "connected_components")
+    n_verts = int(n_verts)
+    f = _faces_i32(faces, n_verts, "connected_components")
+    if lib.ls2fm_mesh_components_workspace_bytes(n_verts, f.shape[0]) < 0:
+        raise ValueError(f"connected_components: {n_verts} vertices / {f.shape[0]} faces refused (both < 2^31)")
+    with torch.cuda.device(f.device):
+        labels = torch.empty(n_verts, dtype=torch.int32, device=f.device)
+        check(lib.ls2fm_mesh_components(ptr(f), n_verts, f.shape[0], ptr(labels), stream_ptr()), "ls2fm_mesh_components")
+    return labels
+
+
+def _largest_count(verts, faces, want_areas):
+    lib = _lib.load()
+    v = _lib.cf(verts)
+    n_verts = v.shape[0]
+    f = _faces_i32(faces, n_verts, "largest_component")
+    ws_bytes = int(lib.ls2fm_mesh_components_workspace_bytes(n_verts, f.shape[0]))
+    if ws_bytes < 0:
+        raise ValueError(f"largest_component: {n_verts} vertices / {f.shape[0]} faces refused (both < 2^31)")
+    dev = v.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    areas = torch.zeros(n_verts, dtype=torch.float64, device=dev) if want_areas else None
+    if f.shape[0]:
+        check(lib.ls2fm_mesh_largest_component_count(ptr(v), n_verts, ptr(f), f.shape[0], ptr(ws), ws_bytes, ptr(counts),
+                                                     ptr(areas), stream_ptr()), "ls2fm_mesh_largest_component_count")
+    return v, f, ws, ws_bytes, counts, areas
+
+
+def component_areas(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """float64 [V]: entry l = the area of the component labelled l (connected_components), 0 where l is no label.  Summed in
+    64-bit fixed point: independent of the face order, identical bits on every call"""
+    _check_mesh(verts, faces, "component_areas")
+    with torch.cuda.device(faces.device):
+        return _largest_count(verts, faces, True)[5]
+
+
+def largest_component(verts: torch.Tensor, faces: torch.Tensor) -> Mesh:
+    """the component of largest area (ties: the one holding the lowest-numbered face), as Trimesh.split + argmax(area) +
+    submesh give it: its faces in their order, the vertices they use in index order, the faces renumbered.  One host read
+    (the counts) after the index check's."""
+    _check_mesh(verts, faces, "largest_component")
+    with torch.cuda.device(faces.device):
+        v, f, ws, ws_bytes, counts, _ = _largest_count(verts, faces, False)
+        n_v, n_f = (int(c) for c in counts.cpu())
+        out_v = torch.empty(n_v, 3, dtype=torch.float32, device=v.device)
+        out_f = torch.empty(n_f, 3, dtype=torch.int32, device=v.device)
+        if n_f:
+            check(_lib.load().ls2fm_mesh_largest_component_emit(ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(ws), ws_bytes,
+                                                                ptr(out_v), ptr(out_f), stream_ptr()),
+                  "ls2fm_mesh_largest_component_emit")
+    return Mesh(out_v, out_f)
+
+
+def _face_areas64(verts, faces):
+    """0.5 |(b - a) x (c - a)| in float64 (trimesh's area_faces on float64 vertices)"""
+    tri = verts.to(torch.float64)[faces.long()]
+    u, w = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    cross = torch.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
+                         u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], dim=1)
+    return (cross * cross).sum(dim=1).sqrt() / 2
+
+
+def _sample_surface_from_uniforms(verts, faces, u0, u1, u2):
+    """trimesh.sample.sample_surface with its uniforms given: u0 [n] picks the face by area, (u1, u2) [n] the point in it.
+    -> (points float32 [n, 3], face index int64 [n])"""
+    area = _face_areas64(verts, faces)
+    cum = torch.cumsum(area, dim=0)
+    face = torch.searchsorted(cum, u0.to(torch.float64) * cum[-1], side="left")
+    face = face.clamp(max=faces.shape[0] - 1)             # u0 < 1 keeps pick < cum[-1]; guards the rounding of the product
+    tri = verts.to(torch.float64)[faces.long()[face]]
+    o, v1, v2 = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    r1, r2 = u1.to(torch.float64), u2.to(torch.float64)
+    flip = r1 + r2 > 1.0
+    r1 = torch.where(flip, (r1 - 1.0).abs(), r1)
+    r2 = torch.where(flip, (r2 - 1.0).abs(), r2)
+    pts = (v1 * r1[:, None] + v2 * r2[:, None]) + o       # trimesh: (vectors * lengths).sum(axis=1) + origins
+    return pts.to(torch.float32), face
+
+
+def sample_surface(verts: torch.Tensor, faces: torch.Tensor, count: int, generator=None) -> torch.Tensor:
+    """`count` points on the surface, faces picked with probability proportional to their area and points uniform in the
+    face: trimesh.sample.sample_surface's algorithm in float64 on the device, cast to float32 (as plots.py:169 does).  The
+    uniforms come from `generator` or torch's default generator of the device, so runs under torch.manual_seed repeat."""
+    _check_mesh(verts, faces, "sample_surface")
+    if faces.shape[0] == 0:
+        raise ValueError("sample_surface: the mesh has no faces")
+    dev = verts.device
+    u0 = torch.rand(count, dtype=torch.float64, device=dev, generator=generator)
+    u12 = torch.rand(count, 2, dtype=torch.float64, device=dev, generator=generator)
+    return _sample_surface_from_uniforms(verts, faces, u0, u12[:, 0], u12[:, 1])[0]
+
+
 def _as_numpy(a, dtype):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
@@ -58,11 +185,38 @@ def ply_header(n_verts: int, n_faces: int) -> bytes:
             f"element face {n_faces}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
 
 
-def write_ply(path, verts, faces) -> None:
-    """write verts [V, 3] / faces [F, 3] (tensors or arrays) in the layout extract_mesh's plyfile branch writes:
-    binary_little_endian 1.0, `element vertex` of float x/y/z, `element face` of `property list uchar int vertex_indices`"""
+def ply_header_ascii(n_verts: int, n_faces: int) -> bytes:
+    """the header of write_ply(encoding="ascii"): the same two elements as the binary layout"""
+    return ("ply\nformat ascii 1.0\n"
+            f"element vertex {n_verts}\nproperty float x\nproperty float y\nproperty float z\n"
+            f"element face {n_faces}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
+
+
+_ASCII_BLOCK = 1 << 16          # rows formatted per string operation
+
+
+def _ascii_rows(fh, rows, fmt):
+    for at in range(0, len(rows), _ASCII_BLOCK):
+        block = rows[at:at + _ASCII_BLOCK]
+        fh.write(((fmt * len(block)) % tuple(block.ravel().tolist())).encode("ascii"))
+
+
+def write_ply(path, verts, faces, encoding: str = "binary") -> None:
+    """write verts [V, 3] / faces [F, 3] (tensors or arrays).
+    encoding="binary": the layout extract_mesh's plyfile branch writes: binary_little_endian 1.0, `element vertex` of float
+    x/y/z, `element face` of `property list uchar int vertex_indices`.
+    encoding="ascii": the same elements as text (get_surface_high_res_mesh's export_ply(encoding='ascii')): one `x y z` line
+    per vertex with 9 significant digits (a float32 round-trips), one `3 a b c` line per face"""
+    if encoding not in ("binary", "ascii"):
+        raise ValueError(f"write_ply: encoding must be 'binary' or 'ascii', got {encoding!r}")
     v = _as_numpy(verts, "<f4")
     f = _as_numpy(faces, "<i4")
+    if encoding == "ascii":
+        with open(path, "wb") as fh:
+            fh.write(ply_header_ascii(len(v), len(f)))
+            _ascii_rows(fh, v.astype(np.float64), "%.9g %.9g %.9g\n")
+            _ascii_rows(fh, f, "3 %d %d %d\n")
+        return
     rows = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))      # packed: 13 bytes per face
     rows["n"] = 3
     rows["idx"] = f
@@ -87,3 +241,26 @@ def read_ply(path):
     if n_faces and not (rows["n"] == 3).all():
         raise ValueError(f"{path}: a face that is not a triangle")
     return v.copy(), rows["idx"].astype(np.int32).reshape(n_faces, 3)
+
+
+def read_ply_ascii(path):
+    """parse back a file of write_ply(encoding="ascii")'s layout (triangles only) -> (verts float32 [V, 3], faces int32 [F, 3])"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    n_verts = int(next(ln for ln in lines if ln.startswith("element vertex")).split()[2])
+    n_faces = int(next(ln for ln in lines if ln.startswith("element face")).split()[2])
+    if ply_header_ascii(n_verts, n_faces) != data[:end]:
+        raise ValueError(f"{path}: not the layout write_ply(encoding='ascii') writes")
+    body = data[end:].split(b"\n")
+    if len(body) != n_verts + n_faces + 1 or body[-1] != b"":
+        raise ValueError(f"{path}: {len(body) - 1} rows, expected {n_verts} + {n_faces}")
+    v = np.array(b" ".join(body[:n_verts]).split(), dtype=np.float64).astype(np.float32)
+    rows = np.array(b" ".join(body[n_verts:n_verts + n_faces]).split(), dtype=np.int64)
+    if v.size != 3 * n_verts or rows.size != 4 * n_faces:
+        raise ValueError(f"{path}: a row without three coordinates or a face that is not a triangle")
+    rows = rows.reshape(n_faces, 4)
+    if n_faces and not (rows[:, 0] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    return v.reshape(n_verts, 3), rows[:, 1:].astype(np.int32)

@@ -6,8 +6,9 @@ The reference walks both lattices in 100 000-point chunks, each a device evaluat
 lattice is built on the device from its three 1-D axes (formed on the host in fp64 exactly as the reference's numpy
 lines do, then rounded to fp32 like its `dtype=torch.float`), optionally rotated on the device, and evaluated by the fused
 no-graph SDF kernel in one pass (`ls2fm.fused.sdf_eval`; chunks of 2^25 points only bound the scratch memory); the volume
-stays in HBM until marching cubes wants it.  Marching cubes, connected components, surface sampling and PLY export are
-third-party (scikit-image, trimesh) and are used when installed -- they are not part of the path.
+stays in HBM until marching cubes wants it.  get_surface_high_res_mesh(backend="device") turns the volumes into the mesh on
+the device too (ls2fm.mesh: marching cubes, largest component, surface sampling, ASCII PLY); backend="trimesh" keeps the
+reference's scikit-image / trimesh steps.
 """
 from __future__ import annotations
 
@@ -88,9 +89,79 @@ def _principal_frame(points):
     return mean, vecs
 
 
-def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), level=0, take_components=True, path=None):
-    """utils/plots.py:140-222, same arguments.  The two SDF sweeps are device passes (see module docstring); everything
-    that turns the volumes into a mesh needs scikit-image and trimesh."""
+def _lattice_shape(axes):
+    """(nx, ny, nz) of the marching-cubes volume of a meshgrid lattice: the flat sweep viewed [ny, nx, nz], axes 0 and 1 swapped"""
+    return len(axes[0]), len(axes[1]), len(axes[2])
+
+
+def _mc_volume(z, axes):
+    nx, ny, nz = _lattice_shape(axes)
+    return z.view(ny, nx, nz).permute(1, 0, 2).contiguous()
+
+
+def _high_res_device(sdf, resolution, grid_boundary, level, take_components):
+    """the device path of get_surface_high_res_mesh -> (Mesh or None, dict of the fitted lattice's volume, spacing, frame and
+    first point; None when the fitted volume has no crossing)"""
+    from .. import _lib, mesh
+    axes = uniform_axes(100, grid_boundary)
+    z = sdf_on_lattice(sdf, axes)
+    device = z.device
+    sp = float(axes[0][2] - axes[0][1])
+    verts, faces = mesh.marching_cubes(_mc_volume(z, axes), level=level, spacing=(sp, sp, sp),
+                                       origin=(float(axes[0][0]), float(axes[1][0]), float(axes[2][0])))
+    if faces.shape[0] == 0:
+        raise ValueError(f"get_surface_high_res_mesh: the coarse 100^3 volume has no crossing of level {level} inside "
+                         f"{list(grid_boundary)}")
+    if take_components:
+        verts, faces = mesh.largest_component(verts, faces)
+    cloud = mesh.sample_surface(verts, faces, 10000)
+    mean, vecs = _principal_frame(cloud)
+    aligned = (cloud - mean) @ vecs.t()
+    axes2, _, _ = fitted_axes(aligned.cpu(), resolution)
+    shape = _lattice_shape(axes2)
+    if _lib.load().ls2fm_marching_cubes_workspace_bytes(*shape) < 0:
+        raise ValueError(f"get_surface_high_res_mesh: the fitted lattice {shape[0]}x{shape[1]}x{shape[2]} is too large for "
+                         "marching cubes (3*nx*ny*nz must stay below 2^31)")
+    z2 = sdf_on_lattice(sdf, axes2, rotation=vecs, offset=mean, device=device)
+    if float(z2.min()) > level or float(z2.max()) < level:
+        return None, None
+    sp2 = float(axes2[0][2] - axes2[0][1])
+    vol2 = _mc_volume(z2, axes2)
+    del z2
+    verts, faces = mesh.marching_cubes(vol2, level=level, spacing=(sp2, sp2, sp2))
+    first = lattice_on_device(axes2, device, 0, 1) @ vecs + mean
+    verts = verts @ vecs + first[0]
+    return mesh.Mesh(verts, faces), dict(volume=vol2, spacing=sp2, vecs=vecs, first=first[0])
+
+
+def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), level=0, take_components=True, path=None,
+                              backend="auto"):
+    """utils/plots.py:140-222, same arguments.  The two SDF sweeps are device passes (see module docstring).
+    backend: "trimesh" = the reference's scikit-image + trimesh steps (ImportError without them; returns a Trimesh);
+    "device" = ls2fm.mesh: marching cubes on the coarse volume, its largest component by area (take_components), 10 000
+    area-weighted surface samples for the principal frame, marching cubes on the fitted volume, ASCII PLY; returns an
+    ls2fm.mesh.Mesh of device tensors, or None (nothing written) when the fitted volume has no crossing.  A coarse volume
+    without a crossing raises ValueError (as skimage does), and so does a fitted lattice marching cubes refuses.
+    "auto" = "trimesh" when both packages import, else "device".
+    Intended differences of the device path: the surface samples come from torch's generator (reproducible under
+    torch.manual_seed) instead of numpy's global one; marching cubes uses its own case table (ls2fm.mesh.marching_cubes);
+    trimesh merges vertices on construction, which only differs where a lattice value equals `level` exactly; the PLY
+    carries no normals, as the reference's (skimage's vertex normals land in Trimesh's face_normals argument)."""
+    if backend not in ("auto", "device", "trimesh"):
+        raise ValueError(f"get_surface_high_res_mesh: backend must be 'auto', 'device' or 'trimesh', got {backend!r}")
+    if backend == "auto":
+        try:
+            import skimage.measure  # noqa: F401
+            import trimesh  # noqa: F401
+            backend = "trimesh"
+        except ImportError:
+            backend = "device"
+    if backend == "device":
+        from .. import mesh
+        result, _ = _high_res_device(sdf, resolution, grid_boundary, level, take_components)
+        if path is not None and result is not None:
+            mesh.write_ply(path, result.vertices, result.faces, encoding="ascii")
+        return result
     try:
         from skimage import measure
         import trimesh
