@@ -412,6 +412,33 @@ int ls2fm_render_image(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf
                        int32_t width, float* rgb, float* depth, float* normal, float* opacity, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sphere-traced depth and normal maps of whole images (new; the library's version stays ABI 13: the calls are additions).
+ * Replaces: Camera.get_depth (pipelines/Camera.py:216-253): get_center_and_ray for every pixel, SDF.sphere_tracing
+ * (models/SDF.py:149-214) over all of them and SDF.gradient (SDF.py:102-114) at the surface points -- without the track
+ * ([R, iters_max+1, 3]), its re-evaluation or a second gradient query.
+ * The rays are those ls2fm_camera_rays forms for poses and pix = 0 .. H*W-1 with width W (centres x + 0.5, y + 0.5).  Each view
+ * gets the trip count K of the reference's loop over that view alone -- the trip at which its last start end finished -- and every
+ * ray of the view sums the field over its first max(K, 1) track points, in ascending order.  Per view, every output is bit for bit
+ * what ls2fm_sphere_trace + ls2fm_trace_depth_fwd (SDF.sphere_tracing(static_trips=True)) and ls2fm_sdf_eval's normal return:
+ *   depth [n_views,H*W] = near + sum, clamped to far;  sdf_last [n_views,H*W]: the last value summed;
+ *   finish uint8 [n_views,H*W] = |sdf_last| < finish_threshold;  points [n_views,H*W,3] = center + depth * ray (two roundings);
+ *   gradient [n_views,H*W,3] or NULL: the analytic d sdf / d p at points;  t_end_k [n_views,H*W] or NULL: the far end after K
+ *   trips;  trips int32 [n_views]: K of each view.  Row-major pixels.
+ * poses [n_views,3,4] world-to-camera (DEVICE: read at run time); kinv_host: the 3 x 3 K^-1 as 9 HOST floats.
+ * workspace: ls2fm_trace_image_workspace_bytes(...) bytes (the packed weights and one chunk of the normal query's sdf column):
+ * it depends on nothing but the build, never on the image size or the number of views.  No allocation, no host
+ * synchronisation, no stream fork: capturable.
+ * Refusals (before any device work): LS2FM_ERR_UNSUPPORTED for bg_sdf; LS2FM_ERR_INVALID_ARGUMENT for null required pointers,
+ * non-positive sizes or views, iters_max < 0 or 2^30 rays or more; LS2FM_ERR_WORKSPACE for a null workspace.  No gradients.
+ */
+int64_t ls2fm_trace_image_workspace_bytes(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid);
+int ls2fm_trace_image(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
+                      const float* poses, int32_t n_views, const float* kinv_host, int32_t height, int32_t width,
+                      float sdf_threshold, int32_t iters_max, float finish_threshold,
+                      float* depth, float* sdf_last, uint8_t* finish, float* points, float* gradient,
+                      float* t_end_k, int32_t* trips, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Bidirectional sphere tracing, the no-grad root-find loop.
  * Replaces: the `while True` of SDF.sphere_tracing (models/SDF.py:149-200) including the AABB
  * near/far (SDF.py:120-122).  Each ray is advanced independently for up to iters_max trips and

@@ -10,51 +10,11 @@
 #include <cstdlib>
 
 #include "render_common.h"
+#include "sdf_point.h"
 
 int ls2fm_launch_prep_sdf(const ls2fm_params* params, int n_levels, Packed* out, hipStream_t stream, int32_t* zero_word = nullptr);
 
 namespace {
-
-// hash-encode a world point into u[35] = [p / rescale, e(x)]
-__device__ __forceinline__ void encode_point(const LevelSet& lv, const FieldC& fc, const float* __restrict__ table,
-                                             const float p[3], float (&u)[kInMax]) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        x[a] = (p[a] - fc.bmin[a]) / (fc.bmax[a] - fc.bmin[a]);
-        u[a] = p[a] / fc.rescale;
-    }
-#pragma unroll
-    for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) {
-        float y0 = 0.f, y1 = 0.f;
-        if (l < lv.n_levels) {
-            Cell c;
-            locate(x, lv.scale[l], lv.res[l], lv.size[l], lv.offset[l], lv.hashed[l], c);
-            float2 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float wt = corner_weight(c.w, k);
-                y0 = fmaf(wt, v[k].x, y0);
-                y1 = fmaf(wt, v[k].y, y1);
-            }
-        }
-        u[3 + 2 * l] = y0;
-        u[4 + 2 * l] = y1;
-    }
-}
-
-__device__ __forceinline__ float signed_sdf(const FieldC& fc, int bg_sdf, float bg_rad, float f0, const float p[3],
-                                            bool* bg_selected) {
-    float sdf = fc.inside ? f0 / fc.scale_mlp : -f0 / fc.scale_mlp;
-    *bg_selected = false;
-    if (bg_sdf) {
-        const float other = bg_rad - sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-        if (other < sdf) { sdf = other; *bg_selected = true; }
-    }
-    return sdf;
-}
 
 // Lattice of a volume sweep, generated on the device (ls2fm_sdf_volume).  ref_indexing reproduces the host arithmetic
 // of the reference's extract_mesh (utils/util.py:399-409), fp64 then rounded to fp32 like its `.float()`: with
@@ -662,6 +622,28 @@ extern "C" int ls2fm_sdf_eval(const ls2fm_field_desc* field, const ls2fm_grid_de
     else
         sdf_eval_kernel<false><<<blocks, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table, p, Lattice{},
                                                       n, sdf, feat, nullptr);
+    ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
+    return ls2fm_launch_status();
+}
+
+// ls2fm_sdf_eval's normal query (feat = NULL) on weights already packed in `pk`, for points p[0 .. n) of a query of n_query points:
+// the kernel ls2fm_sdf_eval picks for n_query, so every point's sdf and normal are bit for bit what one ls2fm_sdf_eval call over all
+// n_query points returns (trace_image.hip walks the surface points in bounded chunks)
+int ls2fm_launch_sdf_normals(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const Packed* pk, const float* table,
+                             const float* p, int64_t n, int64_t n_query, float* sdf, float* normal, hipStream_t s) {
+    if (n <= 0) return LS2FM_OK;
+    const FieldC fc = make_field_c(field);
+    const LevelSet lv = make_level_set(grid);
+    const char* force = getenv("LS2FM_POINTS_KERNEL");
+    const int forced = force ? atoi(force) : 0;
+    const bool wide_full = forced == 2 || (forced != 1 && n_query <= 32768);
+    ls2fm_prof_begin(LS2FM_PROF_SDF_EVAL, s);
+    if (wide_full)
+        sdf_eval_wide_full_kernel<true><<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, n,
+                                                                                  sdf, nullptr, normal);
+    else
+        sdf_eval_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, Lattice{},
+                                                                         n, sdf, nullptr, normal);
     ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
     return ls2fm_launch_status();
 }

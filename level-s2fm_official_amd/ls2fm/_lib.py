@@ -136,6 +136,9 @@ _SIGNATURES = {
     "ls2fm_render_image_workspace_bytes": (c_int64, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc)]),
     "ls2fm_render_image": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc), POINTER(Params), _P, c_int32,
                                      POINTER(c_float), c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_trace_image_workspace_bytes": (c_int64, [POINTER(FieldDesc), POINTER(GridDesc)]),
+    "ls2fm_trace_image": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(Params), _P, c_int32, POINTER(c_float), c_int32,
+                                    c_int32, c_float, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_loss_terms_from_sums": (c_int32, [_P, _P, _P, _P]),
     "ls2fm_sphere_trace": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(Params), _P, _P, c_int64,
                                      c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
