@@ -669,6 +669,82 @@ int ls2fm_match_term_bwd(const float* center, const float* ray, const float* uv_
                          float* const* d_d, float* const* d_sdf, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Absolute pose (csrc/absolute_pose.hip): what Registration.PnP asks of pycolmap (pipelines/Registration.py:94-109,
+ * absolute_pose_estimation + pose_refinement), for many views in one call.  All geometry in fp64.  Poses are world-to-camera
+ * [3,4] = [R | t] row-major; a pinhole view v has intr[v] = (fx, fy, cx, cy) (DEVICE doubles); pixel of a camera point p:
+ * (fx p.x / p.z + cx, fy p.y / p.z + cy).  Correspondences are sorted by view: view v owns [view_start[v], view_start[v + 1])
+ * (DEVICE int32 [n_views + 1], non-decreasing; the ragged convention of ls2fm_reproject_*).  tests/pose_restate.py repeats every
+ * rule below in numpy.
+ *
+ * ls2fm_p3p: m minimal problems, each 3 unit bearings [m][3][3] and 3 world points [m][3][3] (device) -> up to 4 poses
+ * [m][4][3][4] (the kept ones first, in slot order; the rest zero) and n_solutions [m].  Lambda Twist (Persson & Nordberg, ECCV
+ * 2018): the cubic det(D1 + g D2) = 0 of the two homogeneous distance forms (its only real root, or the largest of three; two
+ * Newton steps), the degenerate conic's two lines (slots 0-1: w = e1 - r e2, slots 2-3: w = e1 + r e2), each met with the other
+ * form (roots q / C, then A / q), depths scaled on the longest side and polished by <= 5 Gauss-Newton steps on the three distance
+ * equations; R from the two triangles' orthonormal frames, t from the centroids.  A solution with a sample point at camera
+ * z <= 0 or a non-finite entry is dropped; collinear or coincident points (|d01 x d02|^2 <= 1e-20 |d01|^2 |d02|^2) give 0
+ * solutions, never NaN.
+ *
+ * ls2fm_absolute_pose: LO-RANSAC per view.
+ *   samples   trial t (0, 1, 2, ... per view) draws indices from key = splitmix64(seed ^ splitmix64(t)): draw k is
+ *             ((splitmix64(key + k) >> 32) * n) >> 32 over the view's n correspondences; the sample is the first three distinct
+ *             values among draws k = 0 .. 63 (none: the trial has no pose).  splitmix64(x): z = x + 0x9E3779B97F4A7C15;
+ *             z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)  (mod 2^64).
+ *             The view's position in the batch is not part of the key: a view draws the same samples alone or in any batch.
+ *   hypotheses ls2fm_p3p of the sample's bearings normalise((u - cx) / fx, (v - cy) / fy, 1); slot s = the P3P slot above.
+ *   scoring   correspondence i is an inlier of P when its camera z > 0 and its squared pixel error < max_error_px^2; counts are
+ *             exact integers.
+ *   selection the best (count, then lowest t * 4 + s) over all trials so far: the 64-bit max of (count << 32 | ~(t * 4 + s)).
+ *   rounds    trials run in rounds of LS2FM_POSE_ROUND per view still active; after a round, with eps = best count / n,
+ *             N = clamp(ceil(log(1 - confidence) / log(1 - eps^3)), min(min_num_trials, cap), cap) (eps = 0: cap; eps = 1: the
+ *             lower bound), cap = min(max_num_trials, the same formula at eps = min_inlier_ratio): the cap wins over min_num_trials,
+ *             as in COLMAP's RANSAC.  The view stops once its trials >= N.  The
+ *             host reads one "views still active" word per round: the call SYNCHRONISES and is not capturable.
+ *   local optimisation from the best pose, up to 10 times: Gauss-Newton step on the inliers' squared pixel error (increment
+ *             (w, dt): R <- exp([w]x) R, t <- exp([w]x) t + dt; 6 x 6 normal equations reduced in a fixed order, Cholesky),
+ *             recount; the step is kept when its count is >= the old one, and the loop stops when it is not, when fewer than 3
+ *             inliers remain or when the inlier set did not change.  inliers[] (uint8) = the final set.
+ *   refinement (opts->refine) ls2fm_pose_refine's loop on that fixed set, loss scale 1 px, LS2FM_POSE_REFINE_ITERS iterations.
+ *   outputs   poses [V][3][4], num_inliers, trials (run), best_trial (the winning SAMPLED trial t, before local optimisation;
+ *             -1 when none), success = num_inliers >= 4.  A view with n < 3 (or no hypothesis with an inlier) fails: identity
+ *             pose, 0 inliers, without touching its neighbours.  Every bit depends on the view's own data, seed and options only.
+ *   options   max_error_px > 0, 0 < confidence < 1, 0 <= min_inlier_ratio < 1, 0 <= min_num_trials <= max_num_trials,
+ *             1 <= max_num_trials <= LS2FM_POSE_MAX_TRIALS, refine 0 / 1; 1 <= n_views <= LS2FM_POSE_MAX_VIEWS.  A refusal
+ *             returns LS2FM_ERR_INVALID_ARGUMENT and launches nothing.  workspace: ls2fm_absolute_pose_workspace_bytes
+ *             (~400 KB per view; n_corr does not change it).
+ *
+ * ls2fm_pose_refine: pose_refinement on a FIXED mask (uint8 per correspondence): Levenberg-Marquardt on 0.5 sum rho(s_i),
+ * s_i = squared pixel error, Cauchy rho(s) = c^2 log(1 + s / c^2) with c = loss_scale_px, normal equations weighted by rho'(s);
+ * damping lambda diag(H) (diagonal floored at 1e-12 of its largest entry), lambda = 1e-4 at the start, x 0.1 after a step that
+ * lowers the cost, x 10 after one that does not; at most max_iters iterations; stops when max |gradient| <= 1e-10 or after a kept
+ * step with max |increment| <= 1e-12 (1 + max |t|).  Views with fewer than 3 masked correspondences keep their pose.  One
+ * workgroup per view, fixed-order sums: repeatable bit for bit, and capturable (it reads nothing back).
+ */
+#define LS2FM_POSE_ROUND 1024
+#define LS2FM_POSE_MAX_VIEWS 65535
+#define LS2FM_POSE_MAX_TRIALS (1 << 24)
+#define LS2FM_POSE_REFINE_ITERS 100
+
+typedef struct ls2fm_pose_ransac_opts {
+    double max_error_px;
+    double confidence;
+    double min_inlier_ratio;
+    int64_t min_num_trials;
+    int64_t max_num_trials;
+    uint64_t seed;
+    int32_t refine;
+} ls2fm_pose_ransac_opts;
+
+int ls2fm_p3p(const double* bearings, const double* points, int64_t m, double* poses, int32_t* n_solutions, void* stream);
+int64_t ls2fm_absolute_pose_workspace_bytes(int32_t n_views, int64_t n_corr);
+int ls2fm_absolute_pose(const double* uv, const double* xyz, const int32_t* view_start, int32_t n_views, const double* intr,
+                        const ls2fm_pose_ransac_opts* opts, double* poses, uint8_t* inliers, int32_t* num_inliers, int32_t* trials,
+                        int32_t* best_trial, int32_t* success, void* workspace, void* stream);
+int ls2fm_pose_refine(const double* uv, const double* xyz, const int32_t* view_start, int32_t n_views, const double* intr,
+                      const uint8_t* mask, const double* poses_in, float loss_scale_px, int32_t max_iters, double* poses_out,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -1,0 +1,865 @@
+// Absolute pose of many views in one call: LO-RANSAC over Lambda Twist P3P, Gauss-Newton local optimisation and a Cauchy-loss
+// Levenberg-Marquardt refinement -- what Registration.PnP asks of pycolmap (pipelines/Registration.py:94-109:
+// absolute_pose_estimation + pose_refinement), all geometry in fp64.  include/ls2fm.h states the rules; tests/pose_restate.py
+// repeats them step by step in numpy.  Correspondences are SORTED BY VIEW (view v owns [view_start[v], view_start[v + 1])).
+//
+//   per round (host loop; a view stops once its trial count reaches the stopping rule's N):
+//     pose_hyp_kernel     one thread per (view, trial): three distinct indices from the SplitMix64 stream, P3P, <= 4 poses
+//     pose_score_kernel   (1024-correspondence tile of some view, 16-trial block): inlier counts of the block's 64 poses over the
+//                         tile, wave ballots + integer atomics (exact, order-independent).  The tiles of all views are numbered
+//                         in one flat range (per-view tile offsets from the host), so a view of n gets ceil(n / 1024) x 64
+//                         workgroups -- 128 for n = 2000, 65 536 for n = 2^20 -- whatever the sizes of the other views
+//     pose_select_kernel  one workgroup per view: the best (count, lowest trial * 4 + slot) as a 64-bit max, the stopping rule
+//   then pose_lo_kernel (local optimisation, the final mask) and pose_lm_kernel (refinement), one workgroup per view with
+//   fixed-order reductions: every bit of the result is a function of the view's own data, seed and options.
+#include "ls2fm_device.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+constexpr int kRound = LS2FM_POSE_ROUND;      // trials per view per round (1024)
+constexpr int kHypThreads = 256;
+constexpr int kScoreThreads = 256;
+constexpr int kScorePts = 4;                   // correspondences per thread of a scoring tile
+constexpr int kScoreTile = kScoreThreads * kScorePts;
+constexpr int kScoreTrials = 16;               // trials per scoring workgroup (64 poses in LDS)
+constexpr int kViewThreads = 256;              // LO / LM / selection workgroups
+constexpr int kLoIters = 10;
+constexpr int kMaxDraws = 64;
+constexpr double kGradTol = 1e-10;
+constexpr double kStepTol = 1e-12;
+
+static_assert(kRound % kScoreTrials == 0 && kRound % kHypThreads == 0, "round shape");
+
+// ----------------------------------------------------------------------------------------------------------- sample stream
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ int64_t draw_index(uint64_t key, int k, int64_t n) {
+    return (int64_t)(((splitmix64(key + (uint64_t)k) >> 32) * (uint64_t)n) >> 32);
+}
+
+// -------------------------------------------------------------------------------------------------------------- stopping
+__host__ __device__ inline int64_t num_trials(double eps, double confidence, int64_t min_t, int64_t max_t) {
+    if (eps <= 0.0) return max_t;
+    if (eps >= 1.0) return min_t;
+    const double den = log(1.0 - eps * eps * eps);
+    if (den >= 0.0) return max_t;
+    const double n = ceil(log(1.0 - confidence) / den);
+    if (n >= (double)max_t) return min_t > max_t ? min_t : max_t;
+    const int64_t ni = (int64_t)n;
+    return ni < min_t ? min_t : ni;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- P3P
+struct V3 { double x, y, z; };
+__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 scale(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+
+struct S3 { double m00, m01, m02, m11, m12, m22; };        // symmetric 3 x 3
+
+__device__ __forceinline__ double det_cols(V3 c0, V3 c1, V3 c2) {
+    return (c0.x * (c1.y * c2.z - c1.z * c2.y) - c1.x * (c0.y * c2.z - c0.z * c2.y)) + c2.x * (c0.y * c1.z - c0.z * c1.y);
+}
+__device__ __forceinline__ V3 col(const S3& s, int c) {
+    return c == 0 ? V3{s.m00, s.m01, s.m02} : (c == 1 ? V3{s.m01, s.m11, s.m12} : V3{s.m02, s.m12, s.m22});
+}
+__device__ __forceinline__ S3 axpy(const S3& a, double g, const S3& b) {            // a + g b
+    return {a.m00 + g * b.m00, a.m01 + g * b.m01, a.m02 + g * b.m02, a.m11 + g * b.m11, a.m12 + g * b.m12, a.m22 + g * b.m22};
+}
+__device__ __forceinline__ S3 sxpy(double g, const S3& a, const S3& b) {            // g a + b
+    return {g * a.m00 + b.m00, g * a.m01 + b.m01, g * a.m02 + b.m02, g * a.m11 + b.m11, g * a.m12 + b.m12, g * a.m22 + b.m22};
+}
+__device__ __forceinline__ double quad(const S3& o, V3 u, V3 v) {                    // u^T O v
+    const V3 uo = {(u.x * o.m00 + u.y * o.m01) + u.z * o.m02, (u.x * o.m01 + u.y * o.m11) + u.z * o.m12,
+                   (u.x * o.m02 + u.y * o.m12) + u.z * o.m22};
+    return dot(uo, v);
+}
+
+__device__ __forceinline__ double cubic_root(double b, double c, double d) {       // a real root of x^3 + b x^2 + c x + d (largest of three)
+    const double p = c - b * b / 3.0;
+    const double q = (2.0 * b * b * b / 27.0 - b * c / 3.0) + d;
+    const double disc = q * q / 4.0 + p * p * p / 27.0;
+    double x;
+    if (disc > 0.0) {
+        const double s = sqrt(disc);
+        const double u = -q / 2.0 + (q <= 0.0 ? s : -s);
+        const double cu = cbrt(u);
+        x = (cu != 0.0 ? cu - p / (3.0 * cu) : 0.0) - b / 3.0;
+    } else {
+        const double m = sqrt(fmax(-p / 3.0, 0.0));
+        double arg = p < 0.0 ? 3.0 * q / (2.0 * p) * sqrt(-3.0 / p) : 0.0;
+        arg = fmin(fmax(arg, -1.0), 1.0);
+        x = 2.0 * m * cos(acos(arg) / 3.0) - b / 3.0;
+    }
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const double f = ((x + b) * x + c) * x + d;
+        const double df = (3.0 * x + 2.0 * b) * x + c;
+        if (df != 0.0) x = x - f / df;
+    }
+    return x;
+}
+
+__device__ __forceinline__ bool null_vec(const S3& d, double s, V3& out) {         // unit null vector of d - s I
+    const V3 r0 = {d.m00 - s, d.m01, d.m02}, r1 = {d.m01, d.m11 - s, d.m12}, r2 = {d.m02, d.m12, d.m22 - s};
+    const V3 c01 = cross(r0, r1), c02 = cross(r0, r2), c12 = cross(r1, r2);
+    const double n01 = dot(c01, c01), n02 = dot(c02, c02), n12 = dot(c12, c12);
+    // component-wise selects: a select of whole structs becomes a select of their addresses in scratch
+    const bool u01 = n01 >= n02;
+    double bx = u01 ? c01.x : c02.x, by = u01 ? c01.y : c02.y, bz = u01 ? c01.z : c02.z, nb = u01 ? n01 : n02;
+    const bool keep = nb >= n12;
+    bx = keep ? bx : c12.x; by = keep ? by : c12.y; bz = keep ? bz : c12.z; nb = keep ? nb : n12;
+    if (!(nb > 0.0)) return false;
+    out = scale(V3{bx, by, bz}, 1.0 / sqrt(nb));
+    return true;
+}
+
+struct Lam { double a01, a02, a12, b01, b02, b12; };     // the three distance equations
+
+__device__ __forceinline__ double lam_res(double l0, double l1, double l2, const Lam& q, double& r0, double& r1, double& r2) {
+    r0 = ((l0 * l0 + l1 * l1) - 2.0 * q.b01 * l0 * l1) - q.a01;
+    r1 = ((l0 * l0 + l2 * l2) - 2.0 * q.b02 * l0 * l2) - q.a02;
+    r2 = ((l1 * l1 + l2 * l2) - 2.0 * q.b12 * l1 * l2) - q.a12;
+    return (r0 * r0 + r1 * r1) + r2 * r2;
+}
+
+__device__ __forceinline__ void refine_lambda(double& l0, double& l1, double& l2, const Lam& q) {
+    double r0, r1, r2;
+    double e = lam_res(l0, l1, l2, q, r0, r1, r2);
+#pragma unroll
+    for (int it = 0; it < 5; ++it) {
+        const V3 j0 = {2.0 * (l0 - q.b01 * l1), 2.0 * (l0 - q.b02 * l2), 0.0};            // columns of the Jacobian
+        const V3 j1 = {2.0 * (l1 - q.b01 * l0), 0.0, 2.0 * (l1 - q.b12 * l2)};
+        const V3 j2 = {0.0, 2.0 * (l2 - q.b02 * l0), 2.0 * (l2 - q.b12 * l1)};
+        const double det = det_cols(j0, j1, j2);
+        if (det == 0.0 || !isfinite(det)) break;
+        const V3 rv = {r0, r1, r2};
+        const double n0 = l0 - det_cols(rv, j1, j2) / det;
+        const double n1 = l1 - det_cols(j0, rv, j2) / det;
+        const double n2 = l2 - det_cols(j0, j1, rv) / det;
+        double s0, s1, s2;
+        const double en = lam_res(n0, n1, n2, q, s0, s1, s2);
+        if (!(en < e)) break;
+        l0 = n0; l1 = n1; l2 = n2; e = en;
+        r0 = s0; r1 = s1; r2 = s2;
+    }
+}
+
+// orthonormal frame (columns e1, e2, e3) of the triangle edges a, b
+__device__ __forceinline__ bool frame(V3 a, V3 b, V3& e1, V3& e2, V3& e3) {
+    const double na = dot(a, a);
+    if (!(na > 0.0)) return false;
+    e1 = scale(a, 1.0 / sqrt(na));
+    const V3 b2 = sub(b, scale(e1, dot(e1, b)));
+    const double nb = dot(b2, b2);
+    if (!(nb > 0.0)) return false;
+    e2 = scale(b2, 1.0 / sqrt(nb));
+    e3 = cross(e1, e2);
+    return true;
+}
+
+// Lambda Twist (Persson & Nordberg, ECCV 2018).  y: unit bearings, x: world points.  emit(slot, P[12]) for every kept solution,
+// slot = 2 line + root; every array is indexed at compile time (the loops are unrolled).
+template <class Emit>
+__device__ __forceinline__ void p3p_solve(const V3 y[3], const V3 x[3], Emit emit) {
+    const V3 d01 = sub(x[0], x[1]), d02 = sub(x[0], x[2]), d12 = sub(x[1], x[2]);
+    const double a01 = dot(d01, d01), a02 = dot(d02, d02), a12 = dot(d12, d12);
+    const V3 cr = cross(d01, d02);
+    if (!(dot(cr, cr) > 1e-20 * a01 * a02) || !(a01 > 0.0 && a02 > 0.0 && a12 > 0.0)) return;
+    const double b01 = dot(y[0], y[1]), b02 = dot(y[0], y[2]), b12 = dot(y[1], y[2]);
+    // D1 = a12 M01 - a01 M12, D2 = a12 M02 - a02 M12 (M_ij: lambda^T M_ij lambda = |lambda_i y_i - lambda_j y_j|^2)
+    const S3 D1 = {a12, -a12 * b01, 0.0, a12 - a01, a01 * b12, -a01};
+    const S3 D2 = {a12, 0.0, -a12 * b02, -a02, a02 * b12, a12 - a02};
+    const double c0 = det_cols(col(D1, 0), col(D1, 1), col(D1, 2));
+    const double c3 = det_cols(col(D2, 0), col(D2, 1), col(D2, 2));
+    const double c1 = (det_cols(col(D2, 0), col(D1, 1), col(D1, 2)) + det_cols(col(D1, 0), col(D2, 1), col(D1, 2)))
+                      + det_cols(col(D1, 0), col(D1, 1), col(D2, 2));
+    const double c2 = (det_cols(col(D1, 0), col(D2, 1), col(D2, 2)) + det_cols(col(D2, 0), col(D1, 1), col(D2, 2)))
+                      + det_cols(col(D2, 0), col(D2, 1), col(D1, 2));
+    S3 D0, O;
+    if (fabs(c3) >= fabs(c0)) {
+        if (c3 == 0.0) return;
+        const double g = cubic_root(c2 / c3, c1 / c3, c0 / c3);
+        D0 = axpy(D1, g, D2);
+        O = D2;
+    } else {
+        const double g = cubic_root(c1 / c0, c2 / c0, c3 / c0);
+        D0 = sxpy(g, D1, D2);
+        O = D1;
+    }
+    const double tr = (D0.m00 + D0.m11) + D0.m22;
+    const double m2 = ((D0.m00 * D0.m11 - D0.m01 * D0.m01) + (D0.m00 * D0.m22 - D0.m02 * D0.m02)) + (D0.m11 * D0.m22 - D0.m12 * D0.m12);
+    if (!(m2 < 0.0)) return;
+    const double sq = sqrt(fmax(tr * tr - 4.0 * m2, 0.0));
+    double s1, s2;
+    if (tr >= 0.0) { s1 = 0.5 * (tr + sq); s2 = m2 / s1; }
+    else { s2 = 0.5 * (tr - sq); s1 = m2 / s2; }
+    V3 e1, e2;
+    if (!null_vec(D0, s1, e1) || !null_vec(D0, s2, e2)) return;
+    const double r = sqrt(-s2 / s1);
+    const Lam lq = {a01, a02, a12, b01, b02, b12};
+    const int ks = (a01 >= a02 && a01 >= a12) ? 0 : (a02 >= a12 ? 1 : 2);
+    const double Aks = ks == 0 ? a01 : (ks == 1 ? a02 : a12), Bks = ks == 0 ? b01 : (ks == 1 ? b02 : b12);
+#pragma unroll
+    for (int li = 0; li < 2; ++li) {
+        const double sgn = li == 0 ? 1.0 : -1.0;
+        const V3 w = sub(e1, scale(e2, sgn * r));
+        const double aw0 = fabs(w.x), aw1 = fabs(w.y), aw2 = fabs(w.z);
+        const int k = (aw0 >= aw1 && aw0 >= aw2) ? 0 : (aw1 >= aw2 ? 1 : 2);
+        const double wk = k == 0 ? w.x : (k == 1 ? w.y : w.z);
+        const double wi = k == 0 ? w.y : (k == 1 ? w.z : w.x);           // i = k + 1, j = k + 2 (mod 3)
+        const double wj = k == 0 ? w.z : (k == 1 ? w.x : w.y);
+        const double pk = -wi / wk, qk = -wj / wk;
+        const V3 p = {k == 0 ? pk : (k == 2 ? 1.0 : 0.0), k == 1 ? pk : (k == 0 ? 1.0 : 0.0), k == 2 ? pk : (k == 1 ? 1.0 : 0.0)};
+        const V3 q = {k == 0 ? qk : (k == 1 ? 1.0 : 0.0), k == 1 ? qk : (k == 2 ? 1.0 : 0.0), k == 2 ? qk : (k == 0 ? 1.0 : 0.0)};
+        const double qa = quad(O, p, p), qb = quad(O, p, q), qc = quad(O, q, q);
+        const double disc = qb * qb - qa * qc;
+        if (!(disc >= 0.0)) continue;
+        const double qq = -(qb + copysign(sqrt(disc), qb));
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri) {
+            const double tau = ri == 0 ? (qc != 0.0 ? qq / qc : NAN) : (qq != 0.0 ? qa / qq : NAN);
+            if (!isfinite(tau)) continue;
+            const V3 dv = {p.x + tau * q.x, p.y + tau * q.y, p.z + tau * q.z};
+            const double da = ks == 2 ? dv.y : dv.x, db = ks == 0 ? dv.y : dv.z;
+            const double qs = (da * da + db * db) - 2.0 * Bks * da * db;
+            if (!(qs > 0.0)) continue;
+            double sc = sqrt(Aks / qs);
+            if ((dv.x + dv.y) + dv.z < 0.0) sc = -sc;
+            double l0 = sc * dv.x, l1 = sc * dv.y, l2 = sc * dv.z;
+            refine_lambda(l0, l1, l2, lq);
+            if (!(l0 > 0.0 && l1 > 0.0 && l2 > 0.0)) continue;
+            const V3 c0v = scale(y[0], l0), c1v = scale(y[1], l1), c2v = scale(y[2], l2);
+            V3 f1, f2, f3, g1, g2, g3;
+            if (!frame(sub(c0v, c1v), sub(c0v, c2v), f1, f2, f3) || !frame(d01, d02, g1, g2, g3)) continue;
+            // R = Fc Fw^T ;  t = mean(c) - R mean(x)
+            double P[12];
+            const double fc[3][3] = {{f1.x, f2.x, f3.x}, {f1.y, f2.y, f3.y}, {f1.z, f2.z, f3.z}};
+            const double fw[3][3] = {{g1.x, g2.x, g3.x}, {g1.y, g2.y, g3.y}, {g1.z, g2.z, g3.z}};
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) P[4 * a + b] = (fc[a][0] * fw[b][0] + fc[a][1] * fw[b][1]) + fc[a][2] * fw[b][2];
+            const V3 cm = scale({(c0v.x + c1v.x) + c2v.x, (c0v.y + c1v.y) + c2v.y, (c0v.z + c1v.z) + c2v.z}, 1.0 / 3.0);
+            const V3 xm = scale({(x[0].x + x[1].x) + x[2].x, (x[0].y + x[1].y) + x[2].y, (x[0].z + x[1].z) + x[2].z}, 1.0 / 3.0);
+            bool ok = true;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double cma = a == 0 ? cm.x : (a == 1 ? cm.y : cm.z);
+                P[4 * a + 3] = cma - ((P[4 * a] * xm.x + P[4 * a + 1] * xm.y) + P[4 * a + 2] * xm.z);
+            }
+#pragma unroll
+            for (int q2 = 0; q2 < 12; ++q2) ok = ok && isfinite(P[q2]);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) ok = ok && ((P[8] * x[s].x + P[9] * x[s].y) + P[10] * x[s].z) + P[11] > 0.0;
+            if (ok) emit(2 * li + ri, P);
+        }
+    }
+}
+
+__device__ __forceinline__ V3 bearing(double u, double v, const double* __restrict__ K) {
+    const V3 b = {(u - K[2]) / K[0], (v - K[3]) / K[1], 1.0};
+    return scale(b, 1.0 / sqrt(dot(b, b)));
+}
+
+// camera z and squared pixel error of one correspondence (the operation order of tests/pose_restate.py: project_err2)
+__device__ __forceinline__ double project_err2(const double* P, double x, double y, double z, double u, double v, double fx, double fy,
+                                               double cx, double cy, double& Z) {
+    const double X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
+    const double Y = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
+    Z = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+    const double iz = 1.0 / Z;
+    const double du = (fx * (X * iz) + cx) - u;
+    const double dv = (fy * (Y * iz) + cy) - v;
+    return du * du + dv * dv;
+}
+
+__global__ void __launch_bounds__(kHypThreads)
+p3p_kernel(const double* __restrict__ bear, const double* __restrict__ pts, int64_t m, double* __restrict__ poses,
+           int32_t* __restrict__ n_sol) {
+    const int64_t i = (int64_t)blockIdx.x * kHypThreads + threadIdx.x;
+    if (i >= m) return;
+    V3 y[3], x[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        y[s] = {bear[9 * i + 3 * s], bear[9 * i + 3 * s + 1], bear[9 * i + 3 * s + 2]};
+        x[s] = {pts[9 * i + 3 * s], pts[9 * i + 3 * s + 1], pts[9 * i + 3 * s + 2]};
+    }
+    double* __restrict__ out = poses + 48 * i;
+    int n = 0;
+    p3p_solve(y, x, [&](int, const double* P) {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) out[12 * n + q] = P[q];
+        ++n;
+    });
+    for (int q = 12 * n; q < 48; ++q) out[q] = 0.0;
+    n_sol[i] = n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- RANSAC
+struct Ws {                     // workspace layout (ls2fm_absolute_pose_workspace_bytes)
+    double* hyp;                // [V][kRound][4][12]
+    int32_t* valid;             // [V][kRound]   bit s: slot s holds a pose
+    int32_t* counts;            // [V][kRound][4]
+    unsigned long long* best_key;   // [V]
+    double* best_pose;          // [V][12]
+    int32_t* trials;            // [V]
+    int32_t* active;            // [V]
+    int32_t* n_active;          // [1]
+    int32_t* tile_off;          // [V + 1]   first scoring tile of view v (ceil(n_v / kScoreTile) tiles each)
+};
+
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+__host__ __device__ inline size_t ws_layout(int32_t V, char* base, Ws* w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+    char* hyp = take((size_t)V * kRound * 48 * sizeof(double));
+    char* valid = take((size_t)V * kRound * sizeof(int32_t));
+    char* counts = take((size_t)V * kRound * 4 * sizeof(int32_t));
+    char* bk = take((size_t)V * sizeof(unsigned long long));
+    char* bp = take((size_t)V * 12 * sizeof(double));
+    char* tr = take((size_t)V * sizeof(int32_t));
+    char* ac = take((size_t)V * sizeof(int32_t));
+    char* na = take(sizeof(int32_t));
+    char* to = take(((size_t)V + 1) * sizeof(int32_t));
+    if (w) *w = {(double*)hyp, (int32_t*)valid, (int32_t*)counts, (unsigned long long*)bk, (double*)bp, (int32_t*)tr, (int32_t*)ac,
+                 (int32_t*)na, (int32_t*)to};
+    return off;
+}
+
+__global__ void __launch_bounds__(kViewThreads)
+pose_init_kernel(const int32_t* __restrict__ vs, int32_t V, Ws w) {
+    const int v = blockIdx.x * kViewThreads + threadIdx.x;
+    if (v >= V) return;
+    w.best_key[v] = 0ull;
+    w.trials[v] = 0;
+    w.active[v] = (vs[v + 1] - vs[v]) >= 3 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(kHypThreads)
+pose_hyp_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
+                const double* __restrict__ intr, uint64_t seed, Ws w) {
+    const int v = blockIdx.y;
+    if (!w.active[v]) return;
+    const int tl = blockIdx.x * kHypThreads + threadIdx.x;
+    const int64_t slot = (int64_t)v * kRound + tl;
+    int32_t* __restrict__ cnt = w.counts + 4 * slot;
+    cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
+    const uint64_t t = (uint64_t)(w.trials[v] + tl);
+    const uint64_t key = splitmix64(seed ^ splitmix64(t));
+    int64_t i0 = -1, i1 = -1, i2 = -1;
+    for (int k = 0; k < kMaxDraws && i2 < 0; ++k) {
+        const int64_t d = draw_index(key, k, n);
+        if (i0 < 0) i0 = d;
+        else if (i1 < 0) { if (d != i0) i1 = d; }
+        else if (d != i0 && d != i1) i2 = d;
+    }
+    int mask = 0;
+    if (i2 >= 0) {
+        const double* __restrict__ K = intr + 4 * v;
+        const int64_t id[3] = {s0 + i0, s0 + i1, s0 + i2};
+        V3 y[3], x[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            y[s] = bearing(uv[2 * id[s]], uv[2 * id[s] + 1], K);
+            x[s] = {xyz[3 * id[s]], xyz[3 * id[s] + 1], xyz[3 * id[s] + 2]};
+        }
+        double* __restrict__ out = w.hyp + 48 * slot;
+        p3p_solve(y, x, [&](int s, const double* P) {
+#pragma unroll
+            for (int q = 0; q < 12; ++q) out[12 * s + q] = P[q];
+            mask |= 1 << s;
+        });
+    }
+    w.valid[slot] = mask;
+}
+
+__global__ void __launch_bounds__(kScoreThreads)
+pose_score_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
+                  const double* __restrict__ intr, int32_t V, double thr2, Ws w) {
+    // the view of this tile: the last v with tile_off[v] <= blockIdx.x (views without a tile share its offset)
+    const int32_t bx = (int32_t)blockIdx.x;
+    int lo = 0, hi = V;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (w.tile_off[mid] <= bx) lo = mid; else hi = mid;
+    }
+    const int v = lo;
+    if (!w.active[v]) return;
+    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
+    const int64_t base = (int64_t)(bx - w.tile_off[v]) * kScoreTile;
+    if (base >= n) return;
+    __shared__ double s_h[4 * kScoreTrials][12];
+    __shared__ int s_valid[kScoreTrials];
+    __shared__ int s_cnt[4 * kScoreTrials];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t slot0 = (int64_t)v * kRound + (int64_t)blockIdx.y * kScoreTrials;
+    for (int q = tid; q < 4 * kScoreTrials * 12; q += kScoreThreads) s_h[q / 12][q % 12] = w.hyp[48 * slot0 + q];
+    if (tid < kScoreTrials) s_valid[tid] = w.valid[slot0 + tid];
+    if (tid < 4 * kScoreTrials) s_cnt[tid] = 0;
+    const double fx = intr[4 * v], fy = intr[4 * v + 1], cx = intr[4 * v + 2], cy = intr[4 * v + 3];
+    double px[kScorePts], py[kScorePts], pz[kScorePts], pu[kScorePts], pv[kScorePts];
+    bool live[kScorePts];
+#pragma unroll
+    for (int k = 0; k < kScorePts; ++k) {
+        const int64_t j = base + tid + (int64_t)k * kScoreThreads;
+        live[k] = j < n;
+        const int64_t i = s0 + (live[k] ? j : 0);
+        px[k] = xyz[3 * i]; py[k] = xyz[3 * i + 1]; pz[k] = xyz[3 * i + 2];
+        pu[k] = uv[2 * i]; pv[k] = uv[2 * i + 1];
+    }
+    __syncthreads();
+    for (int h = 0; h < 4 * kScoreTrials; ++h) {
+        if (!((s_valid[h >> 2] >> (h & 3)) & 1)) continue;
+        const double* P = s_h[h];
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < kScorePts; ++k) {
+            double Z;
+            const double e2 = project_err2(P, px[k], py[k], pz[k], pu[k], pv[k], fx, fy, cx, cy, Z);
+            c += __popcll(__ballot(live[k] && Z > 0.0 && e2 < thr2));
+        }
+        if (lane == 0 && c) atomicAdd(&s_cnt[h], c);
+    }
+    __syncthreads();
+    if (tid < 4 * kScoreTrials && s_cnt[tid]) atomicAdd(&w.counts[4 * slot0 + tid], s_cnt[tid]);
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(k, o, 64);
+        k = t > k ? t : k;
+    }
+    return k;
+}
+
+__global__ void __launch_bounds__(kViewThreads)
+pose_select_kernel(const int32_t* __restrict__ vs, double confidence, int64_t min_trials, int64_t max_trials, Ws w) {
+    const int v = blockIdx.x;
+    if (!w.active[v]) return;
+    const int tid = threadIdx.x;
+    __shared__ unsigned long long s_k[kViewThreads / 64];
+    const int32_t t0 = w.trials[v];
+    unsigned long long best = 0ull;
+    for (int c = tid; c < 4 * kRound; c += kViewThreads) {
+        const int64_t slot = (int64_t)v * kRound + (c >> 2);
+        const int cnt = w.counts[4 * slot + (c & 3)];
+        if (cnt > 0 && ((w.valid[slot] >> (c & 3)) & 1)) {
+            const uint32_t idx = (uint32_t)(t0 + (c >> 2)) * 4u + (uint32_t)(c & 3);
+            const unsigned long long key = ((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+            best = key > best ? key : best;
+        }
+    }
+    best = wave_max_u64(best);
+    if ((tid & 63) == 0) s_k[tid >> 6] = best;
+    __syncthreads();
+    if (tid != 0) return;
+    for (int q = 0; q < kViewThreads / 64; ++q) best = s_k[q] > best ? s_k[q] : best;
+    if (best > w.best_key[v]) {
+        w.best_key[v] = best;
+        const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
+        const int64_t slot = (int64_t)v * kRound + (int64_t)(idx / 4u - (uint32_t)t0);
+        for (int q = 0; q < 12; ++q) w.best_pose[12 * v + q] = w.hyp[48 * slot + 12 * (idx & 3u) + q];
+    }
+    const int32_t done = t0 + kRound;
+    w.trials[v] = done;
+    const double eps = (double)(w.best_key[v] >> 32) / (double)(vs[v + 1] - vs[v]);
+    const bool on = done < num_trials(eps, confidence, min_trials, max_trials);
+    w.active[v] = on ? 1 : 0;
+    if (on) atomicAdd(w.n_active, 1);
+}
+
+// -------------------------------------------------------------------------------------------------------- least squares
+constexpr int kNe = 21 + 6 + 3;          // upper triangle of H, g, then {F or count, changed, unused}
+
+__device__ __forceinline__ void block_sum(double (&a)[kNe], double* s_red /* [kViewThreads / 64][kNe] */) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) {
+        double t = a[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        a[q] = t;
+    }
+    __syncthreads();
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int q = 0; q < kNe; ++q) s_red[(tid >> 6) * kNe + q] = a[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) {
+        double t = s_red[q];
+#pragma unroll
+        for (int wv = 1; wv < kViewThreads / 64; ++wv) t += s_red[wv * kNe + q];
+        a[q] = t;
+    }
+}
+
+// one correspondence's contribution: weight w, residual (du, dv), Jacobian rows through d p / d(w, dt) = [-[p]x | I]
+__device__ __forceinline__ void accumulate(double (&a)[kNe], const double* P, double x, double y, double z, double u, double v,
+                                           double fx, double fy, double cx, double cy, double c2, bool robust) {
+    const double X = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
+    const double Y = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
+    const double Z = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
+    const double iz = 1.0 / Z;
+    const double du = (fx * (X * iz) + cx) - u;
+    const double dv = (fy * (Y * iz) + cy) - v;
+    const double s = du * du + dv * dv;
+    const double w = robust ? 1.0 / (1.0 + s / c2) : 1.0;
+    a[27] += robust ? 0.5 * (c2 * log1p(s / c2)) : 0.5 * s;
+    const double ju0 = fx * iz, ju2 = -fx * X * iz * iz;
+    const double jv1 = fy * iz, jv2 = -fy * Y * iz * iz;
+    // p x ju, p x jv  (ju = (ju0, 0, ju2), jv = (0, jv1, jv2))
+    const double Ju[6] = {Y * ju2, Z * ju0 - X * ju2, -Y * ju0, ju0, 0.0, ju2};
+    const double Jv[6] = {Y * jv2 - Z * jv1, -X * jv2, X * jv1, 0.0, jv1, jv2};
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) a[q++] += w * (Ju[r] * Ju[c]) + w * (Jv[r] * Jv[c]);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) a[21 + r] += w * (Ju[r] * du) + w * (Jv[r] * dv);
+}
+
+// solve (H + damp diag) x = b by Cholesky; H as the 21-entry upper triangle of a
+__device__ inline bool chol_solve(const double (&a)[kNe], double lam, const double* dg, double (&x)[6]) {
+    double L[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) L[c][r] = a[q++] + (r == c ? lam * dg[r] : 0.0);       // lower triangle of the matrix
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        ok = ok && d > 0.0;
+        const double ljj = sqrt(d > 0.0 ? d : 1.0);
+        L[j][j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double s = L[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            L[i][j] = s / ljj;
+        }
+    }
+    double z[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = -a[21 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= L[i][k] * z[k];
+        z[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) s -= L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && isfinite(x[i]);
+    return ok;
+}
+
+// R <- exp([w]x) R, t <- exp([w]x) t + dt
+__device__ inline void pose_update(const double* P, const double (&d)[6], double* C) {
+    const double w0 = d[0], w1 = d[1], w2 = d[2];
+    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
+    double A = 1.0, Bc = 0.0;
+    if (th2 >= 1e-30) {
+        const double th = sqrt(th2);
+        A = sin(th) / th;
+        Bc = (1.0 - cos(th)) / th2;
+    }
+    const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+    double E[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double kk = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+            E[i][j] = ((i == j ? 1.0 : 0.0) + A * K[i][j]) + Bc * kk;
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) C[4 * i + j] = (E[i][0] * P[j] + E[i][1] * P[4 + j]) + E[i][2] * P[8 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) C[4 * i + 3] += d[3 + i];
+}
+
+// one pass of the LO loop: counts, changed and the normal equations (w = 1) over the inliers of C; changed against P
+__device__ inline void lo_pass(const double* __restrict__ uv, const double* __restrict__ xyz, int64_t s0, int64_t n, const double* C,
+                               const double* P, bool cmp, double fx, double fy, double cx, double cy, double thr2, double (&a)[kNe],
+                               double* s_red) {
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) a[q] = 0.0;
+    double cnt = 0.0, chg = 0.0;
+    for (int64_t j = threadIdx.x; j < n; j += kViewThreads) {
+        const int64_t i = s0 + j;
+        const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2], u = uv[2 * i], v = uv[2 * i + 1];
+        double Z;
+        const bool in = project_err2(C, x, y, z, u, v, fx, fy, cx, cy, Z) < thr2 && Z > 0.0;
+        if (cmp) {
+            double Zp;
+            const bool inp = project_err2(P, x, y, z, u, v, fx, fy, cx, cy, Zp) < thr2 && Zp > 0.0;
+            chg += in != inp ? 1.0 : 0.0;
+        }
+        if (in) {
+            accumulate(a, C, x, y, z, u, v, fx, fy, cx, cy, 1.0, false);
+            cnt += 1.0;
+        }
+    }
+    a[27] = cnt;
+    a[28] = chg;
+    block_sum(a, s_red);
+}
+
+__global__ void __launch_bounds__(kViewThreads)
+pose_lo_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
+               const double* __restrict__ intr, double thr2, Ws w, double* __restrict__ poses, uint8_t* __restrict__ inliers,
+               int32_t* __restrict__ num_inliers, int32_t* __restrict__ trials, int32_t* __restrict__ best_trial,
+               int32_t* __restrict__ success) {
+    __shared__ double s_red[(kViewThreads / 64) * kNe];
+    const int v = blockIdx.x, tid = threadIdx.x;
+    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
+    const double fx = intr[4 * v], fy = intr[4 * v + 1], cx = intr[4 * v + 2], cy = intr[4 * v + 3];
+    const unsigned long long bk = w.best_key[v];
+    double P[12];
+    if (bk == 0ull) {
+        for (int64_t j = tid; j < n; j += kViewThreads) inliers[s0 + j] = 0;
+        if (tid < 12) poses[12 * v + tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+        if (tid == 0) { num_inliers[v] = 0; trials[v] = w.trials[v]; best_trial[v] = -1; success[v] = 0; }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) P[q] = w.best_pose[12 * v + q];
+    double a[kNe], b[kNe];
+    lo_pass(uv, xyz, s0, n, P, P, false, fx, fy, cx, cy, thr2, a, s_red);
+    for (int it = 0; it < kLoIters; ++it) {
+        if (a[27] < 3.0) break;
+        double d[6];
+        const double zero[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (!chol_solve(a, 0.0, zero, d)) break;
+        double C[12];
+        pose_update(P, d, C);
+        lo_pass(uv, xyz, s0, n, C, P, true, fx, fy, cx, cy, thr2, b, s_red);
+        if (b[27] < a[27]) break;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) P[q] = C[q];
+#pragma unroll
+        for (int q = 0; q < kNe; ++q) a[q] = b[q];
+        if (b[28] == 0.0) break;
+    }
+    for (int64_t j = tid; j < n; j += kViewThreads) {
+        const int64_t i = s0 + j;
+        double Z;
+        const bool in = project_err2(P, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], uv[2 * i], uv[2 * i + 1], fx, fy, cx, cy, Z) < thr2
+                        && Z > 0.0;
+        inliers[i] = in ? 1 : 0;
+    }
+    if (tid < 12) poses[12 * v + tid] = P[tid];
+    if (tid == 0) {
+        const int32_t cnt = (int32_t)a[27];
+        num_inliers[v] = cnt;
+        trials[v] = w.trials[v];
+        best_trial[v] = (int32_t)((0xFFFFFFFFu - (uint32_t)(bk & 0xFFFFFFFFull)) / 4u);
+        success[v] = cnt >= 4 ? 1 : 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ refinement
+__device__ inline void lm_pass(const double* __restrict__ uv, const double* __restrict__ xyz, const uint8_t* __restrict__ mask, int64_t s0,
+                               int64_t n, const double* P, double fx, double fy, double cx, double cy, double c2, double (&a)[kNe],
+                               double* s_red) {
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) a[q] = 0.0;
+    for (int64_t j = threadIdx.x; j < n; j += kViewThreads) {
+        const int64_t i = s0 + j;
+        if (mask[i]) accumulate(a, P, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], uv[2 * i], uv[2 * i + 1], fx, fy, cx, cy, c2, true);
+    }
+    block_sum(a, s_red);
+}
+
+// mask: per correspondence; ok (NULL = every view): refine view v only when ok[v] != 0 (else copy)
+__global__ void __launch_bounds__(kViewThreads)
+pose_lm_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
+               const double* __restrict__ intr, const uint8_t* __restrict__ mask, const double* poses_in, const int32_t* __restrict__ ok,
+               double c2, int max_iters, double* poses_out) {
+    __shared__ double s_red[(kViewThreads / 64) * kNe];
+    const int v = blockIdx.x, tid = threadIdx.x;
+    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
+    const double fx = intr[4 * v], fy = intr[4 * v + 1], cx = intr[4 * v + 2], cy = intr[4 * v + 3];
+    double P[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) P[q] = poses_in[12 * v + q];
+    int cnt = 0;
+    for (int64_t j = tid; j < n; j += kViewThreads) cnt += mask[s0 + j] ? 1 : 0;
+    __shared__ int s_cnt;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    const bool run = s_cnt >= 3 && (ok == nullptr || ok[v] != 0);
+    double lam = 1e-4;
+    for (int it = 0; run && it < max_iters; ++it) {
+        double a[kNe], b[kNe];
+        lm_pass(uv, xyz, mask, s0, n, P, fx, fy, cx, cy, c2, a, s_red);
+        double gmax = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) gmax = fmax(gmax, fabs(a[21 + r]));
+        if (gmax <= kGradTol) break;
+        const int di[6] = {0, 6, 11, 15, 18, 20};           // diagonal entries of the upper triangle
+        double dmax = 0.0, dg[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) dmax = fmax(dmax, a[di[r]]);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) dg[r] = fmax(a[di[r]], 1e-12 * dmax);
+        double d[6];
+        if (!chol_solve(a, lam, dg, d)) {
+            lam *= 10.0;
+            if (lam > 1e32) break;
+            continue;
+        }
+        double C[12];
+        pose_update(P, d, C);
+        lm_pass(uv, xyz, mask, s0, n, C, fx, fy, cx, cy, c2, b, s_red);
+        if (b[27] < a[27]) {
+#pragma unroll
+            for (int q = 0; q < 12; ++q) P[q] = C[q];
+            lam = fmax(lam * 0.1, 1e-16);
+            double dm = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) dm = fmax(dm, fabs(d[r]));
+            const double tm = fmax(fmax(fabs(P[3]), fabs(P[7])), fabs(P[11]));
+            if (dm <= kStepTol * (1.0 + tm)) break;
+        } else {
+            lam *= 10.0;
+            if (lam > 1e32) break;
+        }
+    }
+    if (tid < 12) poses_out[12 * v + tid] = P[tid];
+}
+
+bool opts_ok(const ls2fm_pose_ransac_opts* o) {
+    return o && o->max_error_px > 0.0 && std::isfinite(o->max_error_px) && o->confidence > 0.0 && o->confidence < 1.0 &&
+           o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio < 1.0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 &&
+           o->max_num_trials <= LS2FM_POSE_MAX_TRIALS && o->min_num_trials <= o->max_num_trials && (o->refine == 0 || o->refine == 1);
+}
+
+}  // namespace
+
+extern "C" int ls2fm_p3p(const double* bearings, const double* points, int64_t m, double* poses, int32_t* n_solutions, void* stream) {
+    LS2FM_CHECK_ARG(m >= 0);
+    if (m == 0) return LS2FM_OK;
+    LS2FM_CHECK_ARG(bearings && points && poses && n_solutions);
+    p3p_kernel<<<(unsigned)((m + kHypThreads - 1) / kHypThreads), kHypThreads, 0, (hipStream_t)stream>>>(bearings, points, m, poses,
+                                                                                                      n_solutions);
+    return ls2fm_launch_status();
+}
+
+extern "C" int64_t ls2fm_absolute_pose_workspace_bytes(int32_t n_views, int64_t n_corr) {
+    if (n_views < 1 || n_views > LS2FM_POSE_MAX_VIEWS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
+    return (int64_t)ws_layout(n_views, nullptr, nullptr);
+}
+
+extern "C" int ls2fm_absolute_pose(const double* uv, const double* xyz, const int32_t* view_start, int32_t n_views, const double* intr,
+                                   const ls2fm_pose_ransac_opts* opts, double* poses, uint8_t* inliers, int32_t* num_inliers,
+                                   int32_t* trials, int32_t* best_trial, int32_t* success, void* workspace, void* stream) {
+    LS2FM_CHECK_ARG(n_views >= 1 && n_views <= LS2FM_POSE_MAX_VIEWS && view_start && intr && opts_ok(opts));
+    LS2FM_CHECK_ARG(poses && num_inliers && trials && best_trial && success);
+    if (!workspace) return LS2FM_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    // the views' extents, on the host: the grid of the scoring pass and the argument checks (the call synchronises)
+    int32_t* h_vs = (int32_t*)malloc(sizeof(int32_t) * ((size_t)n_views + 1));
+    if (!h_vs) return LS2FM_ERR_LAUNCH;
+    if (hipMemcpyAsync(h_vs, view_start, sizeof(int32_t) * ((size_t)n_views + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        free(h_vs);
+        return ls2fm_launch_status();
+    }
+    // per-view scoring tile offsets, reusing the host copy (view_start[v] <= ... fits int32, so do the tile counts)
+    int64_t max_n = 0;
+    bool mono = h_vs[0] >= 0;
+    int32_t tiles = 0;
+    for (int v = 0; v < n_views; ++v) {
+        mono = mono && h_vs[v + 1] >= h_vs[v];
+        const int64_t nv = (int64_t)h_vs[v + 1] - h_vs[v];
+        max_n = std::max<int64_t>(max_n, nv);
+        h_vs[v] = tiles;
+        tiles += mono ? (int32_t)((nv + kScoreTile - 1) / kScoreTile) : 0;
+    }
+    const int64_t total = h_vs[n_views];
+    h_vs[n_views] = tiles;
+    if (!(mono && (total == 0 || (uv && xyz && inliers)))) {
+        free(h_vs);
+        return LS2FM_ERR_INVALID_ARGUMENT;
+    }
+    Ws w;
+    ws_layout(n_views, (char*)workspace, &w);
+    const bool copied = hipMemcpyAsync(w.tile_off, h_vs, sizeof(int32_t) * ((size_t)n_views + 1), hipMemcpyHostToDevice, s) == hipSuccess &&
+                        hipStreamSynchronize(s) == hipSuccess;
+    free(h_vs);
+    if (!copied) return ls2fm_launch_status();
+    const double thr2 = opts->max_error_px * opts->max_error_px;
+    // the trial cap, and min_num_trials above it lowered to it (the cap wins, as in COLMAP's RANSAC)
+    const int64_t cap = num_trials(opts->min_inlier_ratio, opts->confidence, 0, opts->max_num_trials);
+    const int64_t min_trials = std::min<int64_t>(opts->min_num_trials, cap);
+    pose_init_kernel<<<(unsigned)((n_views + kViewThreads - 1) / kViewThreads), kViewThreads, 0, s>>>(view_start, n_views, w);
+    int st = ls2fm_launch_status();
+    if (st != LS2FM_OK) return st;
+    const int64_t max_rounds = (cap + kRound - 1) / kRound;          // N <= cap: every view has stopped after these
+    for (int64_t r = 0; max_n >= 3 && r < max_rounds; ++r) {
+        pose_hyp_kernel<<<dim3(kRound / kHypThreads, (unsigned)n_views), kHypThreads, 0, s>>>(uv, xyz, view_start, intr, opts->seed, w);
+        pose_score_kernel<<<dim3((unsigned)tiles, kRound / kScoreTrials), kScoreThreads, 0, s>>>(uv, xyz, view_start, intr, n_views, thr2,
+                                                                                                w);
+        if (hipMemsetAsync(w.n_active, 0, sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
+        pose_select_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(view_start, opts->confidence, min_trials, cap, w);
+        if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
+        int32_t h_active = 0;
+        if (hipMemcpyAsync(&h_active, w.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return ls2fm_launch_status();
+        if (h_active == 0) break;
+    }
+    pose_lo_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(uv, xyz, view_start, intr, thr2, w, poses, inliers, num_inliers, trials,
+                                                              best_trial, success);
+    if (opts->refine)
+        pose_lm_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(uv, xyz, view_start, intr, inliers, poses, success, 1.0,
+                                                                  LS2FM_POSE_REFINE_ITERS, poses);
+    return ls2fm_launch_status();
+}
+
+extern "C" int ls2fm_pose_refine(const double* uv, const double* xyz, const int32_t* view_start, int32_t n_views, const double* intr,
+                                 const uint8_t* mask, const double* poses_in, float loss_scale_px, int32_t max_iters, double* poses_out,
+                                 void* stream) {
+    LS2FM_CHECK_ARG(n_views >= 1 && n_views <= LS2FM_POSE_MAX_VIEWS && view_start && intr && poses_in && poses_out);
+    LS2FM_CHECK_ARG(loss_scale_px > 0.f && std::isfinite(loss_scale_px) && max_iters >= 0);
+    LS2FM_CHECK_ARG(uv && xyz && mask);
+    const double c = (double)loss_scale_px;
+    pose_lm_kernel<<<(unsigned)n_views, kViewThreads, 0, (hipStream_t)stream>>>(uv, xyz, view_start, intr, mask, poses_in, nullptr, c * c,
+                                                                                max_iters, poses_out);
+    return ls2fm_launch_status();
+}

@@ -98,6 +98,12 @@ class RenderOpts(Structure):
                 ("group_events", c_void_p * 4), ("loss_inputs_ready", c_void_p), ("depth_grad_ready", c_void_p), ("depth_bwd", POINTER(DepthBackward))]
 
 
+class PoseRansacOpts(Structure):
+    """ls2fm_pose_ransac_opts"""
+    _fields_ = [("max_error_px", c_double), ("confidence", c_double), ("min_inlier_ratio", c_double), ("min_num_trials", c_int64),
+                ("max_num_trials", c_int64), ("seed", ctypes.c_uint64), ("refine", c_int32)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)        -- must list every symbol include/ls2fm.h declares
@@ -175,6 +181,10 @@ _SIGNATURES = {
     "ls2fm_surface_pts_bwd": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "ls2fm_match_term_fwd": (c_int32, [_P, _P, _P, _P, POINTER(c_float), c_int32, c_int64, _P, _P, _P, _P, _P]),
     "ls2fm_match_term_bwd": (c_int32, [_P, _P, _P, _P, POINTER(c_float), c_int32, c_int64, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_p3p": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
+    "ls2fm_absolute_pose_workspace_bytes": (c_int64, [c_int32, c_int64]),
+    "ls2fm_absolute_pose": (c_int32, [_P, _P, _P, c_int32, _P, POINTER(PoseRansacOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_pose_refine": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, c_float, c_int32, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),
