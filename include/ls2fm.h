@@ -745,6 +745,79 @@ int ls2fm_pose_refine(const double* uv, const double* xyz, const int32_t* view_s
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Relative pose (csrc/relative_pose.hip): what Initializer asks of pycolmap (pipelines/Initialization.py:86-95,
+ * essential_matrix_estimation) and the _Trad drivers of cv2 (triangulatePoints), for many view pairs in one call.  All geometry in
+ * fp64.  Normalised image point of pixel (u, v) under (fx, fy, cx, cy): x = ((u - cx) / fx, (v - cy) / fy).  E (row-major 3 x 3)
+ * maps camera 1 to camera 2: x2h^T E x1h = 0 for X2 = R X1 + t, E ~ [t]x R.  Correspondences are sorted by pair: pair p owns
+ * [pair_start[p], pair_start[p + 1]) of uv0 / uv1 [n][2] (DEVICE int32 [n_pairs + 1], non-decreasing, the ragged convention of
+ * ls2fm_absolute_pose's view_start); intr0 / intr1 [n_pairs][4] are each pair's two cameras.  tests/relpose_restate.py repeats
+ * every rule below in numpy.
+ *
+ * ls2fm_five_point: m minimal problems, x1 / x2 [m][5][2] normalised points -> up to 10 essential matrices E [m][10][3][3] (the
+ * kept ones first, zero beyond) and n_solutions [m].  Nister (CVPR 2003 / PAMI 2004) as COLMAP implements it:
+ *   null space  Gauss-Jordan with partial pivoting on the 5 x 9 rows kron((x2, 1), (x1, 1)); a column whose largest remaining
+ *               |entry| is <= 1e-12 of the matrix's largest is free; rank != 5 gives 0 solutions.  Basis vector j (free column
+ *               f_j, ascending): 1 at f_j, -R[i][f_j] at pivot column i; modified Gram-Schmidt in order j = 0..3 -> X, Y, Z, W.
+ *   constraints E = x X + y Y + z Z + W; det E = 0 and 2 E E^T E - tr(E E^T) E = 0 as a 10 x 20 matrix over the cubic monomials
+ *               x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.
+ *   elimination Gauss-Jordan with partial pivoting of the left 10 x 10 block (pivot <= 1e-14 of the largest entry: 0 solutions)
+ *               -> [I | AA]; B(z) [x y 1]^T = 0 from rows (x^2z, x^2), (y^2z, y^2), (xyz, xy) as <e> - z <f> (degrees 3, 3, 4).
+ *   roots       det B(z), degree 10 (ascending coefficients, each Sturm polynomial divided by its largest |coefficient|): the
+ *               Sturm sequence p0, p0', -rem(...) (a remainder's trailing coefficients with |c| <= LS2FM_STURM_TRIM are dropped),
+ *               the Cauchy bound 1 + max |c_i / c_d|, the k-th real root by bisection on the sign-variation count (at most 100
+ *               halvings, until the bracket is <= LS2FM_BISECT_TOL max(1, |lo|, |hi|)), then <= 5 Newton steps on p0 that stay
+ *               inside the bracket.  No eigen solve.
+ *   recovery    per root z (ascending): the unit null vector of B(z) (the largest cross product of two rows), skipped when
+ *               |X_3| < 1e-10; E = x X + y Y + z Z + W with x = X_1 / X_3, y = X_2 / X_3, scaled to unit Frobenius norm with its
+ *               largest |entry| (the first of equals, row-major) positive.  Non-finite solutions are dropped.
+ *   Degenerate samples (coincident points, a rank-deficient system) give 0 solutions, never NaN.
+ *
+ * ls2fm_relative_pose: LO-RANSAC per pair.
+ *   samples   ls2fm_absolute_pose's SplitMix64 stream keyed by (seed, trial); the sample is the first FIVE distinct draws among
+ *             k = 0 .. 63 (none: the trial has no model).
+ *   hypotheses ls2fm_five_point of the sample; slot s = the solution's place (0..9).
+ *   scoring   squared Sampson error in normalised coordinates, (x2h^T E x1h)^2 / ((E x1h)_1^2 + (E x1h)_2^2 + (E^T x2h)_1^2 +
+ *             (E^T x2h)_2^2); an inlier when it is <= max_error^2, max_error = 0.5 (max_error_px / f1 + max_error_px / f2), f the
+ *             camera's (fx + fy) / 2 (COLMAP).  Counts are exact integers.
+ *   selection the 64-bit max of (count << 32 | ~(t * 10 + s)): the best count, then the lowest t * 10 + s.
+ *   rounds    as ls2fm_absolute_pose with eps^5 for eps^3: N = clamp(ceil(log(1 - confidence) / log(1 - eps^5)), min(min_num_trials,
+ *             cap), cap); the cap wins over min_num_trials.  The call SYNCHRONISES (one word per round) and is not capturable.
+ *   local optimisation from the best E, up to 10 times while >= 5 inliers: the 9 x 9 normal matrix of the inliers' rows
+ *             kron((x2, 1), (x1, 1)) (fixed-order sum), its eigenvectors by cyclic Jacobi (<= 30 sweeps), the four of the smallest
+ *             eigenvalues (the lower index first among equals) as W, Z, Y, X, the five-point steps above from the constraints on;
+ *             each candidate is recounted, the best (count, then lowest slot) is kept when its count is >= the current one, and
+ *             the loop stops when it is lower, when there is no candidate, or when the inlier set did not change.
+ *   pose      COLMAP's PoseFromEssentialMatrix: E = U diag V^T (one-sided Jacobi; U, V proper), R1 = U W V^T, R2 = U W^T V^T,
+ *             t = U col 3, W = [0 1 0; -1 0 0; 0 0 1]; candidates (R1, t), (R2, t), (R1, -t), (R2, -t); each inlier is
+ *             triangulated (ls2fm_triangulate's DLT with [I | 0] and [R | t]) and counted when its depth is in
+ *             (DBL_EPSILON, 1000 |R^T t|) in both cameras; the candidate with the most points wins (ties: the later one).
+ *   outputs   E [P][3][3], poses [P][3][4] = [R | t] (X2 = R X1 + t, |t| = 1), inliers (uint8) of the final E, num_inliers,
+ *             trials, best_trial (the winning SAMPLED trial, -1 when none), success = num_inliers >= 5 and >= 1 point in front.
+ *             A failing pair gets the identity pose (E zero when no hypothesis had an inlier), without touching its neighbours;
+ *             every bit depends on the pair's own data, seed and options only.
+ *   options   ls2fm_pose_ransac_opts with refine == 0 (no refinement is defined for E); otherwise as ls2fm_absolute_pose;
+ *             1 <= n_pairs <= LS2FM_RELPOSE_MAX_PAIRS.  A refusal returns LS2FM_ERR_INVALID_ARGUMENT and launches nothing.
+ *             workspace: ls2fm_relative_pose_workspace_bytes (~780 KB per pair; n_corr does not change it).
+ *
+ * ls2fm_triangulate: two-view DLT of n points, one thread each: P0 / P1 [n_pairs][3][4] (any projection matrices), pixel pairs
+ * uv0 / uv1 [n][2] sorted by pair (pair_start as above) -> X [n][4] homogeneous.  A = the 4 x 4 of cv2.triangulatePoints (rows
+ * u P[2] - P[0], v P[2] - P[1] of each view); the right singular vector of its smallest singular value by one-sided Jacobi on A
+ * (<= 30 sweeps; rotations while |a_p . a_q| > 1e-15 |a_p| |a_q|), unit norm, w >= 0 (cv2's up to sign).  Capturable.
+ */
+#define LS2FM_FIVE_POINT_MAX_SOLUTIONS 10
+#define LS2FM_RELPOSE_MAX_PAIRS 65535
+#define LS2FM_STURM_TRIM 1e-14
+#define LS2FM_BISECT_TOL 1e-10
+
+int ls2fm_five_point(const double* x1, const double* x2, int64_t m, double* E, int32_t* n_solutions, void* stream);
+int64_t ls2fm_relative_pose_workspace_bytes(int32_t n_pairs, int64_t n_corr);
+int ls2fm_relative_pose(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs, const double* intr0,
+                        const double* intr1, const ls2fm_pose_ransac_opts* opts, double* E, double* poses, uint8_t* inliers,
+                        int32_t* num_inliers, int32_t* trials, int32_t* best_trial, int32_t* success, void* workspace, void* stream);
+int ls2fm_triangulate(const double* P0, const double* P1, const double* uv0, const double* uv1, const int32_t* pair_start,
+                      int32_t n_pairs, int64_t n, double* X, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -1,0 +1,1198 @@
+// Relative pose of many view pairs in one call: LO-RANSAC over Nister's five-point algorithm, pose recovery by cheirality, and a
+// batched two-view DLT -- what Initializer asks of pycolmap (essential_matrix_estimation, pipelines/Initialization.py:86-95) and
+// the _Trad drivers of cv2 (triangulatePoints), all geometry in fp64.  include/ls2fm.h states the rules; tests/relpose_restate.py
+// repeats them in numpy.  Correspondences are SORTED BY PAIR (pair p owns [pair_start[p], pair_start[p + 1])).
+//
+//   per round (host loop; a pair stops once its trial count reaches the stopping rule's N):
+//     rel_hyp_kernel     one thread per (pair, trial): five distinct indices from the SplitMix64 stream, five-point, <= 10 E
+//     rel_score_kernel   (1024-correspondence tile of some pair, 16-trial block): inlier counts of the block's 160 E over the
+//                        tile (squared Sampson error), wave ballots + integer atomics; tiles of all pairs in one flat range
+//     rel_select_kernel  one workgroup per pair: the best (count, lowest trial * 10 + slot) as a 64-bit max, the stopping rule
+//   then rel_final_kernel: local optimisation (five-point on the inlier set's normal matrix), the final mask and the pose
+//   recovery, one workgroup per pair with fixed-order reductions: every bit is a function of the pair's own data, seed and options.
+//
+// The five-point solver's per-problem state (null-space basis 36, quadratic terms 70, the 10 x 20 cubic-constraint matrix 200:
+// kWords fp64 words) is a column of LDS: word k of thread j sits at s_buf[k * kFpThreads + j], so every run-time index (pivot
+// rows, polynomial degrees, the Sturm sequence) addresses LDS, never a private array, and no kernel of this file uses scratch.
+// 32 threads per workgroup: kWords x 32 x 8 B = 78 KB, two workgroups per CU.
+#include "ls2fm_device.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+#define HD __host__ __device__
+
+constexpr int kRound = LS2FM_POSE_ROUND;      // trials per pair per round (1024)
+constexpr int kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS;   // 10
+constexpr int kFpThreads = 32;                 // five-point workgroups (hypotheses, ls2fm_five_point)
+constexpr int kScoreThreads = 256;
+constexpr int kScorePts = 4;
+constexpr int kScoreTile = kScoreThreads * kScorePts;
+constexpr int kScoreTrials = 16;               // trials per scoring workgroup (160 E in LDS)
+constexpr int kPairThreads = 256;              // selection / final workgroups
+constexpr int kTriThreads = 256;
+constexpr int kLoIters = 10;
+constexpr int kMaxDraws = 64;
+constexpr int kBisectIters = 100;
+constexpr int kNewtonIters = 5;
+constexpr int kJacobiSweeps = 30;
+
+// LDS words of one five-point solve
+constexpr int kBas = 0;          // basis X, Y, Z, W: 4 x 9 (E = x X + y Y + z Z + W, row-major 3 x 3)
+constexpr int kQ = 36;           // E E^T upper triangle, 6 quadratics x 10, trace 10; later minors (3 x 10), then B (3 x 13)
+constexpr int kA = 106;          // the 10 x 20 matrix; the 5 x 9 system before it; the Sturm sequence after it
+constexpr int kWords = 306;
+constexpr int kSeq = kA;         // Sturm sequence: polynomial k (capacity 11 - k) at kSeq + 11 k - k (k - 1) / 2, 66 words
+constexpr int kDeg = kA + 66;    // their degrees (11)
+constexpr int kRoot = kA + 77;   // real roots (10)
+constexpr int kTmp = kA + 100;   // scratch polynomials (minors of B, the long division's dividend), pivot columns
+
+static_assert(kRound % kScoreTrials == 0 && kRound % kFpThreads == 0, "round shape");
+
+HD inline bool is_finite(double x) { return x - x == 0.0; }       // host and device alike (inf - inf and NaN are NaN)
+
+template <int S>
+struct Col {                     // one solve's words in LDS, stride S
+    double* p;
+    HD double& operator[](int k) const { return p[k * S]; }
+};
+
+// ----------------------------------------------------------------------------------------------------------- sample stream
+HD inline uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+HD inline int64_t draw_index(uint64_t key, int k, int64_t n) {
+    return (int64_t)(((splitmix64(key + (uint64_t)k) >> 32) * (uint64_t)n) >> 32);
+}
+
+// -------------------------------------------------------------------------------------------------------------- stopping
+HD inline int64_t num_trials(double eps, double confidence, int64_t min_t, int64_t max_t) {
+    if (eps <= 0.0) return max_t;
+    if (eps >= 1.0) return min_t;
+    const double den = log(1.0 - eps * eps * eps * eps * eps);
+    if (den >= 0.0) return max_t;
+    const double n = ceil(log(1.0 - confidence) / den);
+    if (n >= (double)max_t) return min_t > max_t ? min_t : max_t;
+    const int64_t ni = (int64_t)n;
+    return ni < min_t ? min_t : ni;
+}
+
+// ------------------------------------------------------------------------------------------------------- monomial indexing
+// quadratic monomials: x^2 y^2 z^2 xy xz yz x y z 1 ; variables 0..3 = x, y, z, 1
+HD inline int quad_index(int a, int b) {
+    if (a > b) { const int t = a; a = b; b = t; }
+    if (a == b) return a == 3 ? 9 : a;
+    if (b == 3) return 6 + a;
+    return a == 0 ? (b == 1 ? 3 : 4) : 5;
+}
+HD inline void quad_exps(int q, int& ex, int& ey, int& ez) {
+    ex = (q == 0) * 2 + (q == 3 || q == 4 || q == 6);
+    ey = (q == 1) * 2 + (q == 3 || q == 5 || q == 7);
+    ez = (q == 2) * 2 + (q == 4 || q == 5 || q == 8);
+}
+// cubic monomials in COLMAP's order: x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1
+HD inline int cubic_index(int ex, int ey, int ez) {
+    switch (ex * 16 + ey * 4 + ez) {
+        case 48: return 0;  case 12: return 1;  case 36: return 2;  case 24: return 3;  case 33: return 4;
+        case 32: return 5;  case 9: return 6;   case 8: return 7;   case 21: return 8;  case 20: return 9;
+        case 18: return 10; case 17: return 11; case 16: return 12; case 6: return 13;  case 5: return 14;
+        case 4: return 15;  case 3: return 16;  case 2: return 17;  case 1: return 18;  default: return 19;
+    }
+}
+HD inline int cubic_of(int q, int v) {          // quadratic monomial q times variable v
+    int ex, ey, ez;
+    quad_exps(q, ex, ey, ez);
+    return cubic_index(ex + (v == 0), ey + (v == 1), ez + (v == 2));
+}
+
+// ------------------------------------------------------------------------------------------------------------ polynomials
+template <int S>
+HD inline double horner(Col<S> w, int off, int deg, double x) {
+    double r = w[off + deg];
+    for (int i = deg - 1; i >= 0; --i) r = r * x + w[off + i];
+    return r;
+}
+
+template <int S>
+HD inline void poly_mul_acc(Col<S> w, int a, int da, int b, int db, int out, double sgn) {   // out += sgn a b
+    for (int i = 0; i <= da; ++i)
+        for (int j = 0; j <= db; ++j) w[out + i + j] += sgn * (w[a + i] * w[b + j]);
+}
+
+HD inline int seq_off(int k) { return kSeq + 11 * k - (k * (k - 1)) / 2; }
+
+template <int S>
+HD inline void poly_normalise(Col<S> w, int off, int deg) {       // divide by the largest |coefficient| (a positive factor)
+    double m = 0.0;
+    for (int i = 0; i <= deg; ++i) m = fmax(m, fabs(w[off + i]));
+    if (m > 0.0)
+        for (int i = 0; i <= deg; ++i) w[off + i] = w[off + i] / m;
+}
+
+template <int S>
+HD inline int sign_changes(Col<S> w, int m, double x) {
+    int changes = 0;
+    double last = 0.0;
+    for (int k = 0; k < m; ++k) {
+        const double v = horner(w, seq_off(k), (int)w[kDeg + k], x);
+        if (v != 0.0) {
+            if (last != 0.0 && (v > 0.0) != (last > 0.0)) ++changes;
+            last = v;
+        }
+    }
+    return changes;
+}
+
+// real roots of the polynomial at seq_off(0) (ascending coefficients, degree <= 10) in ascending order -> kRoot; count returned
+template <int S>
+HD inline int sturm_roots(Col<S> w) {
+    int d = 10;
+    while (d >= 0 && w[seq_off(0) + d] == 0.0) --d;
+    if (d < 1) return 0;
+    for (int i = 0; i <= d; ++i)
+        if (!is_finite(w[seq_off(0) + i])) return 0;
+    poly_normalise(w, seq_off(0), d);
+    for (int i = 0; i < d; ++i) w[seq_off(1) + i] = (double)(i + 1) * w[seq_off(0) + i + 1];
+    poly_normalise(w, seq_off(1), d - 1);
+    w[kDeg] = d;
+    w[kDeg + 1] = d - 1;
+    int m = 2;
+    while (m < 11 && (int)w[kDeg + m - 1] > 0) {
+        const int a = seq_off(m - 2), b = seq_off(m - 1), du = (int)w[kDeg + m - 2], dv = (int)w[kDeg + m - 1];
+        for (int i = 0; i <= du; ++i) w[kTmp + i] = w[a + i];
+        for (int k = du - dv; k >= 0; --k) {
+            const double q = w[kTmp + dv + k] / w[b + dv];
+            for (int j = 0; j < dv; ++j) w[kTmp + j + k] -= q * w[b + j];
+            w[kTmp + dv + k] = 0.0;
+        }
+        int dr = dv - 1;
+        while (dr >= 0 && !(fabs(w[kTmp + dr]) > LS2FM_STURM_TRIM)) --dr;     // the dividend's largest |coefficient| is 1
+        if (dr < 0) break;
+        const int c = seq_off(m);
+        for (int i = 0; i <= dr; ++i) w[c + i] = -w[kTmp + i];
+        poly_normalise(w, c, dr);
+        w[kDeg + m] = dr;
+        ++m;
+    }
+    // Cauchy bound of the (normalised) polynomial
+    const int p0 = seq_off(0);
+    double bound = 0.0;
+    for (int i = 0; i < d; ++i) bound = fmax(bound, fabs(w[p0 + i] / w[p0 + d]));
+    bound = 1.0 + bound;
+    if (!is_finite(bound)) return 0;
+    const int v_lo = sign_changes(w, m, -bound);
+    const int total = v_lo - sign_changes(w, m, bound);
+    int n = 0;
+    double lo = -bound;
+    for (int k = 1; k <= total && n < kMaxSol; ++k) {
+        double hi = bound;
+        // roots in (-bound, x] = v_lo - V(x); the k-th root is the smallest x with at least k
+        for (int it = 0; it < kBisectIters; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            if (!(hi - lo > LS2FM_BISECT_TOL * fmax(1.0, fmax(fabs(lo), fabs(hi)))) || mid == lo || mid == hi) break;
+            if (v_lo - sign_changes(w, m, mid) >= k) hi = mid; else lo = mid;
+        }
+        double x = 0.5 * (lo + hi);
+        for (int it = 0; it < kNewtonIters; ++it) {            // polish on the polynomial itself, inside the bracket
+            double f = w[p0 + d], df = 0.0;
+            for (int i = d - 1; i >= 0; --i) { df = df * x + f; f = f * x + w[p0 + i]; }
+            if (df == 0.0) break;
+            const double xn = x - f / df;
+            if (!(xn >= lo && xn <= hi) || xn == x) break;
+            x = xn;
+        }
+        w[kRoot + n] = x;
+        ++n;
+    }
+    return n;
+}
+
+// ------------------------------------------------------------------------------------------------------ five-point solver
+// unit E (largest |entry| positive, the first of equals) -> emit(slot, E[9]); false when not finite
+HD inline bool canonical_e(double (&e)[9]) {
+    double nrm = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) nrm += e[i] * e[i];
+    if (!(nrm > 0.0) || !is_finite(nrm)) return false;
+    const double inv = 1.0 / sqrt(nrm);
+    double big = 0.0, sgn = 1.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        e[i] = e[i] * inv;
+        if (fabs(e[i]) > big) { big = fabs(e[i]); sgn = e[i] < 0.0 ? -1.0 : 1.0; }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) e[i] = sgn * e[i];
+    return true;
+}
+
+// the 4-dimensional null space of the 5 x 9 epipolar system (rows kron((x2, 1), (x1, 1))), Gauss-Jordan with partial pivoting,
+// then modified Gram-Schmidt -> kBas.  false: rank != 5 (pivot <= 1e-12 of the largest entry) or a degenerate basis
+template <int S>
+HD inline bool nullspace5(const double (&x1)[5][2], const double (&x2)[5][2], Col<S> w) {
+    double amax = 0.0;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        const double a[3] = {x1[r][0], x1[r][1], 1.0}, b[3] = {x2[r][0], x2[r][1], 1.0};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double v = b[i] * a[j];
+                w[kA + 9 * r + 3 * i + j] = v;
+                amax = fmax(amax, fabs(v));
+            }
+    }
+    if (!(amax > 0.0) || !is_finite(amax)) return false;
+    int rank = 0, nfree = 0;
+    for (int c = 0; c < 9; ++c) {
+        int p = -1;
+        double best = 0.0;
+        for (int r = rank; r < 5; ++r) {
+            const double v = fabs(w[kA + 9 * r + c]);
+            if (p < 0 || v > best) { best = v; p = r; }
+        }
+        if (rank == 5 || !(best > 1e-12 * amax)) {
+            w[kTmp + 5 + nfree] = c;
+            ++nfree;
+            continue;
+        }
+        for (int k = 0; k < 9; ++k) {
+            const double t = w[kA + 9 * rank + k];
+            w[kA + 9 * rank + k] = w[kA + 9 * p + k];
+            w[kA + 9 * p + k] = t;
+        }
+        const double inv = 1.0 / w[kA + 9 * rank + c];
+        for (int k = 0; k < 9; ++k) w[kA + 9 * rank + k] = w[kA + 9 * rank + k] * inv;
+        for (int r = 0; r < 5; ++r) {
+            if (r == rank) continue;
+            const double f = w[kA + 9 * r + c];
+            for (int k = 0; k < 9; ++k) w[kA + 9 * r + k] -= f * w[kA + 9 * rank + k];
+        }
+        w[kTmp + rank] = c;
+        ++rank;
+    }
+    if (rank != 5 || nfree != 4) return false;
+    for (int j = 0; j < 4; ++j) {
+        const int f = (int)w[kTmp + 5 + j];
+        for (int k = 0; k < 9; ++k) w[kBas + 9 * j + k] = k == f ? 1.0 : 0.0;
+        for (int i = 0; i < 5; ++i) w[kBas + 9 * j + (int)w[kTmp + i]] = -w[kA + 9 * i + f];
+    }
+    return true;
+}
+
+template <int S>
+HD inline bool orthonormalise_basis(Col<S> w) {         // modified Gram-Schmidt, in the order X, Y, Z, W
+    for (int j = 0; j < 4; ++j) {
+        for (int i = 0; i < j; ++i) {
+            double d = 0.0;
+            for (int k = 0; k < 9; ++k) d += w[kBas + 9 * i + k] * w[kBas + 9 * j + k];
+            for (int k = 0; k < 9; ++k) w[kBas + 9 * j + k] -= d * w[kBas + 9 * i + k];
+        }
+        double n = 0.0;
+        for (int k = 0; k < 9; ++k) n += w[kBas + 9 * j + k] * w[kBas + 9 * j + k];
+        if (!(n > 0.0) || !is_finite(n)) return false;
+        const double inv = 1.0 / sqrt(n);
+        for (int k = 0; k < 9; ++k) w[kBas + 9 * j + k] = w[kBas + 9 * j + k] * inv;
+    }
+    return true;
+}
+
+// linear polynomial of E entry e: coefficient of variable v (x, y, z, 1)
+template <int S>
+HD inline double lin(Col<S> w, int e, int v) { return w[kBas + 9 * v + e]; }
+
+// Nister's constraints from the basis at kBas, elimination, the degree-10 polynomial, its real roots, E per root.
+// emit(slot, const double E[9]) in ascending root order; returns the number emitted
+template <int S, class Emit>
+HD inline int solve_from_basis(Col<S> w, Emit emit) {
+    // E E^T (upper triangle, pairs (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)) as quadratics, then its trace
+    for (int i = 0; i < 70; ++i) w[kQ + i] = 0.0;
+    int k6 = 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j, ++k6)
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 4; ++a)
+                    for (int b = 0; b < 4; ++b) w[kQ + 10 * k6 + quad_index(a, b)] += lin(w, 3 * i + k, a) * lin(w, 3 * j + k, b);
+    for (int q = 0; q < 10; ++q) w[kQ + 60 + q] = (w[kQ + q] + w[kQ + 30 + q]) + w[kQ + 50 + q];
+    // rows 0..8: (2 E E^T E - tr(E E^T) E)_ij
+    for (int i = 0; i < 200; ++i) w[kA + i] = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int row = kA + 20 * (3 * i + j);
+            for (int k = 0; k < 3; ++k) {
+                const int lo = i < k ? i : k, hi = i < k ? k : i;
+                const int q6 = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);
+                for (int q = 0; q < 10; ++q)
+                    for (int v = 0; v < 4; ++v) w[row + cubic_of(q, v)] += 2.0 * (w[kQ + 10 * q6 + q] * lin(w, 3 * k + j, v));
+            }
+            for (int q = 0; q < 10; ++q)
+                for (int v = 0; v < 4; ++v) w[row + cubic_of(q, v)] -= w[kQ + 60 + q] * lin(w, 3 * i + j, v);
+        }
+    // row 9: det E by the first row's cofactors (minors as quadratics in kQ)
+    for (int i = 0; i < 30; ++i) w[kQ + i] = 0.0;
+    const int mi[3][4] = {{4, 8, 5, 7}, {3, 8, 5, 6}, {3, 7, 4, 6}};    // E11 E22 - E12 E21, E10 E22 - E12 E20, E10 E21 - E11 E20
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const int q = quad_index(a, b);
+                w[kQ + 10 * m + q] += lin(w, mi[m][0], a) * lin(w, mi[m][1], b) - lin(w, mi[m][2], a) * lin(w, mi[m][3], b);
+            }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const double sg = m == 1 ? -1.0 : 1.0;
+        for (int q = 0; q < 10; ++q)
+            for (int v = 0; v < 4; ++v) w[kA + 180 + cubic_of(q, v)] += sg * (lin(w, m, v) * w[kQ + 10 * m + q]);
+    }
+    // Gauss-Jordan with partial pivoting on the left 10 x 10 block: [I | AA]
+    double amax = 0.0;
+    for (int i = 0; i < 200; ++i) amax = fmax(amax, fabs(w[kA + i]));
+    if (!(amax > 0.0) || !is_finite(amax)) return 0;
+    for (int c = 0; c < 10; ++c) {
+        int p = c;
+        double best = fabs(w[kA + 20 * c + c]);
+        for (int r = c + 1; r < 10; ++r) {
+            const double v = fabs(w[kA + 20 * r + c]);
+            if (v > best) { best = v; p = r; }
+        }
+        if (!(best > 1e-14 * amax)) return 0;
+        if (p != c)
+            for (int k = c; k < 20; ++k) {
+                const double t = w[kA + 20 * c + k];
+                w[kA + 20 * c + k] = w[kA + 20 * p + k];
+                w[kA + 20 * p + k] = t;
+            }
+        const double inv = 1.0 / w[kA + 20 * c + c];
+        for (int k = c + 1; k < 20; ++k) w[kA + 20 * c + k] = w[kA + 20 * c + k] * inv;
+        w[kA + 20 * c + c] = 1.0;
+        for (int r = 0; r < 10; ++r) {
+            if (r == c) continue;
+            const double f = w[kA + 20 * r + c];
+            for (int k = c + 1; k < 20; ++k) w[kA + 20 * r + k] -= f * w[kA + 20 * c + k];
+            w[kA + 20 * r + c] = 0.0;
+        }
+    }
+    // B(z) [x y 1]^T = 0 from rows (x^2 z, x^2), (y^2 z, y^2), (xyz, xy): <e> - z <f>; ascending powers of z.
+    // B row i at kQ + 13 i: x column (4 coefficients), y column (4), 1 column (5)
+#define AA(r, c) w[kA + 20 * (r) + 10 + (c)]
+    for (int i = 0; i < 3; ++i) {
+        const int e = 2 * i + 4, f = 2 * i + 5, o = kQ + 13 * i;
+        for (int col = 0; col < 2; ++col) {
+            const int c0 = 3 * col;
+            w[o + 4 * col + 3] = -AA(f, c0);
+            w[o + 4 * col + 2] = AA(e, c0) - AA(f, c0 + 1);
+            w[o + 4 * col + 1] = AA(e, c0 + 1) - AA(f, c0 + 2);
+            w[o + 4 * col + 0] = AA(e, c0 + 2);
+        }
+        w[o + 12] = -AA(f, 6);
+        w[o + 11] = AA(e, 6) - AA(f, 7);
+        w[o + 10] = AA(e, 7) - AA(f, 8);
+        w[o + 9] = AA(e, 8) - AA(f, 9);
+        w[o + 8] = AA(e, 9);
+    }
+#undef AA
+    // det B(z): minors of rows 1, 2 (kTmp: 8 + 8 + 7 words), then the first row's cofactor expansion -> seq_off(0)
+    auto bo = [](int i, int c) { return kQ + 13 * i + 4 * c; };
+    auto bd = [](int c) { return c == 2 ? 4 : 3; };
+    for (int i = 0; i < 23; ++i) w[kTmp + i] = 0.0;
+    for (int i = 0; i < 11; ++i) w[seq_off(0) + i] = 0.0;
+    const int mc[3][2] = {{1, 2}, {0, 2}, {0, 1}};
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int a = mc[m][0], b = mc[m][1], out = kTmp + 8 * m;
+        poly_mul_acc(w, bo(1, a), bd(a), bo(2, b), bd(b), out, 1.0);
+        poly_mul_acc(w, bo(1, b), bd(b), bo(2, a), bd(a), out, -1.0);
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        poly_mul_acc(w, bo(0, m), bd(m), kTmp + 8 * m, bd(mc[m][0]) + bd(mc[m][1]), seq_off(0), m == 1 ? -1.0 : 1.0);
+    const int nroots = sturm_roots(w);
+    int n = 0;
+    for (int r = 0; r < nroots; ++r) {
+        const double z = w[kRoot + r];
+        double Bz[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Bz[i][c] = horner(w, bo(i, c), bd(c), z);
+        // null vector of Bz: the largest cross product of two rows
+        double cr[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int a = k == 2 ? 1 : 0, b = k == 0 ? 1 : 2;
+            cr[k][0] = Bz[a][1] * Bz[b][2] - Bz[a][2] * Bz[b][1];
+            cr[k][1] = Bz[a][2] * Bz[b][0] - Bz[a][0] * Bz[b][2];
+            cr[k][2] = Bz[a][0] * Bz[b][1] - Bz[a][1] * Bz[b][0];
+        }
+        const double n0 = (cr[0][0] * cr[0][0] + cr[0][1] * cr[0][1]) + cr[0][2] * cr[0][2];
+        const double n1 = (cr[1][0] * cr[1][0] + cr[1][1] * cr[1][1]) + cr[1][2] * cr[1][2];
+        const double n2 = (cr[2][0] * cr[2][0] + cr[2][1] * cr[2][1]) + cr[2][2] * cr[2][2];
+        const bool u0 = n0 >= n1;
+        double X0 = u0 ? cr[0][0] : cr[1][0], X1 = u0 ? cr[0][1] : cr[1][1], X2 = u0 ? cr[0][2] : cr[1][2], nb = u0 ? n0 : n1;
+        const bool keep = nb >= n2;
+        X0 = keep ? X0 : cr[2][0]; X1 = keep ? X1 : cr[2][1]; X2 = keep ? X2 : cr[2][2]; nb = keep ? nb : n2;
+        if (!(nb > 0.0) || !is_finite(nb)) continue;
+        if (!(fabs(X2) >= 1e-10 * sqrt(nb))) continue;
+        const double x = X0 / X2, y = X1 / X2;
+        double e[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k] = ((x * lin(w, k, 0) + y * lin(w, k, 1)) + z * lin(w, k, 2)) + lin(w, k, 3);
+        if (!canonical_e(e)) continue;
+        emit(n, e);
+        ++n;
+    }
+    return n;
+}
+
+// --------------------------------------------------------------------------------------------------------- Sampson error
+HD inline double sampson2(const double* E, double x1, double y1, double x2, double y2) {
+    const double a0 = (E[0] * x1 + E[1] * y1) + E[2];
+    const double a1 = (E[3] * x1 + E[4] * y1) + E[5];
+    const double a2 = (E[6] * x1 + E[7] * y1) + E[8];
+    const double b0 = (E[0] * x2 + E[3] * y2) + E[6];
+    const double b1 = (E[1] * x2 + E[4] * y2) + E[7];
+    const double num = (x2 * a0 + y2 * a1) + a2;
+    const double den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
+    return num * num / den;
+}
+
+HD inline bool is_inlier(const double* E, double x1, double y1, double x2, double y2, double thr2) {
+    return sampson2(E, x1, y1, x2, y2) <= thr2;       // NaN (0 / 0) is not an inlier
+}
+
+// ----------------------------------------------------------------------------------------------------------- triangulation
+// the 4 x 4 DLT of cv2.triangulatePoints (rows x P[2] - P[0], y P[2] - P[1] of both views); right singular vector of the smallest
+// singular value by one-sided Jacobi on A; unit norm, w >= 0
+HD inline void triangulate_dlt(const double* P0, const double* P1, double u0, double v0, double u1, double v1, double (&X)[4]) {
+    double a[4][4], V[4][4];          // a[c][r]: column c of A
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        a[c][0] = u0 * P0[8 + c] - P0[c];
+        a[c][1] = v0 * P0[8 + c] - P0[4 + c];
+        a[c][2] = u1 * P1[8 + c] - P1[c];
+        a[c][3] = v1 * P1[8 + c] - P1[4 + c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) V[c][r] = c == r ? 1.0 : 0.0;       // V[c]: column c of V
+    }
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const double al = ((a[p][0] * a[p][0] + a[p][1] * a[p][1]) + a[p][2] * a[p][2]) + a[p][3] * a[p][3];
+                const double be = ((a[q][0] * a[q][0] + a[q][1] * a[q][1]) + a[q][2] * a[q][2]) + a[q][3] * a[q][3];
+                const double ga = ((a[p][0] * a[q][0] + a[p][1] * a[q][1]) + a[p][2] * a[q][2]) + a[p][3] * a[q][3];
+                if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double ap = a[p][r], aq = a[q][r];
+                    a[p][r] = c * ap - s * aq;
+                    a[q][r] = s * ap + c * aq;
+                    const double vp = V[p][r], vq = V[q][r];
+                    V[p][r] = c * vp - s * vq;
+                    V[q][r] = s * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double best = 0.0;
+    int bi = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double n = ((a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2]) + a[c][3] * a[c][3];
+        if (c == 0 || n < best) { best = n; bi = c; }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[r] = bi == 0 ? V[0][r] : (bi == 1 ? V[1][r] : (bi == 2 ? V[2][r] : V[3][r]));
+    const double nrm = sqrt(((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]) + X[3] * X[3]);
+    const double s = (X[3] < 0.0 ? -1.0 : 1.0) / nrm;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[r] = X[r] * s;
+}
+
+// ------------------------------------------------------------------------------------------------------ pose from E (COLMAP)
+// E = U diag(s, s, 0) V^T by one-sided Jacobi on E's columns; U, V made proper; R1 = U W V^T, R2 = U W^T V^T, t = U col 2.
+// cand[k] = [R | t] for (R1, t), (R2, t), (R1, -t), (R2, -t)
+HD inline void pose_candidates(const double* E, double (&cand)[4][12]) {
+    double a[3][3], V[3][3];          // a[c]: column c of E V ; V[c]: column c of V
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { a[c][r] = E[3 * r + c]; V[c][r] = c == r ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double al = (a[p][0] * a[p][0] + a[p][1] * a[p][1]) + a[p][2] * a[p][2];
+                const double be = (a[q][0] * a[q][0] + a[q][1] * a[q][1]) + a[q][2] * a[q][2];
+                const double ga = (a[p][0] * a[q][0] + a[p][1] * a[q][1]) + a[p][2] * a[q][2];
+                if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double ap = a[p][r], aq = a[q][r];
+                    a[p][r] = c * ap - s * aq;
+                    a[q][r] = s * ap + c * aq;
+                    const double vp = V[p][r], vq = V[q][r];
+                    V[p][r] = c * vp - s * vq;
+                    V[q][r] = s * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    // order the columns by descending norm (three compare-and-swaps)
+    double nr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) nr[c] = (a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p = k == 1 ? 1 : 0, q = p + 1;
+        const bool sw = nr[q] > nr[p];
+        const double tn = nr[p];
+        nr[p] = sw ? nr[q] : nr[p];
+        nr[q] = sw ? tn : nr[q];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double ta = a[p][r], tv = V[p][r];
+            a[p][r] = sw ? a[q][r] : a[p][r];
+            a[q][r] = sw ? ta : a[q][r];
+            V[p][r] = sw ? V[q][r] : V[p][r];
+            V[q][r] = sw ? tv : V[q][r];
+        }
+    }
+    double U[3][3];                   // U[c]: column c
+    const double i0 = 1.0 / sqrt(nr[0]), i1 = 1.0 / sqrt(nr[1]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { U[0][r] = a[0][r] * i0; U[1][r] = a[1][r] * i1; }
+    U[2][0] = U[0][1] * U[1][2] - U[0][2] * U[1][1];
+    U[2][1] = U[0][2] * U[1][0] - U[0][0] * U[1][2];
+    U[2][2] = U[0][0] * U[1][1] - U[0][1] * U[1][0];
+    const double detV = (V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[1][0] * (V[0][1] * V[2][2] - V[0][2] * V[2][1])) +
+                        V[2][0] * (V[0][1] * V[1][2] - V[0][2] * V[1][1]);
+    const double sv = detV < 0.0 ? -1.0 : 1.0;
+    // U W V^T: W = [[0, 1, 0], [-1, 0, 0], [0, 0, 1]] -> U W = [-u1, u0, u2];  U W^T = [u1, -u0, u2]
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double v0 = sv * V[0][j], v1 = sv * V[1][j], v2 = sv * V[2][j];
+            const double r1 = (-U[1][i] * v0 + U[0][i] * v1) + U[2][i] * v2;
+            const double r2 = (U[1][i] * v0 - U[0][i] * v1) + U[2][i] * v2;
+            cand[0][4 * i + j] = r1; cand[2][4 * i + j] = r1;
+            cand[1][4 * i + j] = r2; cand[3][4 * i + j] = r2;
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        cand[0][4 * i + 3] = U[2][i]; cand[1][4 * i + 3] = U[2][i];
+        cand[2][4 * i + 3] = -U[2][i]; cand[3][4 * i + 3] = -U[2][i];
+    }
+}
+
+// COLMAP's CheckCheirality for one correspondence: depth in (DBL_EPSILON, 1000 |R^T t|) in both cameras
+HD inline bool in_front(const double* P, double x1, double y1, double x2, double y2) {
+    const double P0[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    double X[4];
+    triangulate_dlt(P0, P, x1, y1, x2, y2, X);
+    if (!(X[3] > 0.0)) return false;
+    const double px = X[0] / X[3], py = X[1] / X[3], pz = X[2] / X[3];
+    const double ctx = (P[0] * P[3] + P[4] * P[7]) + P[8] * P[11];       // R^T t
+    const double cty = (P[1] * P[3] + P[5] * P[7]) + P[9] * P[11];
+    const double ctz = (P[2] * P[3] + P[6] * P[7]) + P[10] * P[11];
+    const double max_depth = 1000.0 * sqrt((ctx * ctx + cty * cty) + ctz * ctz);
+    if (!(pz > DBL_EPSILON && pz < max_depth)) return false;
+    const double z2 = ((P[8] * px + P[9] * py) + P[10] * pz) + P[11];
+    const double c2 = sqrt((P[2] * P[2] + P[6] * P[6]) + P[10] * P[10]);
+    const double d2 = z2 * c2;
+    return d2 > DBL_EPSILON && d2 < max_depth;
+}
+
+// ------------------------------------------------------------------------------------------------------ symmetric Jacobi
+constexpr int sidx(int i, int j) { return i <= j ? i * 9 - (i * (i - 1)) / 2 + (j - i) : j * 9 - (j * (j - 1)) / 2 + (i - j); }
+
+// eigen-decomposition of the symmetric 9 x 9 a (upper triangle, 45 entries): cyclic Jacobi, at most kJacobiSweeps sweeps.
+// The caller holds ONE component of the eigenvectors: v[k] = component `row` of the eigenvector of eigenvalue a[sidx(k, k)]
+// (every thread of a workgroup runs the same rotations on the same a, thread r < 9 keeps row r)
+HD inline void jacobi9(double (&a)[45], int row, double (&v)[9]) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = k == row ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        double off = 0.0, dia = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            dia += a[sidx(i, i)] * a[sidx(i, i)];
+#pragma unroll
+            for (int j = i + 1; j < 9; ++j) off += a[sidx(i, j)] * a[sidx(i, j)];
+        }
+        if (!(off > 1e-30 * dia)) break;
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 9; ++q) {
+                const double apq = a[sidx(p, q)];
+                if (apq == 0.0) continue;
+                const double theta = (a[sidx(q, q)] - a[sidx(p, p)]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    if (k == p || k == q) continue;
+                    const double akp = a[sidx(k, p)], akq = a[sidx(k, q)];
+                    a[sidx(k, p)] = c * akp - s * akq;
+                    a[sidx(k, q)] = s * akp + c * akq;
+                }
+                a[sidx(p, p)] = a[sidx(p, p)] - t * apq;
+                a[sidx(q, q)] = a[sidx(q, q)] + t * apq;
+                a[sidx(p, q)] = 0.0;
+                const double vp = v[p], vq = v[q];
+                v[p] = c * vp - s * vq;
+                v[q] = s * vp + c * vq;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- minimal solver
+__device__ __forceinline__ double* fp_column(double* s_buf) { return s_buf + threadIdx.x; }
+
+__global__ void __launch_bounds__(kFpThreads)
+five_point_kernel(const double* __restrict__ x1, const double* __restrict__ x2, int64_t m, double* __restrict__ Eout,
+                  int32_t* __restrict__ n_sol) {
+    __shared__ double s_buf[kWords * kFpThreads];
+    const int64_t i = (int64_t)blockIdx.x * kFpThreads + threadIdx.x;
+    if (i >= m) return;
+    Col<kFpThreads> w{fp_column(s_buf)};
+    double a[5][2], b[5][2];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        a[s][0] = x1[10 * i + 2 * s]; a[s][1] = x1[10 * i + 2 * s + 1];
+        b[s][0] = x2[10 * i + 2 * s]; b[s][1] = x2[10 * i + 2 * s + 1];
+    }
+    double* __restrict__ out = Eout + 90 * i;
+    int n = 0;
+    if (nullspace5(a, b, w) && orthonormalise_basis(w))
+        n = solve_from_basis(w, [&](int s, const double* e) {
+            for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
+        });
+    for (int q = 9 * n; q < 90; ++q) out[q] = 0.0;
+    n_sol[i] = n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- RANSAC
+struct Ws {                     // workspace layout (ls2fm_relative_pose_workspace_bytes)
+    double* hyp;                // [P][kRound][10][9]
+    int32_t* valid;             // [P][kRound]   bit s: slot s holds an E
+    int32_t* counts;            // [P][kRound][10]
+    unsigned long long* best_key;   // [P]
+    double* best_e;             // [P][9]
+    int32_t* trials;            // [P]
+    int32_t* active;            // [P]
+    int32_t* n_active;          // [1]
+    int32_t* tile_off;          // [P + 1]
+};
+
+HD inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+HD inline size_t ws_layout(int32_t P, char* base, Ws* w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+    char* hyp = take((size_t)P * kRound * kMaxSol * 9 * sizeof(double));
+    char* valid = take((size_t)P * kRound * sizeof(int32_t));
+    char* counts = take((size_t)P * kRound * kMaxSol * sizeof(int32_t));
+    char* bk = take((size_t)P * sizeof(unsigned long long));
+    char* be = take((size_t)P * 9 * sizeof(double));
+    char* tr = take((size_t)P * sizeof(int32_t));
+    char* ac = take((size_t)P * sizeof(int32_t));
+    char* na = take(sizeof(int32_t));
+    char* to = take(((size_t)P + 1) * sizeof(int32_t));
+    if (w) *w = {(double*)hyp, (int32_t*)valid, (int32_t*)counts, (unsigned long long*)bk, (double*)be, (int32_t*)tr, (int32_t*)ac,
+                 (int32_t*)na, (int32_t*)to};
+    return off;
+}
+
+__device__ __forceinline__ double pair_thr2(const double* __restrict__ k0, const double* __restrict__ k1, double err_px) {
+    const double f0 = 0.5 * (k0[0] + k0[1]), f1 = 0.5 * (k1[0] + k1[1]);
+    const double e = 0.5 * (err_px / f0 + err_px / f1);
+    return e * e;
+}
+
+__device__ __forceinline__ void normalised(const double* __restrict__ uv, int64_t i, const double* __restrict__ K, double& x, double& y) {
+    x = (uv[2 * i] - K[2]) / K[0];
+    y = (uv[2 * i + 1] - K[3]) / K[1];
+}
+
+__global__ void __launch_bounds__(kPairThreads)
+rel_init_kernel(const int32_t* __restrict__ ps, int32_t P, Ws w) {
+    const int p = blockIdx.x * kPairThreads + threadIdx.x;
+    if (p >= P) return;
+    w.best_key[p] = 0ull;
+    w.trials[p] = 0;
+    w.active[p] = (ps[p + 1] - ps[p]) >= 5 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(kFpThreads)
+rel_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
+               const double* __restrict__ intr0, const double* __restrict__ intr1, uint64_t seed, Ws w) {
+    const int p = blockIdx.y;
+    if (!w.active[p]) return;
+    __shared__ double s_buf[kWords * kFpThreads];
+    const int tl = blockIdx.x * kFpThreads + threadIdx.x;
+    const int64_t slot = (int64_t)p * kRound + tl;
+    int32_t* __restrict__ cnt = w.counts + kMaxSol * slot;
+    for (int s = 0; s < kMaxSol; ++s) cnt[s] = 0;
+    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
+    const uint64_t t = (uint64_t)(w.trials[p] + tl);
+    const uint64_t key = splitmix64(seed ^ splitmix64(t));
+    int64_t id[5] = {-1, -1, -1, -1, -1};
+    int got = 0;
+    for (int k = 0; k < kMaxDraws && got < 5; ++k) {
+        const int64_t d = draw_index(key, k, n);
+        bool fresh = true;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) fresh = fresh && id[q] != d;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) id[q] = (fresh && q == got) ? d : id[q];
+        got += fresh ? 1 : 0;
+    }
+    int mask = 0;
+    if (got == 5) {
+        const double* __restrict__ K0 = intr0 + 4 * p;
+        const double* __restrict__ K1 = intr1 + 4 * p;
+        double a[5][2], b[5][2];
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            normalised(uv0, s0 + id[s], K0, a[s][0], a[s][1]);
+            normalised(uv1, s0 + id[s], K1, b[s][0], b[s][1]);
+        }
+        Col<kFpThreads> c{fp_column(s_buf)};
+        double* __restrict__ out = w.hyp + kMaxSol * 9 * slot;
+        if (nullspace5(a, b, c) && orthonormalise_basis(c))
+            solve_from_basis(c, [&](int s, const double* e) {
+                for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
+                mask |= 1 << s;
+            });
+    }
+    w.valid[slot] = mask;
+}
+
+__global__ void __launch_bounds__(kScoreThreads)
+rel_score_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
+                 const double* __restrict__ intr0, const double* __restrict__ intr1, int32_t P, double err_px, Ws w) {
+    const int32_t bx = (int32_t)blockIdx.x;
+    int lo = 0, hi = P;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (w.tile_off[mid] <= bx) lo = mid; else hi = mid;
+    }
+    const int p = lo;
+    if (!w.active[p]) return;
+    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
+    const int64_t base = (int64_t)(bx - w.tile_off[p]) * kScoreTile;
+    if (base >= n) return;
+    constexpr int kH = kMaxSol * kScoreTrials;
+    __shared__ double s_h[kH][9];
+    __shared__ int s_valid[kScoreTrials];
+    __shared__ int s_cnt[kH];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t slot0 = (int64_t)p * kRound + (int64_t)blockIdx.y * kScoreTrials;
+    for (int q = tid; q < kH * 9; q += kScoreThreads) s_h[q / 9][q % 9] = w.hyp[kMaxSol * 9 * slot0 + q];
+    if (tid < kScoreTrials) s_valid[tid] = w.valid[slot0 + tid];
+    if (tid < kH) s_cnt[tid] = 0;
+    const double* __restrict__ K0 = intr0 + 4 * p;
+    const double* __restrict__ K1 = intr1 + 4 * p;
+    const double thr2 = pair_thr2(K0, K1, err_px);
+    double ax[kScorePts], ay[kScorePts], bxv[kScorePts], byv[kScorePts];
+    bool live[kScorePts];
+#pragma unroll
+    for (int k = 0; k < kScorePts; ++k) {
+        const int64_t j = base + tid + (int64_t)k * kScoreThreads;
+        live[k] = j < n;
+        const int64_t i = s0 + (live[k] ? j : 0);
+        normalised(uv0, i, K0, ax[k], ay[k]);
+        normalised(uv1, i, K1, bxv[k], byv[k]);
+    }
+    __syncthreads();
+    for (int h = 0; h < kH; ++h) {
+        if (!((s_valid[h / kMaxSol] >> (h % kMaxSol)) & 1)) continue;
+        const double* E = s_h[h];
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < kScorePts; ++k) c += __popcll(__ballot(live[k] && is_inlier(E, ax[k], ay[k], bxv[k], byv[k], thr2)));
+        if (lane == 0 && c) atomicAdd(&s_cnt[h], c);
+    }
+    __syncthreads();
+    if (tid < kH && s_cnt[tid]) atomicAdd(&w.counts[kMaxSol * slot0 + tid], s_cnt[tid]);
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(k, o, 64);
+        k = t > k ? t : k;
+    }
+    return k;
+}
+
+__global__ void __launch_bounds__(kPairThreads)
+rel_select_kernel(const int32_t* __restrict__ ps, double confidence, int64_t min_trials, int64_t max_trials, Ws w) {
+    const int p = blockIdx.x;
+    if (!w.active[p]) return;
+    const int tid = threadIdx.x;
+    __shared__ unsigned long long s_k[kPairThreads / 64];
+    const int32_t t0 = w.trials[p];
+    unsigned long long best = 0ull;
+    for (int c = tid; c < kMaxSol * kRound; c += kPairThreads) {
+        const int64_t slot = (int64_t)p * kRound + c / kMaxSol;
+        const int s = c % kMaxSol;
+        const int cnt = w.counts[kMaxSol * slot + s];
+        if (cnt > 0 && ((w.valid[slot] >> s) & 1)) {
+            const uint32_t idx = (uint32_t)(t0 + c / kMaxSol) * (uint32_t)kMaxSol + (uint32_t)s;
+            const unsigned long long key = ((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+            best = key > best ? key : best;
+        }
+    }
+    best = wave_max_u64(best);
+    if ((tid & 63) == 0) s_k[tid >> 6] = best;
+    __syncthreads();
+    if (tid != 0) return;
+    for (int q = 0; q < kPairThreads / 64; ++q) best = s_k[q] > best ? s_k[q] : best;
+    if (best > w.best_key[p]) {
+        w.best_key[p] = best;
+        const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
+        const int64_t slot = (int64_t)p * kRound + (int64_t)(idx / (uint32_t)kMaxSol - (uint32_t)t0);
+        for (int q = 0; q < 9; ++q) w.best_e[9 * p + q] = w.hyp[kMaxSol * 9 * slot + 9 * (idx % (uint32_t)kMaxSol) + q];
+    }
+    const int32_t done = t0 + kRound;
+    w.trials[p] = done;
+    const double eps = (double)(w.best_key[p] >> 32) / (double)(ps[p + 1] - ps[p]);
+    const bool on = done < num_trials(eps, confidence, min_trials, max_trials);
+    w.active[p] = on ? 1 : 0;
+    if (on) atomicAdd(w.n_active, 1);
+}
+
+// ------------------------------------------------------------------------------------------------ local optimisation, pose
+constexpr int kNe = 45;
+
+__device__ __forceinline__ void block_sum(double (&a)[kNe], double* s_red /* [kPairThreads / 64][kNe] */) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) {
+        double t = a[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        a[q] = t;
+    }
+    __syncthreads();
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int q = 0; q < kNe; ++q) s_red[(tid >> 6) * kNe + q] = a[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kNe; ++q) {
+        double t = s_red[q];
+#pragma unroll
+        for (int wv = 1; wv < kPairThreads / 64; ++wv) t += s_red[wv * kNe + q];
+        a[q] = t;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ int block_count(int c, int* s_int) {     // exact integer sum over the workgroup
+    __syncthreads();
+    if (threadIdx.x == 0) *s_int = 0;
+    __syncthreads();
+    if (c) atomicAdd(s_int, c);
+    __syncthreads();
+    return *s_int;
+}
+
+__global__ void __launch_bounds__(kPairThreads)
+rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
+                 const double* __restrict__ intr0, const double* __restrict__ intr1, double err_px, Ws w, double* __restrict__ Eout,
+                 double* __restrict__ poses, uint8_t* __restrict__ inliers, int32_t* __restrict__ num_inliers,
+                 int32_t* __restrict__ trials, int32_t* __restrict__ best_trial, int32_t* __restrict__ success) {
+    __shared__ double s_red[(kPairThreads / 64) * kNe];
+    __shared__ double s_solve[kWords];
+    __shared__ double s_cand[kMaxSol][9];
+    __shared__ int s_ncand, s_int;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
+    const double* __restrict__ K0 = intr0 + 4 * p;
+    const double* __restrict__ K1 = intr1 + 4 * p;
+    const double thr2 = pair_thr2(K0, K1, err_px);
+    const unsigned long long bk = w.best_key[p];
+    if (bk == 0ull) {
+        for (int64_t j = tid; j < n; j += kPairThreads) inliers[s0 + j] = 0;
+        if (tid < 12) poses[12 * p + tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+        if (tid < 9) Eout[9 * p + tid] = 0.0;
+        if (tid == 0) { num_inliers[p] = 0; trials[p] = w.trials[p]; best_trial[p] = -1; success[p] = 0; }
+        return;
+    }
+    double E[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) E[q] = w.best_e[9 * p + q];
+    int cur = 0;
+    for (int64_t j = tid; j < n; j += kPairThreads) {
+        double a0, a1, b0, b1;
+        normalised(uv0, s0 + j, K0, a0, a1);
+        normalised(uv1, s0 + j, K1, b0, b1);
+        cur += is_inlier(E, a0, a1, b0, b1, thr2) ? 1 : 0;
+    }
+    cur = block_count(cur, &s_int);
+    for (int it = 0; it < kLoIters && cur >= 5; ++it) {
+        // normal matrix of the inliers' epipolar rows, upper triangle, fixed-order sum
+        double a[kNe];
+#pragma unroll
+        for (int q = 0; q < kNe; ++q) a[q] = 0.0;
+        for (int64_t j = tid; j < n; j += kPairThreads) {
+            double a0, a1, b0, b1;
+            normalised(uv0, s0 + j, K0, a0, a1);
+            normalised(uv1, s0 + j, K1, b0, b1);
+            if (!is_inlier(E, a0, a1, b0, b1, thr2)) continue;
+            const double r[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+#pragma unroll
+                for (int k = i; k < 9; ++k) a[sidx(i, k)] += r[i] * r[k];
+        }
+        block_sum(a, s_red);
+        {
+            double v[9];
+            jacobi9(a, tid < 9 ? tid : 0, v);
+            // rank of each eigenvalue, ascending (the lower index first among equals); the four smallest are W, Z, Y, X
+            int rank[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                rank[k] = 0;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    const double ej = a[sidx(j, j)], ek = a[sidx(k, k)];
+                    rank[k] += (ej < ek || (ej == ek && j < k)) ? 1 : 0;
+                }
+            }
+            if (tid < 9)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    double x = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) x = rank[k] == 3 - j ? v[k] : x;
+                    s_solve[kBas + 9 * j + tid] = x;
+                }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            Col<1> c{s_solve};
+            s_ncand = solve_from_basis(c, [&](int s, const double* e) {
+                for (int q = 0; q < 9; ++q) s_cand[s][q] = e[q];
+            });
+        }
+        __syncthreads();
+        const int nc = s_ncand;
+        int best_c = -1, best_cnt = -1;
+        for (int cidx = 0; cidx < nc; ++cidx) {
+            int c = 0;
+            for (int64_t j = tid; j < n; j += kPairThreads) {
+                double a0, a1, b0, b1;
+                normalised(uv0, s0 + j, K0, a0, a1);
+                normalised(uv1, s0 + j, K1, b0, b1);
+                c += is_inlier(s_cand[cidx], a0, a1, b0, b1, thr2) ? 1 : 0;
+            }
+            c = block_count(c, &s_int);
+            if (c > best_cnt) { best_cnt = c; best_c = cidx; }
+        }
+        if (best_c < 0 || best_cnt < cur) break;
+        int chg = 0;
+        for (int64_t j = tid; j < n; j += kPairThreads) {
+            double a0, a1, b0, b1;
+            normalised(uv0, s0 + j, K0, a0, a1);
+            normalised(uv1, s0 + j, K1, b0, b1);
+            chg += is_inlier(s_cand[best_c], a0, a1, b0, b1, thr2) != is_inlier(E, a0, a1, b0, b1, thr2) ? 1 : 0;
+        }
+        chg = block_count(chg, &s_int);
+#pragma unroll
+        for (int q = 0; q < 9; ++q) E[q] = s_cand[best_c][q];
+        cur = best_cnt;
+        if (chg == 0) break;
+    }
+    // the final mask and the pose: the candidate with the most triangulated inliers in front of both cameras (ties: the later)
+    __shared__ double s_pose[4][12];
+    if (tid == 0) {
+        double cand[4][12];
+        pose_candidates(E, cand);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int q = 0; q < 12; ++q) s_pose[k][q] = cand[k][q];
+    }
+    __syncthreads();
+    int front[4] = {0, 0, 0, 0};
+    for (int64_t j = tid; j < n; j += kPairThreads) {
+        double a0, a1, b0, b1;
+        normalised(uv0, s0 + j, K0, a0, a1);
+        normalised(uv1, s0 + j, K1, b0, b1);
+        const bool in = is_inlier(E, a0, a1, b0, b1, thr2);
+        inliers[s0 + j] = in ? 1 : 0;
+        if (!in) continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) front[k] += in_front(s_pose[k], a0, a1, b0, b1) ? 1 : 0;
+    }
+    int bestk = 0, bestf = -1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int f = block_count(front[k], &s_int);
+        if (f >= bestf) { bestf = f; bestk = k; }
+    }
+    const bool ok = cur >= 5 && bestf > 0;
+    if (tid < 12) {
+        double v = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v = (ok && bestk == k) ? s_pose[k][tid] : v;
+        poses[12 * p + tid] = v;
+    }
+    if (tid < 9) Eout[9 * p + tid] = E[tid];
+    if (tid == 0) {
+        num_inliers[p] = cur;
+        trials[p] = w.trials[p];
+        best_trial[p] = (int32_t)((0xFFFFFFFFu - (uint32_t)(bk & 0xFFFFFFFFull)) / (uint32_t)kMaxSol);
+        success[p] = ok ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- triangulation
+__global__ void __launch_bounds__(kTriThreads)
+triangulate_kernel(const double* __restrict__ P0, const double* __restrict__ P1, const double* __restrict__ uv0,
+                   const double* __restrict__ uv1, const int32_t* __restrict__ ps, int32_t n_pairs, int64_t n, double* __restrict__ X) {
+    const int64_t i = (int64_t)blockIdx.x * kTriThreads + threadIdx.x;
+    if (i >= n) return;
+    int lo = 0, hi = n_pairs;                 // the last pair with pair_start <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)ps[mid] <= i) lo = mid; else hi = mid;
+    }
+    double A[12], B[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) { A[q] = P0[12 * lo + q]; B[q] = P1[12 * lo + q]; }
+    double h[4];
+    triangulate_dlt(A, B, uv0[2 * i], uv0[2 * i + 1], uv1[2 * i], uv1[2 * i + 1], h);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[4 * i + r] = h[r];
+}
+
+bool opts_ok(const ls2fm_pose_ransac_opts* o) {
+    return o && o->max_error_px > 0.0 && std::isfinite(o->max_error_px) && o->confidence > 0.0 && o->confidence < 1.0 &&
+           o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio < 1.0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 &&
+           o->max_num_trials <= LS2FM_POSE_MAX_TRIALS && o->min_num_trials <= o->max_num_trials && o->refine == 0;
+}
+
+// pair_start (device) -> host copy with the checks; returns false on a transfer error (status in *st)
+bool host_pair_start(const int32_t* ps, int32_t P, hipStream_t s, int32_t* h, int* st) {
+    if (hipMemcpyAsync(h, ps, sizeof(int32_t) * ((size_t)P + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        *st = ls2fm_launch_status();
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int ls2fm_five_point(const double* x1, const double* x2, int64_t m, double* E, int32_t* n_solutions, void* stream) {
+    LS2FM_CHECK_ARG(m >= 0);
+    if (m == 0) return LS2FM_OK;
+    LS2FM_CHECK_ARG(x1 && x2 && E && n_solutions);
+    five_point_kernel<<<(unsigned)((m + kFpThreads - 1) / kFpThreads), kFpThreads, 0, (hipStream_t)stream>>>(x1, x2, m, E, n_solutions);
+    return ls2fm_launch_status();
+}
+
+extern "C" int64_t ls2fm_relative_pose_workspace_bytes(int32_t n_pairs, int64_t n_corr) {
+    if (n_pairs < 1 || n_pairs > LS2FM_RELPOSE_MAX_PAIRS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
+    return (int64_t)ws_layout(n_pairs, nullptr, nullptr);
+}
+
+extern "C" int ls2fm_relative_pose(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs, const double* intr0,
+                                   const double* intr1, const ls2fm_pose_ransac_opts* opts, double* E, double* poses, uint8_t* inliers,
+                                   int32_t* num_inliers, int32_t* trials, int32_t* best_trial, int32_t* success, void* workspace,
+                                   void* stream) {
+    LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && pair_start && intr0 && intr1 && opts_ok(opts));
+    LS2FM_CHECK_ARG(E && poses && num_inliers && trials && best_trial && success);
+    if (!workspace) return LS2FM_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* h_ps = (int32_t*)malloc(sizeof(int32_t) * ((size_t)n_pairs + 1));
+    if (!h_ps) return LS2FM_ERR_LAUNCH;
+    int st = LS2FM_OK;
+    if (!host_pair_start(pair_start, n_pairs, s, h_ps, &st)) {
+        free(h_ps);
+        return st;
+    }
+    int64_t max_n = 0;
+    bool mono = h_ps[0] >= 0;
+    int32_t tiles = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        mono = mono && h_ps[p + 1] >= h_ps[p];
+        const int64_t np = (int64_t)h_ps[p + 1] - h_ps[p];
+        max_n = std::max<int64_t>(max_n, np);
+        h_ps[p] = tiles;
+        tiles += mono ? (int32_t)((np + kScoreTile - 1) / kScoreTile) : 0;
+    }
+    const int64_t total = h_ps[n_pairs];
+    h_ps[n_pairs] = tiles;
+    if (!(mono && (total == 0 || (uv0 && uv1 && inliers)))) {
+        free(h_ps);
+        return LS2FM_ERR_INVALID_ARGUMENT;
+    }
+    Ws w;
+    ws_layout(n_pairs, (char*)workspace, &w);
+    const bool copied = hipMemcpyAsync(w.tile_off, h_ps, sizeof(int32_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s) == hipSuccess &&
+                        hipStreamSynchronize(s) == hipSuccess;
+    free(h_ps);
+    if (!copied) return ls2fm_launch_status();
+    const int64_t cap = num_trials(opts->min_inlier_ratio, opts->confidence, 0, opts->max_num_trials);
+    const int64_t min_trials = std::min<int64_t>(opts->min_num_trials, cap);
+    rel_init_kernel<<<(unsigned)((n_pairs + kPairThreads - 1) / kPairThreads), kPairThreads, 0, s>>>(pair_start, n_pairs, w);
+    if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
+    const int64_t max_rounds = (cap + kRound - 1) / kRound;
+    for (int64_t r = 0; max_n >= 5 && r < max_rounds; ++r) {
+        rel_hyp_kernel<<<dim3(kRound / kFpThreads, (unsigned)n_pairs), kFpThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->seed,
+                                                                                           w);
+        rel_score_kernel<<<dim3((unsigned)tiles, kRound / kScoreTrials), kScoreThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1,
+                                                                                               n_pairs, opts->max_error_px, w);
+        if (hipMemsetAsync(w.n_active, 0, sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
+        rel_select_kernel<<<(unsigned)n_pairs, kPairThreads, 0, s>>>(pair_start, opts->confidence, min_trials, cap, w);
+        if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
+        int32_t h_active = 0;
+        if (hipMemcpyAsync(&h_active, w.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return ls2fm_launch_status();
+        if (h_active == 0) break;
+    }
+    rel_final_kernel<<<(unsigned)n_pairs, kPairThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->max_error_px, w, E, poses,
+                                                                inliers, num_inliers, trials, best_trial, success);
+    return ls2fm_launch_status();
+}
+
+extern "C" int ls2fm_triangulate(const double* P0, const double* P1, const double* uv0, const double* uv1, const int32_t* pair_start,
+                                 int32_t n_pairs, int64_t n, double* X, void* stream) {
+    LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && n >= 0 && P0 && P1 && pair_start);
+    if (n == 0) return LS2FM_OK;
+    LS2FM_CHECK_ARG(uv0 && uv1 && X);
+    triangulate_kernel<<<(unsigned)((n + kTriThreads - 1) / kTriThreads), kTriThreads, 0, (hipStream_t)stream>>>(P0, P1, uv0, uv1,
+                                                                                                              pair_start, n_pairs, n, X);
+    return ls2fm_launch_status();
+}

@@ -185,6 +185,10 @@ _SIGNATURES = {
     "ls2fm_absolute_pose_workspace_bytes": (c_int64, [c_int32, c_int64]),
     "ls2fm_absolute_pose": (c_int32, [_P, _P, _P, c_int32, _P, POINTER(PoseRansacOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_pose_refine": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, c_float, c_int32, _P, _P]),
+    "ls2fm_five_point": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
+    "ls2fm_relative_pose_workspace_bytes": (c_int64, [c_int32, c_int64]),
+    "ls2fm_relative_pose": (c_int32, [_P, _P, _P, c_int32, _P, _P, POINTER(PoseRansacOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_triangulate": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

@@ -1,10 +1,13 @@
-"""Absolute pose on the device: what Registration.PnP asks of pycolmap (pipelines/Registration.py:94-109 of the reference).
+"""Absolute and relative pose on the device: what Registration.PnP (pipelines/Registration.py:94-109 of the reference) and
+Initializer (pipelines/Initialization.py:86-95) ask of pycolmap, and the _Trad drivers of cv2.triangulatePoints.
 
 `absolute_pose` runs LO-RANSAC (Lambda Twist P3P, Gauss-Newton local optimisation, Cauchy-loss Levenberg-Marquardt refinement)
 for one or MANY views in one call of ls2fm_absolute_pose (csrc/absolute_pose.hip) -- the next-best-view search of
 LevelS2fM.train (pipelines/LevelS2fM.py:247-281) forms every candidate view's pnp score from one call instead of one host round
-trip per view.  `refine_pose` is pose_refinement alone (ls2fm_pose_refine), `p3p` the minimal solver alone.  Every rule is stated
-in include/ls2fm.h; tests/pose_restate.py repeats them in numpy.
+trip per view.  `refine_pose` is pose_refinement alone (ls2fm_pose_refine), `p3p` the minimal solver alone.  `relative_pose`
+runs LO-RANSAC over Nister's five-point algorithm and recovers [R | t] for one or many view pairs (ls2fm_relative_pose,
+csrc/relative_pose.hip); `five_point` is the minimal solver alone and `triangulate` the batched two-view DLT.  Every rule is
+stated in include/ls2fm.h; tests/pose_restate.py and tests/relpose_restate.py repeat them in numpy.
 
 Poses are world-to-camera [3,4] = [R | t], fp64; intrinsics per view (fx, fy, cx, cy).  The defaults are pycolmap 0.3.0's
 absolute_pose_estimation defaults as we read them.  There is no CPU path: CPU tensors, a missing device or a missing library raise.
@@ -172,3 +175,105 @@ def rotmat_to_qvec(R):
         q = np.array([(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s])
     q = q / np.linalg.norm(q)
     return -q if q[0] < 0 else q
+
+
+# ----------------------------------------------------------------------------------------------------------- relative pose
+def _ragged_pairs(uv0, uv1, pair_start):
+    """(uv0 [n,2], uv1 [n,2], pair_start int32 [P+1]) on the device from tensors or lists of per-pair tensors"""
+    return _ragged_common(uv0, uv1, pair_start, (2,), "uv0", "uv1", "pair_start")
+
+
+def _ragged_common(a, b, starts, tail_b, name_a, name_b, name_s):
+    if isinstance(a, (list, tuple)):
+        if not isinstance(b, (list, tuple)) or len(b) != len(a) or len(a) == 0:
+            raise ValueError(f"ls2fm.pose: {name_a} and {name_b} lists must have the same non-zero length")
+        if starts is not None:
+            raise ValueError(f"ls2fm.pose: {name_s} is implied by lists of per-pair tensors")
+        dev = torch.as_tensor(a[0]).device
+        As = [torch.as_tensor(u).reshape(-1, 2) for u in a]
+        Bs = [torch.as_tensor(x).reshape(-1, *tail_b) for x in b]
+        for u, x in zip(As, Bs):
+            if u.shape[0] != x.shape[0]:
+                raise ValueError(f"ls2fm.pose: {u.shape[0]} {name_a} rows against {x.shape[0]} {name_b} rows")
+        counts = [u.shape[0] for u in As]
+        st = torch.tensor([0] + list(np.cumsum(counts)), dtype=torch.int32, device=dev)
+        return (_f64(torch.cat(As).to(dev), (2,), name_a), _f64(torch.cat(Bs).to(dev), tail_b, name_b), st)
+    a = _f64(a, (2,), name_a)
+    b = _f64(b, tail_b, name_b)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"ls2fm.pose: {a.shape[0]} {name_a} rows against {b.shape[0]} {name_b} rows")
+    if starts is None:
+        starts = torch.tensor([0, a.shape[0]], dtype=torch.int32, device=a.device)
+    starts = torch.as_tensor(starts, device=a.device).to(torch.int32).contiguous()
+    if starts.dim() != 1 or starts.numel() < 2:
+        raise ValueError(f"ls2fm.pose: {name_s} must be [P + 1]")
+    if not torch.cuda.is_current_stream_capturing():
+        h = starts.cpu()
+        if int(h[0]) != 0 or int(h[-1]) != a.shape[0] or bool((h[1:] < h[:-1]).any()):
+            raise ValueError(f"ls2fm.pose: {name_s} must rise from 0 to the {a.shape[0]} correspondences, "
+                             f"got {h[0].item()} .. {h[-1].item()}")
+    return a, b, starts
+
+
+def five_point(x1, x2):
+    """Nister's five-point solver of m minimal problems: normalised points x1, x2 [m,5,2] (device) -> (E [m,10,3,3] fp64, unit
+    Frobenius norm, kept ones first and zero beyond; n_solutions int32 [m])"""
+    a = torch.as_tensor(x1)
+    b = torch.as_tensor(x2)
+    _device(a, b)
+    a = a.to(torch.float64).reshape(-1, 5, 2).contiguous()
+    b = b.to(torch.float64).reshape(-1, 5, 2).contiguous()
+    if a.shape != b.shape:
+        raise ValueError(f"ls2fm.pose.five_point: x1 {tuple(a.shape)} against x2 {tuple(b.shape)}")
+    m = a.shape[0]
+    E = torch.empty(m, 10, 3, 3, dtype=torch.float64, device=a.device)
+    n = torch.empty(m, dtype=torch.int32, device=a.device)
+    check(_lib.load().ls2fm_five_point(ptr(a), ptr(b), m, ptr(E), ptr(n), stream_ptr()), "ls2fm_five_point")
+    return E, n
+
+
+def relative_pose(uv0, uv1, intr0, intr1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.01,
+                  min_num_trials=1000, max_num_trials=100000, seed=0):
+    """LO-RANSAC relative pose of P view pairs in one call (ls2fm_relative_pose).  uv0 / uv1 [n,2] pixels of the two views,
+    sorted by pair with pair_start [P+1] (None: one pair), or lists of per-pair tensors; intr0 / intr1 [P,4] / [4]
+    (fx, fy, cx, cy) or K [P,3,3] / [3,3] of each pair's first and second camera.  -> dict(E [P,3,3], poses [P,3,4] fp64 with
+    X2 = R X1 + t and |t| = 1, inliers bool [n], num_inliers, trials, best_trial, success, pair_start)"""
+    uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
+    P = ps.numel() - 1
+    dev = uv0.device
+    k0 = _intrinsics(intr0, P, dev)
+    k1 = _intrinsics(intr1, P, dev)
+    lib = _lib.load()
+    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
+                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 0)
+    ws_bytes = lib.ls2fm_relative_pose_workspace_bytes(P, uv0.shape[0])
+    if ws_bytes < 0:
+        check(int(ws_bytes), "ls2fm_relative_pose_workspace_bytes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    E = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
+    poses = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
+    inl = torch.empty(uv0.shape[0], dtype=torch.uint8, device=dev)
+    num, trials, best, succ = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
+    check(lib.ls2fm_relative_pose(ptr(uv0), ptr(uv1), ptr(ps), P, ptr(k0), ptr(k1), ctypes.byref(opts), ptr(E), ptr(poses), ptr(inl),
+                                  ptr(num), ptr(trials), ptr(best), ptr(succ), ptr(ws), stream_ptr()), "ls2fm_relative_pose")
+    return dict(E=E, poses=poses, inliers=inl.view(torch.bool), num_inliers=num, trials=trials, best_trial=best,
+                success=succ.bool(), pair_start=ps)
+
+
+def triangulate(P0, P1, uv0, uv1, pair_start=None):
+    """two-view DLT (cv2.triangulatePoints' system, one-sided Jacobi): projection matrices P0 / P1 [P,3,4] (or [3,4]), pixel pairs
+    uv0 / uv1 [n,2] sorted by pair (pair_start [P+1]; None: one pair) -> homogeneous points [n,4] fp64, unit norm, w >= 0"""
+    uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
+    P = ps.numel() - 1
+    dev = uv0.device
+    a = torch.as_tensor(P0)
+    b = torch.as_tensor(P1)
+    _device(a, b)
+    a = a.to(device=dev, dtype=torch.float64).reshape(-1, 3, 4).contiguous()
+    b = b.to(device=dev, dtype=torch.float64).reshape(-1, 3, 4).contiguous()
+    if a.shape[0] != P or b.shape[0] != P:
+        raise ValueError(f"ls2fm.pose.triangulate: {a.shape[0]} / {b.shape[0]} projection matrices for {P} pairs")
+    X = torch.empty(uv0.shape[0], 4, dtype=torch.float64, device=dev)
+    check(_lib.load().ls2fm_triangulate(ptr(a), ptr(b), ptr(uv0), ptr(uv1), ptr(ps), P, uv0.shape[0], ptr(X), stream_ptr()),
+          "ls2fm_triangulate")
+    return X

@@ -812,7 +812,8 @@ class RefineLoop:
 
 class InitLoop:
     """`Initializer.run` (pipelines/Initialization.py:139-226) for the two initial views with given poses (the essential-matrix
-    pose initialisation of `Initializer.__init__` is pycolmap's: caller side): per iteration the matched key points of each
+    pose initialisation of `Initializer.__init__` stays caller side: `ls2fm.pose.relative_pose`, or the one-line swap to
+    `ls2fm.utils.pycolmap_compat.essential_matrix_estimation`, gives it on the device): per iteration the matched key points of each
     view are sphere-traced onto the surface and projected into the OTHER view (`Camera.proj_cam_i`, Camera.py:168-178) --
     reproj_error = mean ||uv_proj - key point||, sdf_surf = mean |SDF at the end of the tracks|, both over the 2 n tracks; the
     gradient reaches the SDF field through the traced depth -- then the render with the cameras' poses, eikonal over EVERY

@@ -6,7 +6,13 @@ pipelines/Registration.py and Registration_Trad.py run after one edit:
 Camera (SIMPLE_PINHOLE, PINHOLE), absolute_pose_estimation, pose_refinement and qvec_to_rotmat follow pycolmap 0.3.0's names,
 arguments, defaults and result keys as we read them (pycolmap is not available to confirm them).  absolute_pose_estimation
 refines the pose on its inliers before it returns, as we read 0.3.0 to do.  There is no CPU fallback: without a GPU every
-estimation call raises RuntimeError.  essential_matrix_estimation (the two-view initialisation) is not provided yet.
+estimation call raises RuntimeError.
+
+essential_matrix_estimation (Initializer's two-view initialisation, pipelines/Initialization.py:86-95 and
+Initialization_Trad.py:81-85) runs ls2fm.pose.relative_pose.  It takes SIMPLE_PINHOLE cameras only -- the only model any
+reference driver builds for this call -- and raises NotImplementedError for any other model, before any device or shape check;
+ls2fm.pose.relative_pose itself takes general (fx, fy, cx, cy).  Its defaults (max_error_px 4, min_inlier_ratio 0.01, trials
+1000 - 100 000, confidence 0.999) are our reading of pycolmap 0.3.0, unconfirmed as the rest.
 """
 from __future__ import annotations
 
@@ -100,5 +106,30 @@ def rotmat_to_qvec(R):
     return _pose.rotmat_to_qvec(R)
 
 
-def essential_matrix_estimation(*args, **kwargs):
-    raise NotImplementedError("pycolmap_compat.essential_matrix_estimation: the two-view five-point estimate is not provided yet")
+def essential_matrix_estimation(points2D1, points2D2, camera1, camera2, max_error_px=4.0, min_inlier_ratio=0.01,
+                                min_num_trials=1000, max_num_trials=100000, confidence=0.999, seed=0):
+    """-> {success, E, qvec, tvec, num_inliers, inliers (numpy bool [n])}; {success: False} on failure.  qvec / tvec map camera 1
+    to camera 2 (X2 = R X1 + t, |t| = 1)"""
+    for cam in (camera1, camera2):
+        if not isinstance(cam, Camera):
+            raise TypeError("pycolmap_compat: camera must be a pycolmap_compat.Camera")
+        if cam.model_name != "SIMPLE_PINHOLE":
+            raise NotImplementedError(f"pycolmap_compat.essential_matrix_estimation: camera model {cam.model_name!r} "
+                                      "(only SIMPLE_PINHOLE is supported)")
+    p0 = np.asarray(points2D1, dtype=np.float64)
+    p1 = np.asarray(points2D2, dtype=np.float64)
+    for name, p in (("points2D1", p0), ("points2D2", p1)):
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"pycolmap_compat: {name} must be [n, 2], got {p.shape}")
+    if p0.shape[0] != p1.shape[0]:
+        raise ValueError(f"pycolmap_compat: {p0.shape[0]} points2D1 against {p1.shape[0]} points2D2")
+    dev = _device()
+    r = _pose.relative_pose(torch.from_numpy(np.ascontiguousarray(p0)).to(dev), torch.from_numpy(np.ascontiguousarray(p1)).to(dev),
+                            torch.from_numpy(camera1.intrinsics).to(dev), torch.from_numpy(camera2.intrinsics).to(dev),
+                            max_error_px=max_error_px, confidence=confidence, min_inlier_ratio=min_inlier_ratio,
+                            min_num_trials=min_num_trials, max_num_trials=max_num_trials, seed=seed)
+    if not bool(r["success"][0]):
+        return {"success": False}
+    P = r["poses"][0].cpu().numpy()
+    return {"success": True, "E": r["E"][0].cpu().numpy(), "qvec": _pose.rotmat_to_qvec(P[:, :3]), "tvec": P[:, 3].copy(),
+            "num_inliers": int(r["num_inliers"][0]), "inliers": r["inliers"].cpu().numpy()}
