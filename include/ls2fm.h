@@ -818,6 +818,42 @@ int ls2fm_triangulate(const double* P0, const double* P1, const double* uv0, con
                       int32_t n_pairs, int64_t n, double* X, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Classical bundle adjustment over explicit points and se(3) poses (new; the library's version stays ABI 13: the calls are additions): the loop of pipelines/BA_Trad.py:86-130
+ * (`BA.run_ba` behind Ablate_config.ba_trad) -- n_iters iterations in ONE call, two plain launches each, no host read inside.
+ *   iteration pose_v = se3_to_SE3(se3[v]) (ls2fm_se3_exp_fwd's arithmetic) ; x_c = R x + t ; u = K x_c ; uv = u_xy / (u_z + 1e-6) ;
+ *             err = |uv - obs_uv| ; reproj = 0.5 mean(2 log(1 + err^2 / 4)) + 0.5 mean(err) over ALL n_obs observations (fp32 per
+ *             observation in ls2fm_reproject_fwd's order, fp64 fixed-order sums) ; w = reproj > thresh ? w_hi : w_lo ; the
+ *             gradient of w reproj w.r.t. se3 (ls2fm_se3_exp_bwd's arithmetic) and the points (a point's observations summed in
+ *             list order: no floating-point atomics, a run repeats itself bit for bit) ; torch.optim.Adam's update (defaults:
+ *             betas 0.9 / 0.999, eps 1e-8; the element arithmetic of ls2fm_adam_step) with the rates lr_rot (se3[:, 0:3]),
+ *             lr_trans (se3[:, 3:6]) and lr_points, each multiplied by gamma after every iteration (ExponentialLR).  A point
+ *             without an observation is not touched (value and moments).
+ *   prepare   ls2fm_bundle_adjust_prepare, ONCE per loop (it synchronises `stream`; not capturable): view_start [V + 1] (int32,
+ *             device; view v owns observations view_start[v] : view_start[v + 1]) and obs_point [n_obs] (int32, device; the point
+ *             each observation sees) are read back, checked, and copied into `workspace` together with the point -> observations
+ *             lists.  LS2FM_ERR_INVALID_ARGUMENT: n_obs < 1, n_views < 1, n_points < 1, view_start[0] != 0, view_start[V] != n_obs,
+ *             a view without an observation, an obs_point outside [0, n_points).  The kernels index through the workspace's
+ *             copies only.  workspace: ls2fm_bundle_adjust_workspace_bytes (negative for sizes that are refused).
+ *   run       ls2fm_bundle_adjust_run: se3 [V][6] and points [P][3] are updated in place; m_* / v_* are Adam's moment buffers
+ *             (zero before the first iteration) and steps_done the number of iterations already taken on them -- both owned by
+ *             the caller, so 2 calls of 10 iterations equal 1 call of 20 bit for bit.  intrinsic_host: K as 9 HOST floats.
+ *             log [n_iters][3] (device): reproj, w, mean(err) of every iteration.  se3_entering_last [V][6] / points_entering_last
+ *             [P][3]: the state that ENTERED the call's last iteration (what BA_Trad writes back after its loop, BA_Trad.py:124-127;
+ *             log[n_iters - 1][2] is the value it returns); se3 / points hold the state after the last Adam step.
+ *             LS2FM_ERR_INVALID_ARGUMENT: n_iters < 1, null buffers, sizes as above; LS2FM_ERR_WORKSPACE: null workspace;
+ *             LS2FM_ERR_UNSUPPORTED: `stream` is capturing (the per-iteration scalars come from the host's step count).  A
+ *             workspace that prepare did not fill for these sizes moves nothing and logs NaN.
+ */
+int64_t ls2fm_bundle_adjust_workspace_bytes(int32_t n_views, int64_t n_points, int64_t n_obs);
+int ls2fm_bundle_adjust_prepare(const int32_t* view_start, int32_t n_views, const int32_t* obs_point, int64_t n_obs, int64_t n_points,
+                                void* workspace, void* stream);
+int ls2fm_bundle_adjust_run(float* se3, float* points, const float* obs_uv, int32_t n_views, int64_t n_points, int64_t n_obs,
+                            const float* intrinsic_host, double lr_rot, double lr_trans, double lr_points, double gamma, float w_lo,
+                            float w_hi, float thresh, float* m_se3, float* v_se3, float* m_points, float* v_points, int64_t steps_done,
+                            int32_t n_iters, float* log, float* se3_entering_last, float* points_entering_last, void* workspace,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -10,7 +10,7 @@
 // from torch's only in rounding: weight decay is one fmaf, and (1 - b2) g' g' is multiplied in torch's order, so a g'^2 above
 // fp32's range does not overflow where the weighted term fits.  tests/test_hip_fused_adam.py holds every launch form to a
 // float64 Adam element by element.
-#include "ls2fm_device.h"
+#include "adam_element.h"
 
 namespace {
 
@@ -36,16 +36,6 @@ struct AdamJobs {
     int first_block[kAdamMaxTensors + 1];
     int count;
 };
-
-struct AdamHyper { float step_size, bc2_sqrt, w1, beta2, one_minus_beta2, eps, weight_decay; };
-
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
-    if (h.weight_decay != 0.f) g = fmaf(h.weight_decay, p, g);
-    m = h.w1 < 0.5f ? m + h.w1 * (g - m) : g - (g - m) * (1.0f - h.w1);       // torch lerp
-    v = v * h.beta2 + (h.one_minus_beta2 * g) * g;
-    const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
-    p = p - h.step_size * (m / denom);
-}
 
 // Device-resident schedule of a capturable optimizer: a hipGraph replay cannot take a new learning rate or step count from the
 // host, so both live in memory and a one-thread kernel in front of the update advances them

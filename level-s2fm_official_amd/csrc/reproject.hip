@@ -8,34 +8,11 @@
 // ~450 launch-bound kernels of a captured BA iteration.  Observations are SORTED BY VIEW (view v owns [view_start[v],
 // view_start[v + 1])): one workgroup per view, fixed-order reductions -- the pose gradients are deterministic (no atomics).
 #include "render_common.h"
+#include "reproject_point.h"
 
 namespace {
 
 constexpr int kRpThreads = 256;
-
-struct Camera3 { float k[9]; };
-
-struct Obs {                       // forward quantities of one observation
-    float xc[3], u[3], e[2], err, inv;
-    bool on;
-};
-
-__device__ __forceinline__ Obs project(const float* __restrict__ x, const float* __restrict__ pose, const Camera3& K,
-                                       const float* __restrict__ uv_obs, const float* __restrict__ sdf, float bound, int64_t i) {
-    Obs o;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        o.xc[a] = fmaf(pose[4 * a + 2], x[3 * i + 2], fmaf(pose[4 * a + 1], x[3 * i + 1], pose[4 * a] * x[3 * i])) + pose[4 * a + 3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) o.u[a] = fmaf(K.k[3 * a + 2], o.xc[2], fmaf(K.k[3 * a + 1], o.xc[1], K.k[3 * a] * o.xc[0]));
-    o.inv = 1.0f / (o.u[2] + 1e-6f);
-    const float uv0 = o.u[0] * o.inv, uv1 = o.u[1] * o.inv;
-    o.e[0] = uv0 - uv_obs[2 * i];
-    o.e[1] = uv1 - uv_obs[2 * i + 1];
-    o.err = sqrtf(fmaf(o.e[1], o.e[1], o.e[0] * o.e[0]));
-    o.on = (sdf == nullptr || fabsf(sdf[i]) < bound) && !isinf(uv0) && !isinf(uv1);
-    return o;
-}
 
 // one workgroup per view: partial[v] = {sum robust, sum err, count} over its counted observations, in fp64, fixed order
 __global__ void __launch_bounds__(kRpThreads)
@@ -49,7 +26,7 @@ reproject_fwd_kernel(const float* __restrict__ x, const float* __restrict__ pose
     __syncthreads();
     double acc[3] = {0.0, 0.0, 0.0};
     for (int64_t i = view_start[v] + tid; i < view_start[v + 1]; i += kRpThreads) {
-        const Obs o = project(x, s_pose, K, uv_obs, sdf, bound, i);
+        const Obs o = project(x + 3 * i, s_pose, K, uv_obs + 2 * i, sdf ? sdf + i : nullptr, bound);
         const float err = o.on ? o.err : 0.f;
         err_out[i] = err;
         on_out[i] = o.on ? 1 : 0;
@@ -94,7 +71,7 @@ reproject_bwd_kernel(const float* __restrict__ x, const float* __restrict__ pose
 #pragma unroll
     for (int q = 0; q < 12; ++q) acc[q] = 0.f;
     for (int64_t i = view_start[v] + tid; i < view_start[v + 1]; i += kRpThreads) {
-        const Obs o = project(x, s_pose, K, uv_obs, sdf, bound, i);
+        const Obs o = project(x + 3 * i, s_pose, K, uv_obs + 2 * i, sdf ? sdf + i : nullptr, bound);
         float dx[3] = {0.f, 0.f, 0.f};
         if (o.on && o.err > 0.f) {
             // d err: 1 from the plain mean, err / (1 + err^2 / 4) from the robust one
@@ -124,12 +101,6 @@ reproject_bwd_kernel(const float* __restrict__ x, const float* __restrict__ pose
         for (int k = 0; k < kRpThreads; ++k) t += s_red[k][tid];
         d_poses[12 * v + tid] = t;
     }
-}
-
-bool load_intrinsic(const float* host_k, Camera3* out) {
-    if (!host_k) return false;
-    for (int q = 0; q < 9; ++q) out->k[q] = host_k[q];
-    return true;
 }
 
 }  // namespace

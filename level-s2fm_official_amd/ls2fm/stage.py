@@ -1260,3 +1260,145 @@ class BALoop:
 
     def poses_se3(self):
         return torch.cat([self.rot, self.trans], dim=1).detach()
+
+
+class TradBALoop:
+    """`BA_Trad.BA` (pipelines/BA_Trad.py:16-130, the bundle adjustment behind `Ablate_config.ba_trad`): the explicit 3-D points
+    and the se(3) poses of the picked views are the parameters; no field, no renderer, no `opt`.  Per iteration: the live poses
+    `se3_to_SE3(cat(r, t))`, every observation of `util.get_idx3d_camset` (per picked view, every key point that has a 3-D point)
+    projected with the FIRST camera's intrinsic, `reproj = 0.5 mean(2 log(1 + err^2 / 4)) + 0.5 mean(err)` over all of them, the
+    weight 10^1 when `reproj > 10` else 10^0 (the reference's `.item()` decision: a select on the device), backward, Adam over
+    {rotations: lr_pose_r, translations: lr_pose_t, points: lr_xyzs}, ExponentialLR with gamma = (lr_sdf_end / lr_sdf)^(1 / max_iter).
+
+    views: `TrackedViews` (its `images` are not read; `poses` may be [V,6] se(3) parameters or [V,3,4]).  cam_pick: the views to
+    adjust, in this order (`cam_pick_ids`; None: all; a single one halves max_iter, BA_Trad.py:39-41).  w_reproj is the exponent the
+    reference keeps in `opt.loss_weight.ba.reproj_error`; the loop overwrites it before its first use, so it only names the state.
+
+    On the device `run()` is ONE call of ls2fm_bundle_adjust_run (two launches per iteration, nothing read back); off the device the
+    same iteration runs as torch ops (autograd, torch.optim.Adam, ExponentialLR) so that the bookkeeping is testable anywhere.
+
+    State after `run()` / `step()`:
+      poses_se3(), xyzs_all     the STEPPED state: after the last Adam step (what a resumed loop continues from; all points of the
+                                set, the ones no picked view observes unchanged)
+      written_back()            (se3 [V,6], xyzs [M,3], mean err): the state that ENTERED the last iteration and that iteration's
+                                mean(err) -- what BA_Trad writes into its cameras / returns after the loop (BA_Trad.py:124-128);
+                                a drop-in caller writes THIS back
+    """
+
+    def __init__(self, views, cam_pick=None, lr_pose_r=5e-3, lr_pose_t=1e-2, lr_xyzs=1e-2, lr_sdf=1e-4, lr_sdf_end=5e-5, max_iter=1000,
+                 w_reproj=0):
+        n_all = len(views.track_ids)
+        self.cam_pick = list(range(n_all)) if cam_pick is None else [int(c) for c in cam_pick]
+        if not self.cam_pick or any(c < 0 or c >= n_all for c in self.cam_pick):
+            raise ValueError(f"cam_pick {self.cam_pick} does not select views of 0..{n_all - 1}")
+        max_iter = int(max_iter)
+        if cam_pick is not None and len(self.cam_pick) == 1:
+            max_iter = max_iter // 2
+        if max_iter < 1:
+            raise ValueError("max_iter < 1")
+        self.max_iter, self.it = max_iter, 0
+        self.lrs = (float(lr_pose_r), float(lr_pose_t), float(lr_xyzs))
+        self.gamma = (float(lr_sdf_end) / float(lr_sdf)) ** (1.0 / max_iter)
+        self.w_reproj = w_reproj
+        self.views = views
+        dev = views.xyzs.device
+        se3_all = views.poses if views.poses.shape[-1] == 6 else _cam.lie.SE3_to_se3(views.poses)
+        self.se3 = se3_all[self.cam_pick].detach().float().clone().contiguous().to(dev)
+        self.xyzs_all = views.xyzs.detach().float().clone().contiguous()
+        # the observation list of util.get_idx3d_camset (utils/util.py:450-464), sorted by picked view
+        ids = [views.track_ids[c] for c in self.cam_pick]
+        self.obs_view = torch.cat([torch.full((t.shape[0],), j, dtype=torch.long) for j, t in enumerate(ids)]).to(dev)
+        self.obs_point = torch.cat(ids).long().to(dev)
+        self.obs_uv = torch.cat([views.keypoints[c] for c in self.cam_pick]).float().contiguous().to(dev)
+        self.view_start = torch.tensor([0] + [t.shape[0] for t in ids], dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+        self.intrinsic = views.intrinsic.detach().float().to(dev)
+        self.se3_entering_last, self.xyzs_entering_last = self.se3.clone(), self.xyzs_all.clone()
+        self._err_last = None
+        self._keys = ("reproj_error", "w_reproj", "err_mean")
+        if self.xyzs_all.is_cuda:
+            self._init_device()
+        else:
+            self._init_torch()
+
+    # ---- device path
+    def _init_device(self):
+        from . import _lib
+        lib = _lib.load()
+        V, P, n, dev = self.se3.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.se3.device
+        size = int(lib.ls2fm_bundle_adjust_workspace_bytes(V, P, n))
+        if size < 0:
+            _lib.check(size, "ls2fm_bundle_adjust_workspace_bytes")
+        self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
+        self._obs_point32 = self.obs_point.to(torch.int32).contiguous()
+        _lib.check(lib.ls2fm_bundle_adjust_prepare(_lib.ptr(self.view_start), V, _lib.ptr(self._obs_point32), n, P, _lib.ptr(self._ws),
+                                                   _lib.stream_ptr()), "ls2fm_bundle_adjust_prepare")
+        self._k_host = host_intrinsic(self.intrinsic)
+        self._m = [torch.zeros_like(self.se3), torch.zeros_like(self.se3), torch.zeros_like(self.xyzs_all), torch.zeros_like(self.xyzs_all)]
+
+    def _run_device(self, n_iters):
+        from . import _lib
+        lib = _lib.load()
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TradBALoop.run cannot be captured into a graph: the per-iteration Adam / ExponentialLR scalars come "
+                               "from the host's step count (a replay would repeat one iteration's scalars); call it eagerly")
+        V, P, n = self.se3.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0]
+        log = torch.empty(n_iters, 3, device=self.se3.device)
+        _lib.check(lib.ls2fm_bundle_adjust_run(_lib.ptr(self.se3), _lib.ptr(self.xyzs_all), _lib.ptr(self.obs_uv), V, P, n, self._k_host,
+                                               self.lrs[0], self.lrs[1], self.lrs[2], self.gamma, 1.0, 10.0, 10.0, _lib.ptr(self._m[0]),
+                                               _lib.ptr(self._m[1]), _lib.ptr(self._m[2]), _lib.ptr(self._m[3]), self.it, n_iters,
+                                               _lib.ptr(log), _lib.ptr(self.se3_entering_last), _lib.ptr(self.xyzs_entering_last),
+                                               _lib.ptr(self._ws), _lib.stream_ptr()), "ls2fm_bundle_adjust_run")
+        return log
+
+    # ---- the same iteration as torch ops (BA_Trad.py:90-122)
+    def _init_torch(self):
+        self._r = torch.nn.Parameter(self.se3[:, :3].clone())
+        self._t = torch.nn.Parameter(self.se3[:, 3:].clone())
+        self._x = torch.nn.Parameter(self.xyzs_all)
+        self._optim = torch.optim.Adam([dict(params=[self._r], lr=self.lrs[0]), dict(params=[self._t], lr=self.lrs[1]),
+                                        dict(params=[self._x], lr=self.lrs[2])])
+        self._sched = torch.optim.lr_scheduler.ExponentialLR(self._optim, gamma=self.gamma)
+
+    def _run_torch(self, n_iters):
+        rows = []
+        for _ in range(n_iters):
+            se3 = torch.cat([self._r, self._t], dim=1)
+            self._optim.zero_grad()
+            x = self._x[self.obs_point]
+            in_cam = _cam.world2cam(x.unsqueeze(1), _cam.lie.se3_to_SE3(se3[self.obs_view]))
+            uv = _cam.cam2img(in_cam, self.intrinsic.expand(in_cam.shape[0], 3, 3))
+            uv = (uv / (uv[..., 2:] + 1e-6))[..., :2].squeeze(1)
+            err = (uv - self.obs_uv).norm(dim=-1)
+            reproj = 0.5 * (2 * torch.log(1 + err ** 2 / 4)).mean() + 0.5 * err.mean()
+            w = torch.where(reproj.detach() > 10, 10.0, 1.0)                     # BA_Trad.py:111-114 without the `.item()`
+            self.se3_entering_last, self.xyzs_entering_last = se3.detach().clone(), self._x.detach().clone()
+            (w * reproj).backward()
+            self._optim.step()
+            self._sched.step()
+            rows.append(torch.stack([reproj.detach(), w.to(reproj.dtype), err.detach().mean()]))
+        self.se3 = torch.cat([self._r, self._t], dim=1).detach()
+        self.xyzs_all = self._x.detach()
+        return torch.stack(rows)
+
+    def run(self, n_iters=None):
+        """the remaining iterations (or n_iters of them) -> logs: tensors [n] on the loop's device: reproj_error, w_reproj (the
+        factor 10^w the loss was multiplied with), err_mean"""
+        n_iters = self.max_iter - self.it if n_iters is None else int(n_iters)
+        if n_iters < 1:
+            raise ValueError(f"nothing to run: n_iters = {n_iters} (iteration {self.it} of {self.max_iter})")
+        log = self._run_device(n_iters) if self.xyzs_all.is_cuda else self._run_torch(n_iters)
+        self.it += n_iters
+        self._err_last = log[-1, 2]
+        return {k: log[:, q] for q, k in enumerate(self._keys)}
+
+    def step(self):
+        """one iteration -> its terms as 0-d tensors"""
+        return {k: v[0] for k, v in self.run(1).items()}
+
+    def poses_se3(self):
+        return self.se3.detach()
+
+    def written_back(self):
+        if self._err_last is None:
+            raise RuntimeError("TradBALoop.written_back: no iteration has run yet")
+        return self.se3_entering_last, self.xyzs_entering_last, self._err_last
