@@ -854,6 +854,50 @@ int ls2fm_bundle_adjust_run(float* se3, float* points, const float* obs_uv, int3
                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Descriptor matching (csrc/match.hip; additions, the library stays ABI 13): the raw matches `colmap exhaustive_matcher` writes
+ * into its `matches` table (preparation/main.py:98, read back at :30-37) -- COLMAP's CPU SIFT matcher with its defaults,
+ * restated from the published algorithm -- for ALL image pairs in one call.  tests/match_restate.py repeats every rule in numpy.
+ *   descriptor 128 unsigned bytes (COLMAP normalises to length 512 and saturates at 255; every byte value 0..255 is served).
+ *              desc [N_total][128] holds all images; image v owns rows image_start[v] : image_start[v + 1] (HOST int32
+ *              [n_images + 1], from 0, non-decreasing).  pairs [n_pairs][2] (HOST int32): image a (first) and image b (second).
+ *   dot(i, j)  the integer inner product of descriptor i of a and descriptor j of b, exact (<= 128 * 255^2 = 8 323 200 < 2^24).
+ *   one way    row i over all j in increasing j: best = the largest dot, best_j = the LOWEST j that attains it (COLMAP's strict
+ *              >), second = the second largest of the multiset (a tie for the maximum makes second == best); both start at 0,
+ *              and a row whose best is 0 has no match (its best_j is reported as -1).
+ *   thresholds angle(d) = acos(min(d / 262144, 1)).  Row i proposes best_j unless angle(best) > max_distance or
+ *              angle(best) >= max_ratio * angle(second).  COLMAP's defaults: max_ratio 0.8, max_distance 0.7.  Both comparisons
+ *              are evaluated in fp64 from the two integers alone (COLMAP evaluates them in fp32: a decision can differ only where
+ *              the two sides are within fp32 rounding of each other).
+ *   other way  the same rule on the transposed products (rows = descriptors of b, columns = descriptors of a).
+ *   cross check (cross_check != 0, COLMAP's default): (i, j) is a match iff i proposes j and j proposes i; 0: the proposals of a.
+ *   order      the matches of a pair in increasing i.  At most LS2FM_MATCH_MAX_DESCRIPTORS per image (COLMAP's
+ *              max_num_matches); an image with more: LS2FM_ERR_UNSUPPORTED.  Images without descriptors and pairs without a
+ *              match are legal and give empty results.  Not restated: guided matching, COLMAP's two-view geometry table.
+ *   outputs    (device, int32; sizes follow from the host arrays) with first(p) = sum over q < p of n_a(q) and
+ *              rows(p) = sum over q < p of (n_a(q) + n_b(q)):
+ *              match_index [sum n_a]: entry first(p) + i = the j matched to row i of pair p's first image, or -1;
+ *              num_matches [n_pairs];
+ *              best / best_j / second [sum (n_a + n_b)] (each may be NULL): the raw integers of both directions, a -> b at
+ *              rows(p) + i (i < n_a, best_j indexes b), b -> a at rows(p) + n_a + j (j < n_b, best_j indexes a).
+ *              The compacted [M][2] lists are ls2fm.match's (one nonzero over match_index).
+ *   call       asynchronous on `stream`, nothing is read back from the device; the two small tables built from image_start and
+ *              pairs are copied from the host inside the call.  desc and workspace must be 16-byte aligned.  Every bit of a
+ *              pair's result depends on its own descriptors and the thresholds only: a batch equals the single-pair calls and
+ *              a rerun bit for bit (the products are exact integers, the top-2 merges are order independent, the only atomics
+ *              are the integer counts).
+ *   refusals   nothing enqueued: LS2FM_ERR_INVALID_ARGUMENT for NULL image_start / pairs / desc / match_index / num_matches,
+ *              n_images < 1, n_pairs < 0, image_start not rising from 0, a pair index outside [0, n_images), thresholds that are
+ *              negative or not finite, a misaligned desc; LS2FM_ERR_UNSUPPORTED for an image above the cap or totals beyond
+ *              int32; LS2FM_ERR_WORKSPACE for a NULL or misaligned workspace.  The size query refuses the same way (negative).
+ */
+#define LS2FM_MATCH_MAX_DESCRIPTORS 32768
+
+int64_t ls2fm_match_descriptors_workspace_bytes(const int32_t* image_start, int32_t n_images, const int32_t* pairs, int32_t n_pairs);
+int ls2fm_match_descriptors(const uint8_t* desc, const int32_t* image_start, int32_t n_images, const int32_t* pairs, int32_t n_pairs,
+                            double max_ratio, double max_distance, int32_t cross_check, int32_t* match_index, int32_t* num_matches,
+                            int32_t* best, int32_t* best_j, int32_t* second, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -193,6 +193,8 @@ _SIGNATURES = {
     "ls2fm_bundle_adjust_prepare": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P, _P]),
     "ls2fm_bundle_adjust_run": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int64, POINTER(c_float), c_double, c_double, c_double, c_double,
                                           c_float, c_float, c_float, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "ls2fm_match_descriptors_workspace_bytes": (c_int64, [_P, c_int32, _P, c_int32]),
+    "ls2fm_match_descriptors": (c_int32, [_P, _P, c_int32, _P, c_int32, c_double, c_double, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

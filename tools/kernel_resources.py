@@ -6,7 +6,8 @@ import glob, os, re, subprocess, sys
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "level-s2fm_official_amd", "csrc")
 files = sys.argv[1:] or sorted(glob.glob(os.path.join(root, "*.hip")))
 flags = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -munsafe-fp-atomics -Rpass-analysis=kernel-resource-usage".split()
-per_file = {"render_fwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]}      # = the Makefile's FLAGS_<file>
+per_file = {"render_fwd.hip": ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"],      # = the Makefile's FLAGS_<file>
+            "match.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 bad = 0
 for f in files:
     out = subprocess.run(["/opt/rocm/bin/hipcc", *flags, *per_file.get(os.path.basename(f), []), "-c", f, "-o", "/dev/null"], capture_output=True, text=True).stderr
