@@ -112,8 +112,110 @@ def run(se3, xyzs, obs_point, obs_view, obs_uv, intrinsic, n_iters, max_iter, lr
     return out
 
 
+def one_iteration(se3, xyzs, obs_point, obs_view, obs_uv, intrinsic, dtype=torch.float64, zero_err_obs=()):
+    """The loss of ONE iteration and its gradient, written on its own (not through `run`): the reference's formula in `dtype`
+    (float64: the checker; float32: the same formula rounded on the CPU, the yardstick of the bars).
+    zero_err_obs: observations whose key point is replaced by this evaluation's own projection, so that err == 0 exactly in
+    every precision (norm backward at 0: zero) -- the device test places the key point on the kernel's fp32 projection.
+    -> dict: reproj, err_mean, weight (floats), d_se3 [V,6], d_points [P,3] (float64 numpy, of the UNWEIGHTED reproj), u_z [n]"""
+    wu = torch.tensor(np.asarray(se3), dtype=dtype).requires_grad_(True)
+    x = torch.tensor(np.asarray(xyzs), dtype=dtype).requires_grad_(True)
+    K, key = torch.tensor(np.asarray(intrinsic), dtype=dtype), torch.tensor(np.asarray(obs_uv), dtype=dtype)
+    op, ov = torch.tensor(np.asarray(obs_point), dtype=torch.long), torch.tensor(np.asarray(obs_view), dtype=torch.long)
+    pose = se3_to_SE3(wu)[ov]                                                # [n,3,4]
+    xc = (pose[:, :, :3] @ x[op][:, :, None])[..., 0] + pose[:, :, 3]
+    u = xc @ K.T
+    uv = (u / (u[:, 2:] + 1e-6))[:, :2]
+    if len(zero_err_obs):
+        key = key.clone()
+        key[list(zero_err_obs)] = uv.detach()[list(zero_err_obs)]
+    err = (uv - key).norm(dim=-1)
+    reproj = 0.5 * (2 * torch.log(1 + err ** 2 / 4)).mean() + 0.5 * err.mean()
+    d_se3, d_points = torch.autograd.grad(reproj, [wu, x])
+    return dict(reproj=float(reproj.detach()), err_mean=float(err.detach().mean()), weight=10.0 if float(reproj.detach()) > 10 else 1.0,
+                d_se3=d_se3.double().numpy(), d_points=d_points.double().numpy(), u_z=u.detach()[:, 2].double().numpy())
+
+
+# ------------------------------------------------------------------------------------- a scene of the kernels' rarely hit branches
+SCENE_COUNTS = (300, 1, 255, 256, 257, 5000, 120)       # observations per view: around the residual kernel's 256 threads
+SCENE_POINTS, SCENE_UNSEEN = 6000, 200                  # the last SCENE_UNSEEN points are observed by no view
+SCENE_K = np.array([[520.0, 0.0, 320.0], [0.0, 515.0, 240.0], [0.0, 0.0, 1.0]], dtype=np.float32)
+
+
+def _fma32(a, b, c):
+    """fmaf on float32 values: the product of two float32 is exact in float64; the sum is then rounded to float64 and to float32
+    (a double rounding differs from one only on a 2^-29 tie pattern; the device test notices: it asserts the zero gradient)"""
+    return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+def project_identity_f32(x, K):
+    """csrc/reproject_point.h's arithmetic, operation by operation in float32, for the IDENTITY pose (x_c = x exactly):
+    u_a = fmaf(k_a2, z, fmaf(k_a1, y, k_a0 * x)) ; inv = 1 / (u_z + 1e-6f) ; uv = u_xy * inv"""
+    f = np.float32
+    x, K = np.asarray(x, dtype=f), np.asarray(K, dtype=f)
+    u = [_fma32(K[a, 2], x[2], _fma32(K[a, 1], x[1], f(K[a, 0] * x[0]))) for a in range(3)]
+    inv = f(1.0) / f(u[2] + f(1e-6))
+    return np.array([f(u[0] * inv), f(u[1] * inv)], dtype=f)
+
+
+def synthetic_scene(seed=2024):
+    """7 views over 6000 points, float32 values.  On purpose: view 0 has se3 = 0 exactly (theta = 0), view 1 |w| = 1e-4 and ONE
+    observation, view 6 |w| = 3.0 (about the optical axis, so every depth stays near 6); 255 / 256 / 257 / 5000 observations
+    in views 2..5; point 0 is observed by every view, point 1 by view 0 only and its key point IS the kernel's fp32 projection
+    (err == 0 bit for bit), most points by exactly one view, the last 200 by none; the observations of a view are in random
+    order.  Key points: the float64 projection + N(0, 2 px).  -> dict(se3, xyzs, intrinsic, keypoints, track_ids, zero_err_obs)"""
+    rng = np.random.default_rng(seed)
+    V, P = len(SCENE_COUNTS), SCENE_POINTS
+    xyzs = (rng.uniform(-1.0, 1.0, size=(P, 3)) + np.array([0.0, 0.0, 6.0])).astype(np.float32)
+    se3 = np.zeros((V, 6), dtype=np.float64)
+    for v in range(1, V):
+        w = rng.normal(size=3)
+        se3[v, :3] = w / np.linalg.norm(w) * rng.uniform(0.05, 0.6)
+        se3[v, 3:] = rng.uniform(-0.3, 0.3, size=3)
+    w = rng.normal(size=3)
+    se3[1, :3] = w / np.linalg.norm(w) * 1e-4
+    w = np.array([0.02, -0.015, 1.0])
+    se3[6, :3] = w / np.linalg.norm(w) * 3.0
+    se3 = se3.astype(np.float32)
+    seen = P - SCENE_UNSEEN
+    ids = []
+    for v, c in enumerate(SCENE_COUNTS):
+        others = rng.choice(np.arange(2, seen), size=c - 1, replace=False)
+        i = np.concatenate([[0], others])
+        if v == 0:
+            i[1] = 1
+        ids.append(i[rng.permutation(c)].astype(np.int64))
+    assert ids[1].tolist() == [0]
+    op = np.concatenate(ids)
+    ov = np.concatenate([np.full(len(i), v) for v, i in enumerate(ids)])
+    with torch.no_grad():
+        pose = se3_to_SE3(torch.tensor(se3, dtype=torch.float64))[torch.tensor(ov)]
+        xc = (pose[:, :, :3] @ torch.tensor(xyzs, dtype=torch.float64)[torch.tensor(op)][:, :, None])[..., 0] + pose[:, :, 3]
+        u = xc @ torch.tensor(SCENE_K, dtype=torch.float64).T
+        uv = (u[:, :2] / u[:, 2:]).numpy()
+    assert u[:, 2].min() > 3.0, "a point too close to a camera"
+    uv = (uv + rng.normal(0.0, 2.0, size=uv.shape)).astype(np.float32)
+    k0 = int(np.nonzero(ids[0] == 1)[0][0])                          # view 0 starts the list: its local index is the global one
+    uv[k0] = project_identity_f32(xyzs[1], SCENE_K)
+    starts = np.concatenate([[0], np.cumsum(SCENE_COUNTS)])
+    kps = [uv[starts[v]:starts[v + 1]] for v in range(V)]
+    return dict(se3=se3, xyzs=xyzs, intrinsic=SCENE_K.copy(), keypoints=kps, track_ids=ids, zero_err_obs=[k0], obs_point=op, obs_view=ov,
+                obs_uv=uv)
+
+
 # ---------------------------------------------------------------------------------------------------- the bars of both test files
 MARGIN = 4.0          # two independently rounded fp32 runs can each sit one fp32-vs-fp64 gap from the truth; doubled for headroom
+
+
+def within_f32_gap(name, key, mine, ref64, ref32, margin=MARGIN):
+    """one quantity of a single evaluation: |mine - fp64| <= max(margin * |fp32 on the CPU - fp64|, one fp32 spacing of the
+    quantity's largest magnitude), maxima over the quantity's elements.  Prints the figures, returns the failure or None."""
+    mine, ref64, ref32 = (np.asarray(a, dtype=np.float64) for a in (mine, ref64, ref32))
+    d, gap = float(np.abs(mine - ref64).max()), float(np.abs(ref32 - ref64).max())
+    quantum = float(np.spacing(np.float32(np.abs(ref64).max())))
+    bar = max(margin * gap, quantum)
+    print(f"[{name}] {key:10s} device-fp64 {d:.3e}  fp32-fp64 {gap:.3e}  spacing {quantum:.2e}  bar {bar:.3e}  (largest magnitude {np.abs(ref64).max():.3e})")
+    return None if d <= bar else (key, d, gap, quantum)
 
 
 def build_loop(g, device, shuffle_seed=None, **kw):

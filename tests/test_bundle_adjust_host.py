@@ -49,6 +49,51 @@ def test_restatement_follows_the_long_run_while_rounding_is_not_amplified():
     assert worst <= RESTATE_TOL, worst
 
 
+@pytest.mark.parametrize("case", ["local", "heavy"])
+def test_one_iteration_restatement_is_the_trajectory_s_first_step(case):
+    """ba_restate.one_iteration (written on its own) against ba_restate.run's first iteration: the loss terms, and run's stepped
+    parameters against Adam's first step formed from one_iteration's gradient -- the two restatements cannot drift apart"""
+    g = BR.load_case(case)
+    op, ov, uv, pick = BR.observation_list(g)
+    se3 = g["se3"][pick].astype(np.float64)
+    one = BR.one_iteration(se3, g["xyzs"], op, ov, uv, g["intrinsic"])
+    r = BR.run(se3, g["xyzs"], op, ov, uv, g["intrinsic"], 1, g["meta"]["iters"])
+    assert abs(one["reproj"] / r["reproj"][0] - 1) <= RESTATE_TOL and abs(one["err_mean"] / r["err_mean"][0] - 1) <= RESTATE_TOL
+    assert one["weight"] == r["weight"][0] == g["f64/weight"][0]
+    lrs = np.array([5e-3] * 3 + [1e-2] * 3)
+
+    def stepped(p, grad, lr):                                   # m = 0.1 g, v = 0.001 g^2, both bias corrections at step 1
+        gw = one["weight"] * grad
+        return p - (lr / (1 - 0.9)) * (0.1 * gw) / (np.sqrt(0.001 * gw * gw) / np.sqrt(1 - 0.999) + 1e-8)
+    assert np.abs(stepped(se3, one["d_se3"], lrs) - r["se3"]).max() <= RESTATE_TOL
+    assert np.abs(stepped(g["xyzs"].astype(np.float64), one["d_points"], 1e-2) - r["xyzs"]).max() <= RESTATE_TOL
+    unseen = np.setdiff1d(np.arange(g["xyzs"].shape[0]), op)
+    assert not one["d_points"][unseen].any()
+
+
+def test_synthetic_scene_holds_what_it_says():
+    sc = BR.synthetic_scene()
+    counts = [len(i) for i in sc["track_ids"]]
+    assert tuple(counts) == BR.SCENE_COUNTS and {1, 255, 256, 257} <= set(counts) and max(counts) == 5000
+    theta = np.linalg.norm(sc["se3"][:, :3].astype(np.float64), axis=1)
+    assert theta[0] == 0 and not sc["se3"][0].any() and abs(theta[1] - 1e-4) < 1e-9 and abs(theta[6] - 3.0) < 1e-6
+    seen = np.bincount(sc["obs_point"], minlength=BR.SCENE_POINTS)
+    assert seen[0] == 7 and seen[1] == 1 and (seen == 1).sum() > 1000 and not seen[-BR.SCENE_UNSEEN:].any() and seen[:-BR.SCENE_UNSEEN].max() == 7
+    assert all(len(np.unique(i)) == len(i) and not np.array_equal(i, np.sort(i)) for i in sc["track_ids"][2:])
+    k0 = sc["zero_err_obs"][0]
+    assert sc["obs_point"][k0] == 1 and sc["obs_view"][k0] == 0
+    for dtype in (torch.float64, torch.float32):
+        one = BR.one_iteration(sc["se3"], sc["xyzs"], sc["obs_point"], sc["obs_view"], sc["obs_uv"], sc["intrinsic"], dtype, sc["zero_err_obs"])
+        assert one["u_z"].min() > 3.0 and np.isfinite(one["d_se3"]).all() and np.isfinite(one["d_points"]).all()
+        assert not one["d_points"][1].any() and one["d_points"][0].all() and not one["d_points"][-BR.SCENE_UNSEEN:].any()
+        assert one["weight"] == 1.0 and 1.0 < one["err_mean"] < 4.0
+    # the key point of the pinned observation is within fp32 rounding of the float64 projection
+    raw = BR.one_iteration(sc["se3"], sc["xyzs"], sc["obs_point"], sc["obs_view"], sc["obs_uv"], sc["intrinsic"])
+    x = sc["xyzs"][1].astype(np.float64)
+    uv = (sc["intrinsic"].astype(np.float64) @ x)[:2] / (x[2] + 1e-6)
+    assert np.abs(uv - sc["obs_uv"][k0]).max() < 1e-4 and raw["err_mean"] > 0
+
+
 @pytest.mark.parametrize("case", BR.CASES)
 def test_loop_on_the_host_follows_the_reference_fp32_trajectory(case):
     g = BR.load_case(case)

@@ -142,3 +142,92 @@ def test_run_refuses_cleanly_under_graph_capture():
     assert loop.it == 0
     la, lb = loop.run(), fresh.run()                    # nothing was enqueued or moved by the refused call
     assert all(torch.equal(la[k], lb[k]) for k in la) and same_bits(state(loop), state(fresh))
+
+
+# ------------------------------------------------------------------------------------------------ one iteration against float64
+W1 = float(np.float32(0.1))                     # adam_element.h's w1 = (float)(1 - beta1)
+OMB2 = float(np.float32(1.0 - 0.999))           # (float)(1 - beta2)
+
+
+def _scene_views(sc):
+    t = lambda a: torch.tensor(a, device=DEV)
+    return types.SimpleNamespace(poses=t(sc["se3"]), intrinsic=t(sc["intrinsic"]), keypoints=[t(k) for k in sc["keypoints"]],
+                                 track_ids=[t(i) for i in sc["track_ids"]], xyzs=t(sc["xyzs"]))
+
+
+def _one_iteration(name, loop, zero_err_obs=()):
+    """ONE device iteration from zero moments against ba_restate.one_iteration in float64.  After it m = w1 (wt g) exactly as
+    fp32 rounds it, so m / w1 is the kernel's gradient; the bars are within_f32_gap's (4 x the CPU fp32-vs-fp64 distance of the
+    same formula on the same inputs, floored at one fp32 spacing).  Then Adam's own arithmetic on the device's m and v."""
+    f = lambda t: t.detach().double().cpu().numpy()
+    se3_0, xyzs_0 = f(loop.se3), f(loop.xyzs_all)
+    args = (se3_0, xyzs_0, loop.obs_point.cpu().numpy(), loop.obs_view.cpu().numpy(), f(loop.obs_uv), f(loop.intrinsic))
+    r64 = BR.one_iteration(*args, torch.float64, zero_err_obs)
+    r32 = BR.one_iteration(*args, torch.float32, zero_err_obs)
+    assert r64["u_z"].min() > 0.5 and r64["weight"] == r32["weight"]
+    assert all(not m.any() for m in loop._m) and loop.it == 0
+    logs = loop.run(1)
+    m_se3, v_se3, m_pts, v_pts = (f(m) for m in loop._m)
+    se3_1, xyzs_1 = f(loop.se3), f(loop.xyzs_all)
+    assert all(np.isfinite(a).all() for a in (m_se3, v_se3, m_pts, v_pts, se3_1, xyzs_1))
+    wt = float(logs["w_reproj"][0])
+    assert wt == r64["weight"], f"{name}: weight {wt} vs {r64['weight']}"
+    bad = [BR.within_f32_gap(name, "reproj", float(logs["reproj_error"][0]), r64["reproj"], r32["reproj"]),
+           BR.within_f32_gap(name, "err_mean", float(logs["err_mean"][0]), r64["err_mean"], r32["err_mean"]),
+           BR.within_f32_gap(name, "wt d_se3", m_se3 / W1, wt * r64["d_se3"], wt * r32["d_se3"]),
+           BR.within_f32_gap(name, "wt d_points", m_pts / W1, wt * r64["d_points"], wt * r32["d_points"])]
+    for q, what in ((slice(0, 3), "rotation"), (slice(3, 6), "translation")):      # printed only: the bar above is the issue's
+        BR.within_f32_gap(name, "  " + what, m_se3[:, q] / W1, wt * r64["d_se3"][:, q], wt * r32["d_se3"][:, q])
+    assert not any(bad), f"{name}: beyond the bar: {[b for b in bad if b]}"
+    # points no view observes: untouched, moments zero; every other point has a gradient in float64 unless its err is 0
+    unseen = np.setdiff1d(np.arange(xyzs_0.shape[0]), args[2])
+    assert not m_pts[unseen].any() and not v_pts[unseen].any()
+    assert np.array_equal(loop.xyzs_all.cpu().numpy()[unseen].view(np.uint32), xyzs_0.astype(np.float32)[unseen].view(np.uint32))
+    # v = (1 - beta2) (wt g)^2: m / w1 carries one rounding of g (2^-24, squared 2^-23), v two of its own (2 x 2^-24) -> 2^-22
+    for m, v, what in ((m_se3, v_se3, "poses"), (m_pts, v_pts, "points")):
+        want = OMB2 * (m / W1) ** 2
+        rel = np.abs(v - want) / np.maximum(want, 2.0 ** -126)
+        print(f"[{name}] v of the {what}: max relative distance from (1 - beta2) (m / w1)^2 {rel.max():.3e} (bar 2^-22 = {2.0 ** -22:.3e})")
+        assert rel.max() <= 2.0 ** -22 * 1.01, f"{name}: v of the {what}"
+    # the step, in float64 from the device's m and v with the call's fp32 scalars (bundle_adjust.hip): five fp32 roundings in
+    # sqrt, /, +, /, * (bar 8 x 2^-24 of the step) and the rounding of p itself (half a spacing of p)
+    bc2_sqrt, eps = float(np.float32(np.sqrt(1.0 - 0.999 ** 1.0))), float(np.float32(1e-8))
+    lr = np.array([loop.lrs[0]] * 3 + [loop.lrs[1]] * 3)
+    for p0, p1, m, v, rate, what in ((se3_0, se3_1, m_se3, v_se3, lr, "poses"), (xyzs_0, xyzs_1, m_pts, v_pts, loop.lrs[2], "points")):
+        size = np.float32(rate / (1.0 - 0.9 ** 1.0)).astype(np.float64)
+        step = size * (m / (np.sqrt(v) / bc2_sqrt + eps))
+        bar = 0.5 * np.spacing(np.maximum(np.abs(p0), np.abs(p1)).astype(np.float32)).astype(np.float64) + 8 * 2.0 ** -24 * np.abs(step)
+        d = np.abs((p0 - p1) - step)
+        print(f"[{name}] step of the {what}: max distance / bar {(d / bar).max():.3f}, largest step {np.abs(step).max():.3e}")
+        assert (d <= bar).all(), f"{name}: step of the {what}: {(d / bar).max():.3f} bars"
+    return dict(r64=r64, m_pts=m_pts, v_pts=v_pts, xyzs_0=xyzs_0, xyzs_1=xyzs_1, m_se3=m_se3)
+
+
+@pytest.mark.parametrize("case", ["local", "global", "heavy"])
+def test_one_iteration_gradients_match_float64_on_the_fixtures(case):
+    """The yardstick: |float32 on the CPU - float64| of ba_restate.one_iteration per quantity (absolute, maxima over the elements;
+    the bar is 4 x this, floored at one fp32 spacing of the largest magnitude, given in brackets), computed without a device:
+                    reproj            err_mean          wt d_se3          wt d_points
+        local       1.54e-06 (4.15)   1.96e-06 (4.75)   7.77e-05 (64.8)   2.91e-06 (0.263)
+        global      4.68e-07 (3.71)   4.13e-07 (4.23)   4.03e-05 (29.3)   2.94e-06 (0.274)
+        heavy       1.50e-07 (14.5)   7.07e-07 (20.3)   1.84e-04 (274)    8.77e-06 (1.11)     wt = 10
+        synthetic   9.99e-08 (2.19)   2.21e-07 (2.52)   5.00e-04 (6.06)   2.24e-06 (0.0391)
+    within_f32_gap prints the device's distance next to each when the test runs."""
+    _one_iteration(case, BR.build_loop(BR.load_case(case), DEV))
+
+
+def test_one_iteration_gradients_match_float64_on_the_synthetic_scene():
+    """ba_restate.synthetic_scene: theta = 0 / 1e-4 / 3.0, views of 1, 255, 256, 257 and 5000 observations, points seen once, by
+    every view and by none, shuffled lists, and one observation whose key point is the kernel's fp32 projection bit for bit."""
+    from ls2fm import stage
+    sc = BR.synthetic_scene()
+    loop = stage.TradBALoop(_scene_views(sc), max_iter=20)
+    assert loop.view_start.cpu().tolist() == np.concatenate([[0], np.cumsum(BR.SCENE_COUNTS)]).tolist()
+    out = _one_iteration("synthetic", loop, sc["zero_err_obs"])
+    # err == 0: no gradient for the point only that observation sees, nothing moves, everything finite (asserted above)
+    assert not out["m_pts"][1].any() and not out["v_pts"][1].any() and np.array_equal(out["xyzs_0"][1], out["xyzs_1"][1])
+    assert out["m_pts"][0].all() and out["m_se3"].all()
+    # the same scene with every view's list reversed: list order changes rounding only (the same bars hold again)
+    sc2 = dict(sc, keypoints=[k[::-1].copy() for k in sc["keypoints"]], track_ids=[i[::-1].copy() for i in sc["track_ids"]])
+    k0 = BR.SCENE_COUNTS[0] - 1 - sc["zero_err_obs"][0]
+    _one_iteration("synthetic, reversed lists", stage.TradBALoop(_scene_views(sc2), max_iter=20), [k0])

@@ -237,3 +237,53 @@ def test_fused_match_term_matches_the_torch_lines():
     assert abs(float(pr[4]) - float(f[4])) <= 2e-7 * abs(float(f[4]))
     for a, b in zip(pr[2] + pr[3], f[2] + f[3]):      # same kernels, same upstream values: the same bits
         assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------- the exponential alone against float64
+SE3_THETAS = (0.0, 1e-6, 1e-4, 1e-2, 0.5, 1.5, 3.0, 3.14)
+
+
+@pytest.mark.parametrize("n,first", [(1, 4), (63, 0), (64, 1), (65, 2), (1000, 3)])
+def test_se3_exp_fwd_and_bwd_against_the_float64_series(n, first):
+    """ls2fm_se3_exp_fwd / _bwd against tests/ba_restate.se3_to_SE3 (the 11-term series) in float64 and its autograd.  Row i has
+    theta = SE3_THETAS[(first + i) % 8] in a random direction, a random translation part and a random upstream gradient.  Per
+    theta and quantity the bar is ba_restate.within_f32_gap's: 4 x the distance between the same formula in float32 on the CPU
+    and float64, floored at one fp32 spacing of the quantity's largest magnitude.  That CPU distance over 125 such rows per theta
+    (magnitudes about 7): pose 0 at theta 0, 3.8e-07 .. 4.4e-07 up to 1.5 rad, 8.9e-07 at 3.0, 7.4e-07 at 3.14; d_se3 4.9e-07 at 0,
+    4.8e-07 / 6.3e-07 / 8.3e-07 / 8.5e-07 / 9.3e-07 at 1e-6 .. 1.5, 1.6e-06 at 3.0, 1.8e-06 at 3.14."""
+    import numpy as np
+
+    import ba_restate as BR
+    from ls2fm import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(100 + n)
+    which = (first + np.arange(n)) % len(SE3_THETAS)
+    w = rng.normal(size=(n, 3))
+    w = w / np.linalg.norm(w, axis=1, keepdims=True) * np.array(SE3_THETAS)[which][:, None]
+    se3 = np.concatenate([w, 2.0 * rng.normal(size=(n, 3))], axis=1).astype(np.float32)
+    up = rng.normal(size=(n, 3, 4)).astype(np.float32)
+    ref = {}
+    for dtype in (torch.float64, torch.float32):
+        x = torch.tensor(se3, dtype=dtype).requires_grad_(True)
+        pose = BR.se3_to_SE3(x)
+        (pose * torch.tensor(up, dtype=dtype)).sum().backward()
+        ref[dtype] = (pose.detach().double().numpy(), x.grad.double().numpy())
+    d_se3, d_up = torch.tensor(se3, device=DEV), torch.tensor(up, device=DEV)
+    poses, grad = torch.full((n, 3, 4), float("nan"), device=DEV), torch.full((n, 6), float("nan"), device=DEV)
+    assert lib.ls2fm_se3_exp_fwd(_lib.ptr(d_se3), n, _lib.ptr(poses), _lib.stream_ptr()) == 0
+    assert lib.ls2fm_se3_exp_bwd(_lib.ptr(d_se3), _lib.ptr(d_up), n, _lib.ptr(grad), _lib.stream_ptr()) == 0
+    torch.cuda.synchronize()
+    poses, grad = poses.double().cpu().numpy(), grad.double().cpu().numpy()
+    assert np.isfinite(poses).all() and np.isfinite(grad).all()
+    bad = []
+    for k, theta in enumerate(SE3_THETAS):
+        rows = np.nonzero(which == k)[0]
+        if rows.size == 0:
+            continue
+        name = f"se3 exp n={n} theta={theta:g} ({rows.size} rows)"
+        bad.append(BR.within_f32_gap(name, "pose", poses[rows], ref[torch.float64][0][rows], ref[torch.float32][0][rows]))
+        bad.append(BR.within_f32_gap(name, "d_se3", grad[rows], ref[torch.float64][1][rows], ref[torch.float32][1][rows]))
+        if theta == 0.0:
+            assert np.array_equal(poses[rows][:, :, :3], np.broadcast_to(np.eye(3), (rows.size, 3, 3)))      # R = I exactly
+            assert np.array_equal(poses[rows][:, :, 3], se3[rows, 3:].astype(np.float64))                    # t = u exactly
+    assert not any(bad), [b for b in bad if b]

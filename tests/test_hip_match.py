@@ -210,6 +210,212 @@ def test_e_two_view_tables():
             assert own.shape == other.shape == (int(mask.sum()), 2) and mask.sum() >= 30
 
 
+# ------------------------------------------------------------------------------------------------ plans at every chunk size
+# Every call above is small by the planning rule's measure and runs at 1024-column chunks (at most 32 tiles, one key field value
+# in sixteen).  The cases below hold the call at a chosen chunk size by listing a pair several times (the rule counts work
+# items over the whole call); tests/match_restate.plan mirrors the rule, tests/test_match_host.py holds the library to the mirror,
+# and every case asserts its chunk through the mirror AND the library's own byte count before the device is called.
+def _plan(what, counts, pairs, want_chunk):
+    import ctypes
+    from ls2fm import _lib
+    pl = MR.plan(counts, pairs)
+    assert pl["chunk_cols"] == want_chunk, f"{what}: planned at {pl['chunk_cols']}, meant {want_chunk}"
+    start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    prs = np.ascontiguousarray(pairs, dtype=np.int32)
+    size = _lib.load().ls2fm_match_descriptors_workspace_bytes(start.ctypes.data_as(ctypes.c_void_p), len(counts),
+                                                               prs.ctypes.data_as(ctypes.c_void_p), len(prs))
+    assert size == pl["bytes"], f"{what}: the library's workspace is {size} bytes, the mirror's {pl['bytes']}"
+    print(f"[match plan] {what}: chunk {pl['chunk_cols']} columns, {pl['max_tiles']} tiles per chunk, {pl['max_chunks']} chunk(s), "
+          f"{pl['n_items']} items over {len(prs)} listed pairs")
+    return pl
+
+
+def _same_bits(m, s, p, q, what):
+    assert torch.equal(m[p], m[q]) and all(torch.equal(s[p][k], s[q][k]) for k in s[p]), f"{what}: listed pair {q} differs from pair {p}"
+
+
+def _check_repeated(da, db, ref, chunk, what):
+    """the pair listed as often as the plan needs for `chunk`: the first against the restatement on every row of both
+    directions (raw integers, matches), every repeat against the first bit for bit; then the proposals of both directions
+    (cross_check = 0 over the pair and its transpose, listed as often)"""
+    from ls2fm.match import match_descriptors
+    n_a, n_b = da.shape[0], db.shape[0]
+    r = MR.repeats_for(n_a, n_b, chunk)
+    _plan(what, [n_a, n_b], [[0, 1]] * r, chunk)
+    images = [torch.from_numpy(da).cuda(), torch.from_numpy(db).cuda()]
+    m, s = match_descriptors(images, [[0, 1]] * r, return_scores=True)
+    _check_pair(m[0], s[0], ref, what)
+    for q in range(1, r):
+        _same_bits(m, s, 0, q, what)
+    del m, s
+    both = ([[0, 1], [1, 0]] * ((r + 1) // 2))
+    _plan(what + ", proposals", [n_a, n_b], both, chunk)
+    one_way = match_descriptors(images, both, cross_check=False)
+    for q, (key, other) in enumerate((("proposal_ab", "ab"), ("proposal_ba", "ba"))):
+        i = np.nonzero(ref[key] >= 0)[0]
+        want = np.stack([i, ref[key][i]], axis=1).reshape(-1, 2)
+        assert np.array_equal(one_way[q].cpu().numpy(), want), f"{what}: proposals {other}"
+        for k in range(q + 2, len(both), 2):
+            assert torch.equal(one_way[k], one_way[q]), f"{what}: proposals {other}, listed pair {k}"
+
+
+# (n_a, n_b, chunk): a -> b sweeps n_b columns, b -> a sweeps n_a
+WIDE_CASES = [
+    (16384, 16383, 16384),     # one chunk of 512 tiles each way: tile ids 0..511, the last tile of a -> b one column short
+    (16384, 16347, 16384),     # 511 tiles a -> b: an ODD count at the top of the field (the trip's second fold is all padding)
+    (16385, 32768, 16384),     # two chunks each way: 512 + 512 tiles, and 512 tiles + one single column; the finalize merge
+    (32768, 32768, 16384),     # the ABI limit on both sides
+    (8292, 9001, 8192),        # two chunks, ragged last (100 / 809 columns)
+    (4196, 9000, 4096),        # two and three chunks, ragged last
+    (2148, 5000, 2048),        # two and three chunks, ragged last
+]
+
+
+@pytest.mark.parametrize("n_a,n_b,chunk", WIDE_CASES)
+def test_g_wide_chunks_equal_the_blocked_restatement(n_a, n_b, chunk):
+    """Equality on EVERY row of both directions, the 32768 x 32768 pair included: the blocked restatement takes about 10 s for
+    it on 16 CPUs.  Host peak: about 0.5 GB (1024 x 32768 float32 blocks and numpy's temporaries; the descriptors are 4 MB an image)."""
+    da, db, ref = MR.seeded_pair(n_a, n_b, seed=900 + n_a % 1000 + n_b % 1000, restate=MR.match_pair_blocked)
+    assert ref["margin"] >= MR.MIN_MARGIN and max(da.max(), db.max()) == 255
+    print(f"[match] {n_a} x {n_b}: {len(ref['matches'])} matches, margin {ref['margin']:.3e} rad")
+    _check_repeated(da, db, ref, chunk, f"{n_a} x {n_b}")
+
+
+def _many_images(n_images, n, n_sampled, seed):
+    """images that share a pool of descriptors under noise (as _six_images); the pairs sampled for the restatement meet the margin"""
+    pairs = [(a, b) for a in range(n_images) for b in range(a + 1, n_images)]
+    for attempt in range(20):
+        rng = np.random.default_rng(seed + 1000 * attempt)
+        base = MR.sift_like(rng, n)
+        images = []
+        for _ in range(n_images):
+            take = rng.permutation(n)[: n // 2]
+            noisy = base[take] * rng.uniform(0.5, 1.0, size=(len(take), 128))
+            noisy /= np.maximum(np.linalg.norm(noisy, axis=1, keepdims=True), 1e-12)
+            d = np.concatenate([noisy, MR.sift_like(rng, n - len(take))])
+            images.append(MR.to_bytes(d[rng.permutation(n)]))
+        sampled = sorted(int(p) for p in rng.choice(len(pairs), size=n_sampled, replace=False))
+        refs = {p: MR.match_pair_blocked(images[pairs[p][0]], images[pairs[p][1]]) for p in sampled}
+        if min(r["margin"] for r in refs.values()) >= MR.MIN_MARGIN:
+            return images, pairs, refs
+    raise AssertionError("no seed met the margin condition")
+
+
+def test_g_many_views_of_8192_in_one_call():
+    """the README's shape in small: 33 distinct images of 8192 descriptors, all 528 pairs in ONE call and no pair listed twice
+    (135168 items: chunk 16384, 256 tiles).  Six pairs drawn by the fixture's seed against the restatement on every row; all
+    528 against a second run bit for bit.  Host peak: 33 x 1 MB descriptors, 8192 x 8192 float32 blocks (0.6 GB with temporaries)."""
+    from ls2fm.match import match_descriptors
+    images, pairs, refs = _many_images(33, 8192, 6, seed=61)
+    _plan("33 views x 8192", [8192] * 33, pairs, 16384)
+    dev = [torch.from_numpy(d).cuda() for d in images]
+    m1, s1 = match_descriptors(dev, None, return_scores=True)
+    m2, s2 = match_descriptors(dev, None, return_scores=True)
+    assert len(m1) == 528
+    for p, ref in refs.items():
+        _check_pair(m1[p], s1[p], ref, f"pair {pairs[p]} of 33 views")
+        assert len(ref["matches"]) > 1000
+    assert torch.equal(torch.cat(m1), torch.cat(m2)) and [len(x) for x in m1] == [len(x) for x in m2]
+    for k in s1[0]:
+        assert torch.equal(torch.cat([s[k] for s in s1]), torch.cat([s[k] for s in s2])), k
+
+
+# ----------------------------------------------------------------------------------------- directed placements at high tile ids
+HIGH_COLUMNS = (0, 31, 32, 1023, 1024, 8191, 8192, 16351, 16352, 16383)
+
+
+def _queries_and_columns(n_cols, seed, plant, need_margin=True):
+    """a: 70 sift-like query rows (two row blocks, the second ragged); b: n_cols sift-like columns, changed by plant(a, b)"""
+    for attempt in range(20):
+        rng = np.random.default_rng(seed + 1000 * attempt)
+        a, b = MR.to_bytes(MR.sift_like(rng, 70)), MR.to_bytes(MR.sift_like(rng, n_cols))
+        plant(a, b)
+        ref = MR.match_pair_blocked(a, b)
+        if not need_margin or ref["margin"] >= MR.MIN_MARGIN:
+            return a, b, ref
+    raise AssertionError("no seed met the margin condition")
+
+
+def test_h_unique_best_column_in_high_tiles():
+    """row r of a has its only close descriptor at column HIGH_COLUMNS[r] of a 16384-column image (tiles 0, 1, 31, 32, 255, 256,
+    510 and 511, first and last lane of a tile): best_j must be that column"""
+    def plant(a, b):
+        for r, c in enumerate(HIGH_COLUMNS):
+            b[c] = a[r]
+    a, b, ref = _queries_and_columns(16384, 71, plant)
+    rows = np.arange(len(HIGH_COLUMNS))
+    assert np.array_equal(ref["best_j_ab"][rows], HIGH_COLUMNS) and np.all(ref["best_ab"][rows] > ref["second_ab"][rows])
+    assert np.array_equal(ref["proposal_ab"][rows], HIGH_COLUMNS) and np.array_equal(ref["best_j_ba"][list(HIGH_COLUMNS)], rows)
+    _check_repeated(a, b, ref, 16384, "unique best at high tiles")
+
+
+def test_h_equal_dots_in_distant_tiles_of_one_chunk():
+    """two and three copies of a row's best descriptor in different tiles of ONE 16384-column chunk: the lowest column, second ==
+    best, no proposal; and rows whose every dot is 0 (best_j -1), one of them also a column of the other direction"""
+    def plant(a, b):
+        b[[40, 9000, 16383]] = a[0]
+        b[[9001, 16352]] = a[1]
+        b[[16320, 16352 + 31 - 1]] = a[2]             # tiles 510 and 511
+        a[5] = 0
+        a[69] = 0                                     # the last row of the ragged row block
+        b[16381] = 0
+    a, b, ref = _queries_and_columns(16384, 72, plant)
+    assert ref["best_j_ab"][:3].tolist() == [40, 9001, 16320] and np.array_equal(ref["best_ab"][:3], ref["second_ab"][:3])
+    assert np.all(ref["proposal_ab"][:3] == -1) and np.all(ref["best_ab"][:3] > 200000)
+    assert ref["best_j_ab"][5] == -1 and ref["best_j_ab"][69] == -1 and ref["best_ab"][69] == 0 and ref["best_j_ba"][16381] == -1
+    _check_repeated(a, b, ref, 16384, "equal dots in one chunk")
+
+
+def test_h_equal_dots_across_the_chunk_boundary():
+    """16400 columns at chunk 16384: copies on both sides of the boundary (16383, 16384), both in the short second chunk, and far
+    apart in different chunks -- the lowest column through match_finalize_kernel's merge; a unique best in the last column"""
+    def plant(a, b):
+        b[[16383, 16384]] = a[0]
+        b[[16384 + 1, 16399 - 1]] = a[1]
+        b[[5, 16390]] = a[2]
+        b[16399] = a[3]
+    a, b, ref = _queries_and_columns(16400, 73, plant)
+    assert ref["best_j_ab"][:4].tolist() == [16383, 16385, 5, 16399] and np.array_equal(ref["best_ab"][:3], ref["second_ab"][:3])
+    assert np.all(ref["proposal_ab"][:3] == -1) and ref["proposal_ab"][3] == 16399
+    _check_repeated(a, b, ref, 16384, "equal dots across chunks")
+
+
+def test_h_saturated_pair_in_tile_511():
+    """all bytes 255 in a row of a and in column 16380 of b (dot 128 * 255^2, the largest key the sweep can form, beside tile id
+    511 = field value 0), and in column 3 (tile 0 = field value 511): the raw integers only -- a saturated descriptor is far above
+    length 512, so every row's angle is 0 and no decision is compared (as test_a_all_bytes_255)"""
+    from ls2fm.match import match_descriptors
+
+    def plant(a, b):
+        a[7] = 255
+        a[64] = 255
+        b[16380] = 255
+        b[3] = 255
+    a, b, ref = _queries_and_columns(16384, 74, plant, need_margin=False)
+    top = 128 * 255 * 255
+    assert ref["best_ab"][7] == top and ref["best_j_ab"][7] == 3 and ref["second_ab"][7] == top and ref["best_j_ba"][16380] == 7
+    assert ref["best_j_ab"][0] == 3 and ref["second_ab"][0] == ref["best_ab"][0]      # ordinary rows: the two saturated columns tie
+    r = MR.repeats_for(70, 16384, 16384)
+    _plan("saturated pair", [70, 16384], [[0, 1]] * r, 16384)
+    _, scores = match_descriptors([a, b], [[0, 1]] * r, return_scores=True)
+    for names in DIRS:
+        for k in names:
+            got = scores[0][k].cpu().numpy().astype(np.int64)
+            assert np.array_equal(got, ref[k]), f"{k}: first difference at row {np.nonzero(got != ref[k])[0][:5]}"
+            assert all(torch.equal(scores[q][k], scores[0][k]) for q in range(1, r)), k
+
+
+def test_h_every_chunk_size_is_reached_by_this_file():
+    """the plans of this file's calls, through the mirror: the small cases at 1024, the wide ones at each of the other four"""
+    reached = {MR.plan([n_a, n_b], [[0, 1]])["chunk_cols"] for n_a, n_b in [(1, 1), (17, 300), (2000, 1800), (8192, 8191)]}
+    assert reached == {1024}
+    for n_a, n_b, chunk in WIDE_CASES:
+        reached.add(MR.plan([n_a, n_b], [[0, 1]] * MR.repeats_for(n_a, n_b, chunk))["chunk_cols"])
+    reached.add(MR.plan([8192] * 33, [(a, b) for a in range(33) for b in range(a + 1, 33)])["chunk_cols"])
+    print(f"[match plan] chunk sizes reached: {sorted(reached)}")
+    assert reached == set(MR.CHUNKS)
+
+
 def test_f_smoke_unchanged_and_self_contained():
     import inspect
 

@@ -228,3 +228,77 @@ def test_seeded_fixture_meets_margin_and_truth():
     assert ref["margin"] >= MR.MIN_MARGIN
     assert max(da.max(), db.max()) == 255
     assert 100 < len(ref["matches"]) <= 360 and np.all(np.diff(ref["matches"][:, 0]) > 0)
+
+
+# ------------------------------------------------------------------------------------------- the planning rule and its mirror
+def _exhaustive(n):
+    return [[a, b] for a in range(n) for b in range(a + 1, n)]
+
+
+# (images, pairs, the chunk the rule gives by hand).  Items of a pair at chunk c: ceil(n_a / 64) ceil(n_b / c) + ceil(n_b / 64) ceil(n_a / c)
+PLAN_TABLE = [
+    ([100, 100, 300], _exhaustive(3), 1024),                    # tiny: halves all the way down
+    ([8192, 8191], [[0, 1]], 1024),                             # 256 items at 16384, 2048 at 1024: the suite's largest pair so far
+    ([16384, 16384], [[0, 1]] * 16, 16384),                     # 16 x 512 = 8192 items: exactly the target, stays
+    ([16384, 16384, 16320], [[0, 1]] * 15 + [[0, 2]], 8192),    # 15 x 512 + 511 = 8191: one item short, halves once (15 x 1024 + 1022)
+    ([16384, 16384, 64], [[0, 1]] * 16 + [[2, 2]], 16384),      # 8194: one pair of two items above
+    ([16385, 32768], [[0, 1]] * 6, 16384),                      # 6 x (257 x 2 + 512 x 2) = 9228
+    ([16385, 32768], [[0, 1]] * 5, 8192),                       # 7690 -> at 8192: 5 x (257 x 4 + 512 x 3) = 12820
+    ([8292, 8292], [[0, 1]] * 16, 8192),                        # 16 x 260 = 4160 -> 16 x 520 = 8320
+    ([8292, 8292], [[0, 1]] * 15, 4096),                        # 15 x 520 = 7800: one repeat short -> 15 x 780
+    ([4196, 4196], [[0, 1]] * 32, 4096),                        # 32 x 132 = 4224 -> 32 x 264 = 8448
+    ([4196, 4196], [[0, 1]] * 31, 2048),                        # 31 x 264 = 8184: eight items short -> 31 x 396
+    ([2148, 2148], [[0, 1]] * 61, 2048),                        # 61 x 68 = 4148 -> 61 x 136 = 8296
+    ([2148, 2148], [[0, 1]] * 60, 1024),                        # 60 x 136 = 8160 -> 60 x 204 (and 1024 is the floor)
+    ([8192] * 33, _exhaustive(33), 16384),                      # the README's shape in small: 528 x 256 items
+    ([0, 5000, 0], _exhaustive(3), 1024),                       # empty images: no items at any chunk
+]
+
+
+def _telling_neighbours(counts, pairs, want):
+    """the neighbouring chunk sizes at which some job of the call has another number of chunks, so another byte count"""
+    widest = max([0] + [max(counts[a], counts[b]) for a, b in pairs if counts[a] and counts[b]])
+    return [c for c in (want // 2, want * 2) if c in MR.CHUNKS and min(c, want) < widest]
+
+
+@pytest.mark.parametrize("row", range(len(PLAN_TABLE)))
+def test_plan_mirror_equals_the_library_workspace_query(row):
+    """ls2fm_match_descriptors_workspace_bytes against tests/match_restate.plan.  The partial array holds one entry per (row,
+    chunk), so where an image is wider than the next smaller chunk the byte count differs between chunk sizes (asserted where
+    it applies): equal bytes then show the library chose the chunk the mirror chose, and the table pins the mirror by hand."""
+    counts, pairs, want = PLAN_TABLE[row]
+    got = MR.plan(counts, pairs)
+    assert got["chunk_cols"] == want, got
+    start, c_start = _i32(np.concatenate([[0], np.cumsum(counts)]))
+    prs, c_pairs = _i32(pairs)
+    size = _lib().ls2fm_match_descriptors_workspace_bytes(c_start, len(counts), c_pairs, len(pairs))
+    assert size == got["bytes"], (size, got)
+    for c in _telling_neighbours(counts, pairs, want):
+        assert MR.plan(counts, pairs, force_chunk=c)["bytes"] != size, c
+
+
+def test_plan_table_lands_on_every_chunk_size_and_both_sides_of_the_target():
+    chunks = {MR.plan(c, p)["chunk_cols"] for c, p, _ in PLAN_TABLE}
+    assert chunks == set(MR.CHUNKS)
+    for chunk in MR.CHUNKS:                                      # and at each, a row whose byte count tells it from both neighbours
+        assert any(w == chunk and len(_telling_neighbours(c, p, w)) == (1 if chunk in (1024, 16384) else 2) for c, p, w in PLAN_TABLE), chunk
+    items = [MR.plan(c, p, force_chunk=16384)["n_items"] for c, p, _ in PLAN_TABLE]
+    assert {8191, 8192, 8194} <= set(items)
+    assert MR.repeats_for(16384, 16383, 16384) == 16 and MR.repeats_for(2148, 2148, 2048) == 61
+
+
+@pytest.mark.parametrize("n_a,n_b,seed,block", [(400, 360, 11, 64), (200, 700, 7, 1024), (17, 300, 117, 7), (1, 1, 101, 1024), (2000, 1800, 2100, 333)])
+def test_blocked_restatement_equals_the_full_one(n_a, n_b, seed, block):
+    da, db, ref = MR.seeded_pair(n_a, n_b, seed=seed, shared=0.5 if n_a > 1 else 1.0)
+    db = db.copy()
+    if n_b > 500:                                                # the fixture of test_c_ties: a tied maximum in distant blocks
+        db[[5, 31, 32, 33, 100, 401]] = db[int(ref["matches"][ref["matches"][:, 1] > 401][0, 1])]
+        ref = MR.match_pair(da, db)
+    got = MR.match_pair_blocked(da, db, block=block)
+    assert set(got) == set(ref) and got["margin"] == ref["margin"]
+    for k in ref:
+        if k != "margin":
+            assert got[k].dtype == ref[k].dtype and np.array_equal(got[k], ref[k]), k
+    empty = MR.match_pair_blocked(da, np.zeros((0, 128), dtype=np.uint8))
+    full = MR.match_pair(da, np.zeros((0, 128), dtype=np.uint8))
+    assert all(np.array_equal(empty[k], full[k]) for k in full if k != "margin") and len(empty["matches"]) == 0
