@@ -685,7 +685,8 @@ int ls2fm_match_term_bwd(const float* center, const float* ray, const float* uv_
  * z <= 0 or a non-finite entry is dropped; collinear or coincident points (|d01 x d02|^2 <= 1e-20 |d01|^2 |d02|^2) give 0
  * solutions, never NaN.
  *
- * ls2fm_absolute_pose: LO-RANSAC per view.
+ * ls2fm_absolute_pose: LO-RANSAC per view (samples, scoring, selection and rounds are csrc/ransac.h's, which the relative pose
+ * shares).
  *   samples   trial t (0, 1, 2, ... per view) draws indices from key = splitmix64(seed ^ splitmix64(t)): draw k is
  *             ((splitmix64(key + k) >> 32) * n) >> 32 over the view's n correspondences; the sample is the first three distinct
  *             values among draws k = 0 .. 63 (none: the trial has no pose).  splitmix64(x): z = x + 0x9E3779B97F4A7C15;
@@ -772,7 +773,7 @@ int ls2fm_pose_refine(const double* uv, const double* xyz, const int32_t* view_s
  *               largest |entry| (the first of equals, row-major) positive.  Non-finite solutions are dropped.
  *   Degenerate samples (coincident points, a rank-deficient system) give 0 solutions, never NaN.
  *
- * ls2fm_relative_pose: LO-RANSAC per pair.
+ * ls2fm_relative_pose: LO-RANSAC per pair (the rounds of csrc/ransac.h, as ls2fm_absolute_pose).
  *   samples   ls2fm_absolute_pose's SplitMix64 stream keyed by (seed, trial); the sample is the first FIVE distinct draws among
  *             k = 0 .. 63 (none: the trial has no model).
  *   hypotheses ls2fm_five_point of the sample; slot s = the solution's place (0..9).

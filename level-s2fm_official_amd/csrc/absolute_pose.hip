@@ -3,60 +3,25 @@
 // absolute_pose_estimation + pose_refinement), all geometry in fp64.  include/ls2fm.h states the rules; tests/pose_restate.py
 // repeats them step by step in numpy.  Correspondences are SORTED BY VIEW (view v owns [view_start[v], view_start[v + 1])).
 //
-//   per round (host loop; a view stops once its trial count reaches the stopping rule's N):
-//     pose_hyp_kernel     one thread per (view, trial): three distinct indices from the SplitMix64 stream, P3P, <= 4 poses
-//     pose_score_kernel   (1024-correspondence tile of some view, 16-trial block): inlier counts of the block's 64 poses over the
-//                         tile, wave ballots + integer atomics (exact, order-independent).  The tiles of all views are numbered
-//                         in one flat range (per-view tile offsets from the host), so a view of n gets ceil(n / 1024) x 64
-//                         workgroups -- 128 for n = 2000, 65 536 for n = 2^20 -- whatever the sizes of the other views
-//     pose_select_kernel  one workgroup per view: the best (count, lowest trial * 4 + slot) as a 64-bit max, the stopping rule
-//   then pose_lo_kernel (local optimisation, the final mask) and pose_lm_kernel (refinement), one workgroup per view with
-//   fixed-order reductions: every bit of the result is a function of the view's own data, seed and options.
-#include "ls2fm_device.h"
+// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model AbsModel below with this
+// file's pose_hyp_kernel: one thread per (view, trial), P3P on three distinct correspondences, <= 4 poses.  Then pose_lo_kernel
+// (local optimisation, the final mask) and pose_lm_kernel (refinement), one workgroup per view with fixed-order reductions: every
+// bit of the result is a function of the view's own data, seed and options.
+#include "ransac.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 namespace {
 
-constexpr int kRound = LS2FM_POSE_ROUND;      // trials per view per round (1024)
+using namespace ransac;
+
 constexpr int kHypThreads = 256;
-constexpr int kScoreThreads = 256;
-constexpr int kScorePts = 4;                   // correspondences per thread of a scoring tile
-constexpr int kScoreTile = kScoreThreads * kScorePts;
-constexpr int kScoreTrials = 16;               // trials per scoring workgroup (64 poses in LDS)
-constexpr int kViewThreads = 256;              // LO / LM / selection workgroups
+constexpr int kViewThreads = 256;              // LO / LM workgroups
 constexpr int kLoIters = 10;
-constexpr int kMaxDraws = 64;
 constexpr double kGradTol = 1e-10;
 constexpr double kStepTol = 1e-12;
 
-static_assert(kRound % kScoreTrials == 0 && kRound % kHypThreads == 0, "round shape");
-
-// ----------------------------------------------------------------------------------------------------------- sample stream
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int64_t draw_index(uint64_t key, int k, int64_t n) {
-    return (int64_t)(((splitmix64(key + (uint64_t)k) >> 32) * (uint64_t)n) >> 32);
-}
-
-// -------------------------------------------------------------------------------------------------------------- stopping
-__host__ __device__ inline int64_t num_trials(double eps, double confidence, int64_t min_t, int64_t max_t) {
-    if (eps <= 0.0) return max_t;
-    if (eps >= 1.0) return min_t;
-    const double den = log(1.0 - eps * eps * eps);
-    if (den >= 0.0) return max_t;
-    const double n = ceil(log(1.0 - confidence) / den);
-    if (n >= (double)max_t) return min_t > max_t ? min_t : max_t;
-    const int64_t ni = (int64_t)n;
-    return ni < min_t ? min_t : ni;
-}
+static_assert(kRound % kHypThreads == 0, "round shape");
 
 // ------------------------------------------------------------------------------------------------------------------- P3P
 struct V3 { double x, y, z; };
@@ -307,45 +272,22 @@ p3p_kernel(const double* __restrict__ bear, const double* __restrict__ pts, int6
 }
 
 // ---------------------------------------------------------------------------------------------------------------- RANSAC
-struct Ws {                     // workspace layout (ls2fm_absolute_pose_workspace_bytes)
-    double* hyp;                // [V][kRound][4][12]
-    int32_t* valid;             // [V][kRound]   bit s: slot s holds a pose
-    int32_t* counts;            // [V][kRound][4]
-    unsigned long long* best_key;   // [V]
-    double* best_pose;          // [V][12]
-    int32_t* trials;            // [V]
-    int32_t* active;            // [V]
-    int32_t* n_active;          // [1]
-    int32_t* tile_off;          // [V + 1]   first scoring tile of view v (ceil(n_v / kScoreTile) tiles each)
+struct AbsModel {               // ransac.h's model of this file: P3P poses [R | t] scored by the squared pixel error
+    static constexpr int kSample = 3, kMaxSol = 4, kHypWords = 12, kMinGroup = 3;
+    struct Input { const double* uv; const double* xyz; const double* intr; double thr2; };
+    struct Ctx { double fx, fy, cx, cy, thr2; };
+    struct Point { double x, y, z, u, v; };
+    static __device__ __forceinline__ Ctx context(const Input& in, int v) {
+        return {in.intr[4 * v], in.intr[4 * v + 1], in.intr[4 * v + 2], in.intr[4 * v + 3], in.thr2};
+    }
+    static __device__ __forceinline__ Point load(const Input& in, const Ctx&, int64_t i) {
+        return {in.xyz[3 * i], in.xyz[3 * i + 1], in.xyz[3 * i + 2], in.uv[2 * i], in.uv[2 * i + 1]};
+    }
+    static __device__ __forceinline__ bool inlier(const double* P, const Point& p, const Ctx& c) {
+        double Z;
+        return project_err2(P, p.x, p.y, p.z, p.u, p.v, c.fx, c.fy, c.cx, c.cy, Z) < c.thr2 && Z > 0.0;
+    }
 };
-
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-__host__ __device__ inline size_t ws_layout(int32_t V, char* base, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* hyp = take((size_t)V * kRound * 48 * sizeof(double));
-    char* valid = take((size_t)V * kRound * sizeof(int32_t));
-    char* counts = take((size_t)V * kRound * 4 * sizeof(int32_t));
-    char* bk = take((size_t)V * sizeof(unsigned long long));
-    char* bp = take((size_t)V * 12 * sizeof(double));
-    char* tr = take((size_t)V * sizeof(int32_t));
-    char* ac = take((size_t)V * sizeof(int32_t));
-    char* na = take(sizeof(int32_t));
-    char* to = take(((size_t)V + 1) * sizeof(int32_t));
-    if (w) *w = {(double*)hyp, (int32_t*)valid, (int32_t*)counts, (unsigned long long*)bk, (double*)bp, (int32_t*)tr, (int32_t*)ac,
-                 (int32_t*)na, (int32_t*)to};
-    return off;
-}
-
-__global__ void __launch_bounds__(kViewThreads)
-pose_init_kernel(const int32_t* __restrict__ vs, int32_t V, Ws w) {
-    const int v = blockIdx.x * kViewThreads + threadIdx.x;
-    if (v >= V) return;
-    w.best_key[v] = 0ull;
-    w.trials[v] = 0;
-    w.active[v] = (vs[v + 1] - vs[v]) >= 3 ? 1 : 0;
-}
 
 __global__ void __launch_bounds__(kHypThreads)
 pose_hyp_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
@@ -358,23 +300,16 @@ pose_hyp_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, c
     cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
     const int64_t s0 = vs[v], n = vs[v + 1] - s0;
     const uint64_t t = (uint64_t)(w.trials[v] + tl);
-    const uint64_t key = splitmix64(seed ^ splitmix64(t));
-    int64_t i0 = -1, i1 = -1, i2 = -1;
-    for (int k = 0; k < kMaxDraws && i2 < 0; ++k) {
-        const int64_t d = draw_index(key, k, n);
-        if (i0 < 0) i0 = d;
-        else if (i1 < 0) { if (d != i0) i1 = d; }
-        else if (d != i0 && d != i1) i2 = d;
-    }
+    int64_t id[3];
     int mask = 0;
-    if (i2 >= 0) {
+    if (sample_distinct(trial_key(seed, t), n, id)) {
         const double* __restrict__ K = intr + 4 * v;
-        const int64_t id[3] = {s0 + i0, s0 + i1, s0 + i2};
         V3 y[3], x[3];
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            y[s] = bearing(uv[2 * id[s]], uv[2 * id[s] + 1], K);
-            x[s] = {xyz[3 * id[s]], xyz[3 * id[s] + 1], xyz[3 * id[s] + 2]};
+            const int64_t i = s0 + id[s];
+            y[s] = bearing(uv[2 * i], uv[2 * i + 1], K);
+            x[s] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
         }
         double* __restrict__ out = w.hyp + 48 * slot;
         p3p_solve(y, x, [&](int s, const double* P) {
@@ -386,127 +321,8 @@ pose_hyp_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, c
     w.valid[slot] = mask;
 }
 
-__global__ void __launch_bounds__(kScoreThreads)
-pose_score_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
-                  const double* __restrict__ intr, int32_t V, double thr2, Ws w) {
-    // the view of this tile: the last v with tile_off[v] <= blockIdx.x (views without a tile share its offset)
-    const int32_t bx = (int32_t)blockIdx.x;
-    int lo = 0, hi = V;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (w.tile_off[mid] <= bx) lo = mid; else hi = mid;
-    }
-    const int v = lo;
-    if (!w.active[v]) return;
-    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
-    const int64_t base = (int64_t)(bx - w.tile_off[v]) * kScoreTile;
-    if (base >= n) return;
-    __shared__ double s_h[4 * kScoreTrials][12];
-    __shared__ int s_valid[kScoreTrials];
-    __shared__ int s_cnt[4 * kScoreTrials];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t slot0 = (int64_t)v * kRound + (int64_t)blockIdx.y * kScoreTrials;
-    for (int q = tid; q < 4 * kScoreTrials * 12; q += kScoreThreads) s_h[q / 12][q % 12] = w.hyp[48 * slot0 + q];
-    if (tid < kScoreTrials) s_valid[tid] = w.valid[slot0 + tid];
-    if (tid < 4 * kScoreTrials) s_cnt[tid] = 0;
-    const double fx = intr[4 * v], fy = intr[4 * v + 1], cx = intr[4 * v + 2], cy = intr[4 * v + 3];
-    double px[kScorePts], py[kScorePts], pz[kScorePts], pu[kScorePts], pv[kScorePts];
-    bool live[kScorePts];
-#pragma unroll
-    for (int k = 0; k < kScorePts; ++k) {
-        const int64_t j = base + tid + (int64_t)k * kScoreThreads;
-        live[k] = j < n;
-        const int64_t i = s0 + (live[k] ? j : 0);
-        px[k] = xyz[3 * i]; py[k] = xyz[3 * i + 1]; pz[k] = xyz[3 * i + 2];
-        pu[k] = uv[2 * i]; pv[k] = uv[2 * i + 1];
-    }
-    __syncthreads();
-    for (int h = 0; h < 4 * kScoreTrials; ++h) {
-        if (!((s_valid[h >> 2] >> (h & 3)) & 1)) continue;
-        const double* P = s_h[h];
-        int c = 0;
-#pragma unroll
-        for (int k = 0; k < kScorePts; ++k) {
-            double Z;
-            const double e2 = project_err2(P, px[k], py[k], pz[k], pu[k], pv[k], fx, fy, cx, cy, Z);
-            c += __popcll(__ballot(live[k] && Z > 0.0 && e2 < thr2));
-        }
-        if (lane == 0 && c) atomicAdd(&s_cnt[h], c);
-    }
-    __syncthreads();
-    if (tid < 4 * kScoreTrials && s_cnt[tid]) atomicAdd(&w.counts[4 * slot0 + tid], s_cnt[tid]);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(k, o, 64);
-        k = t > k ? t : k;
-    }
-    return k;
-}
-
-__global__ void __launch_bounds__(kViewThreads)
-pose_select_kernel(const int32_t* __restrict__ vs, double confidence, int64_t min_trials, int64_t max_trials, Ws w) {
-    const int v = blockIdx.x;
-    if (!w.active[v]) return;
-    const int tid = threadIdx.x;
-    __shared__ unsigned long long s_k[kViewThreads / 64];
-    const int32_t t0 = w.trials[v];
-    unsigned long long best = 0ull;
-    for (int c = tid; c < 4 * kRound; c += kViewThreads) {
-        const int64_t slot = (int64_t)v * kRound + (c >> 2);
-        const int cnt = w.counts[4 * slot + (c & 3)];
-        if (cnt > 0 && ((w.valid[slot] >> (c & 3)) & 1)) {
-            const uint32_t idx = (uint32_t)(t0 + (c >> 2)) * 4u + (uint32_t)(c & 3);
-            const unsigned long long key = ((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
-            best = key > best ? key : best;
-        }
-    }
-    best = wave_max_u64(best);
-    if ((tid & 63) == 0) s_k[tid >> 6] = best;
-    __syncthreads();
-    if (tid != 0) return;
-    for (int q = 0; q < kViewThreads / 64; ++q) best = s_k[q] > best ? s_k[q] : best;
-    if (best > w.best_key[v]) {
-        w.best_key[v] = best;
-        const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
-        const int64_t slot = (int64_t)v * kRound + (int64_t)(idx / 4u - (uint32_t)t0);
-        for (int q = 0; q < 12; ++q) w.best_pose[12 * v + q] = w.hyp[48 * slot + 12 * (idx & 3u) + q];
-    }
-    const int32_t done = t0 + kRound;
-    w.trials[v] = done;
-    const double eps = (double)(w.best_key[v] >> 32) / (double)(vs[v + 1] - vs[v]);
-    const bool on = done < num_trials(eps, confidence, min_trials, max_trials);
-    w.active[v] = on ? 1 : 0;
-    if (on) atomicAdd(w.n_active, 1);
-}
-
 // -------------------------------------------------------------------------------------------------------- least squares
 constexpr int kNe = 21 + 6 + 3;          // upper triangle of H, g, then {F or count, changed, unused}
-
-__device__ __forceinline__ void block_sum(double (&a)[kNe], double* s_red /* [kViewThreads / 64][kNe] */) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < kNe; ++q) {
-        double t = a[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        a[q] = t;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < kNe; ++q) s_red[(tid >> 6) * kNe + q] = a[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kNe; ++q) {
-        double t = s_red[q];
-#pragma unroll
-        for (int wv = 1; wv < kViewThreads / 64; ++wv) t += s_red[wv * kNe + q];
-        a[q] = t;
-    }
-}
 
 // one correspondence's contribution: weight w, residual (du, dv), Jacobian rows through d p / d(w, dt) = [-[p]x | I]
 __device__ __forceinline__ void accumulate(double (&a)[kNe], const double* P, double x, double y, double z, double u, double v,
@@ -634,7 +450,7 @@ __device__ inline void lo_pass(const double* __restrict__ uv, const double* __re
     }
     a[27] = cnt;
     a[28] = chg;
-    block_sum(a, s_red);
+    block_sum<kNe, kViewThreads>(a, s_red);
 }
 
 __global__ void __launch_bounds__(kViewThreads)
@@ -655,7 +471,7 @@ pose_lo_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, co
         return;
     }
 #pragma unroll
-    for (int q = 0; q < 12; ++q) P[q] = w.best_pose[12 * v + q];
+    for (int q = 0; q < 12; ++q) P[q] = w.best[12 * v + q];
     double a[kNe], b[kNe];
     lo_pass(uv, xyz, s0, n, P, P, false, fx, fy, cx, cy, thr2, a, s_red);
     for (int it = 0; it < kLoIters; ++it) {
@@ -685,7 +501,7 @@ pose_lo_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, co
         const int32_t cnt = (int32_t)a[27];
         num_inliers[v] = cnt;
         trials[v] = w.trials[v];
-        best_trial[v] = (int32_t)((0xFFFFFFFFu - (uint32_t)(bk & 0xFFFFFFFFull)) / 4u);
+        best_trial[v] = best_trial_of<AbsModel>(bk);
         success[v] = cnt >= 4 ? 1 : 0;
     }
 }
@@ -700,7 +516,7 @@ __device__ inline void lm_pass(const double* __restrict__ uv, const double* __re
         const int64_t i = s0 + j;
         if (mask[i]) accumulate(a, P, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], uv[2 * i], uv[2 * i + 1], fx, fy, cx, cy, c2, true);
     }
-    block_sum(a, s_red);
+    block_sum<kNe, kViewThreads>(a, s_red);
 }
 
 // mask: per correspondence; ok (NULL = every view): refine view v only when ok[v] != 0 (else copy)
@@ -718,11 +534,7 @@ pose_lm_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, co
     int cnt = 0;
     for (int64_t j = tid; j < n; j += kViewThreads) cnt += mask[s0 + j] ? 1 : 0;
     __shared__ int s_cnt;
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    atomicAdd(&s_cnt, cnt);
-    __syncthreads();
-    const bool run = s_cnt >= 3 && (ok == nullptr || ok[v] != 0);
+    const bool run = block_count(cnt, &s_cnt) >= 3 && (ok == nullptr || ok[v] != 0);
     double lam = 1e-4;
     for (int it = 0; run && it < max_iters; ++it) {
         double a[kNe], b[kNe];
@@ -763,12 +575,6 @@ pose_lm_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, co
     if (tid < 12) poses_out[12 * v + tid] = P[tid];
 }
 
-bool opts_ok(const ls2fm_pose_ransac_opts* o) {
-    return o && o->max_error_px > 0.0 && std::isfinite(o->max_error_px) && o->confidence > 0.0 && o->confidence < 1.0 &&
-           o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio < 1.0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 &&
-           o->max_num_trials <= LS2FM_POSE_MAX_TRIALS && o->min_num_trials <= o->max_num_trials && (o->refine == 0 || o->refine == 1);
-}
-
 }  // namespace
 
 extern "C" int ls2fm_p3p(const double* bearings, const double* points, int64_t m, double* poses, int32_t* n_solutions, void* stream) {
@@ -782,68 +588,24 @@ extern "C" int ls2fm_p3p(const double* bearings, const double* points, int64_t m
 
 extern "C" int64_t ls2fm_absolute_pose_workspace_bytes(int32_t n_views, int64_t n_corr) {
     if (n_views < 1 || n_views > LS2FM_POSE_MAX_VIEWS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
-    return (int64_t)ws_layout(n_views, nullptr, nullptr);
+    return (int64_t)ws_layout<AbsModel>(n_views, nullptr, nullptr);
 }
 
 extern "C" int ls2fm_absolute_pose(const double* uv, const double* xyz, const int32_t* view_start, int32_t n_views, const double* intr,
                                    const ls2fm_pose_ransac_opts* opts, double* poses, uint8_t* inliers, int32_t* num_inliers,
                                    int32_t* trials, int32_t* best_trial, int32_t* success, void* workspace, void* stream) {
-    LS2FM_CHECK_ARG(n_views >= 1 && n_views <= LS2FM_POSE_MAX_VIEWS && view_start && intr && opts_ok(opts));
+    LS2FM_CHECK_ARG(n_views >= 1 && n_views <= LS2FM_POSE_MAX_VIEWS && view_start && intr && opts_ok(opts) &&
+                    (opts->refine == 0 || opts->refine == 1));
     LS2FM_CHECK_ARG(poses && num_inliers && trials && best_trial && success);
     if (!workspace) return LS2FM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    // the views' extents, on the host: the grid of the scoring pass and the argument checks (the call synchronises)
-    int32_t* h_vs = (int32_t*)malloc(sizeof(int32_t) * ((size_t)n_views + 1));
-    if (!h_vs) return LS2FM_ERR_LAUNCH;
-    if (hipMemcpyAsync(h_vs, view_start, sizeof(int32_t) * ((size_t)n_views + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        free(h_vs);
-        return ls2fm_launch_status();
-    }
-    // per-view scoring tile offsets, reusing the host copy (view_start[v] <= ... fits int32, so do the tile counts)
-    int64_t max_n = 0;
-    bool mono = h_vs[0] >= 0;
-    int32_t tiles = 0;
-    for (int v = 0; v < n_views; ++v) {
-        mono = mono && h_vs[v + 1] >= h_vs[v];
-        const int64_t nv = (int64_t)h_vs[v + 1] - h_vs[v];
-        max_n = std::max<int64_t>(max_n, nv);
-        h_vs[v] = tiles;
-        tiles += mono ? (int32_t)((nv + kScoreTile - 1) / kScoreTile) : 0;
-    }
-    const int64_t total = h_vs[n_views];
-    h_vs[n_views] = tiles;
-    if (!(mono && (total == 0 || (uv && xyz && inliers)))) {
-        free(h_vs);
-        return LS2FM_ERR_INVALID_ARGUMENT;
-    }
-    Ws w;
-    ws_layout(n_views, (char*)workspace, &w);
-    const bool copied = hipMemcpyAsync(w.tile_off, h_vs, sizeof(int32_t) * ((size_t)n_views + 1), hipMemcpyHostToDevice, s) == hipSuccess &&
-                        hipStreamSynchronize(s) == hipSuccess;
-    free(h_vs);
-    if (!copied) return ls2fm_launch_status();
     const double thr2 = opts->max_error_px * opts->max_error_px;
-    // the trial cap, and min_num_trials above it lowered to it (the cap wins, as in COLMAP's RANSAC)
-    const int64_t cap = num_trials(opts->min_inlier_ratio, opts->confidence, 0, opts->max_num_trials);
-    const int64_t min_trials = std::min<int64_t>(opts->min_num_trials, cap);
-    pose_init_kernel<<<(unsigned)((n_views + kViewThreads - 1) / kViewThreads), kViewThreads, 0, s>>>(view_start, n_views, w);
-    int st = ls2fm_launch_status();
+    Ws w;
+    const int st = run_rounds<AbsModel>({uv, xyz, intr, thr2}, view_start, n_views, uv && xyz && inliers, opts, workspace, s, &w,
+                                        [&](const Ws& ws) {
+        pose_hyp_kernel<<<dim3(kRound / kHypThreads, (unsigned)n_views), kHypThreads, 0, s>>>(uv, xyz, view_start, intr, opts->seed, ws);
+    });
     if (st != LS2FM_OK) return st;
-    const int64_t max_rounds = (cap + kRound - 1) / kRound;          // N <= cap: every view has stopped after these
-    for (int64_t r = 0; max_n >= 3 && r < max_rounds; ++r) {
-        pose_hyp_kernel<<<dim3(kRound / kHypThreads, (unsigned)n_views), kHypThreads, 0, s>>>(uv, xyz, view_start, intr, opts->seed, w);
-        pose_score_kernel<<<dim3((unsigned)tiles, kRound / kScoreTrials), kScoreThreads, 0, s>>>(uv, xyz, view_start, intr, n_views, thr2,
-                                                                                                w);
-        if (hipMemsetAsync(w.n_active, 0, sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
-        pose_select_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(view_start, opts->confidence, min_trials, cap, w);
-        if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
-        int32_t h_active = 0;
-        if (hipMemcpyAsync(&h_active, w.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return ls2fm_launch_status();
-        if (h_active == 0) break;
-    }
     pose_lo_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(uv, xyz, view_start, intr, thr2, w, poses, inliers, num_inliers, trials,
                                                               best_trial, success);
     if (opts->refine)

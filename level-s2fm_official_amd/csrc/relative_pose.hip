@@ -3,40 +3,31 @@
 // the _Trad drivers of cv2 (triangulatePoints), all geometry in fp64.  include/ls2fm.h states the rules; tests/relpose_restate.py
 // repeats them in numpy.  Correspondences are SORTED BY PAIR (pair p owns [pair_start[p], pair_start[p + 1])).
 //
-//   per round (host loop; a pair stops once its trial count reaches the stopping rule's N):
-//     rel_hyp_kernel     one thread per (pair, trial): five distinct indices from the SplitMix64 stream, five-point, <= 10 E
-//     rel_score_kernel   (1024-correspondence tile of some pair, 16-trial block): inlier counts of the block's 160 E over the
-//                        tile (squared Sampson error), wave ballots + integer atomics; tiles of all pairs in one flat range
-//     rel_select_kernel  one workgroup per pair: the best (count, lowest trial * 10 + slot) as a 64-bit max, the stopping rule
-//   then rel_final_kernel: local optimisation (five-point on the inlier set's normal matrix), the final mask and the pose
-//   recovery, one workgroup per pair with fixed-order reductions: every bit is a function of the pair's own data, seed and options.
+// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model RelModel below (squared
+// Sampson error) with this file's rel_hyp_kernel: one thread per (pair, trial), five-point on five distinct correspondences,
+// <= 10 E.  Then rel_final_kernel: local optimisation (five-point on the inlier set's normal matrix), the final mask and the pose
+// recovery, one workgroup per pair with fixed-order reductions: every bit is a function of the pair's own data, seed and options.
 //
 // The five-point solver's per-problem state (null-space basis 36, quadratic terms 70, the 10 x 20 cubic-constraint matrix 200:
 // kWords fp64 words) is a column of LDS: word k of thread j sits at s_buf[k * kFpThreads + j], so every run-time index (pivot
 // rows, polynomial degrees, the Sturm sequence) addresses LDS, never a private array, and no kernel of this file uses scratch.
 // 32 threads per workgroup: kWords x 32 x 8 B = 78 KB, two workgroups per CU.
-#include "ls2fm_device.h"
+#include "ransac.h"
 
-#include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
 
 namespace {
 
 #define HD __host__ __device__
 
-constexpr int kRound = LS2FM_POSE_ROUND;      // trials per pair per round (1024)
+using namespace ransac;
+
 constexpr int kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS;   // 10
 constexpr int kFpThreads = 32;                 // five-point workgroups (hypotheses, ls2fm_five_point)
-constexpr int kScoreThreads = 256;
-constexpr int kScorePts = 4;
-constexpr int kScoreTile = kScoreThreads * kScorePts;
-constexpr int kScoreTrials = 16;               // trials per scoring workgroup (160 E in LDS)
-constexpr int kPairThreads = 256;              // selection / final workgroups
+constexpr int kPairThreads = 256;              // final workgroups
 constexpr int kTriThreads = 256;
 constexpr int kLoIters = 10;
-constexpr int kMaxDraws = 64;
 constexpr int kBisectIters = 100;
 constexpr int kNewtonIters = 5;
 constexpr int kJacobiSweeps = 30;
@@ -51,7 +42,7 @@ constexpr int kDeg = kA + 66;    // their degrees (11)
 constexpr int kRoot = kA + 77;   // real roots (10)
 constexpr int kTmp = kA + 100;   // scratch polynomials (minors of B, the long division's dividend), pivot columns
 
-static_assert(kRound % kScoreTrials == 0 && kRound % kFpThreads == 0, "round shape");
+static_assert(kRound % kFpThreads == 0, "round shape");
 
 HD inline bool is_finite(double x) { return x - x == 0.0; }       // host and device alike (inf - inf and NaN are NaN)
 
@@ -60,30 +51,6 @@ struct Col {                     // one solve's words in LDS, stride S
     double* p;
     HD double& operator[](int k) const { return p[k * S]; }
 };
-
-// ----------------------------------------------------------------------------------------------------------- sample stream
-HD inline uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-HD inline int64_t draw_index(uint64_t key, int k, int64_t n) {
-    return (int64_t)(((splitmix64(key + (uint64_t)k) >> 32) * (uint64_t)n) >> 32);
-}
-
-// -------------------------------------------------------------------------------------------------------------- stopping
-HD inline int64_t num_trials(double eps, double confidence, int64_t min_t, int64_t max_t) {
-    if (eps <= 0.0) return max_t;
-    if (eps >= 1.0) return min_t;
-    const double den = log(1.0 - eps * eps * eps * eps * eps);
-    if (den >= 0.0) return max_t;
-    const double n = ceil(log(1.0 - confidence) / den);
-    if (n >= (double)max_t) return min_t > max_t ? min_t : max_t;
-    const int64_t ni = (int64_t)n;
-    return ni < min_t ? min_t : ni;
-}
 
 // ------------------------------------------------------------------------------------------------------- monomial indexing
 // quadratic monomials: x^2 y^2 z^2 xy xz yz x y z 1 ; variables 0..3 = x, y, z, 1
@@ -696,37 +663,6 @@ five_point_kernel(const double* __restrict__ x1, const double* __restrict__ x2, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- RANSAC
-struct Ws {                     // workspace layout (ls2fm_relative_pose_workspace_bytes)
-    double* hyp;                // [P][kRound][10][9]
-    int32_t* valid;             // [P][kRound]   bit s: slot s holds an E
-    int32_t* counts;            // [P][kRound][10]
-    unsigned long long* best_key;   // [P]
-    double* best_e;             // [P][9]
-    int32_t* trials;            // [P]
-    int32_t* active;            // [P]
-    int32_t* n_active;          // [1]
-    int32_t* tile_off;          // [P + 1]
-};
-
-HD inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-HD inline size_t ws_layout(int32_t P, char* base, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* hyp = take((size_t)P * kRound * kMaxSol * 9 * sizeof(double));
-    char* valid = take((size_t)P * kRound * sizeof(int32_t));
-    char* counts = take((size_t)P * kRound * kMaxSol * sizeof(int32_t));
-    char* bk = take((size_t)P * sizeof(unsigned long long));
-    char* be = take((size_t)P * 9 * sizeof(double));
-    char* tr = take((size_t)P * sizeof(int32_t));
-    char* ac = take((size_t)P * sizeof(int32_t));
-    char* na = take(sizeof(int32_t));
-    char* to = take(((size_t)P + 1) * sizeof(int32_t));
-    if (w) *w = {(double*)hyp, (int32_t*)valid, (int32_t*)counts, (unsigned long long*)bk, (double*)be, (int32_t*)tr, (int32_t*)ac,
-                 (int32_t*)na, (int32_t*)to};
-    return off;
-}
-
 __device__ __forceinline__ double pair_thr2(const double* __restrict__ k0, const double* __restrict__ k1, double err_px) {
     const double f0 = 0.5 * (k0[0] + k0[1]), f1 = 0.5 * (k1[0] + k1[1]);
     const double e = 0.5 * (err_px / f0 + err_px / f1);
@@ -738,14 +674,26 @@ __device__ __forceinline__ void normalised(const double* __restrict__ uv, int64_
     y = (uv[2 * i + 1] - K[3]) / K[1];
 }
 
-__global__ void __launch_bounds__(kPairThreads)
-rel_init_kernel(const int32_t* __restrict__ ps, int32_t P, Ws w) {
-    const int p = blockIdx.x * kPairThreads + threadIdx.x;
-    if (p >= P) return;
-    w.best_key[p] = 0ull;
-    w.trials[p] = 0;
-    w.active[p] = (ps[p + 1] - ps[p]) >= 5 ? 1 : 0;
-}
+struct RelModel {               // ransac.h's model of this file: essential matrices scored by the squared Sampson error
+    static constexpr int kSample = 5, kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS, kHypWords = 9, kMinGroup = 5;
+    struct Input { const double* uv0; const double* uv1; const double* intr0; const double* intr1; double err_px; };
+    struct Ctx { const double* K0; const double* K1; double thr2; };
+    struct Point { double x1, y1, x2, y2; };
+    static __device__ __forceinline__ Ctx context(const Input& in, int p) {
+        const double* K0 = in.intr0 + 4 * p;
+        const double* K1 = in.intr1 + 4 * p;
+        return {K0, K1, pair_thr2(K0, K1, in.err_px)};
+    }
+    static __device__ __forceinline__ Point load(const Input& in, const Ctx& c, int64_t i) {
+        Point pt;
+        normalised(in.uv0, i, c.K0, pt.x1, pt.y1);
+        normalised(in.uv1, i, c.K1, pt.x2, pt.y2);
+        return pt;
+    }
+    static __device__ __forceinline__ bool inlier(const double* E, const Point& pt, const Ctx& c) {
+        return is_inlier(E, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
+    }
+};
 
 __global__ void __launch_bounds__(kFpThreads)
 rel_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
@@ -759,20 +707,9 @@ rel_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, c
     for (int s = 0; s < kMaxSol; ++s) cnt[s] = 0;
     const int64_t s0 = ps[p], n = ps[p + 1] - s0;
     const uint64_t t = (uint64_t)(w.trials[p] + tl);
-    const uint64_t key = splitmix64(seed ^ splitmix64(t));
-    int64_t id[5] = {-1, -1, -1, -1, -1};
-    int got = 0;
-    for (int k = 0; k < kMaxDraws && got < 5; ++k) {
-        const int64_t d = draw_index(key, k, n);
-        bool fresh = true;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) fresh = fresh && id[q] != d;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) id[q] = (fresh && q == got) ? d : id[q];
-        got += fresh ? 1 : 0;
-    }
+    int64_t id[5];
     int mask = 0;
-    if (got == 5) {
+    if (sample_distinct(trial_key(seed, t), n, id)) {
         const double* __restrict__ K0 = intr0 + 4 * p;
         const double* __restrict__ K1 = intr1 + 4 * p;
         double a[5][2], b[5][2];
@@ -792,136 +729,8 @@ rel_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, c
     w.valid[slot] = mask;
 }
 
-__global__ void __launch_bounds__(kScoreThreads)
-rel_score_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
-                 const double* __restrict__ intr0, const double* __restrict__ intr1, int32_t P, double err_px, Ws w) {
-    const int32_t bx = (int32_t)blockIdx.x;
-    int lo = 0, hi = P;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (w.tile_off[mid] <= bx) lo = mid; else hi = mid;
-    }
-    const int p = lo;
-    if (!w.active[p]) return;
-    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
-    const int64_t base = (int64_t)(bx - w.tile_off[p]) * kScoreTile;
-    if (base >= n) return;
-    constexpr int kH = kMaxSol * kScoreTrials;
-    __shared__ double s_h[kH][9];
-    __shared__ int s_valid[kScoreTrials];
-    __shared__ int s_cnt[kH];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t slot0 = (int64_t)p * kRound + (int64_t)blockIdx.y * kScoreTrials;
-    for (int q = tid; q < kH * 9; q += kScoreThreads) s_h[q / 9][q % 9] = w.hyp[kMaxSol * 9 * slot0 + q];
-    if (tid < kScoreTrials) s_valid[tid] = w.valid[slot0 + tid];
-    if (tid < kH) s_cnt[tid] = 0;
-    const double* __restrict__ K0 = intr0 + 4 * p;
-    const double* __restrict__ K1 = intr1 + 4 * p;
-    const double thr2 = pair_thr2(K0, K1, err_px);
-    double ax[kScorePts], ay[kScorePts], bxv[kScorePts], byv[kScorePts];
-    bool live[kScorePts];
-#pragma unroll
-    for (int k = 0; k < kScorePts; ++k) {
-        const int64_t j = base + tid + (int64_t)k * kScoreThreads;
-        live[k] = j < n;
-        const int64_t i = s0 + (live[k] ? j : 0);
-        normalised(uv0, i, K0, ax[k], ay[k]);
-        normalised(uv1, i, K1, bxv[k], byv[k]);
-    }
-    __syncthreads();
-    for (int h = 0; h < kH; ++h) {
-        if (!((s_valid[h / kMaxSol] >> (h % kMaxSol)) & 1)) continue;
-        const double* E = s_h[h];
-        int c = 0;
-#pragma unroll
-        for (int k = 0; k < kScorePts; ++k) c += __popcll(__ballot(live[k] && is_inlier(E, ax[k], ay[k], bxv[k], byv[k], thr2)));
-        if (lane == 0 && c) atomicAdd(&s_cnt[h], c);
-    }
-    __syncthreads();
-    if (tid < kH && s_cnt[tid]) atomicAdd(&w.counts[kMaxSol * slot0 + tid], s_cnt[tid]);
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(k, o, 64);
-        k = t > k ? t : k;
-    }
-    return k;
-}
-
-__global__ void __launch_bounds__(kPairThreads)
-rel_select_kernel(const int32_t* __restrict__ ps, double confidence, int64_t min_trials, int64_t max_trials, Ws w) {
-    const int p = blockIdx.x;
-    if (!w.active[p]) return;
-    const int tid = threadIdx.x;
-    __shared__ unsigned long long s_k[kPairThreads / 64];
-    const int32_t t0 = w.trials[p];
-    unsigned long long best = 0ull;
-    for (int c = tid; c < kMaxSol * kRound; c += kPairThreads) {
-        const int64_t slot = (int64_t)p * kRound + c / kMaxSol;
-        const int s = c % kMaxSol;
-        const int cnt = w.counts[kMaxSol * slot + s];
-        if (cnt > 0 && ((w.valid[slot] >> s) & 1)) {
-            const uint32_t idx = (uint32_t)(t0 + c / kMaxSol) * (uint32_t)kMaxSol + (uint32_t)s;
-            const unsigned long long key = ((unsigned long long)(uint32_t)cnt << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
-            best = key > best ? key : best;
-        }
-    }
-    best = wave_max_u64(best);
-    if ((tid & 63) == 0) s_k[tid >> 6] = best;
-    __syncthreads();
-    if (tid != 0) return;
-    for (int q = 0; q < kPairThreads / 64; ++q) best = s_k[q] > best ? s_k[q] : best;
-    if (best > w.best_key[p]) {
-        w.best_key[p] = best;
-        const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
-        const int64_t slot = (int64_t)p * kRound + (int64_t)(idx / (uint32_t)kMaxSol - (uint32_t)t0);
-        for (int q = 0; q < 9; ++q) w.best_e[9 * p + q] = w.hyp[kMaxSol * 9 * slot + 9 * (idx % (uint32_t)kMaxSol) + q];
-    }
-    const int32_t done = t0 + kRound;
-    w.trials[p] = done;
-    const double eps = (double)(w.best_key[p] >> 32) / (double)(ps[p + 1] - ps[p]);
-    const bool on = done < num_trials(eps, confidence, min_trials, max_trials);
-    w.active[p] = on ? 1 : 0;
-    if (on) atomicAdd(w.n_active, 1);
-}
-
 // ------------------------------------------------------------------------------------------------ local optimisation, pose
 constexpr int kNe = 45;
-
-__device__ __forceinline__ void block_sum(double (&a)[kNe], double* s_red /* [kPairThreads / 64][kNe] */) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < kNe; ++q) {
-        double t = a[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        a[q] = t;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < kNe; ++q) s_red[(tid >> 6) * kNe + q] = a[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kNe; ++q) {
-        double t = s_red[q];
-#pragma unroll
-        for (int wv = 1; wv < kPairThreads / 64; ++wv) t += s_red[wv * kNe + q];
-        a[q] = t;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ int block_count(int c, int* s_int) {     // exact integer sum over the workgroup
-    __syncthreads();
-    if (threadIdx.x == 0) *s_int = 0;
-    __syncthreads();
-    if (c) atomicAdd(s_int, c);
-    __syncthreads();
-    return *s_int;
-}
 
 __global__ void __launch_bounds__(kPairThreads)
 rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
@@ -947,7 +756,7 @@ rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1,
     }
     double E[9];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) E[q] = w.best_e[9 * p + q];
+    for (int q = 0; q < 9; ++q) E[q] = w.best[9 * p + q];
     int cur = 0;
     for (int64_t j = tid; j < n; j += kPairThreads) {
         double a0, a1, b0, b1;
@@ -972,7 +781,7 @@ rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1,
 #pragma unroll
                 for (int k = i; k < 9; ++k) a[sidx(i, k)] += r[i] * r[k];
         }
-        block_sum(a, s_red);
+        block_sum<kNe, kPairThreads>(a, s_red);
         {
             double v[9];
             jacobi9(a, tid < 9 ? tid : 0, v);
@@ -1070,7 +879,7 @@ rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1,
     if (tid == 0) {
         num_inliers[p] = cur;
         trials[p] = w.trials[p];
-        best_trial[p] = (int32_t)((0xFFFFFFFFu - (uint32_t)(bk & 0xFFFFFFFFull)) / (uint32_t)kMaxSol);
+        best_trial[p] = best_trial_of<RelModel>(bk);
         success[p] = ok ? 1 : 0;
     }
 }
@@ -1095,22 +904,6 @@ triangulate_kernel(const double* __restrict__ P0, const double* __restrict__ P1,
     for (int r = 0; r < 4; ++r) X[4 * i + r] = h[r];
 }
 
-bool opts_ok(const ls2fm_pose_ransac_opts* o) {
-    return o && o->max_error_px > 0.0 && std::isfinite(o->max_error_px) && o->confidence > 0.0 && o->confidence < 1.0 &&
-           o->min_inlier_ratio >= 0.0 && o->min_inlier_ratio < 1.0 && o->min_num_trials >= 0 && o->max_num_trials >= 1 &&
-           o->max_num_trials <= LS2FM_POSE_MAX_TRIALS && o->min_num_trials <= o->max_num_trials && o->refine == 0;
-}
-
-// pair_start (device) -> host copy with the checks; returns false on a transfer error (status in *st)
-bool host_pair_start(const int32_t* ps, int32_t P, hipStream_t s, int32_t* h, int* st) {
-    if (hipMemcpyAsync(h, ps, sizeof(int32_t) * ((size_t)P + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        *st = ls2fm_launch_status();
-        return false;
-    }
-    return true;
-}
-
 }  // namespace
 
 extern "C" int ls2fm_five_point(const double* x1, const double* x2, int64_t m, double* E, int32_t* n_solutions, void* stream) {
@@ -1123,65 +916,25 @@ extern "C" int ls2fm_five_point(const double* x1, const double* x2, int64_t m, d
 
 extern "C" int64_t ls2fm_relative_pose_workspace_bytes(int32_t n_pairs, int64_t n_corr) {
     if (n_pairs < 1 || n_pairs > LS2FM_RELPOSE_MAX_PAIRS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
-    return (int64_t)ws_layout(n_pairs, nullptr, nullptr);
+    return (int64_t)ws_layout<RelModel>(n_pairs, nullptr, nullptr);
 }
 
 extern "C" int ls2fm_relative_pose(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs, const double* intr0,
                                    const double* intr1, const ls2fm_pose_ransac_opts* opts, double* E, double* poses, uint8_t* inliers,
                                    int32_t* num_inliers, int32_t* trials, int32_t* best_trial, int32_t* success, void* workspace,
                                    void* stream) {
-    LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && pair_start && intr0 && intr1 && opts_ok(opts));
+    LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && pair_start && intr0 && intr1 && opts_ok(opts) &&
+                    opts->refine == 0);
     LS2FM_CHECK_ARG(E && poses && num_inliers && trials && best_trial && success);
     if (!workspace) return LS2FM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    int32_t* h_ps = (int32_t*)malloc(sizeof(int32_t) * ((size_t)n_pairs + 1));
-    if (!h_ps) return LS2FM_ERR_LAUNCH;
-    int st = LS2FM_OK;
-    if (!host_pair_start(pair_start, n_pairs, s, h_ps, &st)) {
-        free(h_ps);
-        return st;
-    }
-    int64_t max_n = 0;
-    bool mono = h_ps[0] >= 0;
-    int32_t tiles = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        mono = mono && h_ps[p + 1] >= h_ps[p];
-        const int64_t np = (int64_t)h_ps[p + 1] - h_ps[p];
-        max_n = std::max<int64_t>(max_n, np);
-        h_ps[p] = tiles;
-        tiles += mono ? (int32_t)((np + kScoreTile - 1) / kScoreTile) : 0;
-    }
-    const int64_t total = h_ps[n_pairs];
-    h_ps[n_pairs] = tiles;
-    if (!(mono && (total == 0 || (uv0 && uv1 && inliers)))) {
-        free(h_ps);
-        return LS2FM_ERR_INVALID_ARGUMENT;
-    }
     Ws w;
-    ws_layout(n_pairs, (char*)workspace, &w);
-    const bool copied = hipMemcpyAsync(w.tile_off, h_ps, sizeof(int32_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s) == hipSuccess &&
-                        hipStreamSynchronize(s) == hipSuccess;
-    free(h_ps);
-    if (!copied) return ls2fm_launch_status();
-    const int64_t cap = num_trials(opts->min_inlier_ratio, opts->confidence, 0, opts->max_num_trials);
-    const int64_t min_trials = std::min<int64_t>(opts->min_num_trials, cap);
-    rel_init_kernel<<<(unsigned)((n_pairs + kPairThreads - 1) / kPairThreads), kPairThreads, 0, s>>>(pair_start, n_pairs, w);
-    if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
-    const int64_t max_rounds = (cap + kRound - 1) / kRound;
-    for (int64_t r = 0; max_n >= 5 && r < max_rounds; ++r) {
+    const int st = run_rounds<RelModel>({uv0, uv1, intr0, intr1, opts->max_error_px}, pair_start, n_pairs, uv0 && uv1 && inliers, opts,
+                                        workspace, s, &w, [&](const Ws& ws) {
         rel_hyp_kernel<<<dim3(kRound / kFpThreads, (unsigned)n_pairs), kFpThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->seed,
-                                                                                           w);
-        rel_score_kernel<<<dim3((unsigned)tiles, kRound / kScoreTrials), kScoreThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1,
-                                                                                               n_pairs, opts->max_error_px, w);
-        if (hipMemsetAsync(w.n_active, 0, sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
-        rel_select_kernel<<<(unsigned)n_pairs, kPairThreads, 0, s>>>(pair_start, opts->confidence, min_trials, cap, w);
-        if ((st = ls2fm_launch_status()) != LS2FM_OK) return st;
-        int32_t h_active = 0;
-        if (hipMemcpyAsync(&h_active, w.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return ls2fm_launch_status();
-        if (h_active == 0) break;
-    }
+                                                                                           ws);
+    });
+    if (st != LS2FM_OK) return st;
     rel_final_kernel<<<(unsigned)n_pairs, kPairThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->max_error_px, w, E, poses,
                                                                 inliers, num_inliers, trials, best_trial, success);
     return ls2fm_launch_status();

@@ -53,36 +53,7 @@ def _intrinsics(intr, n_views, dev):
 
 def _ragged(uv, xyz, view_start):
     """(uv [n,2], xyz [n,3], view_start int32 [V+1]) on the device from tensors or lists of per-view tensors"""
-    if isinstance(uv, (list, tuple)):
-        if not isinstance(xyz, (list, tuple)) or len(xyz) != len(uv) or len(uv) == 0:
-            raise ValueError("ls2fm.pose: uv and xyz lists must have the same non-zero length")
-        if view_start is not None:
-            raise ValueError("ls2fm.pose: view_start is implied by lists of per-view tensors")
-        dev = torch.as_tensor(uv[0]).device
-        us = [torch.as_tensor(u).reshape(-1, 2) for u in uv]
-        xs = [torch.as_tensor(x).reshape(-1, 3) for x in xyz]
-        for u, x in zip(us, xs):
-            if u.shape[0] != x.shape[0]:
-                raise ValueError(f"ls2fm.pose: {u.shape[0]} key points against {x.shape[0]} 3-D points")
-        counts = [u.shape[0] for u in us]
-        vs = torch.tensor([0] + list(np.cumsum(counts)), dtype=torch.int32, device=dev)
-        return (_f64(torch.cat(us).to(dev), (2,), "uv"), _f64(torch.cat(xs).to(dev), (3,), "xyz"), vs)
-    uv = _f64(uv, (2,), "uv")
-    xyz = _f64(xyz, (3,), "xyz")
-    if uv.shape[0] != xyz.shape[0]:
-        raise ValueError(f"ls2fm.pose: {uv.shape[0]} key points against {xyz.shape[0]} 3-D points")
-    if view_start is None:
-        view_start = torch.tensor([0, uv.shape[0]], dtype=torch.int32, device=uv.device)
-    view_start = torch.as_tensor(view_start, device=uv.device).to(torch.int32).contiguous()
-    if view_start.dim() != 1 or view_start.numel() < 2:
-        raise ValueError("ls2fm.pose: view_start must be [V + 1]")
-    if not torch.cuda.is_current_stream_capturing():
-        # the kernels index uv / xyz / the mask through view_start: it must cover exactly [0, n), in order
-        h = view_start.cpu()
-        if int(h[0]) != 0 or int(h[-1]) != uv.shape[0] or bool((h[1:] < h[:-1]).any()):
-            raise ValueError(f"ls2fm.pose: view_start must rise from 0 to the {uv.shape[0]} correspondences, "
-                             f"got {h[0].item()} .. {h[-1].item()}")
-    return uv, xyz, view_start
+    return _ragged_common(uv, xyz, view_start, (3,), "uv", "xyz", "view_start")
 
 
 def p3p(bearings, points):
@@ -188,7 +159,7 @@ def _ragged_common(a, b, starts, tail_b, name_a, name_b, name_s):
         if not isinstance(b, (list, tuple)) or len(b) != len(a) or len(a) == 0:
             raise ValueError(f"ls2fm.pose: {name_a} and {name_b} lists must have the same non-zero length")
         if starts is not None:
-            raise ValueError(f"ls2fm.pose: {name_s} is implied by lists of per-pair tensors")
+            raise ValueError(f"ls2fm.pose: {name_s} is implied by lists of per-view / per-pair tensors")
         dev = torch.as_tensor(a[0]).device
         As = [torch.as_tensor(u).reshape(-1, 2) for u in a]
         Bs = [torch.as_tensor(x).reshape(-1, *tail_b) for x in b]
@@ -206,8 +177,9 @@ def _ragged_common(a, b, starts, tail_b, name_a, name_b, name_s):
         starts = torch.tensor([0, a.shape[0]], dtype=torch.int32, device=a.device)
     starts = torch.as_tensor(starts, device=a.device).to(torch.int32).contiguous()
     if starts.dim() != 1 or starts.numel() < 2:
-        raise ValueError(f"ls2fm.pose: {name_s} must be [P + 1]")
+        raise ValueError(f"ls2fm.pose: {name_s} must be 1-D, one entry more than there are views / pairs")
     if not torch.cuda.is_current_stream_capturing():
+        # the kernels index the correspondences (and masks) through the start array: it must cover exactly [0, n), in order
         h = starts.cpu()
         if int(h[0]) != 0 or int(h[-1]) != a.shape[0] or bool((h[1:] < h[:-1]).any()):
             raise ValueError(f"ls2fm.pose: {name_s} must rise from 0 to the {a.shape[0]} correspondences, "

@@ -12,9 +12,8 @@ import math
 
 import numpy as np
 
-from pose_restate import splitmix64, trial_key  # noqa: F401  (the same sample stream)
+from pose_restate import draw, splitmix64, trial_key  # noqa: F401  (the same sample stream)
 
-M64 = (1 << 64) - 1
 ROUND = 1024
 MAX_SOL = 10
 LO_ITERS = 10
@@ -32,10 +31,6 @@ _VARS = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (0, 0, 0)]
 
 
 # ------------------------------------------------------------------------------------------------------------ sample stream
-def draw(seed, t, k, n):
-    return ((splitmix64((trial_key(seed, t) + k) & M64) >> 32) * n) >> 32
-
-
 def sample(seed, t, n):
     """the first five distinct draws of trial t among k = 0..63, or None"""
     got = []

@@ -219,6 +219,33 @@ def test_batch_equals_single_pairs():
     assert succ.sum() >= 37
 
 
+def test_batch_with_multi_tile_pairs():
+    # a tile boundary (1025), an empty pair sharing the next pair's tile offset, and a three-tile pair (2049) in one scoring grid
+    rng = np.random.default_rng(29)
+    sizes = [1025, 0, 2049, 300]
+    k0 = np.array([[500.0 + 10 * p, 500.0 + 10 * p, 320.0, 240.0] for p in range(4)])
+    k1 = np.array([[520.0 + 5 * p, 530.0 + 5 * p, 330.0, 250.0] for p in range(4)])
+    pairs = [scene(rng, n, outlier_ratio=0.3, sigma=0.3 * (p % 2), intr0=tuple(k0[p]), intr1=tuple(k1[p]))[:2]
+             for p, n in enumerate(sizes)]
+    r = pose.relative_pose([dev(a) for a, _ in pairs], [dev(b) for _, b in pairs], dev(k0), dev(k1))
+    ps = r["pair_start"].cpu().numpy()
+    assert ps.tolist() == [0, 1025, 1025, 3074, 3374]
+    inl = r["inliers"].cpu().numpy()
+    for p, (a, b) in enumerate(pairs):
+        s = pose.relative_pose(dev(a.reshape(-1, 2)), dev(b.reshape(-1, 2)), dev(k0[p]), dev(k1[p]))
+        assert torch.equal(s["E"][0], r["E"][p]), p
+        assert torch.equal(s["poses"][0], r["poses"][p]), p
+        assert np.array_equal(s["inliers"].cpu().numpy(), inl[ps[p]:ps[p + 1]]), p
+        for key in ("num_inliers", "trials", "best_trial", "success"):
+            assert s[key][0].item() == r[key][p].item(), (p, key)
+        if sizes[p]:
+            x1, x2 = RR.normalised(a, tuple(k0[p])), RR.normalised(b, tuple(k1[p]))
+            mask = RR.inliers_of(r["E"][p].cpu().numpy(), x1, x2, RR.threshold2(tuple(k0[p]), tuple(k1[p]), 4.0))
+            assert np.array_equal(inl[ps[p]:ps[p + 1]], mask), p
+    assert int(r["trials"][1]) == 0 and not bool(r["success"][1])
+    assert torch.equal(r["poses"][1], torch.eye(3, 4, dtype=torch.float64, device=DEV))
+
+
 def test_determinism():
     rng = np.random.default_rng(26)
     pairs, k0, k1 = _batch_pairs(rng)
