@@ -819,6 +819,76 @@ int ls2fm_triangulate(const double* P0, const double* P1, const double* uv0, con
                       int32_t n_pairs, int64_t n, double* X, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Uncalibrated two-view geometry (csrc/two_view.hip; additions, the library stays ABI 13): the fundamental matrix and the
+ * homography of COLMAP's two-view geometry for many view pairs in one call, in PIXELS -- no intrinsics.  All geometry in fp64.
+ * F (row-major 3 x 3) has x2h^T F x1h = 0 and H has x2h ~ H x1h for pixels x1 of the first and x2 of the second image.  The ragged
+ * pair_start convention, the options struct and the rounds are ls2fm_relative_pose's.  tests/twoview_restate.py repeats every rule
+ * below in numpy.
+ *
+ * conditioning (both minimal solvers and both local optimisations, per image): Hartley normalisation of the point set at hand:
+ *   c = (sum x) / n ; d2 = sum |x - c|^2 ; s = sqrt(2) / sqrt(d2 / n) ; x_n = s (x - c), i.e. T = [s 0 -s cx; 0 s -s cy; 0 0 1].
+ *   A set whose sqrt(d2 / n) is 0 or not finite yields no model.  A model M_n between normalised points is de-normalised
+ *   (F = T2^T F_n T1, H = T2^-1 H_n T1), scaled to unit Frobenius norm and signed so that its largest |entry| (the first of equals,
+ *   row-major) is positive; a model that is zero or not finite after that is dropped.
+ *
+ * ls2fm_seven_point: m minimal problems, uv0 / uv1 [m][7][2] pixels -> F [m][3][3][3] (kept ones first, zero beyond) and
+ * n_solutions [m].
+ *   null space  the 7 x 9 rows kron((x2_n, 1), (x1_n, 1)) by ls2fm_five_point's Gauss-Jordan rule (partial pivoting; a column whose
+ *               largest remaining |entry| is <= 1e-12 of the matrix's largest is free; basis vector j for free column f_j,
+ *               ascending: 1 at f_j, -R[i][f_j] at pivot column i; modified Gram-Schmidt in order j = 0, 1) -> F1, F2.  rank != 7: 0
+ *               solutions.
+ *   cubic       det(l F1 + (1 - l) F2) = det(F2 + l (F1 - F2)), expanded multilinearly in the rows; its coefficients divided by
+ *               the largest |coefficient|; |c3| < 1e-14 then: a quadratic (|c2| < 1e-14 as well: linear, c1 = 0: no root).
+ *   roots       CLOSED FORM plus a bracketed Newton polish (not the Sturm machinery of ls2fm_five_point).  Monic a, b, d;
+ *               Q = (a^2 - 3 b) / 9, R = (2 a^3 - 9 a b + 27 d) / 54, mid = -a / 3.  R^2 < Q^3: three roots
+ *               mid - 2 sqrt(Q) cos((th + 2 pi k) / 3), th = acos(R / sqrt(Q^3)), k = 0, -1, 1, bracketed by the turning points
+ *               (-inf, mid - sqrt Q], [mid - sqrt Q, mid + sqrt Q], [mid + sqrt Q, inf).  Otherwise one root
+ *               mid + A + Q / A, A = -sign(R) cbrt(|R| + sqrt(R^2 - Q^3)), bracketed on its side of the turning points when
+ *               Q > 0.  A quadratic: q = -(c1 + sign(c1) sqrt(disc)) / 2, roots q / c2 and c0 / q, bracketed by the vertex.  Each
+ *               root takes <= 5 Newton steps on the scaled polynomial; a step that leaves its bracket, does not move or meets a
+ *               zero derivative ends the polish.  Roots ascending.
+ *   recovery    F_n = l F1 + (1 - l) F2 per root, the conditioning block's de-normalisation, norm and sign.
+ *
+ * ls2fm_four_point_homography: m problems uv0 / uv1 [m][4][2] -> H [m][3][3], n_solutions [m] (0 or 1).  DLT: per correspondence
+ *   the rows (-x, -y, -1, 0, 0, 0, u x, u y, u) and (0, 0, 0, -x, -y, -1, v x, v y, v) of (x, y) = x1_n, (u, v) = x2_n; the null
+ *   vector by the same Gauss-Jordan rule; rank != 8 (three collinear points, coincident points): 0 solutions.
+ *
+ * ls2fm_fundamental_matrix / ls2fm_homography: LO-RANSAC per pair (the rounds of csrc/ransac.h).
+ *   samples   ls2fm_absolute_pose's SplitMix64 stream keyed by (seed, trial): the first 7 (F) / 4 (H) distinct draws among
+ *             k = 0 .. 63.  hypotheses: the minimal solver of the sample, slot s = the solution's place (F: 0..2, H: 0).
+ *   scoring   F: squared Sampson error in pixels (ls2fm_relative_pose's formula on pixel coordinates) <= max_error_px^2.
+ *             H: |pi(H x1h) - x2|^2 <= max_error_px^2; a correspondence whose (H x1h)_3 has |.| <= DBL_EPSILON or is not finite is
+ *             not an inlier.  Counts are exact integers.
+ *   selection the 64-bit max of (count << 32 | ~(t * S + s)), S = 3 (F) / 1 (H).
+ *   rounds    as ls2fm_relative_pose with eps^7 (F) / eps^4 (H).  The call SYNCHRONISES (one word per round), not capturable.
+ *   local optimisation from the best model, up to 10 times while >= 8 (F) / >= 4 (H) inliers: the conditioning of the inlier set
+ *             (fixed-order sums), the 9 x 9 normal matrix of the inliers' normalised rows (F: the row kron((x2_n, 1), (x1_n, 1));
+ *             H: the two DLT rows; fixed-order sum), its eigenvector of the smallest eigenvalue by ls2fm_relative_pose's cyclic
+ *             Jacobi (the lower index first among equals); for F the smallest singular value zeroed in normalised coordinates
+ *             (one-sided Jacobi on the columns, the lower index among equal column norms); de-normalised, unit norm, signed; the
+ *             candidate is recounted and kept when its count is >= the current one; the loop stops when it is lower, when there
+ *             is no candidate, or when the inlier set did not change.
+ *   outputs   model [P][3][3], inliers (uint8) of the final model, num_inliers, trials, best_trial (the winning SAMPLED trial, -1
+ *             when none), success = num_inliers >= 8 (F) / >= 4 (H).  A pair without success gets a ZERO matrix, an all-zero mask
+ *             and num_inliers 0 (trials and best_trial still tell what ran; a pair below the sample size has trials 0), without
+ *             touching its neighbours; every bit depends on the pair's own data, seed and options only.
+ *   options   ls2fm_pose_ransac_opts with refine == 0; limits and refusals as ls2fm_relative_pose.  workspace:
+ *             ls2fm_fundamental_matrix_workspace_bytes (~230 KB per pair) / ls2fm_homography_workspace_bytes (~80 KB per pair).
+ */
+#define LS2FM_SEVEN_POINT_MAX_SOLUTIONS 3
+
+int ls2fm_seven_point(const double* uv0, const double* uv1, int64_t m, double* F, int32_t* n_solutions, void* stream);
+int ls2fm_four_point_homography(const double* uv0, const double* uv1, int64_t m, double* H, int32_t* n_solutions, void* stream);
+int64_t ls2fm_fundamental_matrix_workspace_bytes(int32_t n_pairs, int64_t n_corr);
+int64_t ls2fm_homography_workspace_bytes(int32_t n_pairs, int64_t n_corr);
+int ls2fm_fundamental_matrix(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs,
+                             const ls2fm_pose_ransac_opts* opts, double* F, uint8_t* inliers, int32_t* num_inliers, int32_t* trials,
+                             int32_t* best_trial, int32_t* success, void* workspace, void* stream);
+int ls2fm_homography(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs,
+                     const ls2fm_pose_ransac_opts* opts, double* H, uint8_t* inliers, int32_t* num_inliers, int32_t* trials,
+                     int32_t* best_trial, int32_t* success, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Classical bundle adjustment over explicit points and se(3) poses (new; the library's version stays ABI 13: the calls are additions): the loop of pipelines/BA_Trad.py:86-130
  * (`BA.run_ba` behind Ablate_config.ba_trad) -- n_iters iterations in ONE call, two plain launches each, no host read inside.
  *   iteration pose_v = se3_to_SE3(se3[v]) (ls2fm_se3_exp_fwd's arithmetic) ; x_c = R x + t ; u = K x_c ; uv = u_xy / (u_z + 1e-6) ;
@@ -873,7 +943,7 @@ int ls2fm_bundle_adjust_run(float* se3, float* points, const float* obs_uv, int3
  *   cross check (cross_check != 0, COLMAP's default): (i, j) is a match iff i proposes j and j proposes i; 0: the proposals of a.
  *   order      the matches of a pair in increasing i.  At most LS2FM_MATCH_MAX_DESCRIPTORS per image (COLMAP's
  *              max_num_matches); an image with more: LS2FM_ERR_UNSUPPORTED.  Images without descriptors and pairs without a
- *              match are legal and give empty results.  Not restated: guided matching, COLMAP's two-view geometry table.
+ *              match are legal and give empty results.  Not restated: guided matching (the two-view geometry is csrc/two_view.hip's).
  *   outputs    (device, int32; sizes follow from the host arrays) with first(p) = sum over q < p of n_a(q) and
  *              rows(p) = sum over q < p of (n_a(q) + n_b(q)):
  *              match_index [sum n_a]: entry first(p) + i = the j matched to row i of pair p's first image, or -1;

@@ -12,6 +12,7 @@
 // kWords fp64 words) is a column of LDS: word k of thread j sits at s_buf[k * kFpThreads + j], so every run-time index (pivot
 // rows, polynomial degrees, the Sturm sequence) addresses LDS, never a private array, and no kernel of this file uses scratch.
 // 32 threads per workgroup: kWords x 32 x 8 B = 78 KB, two workgroups per CU.
+#include "pose_math.h"
 #include "ransac.h"
 
 #include <cfloat>
@@ -19,8 +20,7 @@
 
 namespace {
 
-#define HD __host__ __device__
-
+using namespace pose_math;
 using namespace ransac;
 
 constexpr int kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS;   // 10
@@ -30,7 +30,6 @@ constexpr int kTriThreads = 256;
 constexpr int kLoIters = 10;
 constexpr int kBisectIters = 100;
 constexpr int kNewtonIters = 5;
-constexpr int kJacobiSweeps = 30;
 
 // LDS words of one five-point solve
 constexpr int kBas = 0;          // basis X, Y, Z, W: 4 x 9 (E = x X + y Y + z Z + W, row-major 3 x 3)
@@ -43,14 +42,6 @@ constexpr int kRoot = kA + 77;   // real roots (10)
 constexpr int kTmp = kA + 100;   // scratch polynomials (minors of B, the long division's dividend), pivot columns
 
 static_assert(kRound % kFpThreads == 0, "round shape");
-
-HD inline bool is_finite(double x) { return x - x == 0.0; }       // host and device alike (inf - inf and NaN are NaN)
-
-template <int S>
-struct Col {                     // one solve's words in LDS, stride S
-    double* p;
-    HD double& operator[](int k) const { return p[k * S]; }
-};
 
 // ------------------------------------------------------------------------------------------------------- monomial indexing
 // quadratic monomials: x^2 y^2 z^2 xy xz yz x y z 1 ; variables 0..3 = x, y, z, 1
@@ -183,24 +174,6 @@ HD inline int sturm_roots(Col<S> w) {
 }
 
 // ------------------------------------------------------------------------------------------------------ five-point solver
-// unit E (largest |entry| positive, the first of equals) -> emit(slot, E[9]); false when not finite
-HD inline bool canonical_e(double (&e)[9]) {
-    double nrm = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) nrm += e[i] * e[i];
-    if (!(nrm > 0.0) || !is_finite(nrm)) return false;
-    const double inv = 1.0 / sqrt(nrm);
-    double big = 0.0, sgn = 1.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        e[i] = e[i] * inv;
-        if (fabs(e[i]) > big) { big = fabs(e[i]); sgn = e[i] < 0.0 ? -1.0 : 1.0; }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) e[i] = sgn * e[i];
-    return true;
-}
-
 // the 4-dimensional null space of the 5 x 9 epipolar system (rows kron((x2, 1), (x1, 1))), Gauss-Jordan with partial pivoting,
 // then modified Gram-Schmidt -> kBas.  false: rank != 5 (pivot <= 1e-12 of the largest entry) or a degenerate basis
 template <int S>
@@ -413,7 +386,7 @@ HD inline int solve_from_basis(Col<S> w, Emit emit) {
         double e[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) e[k] = ((x * lin(w, k, 0) + y * lin(w, k, 1)) + z * lin(w, k, 2)) + lin(w, k, 3);
-        if (!canonical_e(e)) continue;
+        if (!canonical9(e)) continue;
         emit(n, e);
         ++n;
     }
@@ -421,17 +394,6 @@ HD inline int solve_from_basis(Col<S> w, Emit emit) {
 }
 
 // --------------------------------------------------------------------------------------------------------- Sampson error
-HD inline double sampson2(const double* E, double x1, double y1, double x2, double y2) {
-    const double a0 = (E[0] * x1 + E[1] * y1) + E[2];
-    const double a1 = (E[3] * x1 + E[4] * y1) + E[5];
-    const double a2 = (E[6] * x1 + E[7] * y1) + E[8];
-    const double b0 = (E[0] * x2 + E[3] * y2) + E[6];
-    const double b1 = (E[1] * x2 + E[4] * y2) + E[7];
-    const double num = (x2 * a0 + y2 * a1) + a2;
-    const double den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
-    return num * num / den;
-}
-
 HD inline bool is_inlier(const double* E, double x1, double y1, double x2, double y2, double thr2) {
     return sampson2(E, x1, y1, x2, y2) <= thr2;       // NaN (0 / 0) is not an inlier
 }
@@ -500,32 +462,7 @@ HD inline void pose_candidates(const double* E, double (&cand)[4][12]) {
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int r = 0; r < 3; ++r) { a[c][r] = E[3 * r + c]; V[c][r] = c == r ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 3; ++q) {
-                const double al = (a[p][0] * a[p][0] + a[p][1] * a[p][1]) + a[p][2] * a[p][2];
-                const double be = (a[q][0] * a[q][0] + a[q][1] * a[q][1]) + a[q][2] * a[q][2];
-                const double ga = (a[p][0] * a[q][0] + a[p][1] * a[q][1]) + a[p][2] * a[q][2];
-                if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
-                rotated = true;
-                const double zeta = (be - al) / (2.0 * ga);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const double ap = a[p][r], aq = a[q][r];
-                    a[p][r] = c * ap - s * aq;
-                    a[q][r] = s * ap + c * aq;
-                    const double vp = V[p][r], vq = V[q][r];
-                    V[p][r] = c * vp - s * vq;
-                    V[q][r] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
+    onesided_jacobi3(a, V);
     // order the columns by descending norm (three compare-and-swaps)
     double nr[3];
 #pragma unroll
@@ -590,50 +527,6 @@ HD inline bool in_front(const double* P, double x1, double y1, double x2, double
     const double c2 = sqrt((P[2] * P[2] + P[6] * P[6]) + P[10] * P[10]);
     const double d2 = z2 * c2;
     return d2 > DBL_EPSILON && d2 < max_depth;
-}
-
-// ------------------------------------------------------------------------------------------------------ symmetric Jacobi
-constexpr int sidx(int i, int j) { return i <= j ? i * 9 - (i * (i - 1)) / 2 + (j - i) : j * 9 - (j * (j - 1)) / 2 + (i - j); }
-
-// eigen-decomposition of the symmetric 9 x 9 a (upper triangle, 45 entries): cyclic Jacobi, at most kJacobiSweeps sweeps.
-// The caller holds ONE component of the eigenvectors: v[k] = component `row` of the eigenvector of eigenvalue a[sidx(k, k)]
-// (every thread of a workgroup runs the same rotations on the same a, thread r < 9 keeps row r)
-HD inline void jacobi9(double (&a)[45], int row, double (&v)[9]) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) v[k] = k == row ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            dia += a[sidx(i, i)] * a[sidx(i, i)];
-#pragma unroll
-            for (int j = i + 1; j < 9; ++j) off += a[sidx(i, j)] * a[sidx(i, j)];
-        }
-        if (!(off > 1e-30 * dia)) break;
-#pragma unroll
-        for (int p = 0; p < 8; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 9; ++q) {
-                const double apq = a[sidx(p, q)];
-                if (apq == 0.0) continue;
-                const double theta = (a[sidx(q, q)] - a[sidx(p, p)]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    if (k == p || k == q) continue;
-                    const double akp = a[sidx(k, p)], akq = a[sidx(k, q)];
-                    a[sidx(k, p)] = c * akp - s * akq;
-                    a[sidx(k, q)] = s * akp + c * akq;
-                }
-                a[sidx(p, p)] = a[sidx(p, p)] - t * apq;
-                a[sidx(q, q)] = a[sidx(q, q)] + t * apq;
-                a[sidx(p, q)] = 0.0;
-                const double vp = v[p], vq = v[q];
-                v[p] = c * vp - s * vq;
-                v[q] = s * vp + c * vq;
-            }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------- minimal solver

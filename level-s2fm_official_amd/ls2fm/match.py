@@ -5,7 +5,8 @@ preparation/main.py between "images with features" and LevelS2fM.load_matches.
 with its defaults (ratio test 0.8, distance 0.7, cross check) for ALL image pairs in one call of ls2fm_match_descriptors
 (csrc/match.hip: exact integer products on the i8 matrix cores, the top-2 reduction as their epilogue).  `assemble_n_views`
 writes the per-view layout of main.py:177-247; `two_view_tables` chains the matcher, the < 50 filter (:193-194), ONE
-ls2fm.pose.relative_pose call over the surviving pairs for the inlier masks (:209-213) and the assembly.  Every rule is stated in
+ls2fm.pose.relative_pose call (without an intrinsic matrix: ONE ls2fm.pose.fundamental_matrix call) over the surviving pairs for
+the inlier masks (:209-213) and the assembly.  Every rule is stated in
 include/ls2fm.h; tests/match_restate.py repeats the matcher in numpy.
 
 There is no CPU path for the matcher: a missing device or library raises.  `assemble_n_views` is plain numpy.
@@ -144,12 +145,15 @@ def assemble_n_views(keypoints, pair_matches, pair_masks, min_matches=50):
     return views
 
 
-def two_view_tables(keypoints, descriptors, intrinsic, min_matches=50, max_ratio=0.8, max_distance=0.7, cross_check=True, seed=0,
-                    **relative_pose_options):
+def two_view_tables(keypoints, descriptors, intrinsic=None, min_matches=50, max_ratio=0.8, max_distance=0.7, cross_check=True, seed=0,
+                    return_configs=False, **ransac_options):
     """main.py:98-247 without COLMAP: match_descriptors over every pair -> the < min_matches filter -> ONE
     ls2fm.pose.relative_pose call over all surviving pairs for the inlier masks (the call main.py:209-213 makes per pair) ->
     assemble_n_views.  keypoints: list of [n_v,2] pixel arrays; descriptors: list of uint8 [n_v,128]; intrinsic: K [3,3] or
-    (fx, fy, cx, cy), one camera for all views (main.py's single_camera).  -> the list np.save would write as n_views.npy."""
+    (fx, fy, cx, cy), one camera for all views (main.py's single_camera), or None when there is no calibration: the masks then
+    come from ONE ls2fm.pose.fundamental_matrix call.  **ransac_options go to that estimator.  -> the list np.save would write
+    as n_views.npy.  return_configs=True: (that list, config int32 numpy [n (n - 1) / 2]) with ls2fm.pose.two_view_geometry's
+    verdict of every pair in main.py's order (DEGENERATE for the filtered ones), from one more pass over the surviving pairs."""
     from . import pose
     n = len(keypoints)
     if len(descriptors) != n:
@@ -160,12 +164,20 @@ def two_view_tables(keypoints, descriptors, intrinsic, min_matches=50, max_ratio
     kps = [torch.as_tensor(np.asarray(k.cpu() if torch.is_tensor(k) else k), dtype=torch.float64).reshape(-1, 2).to(dev) for k in keypoints]
     keep = [p for p in range(len(matches)) if matches[p].shape[0] >= min_matches]
     masks = [np.zeros((0,), dtype=bool) for _ in matches]
+    configs = np.full(len(matches), pose.DEGENERATE, dtype=np.int32)
     if keep:
         uv0 = [kps[pairs[p, 0]][matches[p][:, 0]] for p in keep]
         uv1 = [kps[pairs[p, 1]][matches[p][:, 1]] for p in keep]
-        out = pose.relative_pose(uv0, uv1, intrinsic, intrinsic, seed=seed, **relative_pose_options)
+        if intrinsic is None:
+            out = pose.fundamental_matrix(uv0, uv1, seed=seed, **ransac_options)
+        else:
+            out = pose.relative_pose(uv0, uv1, intrinsic, intrinsic, seed=seed, **ransac_options)
         inl = out["inliers"].cpu().numpy()
         ps = out["pair_start"].cpu().numpy()
         for q, p in enumerate(keep):
             masks[p] = inl[ps[q]:ps[q + 1]].copy()
-    return assemble_n_views(keypoints, [m.cpu().numpy() for m in matches], masks, min_matches)
+        if return_configs:
+            geo = pose.two_view_geometry(uv0, uv1, intrinsic, intrinsic, seed=seed)
+            configs[keep] = geo["config"].cpu().numpy()
+    tables = assemble_n_views(keypoints, [m.cpu().numpy() for m in matches], masks, min_matches)
+    return (tables, configs) if return_configs else tables

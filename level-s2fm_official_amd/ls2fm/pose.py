@@ -6,8 +6,10 @@ for one or MANY views in one call of ls2fm_absolute_pose (csrc/absolute_pose.hip
 LevelS2fM.train (pipelines/LevelS2fM.py:247-281) forms every candidate view's pnp score from one call instead of one host round
 trip per view.  `refine_pose` is pose_refinement alone (ls2fm_pose_refine), `p3p` the minimal solver alone.  `relative_pose`
 runs LO-RANSAC over Nister's five-point algorithm and recovers [R | t] for one or many view pairs (ls2fm_relative_pose,
-csrc/relative_pose.hip); `five_point` is the minimal solver alone and `triangulate` the batched two-view DLT.  Every rule is
-stated in include/ls2fm.h; tests/pose_restate.py and tests/relpose_restate.py repeat them in numpy.
+csrc/relative_pose.hip); `five_point` is the minimal solver alone and `triangulate` the batched two-view DLT.
+`fundamental_matrix` and `homography` are the uncalibrated LO-RANSACs in pixels (csrc/two_view.hip; `seven_point` and
+`four_point_homography` their minimal solvers) and `two_view_geometry` COLMAP's verdict over their inlier counts.  Every rule is
+stated in include/ls2fm.h; tests/pose_restate.py, tests/relpose_restate.py and tests/twoview_restate.py repeat them in numpy.
 
 Poses are world-to-camera [3,4] = [R | t], fp64; intrinsics per view (fx, fy, cx, cy).  The defaults are pycolmap 0.3.0's
 absolute_pose_estimation defaults as we read them.  There is no CPU path: CPU tensors, a missing device or a missing library raise.
@@ -249,3 +251,146 @@ def triangulate(P0, P1, uv0, uv1, pair_start=None):
     check(_lib.load().ls2fm_triangulate(ptr(a), ptr(b), ptr(uv0), ptr(uv1), ptr(ps), P, uv0.shape[0], ptr(X), stream_ptr()),
           "ls2fm_triangulate")
     return X
+
+
+# ------------------------------------------------------------------------------------------------- uncalibrated two-view geometry
+# COLMAP's TwoViewGeometry::ConfigurationType values
+DEGENERATE, CALIBRATED, UNCALIBRATED, PLANAR_OR_PANORAMIC = 1, 2, 3, 6
+
+
+def _minimal(x1, x2, k, n_sol, symbol, name):
+    a = torch.as_tensor(x1)
+    b = torch.as_tensor(x2)
+    _device(a, b)
+    a = a.to(torch.float64).reshape(-1, k, 2).contiguous()
+    b = b.to(torch.float64).reshape(-1, k, 2).contiguous()
+    if a.shape != b.shape:
+        raise ValueError(f"ls2fm.pose.{name}: uv0 {tuple(a.shape)} against uv1 {tuple(b.shape)}")
+    m = a.shape[0]
+    out = torch.empty(m, n_sol, 3, 3, dtype=torch.float64, device=a.device)
+    n = torch.empty(m, dtype=torch.int32, device=a.device)
+    check(getattr(_lib.load(), symbol)(ptr(a), ptr(b), m, ptr(out), ptr(n), stream_ptr()), symbol)
+    return out, n
+
+
+def seven_point(uv0, uv1):
+    """seven-point fundamental matrices of m minimal problems: pixels uv0, uv1 [m,7,2] (device) -> (F [m,3,3,3] fp64 with
+    x2h^T F x1h = 0, unit Frobenius norm, kept ones first and zero beyond; n_solutions int32 [m])"""
+    return _minimal(uv0, uv1, 7, 3, "ls2fm_seven_point", "seven_point")
+
+
+def four_point_homography(uv0, uv1):
+    """four-point DLT homographies of m minimal problems: pixels uv0, uv1 [m,4,2] (device) -> (H [m,3,3] fp64 with x2h ~ H x1h,
+    unit Frobenius norm, zero where there is none; n_solutions int32 [m], 0 or 1)"""
+    H, n = _minimal(uv0, uv1, 4, 1, "ls2fm_four_point_homography", "four_point_homography")
+    return H[:, 0], n
+
+
+def _two_view_ransac(symbol, key, uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio, min_num_trials, max_num_trials, seed):
+    P = ps.numel() - 1
+    dev = uv0.device
+    lib = _lib.load()
+    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
+                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 0)
+    ws_bytes = getattr(lib, symbol + "_workspace_bytes")(P, uv0.shape[0])
+    if ws_bytes < 0:
+        check(int(ws_bytes), symbol + "_workspace_bytes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    M = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
+    inl = torch.empty(uv0.shape[0], dtype=torch.uint8, device=dev)
+    num, trials, best, succ = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
+    check(getattr(lib, symbol)(ptr(uv0), ptr(uv1), ptr(ps), P, ctypes.byref(opts), ptr(M), ptr(inl), ptr(num), ptr(trials), ptr(best),
+                               ptr(succ), ptr(ws), stream_ptr()), symbol)
+    return {key: M, "inliers": inl.view(torch.bool), "num_inliers": num, "trials": trials, "best_trial": best,
+            "success": succ.bool(), "pair_start": ps}
+
+
+def fundamental_matrix(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.25, min_num_trials=100,
+                       max_num_trials=10000, seed=0):
+    """LO-RANSAC fundamental matrix of P view pairs in one call (ls2fm_fundamental_matrix): seven-point hypotheses scored by the
+    squared Sampson error in pixels, no intrinsics.  uv0 / uv1 and pair_start as `relative_pose`; the defaults are COLMAP's
+    two-view geometry RANSAC options.  -> dict(F [P,3,3] fp64 with x2h^T F x1h = 0 (zero for a failing pair), inliers bool [n],
+    num_inliers, trials, best_trial, success (num_inliers >= 8), pair_start)"""
+    uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
+    return _two_view_ransac("ls2fm_fundamental_matrix", "F", uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio,
+                            min_num_trials, max_num_trials, seed)
+
+
+def homography(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.25, min_num_trials=100,
+               max_num_trials=10000, seed=0):
+    """LO-RANSAC homography of P view pairs in one call (ls2fm_homography): four-point DLT hypotheses scored by the squared
+    forward transfer error |pi(H x1h) - x2|^2 in pixels.  Arguments as `fundamental_matrix`.  -> dict(H [P,3,3] fp64 with
+    x2h ~ H x1h (zero for a failing pair), inliers, num_inliers, trials, best_trial, success (num_inliers >= 4), pair_start)"""
+    uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
+    return _two_view_ransac("ls2fm_homography", "H", uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio, min_num_trials,
+                            max_num_trials, seed)
+
+
+def two_view_config(nE, okE, nF, okF, nH, min_num_inliers=15, min_E_F_inlier_ratio=0.95, max_H_inlier_ratio=0.8):
+    """The verdict of `two_view_geometry` from the per-pair inlier counts and success flags (integer / bool tensors on any
+    device; nE / okE None: no calibration) -> (config int32, choice int64: 0 = E's, 1 = F's, 2 = H's inlier set, -1 = none).
+    Torch ops only: nothing is read back."""
+    nF = torch.as_tensor(nF).to(torch.int64)
+    nH = torch.as_tensor(nH, device=nF.device).to(torch.int64)
+    okF = torch.as_tensor(okF, device=nF.device).bool()
+    uncal = okF & (nF >= min_num_inliers)
+    if nE is None:
+        cal = torch.zeros_like(uncal)
+        nE = torch.zeros_like(nF)
+    else:
+        nE = torch.as_tensor(nE, device=nF.device).to(torch.int64)
+        okE = torch.as_tensor(okE, device=nF.device).bool()
+        # nE / nF > ratio with nF = 0 is +inf or NaN in COLMAP's doubles: true only for nE > 0
+        ratio = nE.double() / nF.double()
+        cal = okE & (ratio > min_E_F_inlier_ratio) & (nE >= min_num_inliers)
+    n_best = torch.where(cal, nE, nF)
+    live = cal | uncal
+    planar = live & (nH.double() / n_best.double() > max_H_inlier_ratio)
+    config = torch.full_like(nF, DEGENERATE)
+    config = torch.where(uncal, torch.full_like(nF, UNCALIBRATED), config)
+    config = torch.where(cal, torch.full_like(nF, CALIBRATED), config)
+    config = torch.where(planar, torch.full_like(nF, PLANAR_OR_PANORAMIC), config)
+    choice = torch.where(cal, torch.zeros_like(nF), torch.ones_like(nF))
+    choice = torch.where(planar & (nH > n_best), torch.full_like(nF, 2), choice)
+    choice = torch.where(live, choice, torch.full_like(nF, -1))
+    return config.to(torch.int32), choice
+
+
+def two_view_geometry(uv0, uv1, intr0=None, intr1=None, pair_start=None, min_num_inliers=15, min_E_F_inlier_ratio=0.95,
+                      max_H_inlier_ratio=0.8, **ransac):
+    """COLMAP's two-view geometry verdict of P view pairs: ONE `fundamental_matrix` call, ONE `homography` call and, when
+    intr0 / intr1 are given, ONE `relative_pose` call over all pairs, then a few integer comparisons per pair on the device
+    (`two_view_config`; no host read).  uv0 / uv1 / pair_start / intrinsics as `relative_pose`; **ransac (max_error_px,
+    confidence, min_inlier_ratio, min_num_trials, max_num_trials, seed) goes to all three estimators, default COLMAP's two-view
+    options (max_error_px 4, confidence 0.999, min_inlier_ratio 0.25, trials 100 - 10 000).
+
+    The rules are COLMAP's EstimateCalibrated / EstimateUncalibrated, with nE, nF, nH the inlier counts:
+      CALIBRATED           E succeeded, nE / nF > min_E_F_inlier_ratio and nE >= min_num_inliers (n_best = nE, E's inliers);
+      UNCALIBRATED         otherwise, F succeeded and nF >= min_num_inliers (n_best = nF, F's inliers);
+      DEGENERATE           otherwise (all-false inliers);
+      PLANAR_OR_PANORAMIC  a non-degenerate pair with nH / n_best > max_H_inlier_ratio; it takes H's inliers when nH > n_best.
+    -> dict(config int32 [P] (the module constants DEGENERATE = 1, CALIBRATED = 2, UNCALIBRATED = 3, PLANAR_OR_PANORAMIC = 6,
+    COLMAP's values), F, H, E [P,3,3] (E None without intrinsics), inliers bool [n] of the chosen model, num_inliers int32 [P],
+    pair_start)"""
+    if (intr0 is None) != (intr1 is None):
+        raise ValueError("ls2fm.pose.two_view_geometry: intr0 and intr1 go together (both or neither)")
+    unknown = set(ransac) - {"max_error_px", "confidence", "min_inlier_ratio", "min_num_trials", "max_num_trials", "seed"}
+    if unknown:
+        raise TypeError(f"ls2fm.pose.two_view_geometry: unexpected options {sorted(unknown)}")
+    uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
+    opt = dict(max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.25, min_num_trials=100, max_num_trials=10000, seed=0)
+    opt.update(ransac)
+    f = fundamental_matrix(uv0, uv1, ps, **opt)
+    h = homography(uv0, uv1, ps, **opt)
+    e = relative_pose(uv0, uv1, intr0, intr1, ps, **opt) if intr0 is not None else None
+    config, choice = two_view_config(e["num_inliers"] if e else None, e["success"] if e else None, f["num_inliers"], f["success"],
+                                     h["num_inliers"], min_num_inliers, min_E_F_inlier_ratio, max_H_inlier_ratio)
+    P = ps.numel() - 1
+    # the pair of each correspondence, then its chosen model's mask
+    pair_of = torch.repeat_interleave(torch.arange(P, device=uv0.device), (ps[1:] - ps[:-1]).to(torch.int64), output_size=uv0.shape[0])
+    pick = choice[pair_of]
+    inl = (pick == 1) & f["inliers"] | (pick == 2) & h["inliers"]
+    if e:
+        inl = inl | (pick == 0) & e["inliers"]
+    return dict(config=config, F=f["F"], H=h["H"], E=e["E"] if e else None, inliers=inl,
+                num_inliers=torch.zeros(P, dtype=torch.int32, device=uv0.device).index_add_(0, pair_of, inl.to(torch.int32)), pair_start=ps)

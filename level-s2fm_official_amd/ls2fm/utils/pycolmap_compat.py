@@ -13,6 +13,9 @@ Initialization_Trad.py:81-85) runs ls2fm.pose.relative_pose.  It takes SIMPLE_PI
 reference driver builds for this call -- and raises NotImplementedError for any other model, before any device or shape check;
 ls2fm.pose.relative_pose itself takes general (fx, fy, cx, cy).  Its defaults (max_error_px 4, min_inlier_ratio 0.01, trials
 1000 - 100 000, confidence 0.999) are our reading of pycolmap 0.3.0, unconfirmed as the rest.
+
+fundamental_matrix_estimation and homography_matrix_estimation (no camera: pixels in) run ls2fm.pose.fundamental_matrix and
+ls2fm.pose.homography with the same RANSAC defaults; F has x2h^T F x1h = 0 and H has x2h ~ H x1h for points2D1 -> points2D2.
 """
 from __future__ import annotations
 
@@ -133,3 +136,40 @@ def essential_matrix_estimation(points2D1, points2D2, camera1, camera2, max_erro
     P = r["poses"][0].cpu().numpy()
     return {"success": True, "E": r["E"][0].cpu().numpy(), "qvec": _pose.rotmat_to_qvec(P[:, :3]), "tvec": P[:, 3].copy(),
             "num_inliers": int(r["num_inliers"][0]), "inliers": r["inliers"].cpu().numpy()}
+
+
+def _pixel_pairs(points2D1, points2D2):
+    p0 = np.asarray(points2D1, dtype=np.float64)
+    p1 = np.asarray(points2D2, dtype=np.float64)
+    for name, p in (("points2D1", p0), ("points2D2", p1)):
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"pycolmap_compat: {name} must be [n, 2], got {p.shape}")
+    if p0.shape[0] != p1.shape[0]:
+        raise ValueError(f"pycolmap_compat: {p0.shape[0]} points2D1 against {p1.shape[0]} points2D2")
+    dev = _device()
+    return torch.from_numpy(np.ascontiguousarray(p0)).to(dev), torch.from_numpy(np.ascontiguousarray(p1)).to(dev)
+
+
+def _two_view_answer(r, key):
+    if not bool(r["success"][0]):
+        return {"success": False}
+    return {"success": True, key: r[key][0].cpu().numpy(), "num_inliers": int(r["num_inliers"][0]),
+            "inliers": r["inliers"].cpu().numpy()}
+
+
+def fundamental_matrix_estimation(points2D1, points2D2, max_error_px=4.0, min_inlier_ratio=0.01, min_num_trials=1000,
+                                  max_num_trials=100000, confidence=0.999, seed=0):
+    """-> {success, F, num_inliers, inliers (numpy bool [n])}; {success: False} on failure"""
+    a, b = _pixel_pairs(points2D1, points2D2)
+    return _two_view_answer(_pose.fundamental_matrix(a, b, max_error_px=max_error_px, confidence=confidence,
+                                                     min_inlier_ratio=min_inlier_ratio, min_num_trials=min_num_trials,
+                                                     max_num_trials=max_num_trials, seed=seed), "F")
+
+
+def homography_matrix_estimation(points2D1, points2D2, max_error_px=4.0, min_inlier_ratio=0.01, min_num_trials=1000,
+                                 max_num_trials=100000, confidence=0.999, seed=0):
+    """-> {success, H, num_inliers, inliers (numpy bool [n])}; {success: False} on failure"""
+    a, b = _pixel_pairs(points2D1, points2D2)
+    return _two_view_answer(_pose.homography(a, b, max_error_px=max_error_px, confidence=confidence,
+                                             min_inlier_ratio=min_inlier_ratio, min_num_trials=min_num_trials,
+                                             max_num_trials=max_num_trials, seed=seed), "H")
