@@ -969,6 +969,88 @@ int ls2fm_match_descriptors(const uint8_t* desc, const int32_t* image_start, int
                             int32_t* best, int32_t* best_j, int32_t* second, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SIFT feature extraction (csrc/sift.hip; additions, the library stays ABI 13 -- its ABI number is pinned by tests that hold for
+ * every addition so far): what `colmap feature_extractor` writes into its `keypoints` and `descriptors` tables
+ * (preparation/main.py:91) -- VLFeat-style DoG SIFT with COLMAP's default options, restated from the published algorithm --
+ * for all views of a call.  tests/sift_restate.py repeats every rule in numpy (float32 and float64); no bit parity with COLMAP or
+ * OpenCV is claimed.  Not restated: affine shape, DSP-SIFT, guided matching.
+ *
+ *   input       one grey image per view, float32 in [0, 1], H x W >= 16 x 16 and <= 8192 x 8192, sizes free inside one call;
+ *               view v starts at pixels[image_offset[v]], rows contiguous.  (uint8 / 255 and RGB by Rec.709 weights
+ *               0.2126 / 0.7152 / 0.0722 are ls2fm.features' host-side conversions.)
+ *   scale space first_octave -1 (default): the base image is the input up-sampled 2x, out(2y, 2x) = in(y, x), odd columns the mean
+ *               of the two neighbours, then odd rows likewise, the last row and column repeated; 0: the input itself.
+ *               octave_resolution S = 3 (other values: LS2FM_ERR_UNSUPPORTED); levels s = -1 .. S + 1 (6 Gaussian, 5 DoG) with
+ *               blur sigma_s = sigma_0 2^(s/S), sigma_0 = 1.6 * 2^(1/S), in octave pixels; the input's nominal blur is 0.5
+ *               (1.0 after the up-sampling).  Level -1 of the first octave is the base blurred by sqrt(sigma_-1^2 - nominal^2),
+ *               every further level the previous one blurred by sqrt(sigma_s^2 - sigma_(s-1)^2): separable, taps
+ *               exp(-k^2 / 2 sigma^2) for |k| <= ceil(4 sigma), normalised in double and rounded to float once, rows then
+ *               columns, edge replication, taps summed from -r to r with one rounded multiply and one rounded add each.
+ *               DoG d = level d + 1 - level d  (d = 0 .. 4, its scale s = d - 1).
+ *               The next octave (at most num_octaves = 4, fewer when a side would drop below 8) is every second pixel
+ *               (0, 2, ...; floor(w / 2) of them) of the level whose blur is twice the first level's: the S-th level above the
+ *               first, s = S - 1, so the new first level needs no further blur.
+ *   detection   a candidate is a strict 3 x 3 x 3 extremum of the DoG (d = 1 .. 3, 1 <= x <= w - 2, 1 <= y <= h - 2) with
+ *               |v| > 0.8 peak_threshold (default 0.02 / S).  At most 5 rounds of the 3-D quadratic fit (central differences,
+ *               offset b = -H^-1 g by the adjugate, b = 0 when det H = 0): after a fit the cell moves by one pixel along x
+ *               (y) when b exceeds 0.6 in magnitude and the step stays in 1 .. w - 2 (1 .. h - 2); the fifth fit is used where
+ *               it stands.  Accepted when |b_x|, |b_y|, |b_s| < 1.5; |v + g.b / 2| > peak_threshold; Dxx Dyy - Dxy^2 > 0 and
+ *               (Dxx + Dyy)^2 r < (r + 1)^2 (Dxx Dyy - Dxy^2) with r = edge_threshold (default 10); 0 <= x <= w - 1 and
+ *               0 <= y <= h - 1; and the nearest level floor(s + 1/2) is one of 0 .. S - 1 (the refined scale is inside the
+ *               octave).
+ *   orientation at the nearest level; gradients by central differences on 1 .. w - 2 / 1 .. h - 2; window exp(-r^2 / 2 sw^2) with
+ *               sw = 1.5 sigma, support W = max(floor(3 sw), 1) pixels around the nearest pixel, samples with
+ *               r^2 >= W^2 + 0.6 skipped; 36 bins, each sample split linearly between the two nearest bin centres; six
+ *               circular passes of (h[i-1] + h[i] + h[i+1]) / 3; peaks h[i] > 0.8 max, > both neighbours, refined by the
+ *               parabola; the first max_num_orientations (default 2, at most 2) in bin order.  upright != 0: one row, angle 0.
+ *   descriptor  4 x 4 spatial bins of width 3 sigma, 8 orientation bins, Gaussian window of 2 bins, support
+ *               floor(sqrt(2) * 3 sigma * 5 / 2 + 1/2), trilinear accumulation; L2-normalise, clamp at 0.2, L2-normalise;
+ *               then LS2FM_SIFT_L1_ROOT (COLMAP's default: v / sum v, square root) or LS2FM_SIFT_L2; byte = min(255,
+ *               floor(512 v + 1/2)).  Stored in the UBC bin order COLMAP stores: VLFeat's index 8 (4 by + bx) + t goes to
+ *               8 (4 by + bx) + (8 - t) mod 8.  Histogram bins (here and in the orientation step) are summed exactly, in
+ *               2^-40 fixed point with integer adds, and rounded to float once: no floating-point atomic, no order dependence.
+ *   order, cap  rows of a view in rising (octave, level, y cell, x cell, orientation index), the cell being the extremum's;
+ *               above max_num_features (default 8192, at most LS2FM_MATCH_MAX_DESCRIPTORS) the rows of largest scale are kept,
+ *               ties by that order, and the kept rows stay in that order.  A view's rows depend on its own pixels only: the
+ *               same bits from a rerun, from any batch around it and from any chunking.
+ *   output      keypoints [n_images * max_num_features][4] = x, y, scale, orientation in input pixels with the centre of the
+ *               first pixel at (0.5, 0.5) (COLMAP); descriptors [n_images * max_num_features][128] uint8; the rows of view v
+ *               start at v * max_num_features; counts [n_images].  counts[v] = -1: the view had more than 32768 accepted
+ *               extrema (min(32768, base pixels / 4) for small views) and its rows are not valid.  A constant image gives 0.
+ *   workspace   caller-owned, 256-byte aligned, ls2fm_sift_workspace_bytes; the views of a call are processed in chunks whose
+ *               workspace stays below max_workspace_bytes (0: 2 GiB; a chunk holds at least one view), so the size is bounded
+ *               by the largest chunk, not by the call.  debug_levels (device, n_images must be 1, NULL otherwise): receives the
+ *               Gaussian levels, octave after octave, 6 planes each.  debug_keys (device, NULL otherwise)
+ *               [n_images * max_num_features][2]: per output row the sort key octave << 30 | level << 28 | y cell << 14 | x cell
+ *               and the orientation index.
+ *   refusals    nothing enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL array, n_images < 1, a side below 16, an option outside
+ *               its range; LS2FM_ERR_UNSUPPORTED for a side above 8192, octave_resolution != 3, num_octaves > 4,
+ *               max_num_orientations > 2, max_num_features > LS2FM_MATCH_MAX_DESCRIPTORS; LS2FM_ERR_WORKSPACE for a NULL or
+ *               misaligned workspace.
+ */
+#define LS2FM_SIFT_L1_ROOT 0
+#define LS2FM_SIFT_L2 1
+typedef struct ls2fm_sift_opts {
+    int32_t first_octave;            /* -1 (default) or 0 */
+    int32_t num_octaves;             /* 4 */
+    int32_t octave_resolution;       /* 3 */
+    int32_t max_num_features;        /* 8192 */
+    int32_t max_num_orientations;    /* 2 */
+    int32_t upright;                 /* 0 */
+    int32_t normalization;           /* LS2FM_SIFT_L1_ROOT */
+    int32_t reserved;
+    double peak_threshold;           /* 0.02 / 3 */
+    double edge_threshold;           /* 10 */
+    int64_t max_workspace_bytes;     /* 0: 2 GiB */
+    float* debug_levels;             /* NULL */
+    int32_t* debug_keys;             /* NULL */
+} ls2fm_sift_opts;
+int64_t ls2fm_sift_workspace_bytes(const int32_t* heights, const int32_t* widths, int32_t n_images, const ls2fm_sift_opts* opts);
+int ls2fm_sift_extract(const float* pixels, const int64_t* image_offset, const int32_t* heights, const int32_t* widths, int32_t n_images,
+                       const ls2fm_sift_opts* opts, float* keypoints, uint8_t* descriptors, int32_t* counts, void* workspace,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -104,6 +104,13 @@ class PoseRansacOpts(Structure):
                 ("max_num_trials", c_int64), ("seed", ctypes.c_uint64), ("refine", c_int32)]
 
 
+class SiftOpts(Structure):
+    """ls2fm_sift_opts"""
+    _fields_ = [("first_octave", c_int32), ("num_octaves", c_int32), ("octave_resolution", c_int32), ("max_num_features", c_int32),
+                ("max_num_orientations", c_int32), ("upright", c_int32), ("normalization", c_int32), ("reserved", c_int32),
+                ("peak_threshold", c_double), ("edge_threshold", c_double), ("max_workspace_bytes", c_int64), ("debug_levels", c_void_p), ("debug_keys", c_void_p)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)        -- must list every symbol include/ls2fm.h declares
@@ -201,6 +208,8 @@ _SIGNATURES = {
                                           c_float, c_float, c_float, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P]),
     "ls2fm_match_descriptors_workspace_bytes": (c_int64, [_P, c_int32, _P, c_int32]),
     "ls2fm_match_descriptors": (c_int32, [_P, _P, c_int32, _P, c_int32, c_double, c_double, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_sift_workspace_bytes": (c_int64, [_P, _P, c_int32, POINTER(SiftOpts)]),
+    "ls2fm_sift_extract": (c_int32, [_P, _P, _P, _P, c_int32, POINTER(SiftOpts), _P, _P, _P, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),
