@@ -317,12 +317,17 @@ def extract(image, dtype=np.float64, **options):
     kp = np.array(rows, dtype=dtype).reshape(-1, 4)
     keys = np.array(keys, dtype=np.int64).reshape(-1, 5)
     descs = np.array(descs, dtype=np.uint8).reshape(-1, 128)
-    cap = o["max_num_features"]
-    if len(kp) > cap:
-        order = np.lexsort((np.arange(len(kp)), -kp[:, 2]))        # largest scale first, ties by the output order
-        keep = np.sort(order[:cap])
-        kp, keys, descs = kp[keep], keys[keep], descs[keep]
-    return dict(keypoints=kp, descriptors=descs, keys=keys, levels=octs)
+    return cap_rows(dict(keypoints=kp, descriptors=descs, keys=keys, levels=octs), o["max_num_features"])
+
+
+def cap_rows(result, cap):
+    """the cap, the last step of `extract`: above `cap` rows the largest scales are kept, ties by the output order, order preserved"""
+    kp = result["keypoints"]
+    if len(kp) <= cap:
+        return result
+    order = np.lexsort((np.arange(len(kp)), -kp[:, 2]))
+    keep = np.sort(order[:cap])
+    return dict(keypoints=kp[keep], descriptors=result["descriptors"][keep], keys=result["keys"][keep], levels=result["levels"])
 
 
 def pair_rows(keys_a, keys_b):
@@ -346,3 +351,35 @@ def gaps(a, b):
         scale=float(np.abs(ka[:, 2] - kb[:, 2]).max(initial=0.0)), orientation=float(dth.max(initial=0.0)),
         descriptor=int(np.abs(a["descriptors"][ia].astype(np.int64) - b["descriptors"][ib].astype(np.int64)).max(initial=0)),
         unpaired=max(len(a["keys"]) - len(ia), len(b["keys"]) - len(ib)) / n, paired=len(ia), n_a=len(a["keys"]), n_b=len(b["keys"]))
+
+
+def quarter_turn(keypoints, width):
+    """keypoints of an image [H, width] -> where np.rot90(image) (a quarter turn counter-clockwise, out[i, j] = image[j, width - 1 - i])
+    carries them.  The pixel of row r and column c goes to row width - 1 - c and column r; with x = c + 0.5 and y = r + 0.5 that is
+    (x, y) -> (y, width - x).  A direction (dx, dy) goes to (dy, -dx), and so does the gradient (d out / dx' = d image / dy,
+    d out / dy' = -d image / dx): an angle t measured from +x towards +y becomes t - pi / 2.  Scales stay."""
+    k = np.asarray(keypoints, dtype=np.float64)
+    return np.stack([k[:, 1], width - k[:, 0], k[:, 2], np.mod(k[:, 3] - 0.5 * np.pi, TWO_PI)], axis=1)
+
+
+def quarter_turn_check(kp, desc, kp_turned, desc_turned, width):
+    """rows of an image against the rows of np.rot90(image): every row is mapped through the turn and paired with the nearest
+    turned row in (position, scale), mutually; a pair counts when it lies within half a pixel, a sixth of an octave in scale and
+    0.1 rad (peaks of one histogram are at least two bins, 0.35 rad, apart: a row whose histogram has two peaks above 0.8 keeps
+    the first in BIN order, which a turn by nine bins changes, and such rows do not pair).
+    -> dict(share = pairs / max(rows), paired (indices), x, y, scale, orientation, descriptor: the worst differences over the pairs)"""
+    m, t = quarter_turn(kp, width), np.asarray(kp_turned, dtype=np.float64)
+    n = max(len(m), len(t), 1)
+    if len(m) == 0 or len(t) == 0:
+        return dict(share=0.0, paired=np.zeros(0, dtype=np.int64), x=0.0, y=0.0, scale=0.0, orientation=0.0, descriptor=0)
+    d = np.hypot(m[:, None, 0] - t[None, :, 0], m[:, None, 1] - t[None, :, 1]) + np.abs(m[:, None, 2] - t[None, :, 2])
+    j = d.argmin(axis=1)
+    mutual = d.argmin(axis=0)[j] == np.arange(len(m))
+    dth = np.abs(m[:, 3] - t[j, 3])
+    dth = np.minimum(dth, TWO_PI - dth)
+    ok = mutual & (np.hypot(m[:, 0] - t[j, 0], m[:, 1] - t[j, 1]) < 0.5) & (np.abs(np.log2(m[:, 2] / t[j, 2])) < 1.0 / 6.0) & (dth < 0.1)
+    i = np.nonzero(ok)[0]
+    j = j[i]
+    return dict(share=len(i) / n, paired=i, x=float(np.abs(m[i, 0] - t[j, 0]).max(initial=0.0)), y=float(np.abs(m[i, 1] - t[j, 1]).max(initial=0.0)),
+                scale=float(np.abs(m[i, 2] - t[j, 2]).max(initial=0.0)), orientation=float(dth[i].max(initial=0.0)),
+                descriptor=int(np.abs(np.asarray(desc)[i].astype(np.int64) - np.asarray(desc_turned)[j].astype(np.int64)).max(initial=0)))
