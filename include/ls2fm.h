@@ -1051,6 +1051,76 @@ int ls2fm_sift_extract(const float* pixels, const int64_t* image_offset, const i
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Feature tracks and multi-view triangulation (csrc/tracks.hip; additions, the library stays ABI 13): what the reference keeps in
+ * Point3DSet.add_point3d / Camera.idx2d_to_3d, filled pair by pair with cv2.triangulatePoints (pipelines/Registration_Trad.py:183-215,
+ * Initialization_Trad.py:97), for all views of a call.  tests/tracks_restate.py repeats every rule in numpy.
+ *
+ * ls2fm_track_labels: connected components of the match graph.  Nodes are the key points of all views, node image_start[v] + k for
+ *   key point k of view v (image_start int32 [n_images + 1], rising from 0 to n_nodes: the caller guarantees it); edges int32
+ *   [n_edges][2] are node pairs in any order.  labels int32 [n_nodes]: the smallest node id of the node's component -- the rule and
+ *   the union-find of ls2fm_mesh_components (csrc/union_find.h), so labels do not depend on the order of the edges or on
+ *   duplicates.  n_edges = 0 writes labels[i] = i.  Three launches, nothing read back.
+ *   status int32 [1] (device, may be NULL) is written by the call: 0, or LS2FM_TRACK_EDGE_RANGE when an edge names a node outside
+ *   [0, n_nodes), LS2FM_TRACK_EDGE_IMAGE when both ends of an edge lie in one image (or-ed).  Such an edge is checked on the device
+ *   before anything is read through it and joins nothing: the call never faults; ls2fm.tracks raises on a non-zero status.
+ *   Refused before anything is enqueued (LS2FM_ERR_INVALID_ARGUMENT): a NULL array, n_images < 1, negative counts, n_nodes or
+ *   n_edges >= 2^31.
+ *   From labels to tracks (ls2fm.tracks.build_tracks, device index operations): a track is a component of >= 2 nodes with at most
+ *   one node per image; a component with two nodes in one image is a conflict and is dropped whole (the OpenMVG / hloc rule; COLMAP's
+ *   correspondence graph would keep such a component and split it while triangulating).  Tracks in rising label order, the
+ *   observations of a track in rising node id (so in rising view).
+ *
+ * ls2fm_triangulate_tracks: one robust N-view triangulation per track, all geometry in fp64 in normalised image coordinates.
+ *   poses [n_views][3][4] world-to-camera P = [R | t]; intrinsics [n_views][4] = fx, fy, cx, cy; track t owns the observations
+ *   [track_start[t], track_start[t + 1]) (int32 [n_tracks + 1], rising from 0 to n_obs, at most LS2FM_TRACK_MAX_OBS each);
+ *   obs_view int32 [n_obs]; obs_uv [n_obs][2] pixels.  Of an observation (u, v) of view w and a point X:
+ *     x = (u - cx) / fx, y = (v - cy) / fy;  xc = ((R00 X0 + R01 X1) + R02 X2) + t0, yc and the depth zc likewise;
+ *     e2 = (fx (xc / zc) + cx - u)^2 + (fy (yc / zc) + cy - v)^2;  INLIER when zc > DBL_EPSILON and e2 <= max_error_px^2.
+ *     centre C_k = -((R0k t0 + R1k t1) + R2k t2).  angle(X, w, w') = min(a, pi - a), a = acos of the cosine, clamped to [-1, 1],
+ *     between X - C_w and X - C_w' (COLMAP's CalculateTriangulationAngle).
+ *   hypotheses  every pair i < j of the track's first LS2FM_TRACK_HYP_OBS observations, numbered lexicographically
+ *               q = i (2 m - i - 1) / 2 + (j - i - 1), m = min(n, 64): ls2fm_triangulate's 4 x 4 one-sided-Jacobi DLT of the two
+ *               normalised observations, X = h[0..2] / h[3].  Dropped when X is not finite, when its depth in either view is <=
+ *               DBL_EPSILON, or when angle(X, view i, view j) is not >= min_tri_angle (a NaN angle drops it).
+ *   scoring     the inliers of X among ALL observations of the track, an exact integer.  A count of 0 does not compete.
+ *   selection   the 64-bit max of count << 32 | (2^32 - 1 - q): the most inliers, then the lowest pair (integer atomics only).
+ *   local optimisation  from the best X with count c, at most 10 times while c >= 2: N = sum over the inliers of r r^T for their two
+ *               rows x P[2] - P[0] and y P[2] - P[1], each scaled to unit length; the observations are dealt to 8 lanes (number k of
+ *               the track to lane k mod 8), a lane adds its own in rising order, and the lanes are summed by the butterfly 4, 2, 1:
+ *               a fixed order.  The eigenvector of N's smallest eigenvalue by cyclic Jacobi (relative_pose's routine at size 4; the
+ *               lower index among equal eigenvalues), X' = v[0..2] / v[3].  Stop when X' is not finite or counts fewer than c;
+ *               otherwise X = X', c = its count, and stop when no observation changed sides.
+ *   acceptance  success = c >= 2, every inlier in front (the inlier rule holds it) and the LARGEST angle(X, ., .) over the pairs of
+ *               the first 64 inliers >= min_tri_angle.
+ *   outputs     X [n_tracks][3] (zero without success), inliers uint8 [n_obs] and num_inliers (of the final X, also without success),
+ *               success, tri_angle (that largest angle in radians; 0 below two inliers), mean_error_px (mean of sqrt(e2) over the
+ *               inliers; 0 without one), best_pair (q of the selected hypothesis, -1 when none survived; then everything is 0).
+ *               Every bit of a track's outputs depends on the track's own observations, their views and the options only.
+ *   deviations  COLMAP's estimator scores by angular error and samples long tracks at random; this one scores by pixel error and
+ *               is exhaustive over the first 64 observations, so it is deterministic without a seed.
+ *   status int32 [1] (device, may be NULL): 0, or LS2FM_TRACK_BAD_START (a track whose extent is not inside [0, n_obs], runs
+ *   backwards or exceeds LS2FM_TRACK_MAX_OBS: treated as empty), LS2FM_TRACK_BAD_VIEW (an obs_view outside [0, n_views): never an
+ *   inlier, its hypotheses dropped), or-ed.  Checked on the device before use: the call never faults.
+ *   Nothing is read back and the launch shapes depend on the counts only: the call can be captured into a graph.
+ *   Refused before any launch: LS2FM_ERR_INVALID_ARGUMENT for a NULL array, n_views < 1, negative counts, n_tracks or n_obs >= 2^31,
+ *   max_error_px not finite or <= 0, min_tri_angle_deg not in [0, 90]; LS2FM_ERR_WORKSPACE for a NULL workspace.
+ */
+#define LS2FM_TRACK_HYP_OBS 64
+#define LS2FM_TRACK_MAX_OBS 4096
+#define LS2FM_TRACK_EDGE_RANGE 1
+#define LS2FM_TRACK_EDGE_IMAGE 2
+#define LS2FM_TRACK_BAD_START 1
+#define LS2FM_TRACK_BAD_VIEW 2
+int ls2fm_track_labels(const int32_t* image_start, int32_t n_images, int64_t n_nodes, const int32_t* edges, int64_t n_edges,
+                       int32_t* labels, int32_t* status, void* stream);
+int64_t ls2fm_triangulate_tracks_workspace_bytes(int64_t n_tracks, int32_t n_views);
+int ls2fm_triangulate_tracks(const double* poses, const double* intrinsics, int32_t n_views, const int32_t* track_start,
+                             int64_t n_tracks, const int32_t* obs_view, const double* obs_uv, int64_t n_obs, double max_error_px,
+                             double min_tri_angle_deg, double* X, uint8_t* inliers, int32_t* num_inliers, int32_t* success,
+                             double* tri_angle, double* mean_error_px, int32_t* best_pair, int32_t* status, void* workspace,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

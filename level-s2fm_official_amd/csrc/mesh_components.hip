@@ -24,8 +24,11 @@
 //   lc_emit_verts   kept vertices in index order; their new ids
 //   lc_emit_faces   kept faces in order, renumbered
 #include "ls2fm_device.h"
+#include "union_find.h"
 
 namespace {
+
+using namespace union_find;
 
 constexpr int kThreads = 256;
 constexpr int kPer = 8;
@@ -39,42 +42,6 @@ struct LcSlots {
     int32_t win_face;                   // lowest first face among the components holding q_max
     int32_t pad;
 };
-
-__device__ __forceinline__ int32_t ld_parent(const int32_t* parent, int32_t x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool cas_parent(int32_t* parent, int32_t x, int32_t expected, int32_t desired) {
-    return __hip_atomic_compare_exchange_strong(parent + x, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x; halves the path on the way (g, the grandparent, is an ancestor of x, so pointing x at it keeps the forest; a failed
-// exchange means x already points higher)
-__device__ __forceinline__ int32_t find_root(int32_t* parent, int32_t x) {
-    for (;;) {
-        const int32_t p = ld_parent(parent, x);
-        if (p == x) return x;
-        const int32_t g = ld_parent(parent, p);
-        if (g == p) return p;
-        cas_parent(parent, x, p, g);
-        x = g;
-    }
-}
-
-__device__ __forceinline__ void unite(int32_t* parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        if (cas_parent(parent, b, b, a)) return;           // the larger root goes under the smaller one
-    }
-}
 
 __global__ void __launch_bounds__(kThreads)
 cc_init(int32_t* __restrict__ parent, uint32_t n_verts, unsigned long long* __restrict__ comp_q, int32_t* __restrict__ comp_first,

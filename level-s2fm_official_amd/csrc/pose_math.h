@@ -1,6 +1,6 @@
-// Small fp64 routines shared by relative_pose.hip and two_view.hip: the LDS column view of a solver's run-time-indexed state, the
-// unit-norm-and-sign rule of a 3 x 3 model, the squared Sampson error, the cyclic Jacobi of a symmetric 9 x 9 and the one-sided
-// Jacobi of a 3 x 3.
+// Small fp64 routines shared by relative_pose.hip, two_view.hip and tracks.hip: the LDS column view of a solver's run-time-indexed state, the
+// unit-norm-and-sign rule of a 3 x 3 model, the squared Sampson error, the cyclic Jacobi of a symmetric 9 x 9 (and 4 x 4), the one-sided
+// Jacobi of a 3 x 3 and the two-view DLT (also used by tracks.hip).
 // Every routine is a fixed sequence of fp64 operations (the library is built with -ffp-contract=off): the same bits on the host,
 // on the device and in whichever file includes it.
 #pragma once
@@ -139,6 +139,109 @@ HD inline int eigen_rank9(const double (&a)[45], int k) {
         rank += (ej < ek || (ej == ek && j < k)) ? 1 : 0;
     }
     return rank;
+}
+
+// ----------------------------------------------------------------------------------------------------------- triangulation
+// the 4 x 4 DLT of cv2.triangulatePoints (rows x P[2] - P[0], y P[2] - P[1] of both views); right singular vector of the smallest
+// singular value by one-sided Jacobi on A; unit norm, w >= 0
+HD inline void triangulate_dlt(const double* P0, const double* P1, double u0, double v0, double u1, double v1, double (&X)[4]) {
+    double a[4][4], V[4][4];          // a[c][r]: column c of A
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        a[c][0] = u0 * P0[8 + c] - P0[c];
+        a[c][1] = v0 * P0[8 + c] - P0[4 + c];
+        a[c][2] = u1 * P1[8 + c] - P1[c];
+        a[c][3] = v1 * P1[8 + c] - P1[4 + c];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) V[c][r] = c == r ? 1.0 : 0.0;       // V[c]: column c of V
+    }
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const double al = ((a[p][0] * a[p][0] + a[p][1] * a[p][1]) + a[p][2] * a[p][2]) + a[p][3] * a[p][3];
+                const double be = ((a[q][0] * a[q][0] + a[q][1] * a[q][1]) + a[q][2] * a[q][2]) + a[q][3] * a[q][3];
+                const double ga = ((a[p][0] * a[q][0] + a[p][1] * a[q][1]) + a[p][2] * a[q][2]) + a[p][3] * a[q][3];
+                if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double ap = a[p][r], aq = a[q][r];
+                    a[p][r] = c * ap - s * aq;
+                    a[q][r] = s * ap + c * aq;
+                    const double vp = V[p][r], vq = V[q][r];
+                    V[p][r] = c * vp - s * vq;
+                    V[q][r] = s * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double best = 0.0;
+    int bi = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double n = ((a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2]) + a[c][3] * a[c][3];
+        if (c == 0 || n < best) { best = n; bi = c; }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[r] = bi == 0 ? V[0][r] : (bi == 1 ? V[1][r] : (bi == 2 ? V[2][r] : V[3][r]));
+    const double nrm = sqrt(((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]) + X[3] * X[3]);
+    const double s = (X[3] < 0.0 ? -1.0 : 1.0) / nrm;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X[r] = X[r] * s;
+}
+
+// ------------------------------------------------------------------------------------------------- symmetric Jacobi, 4 x 4
+// jacobi9's rules at size 4, every lane holding the whole problem: a = upper triangle of the symmetric 4 x 4, row-major (00 01 02
+// 03 11 12 13 22 23 33); on return its diagonal entries are the eigenvalues and V[k] the eigenvector of eigenvalue k
+constexpr int sidx4(int i, int j) { return i <= j ? i * 4 - (i * (i - 1)) / 2 + (j - i) : j * 4 - (j * (j - 1)) / 2 + (i - j); }
+
+HD inline void jacobi4(double (&a)[10], double (&V)[4][4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) V[k][r] = k == r ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        double off = 0.0, dia = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            dia += a[sidx4(i, i)] * a[sidx4(i, i)];
+#pragma unroll
+            for (int j = i + 1; j < 4; ++j) off += a[sidx4(i, j)] * a[sidx4(i, j)];
+        }
+        if (!(off > 1e-30 * dia)) break;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = a[sidx4(p, q)];
+                if (apq == 0.0) continue;
+                const double theta = (a[sidx4(q, q)] - a[sidx4(p, p)]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (k == p || k == q) continue;
+                    const double akp = a[sidx4(k, p)], akq = a[sidx4(k, q)];
+                    a[sidx4(k, p)] = c * akp - s * akq;
+                    a[sidx4(k, q)] = s * akp + c * akq;
+                }
+                a[sidx4(p, p)] = a[sidx4(p, p)] - t * apq;
+                a[sidx4(q, q)] = a[sidx4(q, q)] + t * apq;
+                a[sidx4(p, q)] = 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double vp = V[p][r], vq = V[q][r];
+                    V[p][r] = c * vp - s * vq;
+                    V[q][r] = s * vp + c * vq;
+                }
+            }
+    }
 }
 
 }  // namespace pose_math

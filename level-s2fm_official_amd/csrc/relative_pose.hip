@@ -398,61 +398,6 @@ HD inline bool is_inlier(const double* E, double x1, double y1, double x2, doubl
     return sampson2(E, x1, y1, x2, y2) <= thr2;       // NaN (0 / 0) is not an inlier
 }
 
-// ----------------------------------------------------------------------------------------------------------- triangulation
-// the 4 x 4 DLT of cv2.triangulatePoints (rows x P[2] - P[0], y P[2] - P[1] of both views); right singular vector of the smallest
-// singular value by one-sided Jacobi on A; unit norm, w >= 0
-HD inline void triangulate_dlt(const double* P0, const double* P1, double u0, double v0, double u1, double v1, double (&X)[4]) {
-    double a[4][4], V[4][4];          // a[c][r]: column c of A
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        a[c][0] = u0 * P0[8 + c] - P0[c];
-        a[c][1] = v0 * P0[8 + c] - P0[4 + c];
-        a[c][2] = u1 * P1[8 + c] - P1[c];
-        a[c][3] = v1 * P1[8 + c] - P1[4 + c];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) V[c][r] = c == r ? 1.0 : 0.0;       // V[c]: column c of V
-    }
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double al = ((a[p][0] * a[p][0] + a[p][1] * a[p][1]) + a[p][2] * a[p][2]) + a[p][3] * a[p][3];
-                const double be = ((a[q][0] * a[q][0] + a[q][1] * a[q][1]) + a[q][2] * a[q][2]) + a[q][3] * a[q][3];
-                const double ga = ((a[p][0] * a[q][0] + a[p][1] * a[q][1]) + a[p][2] * a[q][2]) + a[p][3] * a[q][3];
-                if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
-                rotated = true;
-                const double zeta = (be - al) / (2.0 * ga);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double ap = a[p][r], aq = a[q][r];
-                    a[p][r] = c * ap - s * aq;
-                    a[q][r] = s * ap + c * aq;
-                    const double vp = V[p][r], vq = V[q][r];
-                    V[p][r] = c * vp - s * vq;
-                    V[q][r] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    double best = 0.0;
-    int bi = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const double n = ((a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2]) + a[c][3] * a[c][3];
-        if (c == 0 || n < best) { best = n; bi = c; }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X[r] = bi == 0 ? V[0][r] : (bi == 1 ? V[1][r] : (bi == 2 ? V[2][r] : V[3][r]));
-    const double nrm = sqrt(((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]) + X[3] * X[3]);
-    const double s = (X[3] < 0.0 ? -1.0 : 1.0) / nrm;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X[r] = X[r] * s;
-}
-
 // ------------------------------------------------------------------------------------------------------ pose from E (COLMAP)
 // E = U diag(s, s, 0) V^T by one-sided Jacobi on E's columns; U, V made proper; R1 = U W V^T, R2 = U W^T V^T, t = U col 2.
 // cand[k] = [R | t] for (R1, t), (R2, t), (R1, -t), (R2, -t)

@@ -197,6 +197,10 @@ _SIGNATURES = {
     "ls2fm_relative_pose": (c_int32, [_P, _P, _P, c_int32, _P, _P, POINTER(PoseRansacOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_triangulate": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, _P, _P]),
     "ls2fm_seven_point": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
+    "ls2fm_track_labels": (c_int32, [_P, c_int32, c_int64, _P, c_int64, _P, _P, _P]),
+    "ls2fm_triangulate_tracks_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "ls2fm_triangulate_tracks": (c_int32, [_P, _P, c_int32, _P, c_int64, _P, _P, c_int64, c_double, c_double, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P]),
     "ls2fm_four_point_homography": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
     "ls2fm_fundamental_matrix_workspace_bytes": (c_int64, [c_int32, c_int64]),
     "ls2fm_homography_workspace_bytes": (c_int64, [c_int32, c_int64]),
