@@ -36,9 +36,11 @@ def bfs_labels(n, edges):
     return lab
 
 
-@pytest.mark.parametrize("graph", ["random", "path", "star"])
+@pytest.mark.parametrize("graph", ["random", "path", "star", "contended", "path_4097_descending"])
 def test_restated_labels_against_bfs(graph):
-    image_start, edges = {"random": lambda: S.random_graph(1), "path": S.path_graph, "star": S.star_graph}[graph]()
+    image_start, edges = {"random": lambda: S.random_graph(1), "path": S.path_graph, "star": S.star_graph,
+                          "contended": lambda: S.contended_graph(3),
+                          "path_4097_descending": lambda: (S.path_graph(4097)[0], S.path_graph(4097)[1][::-1])}[graph]()
     want = bfs_labels(int(image_start[-1]), edges)
     got = R.track_labels(image_start, edges)
     assert np.array_equal(got, want)
@@ -180,11 +182,31 @@ def test_jacobi_routes_agree_on_a_known_matrix():
     assert min(np.abs(va - vb).max(), np.abs(va + vb).max()) < 1e-9
 
 
+def _restate(sc, **kw):
+    return R.triangulate_tracks(sc["poses"], sc["intr"], sc["track_start"], sc["obs_view"], sc["obs_uv"], **kw)
+
+
+TRACES = {}                 # run -> the local optimisation's trace of every track, filled by the two fixtures below
+
+
 @pytest.fixture(scope="module")
 def restated():
     out = {}
     for name, sc in S.gpu_scenes().items():
-        out[name] = (sc,) + R.triangulate_tracks(sc["poses"], sc["intr"], sc["track_start"], sc["obs_view"], sc["obs_uv"], margins=True)
+        TRACES[name] = []
+        out[name] = (sc,) + _restate(sc, margins=True, trace=TRACES[name])
+    return out
+
+
+@pytest.fixture(scope="module")
+def restated_more():
+    """(scene name, option number) -> (scene, options, result, margins) of every run tests/test_hip_tracks.py makes of
+    S.more_gpu_scenes(), restated once"""
+    out = {}
+    for name, (sc, options) in S.more_gpu_scenes().items():
+        for i, opt in enumerate(options):
+            TRACES[name, i] = []
+            out[name, i] = (sc, opt) + _restate(sc, margins=True, trace=TRACES[name, i], **opt)
     return out
 
 
@@ -198,6 +220,15 @@ def test_gpu_scene_precondition(restated):
         assert mg["error_px"] > ERR_MARGIN_PX, name
         assert mg["angle"] > ANGLE_MARGIN, name
         assert mg["depth"] > 1e-6, name
+
+
+def test_more_gpu_scenes_precondition(restated_more):
+    """the same precondition for every run of the second set of scenes, at the options of that run"""
+    for (name, i), (sc, opt, res, mg) in restated_more.items():
+        print(f"[precondition] {name} {opt}: error margin {mg['error_px']:.3e} px, angle margin {mg['angle']:.3e} rad, depth {mg['depth']:.3e}")
+        assert mg["error_px"] > ERR_MARGIN_PX, (name, opt)
+        assert mg["angle"] > ANGLE_MARGIN, (name, opt)
+        assert mg["depth"] > 1e-6, (name, opt)
 
 
 def test_gpu_scene_precondition_without_angle_threshold():
@@ -223,18 +254,152 @@ def test_restated_scenes_behave_as_planted(restated):
     assert math.isfinite(float(np.abs(res["X"]).max()))
 
 
-def test_tolerance_is_four_times_the_measured_gap(restated):
-    """S.TOL is 4 x the largest difference between the restatement's Jacobi and numpy.linalg routes over the GPU tests' scenes:
-    recomputed here, with the integer outputs equal on both routes"""
+def test_tolerance_is_four_times_the_measured_gap(restated, restated_more):
+    """S.TOL is 4 x the largest difference between the restatement's Jacobi and numpy.linalg routes over the GPU tests' scenes, both
+    sets, at the options of every device run: recomputed here, with the integer outputs equal on both routes"""
     worst = 0.0
-    for name, (sc, res, _) in restated.items():
-        other = R.triangulate_tracks(sc["poses"], sc["intr"], sc["track_start"], sc["obs_view"], sc["obs_uv"], lapack=True)
+    runs = [(name, sc, {}, res) for name, (sc, res, _) in restated.items()]
+    runs += [(f"{name} {opt}", sc, opt, res) for (name, _), (sc, opt, res, _) in restated_more.items()]
+    for name, sc, opt, res in runs:
+        other = _restate(sc, lapack=True, **opt)
         for k in ("inliers", "num_inliers", "success", "best_pair"):
             assert np.array_equal(res[k], other[k]), (name, k)
         gap = max(float(np.abs(res[k] - other[k]).max()) for k in ("X", "tri_angle", "mean_error_px"))
         print(f"[tolerance] {name}: Jacobi against numpy.linalg {gap:.3e}")
         worst = max(worst, gap)
     assert 0.0 < worst <= S.TOL / 4, worst
+
+
+# ------------------------------------------------------------------------------------------- what pins the second set of scenes
+INTEGERS = ("inliers", "num_inliers", "success", "best_pair")
+
+
+def test_per_view_intr_scene_is_pinned(restated_more):
+    """a kernel that swaps fx and fy, or reads another view's intrinsics, cannot pass: all four columns differ between two views of
+    one track, and either mistake, made in the restatement, changes the integer outputs at both thresholds"""
+    sc = S.more_gpu_scenes()["per_view_intr"][0]
+    intr = sc["intr"]
+    assert intr.shape == (len(sc["poses"]), 4) and (intr[:, 0] != intr[:, 1]).all()
+    a, b = sc["obs_view"][:2]                                          # two views of track 0
+    assert sc["track_start"][1] >= 2 and (intr[a] != intr[b]).all()
+    for i in (0, 1):
+        _, opt, res, _ = restated_more["per_view_intr", i]
+        for what, wrong in (("fx and fy swapped", intr[:, [1, 0, 2, 3]]), ("view 0's camera for all", np.tile(intr[0], (len(intr), 1)))):
+            other = R.triangulate_tracks(sc["poses"], wrong, sc["track_start"], sc["obs_view"], sc["obs_uv"], **opt)
+            changed = [k for k in INTEGERS if not np.array_equal(res[k], other[k])]
+            print(f"[pin] per_view_intr {opt}: {what} changes {changed}")
+            assert changed, (what, opt)
+    assert restated_more["per_view_intr", 0][2]["success"].sum() == 70   # every ring track; the three low-parallax ones fail
+
+
+def test_stride_scene_is_pinned(restated_more):
+    """536 copies of the 16 tracks of 64 observations: at least 8 tracks have every hypothesis at or beyond lane
+    kMaxHypBlocks x kThreads, and each of them succeeds in the restatement, so a kernel that does not stride leaves them without a
+    point"""
+    sc, _, res, _ = restated_more["stride", 0]
+    start, view, uv = S.tile_tracks(sc, 536)
+    assert len(start) == 537 and len(view) == 536 * 64 and (np.diff(start) == 64).all()
+    assert np.array_equal(view[-64:], sc["obs_view"][(535 % 16) * 64:(535 % 16 + 1) * 64])
+    hyp_start = np.arange(536) * S.PAIRS_64
+    assert 536 * S.PAIRS_64 == 1080576 and int((hyp_start >= S.HYP_LANE_LIMIT).sum()) == 15 >= 8
+    assert int(np.argmax(hyp_start >= S.HYP_LANE_LIMIT)) == 521
+    assert res["success"].all() and (res["best_pair"] >= 0).all()
+
+
+def test_deep_pair_scene_is_pinned(restated_more):
+    sc, _, res, _ = restated_more["deep_pair", 0]
+    moved, best = sc["moved"], res["best_pair"]
+    print(f"[pin] deep_pair: moved {moved.tolist()} best_pair {best.tolist()} inliers {res['num_inliers'].tolist()}")
+    assert res["success"].all()
+    assert (best[moved == 31] >= 1488).all()                          # the first pair with i = 31 at m = 64
+    assert (best[moved == 61] >= 2013).all()                          # (61, 62)
+    assert best[moved == 62].tolist() == [2015] and np.diff(sc["track_start"])[moved == 62].tolist() == [66]
+    assert not (res["inliers"].astype(bool) & sc["outlier"]).any()
+
+
+def test_short_scene_is_pinned(restated_more):
+    sc, _, res, _ = restated_more["short", 0]
+    n = np.diff(sc["track_start"])
+    short = sc["short"]
+    assert len(n) == 1032 and np.array_equal(short, n < 2) and set(n[short].tolist()) == {0, 1}
+    assert short[:3].all() and short[1022:1026].all() and short[200:208].all() and short[-2:].all()
+    for t in (13, 42, 107, 517):                                       # alone in an ordinary wave of eight
+        assert short[t] and short[t // 8 * 8:t // 8 * 8 + 8].sum() == 1
+    assert not res["success"][short].any() and (res["best_pair"][short] == -1).all() and (res["num_inliers"][short] == 0).all()
+    assert res["success"][~short].all()
+
+
+def test_long_scenes_are_pinned(restated_more):
+    sc, _, res, _ = restated_more["long_outliers", 0]
+    ts = sc["track_start"]
+    assert np.diff(ts).tolist() == [200, 1000] and (res["num_inliers"] > 64).all() and res["success"].all()
+    for t in (0, 1):
+        assert sc["outlier"][ts[t]:ts[t] + 64].sum() == 12 and not (res["inliers"].astype(bool) & sc["outlier"]).any()
+    inl = np.nonzero(res["inliers"][ts[1]:ts[2]])[0]
+    assert not np.array_equal(inl[:64], np.arange(64))                 # the first 64 inliers are not the first 64 observations
+    C = R.centres(sc["poses"])[sc["obs_view"][ts[1]:ts[2]][inl]]
+    i, j = np.triu_indices(len(inl), 1)
+    over_all = float(np.nanmax(R.tri_angle(C[i], C[j], res["X"][1])))
+    print(f"[pin] long_outliers: tri_angle {res['tri_angle'][1]:.6f} rad over the first 64 inliers, {over_all:.6f} over all {len(inl)}")
+    assert over_all > res["tri_angle"][1] + 1e-3                       # a kernel that looks beyond the 64th inlier fails
+    sc, _, res, _ = restated_more["longest", 0]
+    n = np.diff(sc["track_start"])
+    assert n.tolist() == S.LONGEST and n.max() == R.MAX_OBS and (res["num_inliers"][n == R.MAX_OBS] > 64).all() and res["success"].all()
+    start, view, uv, keep = S.with_overlong_track(sc, 4)
+    assert np.diff(start)[4] == R.MAX_OBS + 1 and np.array_equal(np.diff(start)[keep], n) and view.max() < len(sc["poses"])
+    assert len(np.unique(view[start[4]:start[5]])) == R.MAX_OBS + 1
+
+
+def test_local_optimisation_exits_reached(restated, restated_more):
+    """over every device run: some track refits at least twice (its inlier set changed sides after the first refit), and some
+    track leaves by "fewer", where the kernel must keep the old X.  Seeds 0 .. 49 of S.lo_scene were searched for "fewer";
+    S.LO_FEWER_SEED is the first that has it."""
+    sc = S.gpu_scenes()["outliers"]
+    TRACES["outliers, no angle threshold"] = []
+    _restate(sc, min_tri_angle_deg=0.0, trace=TRACES["outliers, no angle threshold"])
+    count = {e: 0 for e in R.LO_EXITS}
+    most = 0
+    for run, traces in TRACES.items():
+        for tr in traces:
+            if tr:
+                count[tr["exit"]] += 1
+                most = max(most, tr["iterations"])
+    print(f"[lo exits] over {len(TRACES)} runs: {count}, most refits of one track {most}")
+    assert len(TRACES) == len(restated) + len(restated_more) + 1
+    assert most >= 2
+    assert count["fewer"] >= 1 and count["unchanged"] >= 1
+    assert any(tr and tr["exit"] == "fewer" for tr in TRACES["lo_exits", 0])
+    assert S.more_gpu_scenes()["lo_exits"][1] == [dict(max_error_px=1.0)] and S.more_gpu_scenes()["lo_exits"][0]["noise_px"] == 0.7
+
+
+def test_noise_free_scene_lowest_pair_wins(restated_more):
+    """without noise every pair counts every observation: the key's index half decides, and the lowest pair must win"""
+    sc, _, res, _ = restated_more["noise_free", 0]
+    assert res["success"].all() and (res["best_pair"] == 0).all() and np.array_equal(res["num_inliers"], np.diff(sc["track_start"]))
+
+
+def test_empty_images_against_brute_force():
+    """images without a key point (a repeated image_start entry): the restated edge check and labels against the image of a
+    node found by trying every image"""
+    start = S.EMPTY_IMAGES
+    n = int(start[-1])
+    image = np.array([[v for v in range(len(start) - 1) if start[v] <= x < start[v + 1]] for x in range(n)])
+    assert image.shape == (n, 1) and sorted(set(image[:, 0].tolist())) == [1, 4, 6]
+    image = image[:, 0]
+    for a in range(n + 1):
+        for b in range(n + 1):
+            want = R.EDGE_RANGE if n in (a, b) else (R.EDGE_IMAGE if image[a] == image[b] else 0)
+            assert R.edge_status(start, np.array([[a, b]])) == want, (a, b)
+            lab = R.track_labels(start, np.array([[a, b]]))
+            joined = np.arange(n)
+            if want == 0:
+                joined[max(a, b)] = min(a, b)
+            assert np.array_equal(lab, joined), (a, b)
+    edges = np.array([[4, 5], [8, 9]])                                 # the last node of an image to the first of the next
+    assert R.edge_status(start, edges) == 0
+    assert R.track_labels(start, edges).tolist() == [0, 1, 2, 3, 4, 4, 6, 7, 8, 8, 10, 11, 12, 13]
+    # as one image every edge is refused
+    assert R.edge_status([0, n], edges) == R.EDGE_IMAGE and np.array_equal(R.track_labels([0, n], edges), np.arange(n))
 
 
 def test_key_points_with_scale_and_orientation_columns():

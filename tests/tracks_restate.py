@@ -274,8 +274,13 @@ def _lane_sum(terms):
     return lanes[0]
 
 
-def triangulate_track(P, K, C, uv, thr2, min_angle, lapack=False, mg=None):
-    """one track: P [n,3,4], K [n,4], C [n,3] (centres), uv [n,2] of its observations -> dict of its outputs"""
+LO_EXITS = ("below two", "not finite", "fewer", "unchanged", "limit")
+
+
+def triangulate_track(P, K, C, uv, thr2, min_angle, lapack=False, mg=None, trace=None):
+    """one track: P [n,3,4], K [n,4], C [n,3] (centres), uv [n,2] of its observations -> dict of its outputs.  trace: a dict that, for a
+    track that reaches the local optimisation, receives iterations (the refits computed) and exit (one of LO_EXITS: how the loop
+    was left); it changes no result"""
     n = len(uv)
     out = dict(X=np.zeros(3), inliers=np.zeros(n, np.uint8), num_inliers=0, success=False, tri_angle=0.0, mean_error_px=0.0,
                best_pair=-1)
@@ -324,8 +329,10 @@ def triangulate_track(P, K, C, uv, thr2, min_angle, lapack=False, mg=None):
 
     inl, e2c = mask_of(Xc)
     assert int(inl.sum()) == cur
+    iterations, left_by = 0, "limit"
     for _ in range(LO_ITERS):
         if cur < 2:
+            left_by = "below two"
             break
         terms = []
         for k in range(n):
@@ -340,18 +347,24 @@ def triangulate_track(P, K, C, uv, thr2, min_angle, lapack=False, mg=None):
             terms.append(rows)
         N = _lane_sum(terms)
         v = smallest_eigenvector(N, lapack)
+        iterations += 1
         with np.errstate(all="ignore"):
             Xn = v[:3] / v[3]
         if not np.isfinite(Xn).all():
+            left_by = "not finite"
             break
         inl_n, e2n = mask_of(Xn)
         cnt = int(inl_n.sum())
         if cnt < cur:
+            left_by = "fewer"
             break
         changed = bool((inl_n != inl).any())
         Xc, cur, inl, e2c = Xn, cnt, inl_n, e2n
         if not changed:
+            left_by = "unchanged"
             break
+    if trace is not None:
+        trace.update(iterations=iterations, exit=left_by)
     first = np.nonzero(inl)[0][:HYP_OBS]
     best_angle = 0.0
     if len(first) >= 2:
@@ -369,9 +382,10 @@ def triangulate_track(P, K, C, uv, thr2, min_angle, lapack=False, mg=None):
 
 
 def triangulate_tracks(poses, intrinsics, track_start, obs_view, obs_uv, max_error_px=4.0, min_tri_angle_deg=1.5, lapack=False,
-                       margins=False):
+                       margins=False, trace=None):
     """every track -> dict(X [T,3], inliers uint8 [n_obs], num_inliers, success, tri_angle, mean_error_px, best_pair) and, with
-    margins=True, dict(error_px, angle, depth): the closest any decision came to its threshold"""
+    margins=True, dict(error_px, angle, depth): the closest any decision came to its threshold.  trace: a list that receives one
+    dict per track (triangulate_track's; empty for a track that never reached the local optimisation)"""
     poses = np.asarray(poses, np.float64).reshape(-1, 3, 4)
     intr = np.asarray(intrinsics, np.float64).reshape(-1, 4)
     if len(intr) == 1:
@@ -389,7 +403,10 @@ def triangulate_tracks(poses, intrinsics, track_start, obs_view, obs_uv, max_err
     for t in range(T):
         s, e = int(ts[t]), int(ts[t + 1])
         v = view[s:e]
-        o = triangulate_track(poses[v], intr[v], C[v], uv[s:e], thr2, min_angle, lapack, mg)
+        tr = {} if trace is not None else None
+        o = triangulate_track(poses[v], intr[v], C[v], uv[s:e], thr2, min_angle, lapack, mg, tr)
+        if trace is not None:
+            trace.append(tr)
         res["inliers"][s:e] = o.pop("inliers")
         for k, val in o.items():
             res[k][t] = val

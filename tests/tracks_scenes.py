@@ -1,6 +1,8 @@
 """Seeded synthetic scenes for the track tests (numpy only): points in a box, cameras on a ring (or an arc of it) looking in, exact
 projections plus Gaussian pixel noise, a planted share of wrong observations moved by at least 20 px, planted conflicts, and planted
-low-parallax tracks seen only by two nearly coincident cameras.  One pinhole camera for all views."""
+low-parallax tracks seen only by two nearly coincident cameras.  One pinhole camera for all views, except in per_view_scene."""
+import functools
+
 import numpy as np
 
 F_PX, CX, CY = 600.0, 320.0, 240.0
@@ -8,9 +10,10 @@ INTR = (F_PX, F_PX, CX, CY)
 K = np.array([[F_PX, 0.0, CX], [0.0, F_PX, CY], [0.0, 0.0, 1.0]])
 RADIUS = 6.0                # of the ring; the points lie in [-1, 1]^3
 EXTENT = 2.0 * np.sqrt(3.0)  # the box's diagonal
-# Tolerance of X, tri_angle and mean_error_px in the GPU tests: 4 x the largest difference, over gpu_scenes() below, between the
-# restatement's Jacobi route and its numpy.linalg route (3.46e-13, X of scene "mixed").  tests/test_tracks_host.py recomputes that
-# difference and holds it to TOL / 4, so a changed seed or scene cannot leave the tolerance behind its measurement.
+# Tolerance of X, tri_angle and mean_error_px in the GPU tests: 4 x the largest difference, over gpu_scenes() and more_gpu_scenes()
+# below at the options of every device run, between the restatement's Jacobi route and its numpy.linalg route (3.46e-13, X of scene
+# "mixed"; the second set stays below it, 1.1e-13 at most).  tests/test_tracks_host.py recomputes that difference and holds it to
+# TOL / 4, so a changed seed or scene cannot leave the tolerance behind its measurement.
 TOL = 1.4e-12
 
 
@@ -178,6 +181,145 @@ def gpu_scenes():
         "mixed": track_scene(15, mixed_lengths, n_outlier_tracks=0, n_low_parallax=5),
         "outliers": track_scene(16, [8] * 20 + [12] * 20, n_outlier_tracks=25, n_low_parallax=6),
     }
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The second set: the shapes and options the first set never reaches.  more_gpu_scenes() is iterated by tests/test_tracks_host.py
+# (precondition, Jacobi-against-LAPACK gap, the conditions that pin each scene) and by tests/test_hip_tracks.py (the device).
+HYP_LANE_LIMIT = 4096 * 256     # kMaxHypBlocks x kThreads of csrc/tracks.hip: tt_hyp reaches a hypothesis numbered at or above it
+                                # only by striding
+PAIRS_64 = 64 * 63 // 2         # the hypotheses of a track of >= 64 observations
+
+
+def displace(scene, obs, rng):
+    """move the observations `obs` by 20 .. 60 px in a random direction and mark them as planted outliers (in place)"""
+    obs = np.asarray(obs, np.int64)
+    a = rng.uniform(0.0, 2.0 * np.pi, len(obs))
+    scene["obs_uv"][obs] += rng.uniform(20.0, 60.0, len(obs))[:, None] * np.stack([np.cos(a), np.sin(a)], axis=1)
+    scene["outlier"][obs] = True
+    return scene
+
+
+def per_view_scene(seed):
+    """a camera of its own for every view, fx != fy: the observations of a one-camera scene re-expressed view by view,
+    u' = fx_v (u - CX) / F_PX + cx_v and v' likewise; intr [V, 4]"""
+    sc = track_scene(seed, [8] * 20 + [12] * 20 + [2, 3, 5] * 10, n_outlier_tracks=20, n_low_parallax=3)
+    rng = np.random.default_rng(seed + 1000)
+    V = len(sc["poses"])
+    intr = np.stack([rng.uniform(400.0, 900.0, V), rng.uniform(400.0, 900.0, V), rng.uniform(200.0, 440.0, V),
+                     rng.uniform(150.0, 330.0, V)], axis=1)
+    k = intr[sc["obs_view"]]
+    uv = sc["obs_uv"]
+    sc["obs_uv"] = np.stack([k[:, 0] * (uv[:, 0] - CX) / F_PX + k[:, 2], k[:, 1] * (uv[:, 1] - CY) / F_PX + k[:, 3]], axis=1)
+    sc["intr"] = intr
+    return sc
+
+
+def tile_tracks(scene, copies):
+    """the scene's tracks `copies` times over, then cut to `copies` tracks: track t is a copy of track t mod T
+    -> (track_start, obs_view, obs_uv)"""
+    T = len(scene["track_start"]) - 1
+    return permute_tracks(scene, np.arange(copies) % T)[:3]
+
+
+def deep_pair_scene(seed):
+    """tracks whose first `moved` observations are wrong, so that the winning pair lies deep in the pair range: lengths 64, 66 and
+    200 with 1, 31 and 61 moved, and one track of 66 with 62 moved, whose only clean pair among its first 64 is (62, 63).
+    Noise 0.2 px, for a run at max_error_px = 1: at 4 px some of the ~1900 pairs of 62 wrong observations gather four inliers by
+    chance, tie with the clean pair and win by their lower index on every seed tried."""
+    moved = [L for L in (1, 31, 61) for _ in range(3)] + [62]
+    sc = track_scene(seed, [64, 66, 200] * 3 + [66], n_views=220, noise_px=0.2)
+    obs = np.concatenate([np.arange(s, s + L) for s, L in zip(sc["track_start"][:-1], moved)])
+    sc["moved"] = np.array(moved)
+    return displace(sc, obs, np.random.default_rng(seed + 1000))
+
+
+SHORT_TRACKS = 1032
+# tracks of 0 or 1 observations: three at the very start, four across 1023 / 1024 (the boundary of tt_prepare's scan round), singles
+# inside ordinary waves of eight, the whole wave 200 .. 207, and the last two
+SHORT_AT = [0, 1, 2, 13, 42, 107, 200, 201, 202, 203, 204, 205, 206, 207, 517, 1022, 1023, 1024, 1025, 1030, 1031]
+
+
+def short_scene(seed):
+    """1032 tracks of 2 .. 7 observations with tracks of 0 and 1 observations (alternating) at SHORT_AT; short bool [T]"""
+    lengths = np.random.default_rng(seed + 1000).integers(2, 8, SHORT_TRACKS)
+    lengths[SHORT_AT] = np.arange(len(SHORT_AT)) % 2
+    sc = track_scene(seed, lengths.tolist())
+    sc["short"] = lengths < 2
+    return sc
+
+
+def long_outlier_scene(seed):
+    """tracks of 200 and 1000 observations over 1100 views, 12 of each track's first 64 observations wrong"""
+    sc = track_scene(seed, [200, 1000], n_views=1100)
+    rng = np.random.default_rng(seed + 1000)
+    obs = np.concatenate([s + np.sort(rng.choice(64, 12, replace=False)) for s in sc["track_start"][:-1]])
+    return displace(sc, obs, rng)
+
+
+LONGEST = [5, 5, 5, 4096, 5, 5, 5, 5, 3, 4096, 2]       # 4096 = LS2FM_TRACK_MAX_OBS at group 3 of a full wave and in a partial last wave
+
+
+def longest_scene(seed):
+    return track_scene(seed, LONGEST, n_views=4200)
+
+
+def with_overlong_track(scene, at):
+    """the scene's table with a track of 4097 observations (one more than LS2FM_TRACK_MAX_OBS; the origin seen from views
+    0 .. 4096) inserted as track `at` -> (track_start, obs_view, obs_uv, keep: the tracks of the result that are the scene's)"""
+    n = 4097
+    ts = scene["track_start"].astype(np.int64)
+    cut = int(ts[at])
+    vs = np.arange(n)
+    start = np.concatenate([ts[:at + 1], ts[at:] + n]).astype(np.int32)
+    view = np.concatenate([scene["obs_view"][:cut], vs, scene["obs_view"][cut:]]).astype(np.int32)
+    uv = np.concatenate([scene["obs_uv"][:cut], project(scene["poses"][vs], np.zeros((n, 3))), scene["obs_uv"][cut:]])
+    return start, view, uv, np.delete(np.arange(len(start) - 1), at)
+
+
+LO_FEWER_SEED = 0           # the first seed of 0 .. 49 on which a track of lo_scene leaves the local optimisation by "fewer"
+
+
+def lo_scene(seed=LO_FEWER_SEED):
+    return track_scene(seed, [8] * 40, noise_px=0.7)
+
+
+def noise_free_scene():
+    return track_scene(17, [2, 3, 4, 5, 6, 7, 8] * 6, noise_px=0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def more_gpu_scenes():
+    """name -> (scene, the options of every device run of it).  What is restated: "stride" is the 16 distinct tracks, which the
+    device test tiles to 536.  Cached: callers do not write into the scenes."""
+    default = {}
+    return {
+        "per_view_intr": (per_view_scene(31), [default, dict(max_error_px=1.0)]),
+        "stride": (track_scene(32, [64] * 16, n_outlier_tracks=4), [default]),
+        "deep_pair": (deep_pair_scene(34), [dict(max_error_px=1.0)]),
+        "short": (short_scene(34), [default]),
+        "long_outliers": (long_outlier_scene(35), [default]),
+        "longest": (longest_scene(40), [default]),
+        "lo_exits": (lo_scene(), [dict(max_error_px=1.0)]),
+        "noise_free": (noise_free_scene(), [default]),
+        "len3_b": (track_scene(37, [3] * 5), [default]),
+    }
+
+
+def contended_graph(seed, n_views=50, n_points=400, n_edges=100000):
+    """every view sees every point (key points shuffled per view); edges between observations of one point in two views: 250
+    edges per component of 50 nodes, every lane of a wave uniting into the same few trees -> (image_start, edges)"""
+    rng = np.random.default_rng(seed)
+    image_start = (np.arange(n_views + 1) * n_points).astype(np.int32)
+    where = np.stack([rng.permutation(n_points) for _ in range(n_views)])          # where[v, p]: the key point of point p in view v
+    p = rng.integers(0, n_points, n_edges)
+    va = rng.integers(0, n_views, n_edges)
+    vb = (va + rng.integers(1, n_views, n_edges)) % n_views
+    edges = np.stack([image_start[va] + where[va, p], image_start[vb] + where[vb, p]], axis=1)
+    return image_start, edges.astype(np.int32)
+
+
+EMPTY_IMAGES = np.array([0, 0, 5, 5, 5, 9, 9, 14, 14], np.int32)     # images 0, 2, 3, 5 and 7 have no key point
 
 
 def perturb_poses(poses, seed, rot_rad, trans):
