@@ -1,393 +1,28 @@
-"""The optimisation step the reference's stage drivers share:
-
-    Initializer.run        pipelines/Initialization.py:149-179      BA.run_ba (mode != "sfm")   pipelines/BA.py:117-182
-    Refine.run             pipelines/rendering_refine.py:78-96
-
-each iteration of which is  `CameraSet.render` (pipelines/Camera.py:448-538: Renderer.forward, SDF.sphere_tracing, mask_bg /
-mask_finish, rgb_loss / DC_loss / PSNR)  ->  compute_loss / summarize_loss (eikonal over mask_bg, 10^w weighted sum:
-BA.py:186-218)  ->  loss.all.backward()  ->  Adam.step()  ->  ExponentialLR.step().
-
-`surface_losses` is the point side of a BA iteration (BA.py:117-131, compute_loss "sfm" branch) on the fused point queries;
-`render_losses` is that render-and-loss part for rays that are already picked (ray picking, poses, key points, COLMAP
-bookkeeping are the drivers' camera-side logic: SURVEY section 2, out of scope); `RenderStage` adds the update and, with
-`capture=True`, records the WHOLE step -- tracing kernel, point-query node of the traced depth, fused render with the loss
-head inside, backward, Adam with the learning-rate schedule on the device -- into one hipGraph: a step is then a single
-graph launch with no host synchronisation (the reference syncs at `mask_finish.sum() > 0`, at the tracing loop's
-`.sum()` per trip and at `loss.item()`).
+"""The stage LOOPS: `Refine.run` (pipelines/rendering_refine.py:72-97) and `BA.run_ba` (pipelines/BA.py:110-188) as loops over
+`RenderStage`, and beside them `Initializer.run`, `Registration.geo_init_nf` and `BA_Trad.BA`:
+every iteration is the reference's -- ray pick, multi-view tracing consistency of one random camera's key points, render +
+tracing + masks + losses, (BA: the point side and the re-projection through the pose parameters), one backward, one Adam
+update over every parameter group, one ExponentialLR step -- with nothing read back to the host inside an iteration: the
+reference's `.item()` (the adaptive re-projection weight, BA.py:164), `mask_surf.sum() == 0` and `mask_finish.sum() > 0`
+branches are device-side selects here, the logs come back as device tensors.  Scene containers are plain tensors: the
+reference's Camera / Point3D bookkeeping (COLMAP ids, feature tracks) stays with the caller.
 """
 from __future__ import annotations
 
 import random
 
+import numpy as np
 import torch
 
-from .losses import RenderLossHead, psnr
-from .optim import FusedAdam
-from .utils import camera as _cam
+from .. import _lib
+from .. import dist as _dist
+from .. import fused as _fused
+from ..optim import FusedAdam
+from ..utils import camera as _cam
+from .step import RenderStage, _EarlyTrace, _capture_step, _point_side, _weight_factor, _weight_lookup
+from .terms import _BATerms, _MatchTerm, _TracingTerm, _weighted_pair, host_intrinsic, reprojection_term
 
 
-_TRACE_STREAMS = {}
-
-
-def _trace_stream(device, slot=0):
-    """the stream(s) sphere tracings are launched on beside the render's forward: slot 0 the render rays', slots 1.. the key-point
-    tracings of a loop's extra terms (latency-bound kernels of a few workgroups each: they overlap each other almost for free).
-    None (= the current stream) inside a hipGraph capture under torch.distributed: the tracing max-reduces its trip count over the
-    ranks on the stream it runs on, and a side-stream branch that forks again into RCCL's own stream is the depth-three fork tree
-    that takes a capture down on ROCm 7.2 (csrc/streams.hip)."""
-    from . import dist as _dist
-    if _dist.is_distributed() and torch.cuda.is_current_stream_capturing():
-        return None
-    idx = torch.device(device).index
-    idx = torch.cuda.current_device() if idx is None else idx
-    if (idx, slot) not in _TRACE_STREAMS:
-        _TRACE_STREAMS[(idx, slot)] = torch.cuda.Stream(device=idx)
-    return _TRACE_STREAMS[(idx, slot)]
-
-
-class _EarlyTrace:
-    """A key-point sphere tracing launched AHEAD of the render on a stream of its own (the render does not depend on it), its
-    results picked up where the loss term is formed.  Holds the call's autograd-node record until the next launch: that record
-    owns every tensor the other stream touches (no record_stream under hipGraph capture, see ls2fm.fused.TracedDepthNode)."""
-
-    def __init__(self, sdf_field, slot):
-        self.sdf, self.slot = sdf_field, slot
-        self.out = self.ready = self.node = None
-
-    def launch(self, center, ray):
-        side = _trace_stream(center.device, self.slot)
-        self.out = self.sdf.sphere_tracing(center, ray, self.sdf, static_trips=True, launch_stream=side)
-        self.node = getattr(self.sdf, "last_trace_node", None)
-        self.ready = torch.cuda.Event()
-        self.ready.record(side)
-
-    def take(self):
-        """-> the tracing's outputs (joined into the current stream), or None when nothing was launched"""
-        if self.out is None:
-            return None
-        torch.cuda.current_stream(self.out[0].device).wait_event(self.ready)
-        out, self.out = self.out, None
-        return out
-
-
-def render_losses(opt, renderer, sdf_field, rad_field, head, centers, rays, rgbs_gt, static_trips=False, eikonal_over="bg"):
-    """CameraSet.render(mode="train") after the ray pick + the render-side terms of compute_loss: -> the reference's `ret`
-    keys (rgb, sdfs_volume, normals, depth_mlp, normal_mlp, mask_bg, rgb_loss, DC_loss, PSNR, tracing_loss) plus
-    eikonal_loss (over mask_bg, BA.py:193-194), mse and `loss_all` (the head's 10^w weighted sum).
-    centers, rays [B,R,3]; rgbs_gt [B,R,3].  The tracing runs first (it is independent of the render): its masks and depth
-    are then inputs of the loss head that runs INSIDE the fused render (Renderer.forward_with_loss).
-    eikonal_over: "bg" = over the rays of mask_bg (BA.py:193-194, Initialization.py:257-258), "all" = over every normal
-    (rendering_refine.py:101-102)."""
-    b, r = centers.shape[:2]
-    ready = None
-    if static_trips:
-        # one fused node forms the traced depth AND the two masks of Camera.py:515-516 (uint8, as the loss head takes them):
-        # as torch ops these lines were ~25 launch-bound elementwise kernels of the captured step.
-        # The tracing (one latency-bound kernel of few workgroups, then the track evaluation) is independent of the render up to
-        # the loss head inside shade_fwd: it runs on its own stream BESIDE the render's gather pass (L2-bound), and the forward
-        # waits for its event only in front of shade_fwd.  (The autograd node itself belongs to the current stream -- its
-        # backward runs there --; only the forward's kernels are launched on the other one.)
-        side = _trace_stream(centers.device)
-        d_points, sdf_last, _, _ = sdf_field.sphere_tracing(centers.reshape(1, -1, 3), rays.reshape(1, -1, 3), sdf_field, iter=0,
-                                                            static_trips=True, rgbs_gt=rgbs_gt.reshape(-1, 3), launch_stream=side)
-        mask_bg8, mask_dc8 = sdf_field.last_masks
-        ready = torch.cuda.Event()
-        ready.record(side)
-        mask_bg, mask_finish = mask_bg8.view(b, r), mask_dc8.view(b, r)
-        # the render's loss head evaluates mask_bg itself from the colours ("gt"): only the traced depth and mask_finish come out
-        # of the tracing, and those are read by the loss REDUCTION behind the shading kernel -- the render waits for `ready` there
-        head_bg = "gt"
-    else:
-        d_points, sdf_last, _, mask_finish = sdf_field.sphere_tracing(centers.reshape(1, -1, 3), rays.reshape(1, -1, 3), sdf_field,
-                                                                     iter=0)
-        gray = rgbs_gt.mean(dim=-1)
-        mask_bg = (gray < 0.95) & (gray > 0.05)                               # Camera.py:515
-        mask_finish = mask_finish.view(b, r) & mask_bg                        # Camera.py:516
-        head_bg = mask_bg
-    ret, losses = renderer.forward_with_loss(opt, centers, rays, sdf_field, rad_field, head, rgbs_gt, d_points=d_points.view(b, r),
-                                             mask_finish=mask_finish, mask_eik=head_bg if eikonal_over == "bg" else None,
-                                             mask_bg=head_bg, inputs_ready=ready,
-                                             depth_node=getattr(sdf_field, "last_trace_node", None) if static_trips else None)
-    if ready is not None:
-        torch.cuda.current_stream(centers.device).wait_event(ready)       # join: later readers of the traced outputs, the backward
-    if static_trips:
-        mask_bg, mask_finish = mask_bg.view(torch.bool), mask_finish.view(torch.bool)      # 0 / 1 bytes: same storage, no kernel
-    ret = dict(ret)
-    ret.update(tracing_loss=0, mask_bg=mask_bg, mask_finish=mask_finish, d_points=d_points.view(b, r, 1),
-               sdf_tracks=sdf_last.view(b, r, 1), rgb_loss=losses["rgb_loss"], DC_loss=losses["DC_loss"],
-               eikonal_loss=losses["eikonal_loss"], mse=losses["mse"], PSNR=losses["PSNR"] if "PSNR" in losses else psnr(losses["mse"]),
-               loss_all=losses["all"])
-    return ret
-
-
-def surface_losses(opt, sdf_field, xyzs, res=None):
-    """The POINT side of a bundle-adjustment iteration (pipelines/BA.py:117-131) and the "sfm" branch of BA.compute_loss
-    (BA.py:199-202): tracked 3-D points are projected onto the surface, `xyzs_new, normals_value = get_surface_pts(xyzs)`,
-    re-evaluated, `sdfs = infer_sdf(xyzs_new)`, and give  sdf_surf = L1(sdfs, 0),  eikonal_loss = L1(normals_value, 1)
-    and  mask_surf = |sdfs| < 2 * (extent / 10 / opt.Res).  Every field evaluation is one fused point-query node
-    (ls2fm_sdf_eval forward, ls2fm_sdf_points_bwd backward with the analytic double backward of the normal); the
-    re-projection term the drivers add on top of `xyzs_new` is camera-side logic (world2cam / cam2img), out of scope."""
-    xyzs_new, normals_value = sdf_field.get_surface_pts(xyzs)
-    sdfs = sdf_field.infer_sdf(xyzs_new, mode="ret_sdf").view(-1, 1)
-    res = int(opt.Res) if res is None else int(res)
-    sdf_threshold = (sdf_field.bound_max.reshape(-1)[0] - sdf_field.bound_min.reshape(-1)[0]) / 10 / res
-    return dict(xyzs_new=xyzs_new, gradients=normals_value, sdfs=sdfs, mask_surf=sdfs.abs() < 2 * sdf_threshold,
-                sdf_surf=sdfs.abs().mean(), eikonal_loss=(normals_value - 1).abs().mean())
-
-
-class RenderStage:
-    """render -> losses -> backward -> Adam + ExponentialLR over the two fields' parameters (and any extra ones, e.g. poses).
-
-        stage = RenderStage(opt, renderer, sdf, rad, weights=opt.loss_weight.ba, lr=1e-2, lr_end=1e-4, max_iter=500)
-        for it in range(500): ret = stage.step(centers, rays, rgbs_gt)
-
-    capture=True: the first `step` call records the whole step into a hipGraph at the given batch shape; later calls copy
-    the new rays into the captured input buffers and replay it (shapes must not change; no `.item()` anywhere).
-
-    extra_loss: a callable `ret -> scalar tensor` evaluated inside the step and ADDED to `loss_all` before the backward -- the
-    terms a driver forms outside the render (BA.run_ba's key-point re-projection error and, through `surface_losses`, its
-    sdf_surf term: BA.py:119-147, 186-202), already weighted.  With capture=True it is recorded with the step: it must read
-    its inputs from tensors that are updated in place and must not synchronise."""
-
-    def __init__(self, opt, renderer, sdf_field, rad_field, weights=None, lr=1e-2, lr_end=1e-4, max_iter=1000, betas=(0.9, 0.999),
-                 eps=1e-8, extra_params=(), capture=False, extra_loss=None, lr_color=None, eikonal_over="bg", reducer=None,
-                 sharded=False, async_gather=False, extra_prepare=None, input_fn=None, share_gradients=False, shard_groups=1,
-                 shard_views=False):
-        """lr / lr_color: the reference's two field groups (`[{sdf_func.parameters(), lr_sdf}, {color_func.parameters(),
-        lr_color}]`, BA.py:79-83; lr_color=None: one rate); extra_params: tensors (one more group at `lr`) or
-        `{"params": [...], "lr": x}` dicts (the pose groups of BA.py:60-75).  ONE ExponentialLR factor for all groups,
-        (lr_end / lr) ** (1 / max_iter), as the reference's scheduler (BA.py:87-88).
-        reducer: an `ls2fm.dist.GradAllReducer` over the same parameters, called between backward and the update -- required
-        when a process group is up (the fused loss head then divides by GLOBAL counts: without the reduction every rank would
-        apply 1/world of its local gradient and the replicas would drift apart) -- or sharded=True: the update is
-        `ls2fm.dist.ShardedAdam` (reduce-scatter of the flat gradient buffer, Adam on this rank's 1/world of the parameters,
-        all-gather of the updated shards; async_gather: the all-gather runs on the communication stream until the next step's
-        first parameter read; shard_groups >= 2: the exchange is pipelined by level groups of the two tables, `ShardedAdam`).
-        Fields only: pose groups (extra_params) take the all-reduce form.
-        reducer="auto": a GradAllReducer over this stage's parameters when a process group is up (else none).
-        shard_views=True (with a process group of W ranks): the step's [B,R,3] batch is the GLOBAL one, identical on every rank,
-        and rank r renders views r, r + W, ... of it (B % W == 0) -- BASELINE.json configs[3]: a BA step with the rays of 8
-        registered views sharded over 8 GPUs; the loss head divides by global counts, the all-reduce sums the shards' gradients.
-        `extra_loss` (terms formed outside the render: point side, re-projection, tracing consistency) is evaluated on every rank
-        over the same inputs and enters the backward with weight 1 / W, so that the summed gradient is the single-process one;
-        the returned `loss_all` is the global value on every rank.  capture=True under torch.distributed needs the RCCL ("nccl")
-        backend: the step's collectives -- loss counts, trip count, gradient all-reduce -- are recorded into the hipGraph."""
-        self.opt, self.renderer, self.sdf, self.rad = opt, renderer, sdf_field, rad_field
-        dev = next(sdf_field.parameters()).device
-        w = weights or {}
-        get = (lambda k: w.get(k)) if isinstance(w, dict) else (lambda k: getattr(w, k, None))
-        self.head = RenderLossHead(dev, w_rgb=get("rgb"), w_eikonal=get("eikonal_loss"), w_dc=get("DC_Loss"))
-        groups = [dict(params=[p for p in sdf_field.parameters() if p.requires_grad], lr=lr),
-                  dict(params=[p for p in rad_field.parameters() if p.requires_grad], lr=lr if lr_color is None else lr_color)]
-        loose = [p for p in extra_params if not isinstance(p, dict)]
-        if loose:
-            groups.append(dict(params=[p for p in loose if p.requires_grad], lr=lr))
-        groups += [dict(g) for g in extra_params if isinstance(g, dict)]
-        groups = [g for g in groups if g["params"]]
-        self.params = [p for g in groups for p in g["params"]]
-        self.gamma = (lr_end / lr) ** (1.0 / max_iter)                        # BA.py:87-88
-        self.sharded = bool(sharded)
-        if self.sharded:
-            if len(groups) > 2 or capture:
-                raise NotImplementedError("ls2fm.stage.RenderStage(sharded=True): the two field groups only, eager steps only "
-                                          "(pose groups and captured steps take the all-reduce form: reducer=\"auto\")")
-            from .dist import ShardedAdam
-            self.optim = ShardedAdam.for_fields(sdf_field, rad_field, lr=lr, lr_color=lr_color, betas=betas, eps=eps,
-                                                scheduled_gamma=self.gamma, async_gather=async_gather, n_groups=shard_groups,
-                                                in_backward=False)       # (a traced-depth node rides in every step)
-            self.params = list(self.optim.params)
-        else:
-            self.optim = FusedAdam(groups, lr=lr, betas=betas, eps=eps, scheduled_gamma=self.gamma)
-        self.capture = capture
-        self.extra_loss = extra_loss
-        # called at the start of a step, before the render is enqueued: work of the extra terms that does not depend on the
-        # render (their key-point tracings) starts here, on streams of its own, and runs beside the render's forward
-        self.extra_prepare = extra_prepare
-        # `() -> (centers, rays, rgbs_gt)` evaluated INSIDE the step (and inside its capture): a loop's ray pick and pose algebra
-        # from device tensors it updates in place -- `step()` then takes no arguments and a captured iteration has no eager
-        # preamble (the loops' ~50 launch-bound kernels of camera arithmetic per iteration were half of their time)
-        self.input_fn = input_fn
-        # one gradient buffer per backward pass (ls2fm.fused.pass_gradient_sharing): only for a caller whose extra terms issue
-        # ALL their field queries in `extra_prepare`, i.e. ahead of the render (the loops below)
-        self.share_gradients = bool(share_gradients)
-        self.eikonal_over = eikonal_over
-        if isinstance(reducer, str):
-            if reducer != "auto":
-                raise ValueError(f"ls2fm.stage.RenderStage: reducer={reducer!r}")
-            from . import dist as _dist
-            reducer = _dist.GradAllReducer(self.params) if (_dist.is_distributed() and not self.sharded) else None
-        self.reducer = reducer
-        self.shard_views = bool(shard_views)
-        self._graph = None
-        self._table_versions = None
-        self._one = torch.ones((), device=dev)
-
-    def _eager(self, centers, rays, rgbs_gt, static_trips):
-        from . import dist as _dist
-        if self.sharded:
-            self.optim.wait_params()               # the previous step's all-gather (async_gather) before anything reads a parameter
-        if _dist.is_distributed() and self.reducer is None and not self.sharded:
-            raise RuntimeError("ls2fm.stage.RenderStage under torch.distributed needs reducer=GradAllReducer(stage.params): the loss "
-                               "head normalises by global counts, the gradients must be summed over the ranks before the update")
-        for p in self.params:
-            p.grad = None
-        world = 1
-        if self.shard_views and _dist.is_distributed():
-            import torch.distributed as tdist
-            world, rank = tdist.get_world_size(), tdist.get_rank()
-            if centers.shape[0] % world:
-                raise RuntimeError(f"ls2fm.stage.RenderStage(shard_views=True): {centers.shape[0]} views over {world} ranks")
-            if world > 1:                  # views rank, rank + world, ...: strided views of the global batch, made contiguous
-                centers, rays, rgbs_gt = (t[rank::world].contiguous() for t in (centers, rays, rgbs_gt))
-        if self.extra_prepare is not None and static_trips:
-            self.extra_prepare()
-        ret = render_losses(self.opt, self.renderer, self.sdf, self.rad, self.head, centers, rays, rgbs_gt, static_trips=static_trips,
-                            eikonal_over=self.eikonal_over)
-        loss_bwd = ret["loss_all"]
-        if self.extra_loss is not None:
-            ret["loss_extra"] = self.extra_loss(ret)
-            # (replicated on every rank of a view-sharded step: 1 / world of it per rank in the backward, the whole in the log)
-            total = ret["loss_all"] + ret["loss_extra"]
-            loss_bwd = total if world == 1 else ret["loss_all"] + ret["loss_extra"] * (1.0 / world)
-            ret["loss_all"] = total
-        from . import fused as _fused
-        with _fused.pass_gradient_sharing(self.share_gradients and static_trips and self.extra_prepare is not None):
-            loss_bwd.backward(gradient=self._one)
-        if self.reducer is not None:
-            self.reducer.all_reduce()
-        self.optim.step()
-        return ret
-
-    def step(self, centers=None, rays=None, rgbs_gt=None):
-        if centers is None:
-            if self.input_fn is None:
-                raise TypeError("ls2fm.stage.RenderStage.step(): centers, rays, rgbs_gt -- or construct the stage with input_fn")
-            if not self.capture:
-                centers, rays, rgbs_gt = self.input_fn()
-            elif self._graph is None:
-                return self._capture(lambda: self._eager(*self.input_fn(), static_trips=True))
-            else:
-                return self._replay()
-        if not self.capture:
-            # the static form (trip count stays on the device, traced depth + masks as one fused node) whenever the fused tracing
-            # kernel serves this field: no host round trip per step, ~40 fewer launches; else the reference-shaped form
-            from . import fused as _fused
-            static = _fused.available(self.sdf, centers)
-            return self._eager(centers, rays, rgbs_gt, static_trips=static)
-        if self._graph is None:
-            self._in = (centers.detach().clone(), rays.detach().clone(), rgbs_gt.detach().clone())
-            return self._capture(lambda: self._eager(*self._in, static_trips=True))
-        srcs = (centers, rays, rgbs_gt)
-        for dst, src in zip(self._in, srcs):
-            if dst.shape != src.shape:
-                raise RuntimeError("ls2fm.stage.RenderStage(capture=True): the batch shape is fixed by the first step")
-        torch._foreach_copy_(list(self._in), [s.detach() for s in srcs])         # one launch for the three inputs
-        return self._replay()
-
-    def _replay(self):
-        """one replay of the captured step.  The graph reads the entry-interleaved table copy WITHOUT checking it (inside a capture
-        nothing can be checked): a foreign writer of a table since the last replay -- a checkpoint load, `load_state_dict`, another
-        optimizer -- is detected here, on the host, through the tables' version counters, and costs one rebuild of the copy."""
-        from . import fused as _fused
-        tabs = _fused.table_params(self.sdf, self.rad)
-        if tabs is not None and [t._version for t in tabs] != self._table_versions:
-            _fused.sync_mirror(self.sdf, self.rad)
-        out = self._graph.replay()
-        self.optim.replayed(1)
-        self._table_versions = None if tabs is None else [t._version for t in tabs]
-        return out
-
-    # ---- checkpoint / resume (utils/util.py:198-259 stores `optim_*` / `sched_*` state dicts next to the fields')
-    def state_dict(self):
-        """the optimizer's state in torch's layout (per-parameter `step, exp_avg, exp_avg_sq`, per-group `lr`): with the device-
-        resident schedule that IS the scheduler state -- ExponentialLR's only state is the current rate"""
-        if self.sharded:
-            raise NotImplementedError("ls2fm.stage.RenderStage.state_dict: use ShardedAdam.state_dict() (per-rank shards)")
-        return {"optim": self.optim.state_dict(), "gamma": self.gamma}
-
-    def load_state_dict(self, state):
-        """resume: moments, step counts and rates are copied INTO the tensors this stage (and a captured graph of it) already
-        owns; the next step -- eager or a replay -- continues the saved trajectory.  Load the fields' state dicts first."""
-        self.optim.load_state_dict(state["optim"])
-        self._table_versions = None            # the next replay re-checks the interleaved copy against the (reloaded) tables
-
-    def _capture(self, fn):
-        from . import dist as _dist
-        if _dist.is_distributed():
-            import torch.distributed as tdist
-            if tdist.get_backend() != "nccl" or self.sharded:
-                raise NotImplementedError("ls2fm.stage.RenderStage(capture=True) under torch.distributed needs the RCCL (\"nccl\") "
-                                          "backend and the all-reduce form (reducer=...): its collectives -- loss counts, trip count, "
-                                          "gradient all-reduce -- are then recorded into the hipGraph; gloo moves tensors through "
-                                          "the host, and the sharded update keeps per-rank state the snapshot around a capture does "
-                                          "not cover.  Use capture=False")
-        from .graph import CapturedStep
-        # the capture warms the step up by running it for real: parameters, Adam state and the schedule are put back
-        # afterwards (in place: the graph holds their addresses), so that this call, too, is exactly one step
-        snap = self._snapshot()
-        # the captured step's own Adam keeps the interleaved table copy current (ls2fm.fused): no rebuild inside the graph
-        from . import fused as _fused
-        _fused.trust_mirror_in_capture(self.sdf, self.rad)
-        self._graph = CapturedStep(fn, params=self.params)
-        self._restore(snap)
-        self._table_versions = None                     # the restore rewrote the tables behind the graph's back: _replay re-syncs
-        return self._replay()
-
-    # ---- state snapshot around the capture's warm-up steps
-    def _snapshot(self):
-        return _snapshot_training_state(self.params, self.optim)
-
-    def _restore(self, snap):
-        _restore_training_state(self.params, self.optim, snap)
-
-
-def _snapshot_training_state(params, opt):
-    """parameters, Adam moments / step counts, learning rates and device schedules -- what a capture's warm-up steps change"""
-    return dict(params=[p.detach().clone() for p in params],
-                state=[({k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state[p].items()} if p in opt.state else None)
-                       for p in params],
-                lrs=[float(g["lr"]) for g in opt.param_groups],
-                sched={gi: t.clone() for gi, t in opt._sched.items()})
-
-
-def _restore_training_state(params, opt, snap):
-    """put a `_snapshot_training_state` back IN PLACE (a captured graph holds the addresses)"""
-    with torch.no_grad():
-        for p, old in zip(params, snap["params"]):
-            p.copy_(old)
-            torch.autograd.graph.increment_version(p)
-        for p, old in zip(params, snap["state"]):
-            st = opt.state.get(p)
-            if not st:
-                continue
-            if old:
-                st["step"] = old["step"]
-                st["exp_avg"].copy_(old["exp_avg"])
-                st["exp_avg_sq"].copy_(old["exp_avg_sq"])
-            else:                       # state created by the warm-up: back to its initial value
-                st["step"] = 0
-                st["exp_avg"].zero_()
-                st["exp_avg_sq"].zero_()
-        for g, lr in zip(opt.param_groups, snap["lrs"]):
-            g["lr"] = lr
-        for gi, t in opt._sched.items():
-            if gi in snap["sched"]:
-                t.copy_(snap["sched"][gi])
-            else:                       # schedule created by the warm-up: seeded from the step the group had BEFORE it
-                steps = [int(old["step"]) for p, old in zip(params, snap["state"])
-                         if old and any(p is q for q in opt.param_groups[gi]["params"])]
-                t.copy_(torch.tensor([float(steps[0]) if steps else 0.0, snap["lrs"][gi], opt.scheduled_gamma, 0.0],
-                                     dtype=torch.float64))
-
-
-# ================================================================================================ the stage LOOPS
-# `Refine.run` (pipelines/rendering_refine.py:72-97) and `BA.run_ba` (pipelines/BA.py:110-188) as loops over `RenderStage`:
-# every iteration is the reference's -- ray pick, multi-view tracing consistency of one random camera's key points, render +
-# tracing + masks + losses, (BA: the point side and the re-projection through the pose parameters), one backward, one Adam
-# update over every parameter group, one ExponentialLR step -- with nothing read back to the host inside an iteration: the
-# reference's `.item()` (the adaptive re-projection weight, BA.py:164), `mask_surf.sum() == 0` and `mask_finish.sum() > 0`
-# branches are device-side selects here, the logs come back as device tensors.  Scene containers are plain tensors: the
-# reference's Camera / Point3D bookkeeping (COLMAP ids, feature tracks) stays with the caller.
 class TrackedViews:
     """What the loops need of a CameraSet + Point3DSet: world-to-camera poses [V,3,4] (or se(3) parameters [V,6]), one
     intrinsic matrix [3,3], the images as [V, H*W, 3], per view its key points [n_v, 2] (pixels) and the index of the tracked 3-D
@@ -408,6 +43,19 @@ class TrackedViews:
         # K^-1 on the host for the fused ray construction (ls2fm_camera_rays): read back here, once, outside any captured step
         self.kinv_host = _cam.host_inverse_intrinsic(intrinsic) if images.is_cuda else None
 
+    @staticmethod
+    def observations(views, device, pick=None):
+        """the observation list of util.get_idx3d_camset (utils/util.py:450-464) of `views` -- a TrackedViews, or any object with its
+        `track_ids` and `keypoints` (TradBALoop reads no more of the lists; the class itself pads key points and takes no empty
+        view): per view of `pick` (None: every view, in order), every key point with a 3-D point, sorted by view -> obs_view [n] long (the position IN the pick), obs_point [n] long, obs_uv
+        [n,2], view_start [len(pick) + 1] int32 (view j owns rows view_start[j] : view_start[j + 1]), all on `device`"""
+        pick = range(len(views.track_ids)) if pick is None else pick
+        ids = [views.track_ids[c] for c in pick]
+        obs_view = torch.cat([torch.full((t.shape[0],), j, dtype=torch.long) for j, t in enumerate(ids)])
+        view_start = torch.tensor([0] + [t.shape[0] for t in ids], dtype=torch.int64).cumsum(0).to(torch.int32)
+        return (obs_view.to(device), torch.cat(ids).long().to(device), torch.cat([views.keypoints[c] for c in pick]).to(device),
+                view_start.to(device))
+
 
 def keypoint_rays(pose, intrinsic, kypts):
     """centers / rays of a view's key points as `Camera.get_pts3D` forms them (pipelines/Camera.py:129-133): pose [3,4],
@@ -415,6 +63,11 @@ def keypoint_rays(pose, intrinsic, kypts):
     in_cam = _cam.img2cam(_cam.to_hom(kypts), intrinsic.unsqueeze(0))            # [1,n,3]
     center = _cam.cam2world(torch.zeros_like(in_cam), pose.unsqueeze(0))
     return center, _cam.cam2world(in_cam, pose.unsqueeze(0)) - center
+
+
+def _to_pixels(uv):
+    """homogeneous image coordinates [..,3] -> pixels [..,2] with the reference's guarded divide (Camera.py:173)"""
+    return (uv / (uv[..., 2:] + 1e-6))[..., :2]
 
 
 class TracingConsistency:
@@ -425,8 +78,7 @@ class TracingConsistency:
 
     def __init__(self, sdf_field, views, w_tracing, w_surf, static_trips=True):
         self.sdf, self.views, self.static = sdf_field, views, static_trips
-        self.w_tracing = 0.0 if w_tracing is None else 10.0 ** float(w_tracing)
-        self.w_surf = 0.0 if w_surf is None else 10.0 ** float(w_surf)
+        self.w_tracing, self.w_surf = _weight_factor(w_tracing), _weight_factor(w_surf)
         n = views.kp_pad.shape[1]
         dev = views.kp_pad.device
         self.center, self.ray = torch.zeros(1, n, 3, device=dev), torch.zeros(1, n, 3, device=dev)
@@ -475,8 +127,7 @@ class TracingConsistency:
 
     def __call__(self, ret, raw=False):
         """raw=True (fused CUDA path without sdf_surf only): the UNWEIGHTED tracing loss -- the caller multiplies by `w_tracing`"""
-        early = self._early.take()
-        d, sdf_last = early[:2] if early is not None else self.sdf.sphere_tracing(self.center, self.ray, self.sdf, static_trips=self.static)[:2]
+        d, sdf_last = self._early.take_or_trace(self.center, self.ray, self.static)[:2]
         if d.is_cuda and d.dtype == torch.float32:
             # one node each way (ls2fm_tracing_term_fwd / _bwd): in a captured iteration every torch kernel of the lines below and
             # of their autograd mirror is a graph node of >= 4.6 us, whatever its size
@@ -499,166 +150,6 @@ class TracingConsistency:
         return loss
 
 
-class _TracingTerm(torch.autograd.Function):
-    """the tracing-consistency sums of TracingConsistency.__call__ as one fused node (include/ls2fm.h: ls2fm_tracing_term_fwd /
-    _bwd): (tracing_loss, sdf_surf) from the traced depths d [.., n] and, optionally, the last SDF values; differentiable w.r.t.
-    both"""
-
-    @staticmethod
-    def forward(ctx, center, ray, d, target, live, sdf_last):
-        from . import _lib
-        lib = _lib.load()
-        n = live.numel()
-        c, r, t = center.detach().reshape(-1, 3).contiguous(), ray.detach().reshape(-1, 3).contiguous(), target.detach().contiguous()
-        dd, lv = d.detach().reshape(-1).contiguous(), live.detach().contiguous()
-        sl = None if sdf_last is None else sdf_last.detach().reshape(-1).contiguous()
-        out = torch.empty(3, device=d.device)
-        _lib.check(lib.ls2fm_tracing_term_fwd(_lib.ptr(c), _lib.ptr(r), _lib.ptr(dd), _lib.ptr(t), _lib.ptr(lv), _lib.ptr(sl), n,
-                                              _lib.ptr(out), _lib.stream_ptr()), "ls2fm_tracing_term_fwd")
-        ctx.save_for_backward(c, r, dd, t, lv, out, *([] if sl is None else [sl]))
-        ctx.shapes = (d.shape, None if sdf_last is None else sdf_last.shape)
-        # the two terms as tensors of their own (views of `out` made HERE, outside autograd): indexing a stacked result afterwards
-        # costs a zero fill + a copy per term in the backward -- graph nodes of a captured iteration
-        ctx.set_materialize_grads(False)
-        return out[0], out[1]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_tl, g_sd):
-        from . import _lib
-        lib = _lib.load()
-        c, r, dd, t, lv, out = ctx.saved_tensors[:6]
-        sl = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        g_tl = None if g_tl is None else g_tl.reshape(1).float().contiguous()
-        g_sd = None if g_sd is None else g_sd.reshape(1).float().contiguous()
-        d_d = torch.empty_like(dd)
-        d_s = None if sl is None else torch.empty_like(sl)
-        _lib.check(lib.ls2fm_tracing_term_bwd(_lib.ptr(c), _lib.ptr(r), _lib.ptr(dd), _lib.ptr(t), _lib.ptr(lv), _lib.ptr(sl), lv.numel(),
-                                              _lib.ptr(out), _lib.ptr(g_tl), _lib.ptr(g_sd), _lib.ptr(d_d), _lib.ptr(d_s), _lib.stream_ptr()),
-                   "ls2fm_tracing_term_bwd")
-        return None, None, d_d.view(ctx.shapes[0]), None, None, (None if d_s is None else d_s.view(ctx.shapes[1]))
-
-
-class _WeightedPair(torch.autograd.Function):
-    """wa a + wb b of two device scalars as one node each way (ls2fm_weighted_pair_fwd / _bwd).  The two gradients are the halves
-    of ONE two-float buffer: a producer that returned `a` and `b` as the halves of one buffer too (_MatchTerm) gets its upstream
-    back contiguous and needs no stacking kernel"""
-
-    @staticmethod
-    def forward(ctx, a, b, wa, wb):
-        from . import _lib
-        lib = _lib.load()
-        out = torch.empty((), device=a.device)
-        _lib.check(lib.ls2fm_weighted_pair_fwd(_lib.ptr(a.detach()), _lib.ptr(b.detach()), float(wa), float(wb), _lib.ptr(out),
-                                               _lib.stream_ptr()), "ls2fm_weighted_pair_fwd")
-        ctx.w = (float(wa), float(wb), a.shape, b.shape)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from . import _lib
-        lib = _lib.load()
-        wa, wb, sa, sb = ctx.w
-        d2 = torch.empty(2, device=g.device)
-        _lib.check(lib.ls2fm_weighted_pair_bwd(_lib.ptr(g.reshape(1).float().contiguous()), wa, wb, _lib.ptr(d2), _lib.stream_ptr()),
-                   "ls2fm_weighted_pair_bwd")
-        return d2[0].view(sa), d2[1].view(sb), None, None
-
-
-def _weighted_pair(a, b, wa, wb):
-    if a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.numel() == 1 and b.numel() == 1:
-        return _WeightedPair.apply(a, b, wa, wb)
-    return wa * a + wb * b
-
-
-class _BATerms(torch.autograd.Function):
-    """BA.run_ba's loss lines outside the render (pipelines/BA.py:160-170) as one fused node each way (include/ls2fm.h:
-    ls2fm_ba_terms_fwd / _bwd): (sdf_surf, w_reproj, extra) with sdf_surf = mean |sdfs|, w_reproj = w_hi where the re-projection
-    error exceeds `thresh` else w_lo (from the detached error), extra = w_reproj reproj + w_surf sdf_surf + w_add add.  Only
-    `extra` carries a gradient (the other two are the log's)."""
-
-    @staticmethod
-    def forward(ctx, reproj, sdfs, add, thresh, w_lo, w_hi, w_surf, w_add):
-        from . import _lib
-        lib = _lib.load()
-        r = reproj.detach().reshape(1).float().contiguous()
-        s = sdfs.detach().reshape(-1).float().contiguous()
-        a = None if add is None else add.detach().reshape(1).float().contiguous()
-        surf, w, extra = (torch.empty((), device=s.device) for _ in range(3))
-        _lib.check(lib.ls2fm_ba_terms_fwd(_lib.ptr(r), _lib.ptr(s), s.numel(), _lib.ptr(a), float(thresh), float(w_lo), float(w_hi),
-                                          float(w_surf), float(w_add), _lib.ptr(surf), _lib.ptr(w), _lib.ptr(extra), _lib.stream_ptr()),
-                   "ls2fm_ba_terms_fwd")
-        ctx.save_for_backward(s, w)
-        ctx.consts = (float(w_surf), float(w_add), reproj.shape, sdfs.shape, None if add is None else add.shape)
-        ctx.mark_non_differentiable(surf, w)
-        ctx.set_materialize_grads(False)
-        return surf, w, extra
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_surf, g_w, g):
-        from . import _lib
-        lib = _lib.load()
-        s, w = ctx.saved_tensors
-        w_surf, w_add, shape_r, shape_s, shape_a = ctx.consts
-        if g is None:
-            return (None,) * 8
-        g = g.reshape(1).float().contiguous()
-        d_r, d_s = torch.empty(1, device=s.device), torch.empty_like(s)
-        d_a = None if shape_a is None else torch.empty(1, device=s.device)
-        _lib.check(lib.ls2fm_ba_terms_bwd(_lib.ptr(s), s.numel(), _lib.ptr(w), _lib.ptr(g), w_surf, w_add, _lib.ptr(d_r), _lib.ptr(d_s),
-                                          _lib.ptr(d_a), _lib.stream_ptr()), "ls2fm_ba_terms_bwd")
-        return d_r.view(shape_r), d_s.view(shape_s), (None if d_a is None else d_a.view(shape_a)), None, None, None, None, None
-
-
-class _MatchTerm(torch.autograd.Function):
-    """the explicit-match terms of the two-view initialisation as one fused node (include/ls2fm.h: ls2fm_match_term_fwd / _bwd):
-    (reproj_error, sdf_surf) from the traced depths and last SDF values of each source view; `surface` receives the traced points"""
-
-    @staticmethod
-    def forward(ctx, fixed, surface, *ds):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        center, ray, uv_obs, poses, k_host, n = fixed
-        S = len(ds) // 2
-        d = [t.detach().reshape(-1).float().contiguous() for t in ds[:S]]
-        sl = [t.detach().reshape(-1).float().contiguous() for t in ds[S:]]
-        arr = lambda ts: (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts])          # noqa: E731
-        out = torch.empty(2, device=center.device)
-        _lib.check(lib.ls2fm_match_term_fwd(_lib.ptr(center), _lib.ptr(ray), _lib.ptr(uv_obs), _lib.ptr(poses), k_host, S, n, arr(d), arr(sl),
-                                            _lib.ptr(surface), _lib.ptr(out), _lib.stream_ptr()), "ls2fm_match_term_fwd")
-        ctx.fixed, ctx.S = fixed, S
-        ctx.shapes = [t.shape for t in ds]
-        ctx.save_for_backward(*d, *sl)
-        ctx.set_materialize_grads(False)
-        return out[0], out[1]            # (tensors of their own: no select backward -- a fill + a copy per term -- behind them)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g0, g1):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        center, ray, uv_obs, poses, k_host, n = ctx.fixed
-        S = ctx.S
-        saved = ctx.saved_tensors
-        d, sl = list(saved[:S]), list(saved[S:])
-        dd, dsl = [torch.empty_like(t) for t in d], [torch.empty_like(t) for t in sl]
-        arr = lambda ts: (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts])          # noqa: E731
-        if g0 is not None and g1 is not None and g0.dtype == torch.float32 and g1.dtype == torch.float32 and \
-                g1.data_ptr() == g0.data_ptr() + 4:
-            g = g0                       # the halves of one buffer (_WeightedPair's backward): the kernel reads g[0], g[1] from there
-        else:
-            zero = torch.zeros((), device=center.device)
-            g = torch.stack([(zero if t is None else t).reshape(()).float() for t in (g0, g1)])
-        _lib.check(lib.ls2fm_match_term_bwd(_lib.ptr(center), _lib.ptr(ray), _lib.ptr(uv_obs), _lib.ptr(poses), k_host, S, n, arr(d), arr(sl),
-                                            _lib.ptr(g), arr(dd), arr(dsl), _lib.stream_ptr()), "ls2fm_match_term_bwd")
-        grads = [t.view(sh) for t, sh in zip(dd + dsl, ctx.shapes)]
-        return (None, None, *grads)
-
-
 class _HostPicks:
     """The per-iteration ray pick of the loops -- the first k entries of a random permutation of the H W pixels, as the reference's
     `torch.randperm(H * W, device=...)[:k]` (pipelines/Camera.py:263, 431, 468) -- drawn on the HOST (numpy `Generator.choice`
@@ -674,11 +165,9 @@ class _HostPicks:
         """shared=True (a loop under torch.distributed: every rank must evaluate the replicated terms on the SAME pixels and view):
         the generator is seeded with rank 0's seed -- one 8-byte broadcast at construction, no collective per iteration -- and
         the view index comes from the same generator (`view(V)`) instead of the process-global, per-rank `random` module."""
-        import numpy as np
         self.n, self.k, self.tail = int(n_total), int(k), int(tail)
         seed = (int(torch.initial_seed()) + 0x9E3779B97F4A7C15 * _HostPicks._instances) & 0x7FFFFFFFFFFFFFFF
         _HostPicks._instances += 1
-        from . import dist as _dist
         self.shared = bool(shared) and _dist.is_distributed()
         if self.shared:
             import torch.distributed as tdist
@@ -718,6 +207,20 @@ class _HostPicks:
             self.events[self.slot].record()
         self.slot = (self.slot + 1) % len(self.host)
 
+    def pick(self, n_views=None, rays_idx=None, view=None, device_picks=False):
+        """one iteration's pick, left in `dev`.  Nothing given: the host draw -- the view (when there is a tail slot for it) BEFORE
+        the pixels, one asynchronous copy.  Else the caller's pixels, or (`device_picks`) the reference's device-side
+        `torch.randperm(H * W, device=...)[:k]` (rank 0's under a shared pick), and the caller's view or a drawn one, written
+        in place"""
+        if rays_idx is None and view is None and not device_picks:
+            self.draw(*([self.view(n_views)] if self.tail else []))
+            return
+        if rays_idx is None:
+            rays_idx = self.shared_pixels(torch.randperm(self.n, device=self.dev.device)[:self.k])
+        self.dev[:self.k].copy_(rays_idx)
+        if self.tail:
+            self.dev[self.k:].fill_(self.view(n_views) if view is None else int(view))
+
 
 def _pick_rays(views, poses, rays_idx, se3=None, poses_out=None):
     """CameraSet.render's ray pick for given poses (Camera.py:457-463): the same pixels in every view.  se3 [V,6]: the poses are
@@ -751,7 +254,20 @@ class _FixedPoseRays:
         return self.centers[:, rays_idx, :], self.rays[:, rays_idx, :], self.views.images[:, rays_idx, :]
 
 
-class RefineLoop:
+class _LoggedLoop:
+    """a loop whose `step(...)` returns one iteration's terms as device tensors and whose `_keys` names the ones to log"""
+
+    def _run_logged(self, n_iters, step_args=None):
+        """n_iters calls of `step(*step_args[it])` (None: `step()`) -> the logged terms, each stacked to [n_iters]"""
+        logs = {k: [] for k in self._keys}
+        for it in range(n_iters):
+            ret = self.step(*(step_args[it] if step_args is not None else ()))
+            for k in self._keys:
+                logs[k].append(ret[k].detach().reshape(()).clone())
+        return {("all" if k == "loss_all" else k): torch.stack(v) for k, v in logs.items()}
+
+
+class RefineLoop(_LoggedLoop):
     """`Refine` (pipelines/rendering_refine.py:15-126): fields only, fixed poses, eikonal over every normal, tracing consistency
     and sdf_surf on one random view's key points.
 
@@ -767,9 +283,8 @@ class RefineLoop:
                  capture=False, static_trips=None, distributed=False, device_picks=False):
         """distributed=True (a process group is up; every rank holds the same views, weights and per-iteration picks): the render
         rays are sharded by view, the gradients all-reduced (RenderStage(shard_views=True, reducer="auto"))"""
-        get = (lambda k: weights.get(k)) if isinstance(weights, dict) else (lambda k: getattr(weights, k, None))
+        get = _weight_lookup(weights)
         self.views, self.max_iter, self.rand_rays = views, int(max_iter), int(rand_rays)
-        from . import fused as _fused
         static = _fused.available(sdf_field, views.images) if static_trips is None else static_trips
         self.extra = TracingConsistency(sdf_field, views, get("tracing_loss"), get("sdf_surf"), static_trips=static)
         self.stage = RenderStage(opt, renderer, sdf_field, rad_field, weights=weights, lr=lr_sdf, lr_end=lr_sdf_end, max_iter=max_iter,
@@ -791,26 +306,14 @@ class RefineLoop:
         return self._fixed.pick(self._idx)
 
     def step(self, rays_idx=None, view=None):
-        V = self.poses.shape[0]
-        if rays_idx is None and view is None and not self.device_picks:
-            self._picks.draw(self._picks.view(V))
-            return self.stage.step()
-        if rays_idx is None:
-            rays_idx = self._picks.shared_pixels(torch.randperm(self.views.H * self.views.W, device=self.poses.device)[: self.rand_rays // V])
-        self._idx.copy_(rays_idx)
-        self._view.fill_(self._picks.view(V) if view is None else int(view))
+        self._picks.pick(self.poses.shape[0], rays_idx, view, self.device_picks)
         return self.stage.step()
 
     def run(self, n_iters=None, picks=None):
-        logs = {k: [] for k in self._keys}
-        for it in range(self.max_iter if n_iters is None else int(n_iters)):
-            ret = self.step(*(picks[it] if picks is not None else (None, None)))
-            for k in self._keys:
-                logs[k].append(ret[k].detach().reshape(()).clone())
-        return {("all" if k == "loss_all" else k): torch.stack(v) for k, v in logs.items()}
+        return self._run_logged(self.max_iter if n_iters is None else int(n_iters), picks)
 
 
-class InitLoop:
+class InitLoop(_LoggedLoop):
     """`Initializer.run` (pipelines/Initialization.py:139-226) for the two initial views with given poses (the essential-matrix
     pose initialisation of `Initializer.__init__` stays caller side: `ls2fm.pose.relative_pose`, or the one-line swap to
     `ls2fm.utils.pycolmap_compat.essential_matrix_estimation`, gives it on the device): per iteration the matched key points of each
@@ -825,16 +328,14 @@ class InitLoop:
 
     def __init__(self, opt, renderer, sdf_field, rad_field, views, weights, lr_sdf, lr_sdf_end, lr_color, max_iter, rand_rays,
                  capture=False, static_trips=None, sdf_filter=True, device_picks=False):
-        get = (lambda k: weights.get(k)) if isinstance(weights, dict) else (lambda k: getattr(weights, k, None))
+        get = _weight_lookup(weights)
         if len(views.keypoints) != 2 or views.keypoints[0].shape != views.keypoints[1].shape:
             raise ValueError("ls2fm.stage.InitLoop: two views with the same number of matched key points")
         self.sdf, self.views, self.max_iter, self.rand_rays = sdf_field, views, int(max_iter), int(rand_rays)
         self.sdf_filter = bool(sdf_filter)
         self.poses = (views.poses if views.poses.shape[-1] == 4 else _cam.lie.se3_to_SE3(views.poses)).detach()
-        from . import fused as _fused
         self.static = _fused.available(sdf_field, views.images) if static_trips is None else static_trips
-        self.w_reproj = 0.0 if get("reproj_error") is None else 10.0 ** float(get("reproj_error"))
-        self.w_surf = 0.0 if get("sdf_surf") is None else 10.0 ** float(get("sdf_surf"))
+        self.w_reproj, self.w_surf = _weight_factor(get("reproj_error")), _weight_factor(get("sdf_surf"))
         with torch.no_grad():              # the poses do not move during the loop: the key points' rays are formed once
             self._kp_rays = [keypoint_rays(self.poses[v], views.intrinsic, views.keypoints[v]) for v in range(2)]
         self.stage = RenderStage(opt, renderer, sdf_field, rad_field, weights=weights, lr=lr_sdf, lr_end=lr_sdf_end, max_iter=max_iter,
@@ -870,9 +371,7 @@ class InitLoop:
             # one node each way for the whole block below (ls2fm_match_term_fwd / _bwd): ~70 graph nodes of a captured iteration
             ds, sls, fins = [], [], []
             for v in range(2):
-                center, ray = self._kp_rays[v]
-                early = self._early[v].take()
-                d, sdf_last, _, fin = early if early is not None else self.sdf.sphere_tracing(center, ray, self.sdf, static_trips=self.static)
+                d, sdf_last, _, fin = self._early[v].take_or_trace(*self._kp_rays[v], self.static)
                 ds.append(d); sls.append(sdf_last); fins.append(fin.reshape(-1).bool())
             terms = _MatchTerm.apply(self._match, self._surface_buf.view(-1, 3), *ds, *sls)
             ret["reproj_error"], ret["sdf_surf"] = terms[0], terms[1]
@@ -881,12 +380,10 @@ class InitLoop:
         errs, sdfs, surface, finish = [], [], [], []
         for v in range(2):
             center, ray = self._kp_rays[v]
-            early = self._early[v].take()
-            d, sdf_last, _, fin = early if early is not None else self.sdf.sphere_tracing(center, ray, self.sdf, static_trips=self.static)
+            d, sdf_last, _, fin = self._early[v].take_or_trace(center, ray, self.static)
             pts = center + ray * d.reshape(1, -1, 1)                                             # Camera.py:136
             o = 1 - v
-            uv = _cam.cam2img(_cam.world2cam(pts, self.poses[o:o + 1]), self.views.intrinsic.unsqueeze(0))
-            uv = (uv / (uv[..., 2:] + 1e-6))[..., :2]                                            # Camera.py:173
+            uv = _to_pixels(_cam.cam2img(_cam.world2cam(pts, self.poses[o:o + 1]), self.views.intrinsic.unsqueeze(0)))
             errs.append((uv[0] - self.views.keypoints[o]).norm(dim=-1))
             sdfs.append(sdf_last.reshape(-1))
             surface.append(pts[0].detach())
@@ -897,22 +394,11 @@ class InitLoop:
         return self.w_reproj * ret["reproj_error"] + self.w_surf * ret["sdf_surf"]
 
     def step(self, rays_idx=None):
-        if rays_idx is None and not self.device_picks:
-            self._picks.draw()
-            rays_idx = self._idx
-        elif rays_idx is None:
-            rays_idx = torch.randperm(self.views.H * self.views.W, device=self.poses.device)[: self.rand_rays // 2]
-        if rays_idx is not self._idx:
-            self._idx.copy_(rays_idx)
+        self._picks.pick(rays_idx=rays_idx, device_picks=self.device_picks)
         return self.stage.step()
 
     def run(self, n_iters=None, picks=None):
-        logs = {k: [] for k in self._keys}
-        for it in range(self.max_iter if n_iters is None else int(n_iters)):
-            ret = self.step(picks[it] if picks is not None else None)
-            for k in self._keys:
-                logs[k].append(ret[k].detach().reshape(()).clone())
-        return {("all" if k == "loss_all" else k): torch.stack(v) for k, v in logs.items()}
+        return self._run_logged(self.max_iter if n_iters is None else int(n_iters), None if picks is None else [(p,) for p in picks])
 
     @torch.no_grad()
     def triangulate(self):
@@ -928,7 +414,7 @@ class InitLoop:
         return (self._surface[0] + self._surface[1]) / 2, kept
 
 
-class GeoInitLoop:
+class GeoInitLoop(_LoggedLoop):
     """`Registration.geo_init_nf` (pipelines/Registration.py:133-296): a NEW view against registered ones, SDF field only, no
     render.  Per iteration ONE sphere tracing over the matched key points of every (new, registered) pair from both sides; for
     the matches without a 3-D point the two traced points are re-projected into the other view -- outliers by the finish flags
@@ -947,8 +433,8 @@ class GeoInitLoop:
         """capture=True: the first `step` records the whole iteration -- tracing, the fixed-shape sample points and their mask,
         three point-query nodes, every term, the backward, Adam with the schedule on the device -- into ONE hipGraph; later
         steps write the iteration's uniform draws into a persistent buffer and replay it."""
-        get = (lambda k: weights.get(k)) if isinstance(weights, dict) else (lambda k: getattr(weights, k, None))
-        w = lambda k: 0.0 if get(k) is None else 10.0 ** float(get(k))
+        get = _weight_lookup(weights)
+        w = lambda k: _weight_factor(get(k))                                       # noqa: E731
         self.w_reproj, self.w_tracing, self.w_surf, self.w_eik = w("reproj_error"), w("tracing_loss"), w("sdf_surf"), w("eikonal_loss")
         self.sdf, self.intrinsic, self.xyzs = sdf_field, intrinsic, xyzs
         self.poses = (poses if poses.shape[-1] == 4 else _cam.lie.se3_to_SE3(poses)).detach()
@@ -991,17 +477,13 @@ class GeoInitLoop:
         else:
             self._u.copy_(sample_u.reshape(-1))
         if self._graph is None:
-            from .graph import CapturedStep
-            snap = _snapshot_training_state(self.params, self.optim)      # the capture warms up by stepping for real
-            self._graph = CapturedStep(lambda: self._iteration(self._u), params=self.params)
-            _restore_training_state(self.params, self.optim, snap)
+            self._graph = _capture_step(lambda: self._iteration(self._u), self.params, self.optim)
         ret, self._last = self._graph.replay()
         self.optim.replayed(1)
         return ret
 
     def _project(self, pts, view):
-        uv = _cam.cam2img(_cam.world2cam(pts.unsqueeze(0), self.poses[view:view + 1]), self.intrinsic.unsqueeze(0))[0]
-        return (uv / (uv[..., 2:] + 1e-6))[..., :2]
+        return _to_pixels(_cam.cam2img(_cam.world2cam(pts.unsqueeze(0), self.poses[view:view + 1]), self.intrinsic.unsqueeze(0))[0])
 
     def _iteration(self, sample_u=None):
         for p in self.params:
@@ -1047,12 +529,7 @@ class GeoInitLoop:
         return ret, last
 
     def run(self, n_iters=None, draws=None):
-        logs = {k: [] for k in self._keys}
-        for it in range(self.n_iters if n_iters is None else int(n_iters)):
-            ret = self.step(draws[it] if draws is not None else None)
-            for k in self._keys:
-                logs[k].append(ret[k].detach().reshape(()).clone())
-        return {("all" if k == "loss_all" else k): torch.stack(v) for k, v in logs.items()}
+        return self._run_logged(self.n_iters if n_iters is None else int(n_iters), None if draws is None else [(u,) for u in draws])
 
     @torch.no_grad()
     def triangulate(self):
@@ -1070,63 +547,7 @@ class GeoInitLoop:
         return out
 
 
-class _Reproject(torch.autograd.Function):
-    """ls2fm_reproject_fwd / _bwd: the re-projection term of a BA iteration (BA.py:126-147, 199-202) as one node
-    -> (reproj scalar, counted bool [n])"""
-
-    @staticmethod
-    def forward(ctx, points, poses, view_start, k_host, obs_uv, sdf, bound):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        x, ps = points.detach().float().contiguous(), poses.detach().float().contiguous()
-        _lib.require_device(x)
-        n, n_views, dev = x.shape[0], ps.shape[0], x.device
-        err = torch.empty(n, device=dev)
-        on = torch.empty(n, device=dev, dtype=torch.uint8)
-        sums = torch.empty(4, device=dev, dtype=torch.float64)
-        ws = torch.empty(int(lib.ls2fm_reproject_workspace_bytes(n_views)) // 8, device=dev, dtype=torch.float64)
-        sdf_c = None if sdf is None else sdf.detach().float().contiguous().reshape(-1)
-        _lib.check(lib.ls2fm_reproject_fwd(_lib.ptr(x), _lib.ptr(ps), _lib.ptr(view_start), n_views, k_host, _lib.ptr(obs_uv), _lib.ptr(sdf_c),
-                                           float(bound), n, _lib.ptr(err), _lib.ptr(on), _lib.ptr(sums), _lib.ptr(ws),
-                                           _lib.stream_ptr()), "ls2fm_reproject_fwd")
-        ctx.save_for_backward(x, ps, view_start, obs_uv, sdf_c if sdf_c is not None else x.new_empty(0), sums)
-        ctx.k_host, ctx.bound, ctx.has_sdf = k_host, float(bound), sdf_c is not None
-        counted = on.view(torch.bool)
-        ctx.mark_non_differentiable(counted)
-        ctx.set_materialize_grads(False)         # (no zero fill for the bool output's "gradient" in the backward)
-        return sums[3].float(), counted
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_reproj, _):
-        from . import _lib
-        lib = _lib.load()
-        x, ps, view_start, obs_uv, sdf_c, sums = ctx.saved_tensors
-        if d_reproj is None:
-            return (None,) * 7
-        d_x, d_ps = torch.empty_like(x), torch.empty_like(ps)
-        g = d_reproj.detach().float().reshape(1).contiguous()
-        _lib.check(lib.ls2fm_reproject_bwd(_lib.ptr(x), _lib.ptr(ps), _lib.ptr(view_start), ps.shape[0], ctx.k_host, _lib.ptr(obs_uv),
-                                           _lib.ptr(sdf_c) if ctx.has_sdf else None, ctx.bound, x.shape[0], _lib.ptr(sums), _lib.ptr(g),
-                                           _lib.ptr(d_x), _lib.ptr(d_ps), _lib.stream_ptr()), "ls2fm_reproject_bwd")
-        return d_x, d_ps, None, None, None, None, None
-
-
-def reprojection_term(points, poses, view_start, intrinsic_host, obs_uv, sdf=None, bound=float("inf")):
-    """points [n,3] (observations sorted by view: view v owns rows view_start[v] : view_start[v + 1], int32 [V + 1] on the device),
-    poses [V,3,4] world-to-camera, intrinsic_host: the 3 x 3 K as 9 host floats (`ctypes` array, see `host_intrinsic`), obs_uv
-    [n,2] -> (reproj, counted [n] bool): 0.5 mean(2 log(1 + err^2 / 4)) + 0.5 mean(err) over the observations with
-    |sdf| < bound and a finite projection (BA.py:126-147, 199-202); differentiable w.r.t. points and poses"""
-    return _Reproject.apply(points, poses, view_start, intrinsic_host, obs_uv.float().contiguous(), sdf, bound)
-
-
-def host_intrinsic(intrinsic):
-    import ctypes
-    return (ctypes.c_float * 9)(*[float(v) for v in intrinsic.detach().reshape(-1).cpu().tolist()])
-
-
-class BALoop:
+class BALoop(_LoggedLoop):
     """`BA` in mode "sfm_refine" with several cameras (pipelines/BA.py:24-218; optim_split: rotation / translation parameters
     with their own rates, BA.py:66-75): per iteration the POINT side -- tracked points projected onto the surface
     (get_surface_pts), re-evaluated (infer_sdf), re-projected through the live poses against their key points (robust mean over
@@ -1140,27 +561,20 @@ class BALoop:
         """distributed=True: BASELINE.json configs[3] -- the render rays of the registered views sharded by view over the ranks of
         the process group, one gradient all-reduce per iteration (fields' flat buffer + the pose groups); the point side,
         re-projection and tracing consistency are evaluated on every rank (same inputs) with weight 1 / world in the backward"""
-        get = (lambda k: weights.get(k)) if isinstance(weights, dict) else (lambda k: getattr(weights, k, None))
+        get = _weight_lookup(weights)
         self.opt, self.sdf, self.views = opt, sdf_field, views
         self.max_iter, self.rand_rays = int(max_iter), int(rand_rays)
         se3 = views.poses if views.poses.shape[-1] == 6 else _cam.lie.SE3_to_se3(views.poses)
         self.rot = torch.nn.Parameter(se3[:, :3].detach().clone())
         self.trans = torch.nn.Parameter(se3[:, 3:].detach().clone())
-        # the observation list of util.get_idx3d_camset (utils/util.py:450-464): per view, every key point with a 3-D point
-        self.obs_view = torch.cat([torch.full((t.shape[0],), v, dtype=torch.long) for v, t in enumerate(views.track_ids)]).to(se3.device)
-        self.obs_point = torch.cat(views.track_ids).to(se3.device)
-        self.obs_uv = torch.cat(views.keypoints).to(se3.device)
-        counts = [0] + [t.shape[0] for t in views.track_ids]
-        self.view_start = torch.tensor(counts, dtype=torch.int32).cumsum(0).to(torch.int32).to(se3.device)       # observations are sorted by view
+        self.obs_view, self.obs_point, self.obs_uv, self.view_start = TrackedViews.observations(views, se3.device)
         self._k_host = host_intrinsic(views.intrinsic)
         # the loop's OWN copy of the points (BA.py:77): it is what gets projected and replaced every iteration, while the
         # tracing consistency keeps comparing against the point set's coordinates, which do not move during the loop (and not
         # after it either: Point3DSet.update_xyzs never runs its lazy map, SURVEY C-13)
         self.xyzs_all = views.xyzs.detach().clone()
-        self.w_surf = 0.0 if get("sdf_surf") is None else 10.0 ** float(get("sdf_surf"))
-        self.w_reproj_lo = 0.0 if get("reproj_error") is None else 10.0 ** float(get("reproj_error"))
+        self.w_surf, self.w_reproj_lo = _weight_factor(get("sdf_surf")), _weight_factor(get("reproj_error"))
         self.sdf_threshold = float((float(opt.data.bound_max[0]) - float(opt.data.bound_min[0])) / 10 / int(opt.Res))
-        from . import fused as _fused
         static = _fused.available(sdf_field, views.images) if static_trips is None else static_trips
         self.tracing = TracingConsistency(sdf_field, views, get("tracing_loss"), None, static_trips=static)
         self.tracing.use_sdfs = False
@@ -1178,6 +592,8 @@ class BALoop:
         # the key-point rays of the tracing consistency come from the CAMERAS' own poses (Camera.get_pts3D -> get_pose,
         # Camera.py:131), which the loop only writes back after its last iteration (BA.py:184-185): fixed during the loop
         self._camera_poses = _cam.lie.se3_to_SE3(se3).detach()
+        self._point_side = None            # (xyzs_new, sdfs) of `_prepare`, consumed by the same step's `_extra`
+        self._w_hi = self._w_lo = None     # the adaptive weight's two values as device constants (torch-op branch of `_extra`)
 
     def _inputs(self):
         self.tracing.select(self._view, self._camera_poses)
@@ -1190,16 +606,16 @@ class BALoop:
         PRECEDE the render's, so that in the backward they run after it and add into its gradient buffer (ls2fm.fused: one
         gradient buffer per backward pass) instead of producing dense gradients of their own"""
         self.tracing.prepare()
-        xyzs_new, _ = self.sdf.get_surface_pts(self.xyzs_all[self.obs_point])
-        self._point_side = (xyzs_new, self.sdf.infer_sdf(xyzs_new, mode="ret_sdf").view(-1, 1))
+        self._point_side = self._project_points()
+
+    def _project_points(self):
+        xyzs_new, _, sdfs = _point_side(self.sdf, self.xyzs_all[self.obs_point])
+        return xyzs_new, sdfs
 
     def _extra(self, ret):
         """the terms BA.run_ba forms outside the render (BA.py:119-147) + the tracing consistency, already weighted"""
-        if getattr(self, "_point_side", None) is not None:
-            (xyzs_new, sdfs), self._point_side = self._point_side, None
-        else:
-            xyzs_new, _ = self.sdf.get_surface_pts(self.xyzs_all[self.obs_point])
-            sdfs = self.sdf.infer_sdf(xyzs_new, mode="ret_sdf").view(-1, 1)
+        xyzs_new, sdfs = self._project_points() if self._point_side is None else self._point_side
+        self._point_side = None
         poses = _cam.se3_to_SE3_fused(torch.cat([self.rot, self.trans], dim=1))                  # [V,3,4]: the live poses
         if xyzs_new.is_cuda:
             # one fused node each way for the per-observation block (projection, pixel error, on-surface / finite mask, robust mean)
@@ -1216,7 +632,7 @@ class BALoop:
             ret["reproj_error"], ret["w_reproj"], ret["sdf_surf"] = reproj, w_reproj, surf
             self._new_points = xyzs_new.detach()
             return extra if raw else extra + tl
-        if getattr(self, "_w_hi", None) is None or self._w_hi.device != reproj.device:       # constants once, not two fill kernels per iteration
+        if self._w_hi is None or self._w_hi.device != reproj.device:       # constants once, not two fill kernels per iteration
             on = 1.0 if self.w_reproj_lo else 0.0
             self._w_hi, self._w_lo = torch.full((), 10.0 * on, device=reproj.device), torch.full((), on, device=reproj.device)
         w_reproj = torch.where(reproj.detach() > 10, self._w_hi, self._w_lo)                  # BA.py:163-166
@@ -1229,7 +645,7 @@ class BALoop:
         """the same term written with torch ops (the reference's lines: BA.py:126-147, 199-202)"""
         in_cam = _cam.world2cam(xyzs_new.unsqueeze(1), poses[self.obs_view])
         uv = _cam.cam2img(in_cam, self.views.intrinsic.expand(in_cam.shape[0], 3, 3))
-        uv = (uv / (uv[..., 2:] + 1e-6))[..., :2].squeeze(1)
+        uv = _to_pixels(uv).squeeze(1)
         on_surface = (sdfs.abs() < 2 * self.sdf_threshold).squeeze(-1) & ~torch.isinf(uv).any(dim=-1)
         err = torch.where(on_surface, (uv - self.obs_uv).norm(dim=-1), torch.zeros((), device=uv.device))
         n = on_surface.sum()
@@ -1237,26 +653,14 @@ class BALoop:
         return torch.where(n > 0, 0.5 * robust.sum() / n.clamp_min(1) + 0.5 * err.sum() / n.clamp_min(1), torch.zeros((), device=uv.device))
 
     def step(self, rays_idx=None, view=None):
-        V = self.rot.shape[0]
-        if rays_idx is None and view is None and not self.device_picks:
-            self._picks.draw(self._picks.view(V))
-        else:
-            if rays_idx is None:
-                rays_idx = self._picks.shared_pixels(torch.randperm(self.views.H * self.views.W, device=self.rot.device)[: self.rand_rays // V])
-            self._idx.copy_(rays_idx)
-            self._view.fill_(self._picks.view(V) if view is None else int(view))
+        self._picks.pick(self.rot.shape[0], rays_idx, view, self.device_picks)
         ret = self.stage.step()
         with torch.no_grad():
             self.xyzs_all[self.obs_point] = self._new_points                                     # BA.py:181
         return ret
 
     def run(self, n_iters=None, picks=None):
-        logs = {k: [] for k in self._keys}
-        for it in range(self.max_iter if n_iters is None else int(n_iters)):
-            ret = self.step(*(picks[it] if picks is not None else (None, None)))
-            for k in self._keys:
-                logs[k].append(ret[k].detach().reshape(()).clone())
-        return {("all" if k == "loss_all" else k): torch.stack(v) for k, v in logs.items()}
+        return self._run_logged(self.max_iter if n_iters is None else int(n_iters), picks)
 
     def poses_se3(self):
         return torch.cat([self.rot, self.trans], dim=1).detach()
@@ -1305,12 +709,8 @@ class TradBALoop:
         se3_all = views.poses if views.poses.shape[-1] == 6 else _cam.lie.SE3_to_se3(views.poses)
         self.se3 = se3_all[self.cam_pick].detach().float().clone().contiguous().to(dev)
         self.xyzs_all = views.xyzs.detach().float().clone().contiguous()
-        # the observation list of util.get_idx3d_camset (utils/util.py:450-464), sorted by picked view
-        ids = [views.track_ids[c] for c in self.cam_pick]
-        self.obs_view = torch.cat([torch.full((t.shape[0],), j, dtype=torch.long) for j, t in enumerate(ids)]).to(dev)
-        self.obs_point = torch.cat(ids).long().to(dev)
-        self.obs_uv = torch.cat([views.keypoints[c] for c in self.cam_pick]).float().contiguous().to(dev)
-        self.view_start = torch.tensor([0] + [t.shape[0] for t in ids], dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+        self.obs_view, self.obs_point, obs_uv, self.view_start = TrackedViews.observations(views, dev, self.cam_pick)
+        self.obs_uv = obs_uv.float().contiguous()
         self.intrinsic = views.intrinsic.detach().float().to(dev)
         self.se3_entering_last, self.xyzs_entering_last = self.se3.clone(), self.xyzs_all.clone()
         self._err_last = None
@@ -1322,7 +722,6 @@ class TradBALoop:
 
     # ---- device path
     def _init_device(self):
-        from . import _lib
         lib = _lib.load()
         V, P, n, dev = self.se3.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.se3.device
         size = int(lib.ls2fm_bundle_adjust_workspace_bytes(V, P, n))
@@ -1336,7 +735,6 @@ class TradBALoop:
         self._m = [torch.zeros_like(self.se3), torch.zeros_like(self.se3), torch.zeros_like(self.xyzs_all), torch.zeros_like(self.xyzs_all)]
 
     def _run_device(self, n_iters):
-        from . import _lib
         lib = _lib.load()
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("TradBALoop.run cannot be captured into a graph: the per-iteration Adam / ExponentialLR scalars come "
@@ -1367,7 +765,7 @@ class TradBALoop:
             x = self._x[self.obs_point]
             in_cam = _cam.world2cam(x.unsqueeze(1), _cam.lie.se3_to_SE3(se3[self.obs_view]))
             uv = _cam.cam2img(in_cam, self.intrinsic.expand(in_cam.shape[0], 3, 3))
-            uv = (uv / (uv[..., 2:] + 1e-6))[..., :2].squeeze(1)
+            uv = _to_pixels(uv).squeeze(1)
             err = (uv - self.obs_uv).norm(dim=-1)
             reproj = 0.5 * (2 * torch.log(1 + err ** 2 / 4)).mean() + 0.5 * err.mean()
             w = torch.where(reproj.detach() > 10, 10.0, 1.0)                     # BA_Trad.py:111-114 without the `.item()`

@@ -302,7 +302,7 @@ def _picks_worker(rank, world, port, out_dir):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from ls2fm.stage import _HostPicks
+        from ls2fm.stage.loops import _HostPicks
         torch.manual_seed(1000 + 17 * rank)                      # the ranks' own seeds differ
         import random
         random.seed(5 + rank)

@@ -119,7 +119,7 @@ def test_fused_tracing_term_matches_the_torch_lines(use_sdfs):
     """ls2fm_tracing_term_fwd / _bwd against the torch lines they replace in TracingConsistency.__call__ (addcmul, live / sum,
     norm, dot, abs, dot): values and the gradients w.r.t. the traced depths and the last SDF values, incl. a key point that
     sits exactly on its target (norm backward at 0: zero) and padded (live = 0) rows"""
-    from ls2fm.stage import _TracingTerm
+    from ls2fm.stage.terms import _TracingTerm
     gen = torch.Generator().manual_seed(17)
     n = 1500
     center = torch.randn(1, n, 3, generator=gen).to(DEV)
@@ -159,7 +159,7 @@ def test_fused_ba_terms_match_the_torch_lines(error, with_add):
     weight from the DETACHED re-projection error (10^1 above 10 px, not AT 10), the weighted sum with the tracing loss -- values and
     the gradients w.r.t. the error, the SDF values (a zero among them: sign(0) = 0) and the added term"""
     from ls2fm import _lib
-    from ls2fm.stage import _BATerms
+    from ls2fm.stage.terms import _BATerms
     gen = torch.Generator().manual_seed(29)
     n = 1337
     s0 = torch.randn(n, 1, generator=gen).to(DEV) * 0.01
@@ -195,7 +195,7 @@ def test_fused_match_term_matches_the_torch_lines():
     """ls2fm_match_term_fwd / _bwd against the torch lines of InitLoop._extra they replace (Camera.py:136, 168-178 +
     Initialization.py:154-160): surface points, cross-view projection, pixel error and |sdf| means over both views, and the
     gradients w.r.t. the traced depths and the last SDF values"""
-    from ls2fm.stage import _MatchTerm, _weighted_pair, host_intrinsic
+    from ls2fm.stage.terms import _MatchTerm, _weighted_pair, host_intrinsic
     se3, intr, H, W, g = _setup()
     poses = cam.lie.se3_to_SE3(se3[:2]).contiguous()
     gen = torch.Generator().manual_seed(23)

@@ -385,7 +385,7 @@ def test_static_sphere_tracing_samples_have_the_reference_structure():
     columns), then one point per ray between near and min(1.5 t_end, far)."""
     g = load_golden("stage_refine_eth3d_single")
     meta, opt, sdf, rad, ren, views, picks = _scene(g)
-    centers, rays, _ = stage._pick_rays(views, views.poses, picks[0][0])
+    centers, rays, _ = stage.loops._pick_rays(views, views.poses, picks[0][0])
     o, d = centers.reshape(1, -1, 3), rays.reshape(1, -1, 3)
     n_rays, it = o.shape[1], int(sdf.iters_max)
     d_a, last_a, samp, fin_a = sdf.sphere_tracing(o, d, sdf, static_trips=True, want_samples=True)

@@ -381,3 +381,82 @@ def test_integration_lists_exactly_the_librarys_switches():
     assert env and build
     assert _integration_switch_list("Library environment switches") == env
     assert _integration_switch_list("Library build-time switches") == build
+
+
+def _recording_pick_object(monkeypatch, events):
+    """a `_HostPicks` over 48 pixels, 5 per pick, one tail slot (the view), on the CPU -> (it, the seed its generator got); every
+    view draw of the `random` module and every pixel draw of its own generator is appended to `events`"""
+    import random
+    from ls2fm.stage.loops import _HostPicks
+    seed = (int(torch.initial_seed()) + 0x9E3779B97F4A7C15 * _HostPicks._instances) & 0x7FFFFFFFFFFFFFFF
+    picks = _HostPicks(48, 5, "cpu", tail=1)
+    randint, rng = random.randint, picks.rng
+
+    class Recorder:
+        bit_generator = rng.bit_generator
+
+        def choice(self, *a, **kw):
+            events.append("pixels")
+            return rng.choice(*a, **kw)
+
+        def integers(self, *a, **kw):
+            events.append("view (numpy)")
+            return rng.integers(*a, **kw)
+
+    monkeypatch.setattr(random, "randint", lambda lo, hi: (events.append("view"), randint(lo, hi))[1])
+    picks.rng = Recorder()
+    return picks, seed
+
+
+def test_default_pick_stream_is_view_then_pixels_from_their_own_generators(monkeypatch):
+    """The draw order the loops imply (RefineLoop / BALoop.step): per iteration the view from `random.randint(0, V - 1)`, THEN k
+    pixels from the pick object's numpy generator, seeded (torch.initial_seed() + 0x9E3779B97F4A7C15 * instances so far) mod 2^63."""
+    import random
+    V, s, t = 7, 1234, 98765
+    random.seed(s)
+    torch.manual_seed(t)
+    events = []
+    picks, seed = _recording_pick_object(monkeypatch, events)
+    got = []
+    for _ in range(3):
+        picks.pick(V)
+        got.append(picks.dev.clone())
+    assert events == ["view", "pixels"] * 3
+    random.seed(s)
+    events.clear()
+    want_views = [random.randint(0, V - 1) for _ in range(3)]
+    rng = np.random.default_rng(seed)
+    want_pixels = [rng.choice(48, 5, replace=False) for _ in range(3)]
+    for it in range(3):
+        assert got[it].dtype == torch.long and got[it].shape == (6,)
+        assert int(got[it][5]) == want_views[it]
+        assert got[it][:5].tolist() == want_pixels[it].tolist()
+
+
+def test_caller_given_pick_is_stored_as_is_and_draws_nothing(monkeypatch):
+    import random
+    random.seed(4321)
+    torch.manual_seed(5678)
+    events = []
+    picks, _ = _recording_pick_object(monkeypatch, events)
+    before = (random.getstate(), picks.rng.bit_generator.state, torch.get_rng_state().clone())
+    pixels = torch.tensor([47, 0, 13, 13, 5])
+    picks.pick(7, rays_idx=pixels, view=3)
+    assert picks.dev.tolist() == [47, 0, 13, 13, 5, 3]
+    assert events == []
+    assert random.getstate() == before[0] and picks.rng.bit_generator.state == before[1]
+    assert torch.equal(torch.get_rng_state(), before[2])
+
+
+def test_stage_package_reexports_its_public_names():
+    """every name code outside the package reaches as `ls2fm.stage.X` is the object its defining module holds"""
+    from ls2fm import stage
+    from ls2fm.stage import loops, step, terms
+    public = {step: ("render_losses", "surface_losses", "RenderStage"),
+              terms: ("reprojection_term", "host_intrinsic"),
+              loops: ("TrackedViews", "keypoint_rays", "TracingConsistency", "RefineLoop", "InitLoop", "GeoInitLoop", "BALoop",
+                      "TradBALoop")}
+    for module, names in public.items():
+        for name in names:
+            assert getattr(stage, name) is getattr(module, name), name
+            assert getattr(module, name).__module__ == module.__name__, name
