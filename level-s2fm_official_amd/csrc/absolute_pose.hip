@@ -3,10 +3,10 @@
 // absolute_pose_estimation + pose_refinement), all geometry in fp64.  include/ls2fm.h states the rules; tests/pose_restate.py
 // repeats them step by step in numpy.  Correspondences are SORTED BY VIEW (view v owns [view_start[v], view_start[v + 1])).
 //
-// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model AbsModel below with this
-// file's pose_hyp_kernel: one thread per (view, trial), P3P on three distinct correspondences, <= 4 poses.  Then pose_lo_kernel
-// (local optimisation, the final mask) and pose_lm_kernel (refinement), one workgroup per view with fixed-order reductions: every
-// bit of the result is a function of the view's own data, seed and options.
+// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model AbsModel below: one thread
+// per (view, trial), P3P on three distinct correspondences, <= 4 poses.  Then pose_lo_kernel (local optimisation, the final mask)
+// and pose_lm_kernel (refinement), one workgroup per view with fixed-order reductions: every bit of the result is a function of the
+// view's own data, seed and options.
 #include "ransac.h"
 
 #include <cmath>
@@ -15,13 +15,11 @@ namespace {
 
 using namespace ransac;
 
-constexpr int kHypThreads = 256;
+constexpr int kP3pThreads = 256;               // P3P workgroups (hypotheses, ls2fm_p3p)
 constexpr int kViewThreads = 256;              // LO / LM workgroups
 constexpr int kLoIters = 10;
 constexpr double kGradTol = 1e-10;
 constexpr double kStepTol = 1e-12;
-
-static_assert(kRound % kHypThreads == 0, "round shape");
 
 // ------------------------------------------------------------------------------------------------------------------- P3P
 struct V3 { double x, y, z; };
@@ -232,11 +230,6 @@ __device__ __forceinline__ void p3p_solve(const V3 y[3], const V3 x[3], Emit emi
     }
 }
 
-__device__ __forceinline__ V3 bearing(double u, double v, const double* __restrict__ K) {
-    const V3 b = {(u - K[2]) / K[0], (v - K[3]) / K[1], 1.0};
-    return scale(b, 1.0 / sqrt(dot(b, b)));
-}
-
 // camera z and squared pixel error of one correspondence (the operation order of tests/pose_restate.py: project_err2)
 __device__ __forceinline__ double project_err2(const double* P, double x, double y, double z, double u, double v, double fx, double fy,
                                                double cx, double cy, double& Z) {
@@ -249,10 +242,10 @@ __device__ __forceinline__ double project_err2(const double* P, double x, double
     return du * du + dv * dv;
 }
 
-__global__ void __launch_bounds__(kHypThreads)
+__global__ void __launch_bounds__(kP3pThreads)
 p3p_kernel(const double* __restrict__ bear, const double* __restrict__ pts, int64_t m, double* __restrict__ poses,
            int32_t* __restrict__ n_sol) {
-    const int64_t i = (int64_t)blockIdx.x * kHypThreads + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kP3pThreads + threadIdx.x;
     if (i >= m) return;
     V3 y[3], x[3];
 #pragma unroll
@@ -273,7 +266,7 @@ p3p_kernel(const double* __restrict__ bear, const double* __restrict__ pts, int6
 
 // ---------------------------------------------------------------------------------------------------------------- RANSAC
 struct AbsModel {               // ransac.h's model of this file: P3P poses [R | t] scored by the squared pixel error
-    static constexpr int kSample = 3, kMaxSol = 4, kHypWords = 12, kMinGroup = 3;
+    static constexpr int kSample = 3, kMaxSol = 4, kHypWords = 12, kMinGroup = 3, kHypThreads = kP3pThreads, kHypLdsWords = 0;
     struct Input { const double* uv; const double* xyz; const double* intr; double thr2; };
     struct Ctx { double fx, fy, cx, cy, thr2; };
     struct Point { double x, y, z, u, v; };
@@ -287,39 +280,19 @@ struct AbsModel {               // ransac.h's model of this file: P3P poses [R |
         double Z;
         return project_err2(P, p.x, p.y, p.z, p.u, p.v, c.fx, c.fy, c.cx, c.cy, Z) < c.thr2 && Z > 0.0;
     }
-};
-
-__global__ void __launch_bounds__(kHypThreads)
-pose_hyp_kernel(const double* __restrict__ uv, const double* __restrict__ xyz, const int32_t* __restrict__ vs,
-                const double* __restrict__ intr, uint64_t seed, Ws w) {
-    const int v = blockIdx.y;
-    if (!w.active[v]) return;
-    const int tl = blockIdx.x * kHypThreads + threadIdx.x;
-    const int64_t slot = (int64_t)v * kRound + tl;
-    int32_t* __restrict__ cnt = w.counts + 4 * slot;
-    cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
-    const int64_t s0 = vs[v], n = vs[v + 1] - s0;
-    const uint64_t t = (uint64_t)(w.trials[v] + tl);
-    int64_t id[3];
-    int mask = 0;
-    if (sample_distinct(trial_key(seed, t), n, id)) {
-        const double* __restrict__ K = intr + 4 * v;
+    template <class Emit>
+    static __device__ __forceinline__ void hypotheses(const Input& in, const Ctx& c, int64_t s0, const int64_t (&id)[3], double*, Emit emit) {
         V3 y[3], x[3];
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            const int64_t i = s0 + id[s];
-            y[s] = bearing(uv[2 * i], uv[2 * i + 1], K);
-            x[s] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+            const Point p = load(in, c, s0 + id[s]);
+            const V3 b = {(p.u - c.cx) / c.fx, (p.v - c.cy) / c.fy, 1.0};           // the unit bearing of the pixel
+            y[s] = scale(b, 1.0 / sqrt(dot(b, b)));
+            x[s] = {p.x, p.y, p.z};
         }
-        double* __restrict__ out = w.hyp + 48 * slot;
-        p3p_solve(y, x, [&](int s, const double* P) {
-#pragma unroll
-            for (int q = 0; q < 12; ++q) out[12 * s + q] = P[q];
-            mask |= 1 << s;
-        });
+        p3p_solve(y, x, emit);
     }
-    w.valid[slot] = mask;
-}
+};
 
 // -------------------------------------------------------------------------------------------------------- least squares
 constexpr int kNe = 21 + 6 + 3;          // upper triangle of H, g, then {F or count, changed, unused}
@@ -581,7 +554,7 @@ extern "C" int ls2fm_p3p(const double* bearings, const double* points, int64_t m
     LS2FM_CHECK_ARG(m >= 0);
     if (m == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(bearings && points && poses && n_solutions);
-    p3p_kernel<<<(unsigned)((m + kHypThreads - 1) / kHypThreads), kHypThreads, 0, (hipStream_t)stream>>>(bearings, points, m, poses,
+    p3p_kernel<<<(unsigned)((m + kP3pThreads - 1) / kP3pThreads), kP3pThreads, 0, (hipStream_t)stream>>>(bearings, points, m, poses,
                                                                                                       n_solutions);
     return ls2fm_launch_status();
 }
@@ -597,14 +570,10 @@ extern "C" int ls2fm_absolute_pose(const double* uv, const double* xyz, const in
     LS2FM_CHECK_ARG(n_views >= 1 && n_views <= LS2FM_POSE_MAX_VIEWS && view_start && intr && opts_ok(opts) &&
                     (opts->refine == 0 || opts->refine == 1));
     LS2FM_CHECK_ARG(poses && num_inliers && trials && best_trial && success);
-    if (!workspace) return LS2FM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const double thr2 = opts->max_error_px * opts->max_error_px;
     Ws w;
-    const int st = run_rounds<AbsModel>({uv, xyz, intr, thr2}, view_start, n_views, uv && xyz && inliers, opts, workspace, s, &w,
-                                        [&](const Ws& ws) {
-        pose_hyp_kernel<<<dim3(kRound / kHypThreads, (unsigned)n_views), kHypThreads, 0, s>>>(uv, xyz, view_start, intr, opts->seed, ws);
-    });
+    const int st = run_rounds<AbsModel>({uv, xyz, intr, thr2}, view_start, n_views, uv && xyz && inliers, opts, workspace, s, &w);
     if (st != LS2FM_OK) return st;
     pose_lo_kernel<<<(unsigned)n_views, kViewThreads, 0, s>>>(uv, xyz, view_start, intr, thr2, w, poses, inliers, num_inliers, trials,
                                                               best_trial, success);

@@ -1,10 +1,11 @@
-// Batched LO-RANSAC rounds shared by absolute_pose.hip (P3P) and relative_pose.hip (five-point): the sample stream, the stopping
-// rule, the workspace, the scoring and selection kernels, the fixed-order reductions and the host loop.  include/ls2fm.h states the
-// rules.  Correspondences are SORTED BY GROUP (a view or a view pair; group g owns [group_start[g], group_start[g + 1])).
+// Batched LO-RANSAC rounds shared by absolute_pose.hip (P3P), relative_pose.hip (five-point) and two_view.hip (seven-point,
+// four-point): the sample stream, the stopping rule, the workspace, the hypothesis, scoring and selection kernels, the fixed-order
+// reductions and the host loop.  include/ls2fm.h states the rules.  Correspondences are SORTED BY GROUP (a view or a view pair;
+// group g owns [group_start[g], group_start[g + 1])).
 //
 //   per round (host loop, run_rounds; a group stops once its trial count reaches the stopping rule's N):
-//     the file's own hypothesis kernel   one thread per (group, trial): M::kSample distinct indices from the SplitMix64 stream
-//                        (sample_distinct), the minimal solver, <= M::kMaxSol hypotheses of M::kHypWords fp64 words
+//     hyp_kernel<M>      one thread per (group, trial): M::kSample distinct indices from the SplitMix64 stream (sample_distinct),
+//                        the model's minimal solver, <= M::kMaxSol hypotheses of M::kHypWords fp64 words
 //     score_kernel<M>    (1024-correspondence tile of some group, 16-trial block): inlier counts of the block's 16 x kMaxSol
 //                        hypotheses over the tile, wave ballots + integer atomics (exact, order-independent).  The tiles of all
 //                        groups are numbered in one flat range (per-group tile offsets from the host), so a group of n gets
@@ -18,6 +19,10 @@
 //     Ctx   context(in, g)          per-group constants, built once per workgroup
 //     Point load(in, ctx, i)        correspondence i, loaded once per thread per tile slot
 //     bool  inlier(H, pt, ctx)      one hypothesis against one correspondence
+//     kHypThreads, kHypLdsWords     workgroup size of hyp_kernel<M> (it divides kRound) and the fp64 words of LDS per thread that the
+//                                   minimal solver indexes at run time (word k of thread j at column[k * kHypThreads], 0: none)
+//     hypotheses(in, ctx, s0, id, column, emit)   load the sample s0 + id[0 .. kSample) and run the minimal solver: emit(slot, H)
+//                                   per kept hypothesis, slot < kMaxSol
 #pragma once
 
 #include "ls2fm_device.h"
@@ -128,6 +133,33 @@ init_kernel(const int32_t* __restrict__ gs, int32_t G, Ws w) {
     w.best_key[g] = 0ull;
     w.trials[g] = 0;
     w.active[g] = (gs[g + 1] - gs[g]) >= M::kMinGroup ? 1 : 0;
+}
+
+template <class M>
+__global__ void __launch_bounds__(M::kHypThreads)
+hyp_kernel(typename M::Input in, const int32_t* __restrict__ gs, uint64_t seed, Ws w) {
+    constexpr int kS = M::kMaxSol, kW = M::kHypWords, kT = M::kHypThreads, kLds = M::kHypLdsWords * kT;
+    static_assert(kRound % kT == 0, "round shape");
+    const int g = blockIdx.y;
+    if (!w.active[g]) return;
+    __shared__ double s_buf[kLds > 0 ? kLds : 1];          // unused, and dropped by the compiler, for a model without LDS words
+    const int tl = blockIdx.x * kT + threadIdx.x;
+    const int64_t slot = (int64_t)g * kRound + tl;
+    int32_t* __restrict__ cnt = w.counts + kS * slot;
+#pragma unroll
+    for (int s = 0; s < kS; ++s) cnt[s] = 0;
+    const int64_t s0 = gs[g], n = gs[g + 1] - s0;
+    int64_t id[M::kSample];
+    int mask = 0;
+    if (sample_distinct(trial_key(seed, (uint64_t)(w.trials[g] + tl)), n, id)) {
+        double* __restrict__ out = w.hyp + kS * kW * slot;
+        M::hypotheses(in, M::context(in, g), s0, id, s_buf + threadIdx.x, [&](int s, const double* h) {
+#pragma unroll
+            for (int q = 0; q < kW; ++q) out[kW * s + q] = h[q];
+            mask |= 1 << s;
+        });
+    }
+    w.valid[slot] = mask;
 }
 
 template <class M>
@@ -277,13 +309,14 @@ inline bool opts_ok(const ls2fm_pose_ransac_opts* o) {       // all but the mode
            o->max_num_trials <= LS2FM_POSE_MAX_TRIALS && o->min_num_trials <= o->max_num_trials;
 }
 
-// The rounds of one call, after the entry's own argument checks: group_start [G + 1] (device) is copied to the host and checked
-// (have_corr: the correspondence arrays and the mask are there, required once there is a correspondence), the tile offsets and the
-// initial state are written, then rounds run until no group is active.  launch_hyp(w) launches the file's hypothesis kernel on s.
-// The call synchronises.  *w: the workspace's arrays, for the kernels that follow.
-template <class M, class LaunchHyp>
+// The rounds of one call, after the entry's own argument checks: the workspace must be there; group_start [G + 1] (device) is copied
+// to the host and checked (have_corr: the correspondence arrays and the mask are there, required once there is a correspondence),
+// the tile offsets and the initial state are written, then rounds run until no group is active.  The call synchronises.
+// *w: the workspace's arrays, for the entry's own kernels that follow a return of LS2FM_OK.
+template <class M>
 int run_rounds(const typename M::Input& in, const int32_t* group_start, int32_t G, bool have_corr, const ls2fm_pose_ransac_opts* opts,
-               void* workspace, hipStream_t s, Ws* w, LaunchHyp launch_hyp) {
+               void* workspace, hipStream_t s, Ws* w) {
+    if (!workspace) return LS2FM_ERR_WORKSPACE;
     // the groups' extents, on the host: the grid of the scoring pass and the argument checks
     int32_t* h_gs = (int32_t*)malloc(sizeof(int32_t) * ((size_t)G + 1));
     if (!h_gs) return LS2FM_ERR_LAUNCH;
@@ -322,7 +355,7 @@ int run_rounds(const typename M::Input& in, const int32_t* group_start, int32_t 
     if (st != LS2FM_OK) return st;
     const int64_t max_rounds = (cap + kRound - 1) / kRound;          // N <= cap: every group has stopped after these
     for (int64_t r = 0; max_n >= M::kMinGroup && r < max_rounds; ++r) {
-        launch_hyp(*w);
+        hyp_kernel<M><<<dim3(kRound / M::kHypThreads, (unsigned)G), M::kHypThreads, 0, s>>>(in, group_start, opts->seed, *w);
         score_kernel<M><<<dim3((unsigned)tiles, kRound / kScoreTrials), kScoreThreads, 0, s>>>(in, group_start, G, *w);
         if (hipMemsetAsync(w->n_active, 0, sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
         select_kernel<M><<<(unsigned)G, kGroupThreads, 0, s>>>(group_start, opts->confidence, min_trials, cap, *w);

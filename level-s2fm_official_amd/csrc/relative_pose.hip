@@ -3,31 +3,29 @@
 // the _Trad drivers of cv2 (triangulatePoints), all geometry in fp64.  include/ls2fm.h states the rules; tests/relpose_restate.py
 // repeats them in numpy.  Correspondences are SORTED BY PAIR (pair p owns [pair_start[p], pair_start[p + 1])).
 //
-// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model RelModel below (squared
-// Sampson error) with this file's rel_hyp_kernel: one thread per (pair, trial), five-point on five distinct correspondences,
-// <= 10 E.  Then rel_final_kernel: local optimisation (five-point on the inlier set's normal matrix), the final mask and the pose
-// recovery, one workgroup per pair with fixed-order reductions: every bit is a function of the pair's own data, seed and options.
+// E is the third two-view model beside two_view.hip's F and H (csrc/two_view.h): its correspondences are normalised by K as they
+// are loaded, its rows are F's epipolar rows, its re-fit returns up to 10 candidates, and it has a pose-recovery tail.  The rounds
+// (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the model EModel below (squared Sampson error):
+// one thread per (pair, trial), five-point on five distinct correspondences, <= 10 E.  Then two_view.h's final_kernel: local
+// optimisation (five-point on the inlier set's normal matrix), the final mask and the pose recovery, one workgroup per pair with
+// fixed-order reductions: every bit is a function of the pair's own data, seed and options.
 //
 // The five-point solver's per-problem state (null-space basis 36, quadratic terms 70, the 10 x 20 cubic-constraint matrix 200:
 // kWords fp64 words) is a column of LDS: word k of thread j sits at s_buf[k * kFpThreads + j], so every run-time index (pivot
 // rows, polynomial degrees, the Sturm sequence) addresses LDS, never a private array, and no kernel of this file uses scratch.
 // 32 threads per workgroup: kWords x 32 x 8 B = 78 KB, two workgroups per CU.
-#include "pose_math.h"
-#include "ransac.h"
+#include "two_view.h"
 
 #include <cfloat>
 #include <cmath>
 
 namespace {
 
-using namespace pose_math;
-using namespace ransac;
+using namespace two_view;
 
 constexpr int kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS;   // 10
 constexpr int kFpThreads = 32;                 // five-point workgroups (hypotheses, ls2fm_five_point)
-constexpr int kPairThreads = 256;              // final workgroups
 constexpr int kTriThreads = 256;
-constexpr int kLoIters = 10;
 constexpr int kBisectIters = 100;
 constexpr int kNewtonIters = 5;
 
@@ -40,8 +38,6 @@ constexpr int kSeq = kA;         // Sturm sequence: polynomial k (capacity 11 - 
 constexpr int kDeg = kA + 66;    // their degrees (11)
 constexpr int kRoot = kA + 77;   // real roots (10)
 constexpr int kTmp = kA + 100;   // scratch polynomials (minors of B, the long division's dividend), pivot columns
-
-static_assert(kRound % kFpThreads == 0, "round shape");
 
 // ------------------------------------------------------------------------------------------------------- monomial indexing
 // quadratic monomials: x^2 y^2 z^2 xy xz yz x y z 1 ; variables 0..3 = x, y, z, 1
@@ -174,59 +170,19 @@ HD inline int sturm_roots(Col<S> w) {
 }
 
 // ------------------------------------------------------------------------------------------------------ five-point solver
-// the 4-dimensional null space of the 5 x 9 epipolar system (rows kron((x2, 1), (x1, 1))), Gauss-Jordan with partial pivoting,
-// then modified Gram-Schmidt -> kBas.  false: rank != 5 (pivot <= 1e-12 of the largest entry) or a degenerate basis
+// the 4-dimensional null space of the 5 x 9 epipolar system (rows kron((x2, 1), (x1, 1))) -> kBas; the pivot columns at kTmp.
+// false: rank != 5
 template <int S>
 HD inline bool nullspace5(const double (&x1)[5][2], const double (&x2)[5][2], Col<S> w) {
-    double amax = 0.0;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
         const double a[3] = {x1[r][0], x1[r][1], 1.0}, b[3] = {x2[r][0], x2[r][1], 1.0};
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double v = b[i] * a[j];
-                w[kA + 9 * r + 3 * i + j] = v;
-                amax = fmax(amax, fabs(v));
-            }
+            for (int j = 0; j < 3; ++j) w[kA + 9 * r + 3 * i + j] = b[i] * a[j];
     }
-    if (!(amax > 0.0) || !is_finite(amax)) return false;
-    int rank = 0, nfree = 0;
-    for (int c = 0; c < 9; ++c) {
-        int p = -1;
-        double best = 0.0;
-        for (int r = rank; r < 5; ++r) {
-            const double v = fabs(w[kA + 9 * r + c]);
-            if (p < 0 || v > best) { best = v; p = r; }
-        }
-        if (rank == 5 || !(best > 1e-12 * amax)) {
-            w[kTmp + 5 + nfree] = c;
-            ++nfree;
-            continue;
-        }
-        for (int k = 0; k < 9; ++k) {
-            const double t = w[kA + 9 * rank + k];
-            w[kA + 9 * rank + k] = w[kA + 9 * p + k];
-            w[kA + 9 * p + k] = t;
-        }
-        const double inv = 1.0 / w[kA + 9 * rank + c];
-        for (int k = 0; k < 9; ++k) w[kA + 9 * rank + k] = w[kA + 9 * rank + k] * inv;
-        for (int r = 0; r < 5; ++r) {
-            if (r == rank) continue;
-            const double f = w[kA + 9 * r + c];
-            for (int k = 0; k < 9; ++k) w[kA + 9 * r + k] -= f * w[kA + 9 * rank + k];
-        }
-        w[kTmp + rank] = c;
-        ++rank;
-    }
-    if (rank != 5 || nfree != 4) return false;
-    for (int j = 0; j < 4; ++j) {
-        const int f = (int)w[kTmp + 5 + j];
-        for (int k = 0; k < 9; ++k) w[kBas + 9 * j + k] = k == f ? 1.0 : 0.0;
-        for (int i = 0; i < 5; ++i) w[kBas + 9 * j + (int)w[kTmp + i]] = -w[kA + 9 * i + f];
-    }
-    return true;
+    return gj_nullspace<5, kA, kTmp, kBas>(w);
 }
 
 template <int S>
@@ -393,11 +349,6 @@ HD inline int solve_from_basis(Col<S> w, Emit emit) {
     return n;
 }
 
-// --------------------------------------------------------------------------------------------------------- Sampson error
-HD inline bool is_inlier(const double* E, double x1, double y1, double x2, double y2, double thr2) {
-    return sampson2(E, x1, y1, x2, y2) <= thr2;       // NaN (0 / 0) is not an inlier
-}
-
 // ------------------------------------------------------------------------------------------------------ pose from E (COLMAP)
 // E = U diag(s, s, 0) V^T by one-sided Jacobi on E's columns; U, V made proper; R1 = U W V^T, R2 = U W^T V^T, t = U col 2.
 // cand[k] = [R | t] for (R1, t), (R2, t), (R1, -t), (R2, -t)
@@ -474,253 +425,95 @@ HD inline bool in_front(const double* P, double x1, double y1, double x2, double
     return d2 > DBL_EPSILON && d2 < max_depth;
 }
 
-// ---------------------------------------------------------------------------------------------------------- minimal solver
-__device__ __forceinline__ double* fp_column(double* s_buf) { return s_buf + threadIdx.x; }
-
-__global__ void __launch_bounds__(kFpThreads)
-five_point_kernel(const double* __restrict__ x1, const double* __restrict__ x2, int64_t m, double* __restrict__ Eout,
-                  int32_t* __restrict__ n_sol) {
-    __shared__ double s_buf[kWords * kFpThreads];
-    const int64_t i = (int64_t)blockIdx.x * kFpThreads + threadIdx.x;
-    if (i >= m) return;
-    Col<kFpThreads> w{fp_column(s_buf)};
-    double a[5][2], b[5][2];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        a[s][0] = x1[10 * i + 2 * s]; a[s][1] = x1[10 * i + 2 * s + 1];
-        b[s][0] = x2[10 * i + 2 * s]; b[s][1] = x2[10 * i + 2 * s + 1];
-    }
-    double* __restrict__ out = Eout + 90 * i;
-    int n = 0;
-    if (nullspace5(a, b, w) && orthonormalise_basis(w))
-        n = solve_from_basis(w, [&](int s, const double* e) {
-            for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
-        });
-    for (int q = 9 * n; q < 90; ++q) out[q] = 0.0;
-    n_sol[i] = n;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- RANSAC
-__device__ __forceinline__ double pair_thr2(const double* __restrict__ k0, const double* __restrict__ k1, double err_px) {
-    const double f0 = 0.5 * (k0[0] + k0[1]), f1 = 0.5 * (k1[0] + k1[1]);
-    const double e = 0.5 * (err_px / f0 + err_px / f1);
-    return e * e;
-}
-
-__device__ __forceinline__ void normalised(const double* __restrict__ uv, int64_t i, const double* __restrict__ K, double& x, double& y) {
-    x = (uv[2 * i] - K[2]) / K[0];
-    y = (uv[2 * i + 1] - K[3]) / K[1];
-}
-
-struct RelModel {               // ransac.h's model of this file: essential matrices scored by the squared Sampson error
-    static constexpr int kSample = 5, kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS, kHypWords = 9, kMinGroup = 5;
+// ------------------------------------------------------------------------------------------------------------------ model
+struct EModel : Epipolar {      // essential matrices between K-normalised points, scored by the squared Sampson error
+    static constexpr int kSample = 5, kMaxSol = LS2FM_FIVE_POINT_MAX_SOLUTIONS, kHypWords = 9, kMinGroup = 5, kHypThreads = kFpThreads, kHypLdsWords = kWords;
+    static constexpr int kMinInliers = 5, kMaxCand = kMaxSol;
     struct Input { const double* uv0; const double* uv1; const double* intr0; const double* intr1; double err_px; };
     struct Ctx { const double* K0; const double* K1; double thr2; };
-    struct Point { double x1, y1, x2, y2; };
+    using Point = two_view::Point;
+    struct Lds { double solve[kWords]; double cand[kMaxCand][9]; double pose[4][12]; int ncand; };
     static __device__ __forceinline__ Ctx context(const Input& in, int p) {
         const double* K0 = in.intr0 + 4 * p;
         const double* K1 = in.intr1 + 4 * p;
-        return {K0, K1, pair_thr2(K0, K1, in.err_px)};
+        const double f0 = 0.5 * (K0[0] + K0[1]), f1 = 0.5 * (K1[0] + K1[1]);
+        const double e = 0.5 * (in.err_px / f0 + in.err_px / f1);
+        return {K0, K1, e * e};
     }
     static __device__ __forceinline__ Point load(const Input& in, const Ctx& c, int64_t i) {
-        Point pt;
-        normalised(in.uv0, i, c.K0, pt.x1, pt.y1);
-        normalised(in.uv1, i, c.K1, pt.x2, pt.y2);
-        return pt;
+        return {(in.uv0[2 * i] - c.K0[2]) / c.K0[0], (in.uv0[2 * i + 1] - c.K0[3]) / c.K0[1],
+                (in.uv1[2 * i] - c.K1[2]) / c.K1[0], (in.uv1[2 * i + 1] - c.K1[3]) / c.K1[1]};
     }
     static __device__ __forceinline__ bool inlier(const double* E, const Point& pt, const Ctx& c) {
-        return is_inlier(E, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
+        return test(E, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
     }
-};
-
-__global__ void __launch_bounds__(kFpThreads)
-rel_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
-               const double* __restrict__ intr0, const double* __restrict__ intr1, uint64_t seed, Ws w) {
-    const int p = blockIdx.y;
-    if (!w.active[p]) return;
-    __shared__ double s_buf[kWords * kFpThreads];
-    const int tl = blockIdx.x * kFpThreads + threadIdx.x;
-    const int64_t slot = (int64_t)p * kRound + tl;
-    int32_t* __restrict__ cnt = w.counts + kMaxSol * slot;
-    for (int s = 0; s < kMaxSol; ++s) cnt[s] = 0;
-    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
-    const uint64_t t = (uint64_t)(w.trials[p] + tl);
-    int64_t id[5];
-    int mask = 0;
-    if (sample_distinct(trial_key(seed, t), n, id)) {
-        const double* __restrict__ K0 = intr0 + 4 * p;
-        const double* __restrict__ K1 = intr1 + 4 * p;
-        double a[5][2], b[5][2];
-#pragma unroll
-        for (int s = 0; s < 5; ++s) {
-            normalised(uv0, s0 + id[s], K0, a[s][0], a[s][1]);
-            normalised(uv1, s0 + id[s], K1, b[s][0], b[s][1]);
-        }
-        Col<kFpThreads> c{fp_column(s_buf)};
-        double* __restrict__ out = w.hyp + kMaxSol * 9 * slot;
-        if (nullspace5(a, b, c) && orthonormalise_basis(c))
-            solve_from_basis(c, [&](int s, const double* e) {
-                for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
-                mask |= 1 << s;
-            });
+    template <int S, class Emit>
+    static HD inline int solve(const double (&p1)[5][2], const double (&p2)[5][2], Col<S> w, Emit emit) {
+        return nullspace5(p1, p2, w) && orthonormalise_basis(w) ? solve_from_basis(w, emit) : 0;
     }
-    w.valid[slot] = mask;
-}
-
-// ------------------------------------------------------------------------------------------------ local optimisation, pose
-constexpr int kNe = 45;
-
-__global__ void __launch_bounds__(kPairThreads)
-rel_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps,
-                 const double* __restrict__ intr0, const double* __restrict__ intr1, double err_px, Ws w, double* __restrict__ Eout,
-                 double* __restrict__ poses, uint8_t* __restrict__ inliers, int32_t* __restrict__ num_inliers,
-                 int32_t* __restrict__ trials, int32_t* __restrict__ best_trial, int32_t* __restrict__ success) {
-    __shared__ double s_red[(kPairThreads / 64) * kNe];
-    __shared__ double s_solve[kWords];
-    __shared__ double s_cand[kMaxSol][9];
-    __shared__ int s_ncand, s_int;
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
-    const double* __restrict__ K0 = intr0 + 4 * p;
-    const double* __restrict__ K1 = intr1 + 4 * p;
-    const double thr2 = pair_thr2(K0, K1, err_px);
-    const unsigned long long bk = w.best_key[p];
-    if (bk == 0ull) {
-        for (int64_t j = tid; j < n; j += kPairThreads) inliers[s0 + j] = 0;
-        if (tid < 12) poses[12 * p + tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
-        if (tid < 9) Eout[9 * p + tid] = 0.0;
-        if (tid == 0) { num_inliers[p] = 0; trials[p] = w.trials[p]; best_trial[p] = -1; success[p] = 0; }
-        return;
+    template <class Emit>
+    static __device__ __forceinline__ void hypotheses(const Input& in, const Ctx& c, int64_t s0, const int64_t (&id)[5], double* column,
+                                                      Emit emit) {
+        sampled_solve<EModel>(in, c, s0, id, column, emit);
     }
-    double E[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) E[q] = w.best[9 * p + q];
-    int cur = 0;
-    for (int64_t j = tid; j < n; j += kPairThreads) {
-        double a0, a1, b0, b1;
-        normalised(uv0, s0 + j, K0, a0, a1);
-        normalised(uv1, s0 + j, K1, b0, b1);
-        cur += is_inlier(E, a0, a1, b0, b1, thr2) ? 1 : 0;
-    }
-    cur = block_count(cur, &s_int);
-    for (int it = 0; it < kLoIters && cur >= 5; ++it) {
-        // normal matrix of the inliers' epipolar rows, upper triangle, fixed-order sum
+    static __device__ __forceinline__ bool keeps(bool have, int) { return have; }     // E and the count are written below 5 inliers too
+    // five-point on the normal matrix of X's inliers: its four smallest eigenvectors are the basis W, Z, Y, X
+    static __device__ __forceinline__ int refit(const Input& in, const Ctx& ctx, int64_t s0, int64_t n, const double* X, int, Lds& lds,
+                                                double* s_red) {
         double a[kNe];
 #pragma unroll
         for (int q = 0; q < kNe; ++q) a[q] = 0.0;
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            double a0, a1, b0, b1;
-            normalised(uv0, s0 + j, K0, a0, a1);
-            normalised(uv1, s0 + j, K1, b0, b1);
-            if (!is_inlier(E, a0, a1, b0, b1, thr2)) continue;
-            const double r[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};
-#pragma unroll
-            for (int i = 0; i < 9; ++i)
-#pragma unroll
-                for (int k = i; k < 9; ++k) a[sidx(i, k)] += r[i] * r[k];
-        }
-        block_sum<kNe, kPairThreads>(a, s_red);
-        {
-            double v[9];
-            jacobi9(a, tid < 9 ? tid : 0, v);
-            // rank of each eigenvalue, ascending (the lower index first among equals); the four smallest are W, Z, Y, X
-            int rank[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                rank[k] = 0;
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    const double ej = a[sidx(j, j)], ek = a[sidx(k, k)];
-                    rank[k] += (ej < ek || (ej == ek && j < k)) ? 1 : 0;
-                }
-            }
-            if (tid < 9)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    double x = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) x = rank[k] == 3 - j ? v[k] : x;
-                    s_solve[kBas + 9 * j + tid] = x;
-                }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            Col<1> c{s_solve};
-            s_ncand = solve_from_basis(c, [&](int s, const double* e) {
-                for (int q = 0; q < 9; ++q) s_cand[s][q] = e[q];
+        for_each_corr<EModel>(in, ctx, s0, n, [&](int64_t, double x1, double y1, double x2, double y2) {
+            if (test(X, x1, y1, x2, y2, ctx.thr2)) accumulate(a, x1, y1, x2, y2);
+        });
+        smallest_eigenvectors<4>(a, s_red, lds.solve + kBas);
+        if (threadIdx.x == 0)
+            lds.ncand = solve_from_basis(Col<1>{lds.solve}, [&](int s, const double* e) {
+                for (int q = 0; q < 9; ++q) lds.cand[s][q] = e[q];
             });
-        }
         __syncthreads();
-        const int nc = s_ncand;
-        int best_c = -1, best_cnt = -1;
-        for (int cidx = 0; cidx < nc; ++cidx) {
-            int c = 0;
-            for (int64_t j = tid; j < n; j += kPairThreads) {
-                double a0, a1, b0, b1;
-                normalised(uv0, s0 + j, K0, a0, a1);
-                normalised(uv1, s0 + j, K1, b0, b1);
-                c += is_inlier(s_cand[cidx], a0, a1, b0, b1, thr2) ? 1 : 0;
+        return lds.ncand;
+    }
+    // the pose: the candidate with the most triangulated inliers in front of both cameras (ties: the later); success: at least 5
+    // inliers and one of them in front
+    struct Tail {
+        int front[4];
+        __device__ __forceinline__ void begin(const double* E, bool keep, Lds& lds) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) front[k] = 0;
+            if (keep && threadIdx.x == 0) {
+                double cand[4][12];
+                pose_candidates(E, cand);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int q = 0; q < 12; ++q) lds.pose[k][q] = cand[k][q];
             }
-            c = block_count(c, &s_int);
-            if (c > best_cnt) { best_cnt = c; best_c = cidx; }
+            __syncthreads();
         }
-        if (best_c < 0 || best_cnt < cur) break;
-        int chg = 0;
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            double a0, a1, b0, b1;
-            normalised(uv0, s0 + j, K0, a0, a1);
-            normalised(uv1, s0 + j, K1, b0, b1);
-            chg += is_inlier(s_cand[best_c], a0, a1, b0, b1, thr2) != is_inlier(E, a0, a1, b0, b1, thr2) ? 1 : 0;
+        __device__ __forceinline__ void inlier(Lds& lds, double x1, double y1, double x2, double y2) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) front[k] += in_front(lds.pose[k], x1, y1, x2, y2) ? 1 : 0;
         }
-        chg = block_count(chg, &s_int);
+        __device__ __forceinline__ bool finish(bool keep, int cur, Lds& lds, int* s_int, double* __restrict__ poses, int p) {
+            int bestk = 0, bestf = -1;
 #pragma unroll
-        for (int q = 0; q < 9; ++q) E[q] = s_cand[best_c][q];
-        cur = best_cnt;
-        if (chg == 0) break;
-    }
-    // the final mask and the pose: the candidate with the most triangulated inliers in front of both cameras (ties: the later)
-    __shared__ double s_pose[4][12];
-    if (tid == 0) {
-        double cand[4][12];
-        pose_candidates(E, cand);
+            for (int k = 0; k < 4; ++k) {
+                const int f = block_count(front[k], s_int);
+                if (f >= bestf) { bestf = f; bestk = k; }
+            }
+            const bool ok = keep && cur >= kMinInliers && bestf > 0;
+            const int tid = threadIdx.x;
+            if (tid < 12) {
+                double v = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int q = 0; q < 12; ++q) s_pose[k][q] = cand[k][q];
-    }
-    __syncthreads();
-    int front[4] = {0, 0, 0, 0};
-    for (int64_t j = tid; j < n; j += kPairThreads) {
-        double a0, a1, b0, b1;
-        normalised(uv0, s0 + j, K0, a0, a1);
-        normalised(uv1, s0 + j, K1, b0, b1);
-        const bool in = is_inlier(E, a0, a1, b0, b1, thr2);
-        inliers[s0 + j] = in ? 1 : 0;
-        if (!in) continue;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) front[k] += in_front(s_pose[k], a0, a1, b0, b1) ? 1 : 0;
-    }
-    int bestk = 0, bestf = -1;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int f = block_count(front[k], &s_int);
-        if (f >= bestf) { bestf = f; bestk = k; }
-    }
-    const bool ok = cur >= 5 && bestf > 0;
-    if (tid < 12) {
-        double v = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v = (ok && bestk == k) ? s_pose[k][tid] : v;
-        poses[12 * p + tid] = v;
-    }
-    if (tid < 9) Eout[9 * p + tid] = E[tid];
-    if (tid == 0) {
-        num_inliers[p] = cur;
-        trials[p] = w.trials[p];
-        best_trial[p] = best_trial_of<RelModel>(bk);
-        success[p] = ok ? 1 : 0;
-    }
-}
+                for (int k = 0; k < 4; ++k) v = (ok && bestk == k) ? lds.pose[k][tid] : v;
+                poses[12 * p + tid] = v;
+            }
+            return ok;
+        }
+    };
+};
 
 // ---------------------------------------------------------------------------------------------------------- triangulation
 __global__ void __launch_bounds__(kTriThreads)
@@ -745,17 +538,10 @@ triangulate_kernel(const double* __restrict__ P0, const double* __restrict__ P1,
 }  // namespace
 
 extern "C" int ls2fm_five_point(const double* x1, const double* x2, int64_t m, double* E, int32_t* n_solutions, void* stream) {
-    LS2FM_CHECK_ARG(m >= 0);
-    if (m == 0) return LS2FM_OK;
-    LS2FM_CHECK_ARG(x1 && x2 && E && n_solutions);
-    five_point_kernel<<<(unsigned)((m + kFpThreads - 1) / kFpThreads), kFpThreads, 0, (hipStream_t)stream>>>(x1, x2, m, E, n_solutions);
-    return ls2fm_launch_status();
+    return minimal_call<EModel>(x1, x2, m, E, n_solutions, stream);
 }
 
-extern "C" int64_t ls2fm_relative_pose_workspace_bytes(int32_t n_pairs, int64_t n_corr) {
-    if (n_pairs < 1 || n_pairs > LS2FM_RELPOSE_MAX_PAIRS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
-    return (int64_t)ws_layout<RelModel>(n_pairs, nullptr, nullptr);
-}
+extern "C" int64_t ls2fm_relative_pose_workspace_bytes(int32_t n_pairs, int64_t n_corr) { return workspace_bytes<EModel>(n_pairs, n_corr); }
 
 extern "C" int ls2fm_relative_pose(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs, const double* intr0,
                                    const double* intr1, const ls2fm_pose_ransac_opts* opts, double* E, double* poses, uint8_t* inliers,
@@ -764,18 +550,8 @@ extern "C" int ls2fm_relative_pose(const double* uv0, const double* uv1, const i
     LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && pair_start && intr0 && intr1 && opts_ok(opts) &&
                     opts->refine == 0);
     LS2FM_CHECK_ARG(E && poses && num_inliers && trials && best_trial && success);
-    if (!workspace) return LS2FM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    Ws w;
-    const int st = run_rounds<RelModel>({uv0, uv1, intr0, intr1, opts->max_error_px}, pair_start, n_pairs, uv0 && uv1 && inliers, opts,
-                                        workspace, s, &w, [&](const Ws& ws) {
-        rel_hyp_kernel<<<dim3(kRound / kFpThreads, (unsigned)n_pairs), kFpThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->seed,
-                                                                                           ws);
-    });
-    if (st != LS2FM_OK) return st;
-    rel_final_kernel<<<(unsigned)n_pairs, kPairThreads, 0, s>>>(uv0, uv1, pair_start, intr0, intr1, opts->max_error_px, w, E, poses,
-                                                                inliers, num_inliers, trials, best_trial, success);
-    return ls2fm_launch_status();
+    return estimate<EModel>({uv0, uv1, intr0, intr1, opts->max_error_px}, pair_start, n_pairs, uv0 && uv1 && inliers, opts, E, poses,
+                            inliers, num_inliers, trials, best_trial, success, workspace, stream);
 }
 
 extern "C" int ls2fm_triangulate(const double* P0, const double* P1, const double* uv0, const double* uv1, const int32_t* pair_start,

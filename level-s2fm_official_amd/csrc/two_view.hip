@@ -3,29 +3,25 @@
 // ls2fm_relative_pose's E) give the CALIBRATED / UNCALIBRATED / PLANAR_OR_PANORAMIC / DEGENERATE verdict of ls2fm.pose.
 // include/ls2fm.h states the rules; tests/twoview_restate.py repeats them in numpy.  Correspondences are SORTED BY PAIR.
 //
-// The rounds (scoring, selection, the stopping rule) are csrc/ransac.h's, run on the models FModel (squared Sampson error) and
-// HModel (squared forward transfer error) with this file's tv_hyp_kernel: one thread per (pair, trial), the minimal solver on
-// kSample distinct correspondences.  Then tv_final_kernel: local optimisation (Hartley-normalised DLT on the inlier set through
-// the 9 x 9 normal matrix's smallest eigenvector) and the final mask, one workgroup per pair with fixed-order reductions: every
-// bit is a function of the pair's own data, seed and options.
+// The rounds (hypotheses, scoring, selection, the stopping rule) are csrc/ransac.h's, run on the models FModel (squared Sampson
+// error) and HModel (squared forward transfer error): one thread per (pair, trial), the minimal solver on kSample distinct
+// correspondences.  Then csrc/two_view.h's final_kernel, which relative_pose.hip's EModel shares: local optimisation (here the
+// Hartley-normalised DLT on the inlier set through the 9 x 9 normal matrix's smallest eigenvector) and the final mask, one
+// workgroup per pair with fixed-order reductions: every bit is a function of the pair's own data, seed and options.
 //
 // A minimal solve's run-time-indexed state (the R x 9 system, the pivot columns, the null-space basis: kWords fp64 words) is a
 // column of LDS, word k of thread j at s_buf[k * kMsThreads + j], as in relative_pose.hip: no kernel of this file indexes a
 // private array at run time.  64 threads per workgroup: kWords x 64 x 8 B = 50 KB.
-#include "pose_math.h"
-#include "ransac.h"
+#include "two_view.h"
 
 #include <cfloat>
 #include <cmath>
 
 namespace {
 
-using namespace ransac;
-using namespace pose_math;
+using namespace two_view;
 
 constexpr int kMsThreads = 64;                 // minimal-solver workgroups (hypotheses, ls2fm_seven_point, ls2fm_four_point_homography)
-constexpr int kPairThreads = 256;              // final workgroups
-constexpr int kLoIters = 10;
 constexpr int kNewtonIters = 5;
 
 // LDS words of one minimal solve
@@ -33,8 +29,6 @@ constexpr int kA = 0;            // the R x 9 system, R <= 8
 constexpr int kPiv = 72;         // pivot columns [0, R), then the free columns (9 - R)
 constexpr int kBas = 81;         // null-space basis, (9 - R) x 9, R >= 7
 constexpr int kWords = 99;
-
-static_assert(kRound % kMsThreads == 0, "round shape");
 
 // ------------------------------------------------------------------------------------------------------------ conditioning
 struct Norm { double cx, cy, s; };             // Hartley: x_n = s (x - c)
@@ -93,53 +87,6 @@ HD inline void denormalise_h(const double (&h)[9], const Norm& t1, const Norm& t
         out[3 + j] = g[3 + j] / t2.s + t2.cy * g[6 + j];
         out[6 + j] = g[6 + j];
     }
-}
-
-// -------------------------------------------------------------------------------------------------------------- null space
-// the (9 - R)-dimensional null space of the R x 9 system at kA: Gauss-Jordan with partial pivoting (ls2fm_five_point's rule: a
-// column whose largest remaining |entry| is <= 1e-12 of the matrix's largest is free) -> basis vector j (free column f_j,
-// ascending) at kBas + 9 j: 1 at f_j, -R[i][f_j] at pivot column i.  false: rank != R
-template <int R, int S>
-HD inline bool gj_nullspace(Col<S> w) {
-    double amax = 0.0;
-    for (int i = 0; i < 9 * R; ++i) amax = fmax(amax, fabs(w[kA + i]));
-    if (!(amax > 0.0) || !is_finite(amax)) return false;
-    int rank = 0, nfree = 0;
-    for (int c = 0; c < 9; ++c) {
-        int p = -1;
-        double best = 0.0;
-        for (int r = rank; r < R; ++r) {
-            const double v = fabs(w[kA + 9 * r + c]);
-            if (p < 0 || v > best) { best = v; p = r; }
-        }
-        if (rank == R || !(best > 1e-12 * amax)) {
-            if (nfree == 9 - R) return false;          // one free column too many: the rank cannot reach R
-            w[kPiv + R + nfree] = c;
-            ++nfree;
-            continue;
-        }
-        for (int k = 0; k < 9; ++k) {
-            const double t = w[kA + 9 * rank + k];
-            w[kA + 9 * rank + k] = w[kA + 9 * p + k];
-            w[kA + 9 * p + k] = t;
-        }
-        const double inv = 1.0 / w[kA + 9 * rank + c];
-        for (int k = 0; k < 9; ++k) w[kA + 9 * rank + k] = w[kA + 9 * rank + k] * inv;
-        for (int r = 0; r < R; ++r) {
-            if (r == rank) continue;
-            const double f = w[kA + 9 * r + c];
-            for (int k = 0; k < 9; ++k) w[kA + 9 * r + k] -= f * w[kA + 9 * rank + k];
-        }
-        w[kPiv + rank] = c;
-        ++rank;
-    }
-    if (rank != R || nfree != 9 - R) return false;
-    for (int j = 0; j < 9 - R; ++j) {
-        const int f = (int)w[kPiv + R + j];
-        for (int k = 0; k < 9; ++k) w[kBas + 9 * j + k] = k == f ? 1.0 : 0.0;
-        for (int i = 0; i < R; ++i) w[kBas + 9 * j + (int)w[kPiv + i]] = -w[kA + 9 * i + f];
-    }
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ cubic
@@ -241,7 +188,7 @@ HD inline int seven_point(const double (&p1)[7][2], const double (&p2)[7][2], Co
 #pragma unroll
             for (int j = 0; j < 3; ++j) w[kA + 9 * r + 3 * i + j] = b[i] * a[j];
     }
-    if (!gj_nullspace<7>(w)) return 0;
+    if (!gj_nullspace<7, kA, kPiv, kBas>(w)) return 0;
     double F1[9], F2[9], D[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) { F1[k] = w[kBas + k]; F2[k] = w[kBas + 9 + k]; }
@@ -296,7 +243,7 @@ HD inline int four_point(const double (&p1)[4][2], const double (&p2)[4][2], Col
 #pragma unroll
         for (int k = 0; k < 9; ++k) { w[kA + 18 * r + k] = ra[k]; w[kA + 18 * r + 9 + k] = rb[k]; }
     }
-    if (!gj_nullspace<8>(w)) return 0;
+    if (!gj_nullspace<8, kA, kPiv, kBas>(w)) return 0;
     double h[9], out[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) h[k] = w[kBas + k];
@@ -306,40 +253,118 @@ HD inline int four_point(const double (&p1)[4][2], const double (&p2)[4][2], Col
     return 1;
 }
 
+// ------------------------------------------------------------------------------------------------------ local optimisation
+// the fundamental matrix of the normal matrix's smallest eigenvector v (between normalised points): its smallest singular value
+// zeroed, de-normalised
+__device__ inline void f_from_vector(const double (&v)[9], const Norm& t1, const Norm& t2, double (&out)[9]) {
+    double a[3][3], V[3][3];          // a[c]: column c of F V ; V[c]: column c of V
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { a[c][r] = v[3 * r + c]; V[c][r] = c == r ? 1.0 : 0.0; }
+    onesided_jacobi3(a, V);
+    double nr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) nr[c] = (a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2];
+    const int lo = (nr[0] <= nr[1] && nr[0] <= nr[2]) ? 0 : (nr[1] <= nr[2] ? 1 : 2);      // the lower index among equals
+    double f[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s += c == lo ? 0.0 : a[c][r] * V[c][j];
+            f[3 * r + j] = s;
+        }
+    denormalise_f(f, t1, t2, out);
+}
+
 // ----------------------------------------------------------------------------------------------------------------- models
 struct TvInput { const double* uv0; const double* uv1; double err_px; };
 struct TvCtx { double thr2; };
-struct TvPoint { double x1, y1, x2, y2; };
+struct TvLds { double vec[9]; double cand[1][9]; int ok; };
 
-struct TvBase {                  // what the two models of ransac.h share: pixels in, the squared threshold
-    static constexpr int kHypWords = 9;
+template <class M>
+struct TvBase {                  // what the two models share: pixels in, the squared threshold, the re-fit but for its rows
+    static constexpr int kHypWords = 9, kHypThreads = kMsThreads, kHypLdsWords = kWords, kMaxCand = 1;
     using Input = TvInput;
     using Ctx = TvCtx;
-    using Point = TvPoint;
+    using Point = two_view::Point;
+    using Lds = TvLds;
+    using Tail = NoTail;
     static __device__ __forceinline__ Ctx context(const Input& in, int) { return {in.err_px * in.err_px}; }
     static __device__ __forceinline__ Point load(const Input& in, const Ctx&, int64_t i) {
         return {in.uv0[2 * i], in.uv0[2 * i + 1], in.uv1[2 * i], in.uv1[2 * i + 1]};
     }
+    static __device__ __forceinline__ bool inlier(const double* X, const Point& pt, const Ctx& c) {
+        return M::test(X, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
+    }
+    template <int K, class Emit>
+    static __device__ __forceinline__ void hypotheses(const Input& in, const Ctx& c, int64_t s0, const int64_t (&id)[K], double* column,
+                                                      Emit emit) {
+        sampled_solve<M>(in, c, s0, id, column, emit);
+    }
+    static __device__ __forceinline__ bool keeps(bool, int cur) { return cur >= M::kMinInliers; }
+    // the Hartley-normalised DLT of X's inliers: the model of the normal matrix's smallest eigenvector, de-normalised, unit norm,
+    // sign fixed; no candidate when the inliers coincide or the model is not finite
+    static __device__ __forceinline__ int refit(const Input& in, const Ctx& ctx, int64_t s0, int64_t n, const double* X, int cur, Lds& lds,
+                                       double* s_red) {
+        const double thr2 = ctx.thr2;
+        // per image: centroids, then the squared distances
+        double sm[4] = {0.0, 0.0, 0.0, 0.0};
+        for_each_corr<M>(in, ctx, s0, n, [&](int64_t, double x1, double y1, double x2, double y2) {
+            if (!M::test(X, x1, y1, x2, y2, thr2)) return;
+            sm[0] += x1; sm[1] += y1; sm[2] += x2; sm[3] += y2;
+        });
+        block_sum<4, kPairThreads>(sm, s_red);
+        Norm t1, t2;
+        t1.cx = sm[0] / (double)cur; t1.cy = sm[1] / (double)cur;
+        t2.cx = sm[2] / (double)cur; t2.cy = sm[3] / (double)cur;
+        double d2[2] = {0.0, 0.0};
+        for_each_corr<M>(in, ctx, s0, n, [&](int64_t, double x1, double y1, double x2, double y2) {
+            if (!M::test(X, x1, y1, x2, y2, thr2)) return;
+            const double ax = x1 - t1.cx, ay = y1 - t1.cy, bx = x2 - t2.cx, by = y2 - t2.cy;
+            d2[0] += ax * ax + ay * ay;
+            d2[1] += bx * bx + by * by;
+        });
+        block_sum<2, kPairThreads>(d2, s_red);
+        if (!norm_scale(d2[0], (double)cur, t1) || !norm_scale(d2[1], (double)cur, t2)) return 0;
+        double a[kNe];
+#pragma unroll
+        for (int q = 0; q < kNe; ++q) a[q] = 0.0;
+        for_each_corr<M>(in, ctx, s0, n, [&](int64_t, double x1, double y1, double x2, double y2) {
+            if (!M::test(X, x1, y1, x2, y2, thr2)) return;
+            M::accumulate(a, (x1 - t1.cx) * t1.s, (y1 - t1.cy) * t1.s, (x2 - t2.cx) * t2.s, (y2 - t2.cy) * t2.s);
+        });
+        smallest_eigenvectors<1>(a, s_red, lds.vec);
+        if (threadIdx.x == 0) {
+            double v[9], out[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) v[q] = lds.vec[q];
+            M::from_vector(v, t1, t2, out);
+            lds.ok = canonical9(out) ? 1 : 0;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) lds.cand[0][q] = out[q];
+        }
+        __syncthreads();
+        return lds.ok;
+    }
 };
 
-struct FModel : TvBase {         // fundamental matrices scored by the squared Sampson error in pixels
+struct FModel : TvBase<FModel>, Epipolar {     // fundamental matrices scored by the squared Sampson error in pixels
     static constexpr int kSample = 7, kMaxSol = LS2FM_SEVEN_POINT_MAX_SOLUTIONS, kMinGroup = 7, kMinInliers = 8;
-    static constexpr bool kIsF = true;
-    static HD inline bool test(const double* F, double x1, double y1, double x2, double y2, double thr2) {
-        return sampson2(F, x1, y1, x2, y2) <= thr2;       // NaN (0 / 0) is not an inlier
-    }
-    static __device__ __forceinline__ bool inlier(const double* F, const Point& pt, const Ctx& c) {
-        return test(F, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
-    }
     template <int S, class Emit>
     static HD inline int solve(const double (&p1)[7][2], const double (&p2)[7][2], Col<S> w, Emit emit) {
         return seven_point(p1, p2, w, emit);
     }
+    static __device__ inline void from_vector(const double (&v)[9], const Norm& t1, const Norm& t2, double (&out)[9]) {
+        f_from_vector(v, t1, t2, out);
+    }
 };
 
-struct HModel : TvBase {         // homographies scored by the squared forward transfer error in pixels
+struct HModel : TvBase<HModel> {     // homographies scored by the squared forward transfer error in pixels
     static constexpr int kSample = 4, kMaxSol = 1, kMinGroup = 4, kMinInliers = 4;
-    static constexpr bool kIsF = false;
     static HD inline bool test(const double* H, double x1, double y1, double x2, double y2, double thr2) {
         const double w3 = (H[6] * x1 + H[7] * y1) + H[8];
         if (!(fabs(w3) > DBL_EPSILON) || !is_finite(w3)) return false;
@@ -347,259 +372,32 @@ struct HModel : TvBase {         // homographies scored by the squared forward t
         const double dy = ((H[3] * x1 + H[4] * y1) + H[5]) / w3 - y2;
         return dx * dx + dy * dy <= thr2;
     }
-    static __device__ __forceinline__ bool inlier(const double* H, const Point& pt, const Ctx& c) {
-        return test(H, pt.x1, pt.y1, pt.x2, pt.y2, c.thr2);
-    }
     template <int S, class Emit>
     static HD inline int solve(const double (&p1)[4][2], const double (&p2)[4][2], Col<S> w, Emit emit) {
         return four_point(p1, p2, w, emit);
     }
-};
-
-// ---------------------------------------------------------------------------------------------------------------- kernels
-template <class M>
-__global__ void __launch_bounds__(kMsThreads)
-tv_minimal_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, int64_t m, double* __restrict__ Mout,
-                  int32_t* __restrict__ n_sol) {
-    __shared__ double s_buf[kWords * kMsThreads];
-    const int64_t i = (int64_t)blockIdx.x * kMsThreads + threadIdx.x;
-    if (i >= m) return;
-    constexpr int kK = M::kSample, kS = M::kMaxSol;
-    double a[kK][2], b[kK][2];
+    static __device__ __forceinline__ void accumulate(double (&a)[kNe], double x, double y, double u, double v) {      // the two DLT rows
+        const double ra[9] = {-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u};
+        const double rb[9] = {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v};
 #pragma unroll
-    for (int s = 0; s < kK; ++s) {
-        a[s][0] = uv0[2 * kK * i + 2 * s]; a[s][1] = uv0[2 * kK * i + 2 * s + 1];
-        b[s][0] = uv1[2 * kK * i + 2 * s]; b[s][1] = uv1[2 * kK * i + 2 * s + 1];
+        for (int i = 0; i < 9; ++i)
+#pragma unroll
+            for (int k = i; k < 9; ++k) a[sidx(i, k)] += ra[i] * ra[k] + rb[i] * rb[k];
     }
-    double* __restrict__ out = Mout + 9 * kS * i;
-    const int n = M::solve(a, b, Col<kMsThreads>{s_buf + threadIdx.x}, [&](int s, const double* e) {
-        for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
-    });
-    for (int q = 9 * n; q < 9 * kS; ++q) out[q] = 0.0;
-    n_sol[i] = n;
-}
-
-template <class M>
-__global__ void __launch_bounds__(kMsThreads)
-tv_hyp_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps, uint64_t seed, Ws w) {
-    const int p = blockIdx.y;
-    if (!w.active[p]) return;
-    __shared__ double s_buf[kWords * kMsThreads];
-    constexpr int kK = M::kSample, kS = M::kMaxSol;
-    const int tl = blockIdx.x * kMsThreads + threadIdx.x;
-    const int64_t slot = (int64_t)p * kRound + tl;
-    int32_t* __restrict__ cnt = w.counts + kS * slot;
-    for (int s = 0; s < kS; ++s) cnt[s] = 0;
-    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
-    const uint64_t t = (uint64_t)(w.trials[p] + tl);
-    int64_t id[kK];
-    int mask = 0;
-    if (sample_distinct(trial_key(seed, t), n, id)) {
-        double a[kK][2], b[kK][2];
-#pragma unroll
-        for (int s = 0; s < kK; ++s) {
-            a[s][0] = uv0[2 * (s0 + id[s])]; a[s][1] = uv0[2 * (s0 + id[s]) + 1];
-            b[s][0] = uv1[2 * (s0 + id[s])]; b[s][1] = uv1[2 * (s0 + id[s]) + 1];
-        }
-        double* __restrict__ out = w.hyp + kS * 9 * slot;
-        M::solve(a, b, Col<kMsThreads>{s_buf + threadIdx.x}, [&](int s, const double* e) {
-            for (int q = 0; q < 9; ++q) out[9 * s + q] = e[q];
-            mask |= 1 << s;
-        });
-    }
-    w.valid[slot] = mask;
-}
-
-// ------------------------------------------------------------------------------------------------------ local optimisation
-constexpr int kNe = 45;
-
-// the model of the normal matrix's smallest eigenvector v (between normalised points): F with its smallest singular value
-// zeroed, H as it is; de-normalised, unit norm, sign fixed.  false when not finite
-template <class M>
-__device__ inline bool model_from_vector(const double (&v)[9], const Norm& t1, const Norm& t2, double (&out)[9]) {
-    if constexpr (M::kIsF) {
-        double a[3][3], V[3][3];          // a[c]: column c of F V ; V[c]: column c of V
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) { a[c][r] = v[3 * r + c]; V[c][r] = c == r ? 1.0 : 0.0; }
-        onesided_jacobi3(a, V);
-        double nr[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) nr[c] = (a[c][0] * a[c][0] + a[c][1] * a[c][1]) + a[c][2] * a[c][2];
-        const int lo = (nr[0] <= nr[1] && nr[0] <= nr[2]) ? 0 : (nr[1] <= nr[2] ? 1 : 2);      // the lower index among equals
-        double f[9];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) s += c == lo ? 0.0 : a[c][r] * V[c][j];
-                f[3 * r + j] = s;
-            }
-        denormalise_f(f, t1, t2, out);
-    } else {
+    static __device__ inline void from_vector(const double (&v)[9], const Norm& t1, const Norm& t2, double (&out)[9]) {
         denormalise_h(v, t1, t2, out);
     }
-    return canonical9(out);
-}
+};
 
-template <class M>
-__global__ void __launch_bounds__(kPairThreads)
-tv_final_kernel(const double* __restrict__ uv0, const double* __restrict__ uv1, const int32_t* __restrict__ ps, double err_px, Ws w,
-                double* __restrict__ Mout, uint8_t* __restrict__ inliers, int32_t* __restrict__ num_inliers,
-                int32_t* __restrict__ trials, int32_t* __restrict__ best_trial, int32_t* __restrict__ success) {
-    __shared__ double s_red[(kPairThreads / 64) * kNe];
-    __shared__ double s_vec[9];
-    __shared__ double s_cand[9];
-    __shared__ int s_ok, s_int;
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int64_t s0 = ps[p], n = ps[p + 1] - s0;
-    const double thr2 = err_px * err_px;
-    const unsigned long long bk = w.best_key[p];
-    int cur = 0;
-    double X[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) X[q] = 0.0;
-    if (bk != 0ull) {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) X[q] = w.best[9 * p + q];
-        for (int64_t j = tid; j < n; j += kPairThreads)
-            cur += M::test(X, uv0[2 * (s0 + j)], uv0[2 * (s0 + j) + 1], uv1[2 * (s0 + j)], uv1[2 * (s0 + j) + 1], thr2) ? 1 : 0;
-        cur = block_count(cur, &s_int);
-    }
-    // every condition below is uniform over the workgroup: it comes from a block-wide sum or from LDS
-    for (int it = 0; it < kLoIters && cur >= M::kMinInliers; ++it) {
-        // Hartley normalisation of the inlier set, per image: centroids, then the squared distances
-        double sm[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            const double x1 = uv0[2 * (s0 + j)], y1 = uv0[2 * (s0 + j) + 1], x2 = uv1[2 * (s0 + j)], y2 = uv1[2 * (s0 + j) + 1];
-            if (!M::test(X, x1, y1, x2, y2, thr2)) continue;
-            sm[0] += x1; sm[1] += y1; sm[2] += x2; sm[3] += y2;
-        }
-        block_sum<4, kPairThreads>(sm, s_red);
-        Norm t1, t2;
-        t1.cx = sm[0] / (double)cur; t1.cy = sm[1] / (double)cur;
-        t2.cx = sm[2] / (double)cur; t2.cy = sm[3] / (double)cur;
-        double d2[2] = {0.0, 0.0};
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            const double x1 = uv0[2 * (s0 + j)], y1 = uv0[2 * (s0 + j) + 1], x2 = uv1[2 * (s0 + j)], y2 = uv1[2 * (s0 + j) + 1];
-            if (!M::test(X, x1, y1, x2, y2, thr2)) continue;
-            const double ax = x1 - t1.cx, ay = y1 - t1.cy, bx = x2 - t2.cx, by = y2 - t2.cy;
-            d2[0] += ax * ax + ay * ay;
-            d2[1] += bx * bx + by * by;
-        }
-        block_sum<2, kPairThreads>(d2, s_red);
-        if (!norm_scale(d2[0], (double)cur, t1) || !norm_scale(d2[1], (double)cur, t2)) break;
-        // normal matrix of the inliers' normalised rows, upper triangle, fixed-order sum
-        double a[kNe];
-#pragma unroll
-        for (int q = 0; q < kNe; ++q) a[q] = 0.0;
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            const double x1 = uv0[2 * (s0 + j)], y1 = uv0[2 * (s0 + j) + 1], x2 = uv1[2 * (s0 + j)], y2 = uv1[2 * (s0 + j) + 1];
-            if (!M::test(X, x1, y1, x2, y2, thr2)) continue;
-            const double x = (x1 - t1.cx) * t1.s, y = (y1 - t1.cy) * t1.s, u = (x2 - t2.cx) * t2.s, v = (y2 - t2.cy) * t2.s;
-            if constexpr (M::kIsF) {
-                const double r[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
-#pragma unroll
-                for (int i = 0; i < 9; ++i)
-#pragma unroll
-                    for (int k = i; k < 9; ++k) a[sidx(i, k)] += r[i] * r[k];
-            } else {
-                const double ra[9] = {-x, -y, -1.0, 0.0, 0.0, 0.0, u * x, u * y, u};
-                const double rb[9] = {0.0, 0.0, 0.0, -x, -y, -1.0, v * x, v * y, v};
-#pragma unroll
-                for (int i = 0; i < 9; ++i)
-#pragma unroll
-                    for (int k = i; k < 9; ++k) a[sidx(i, k)] += ra[i] * ra[k] + rb[i] * rb[k];
-            }
-        }
-        block_sum<kNe, kPairThreads>(a, s_red);
-        {
-            double v[9];
-            jacobi9(a, tid < 9 ? tid : 0, v);
-            if (tid < 9) {
-                double x = 0.0;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) x = eigen_rank9(a, k) == 0 ? v[k] : x;
-                s_vec[tid] = x;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double v[9], out[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) v[q] = s_vec[q];
-            const bool ok = model_from_vector<M>(v, t1, t2, out);
-#pragma unroll
-            for (int q = 0; q < 9; ++q) s_cand[q] = out[q];
-            s_ok = ok ? 1 : 0;
-        }
-        __syncthreads();
-        if (!s_ok) break;
-        int c = 0, chg = 0;
-        for (int64_t j = tid; j < n; j += kPairThreads) {
-            const double x1 = uv0[2 * (s0 + j)], y1 = uv0[2 * (s0 + j) + 1], x2 = uv1[2 * (s0 + j)], y2 = uv1[2 * (s0 + j) + 1];
-            const bool in = M::test(s_cand, x1, y1, x2, y2, thr2);
-            c += in ? 1 : 0;
-            chg += in != M::test(X, x1, y1, x2, y2, thr2) ? 1 : 0;
-        }
-        c = block_count(c, &s_int);
-        chg = block_count(chg, &s_int);
-        if (c < cur) break;
-#pragma unroll
-        for (int q = 0; q < 9; ++q) X[q] = s_cand[q];
-        cur = c;
-        if (chg == 0) break;
-    }
-    const bool ok = cur >= M::kMinInliers;
-    for (int64_t j = tid; j < n; j += kPairThreads)
-        inliers[s0 + j] =
-            ok && M::test(X, uv0[2 * (s0 + j)], uv0[2 * (s0 + j) + 1], uv1[2 * (s0 + j)], uv1[2 * (s0 + j) + 1], thr2) ? 1 : 0;
-    if (tid < 9) Mout[9 * p + tid] = ok ? X[tid] : 0.0;
-    if (tid == 0) {
-        num_inliers[p] = ok ? cur : 0;
-        trials[p] = w.trials[p];
-        best_trial[p] = bk != 0ull ? best_trial_of<M>(bk) : -1;
-        success[p] = ok ? 1 : 0;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------- host
-template <class M>
-int minimal_call(const double* uv0, const double* uv1, int64_t m, double* out, int32_t* n_solutions, void* stream) {
-    LS2FM_CHECK_ARG(m >= 0);
-    if (m == 0) return LS2FM_OK;
-    LS2FM_CHECK_ARG(uv0 && uv1 && out && n_solutions);
-    tv_minimal_kernel<M><<<(unsigned)((m + kMsThreads - 1) / kMsThreads), kMsThreads, 0, (hipStream_t)stream>>>(uv0, uv1, m, out,
-                                                                                                                n_solutions);
-    return ls2fm_launch_status();
-}
-
+// ls2fm_fundamental_matrix, ls2fm_homography
 template <class M>
 int ransac_call(const double* uv0, const double* uv1, const int32_t* pair_start, int32_t n_pairs, const ls2fm_pose_ransac_opts* opts,
                 double* model, uint8_t* inliers, int32_t* num_inliers, int32_t* trials, int32_t* best_trial, int32_t* success,
                 void* workspace, void* stream) {
     LS2FM_CHECK_ARG(n_pairs >= 1 && n_pairs <= LS2FM_RELPOSE_MAX_PAIRS && pair_start && opts_ok(opts) && opts->refine == 0);
     LS2FM_CHECK_ARG(model && num_inliers && trials && best_trial && success);
-    if (!workspace) return LS2FM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    Ws w;
-    const int st = run_rounds<M>({uv0, uv1, opts->max_error_px}, pair_start, n_pairs, uv0 && uv1 && inliers, opts, workspace, s, &w,
-                                 [&](const Ws& ws) {
-        tv_hyp_kernel<M><<<dim3(kRound / kMsThreads, (unsigned)n_pairs), kMsThreads, 0, s>>>(uv0, uv1, pair_start, opts->seed, ws);
-    });
-    if (st != LS2FM_OK) return st;
-    tv_final_kernel<M><<<(unsigned)n_pairs, kPairThreads, 0, s>>>(uv0, uv1, pair_start, opts->max_error_px, w, model, inliers,
-                                                                  num_inliers, trials, best_trial, success);
-    return ls2fm_launch_status();
-}
-
-template <class M>
-int64_t workspace_bytes(int32_t n_pairs, int64_t n_corr) {
-    if (n_pairs < 1 || n_pairs > LS2FM_RELPOSE_MAX_PAIRS || n_corr < 0) return LS2FM_ERR_INVALID_ARGUMENT;
-    return (int64_t)ws_layout<M>(n_pairs, nullptr, nullptr);
+    return estimate<M>({uv0, uv1, opts->max_error_px}, pair_start, n_pairs, uv0 && uv1 && inliers, opts, model, nullptr, inliers,
+                       num_inliers, trials, best_trial, success, workspace, stream);
 }
 
 }  // namespace

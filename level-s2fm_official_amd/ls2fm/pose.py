@@ -58,6 +58,25 @@ def _ragged(uv, xyz, view_start):
     return _ragged_common(uv, xyz, view_start, (3,), "uv", "xyz", "view_start")
 
 
+def _ransac(symbol, a, b, starts, extra_in, model_out, max_error_px, confidence, min_inlier_ratio, min_num_trials, max_num_trials, seed,
+            refine=False):
+    """One LO-RANSAC entry of the library: ls2fm_<symbol>(a, b, starts, G, *extra_in, opts, *model_out, inliers, num_inliers, trials,
+    best_trial, success, workspace, stream) with its workspace -> the dict entries every estimator returns"""
+    G, n, dev = starts.numel() - 1, a.shape[0], a.device
+    lib = _lib.load()
+    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
+                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 1 if refine else 0)
+    ws_bytes = getattr(lib, symbol + "_workspace_bytes")(G, n)
+    if ws_bytes < 0:
+        check(int(ws_bytes), symbol + "_workspace_bytes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    inl = torch.empty(n, dtype=torch.uint8, device=dev)
+    num, trials, best, succ = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(4))
+    check(getattr(lib, symbol)(ptr(a), ptr(b), ptr(starts), G, *map(ptr, extra_in), ctypes.byref(opts), *map(ptr, model_out), ptr(inl),
+                               ptr(num), ptr(trials), ptr(best), ptr(succ), ptr(ws), stream_ptr()), symbol)
+    return dict(inliers=inl.view(torch.bool), num_inliers=num, trials=trials, best_trial=best, success=succ.bool())
+
+
 def p3p(bearings, points):
     """Lambda Twist P3P of m minimal problems: bearings [m,3,3] (unit rows), points [m,3,3] (device) -> (poses [m,4,3,4] fp64,
     kept ones first, zero beyond; n_solutions int32 [m])"""
@@ -85,20 +104,10 @@ def absolute_pose(uv, xyz, intrinsics, view_start=None, max_error_px=12.0, confi
     V = vs.numel() - 1
     dev = uv.device
     intr = _intrinsics(intrinsics, V, dev)
-    lib = _lib.load()
-    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
-                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 1 if refine else 0)
-    ws_bytes = lib.ls2fm_absolute_pose_workspace_bytes(V, uv.shape[0])
-    if ws_bytes < 0:
-        check(int(ws_bytes), "ls2fm_absolute_pose_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     poses = torch.empty(V, 3, 4, dtype=torch.float64, device=dev)
-    inl = torch.empty(uv.shape[0], dtype=torch.uint8, device=dev)
-    num, trials, best, succ = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(4))
-    check(lib.ls2fm_absolute_pose(ptr(uv), ptr(xyz), ptr(vs), V, ptr(intr), ctypes.byref(opts), ptr(poses), ptr(inl), ptr(num),
-                                  ptr(trials), ptr(best), ptr(succ), ptr(ws), stream_ptr()), "ls2fm_absolute_pose")
-    return dict(poses=poses, inliers=inl.view(torch.bool), num_inliers=num, trials=trials, best_trial=best,
-                success=succ.bool(), view_start=vs)
+    r = _ransac("ls2fm_absolute_pose", uv, xyz, vs, (intr,), (poses,), max_error_px, confidence, min_inlier_ratio, min_num_trials,
+                max_num_trials, seed, refine)
+    return dict(poses=poses, **r, view_start=vs)
 
 
 def refine_pose(uv, xyz, intrinsics, poses, mask, view_start=None, loss_scale_px=1.0, max_iters=100):
@@ -192,18 +201,7 @@ def _ragged_common(a, b, starts, tail_b, name_a, name_b, name_s):
 def five_point(x1, x2):
     """Nister's five-point solver of m minimal problems: normalised points x1, x2 [m,5,2] (device) -> (E [m,10,3,3] fp64, unit
     Frobenius norm, kept ones first and zero beyond; n_solutions int32 [m])"""
-    a = torch.as_tensor(x1)
-    b = torch.as_tensor(x2)
-    _device(a, b)
-    a = a.to(torch.float64).reshape(-1, 5, 2).contiguous()
-    b = b.to(torch.float64).reshape(-1, 5, 2).contiguous()
-    if a.shape != b.shape:
-        raise ValueError(f"ls2fm.pose.five_point: x1 {tuple(a.shape)} against x2 {tuple(b.shape)}")
-    m = a.shape[0]
-    E = torch.empty(m, 10, 3, 3, dtype=torch.float64, device=a.device)
-    n = torch.empty(m, dtype=torch.int32, device=a.device)
-    check(_lib.load().ls2fm_five_point(ptr(a), ptr(b), m, ptr(E), ptr(n), stream_ptr()), "ls2fm_five_point")
-    return E, n
+    return _minimal(x1, x2, 5, 10, "ls2fm_five_point", "five_point", "x1", "x2")
 
 
 def relative_pose(uv0, uv1, intr0, intr1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.01,
@@ -217,21 +215,11 @@ def relative_pose(uv0, uv1, intr0, intr1, pair_start=None, max_error_px=4.0, con
     dev = uv0.device
     k0 = _intrinsics(intr0, P, dev)
     k1 = _intrinsics(intr1, P, dev)
-    lib = _lib.load()
-    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
-                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 0)
-    ws_bytes = lib.ls2fm_relative_pose_workspace_bytes(P, uv0.shape[0])
-    if ws_bytes < 0:
-        check(int(ws_bytes), "ls2fm_relative_pose_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     E = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
     poses = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
-    inl = torch.empty(uv0.shape[0], dtype=torch.uint8, device=dev)
-    num, trials, best, succ = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
-    check(lib.ls2fm_relative_pose(ptr(uv0), ptr(uv1), ptr(ps), P, ptr(k0), ptr(k1), ctypes.byref(opts), ptr(E), ptr(poses), ptr(inl),
-                                  ptr(num), ptr(trials), ptr(best), ptr(succ), ptr(ws), stream_ptr()), "ls2fm_relative_pose")
-    return dict(E=E, poses=poses, inliers=inl.view(torch.bool), num_inliers=num, trials=trials, best_trial=best,
-                success=succ.bool(), pair_start=ps)
+    r = _ransac("ls2fm_relative_pose", uv0, uv1, ps, (k0, k1), (E, poses), max_error_px, confidence, min_inlier_ratio, min_num_trials,
+                max_num_trials, seed)
+    return dict(E=E, poses=poses, **r, pair_start=ps)
 
 
 def triangulate(P0, P1, uv0, uv1, pair_start=None):
@@ -258,14 +246,14 @@ def triangulate(P0, P1, uv0, uv1, pair_start=None):
 DEGENERATE, CALIBRATED, UNCALIBRATED, PLANAR_OR_PANORAMIC = 1, 2, 3, 6
 
 
-def _minimal(x1, x2, k, n_sol, symbol, name):
+def _minimal(x1, x2, k, n_sol, symbol, name, name_a="uv0", name_b="uv1"):
     a = torch.as_tensor(x1)
     b = torch.as_tensor(x2)
     _device(a, b)
     a = a.to(torch.float64).reshape(-1, k, 2).contiguous()
     b = b.to(torch.float64).reshape(-1, k, 2).contiguous()
     if a.shape != b.shape:
-        raise ValueError(f"ls2fm.pose.{name}: uv0 {tuple(a.shape)} against uv1 {tuple(b.shape)}")
+        raise ValueError(f"ls2fm.pose.{name}: {name_a} {tuple(a.shape)} against {name_b} {tuple(b.shape)}")
     m = a.shape[0]
     out = torch.empty(m, n_sol, 3, 3, dtype=torch.float64, device=a.device)
     n = torch.empty(m, dtype=torch.int32, device=a.device)
@@ -286,23 +274,9 @@ def four_point_homography(uv0, uv1):
     return H[:, 0], n
 
 
-def _two_view_ransac(symbol, key, uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio, min_num_trials, max_num_trials, seed):
-    P = ps.numel() - 1
-    dev = uv0.device
-    lib = _lib.load()
-    opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
-                               int(max_num_trials), int(seed) & ((1 << 64) - 1), 0)
-    ws_bytes = getattr(lib, symbol + "_workspace_bytes")(P, uv0.shape[0])
-    if ws_bytes < 0:
-        check(int(ws_bytes), symbol + "_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    M = torch.empty(P, 3, 3, dtype=torch.float64, device=dev)
-    inl = torch.empty(uv0.shape[0], dtype=torch.uint8, device=dev)
-    num, trials, best, succ = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
-    check(getattr(lib, symbol)(ptr(uv0), ptr(uv1), ptr(ps), P, ctypes.byref(opts), ptr(M), ptr(inl), ptr(num), ptr(trials), ptr(best),
-                               ptr(succ), ptr(ws), stream_ptr()), symbol)
-    return {key: M, "inliers": inl.view(torch.bool), "num_inliers": num, "trials": trials, "best_trial": best,
-            "success": succ.bool(), "pair_start": ps}
+def _two_view_ransac(symbol, key, uv0, uv1, ps, **opts):
+    M = torch.empty(ps.numel() - 1, 3, 3, dtype=torch.float64, device=uv0.device)
+    return {key: M, **_ransac(symbol, uv0, uv1, ps, (), (M,), **opts), "pair_start": ps}
 
 
 def fundamental_matrix(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.25, min_num_trials=100,
@@ -312,8 +286,8 @@ def fundamental_matrix(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0
     two-view geometry RANSAC options.  -> dict(F [P,3,3] fp64 with x2h^T F x1h = 0 (zero for a failing pair), inliers bool [n],
     num_inliers, trials, best_trial, success (num_inliers >= 8), pair_start)"""
     uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
-    return _two_view_ransac("ls2fm_fundamental_matrix", "F", uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio,
-                            min_num_trials, max_num_trials, seed)
+    return _two_view_ransac("ls2fm_fundamental_matrix", "F", uv0, uv1, ps, max_error_px=max_error_px, confidence=confidence,
+                            min_inlier_ratio=min_inlier_ratio, min_num_trials=min_num_trials, max_num_trials=max_num_trials, seed=seed)
 
 
 def homography(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0.999, min_inlier_ratio=0.25, min_num_trials=100,
@@ -322,8 +296,8 @@ def homography(uv0, uv1, pair_start=None, max_error_px=4.0, confidence=0.999, mi
     forward transfer error |pi(H x1h) - x2|^2 in pixels.  Arguments as `fundamental_matrix`.  -> dict(H [P,3,3] fp64 with
     x2h ~ H x1h (zero for a failing pair), inliers, num_inliers, trials, best_trial, success (num_inliers >= 4), pair_start)"""
     uv0, uv1, ps = _ragged_pairs(uv0, uv1, pair_start)
-    return _two_view_ransac("ls2fm_homography", "H", uv0, uv1, ps, max_error_px, confidence, min_inlier_ratio, min_num_trials,
-                            max_num_trials, seed)
+    return _two_view_ransac("ls2fm_homography", "H", uv0, uv1, ps, max_error_px=max_error_px, confidence=confidence,
+                            min_inlier_ratio=min_inlier_ratio, min_num_trials=min_num_trials, max_num_trials=max_num_trials, seed=seed)
 
 
 def two_view_config(nE, okE, nF, okF, nH, min_num_inliers=15, min_E_F_inlier_ratio=0.95, max_H_inlier_ratio=0.8):
