@@ -1121,6 +1121,77 @@ int ls2fm_triangulate_tracks(const double* poses, const double* intrinsics, int3
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The incremental mapper's two per-step device calls (csrc/mapper.hip behind ls2fm.mapper; additions, the library stays ABI 13): the
+ * next-view score that COLMAP's IncrementalMapper::FindNextImages ranks candidates by, and the upkeep of the observation and point
+ * state that its CompleteTracks / FilterPoints do one point at a time.  The reference spends one PnP RANSAC per candidate view for
+ * the former and keeps the latter in Python lists (pipelines/LevelS2fM.py:247-281, Registration_Trad.py:183-215).
+ * tests/mapper_restate.py repeats every rule in numpy.  The track table (track_start, obs_view, obs_uv), poses, intrinsics, the
+ * centre, the pixel error e2, the depth zc and angle(X, w, w') are those of ls2fm_triangulate_tracks above (csrc/track_geom.h).
+ * Both calls: take a stream and read nothing back; write their status word; use no floating-point atomic (lanes meet in 64-bit
+ * integer OR / MAX and in plain stores of one value), so the results do not depend on the launch order and a rerun repeats every
+ * bit; launch shapes depend on the counts only, so they can be captured into a graph.  An observation o belongs to the track whose
+ * extent holds it, found by bisection over track_start (the last t with track_start[t] <= o; a well-formed table rises), and to
+ * none when that track's extent is malformed or does not hold o.  In a malformed table, which the status word reports, an
+ * observation may so be left without a track; nothing is ever read outside the arrays.
+ *
+ * ls2fm_view_scores: COLMAP's VisibilityPyramid score of every view, in one call.
+ *   obs_keep uint8 [n_obs], track_valid uint8 [n_tracks], registered uint8 [n_views] (non-zero = true); image_size fp64
+ *   [n_views][2] = (W, H) of every view, which the caller guarantees positive and finite.
+ *   seen        track t is SEEN iff track_valid[t] and one of its observations o has obs_keep[o] and registered[obs_view[o]].
+ *   counting    observation o COUNTS iff its track is seen and its own view is not registered.
+ *   num_visible int32 [n_views]: the counting observations of the view (what ls2fm.tracks.visible_points counts).
+ *   cells       of a counting observation (x, y) of view v: q = (64.0 * x) / W, cx = 63 when q >= 63, floor(q) when q > 0, else 0
+ *               (so pixels left of, on or beyond the borders land in the border cells); cy from y and H likewise.  An
+ *               observation with a non-finite x or y is counted in num_visible, marks no cell and sets LS2FM_MAPPER_BAD_PIXEL.
+ *   levels      l = 1 .. 6; level l has 2^l x 2^l cells, level 6 is the 64 x 64 grid of (cx, cy); a coarser cell is occupied iff
+ *               one of its four children is.
+ *   score       int64 [n_views]: sum over l of 4^l x (occupied cells of level l): a cell weighs as many as its level has cells.
+ *               One observation scores 4 + 16 + 64 + 256 + 1024 + 4096 = 5460, every cell occupied LS2FM_VIEW_SCORE_MAX
+ *               = sum 16^l = 17 895 696.  A registered view has no counting observation: score 0, num_visible 0.
+ *   Three launches after the memsets: the seen flags (one lane per observation, its track by bisection), a 4096-bit occupancy mask
+ *   per view joined with 64-bit OR atomics, and one wave per view that folds the mask through the levels with shifts, lane
+ *   exchanges and popcounts.
+ *   status int32 [1] (device, may be NULL): 0, or LS2FM_MAPPER_BAD_START (a track whose extent is not inside [0, n_obs], runs
+ *   backwards or exceeds LS2FM_TRACK_MAX_OBS: treated as empty), LS2FM_MAPPER_BAD_VIEW (an obs_view outside [0, n_views): the
+ *   observation belongs to no track), LS2FM_MAPPER_BAD_PIXEL, or-ed.  Checked on the device before use: the call never faults.
+ *   Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL array, n_views < 1, negative counts, n_tracks or
+ *   n_obs >= 2^31; LS2FM_ERR_WORKSPACE for a NULL workspace.
+ *
+ * ls2fm_update_observations: holds obs_keep / track_valid to the current poses and points, in one call.
+ *   X fp64 [n_tracks][3]; track_valid_in uint8 [n_tracks] (may be the array track_valid is written to).
+ *   kept        obs_keep[o] = 1 iff o's track t has track_valid_in[t], registered[obs_view[o]], zc > DBL_EPSILON of X[t] in that view
+ *               (the "in front" of the triangulation's inlier rule) and e2 <= max_error_px^2; all in fp64, a NaN keeps nothing.
+ *               One rule completes tracks into newly registered views and filters what drifted (COLMAP's complete and filter steps
+ *               share the threshold).  The pose of a view that is not registered is never read.
+ *   num_kept    int32 [n_tracks]: the kept observations of the track.
+ *   tri_angle   fp64 [n_tracks]: the LARGEST angle(X[t], w, w') over the pairs of the views of the track's first
+ *               LS2FM_TRACK_HYP_OBS kept observations in rising observation order (so rising view), in radians; 0 below two kept;
+ *               a NaN angle (X on a centre) does not count: the tri_angle convention of ls2fm_triangulate_tracks.
+ *   track_valid = num_kept >= 2 and tri_angle >= min_tri_angle (degrees, converted as min_tri_angle_deg * (pi / 180)).  X is not
+ *               changed; obs_keep of a track that ends invalid stays as the rule above gives it.
+ *   Five launches after the memset: one lane per observation (its track by bisection) for kept and one per view for the centres;
+ *   eight lanes per track that count and pack the views of the first 64 kept; one workgroup's prefix sum of the tracks' pair
+ *   counts; one lane per (track, pair) over that flat range, as ls2fm_triangulate_tracks numbers its hypotheses, joining the track's
+ *   angle by a 64-bit integer max of the angle's bits (angles are >= 0, so their bits order as they do); one lane per track.
+ *   status as above (LS2FM_MAPPER_BAD_START, LS2FM_MAPPER_BAD_VIEW); refused before anything is enqueued as above, and for
+ *   max_error_px not finite or <= 0 or min_tri_angle_deg not in [0, 90].
+ */
+#define LS2FM_MAPPER_BAD_START 1
+#define LS2FM_MAPPER_BAD_VIEW 2
+#define LS2FM_MAPPER_BAD_PIXEL 4
+#define LS2FM_VIEW_SCORE_MAX 17895696
+int64_t ls2fm_view_scores_workspace_bytes(int64_t n_tracks, int32_t n_views, int64_t n_obs);
+int ls2fm_view_scores(const int32_t* track_start, int64_t n_tracks, const int32_t* obs_view, const double* obs_uv, int64_t n_obs,
+                      const uint8_t* obs_keep, const uint8_t* track_valid, const uint8_t* registered, const double* image_size,
+                      int32_t n_views, int64_t* score, int32_t* num_visible, int32_t* status, void* workspace, void* stream);
+int64_t ls2fm_update_observations_workspace_bytes(int64_t n_tracks, int32_t n_views, int64_t n_obs);
+int ls2fm_update_observations(const double* poses, const double* intrinsics, const uint8_t* registered, int32_t n_views,
+                              const int32_t* track_start, int64_t n_tracks, const int32_t* obs_view, const double* obs_uv,
+                              int64_t n_obs, const double* X, const uint8_t* track_valid_in, double max_error_px,
+                              double min_tri_angle_deg, uint8_t* obs_keep, uint8_t* track_valid, int32_t* num_kept, double* tri_angle,
+                              int32_t* status, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

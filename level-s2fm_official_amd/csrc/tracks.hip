@@ -21,6 +21,7 @@
 //               fixed butterfly 4, 2, 1.  Every loop runs a wave-uniform number of rounds (the longest track of the wave, the
 //               others predicated off), so every shuffle, ballot and barrier is reached by all 64 lanes.
 #include "pose_math.h"
+#include "track_geom.h"
 #include "union_find.h"
 
 #include <algorithm>
@@ -30,18 +31,16 @@
 namespace {
 
 using namespace pose_math;
+using namespace track_geom;
 using namespace union_find;
 
 constexpr int kThreads = 256;
 constexpr int kScanThreads = 1024;
-constexpr int kHypObs = LS2FM_TRACK_HYP_OBS;
-constexpr int kMaxObs = LS2FM_TRACK_MAX_OBS;
 constexpr int kSub = 8;                        // lanes per track in tt_final
 constexpr int kFinalThreads = 64;
 constexpr int kFinalTracks = kFinalThreads / kSub;
 constexpr int kLoIters = 10;
 constexpr unsigned kMaxHypBlocks = 4096;       // ~5 x the 768 workgroups of tt_hyp the device holds at once; beyond it lanes stride
-constexpr double kPi = 3.14159265358979323846;
 
 static_assert(kHypObs == 64 && kFinalThreads == 64, "tt_final keeps a track's first 64 inliers and runs as one wave");
 
@@ -117,52 +116,9 @@ size_t tt_layout(int64_t T, int32_t V, char* base, TtWs* w) {
     return off;
 }
 
-// the extent of track t: false (n = 0) when it is not inside [0, n_obs], runs backwards or is too long
+// the extent of track t (track_geom.h): false (n = 0) when it is not inside [0, n_obs], runs backwards or is too long
 __device__ __forceinline__ bool track_extent(const TtIn& in, int64_t t, int64_t& s0, int& n) {
-    const int64_t a = in.track_start[t], b = in.track_start[t + 1];
-    const bool ok = a >= 0 && b >= a && b <= in.n_obs && b - a <= kMaxObs;
-    s0 = ok ? a : 0;
-    n = ok ? (int)(b - a) : 0;
-    return ok;
-}
-
-__device__ __forceinline__ int pair_count(int n) {
-    const int m = n < kHypObs ? n : kHypObs;
-    return m >= 2 ? m * (m - 1) / 2 : 0;
-}
-
-// pair q of m observations in lexicographic order: q = i (2 m - i - 1) / 2 + (j - i - 1)
-__device__ __forceinline__ void pair_of(int q, int m, int& i, int& j) {
-    int row = 0, left = q;
-    while (row < m - 2 && left >= m - 1 - row) {
-        left -= m - 1 - row;
-        ++row;
-    }
-    i = row;
-    j = row + 1 + left;
-}
-
-template <int NT>
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long& total, long long* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long x = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const long long y = __shfl_up(x, s, 64);
-        if (lane >= s) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const long long s = s_wave[w];
-        before += w < wave ? s : 0ll;
-        all += s;
-    }
-    __syncthreads();                                   // s_wave is written again by the next round
-    total = all;
-    return before + x - v;
+    return track_geom::track_extent(in.track_start, in.n_obs, t, s0, n);
 }
 
 __global__ void __launch_bounds__(kScanThreads)
@@ -173,9 +129,7 @@ tt_prepare(TtIn in, TtWs w, int32_t* __restrict__ status) {
     if (tid == 0) s_status = 0;
     __syncthreads();
     for (int v = tid; v < in.V; v += kScanThreads) {
-        const double* P = in.poses + 12 * (int64_t)v;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) w.centre[3 * (int64_t)v + k] = -((P[k] * P[3] + P[4 + k] * P[7]) + P[8 + k] * P[11]);
+        centre_of(in.poses + 12 * (int64_t)v, w.centre + 3 * (int64_t)v);
     }
     long long carry = 0;
     for (int64_t base = 0; base < in.T; base += kScanThreads) {
@@ -202,34 +156,13 @@ tt_prepare(TtIn in, TtWs w, int32_t* __restrict__ status) {
 __device__ __forceinline__ bool observe(const TtIn& in, int64_t o, const double (&X)[3], double& e2, double& depth) {
     const int32_t v = in.obs_view[o];
     if ((uint32_t)v >= (uint32_t)in.V) return false;
-    const double* __restrict__ P = in.poses + 12 * (int64_t)v;
-    const double* __restrict__ K = in.intr + 4 * (int64_t)v;
-    const double xc = ((P[0] * X[0] + P[1] * X[1]) + P[2] * X[2]) + P[3];
-    const double yc = ((P[4] * X[0] + P[5] * X[1]) + P[6] * X[2]) + P[7];
-    const double zc = ((P[8] * X[0] + P[9] * X[1]) + P[10] * X[2]) + P[11];
-    const double du = (K[0] * (xc / zc) + K[2]) - in.obs_uv[2 * o];
-    const double dv = (K[1] * (yc / zc) + K[3]) - in.obs_uv[2 * o + 1];
-    e2 = du * du + dv * dv;
-    depth = zc;
+    pixel_error(in.poses + 12 * (int64_t)v, in.intr + 4 * (int64_t)v, in.obs_uv[2 * o], in.obs_uv[2 * o + 1], X, e2, depth);
     return true;
 }
 
 __device__ __forceinline__ bool is_inlier(const TtIn& in, int64_t o, const double (&X)[3]) {
     double e2, z;
     return observe(in, o, X, e2, z) && z > DBL_EPSILON && e2 <= in.thr2;         // a NaN error is not an inlier
-}
-
-// min(a, pi - a) of the angle at X between the centres of views va and vb
-__device__ __forceinline__ double tri_angle_of(const double* __restrict__ centre, int32_t va, int32_t vb, const double (&X)[3]) {
-    const double* __restrict__ A = centre + 3 * (int64_t)va;
-    const double* __restrict__ B = centre + 3 * (int64_t)vb;
-    const double a0 = X[0] - A[0], a1 = X[1] - A[1], a2 = X[2] - A[2];
-    const double b0 = X[0] - B[0], b1 = X[1] - B[1], b2 = X[2] - B[2];
-    const double na = sqrt((a0 * a0 + a1 * a1) + a2 * a2), nb = sqrt((b0 * b0 + b1 * b1) + b2 * b2);
-    double c = ((a0 * b0 + a1 * b1) + a2 * b2) / (na * nb);
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);                  // a NaN stays a NaN
-    const double a = acos(c);
-    return a < kPi - a ? a : kPi - a;
 }
 
 // the hypothesis of observations oi, oj of one track: false when dropped
@@ -258,12 +191,7 @@ __global__ void __launch_bounds__(kThreads)
 tt_hyp(TtIn in, TtWs w, unsigned n_blocks) {
     const long long total = w.hyp_start[in.T];
     for (long long h = (long long)blockIdx.x * kThreads + threadIdx.x; h < total; h += (long long)n_blocks * kThreads) {
-        int64_t lo = 0, hi = in.T;                 // the last track with hyp_start <= h (tracks without a pair share an offset)
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (w.hyp_start[mid] <= h) lo = mid; else hi = mid;
-        }
-        const int64_t t = lo;
+        const int64_t t = last_not_above(w.hyp_start, in.T, h);      // tracks without a pair share an offset
         int64_t s0;
         int n;
         track_extent(in, t, s0, n);

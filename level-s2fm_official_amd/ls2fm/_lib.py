@@ -201,6 +201,11 @@ _SIGNATURES = {
     "ls2fm_triangulate_tracks_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "ls2fm_triangulate_tracks": (c_int32, [_P, _P, c_int32, _P, c_int64, _P, _P, c_int64, c_double, c_double, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P]),
+    "ls2fm_view_scores_workspace_bytes": (c_int64, [c_int64, c_int32, c_int64]),
+    "ls2fm_view_scores": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P]),
+    "ls2fm_update_observations_workspace_bytes": (c_int64, [c_int64, c_int32, c_int64]),
+    "ls2fm_update_observations": (c_int32, [_P, _P, _P, c_int32, _P, c_int64, _P, _P, c_int64, _P, _P, c_double, c_double, _P, _P, _P, _P,
+                                            _P, _P, _P]),
     "ls2fm_four_point_homography": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
     "ls2fm_fundamental_matrix_workspace_bytes": (c_int64, [c_int32, c_int64]),
     "ls2fm_homography_workspace_bytes": (c_int64, [c_int32, c_int64]),
