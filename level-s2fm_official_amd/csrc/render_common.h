@@ -154,6 +154,20 @@ __device__ __forceinline__ float sigma_of(float s, float alpha, float beta) {
     return alpha * (s >= 0.0f ? e : 1.0f - e);
 }
 
+// Layer-0 pre-activation of one hidden unit, w = its W0 row [0..34] and b0 [35] (a packed record, an LDS row or registers): two
+// fmaf chains over the even and the odd inputs, the odd tail, then their sum.  THE summation order of every evaluator of the
+// geometry MLP (thread per point, 16 lanes, wave): their results are bit identical because they all call this.
+__device__ __forceinline__ float layer0_preact(const float* __restrict__ w, const float (&u)[kInMax]) {
+    float a0 = w[kRecB0], a1 = 0.0f;
+#pragma unroll
+    for (int k = 0; k + 1 < kInMax; k += 2) {
+        a0 = fmaf(w[k], u[k], a0);
+        a1 = fmaf(w[k + 1], u[k + 1], a1);
+    }
+    a0 = fmaf(w[kInMax - 1], u[kInMax - 1], a0);
+    return a0 + a1;
+}
+
 // Geometry MLP forward with the weights streamed from the packed records (wave-uniform addresses ->
 // scalar loads; every FMA is a VALU op with one SGPR operand).  u[35] -> f[17] and, optionally,
 // r = W0^T (s' * w1_0)  (the vector whose contraction with d u / d p gives the analytic normal).
@@ -169,15 +183,8 @@ __device__ __forceinline__ void geometry_forward(const float* __restrict__ rec, 
 #pragma unroll 1
     for (int j = 0; j < kHidden; ++j) {
         const float* __restrict__ w = rec + j * kRecStride;
-        float a0 = w[kRecB0], a1 = 0.0f;
-#pragma unroll
-        for (int k = 0; k + 1 < kInMax; k += 2) {
-            a0 = fmaf(w[k], u[k], a0);
-            a1 = fmaf(w[k + 1], u[k + 1], a1);
-        }
-        a0 = fmaf(w[kInMax - 1], u[kInMax - 1], a0);
         float h, s1, s2;
-        softplus100(a0 + a1, h, s1, s2);
+        softplus100(layer0_preact(w, u), h, s1, s2);
 #pragma unroll
         for (int o = 0; o < kOut; ++o) f[o] = fmaf(w[kRecW1 + o], h, f[o]);
         if (WANT_R) {

@@ -2,17 +2,15 @@
 //
 //   sdf_eval      thread per point: 16 x 8 hash-grid gathers + 35->64 softplus(100) -> 64->17 MLP (weights as
 //                 wave-uniform scalar loads), sign / scale_mlp, optional background-sphere min, optional
-//                 analytic normal (second gather pass contracting the hash Jacobian with W0^T (s' * w1_0))
+//                 analytic normal (second gather pass contracting the hash Jacobian with W0^T (s' * w1_0));
+//                 16 lanes per point for the latency-bound small calls.
 //                 Replaces SDF.infer_sdf (models/SDF.py:55-78) where no graph is needed.
-//   sphere_trace  two lanes per ray (start end / far end), the reference's `while True` (models/SDF.py:149-200)
-//                 run to completion per ray without host round trips; the global trip count K of the reference is
-//                 recovered as max over rays of the first trip at which the ray's start end is finished.
+//   sphere_trace  the reference's `while True` (models/SDF.py:149-200) run to completion per ray without host round trips, as
+//                 trace_loop.h states it, on a lane, a 16-lane group or a wave per ray end; the global trip count K of the
+//                 reference is recovered as max over rays of the first trip at which the ray's start end is finished.
 #include <cstdlib>
 
-#include "render_common.h"
-#include "sdf_point.h"
-
-int ls2fm_launch_prep_sdf(const ls2fm_params* params, int n_levels, Packed* out, hipStream_t stream, int32_t* zero_word = nullptr);
+#include "trace_loop.h"
 
 namespace {
 
@@ -69,8 +67,7 @@ sdf_eval_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* 
     if (WANT_NORMAL) {
         float acc[3] = {0.f, 0.f, 0.f};
         float x[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) x[a] = (p[a] - fc.bmin[a]) / (fc.bmax[a] - fc.bmin[a]);
+        unit_cube(fc, p, x);
 #pragma unroll
         for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) {
             if (l < lv.n_levels) {
@@ -94,154 +91,14 @@ sdf_eval_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* 
     }
 }
 
-// two lanes per ray: side 0 = start end (from near), side 1 = far end
-__global__ void __launch_bounds__(256)
-sphere_trace_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* __restrict__ pk,
-                    const float* __restrict__ table, const float* __restrict__ ray0, const float* __restrict__ ray_dir,
-                    int64_t n_rays, float thr, int iters_max, float* __restrict__ near_out, float* __restrict__ far_out,
-                    float* __restrict__ track, float* __restrict__ t_end, float* __restrict__ track_sdf, int* __restrict__ trips) {
-    const int64_t tidg = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t r = tidg >> 1;
-    const int side = (int)(tidg & 1);
-    const bool live = r < n_rays;
-    const int64_t rr_ = live ? r : n_rays - 1;
-    const RayGeom g = load_ray(fc, ray0, ray_dir, rr_);
-    const float far = g.t_far;
-    float t_me = side ? g.t_far : g.t_near;
-    float p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-    float u[kInMax], f[kOut], dummy[kInMax];
-    bool bg;
-    encode_point(lv, fc, table, p, u);
-    geometry_forward<false>(pk->sdf, u, f, dummy);
-    float sdf_me = signed_sdf(fc, bg_sdf, bg_rad, f[0], p, &bg);
-    float raw_me = sdf_me;               // the field's value at the current point (sdf_me is zeroed / goes stale: (1), (6))
-    const bool want_raw = track_sdf != nullptr && side == 0;
-    if (live && side == 0) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
-    if (live && side == 1) t_end[r * (iters_max + 1)] = t_me;
-    bool unf = false;
-    int kfin = -1;
-    for (int k = 0;; ++k) {
-        if (fabsf(sdf_me) <= thr) sdf_me = 0.f;                          // (1) converged values are zeroed
-        const bool m = fabsf(sdf_me) > thr;
-        unf = k == 0 ? m : (unf && m);                                    // (2)
-        const int unf_start = __shfl((int)unf, (threadIdx.x & 63) & ~1, 64);
-        if (!unf_start && kfin < 0) kfin = k;                             // (3) this ray's start end is done at trip k
-        if (k == iters_max) break;
-        if (live && side == 0) {                                          // (5) pre-update start point -> track
-#pragma unroll
-            for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + k) * 3 + a] = p[a];
-            if (track_sdf) track_sdf[r * (iters_max + 1) + k] = raw_me;
-        }
-        const float t_before = t_me;
-        t_me = t_me + sdf_me;                                             // (4) both ends step with '+', clamp to far
-        if (t_me > far) t_me = far;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-        // (6) refresh only where unfinished; for the track's values also where a finished start end still moved (crossed
-        // ends keep stepping with their stale value: the reference evaluates those points afterwards, SDF.py:203)
-        if (unf || (want_raw && t_me != t_before)) {
-            encode_point(lv, fc, table, p, u);
-            geometry_forward<false>(pk->sdf, u, f, dummy);
-            raw_me = signed_sdf(fc, bg_sdf, bg_rad, f[0], p, &bg);
-            if (unf) sdf_me = raw_me;
-        }
-        const float t_other = __shfl_xor(t_me, 1, 64);
-        const float t_s = side ? t_other : t_me, t_e = side ? t_me : t_other;
-        unf = unf && (t_s < t_e);                                         // (7) crossed ends drop out
-        if (live && side == 1) t_end[r * (iters_max + 1) + k + 1] = t_me;
-    }
-    if (live && side == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + iters_max) * 3 + a] = p[a];
-        if (track_sdf) track_sdf[r * (iters_max + 1) + iters_max] = raw_me;
-    }
-    // global trip count = max over rays: one atomic per wave (same-address global atomics serialise: ~6 ns each)
-    int kmax = (live && side == 0) ? (kfin < 0 ? iters_max : kfin) : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, 64));
-    if ((threadIdx.x & 63) == 0 && kmax > 0) atomicMax(trips, kmax);
-}
-
-// ---- sphere tracing, one 16-lane group per ray END (four ends = two rays per wave).  The thread-per-end kernel above is
-// bound by the latency of its serial chain -- 11 SDF evaluations, each 16 levels of dependent gathers and 3.3 k scalar-operand
-// FMAs in ONE lane: 477 us for 8192 rays with one wave per CU.  Here lane jl of a group gathers level jl, the 35 inputs are
-// exchanged by shuffles, the lane evaluates hidden units jl, jl + 16, jl + 32, jl + 48 from an LDS copy of W0 and the sdf row is summed
-// in the thread-per-end kernel's order (bit-identical results): the same loop (steps 1-7 below are those of sphere_trace_kernel) with a ~10x shorter step.
-constexpr int kW0Stride = 36;       // W0[j][0..34], b0[j] : 16-byte aligned rows, 2-way bank conflicts at most
-
-// f += w[J] * (lane J of this lane's 16-lane row).h for J = 0 .. 15, one fmaf chain; the broadcast is a DPP row_share operand
-// (full-rate VALU), not an LDS permute
-template <int J>
-__device__ __forceinline__ float row_chain(const float* __restrict__ w, float h, float f) {
-    if constexpr (J < 16) {
-        const float hv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(h), 0x150 + J, 0xF, 0xF, false));
-        return row_chain<J + 1>(w, h, fmaf(w[J], hv, f));
-    } else {
-        return f;
-    }
-}
-
-__device__ __forceinline__ float group_sdf(const LevelSet& lv, const FieldC& fc, int bg_sdf, float bg_rad,
-                                           const float* __restrict__ table, const float* __restrict__ s_w0,
-                                           const float* __restrict__ s_w1, float b1_0, const float p[3], int jl, int gbase) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = (p[a] - fc.bmin[a]) / (fc.bmax[a] - fc.bmin[a]);
-    float y0 = 0.f, y1 = 0.f;
-    if (jl < lv.n_levels) {
-        Cell c;
-        locate(x, lv.scale[jl], lv.res[jl], lv.size[jl], lv.offset[jl], lv.hashed[jl], c);
-        float2 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float wt = corner_weight(c.w, k);
-            y0 = fmaf(wt, v[k].x, y0);
-            y1 = fmaf(wt, v[k].y, y1);
-        }
-    }
-    float u[kInMax];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) u[a] = p[a] / fc.rescale;
-#pragma unroll
-    for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) {
-        u[3 + 2 * l] = __shfl(y0, gbase + l, 64);
-        u[4 + 2 * l] = __shfl(y1, gbase + l, 64);
-    }
-    float h[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float* __restrict__ w = s_w0 + (jl + 16 * q) * kW0Stride;
-        float a0 = w[kRecB0], a1 = 0.0f;           // same two-chain order as geometry_forward
-#pragma unroll
-        for (int k = 0; k + 1 < kInMax; k += 2) {
-            a0 = fmaf(w[k], u[k], a0);
-            a1 = fmaf(w[k + 1], u[k + 1], a1);
-        }
-        a0 = fmaf(w[kInMax - 1], u[kInMax - 1], a0);
-        h[q] = softplus100_value(a0 + a1);
-    }
-    // the sdf row in geometry_forward's order (j = 0 .. 63, one fmaf chain): every lane of the group forms the same sum, and
-    // the result is BIT-IDENTICAL to the thread-per-point kernels (a point evaluates the same in a small and in a large call)
-    float f0 = b1_0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) f0 = row_chain<0>(s_w1 + 16 * q, h[q], f0);
-    bool bg;
-    return signed_sdf(fc, bg_sdf, bg_rad, f0, p, &bg);
-}
-
-// sdf only, 16 lanes per point: the latency-bound small calls of infer_sdf(mode="ret_sdf") (thread-per-point: ~90 us however
-// few the points)
+// sdf only, 16 lanes per point (group_sdf): the latency-bound small calls of infer_sdf(mode="ret_sdf") (thread-per-point: ~90 us
+// however few the points)
 __global__ void __launch_bounds__(256)
 sdf_eval_wide_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* __restrict__ pk,
                      const float* __restrict__ table, const float* __restrict__ pts, int64_t n, float* __restrict__ sdf_out) {
     __shared__ float s_w0[kHidden * kW0Stride];
     __shared__ float s_w1[kHidden];
-    for (int q = threadIdx.x; q < kHidden * kW0Stride; q += 256) s_w0[q] = pk->sdf[(q / kW0Stride) * kRecStride + q % kW0Stride];
-    for (int q = threadIdx.x; q < kHidden; q += 256) s_w1[q] = pk->sdf[q * kRecStride + kRecW1];
+    stage_weights(pk->sdf, s_w0, s_w1, 1);
     const float b1_0 = pk->sdf[kHidden * kRecStride];
     __syncthreads();
     const int lane = threadIdx.x & 63, jl = lane & 15, gbase = lane & 48;
@@ -258,8 +115,6 @@ sdf_eval_wide_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Pac
 // pass over j = 0 .. 63 with unit j's h and s' w1_0 broadcast by DPP, in which the lane advances the sdf row (every lane),
 // feature row 1 + jl and r[jl], r[16 + jl], r[32 + jl] -- each the same fmaf chain over j as geometry_forward's; the normal's
 // sum over (level, corner) runs through the lanes in level order.  Every sum in the thread-per-point order: BIT-IDENTICAL outputs.
-constexpr int kW1Stride = kOut;         // 17: odd, the 16 lanes' feature weights of one unit are conflict-free
-
 template <bool WANT_R, int J>
 __device__ __forceinline__ void full_chain(const float* __restrict__ w0, const float* __restrict__ w1, float h, float g, int jl,
                                            float& f0, float& fm, float (&r)[3]) {
@@ -287,8 +142,7 @@ sdf_eval_wide_full_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, cons
     __shared__ float s_w0[kHidden * kW0Stride + 16];          // + 16: the k = 32 + jl reads of the last row stay inside
     __shared__ float s_w1[kHidden * kW1Stride];
     __shared__ float s_r[16][48];                             // r[0 .. 34] of the group's point
-    for (int q = threadIdx.x; q < kHidden * kW0Stride; q += 256) s_w0[q] = pk->sdf[(q / kW0Stride) * kRecStride + q % kW0Stride];
-    for (int q = threadIdx.x; q < kHidden * kW1Stride; q += 256) s_w1[q] = pk->sdf[(q / kW1Stride) * kRecStride + kRecW1 + q % kW1Stride];
+    stage_weights(pk->sdf, s_w0, s_w1, kW1Stride);
     if (threadIdx.x < 16) s_w0[kHidden * kW0Stride + threadIdx.x] = 0.f;
     __syncthreads();
     const int lane = threadIdx.x & 63, jl = lane & 15, gbase = lane & 48, grp = threadIdx.x >> 4;
@@ -296,8 +150,7 @@ sdf_eval_wide_full_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, cons
     const int64_t ii = i < n ? i : n - 1;
     const float p[3] = {pts[ii * 3], pts[ii * 3 + 1], pts[ii * 3 + 2]};
     float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = (p[a] - fc.bmin[a]) / (fc.bmax[a] - fc.bmin[a]);
+    unit_cube(fc, p, x);
     // ---- this lane's level: corner values (kept for the normal) and the trilinear value
     const bool has_level = jl < lv.n_levels;
     float2 v[8];
@@ -308,15 +161,7 @@ sdf_eval_wide_full_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, cons
     c.w[0] = c.w[1] = c.w[2] = 0.f;
     if (has_level) {
         scale_l = lv.scale[jl];
-        locate(x, scale_l, lv.res[jl], lv.size[jl], lv.offset[jl], lv.hashed[jl], c);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float wt = corner_weight(c.w, k);
-            y0 = fmaf(wt, v[k].x, y0);
-            y1 = fmaf(wt, v[k].y, y1);
-        }
+        gather_level(lv, table, jl, x, c, v, y0, y1);
     }
     float u[kInMax];
 #pragma unroll
@@ -331,16 +176,8 @@ sdf_eval_wide_full_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, cons
     float f0 = pk->sdf[kHidden * kRecStride], fm = pk->sdf[kHidden * kRecStride + 1 + jl], r[3] = {0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
-        const float* __restrict__ w = s_w0 + (jl + 16 * q) * kW0Stride;
-        float a0 = w[kRecB0], a1 = 0.0f;           // same two-chain order as geometry_forward
-#pragma unroll
-        for (int k = 0; k + 1 < kInMax; k += 2) {
-            a0 = fmaf(w[k], u[k], a0);
-            a1 = fmaf(w[k + 1], u[k + 1], a1);
-        }
-        a0 = fmaf(w[kInMax - 1], u[kInMax - 1], a0);
         float h, s1, s2;
-        softplus100(a0 + a1, h, s1, s2);
+        softplus100(layer0_preact(s_w0 + (jl + 16 * q) * kW0Stride, u), h, s1, s2);
         const float g = s1 * s_w1[(jl + 16 * q) * kW1Stride];
         full_chain<WANT_NORMAL, 0>(s_w0 + 16 * q * kW0Stride, s_w1 + 16 * q * kW1Stride, h, g, jl, f0, fm, r);
     }
@@ -385,6 +222,46 @@ sdf_eval_wide_full_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, cons
     }
 }
 
+// ---- sphere tracing: trace_loop.h's steps (1)-(7) on three layouts of a ray's two ends, each with the exit k == iters_max and the
+// stores of ls2fm_sphere_trace (near / far, the start end's track and the field's values there, the far end's t after every trip,
+// the trip count).  The reference's global trip count K is the max over rays of the first trip at which the ray's start end is
+// finished: one atomic per wave (same-address global atomics serialise: ~6 ns each).
+//
+// One lane per end: bound by the latency of its serial chain (11 evaluations in ONE lane: 477 us for 8192 rays with one wave per CU),
+// but no redundant lanes -- the kernel for tens of thousands of rays.
+__global__ void __launch_bounds__(256)
+sphere_trace_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* __restrict__ pk,
+                    const float* __restrict__ table, const float* __restrict__ ray0, const float* __restrict__ ray_dir,
+                    int64_t n_rays, float thr, int iters_max, float* __restrict__ near_out, float* __restrict__ far_out,
+                    float* __restrict__ track, float* __restrict__ t_end, float* __restrict__ track_sdf, int* __restrict__ trips) {
+    const int64_t tidg = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t r = tidg >> 1;
+    const bool live = r < n_rays;
+    const RayGeom g = load_ray(fc, ray0, ray_dir, live ? r : n_rays - 1);
+    const LaneEnds ends{lv, fc, bg_sdf, bg_rad, pk->sdf, table, (int)(tidg & 1)};
+    const bool start = live && ends.side == 0, end = live && ends.side == 1;
+    TraceEnd e;
+    trace_begin(ends, g, e);
+    if (start) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
+    if (end) t_end[r * (iters_max + 1)] = e.t;
+    const bool want_raw = track_sdf != nullptr && ends.side == 0;
+    int kfin = -1;
+    for (int k = 0;; ++k) {
+        trace_mask(e, thr, k);
+        if (!ends.start_unfinished(e.unf) && kfin < 0) kfin = k;          // (3) this ray's start end is done at trip k
+        if (k == iters_max) break;
+        if (start) store_track_point(e, r, iters_max, k, track, track_sdf);       // (5) pre-update start point -> track
+        const bool moved = trace_step(e, g.t_far);
+        trace_refresh(ends, g, e, want_raw && moved);
+        trace_cross(ends, e, k);
+        if (end) t_end[r * (iters_max + 1) + k + 1] = e.t;
+    }
+    if (start) store_track_point(e, r, iters_max, iters_max, track, track_sdf);
+    const int kmax = wave_max(start ? (kfin < 0 ? iters_max : kfin) : 0);
+    if ((threadIdx.x & 63) == 0 && kmax > 0) atomicMax(trips, kmax);
+}
+
+// One 16-lane group per end, 8 rays per 256-thread workgroup: the latency-bound stage-loop sizes.
 __global__ void __launch_bounds__(256)
 sphere_trace_wide_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* __restrict__ pk,
                          const float* __restrict__ table, const float* __restrict__ ray0, const float* __restrict__ ray_dir,
@@ -392,190 +269,72 @@ sphere_trace_wide_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const
                          float* __restrict__ track, float* __restrict__ t_end, float* __restrict__ track_sdf, int* __restrict__ trips) {
     __shared__ float s_w0[kHidden * kW0Stride];
     __shared__ float s_w1[kHidden];
-    for (int q = threadIdx.x; q < kHidden * kW0Stride; q += 256) s_w0[q] = pk->sdf[(q / kW0Stride) * kRecStride + q % kW0Stride];
-    for (int q = threadIdx.x; q < kHidden; q += 256) s_w1[q] = pk->sdf[q * kRecStride + kRecW1];
+    stage_weights(pk->sdf, s_w0, s_w1, 1);
     const float b1_0 = pk->sdf[kHidden * kRecStride];
     __syncthreads();
-    const int lane = threadIdx.x & 63, jl = lane & 15, gq = lane >> 4, gbase = lane & 48;
-    const int side = gq & 1;
+    const int lane = threadIdx.x & 63, gq = lane >> 4;
     const int64_t r = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (gq >> 1);
     const bool live = r < n_rays;
-    const int64_t rr_ = live ? r : n_rays - 1;
-    const RayGeom g = load_ray(fc, ray0, ray_dir, rr_);
-    const float far = g.t_far;
-    float t_me = side ? g.t_far : g.t_near;
-    float p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-    float sdf_me = group_sdf(lv, fc, bg_sdf, bg_rad, table, s_w0, s_w1, b1_0, p, jl, gbase);
-    float raw_me = sdf_me;               // the field's value at the current point (see sphere_trace_kernel)
-    const bool want_raw = track_sdf != nullptr && side == 0;
-    const bool writer = live && jl == 0;
-    if (writer && side == 0) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
-    if (writer && side == 1) t_end[r * (iters_max + 1)] = t_me;
-    bool unf = false;
+    const RayGeom g = load_ray(fc, ray0, ray_dir, live ? r : n_rays - 1);
+    const GroupEnds ends{lv, fc, bg_sdf, bg_rad, table, s_w0, s_w1, b1_0, gq & 1, lane & 15, lane & 48};
+    const bool start = live && ends.writer() && ends.side == 0, end = live && ends.writer() && ends.side == 1;
+    TraceEnd e;
+    trace_begin(ends, g, e);
+    if (start) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
+    if (end) t_end[r * (iters_max + 1)] = e.t;
+    const bool want_raw = track_sdf != nullptr && ends.side == 0;        // group-uniform, unlike `start`
     int kfin = -1;
     for (int k = 0;; ++k) {
-        if (fabsf(sdf_me) <= thr) sdf_me = 0.f;                          // (1) converged values are zeroed
-        const bool m = fabsf(sdf_me) > thr;
-        unf = k == 0 ? m : (unf && m);                                    // (2)
-        const int unf_start = __shfl((int)unf, lane & ~16, 64);           // the start end's group of this ray
-        if (!unf_start && kfin < 0) kfin = k;                             // (3) this ray's start end is done at trip k
+        trace_mask(e, thr, k);
+        if (!ends.start_unfinished(e.unf) && kfin < 0) kfin = k;          // (3) this ray's start end is done at trip k
         if (k == iters_max) break;
-        if (writer && side == 0) {                                        // (5) pre-update start point -> track
-#pragma unroll
-            for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + k) * 3 + a] = p[a];
-            if (track_sdf) track_sdf[r * (iters_max + 1) + k] = raw_me;
-        }
-        const float t_before = t_me;
-        t_me = t_me + sdf_me;                                             // (4) both ends step with '+', clamp to far
-        if (t_me > far) t_me = far;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-        if (unf || (want_raw && t_me != t_before)) {                      // (6) group-uniform
-            // compiler barrier: without it the 144 weight values a lane reads from LDS per evaluation are hoisted out of the
-            // trip loop into registers (256 VGPRs + 44 AGPRs, one wave per SIMD) -- and a kernel running BESIDE this one
-            // (ls2fm.stage: the render's gather pass) loses more than half of its waves on every SIMD this kernel sits on
-            __asm__ volatile("" ::: "memory");
-            raw_me = group_sdf(lv, fc, bg_sdf, bg_rad, table, s_w0, s_w1, b1_0, p, jl, gbase);
-            if (unf) sdf_me = raw_me;
-        }
-        const float t_other = __shfl_xor(t_me, 16, 64);
-        const float t_s = side ? t_other : t_me, t_e = side ? t_me : t_other;
-        unf = unf && (t_s < t_e);                                         // (7) crossed ends drop out
-        if (writer && side == 1) t_end[r * (iters_max + 1) + k + 1] = t_me;
+        if (start) store_track_point(e, r, iters_max, k, track, track_sdf);       // (5) pre-update start point -> track
+        const bool moved = trace_step(e, g.t_far);
+        trace_refresh(ends, g, e, want_raw && moved);
+        trace_cross(ends, e, k);
+        if (end) t_end[r * (iters_max + 1) + k + 1] = e.t;
     }
-    if (writer && side == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + iters_max) * 3 + a] = p[a];
-        if (track_sdf) track_sdf[r * (iters_max + 1) + iters_max] = raw_me;
-    }
-    int kmax = (writer && side == 0) ? (kfin < 0 ? iters_max : kfin) : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, 64));
+    if (start) store_track_point(e, r, iters_max, iters_max, track, track_sdf);
+    const int kmax = wave_max(start ? (kfin < 0 ? iters_max : kfin) : 0);
     if (lane == 0 && kmax > 0) atomicMax(trips, kmax);
 }
 
-// ---- sphere tracing, one WAVE per ray end (a 128-thread workgroup = one ray).  At the stage loops' ray counts (1024 rays) the
-// 16-lane kernel above leaves the chip almost idle (one wave on half the SIMDs) and spends its step on 144 LDS weight reads and
-// 140 FMAs per lane.  Here lane j owns hidden unit j with its W0 row in registers for the whole trace, lanes 0-15 gather the 16
-// levels, the 32 encoding values are broadcast as scalars (v_readlane) and the sdf row is the same j = 0 .. 63 fmaf chain fed by
-// v_readlane -- every sum in the order of geometry_forward, so the result is BIT-IDENTICAL to the other two tracing kernels.
-// The two ends of a ray exchange their parameter through LDS once per trip (step 7).
-__device__ __forceinline__ float lane_bcast(float v, int src) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
-template <int J>
-__device__ __forceinline__ float wave_chain(float w1_me, float h, float f) {
-    if constexpr (J < kHidden) {
-        const float hv = lane_bcast(h, J);
-        const float wv = lane_bcast(w1_me, J);
-        return wave_chain<J + 1>(w1_me, h, fmaf(wv, hv, f));
-    } else {
-        return f;
-    }
-}
-
-__device__ __forceinline__ float wave_sdf(const LevelSet& lv, const FieldC& fc, int bg_sdf, float bg_rad,
-                                          const float* __restrict__ table, const float (&w)[kInMax + 1], float w1_me, float b1_0,
-                                          const float p[3], int lane) {
-    float x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = (p[a] - fc.bmin[a]) / (fc.bmax[a] - fc.bmin[a]);
-    float y0 = 0.f, y1 = 0.f;
-    if (lane < lv.n_levels) {
-        Cell c;
-        locate(x, lv.scale[lane], lv.res[lane], lv.size[lane], lv.offset[lane], lv.hashed[lane], c);
-        float2 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float wt = corner_weight(c.w, k);
-            y0 = fmaf(wt, v[k].x, y0);
-            y1 = fmaf(wt, v[k].y, y1);
-        }
-    }
-    float u[kInMax];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) u[a] = p[a] / fc.rescale;
-#pragma unroll
-    for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) {
-        u[3 + 2 * l] = lane_bcast(y0, l);
-        u[4 + 2 * l] = lane_bcast(y1, l);
-    }
-    float a0 = w[kRecB0], a1 = 0.0f;               // same two-chain order as geometry_forward
-#pragma unroll
-    for (int k = 0; k + 1 < kInMax; k += 2) {
-        a0 = fmaf(w[k], u[k], a0);
-        a1 = fmaf(w[k + 1], u[k + 1], a1);
-    }
-    a0 = fmaf(w[kInMax - 1], u[kInMax - 1], a0);
-    const float h = softplus100_value(a0 + a1);
-    const float f0 = wave_chain<0>(w1_me, h, b1_0);
-    bool bg;
-    return signed_sdf(fc, bg_sdf, bg_rad, f0, p, &bg);
-}
-
+// One WAVE per end, one ray per 128-thread workgroup (the grid is n_rays workgroups).  At the stage loops' ray counts (1024 rays)
+// the 16-lane kernel leaves the chip almost idle (one wave on half the SIMDs) and spends its step on 144 LDS weight reads and
+// 140 FMAs per lane; here the W0 row stays in registers for the whole trace.
 __global__ void __launch_bounds__(128)
 sphere_trace_wave_kernel(LevelSet lv, FieldC fc, int bg_sdf, float bg_rad, const Packed* __restrict__ pk,
                          const float* __restrict__ table, const float* __restrict__ ray0, const float* __restrict__ ray_dir,
                          int64_t n_rays, float thr, int iters_max, float* __restrict__ near_out, float* __restrict__ far_out,
                          float* __restrict__ track, float* __restrict__ t_end, float* __restrict__ track_sdf, int* __restrict__ trips) {
     __shared__ float s_t[2][2];
-    const int lane = threadIdx.x & 63, side = threadIdx.x >> 6;
-    const int64_t r = blockIdx.x;                  // the grid is n_rays workgroups
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x;
     float w[kInMax + 1];
 #pragma unroll
     for (int k = 0; k <= kInMax; ++k) w[k] = pk->sdf[lane * kRecStride + k];
-    const float w1_me = pk->sdf[lane * kRecStride + kRecW1];
-    const float b1_0 = pk->sdf[kHidden * kRecStride];
     const RayGeom g = load_ray(fc, ray0, ray_dir, r);
-    const float far = g.t_far;
-    float t_me = side ? g.t_far : g.t_near;
-    float p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-    float sdf_me = wave_sdf(lv, fc, bg_sdf, bg_rad, table, w, w1_me, b1_0, p, lane);
-    float raw_me = sdf_me;               // the field's value at the current point (see sphere_trace_kernel)
-    const bool want_raw = track_sdf != nullptr && side == 0;
-    const bool writer = lane == 0;
-    if (writer && side == 0) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
-    if (writer && side == 1) t_end[r * (iters_max + 1)] = t_me;
-    bool unf = false;
+    const WaveEnds ends{lv, fc, bg_sdf, bg_rad, table, w, pk->sdf[lane * kRecStride + kRecW1], pk->sdf[kHidden * kRecStride], s_t,
+                        (int)(threadIdx.x >> 6), lane};
+    const bool start = ends.writer() && ends.side == 0, end = ends.writer() && ends.side == 1;
+    TraceEnd e;
+    trace_begin(ends, g, e);
+    if (start) { near_out[r] = g.t_near; far_out[r] = g.t_far; }
+    if (end) t_end[r * (iters_max + 1)] = e.t;
+    const bool want_raw = track_sdf != nullptr && ends.side == 0;        // wave-uniform
     int kfin = -1;
     for (int k = 0;; ++k) {
-        if (fabsf(sdf_me) <= thr) sdf_me = 0.f;                          // (1) converged values are zeroed
-        const bool m = fabsf(sdf_me) > thr;
-        unf = k == 0 ? m : (unf && m);                                    // (2)
-        if (side == 0 && !unf && kfin < 0) kfin = k;                      // (3) this ray's start end is done at trip k
+        trace_mask(e, thr, k);
+        if (!ends.start_unfinished(e.unf) && kfin < 0) kfin = k;          // (3) this ray's start end is done at trip k
         if (k == iters_max) break;
-        if (writer && side == 0) {                                        // (5) pre-update start point -> track
-#pragma unroll
-            for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + k) * 3 + a] = p[a];
-            if (track_sdf) track_sdf[r * (iters_max + 1) + k] = raw_me;
-        }
-        const float t_before = t_me;
-        t_me = t_me + sdf_me;                                             // (4) both ends step with '+', clamp to far
-        if (t_me > far) t_me = far;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = g.o[a] + t_me * g.d[a];
-        if (unf || (want_raw && t_me != t_before)) {                      // (6) wave-uniform
-            raw_me = wave_sdf(lv, fc, bg_sdf, bg_rad, table, w, w1_me, b1_0, p, lane);
-            if (unf) sdf_me = raw_me;
-        }
-        if (writer) s_t[k & 1][side] = t_me;                              // the other end's parameter: one barrier per trip
-        __syncthreads();                                                  // (slot k & 1 is rewritten two barriers later)
-        const float t_other = s_t[k & 1][side ^ 1];
-        const float t_s = side ? t_other : t_me, t_e = side ? t_me : t_other;
-        unf = unf && (t_s < t_e);                                         // (7) crossed ends drop out
-        if (writer && side == 1) t_end[r * (iters_max + 1) + k + 1] = t_me;
+        if (start) store_track_point(e, r, iters_max, k, track, track_sdf);       // (5) pre-update start point -> track
+        const bool moved = trace_step(e, g.t_far);
+        trace_refresh(ends, g, e, want_raw && moved);
+        trace_cross(ends, e, k);
+        if (end) t_end[r * (iters_max + 1) + k + 1] = e.t;
     }
-    if (writer && side == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) track[(r * (iters_max + 1) + iters_max) * 3 + a] = p[a];
-        if (track_sdf) track_sdf[r * (iters_max + 1) + iters_max] = raw_me;
+    if (start) {
+        store_track_point(e, r, iters_max, iters_max, track, track_sdf);
         const int kmax = kfin < 0 ? iters_max : kfin;
         if (kmax > 0) atomicMax(trips, kmax);
     }
@@ -589,6 +348,36 @@ static bool field_ok(const ls2fm_field_desc* f, const ls2fm_grid_desc* g, const 
 
 extern "C" int64_t ls2fm_sdf_eval_workspace_bytes(void) { return (int64_t)((sizeof(Packed) + 255) / 256 * 256); }
 
+// Picks and launches the point-query kernel for points p[0 .. n) of a query of n_query points (the thresholds look at the query: a
+// caller that walks it in chunks gets one kernel, and so one set of bits, throughout).  prep_from: the parameters to pack into `pk`
+// first; null where a preceding call on the same stream left them there.
+static int launch_point_query(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* prep_from, Packed* pk,
+                              const float* table, const float* p, int64_t n, int64_t n_query, float* sdf, float* feat, float* normal,
+                              hipStream_t s) {
+    if (n <= 0) return LS2FM_OK;
+    const int st = prep_from ? ls2fm_launch_prep_sdf(prep_from, grid->n_levels, pk, s) : LS2FM_OK;
+    if (st != LS2FM_OK) return st;
+    const FieldC fc = make_field_c(field);
+    const LevelSet lv = make_level_set(grid);
+    const unsigned blocks = (unsigned)((n + 255) / 256), groups = (unsigned)((n + 15) / 16);
+    const char* force = getenv("LS2FM_POINTS_KERNEL");           // tests: 1 = thread per point, 2 = 16 lanes per point, whatever n
+    const int forced = force ? atoi(force) : 0;
+    const bool wide_full = forced == 2 || (forced != 1 && n_query <= 32768);      // measured alone: 47 against 67 us at 32 768 points, 81 against 92 at 65 536
+    ls2fm_prof_begin(LS2FM_PROF_SDF_EVAL, s);
+    if (!normal && !feat && n_query <= 65536)       // sdf only, few points: latency-bound -> 16 lanes per point (bit-identical)
+        sdf_eval_wide_kernel<<<groups, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, n, sdf);
+    else if (wide_full && normal)                   // sdf + features + normal of up to 32 768 points (the loops' point queries)
+        sdf_eval_wide_full_kernel<true><<<groups, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, n, sdf, feat, normal);
+    else if (wide_full && feat)
+        sdf_eval_wide_full_kernel<false><<<groups, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, n, sdf, feat, nullptr);
+    else if (normal)
+        sdf_eval_kernel<true><<<blocks, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, Lattice{}, n, sdf, feat, normal);
+    else
+        sdf_eval_kernel<false><<<blocks, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, Lattice{}, n, sdf, feat, nullptr);
+    ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
+    return ls2fm_launch_status();
+}
+
 extern "C" int ls2fm_sdf_eval(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
                               const float* p, int64_t n, float* sdf, float* feat, float* normal, void* workspace,
                               void* stream) {
@@ -596,56 +385,15 @@ extern "C" int ls2fm_sdf_eval(const ls2fm_field_desc* field, const ls2fm_grid_de
     if (n == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(p && sdf);
     if (!workspace) return LS2FM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    Packed* pk = (Packed*)workspace;
-    int st = ls2fm_launch_prep_sdf(params, grid->n_levels, pk, s);
-    if (st != LS2FM_OK) return st;
-    const FieldC fc = make_field_c(field);
-    const LevelSet lv = make_level_set(grid);
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    const char* force = getenv("LS2FM_POINTS_KERNEL");           // tests: 1 = thread per point, 2 = 16 lanes per point, whatever n
-    const int forced = force ? atoi(force) : 0;
-    const bool wide_full = forced == 2 || (forced != 1 && n <= 32768);      // measured alone: 47 against 67 us at 32 768 points, 81 against 92 at 65 536
-    ls2fm_prof_begin(LS2FM_PROF_SDF_EVAL, s);
-    if (!normal && !feat && n <= 65536)       // sdf only, few points: latency-bound -> 16 lanes per point (bit-identical)
-        sdf_eval_wide_kernel<<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table,
-                                                                      p, n, sdf);
-    else if (wide_full && normal)             // sdf + features + normal of up to 32 768 points (the loops' point queries)
-        sdf_eval_wide_full_kernel<true><<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk,
-                                                                                  params->sdf_table, p, n, sdf, feat, normal);
-    else if (wide_full && feat)
-        sdf_eval_wide_full_kernel<false><<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk,
-                                                                                   params->sdf_table, p, n, sdf, feat, nullptr);
-    else if (normal)
-        sdf_eval_kernel<true><<<blocks, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table, p, Lattice{},
-                                                     n, sdf, feat, normal);
-    else
-        sdf_eval_kernel<false><<<blocks, 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table, p, Lattice{},
-                                                      n, sdf, feat, nullptr);
-    ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
-    return ls2fm_launch_status();
+    return launch_point_query(field, grid, params, (Packed*)workspace, params->sdf_table, p, n, n, sdf, feat, normal, (hipStream_t)stream);
 }
 
 // ls2fm_sdf_eval's normal query (feat = NULL) on weights already packed in `pk`, for points p[0 .. n) of a query of n_query points:
-// the kernel ls2fm_sdf_eval picks for n_query, so every point's sdf and normal are bit for bit what one ls2fm_sdf_eval call over all
-// n_query points returns (trace_image.hip walks the surface points in bounded chunks)
+// every point's sdf and normal are bit for bit what one ls2fm_sdf_eval call over all n_query points returns (trace_image.hip walks
+// the surface points in bounded chunks)
 int ls2fm_launch_sdf_normals(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const Packed* pk, const float* table,
                              const float* p, int64_t n, int64_t n_query, float* sdf, float* normal, hipStream_t s) {
-    if (n <= 0) return LS2FM_OK;
-    const FieldC fc = make_field_c(field);
-    const LevelSet lv = make_level_set(grid);
-    const char* force = getenv("LS2FM_POINTS_KERNEL");
-    const int forced = force ? atoi(force) : 0;
-    const bool wide_full = forced == 2 || (forced != 1 && n_query <= 32768);
-    ls2fm_prof_begin(LS2FM_PROF_SDF_EVAL, s);
-    if (wide_full)
-        sdf_eval_wide_full_kernel<true><<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, n,
-                                                                                  sdf, nullptr, normal);
-    else
-        sdf_eval_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, table, p, Lattice{},
-                                                                         n, sdf, nullptr, normal);
-    ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
-    return ls2fm_launch_status();
+    return launch_point_query(field, grid, nullptr, const_cast<Packed*>(pk), table, p, n, n_query, sdf, nullptr, normal, s);
 }
 
 // sdf only, with the packed weights a preceding ls2fm_sdf_eval / ls2fm_sphere_trace left in `workspace` (same stream, same
@@ -656,19 +404,8 @@ extern "C" int ls2fm_sdf_eval_prepared(const ls2fm_field_desc* field, const ls2f
     if (n == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(p && sdf);
     if (!workspace) return LS2FM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const Packed* pk = (const Packed*)workspace;
-    const FieldC fc = make_field_c(field);
-    const LevelSet lv = make_level_set(grid);
-    ls2fm_prof_begin(LS2FM_PROF_SDF_EVAL, s);
-    if (n <= 65536)
-        sdf_eval_wide_kernel<<<(unsigned)((n + 15) / 16), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table,
-                                                                      p, n, sdf);
-    else
-        sdf_eval_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(lv, fc, field->bg_sdf, field->bg_rad, pk, params->sdf_table, p,
-                                                                          Lattice{}, n, sdf, nullptr, nullptr);
-    ls2fm_prof_end(LS2FM_PROF_SDF_EVAL, s);
-    return ls2fm_launch_status();
+    return launch_point_query(field, grid, nullptr, (Packed*)const_cast<void*>(workspace), params->sdf_table, p, n, n, sdf, nullptr, nullptr,
+                              (hipStream_t)stream);
 }
 
 extern "C" int ls2fm_sdf_volume(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
@@ -710,27 +447,6 @@ extern "C" int ls2fm_sdf_prepare(const ls2fm_grid_desc* grid, const ls2fm_params
 static int sphere_trace_impl(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
                              const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold, int32_t iters_max,
                              float* near, float* far, float* track, float* t_end, float* track_sdf, int32_t* trips, void* workspace,
-                             void* stream, bool prepared);
-
-extern "C" int ls2fm_sphere_trace(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
-                                  const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold,
-                                  int32_t iters_max, float* near, float* far, float* track, float* t_end, float* track_sdf,
-                                  int32_t* trips, void* workspace, void* stream) {
-    return sphere_trace_impl(field, grid, params, ray0, ray_dir, n_rays, sdf_threshold, iters_max, near, far, track, t_end, track_sdf,
-                             trips, workspace, stream, false);
-}
-
-extern "C" int ls2fm_sphere_trace_prepared(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
-                                           const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold,
-                                           int32_t iters_max, float* near, float* far, float* track, float* t_end,
-                                           float* track_sdf, int32_t* trips, void* workspace, void* stream) {
-    return sphere_trace_impl(field, grid, params, ray0, ray_dir, n_rays, sdf_threshold, iters_max, near, far, track, t_end, track_sdf,
-                             trips, workspace, stream, true);
-}
-
-static int sphere_trace_impl(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
-                             const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold, int32_t iters_max,
-                             float* near, float* far, float* track, float* t_end, float* track_sdf, int32_t* trips, void* workspace,
                              void* stream, bool prepared) {
     LS2FM_CHECK_ARG(field_ok(field, grid, params) && n_rays >= 0 && iters_max >= 0);
     LS2FM_CHECK_ARG(trips);
@@ -763,4 +479,20 @@ static int sphere_trace_impl(const ls2fm_field_desc* field, const ls2fm_grid_des
             sdf_threshold, iters_max, near, far, track, t_end, track_sdf, trips);
     ls2fm_prof_end(LS2FM_PROF_SPHERE_TRACE, s);
     return ls2fm_launch_status();
+}
+
+extern "C" int ls2fm_sphere_trace(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
+                                  const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold,
+                                  int32_t iters_max, float* near, float* far, float* track, float* t_end, float* track_sdf,
+                                  int32_t* trips, void* workspace, void* stream) {
+    return sphere_trace_impl(field, grid, params, ray0, ray_dir, n_rays, sdf_threshold, iters_max, near, far, track, t_end, track_sdf,
+                             trips, workspace, stream, false);
+}
+
+extern "C" int ls2fm_sphere_trace_prepared(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const ls2fm_params* params,
+                                           const float* ray0, const float* ray_dir, int64_t n_rays, float sdf_threshold,
+                                           int32_t iters_max, float* near, float* far, float* track, float* t_end,
+                                           float* track_sdf, int32_t* trips, void* workspace, void* stream) {
+    return sphere_trace_impl(field, grid, params, ray0, ray_dir, n_rays, sdf_threshold, iters_max, near, far, track, t_end, track_sdf,
+                             trips, workspace, stream, true);
 }

@@ -5,7 +5,7 @@
 // EVERY ray (K: the trip at which the last start end finished, SDF.py:149-206), so one pixel's depth depends on the whole view.
 // Each view gets the K a call over that view alone gets, in two passes over the rays of all views ([n_views][H*W], row-major,
 // pixel centres x + 0.5, y + 0.5, each ray formed from its pixel index with ls2fm_camera_rays' arithmetic, camera_ray.h):
-//   trips   : sphere_trace_kernel's loop (steps 1-7, sdf_eval.hip) until the ray's start end is finished; max over a view's
+//   trips   : the loop of trace_loop.h (steps 1-7), one lane per ray end, until the ray's start end is finished; max over a view's
 //             rays -> trips[view] (one atomic per wave).  Nothing else is written.
 //   trace   : the same loop for exactly max(K, 1) trips, summing the field's raw value at the start end's track points in
 //             ascending k -- finished start ends that still move on a stale step included (step 6) -- as trace_depth_fwd_kernel
@@ -14,11 +14,7 @@
 // Every output is bit for bit what SDF.sphere_tracing(static_trips=True) and SDF.gradient return for the view's rays.  The
 // workspace holds the packed weights and the normal query's (unread) sdf column for one chunk: it depends on nothing else.
 #include "camera_ray.h"
-#include "sdf_point.h"
-
-int ls2fm_launch_prep_sdf(const ls2fm_params* params, int n_levels, Packed* out, hipStream_t stream, int32_t* zero_word = nullptr);
-int ls2fm_launch_sdf_normals(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const Packed* pk, const float* table,
-                             const float* p, int64_t n, int64_t n_query, float* sdf, float* normal, hipStream_t s);
+#include "trace_loop.h"
 
 namespace {
 
@@ -49,63 +45,41 @@ __device__ __forceinline__ RayGeom image_ray(const FieldC& fc, const ImageRays& 
     return rg;
 }
 
-__device__ __forceinline__ float field_at(const LevelSet& lv, const FieldC& fc, const Packed* __restrict__ pk,
-                                          const float* __restrict__ table, const float p[3]) {
-    float u[kInMax], f[kOut], dummy[kInMax];
-    encode_point(lv, fc, table, p, u);
-    geometry_forward<false>(pk->sdf, u, f, dummy);
-    bool bg;
-    return signed_sdf(fc, 0, 0.f, f[0], p, &bg);
-}
-
-// pass 1: each ray's finishing trip, max over the view's rays into trips[view] (zeroed before the launch)
+// pass 1: each ray's finishing trip, max over the view's rays into trips[view] (zeroed before the launch).  The loop with the
+// exits "the start end is done" and k == iters_max, and no stores
 __global__ void __launch_bounds__(kThreads)
 trace_image_trips_kernel(LevelSet lv, FieldC fc, const Packed* __restrict__ pk, const float* __restrict__ table, ImageRays im,
                          float thr, int iters_max, int* __restrict__ trips) {
     const int64_t tidg = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t r = tidg >> 1;
-    const int side = (int)(tidg & 1);
     const int lane = threadIdx.x & 63;
     const bool live = r < im.total;
     const int64_t g = live ? r : im.total - 1;
     const int64_t v = g / im.hw;
     const RayGeom rg = image_ray(fc, im, g, v);
-    const float far = rg.t_far;
-    float t_me = side ? rg.t_far : rg.t_near;
-    float p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = rg.o[a] + t_me * rg.d[a];
-    float sdf_me = field_at(lv, fc, pk, table, p);
-    bool unf = false;
+    const LaneEnds ends{lv, fc, 0, 0.f, pk->sdf, table, (int)(tidg & 1)};         // no background sphere (trace_config)
+    TraceEnd e;
+    trace_begin(ends, rg, e);
     int kfin = iters_max;
-    // both lanes of a ray leave the loop at the same trip: the shuffles below always read a lane that is still in it
+    // both lanes of a ray leave the loop at the same trip: the shuffles always read a lane that is still in it
     for (int k = 0;; ++k) {
-        if (fabsf(sdf_me) <= thr) sdf_me = 0.f;                          // (1)
-        const bool m = fabsf(sdf_me) > thr;
-        unf = k == 0 ? m : (unf && m);                                    // (2)
-        const int unf_start = __shfl((int)unf, lane & ~1, 64);
-        if (!unf_start) { kfin = k; break; }                              // (3) the start end is done: K does not need more
+        trace_mask(e, thr, k);
+        if (!ends.start_unfinished(e.unf)) { kfin = k; break; }           // (3) the start end is done: K does not need more
         if (k == iters_max) break;
-        t_me = t_me + sdf_me;                                             // (4)
-        if (t_me > far) t_me = far;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = rg.o[a] + t_me * rg.d[a];
-        if (unf) sdf_me = field_at(lv, fc, pk, table, p);                 // (6) only the unfinished ends' values are read here
-        const float t_other = __shfl_xor(t_me, 1, 64);
-        const float t_s = side ? t_other : t_me, t_e = side ? t_me : t_other;
-        unf = unf && (t_s < t_e);                                         // (7)
+        trace_step(e, rg.t_far);
+        trace_refresh(ends, rg, e, false);                                // only the unfinished ends' values are read here
+        trace_cross(ends, e, k);
     }
     // one atomic per wave for the view of lane 0's ray; rays of another view in the same wave (view boundaries) add their own
-    const int kme = (live && side == 0) ? kfin : 0;
+    const int kme = (live && ends.side == 0) ? kfin : 0;
     const int64_t v0 = __shfl((int)v, 0, 64);
-    int kmax = v == v0 ? kme : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, 64));
+    const int kmax = wave_max(v == v0 ? kme : 0);
     if (lane == 0 && kmax > 0) atomicMax(trips + v0, kmax);
     if (v != v0 && kme > 0) atomicMax(trips + v, kme);
 }
 
-// pass 2: max(K, 1) trips per ray with the view's K, the depth sum and the per-pixel outputs
+// pass 2: the loop for max(K, 1) trips per ray with the view's K (exits k == K and k + 1 == k_eff), the depth sum and the
+// per-pixel outputs
 __global__ void __launch_bounds__(kThreads)
 trace_image_kernel(LevelSet lv, FieldC fc, const Packed* __restrict__ pk, const float* __restrict__ table, ImageRays im,
                    float thr, float finish_thr, const int* __restrict__ trips, float* __restrict__ depth,
@@ -113,7 +87,6 @@ trace_image_kernel(LevelSet lv, FieldC fc, const Packed* __restrict__ pk, const 
                    float* __restrict__ t_end_k) {
     const int64_t tidg = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t r = tidg >> 1;
-    const int side = (int)(tidg & 1);
     const bool live = r < im.total;
     const int64_t g = live ? r : im.total - 1;
     const int64_t v = g / im.hw;
@@ -121,38 +94,23 @@ trace_image_kernel(LevelSet lv, FieldC fc, const Packed* __restrict__ pk, const 
     const int k_eff = K < 1 ? 1 : K;
     const RayGeom rg = image_ray(fc, im, g, v);
     const float far = rg.t_far;
-    float t_me = side ? rg.t_far : rg.t_near;
-    float p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = rg.o[a] + t_me * rg.d[a];
-    float sdf_me = field_at(lv, fc, pk, table, p);
-    float raw_me = sdf_me;               // the field's value at the current point (sdf_me is zeroed / goes stale: (1), (6))
+    const LaneEnds ends{lv, fc, 0, 0.f, pk->sdf, table, (int)(tidg & 1)};
+    TraceEnd e;
+    trace_begin(ends, rg, e);
     float acc = 0.f, last = 0.f;
-    bool unf = false;
     for (int k = 0;; ++k) {
-        if (fabsf(sdf_me) <= thr) sdf_me = 0.f;                          // (1)
-        const bool m = fabsf(sdf_me) > thr;
-        unf = k == 0 ? m : (unf && m);                                    // (2)
-        last = raw_me;                                                    // track point k (start end): summed in ascending k
+        trace_mask(e, thr, k);
+        last = e.raw;                                                     // track point k (start end): summed in ascending k
         acc += last;
         if (k == K) break;                                                // K = 0: the far end has not moved
-        const float t_before = t_me;
-        t_me = t_me + sdf_me;                                             // (4)
-        if (t_me > far) t_me = far;
-        if (k + 1 == k_eff) break;                                        // t_me of the far end: t_end after K trips
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = rg.o[a] + t_me * rg.d[a];
-        if (unf || (side == 0 && t_me != t_before)) {                     // (6) the start end's value also where it moved stale
-            raw_me = field_at(lv, fc, pk, table, p);
-            if (unf) sdf_me = raw_me;
-        }
-        const float t_other = __shfl_xor(t_me, 1, 64);
-        const float t_s = side ? t_other : t_me, t_e = side ? t_me : t_other;
-        unf = unf && (t_s < t_e);                                         // (7)
+        const bool moved = trace_step(e, far);
+        if (k + 1 == k_eff) break;                                        // e.t of the far end: t_end after K trips
+        trace_refresh(ends, rg, e, ends.side == 0 && moved);              // the start end's value also where it moved stale
+        trace_cross(ends, e, k);
     }
     if (!live) return;
-    if (side == 1) {
-        if (t_end_k) t_end_k[r] = t_me;
+    if (ends.side == 1) {
+        if (t_end_k) t_end_k[r] = e.t;
         return;
     }
     const float d_sum = acc + rg.t_near;                                  // trace_depth_fwd_kernel: near + sum, clamped to far
