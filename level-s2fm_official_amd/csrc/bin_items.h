@@ -145,7 +145,7 @@ __device__ __forceinline__ void for_each_item(const LevelC& L, const uint32_t g[
 // round trips, fewer 64-bit LDS atomics, and far fewer same-address collisions in the coarse slabs.  Which lanes continue a
 // run is a function of the cells alone, so the counting pass (render_fwd.hip) and the fill pass classify identically; a wave
 // takes the merging path only when at least kMergeMin of its lanes continue a run (a wave-uniform decision both passes make
-// from the same ballot), so the fine levels pay three shuffles and a ballot.
+// from the same ballot; per RAY where rays share a wave: wave_runs), so the fine levels pay three shuffles and a ballot.
 // Single field: a run is one explicit item per corner pair.  Dual field: the factored item cannot carry a sum over different
 // x weights, so a merged run is two half items per pair (wx = 0 / 1, A = the summed corner values, B = 0).
 #ifndef LS2FM_MERGE_MIN
@@ -162,13 +162,32 @@ __device__ __forceinline__ void for_each_item(const LevelC& L, const uint32_t g[
 constexpr int kMergeMinSingle = LS2FM_MERGE_MIN, kMergeMinDual = LS2FM_MERGE_MIN_DUAL;
 struct RunFlags { unsigned long long cont; bool head, merged; };      // cont: lanes that continue their predecessor's run
 
-__device__ __forceinline__ RunFlags wave_runs(const uint32_t g[3], bool live, int lane, int merge_min) {
+// ray_len > 0 (wave-uniform): the wave's lanes are consecutive samples of rays of ray_len samples, and rays begin and end inside
+// it (ray_len is no multiple of 64); n_in_ray = this lane's sample number within its ray.  Then everything is decided PER RAY: a
+// run does not continue from one ray into the next, and a lane merges when at least merge_min lanes of ITS ray in this wave
+// continue a run -- what a ray contributes, merged sums or single samples, is then a function of that ray alone, whichever ray
+// shares the wave (with the threshold over the whole wave, the table gradient of a 96-sample ray changed in its last bits with
+// its neighbour).  Rays of a multiple of 64 samples never share a wave and free points have no rays: ray_len = 0, one decision
+// for the wave.  ls2fm_ray_len_of_runs is the one rule both passes use.
+__host__ __device__ __forceinline__ int ls2fm_ray_len_of_runs(bool has_rays, int n_samples) {
+    return has_rays && n_samples > 1 && (n_samples & 63) != 0 ? n_samples : 0;
+}
+__device__ __forceinline__ RunFlags wave_runs(const uint32_t g[3], bool live, int lane, int merge_min, int ray_len = 0,
+                                              uint32_t n_in_ray = 0u) {
     if (merge_min > 64) { RunFlags r; r.cont = 0ull; r.head = live; r.merged = false; return r; }
     const uint32_t p0 = __shfl_up(g[0], 1, 64), p1 = __shfl_up(g[1], 1, 64), p2 = __shfl_up(g[2], 1, 64);
     const int prev_live = __shfl_up((int)live, 1, 64);
-    const bool same = lane > 0 && live && prev_live != 0 && p0 == g[0] && p1 == g[1] && p2 == g[2];
+    const bool same = lane > 0 && live && prev_live != 0 && p0 == g[0] && p1 == g[1] && p2 == g[2] && (ray_len == 0 || n_in_ray != 0u);
     unsigned long long m = __ballot(same);
-    if ((int)__popcll(m) < merge_min) m = 0ull;
+    if (ray_len == 0) {
+        if ((int)__popcll(m) < merge_min) m = 0ull;
+    } else {
+        // this lane's ray holds lanes [lane - n_in_ray, lane - n_in_ray + ray_len) of the wave, as far as the wave reaches
+        const int first = lane - (int)n_in_ray, lo = first > 0 ? first : 0, hi = first + ray_len - 1 < 63 ? first + ray_len - 1 : 63;
+        const unsigned long long upto_hi = hi == 63 ? ~0ull : (1ull << (hi + 1)) - 1ull;
+        const unsigned long long of_ray = upto_hi & ~((1ull << lo) - 1ull);
+        m = __ballot(same && (int)__popcll(m & of_ray) >= merge_min);
+    }
     RunFlags r;
     r.cont = m;
     r.head = live && ((m >> lane) & 1ull) == 0ull;

@@ -135,7 +135,10 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
     // runs of consecutive points in one cell (bin_items.h): the same flags the counting pass derived
     const bool expl = DUAL && l < n_explicit;               // (workgroup-uniform) explicit, run-merged dual items on this level
     const bool halves = DUAL && !expl;                      // factored items: a merged run would be two half items per pair
-    const RunFlags rf = wave_runs(g, live, lane, halves ? kMergeMinDual : kMergeMinSingle);
+    // (rays that share a wave are classified ray by ray; center == null: free points, which have no rays)
+    const int ray_len = ls2fm_ray_len_of_runs(center != nullptr, fc.n_samples);
+    const uint32_t n_in_ray = ray_len != 0 ? (uint32_t)i % (uint32_t)ray_len : 0u;       // (i < 2^23: LS2FM_MAX_RENDER_POINTS)
+    const RunFlags rf = wave_runs(g, live, lane, halves ? kMergeMinDual : kMergeMinSingle, ray_len, n_in_ray);
     // ---- ONE pass over the pairs' hashes (rounds 1-5: one per counting / ranking / window pass).  Kept per pair c: ij (both
     // x-corners' local indices, each relative to its own slab), the slab of the pair's first item in byte c of sb0 (bit 7: the pair
     // is split into two half items), the second half item's slab in byte c of sb1.  Nothing here (nor in the factors below) needs

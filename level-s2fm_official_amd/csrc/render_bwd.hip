@@ -140,9 +140,10 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     // the MLPs' weight gradients are contracted inside shade_bwd (LS2FM_FUSED_WGRAD=0: round 4's separate wgrad_mlp launches,
     // for A/B measurements)
     // (one-sample rays share the workspace layout of free points, which has no per-ray partials: wgrad_mlp.hip serves them)
-    ls2fm_launch_shade_bwd(fc, lsc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, up, want_pose, sdf_grid, grads->sdf_table,
-                           dual ? grads->rad_table : nullptr, s, fused_wgrad);
+    const int st_shade = ls2fm_launch_shade_bwd(fc, lsc, dual, 2 * L1, 2 * L2, w, pk, center, ray, n_rays, ws, up, want_pose, sdf_grid,
+                                                grads->sdf_table, dual ? grads->rad_table : nullptr, s, fused_wgrad);
     ls2fm_prof_end(LS2FM_PROF_SHADE_BWD, s);
+    if (st_shade != LS2FM_OK) return st_shade;
     if (opts && opts->depth_grad_ready && hipEventRecord((hipEvent_t)opts->depth_grad_ready, s) != hipSuccess) return LS2FM_ERR_LAUNCH;
     SideCtx sc1, sc2;
     bool forked2 = false;
@@ -187,8 +188,10 @@ extern "C" int ls2fm_render_bwd(const ls2fm_field_desc* field, const ls2fm_grid_
     // rounds 2-4 (A/B).
     static const int side_in_fill_env = [] { const char* e = getenv("LS2FM_SIDE_IN_FILL"); return e ? atoi(e) : 1; }();
     // (only where the fill is long enough to hide the jobs' ~45 us chain of hand-offs: >= 32 k sample points; and while the level-1
-    // sums -- 39 KB of per-ray partials per ray -- stay small beside the fill's own traffic: C5, 4096 rays x 256: 2.002 -> 1.984 ms;
-    // C3, 8192 rays x 128: 3.074 -> 3.100)
+    // sums -- 39 KB of partials per workgroup slot of shade_bwd: per ray, or per PAIR of rays of up to 128 samples -- stay small
+    // beside the fill's own traffic: C5, 4096 rays x 256: 2.002 -> 1.984 ms; C3, 8192 rays x 128: 3.074 -> 3.100 with a slot per
+    // ray.  The threshold stays a count of RAYS: 4096 is where it was measured, and 8192 paired rays -- the same 4096 slots --
+    // have not been timed in the fill.)
     // (and only on a device with an order of magnitude more workgroup slots than the launch has WAITING workgroups -- the reduction
     // rows and finalize tasks, ~180: side_jobs.h -- so that the producers they poll can never be kept off the chip by them)
     const int n_waiters = kRegsSdf + (dual ? kRegsGeo : 0) + kRegsDec + kFinalizeTasks;

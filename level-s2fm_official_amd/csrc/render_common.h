@@ -245,8 +245,8 @@ constexpr int kRegsSdf = 48 + 16 + 16 + 5;
 constexpr int kRegsGeo = 48 + 16 + 4;
 constexpr int kRegsDec = 20;                     // 5 output tiles of the decoder columns
 // Round 5: the render's backward contracts the MLPs' weight gradients inside shade_bwd (shade_bwd.hip, 3.): one partial per
-// RAY (= workgroup), summed in two fixed-order levels -- kL1Seg segment sums (wgrad_l1 blocks of the wgrad_dec launch), then
-// wgrad_tail.
+// WORKGROUP (a pair of rays of up to 128 samples, one longer ray), summed in two fixed-order levels -- kL1Seg segment sums
+// (wgrad_l1 blocks of the wgrad_dec launch), then wgrad_tail.
 constexpr int kL1Seg = 16;
 // partial buffers inside WsLayout::mpart (floats)
 struct WgPartLayout {
@@ -259,18 +259,21 @@ struct WgPartLayout {
     int64_t total;
     int n_slots;
 };
-// the render's backward contracts the MLPs' weight gradients inside shade_bwd (one partial per ray) for rays of >= 64 samples unless
+// the render's backward contracts the MLPs' weight gradients inside shade_bwd (one partial per workgroup) for rays of >= 64 samples unless
 // LS2FM_FUSED_WGRAD=0 (round 4's separate wgrad_mlp launches, for A/B runs): ONE predicate for the kernels' choice and the workspace
 static inline bool ls2fm_fused_wgrad(int n_samples) {
     static const int env = [] { const char* e = getenv("LS2FM_FUSED_WGRAD"); return e ? atoi(e) : 1; }();
     return env != 0 && n_samples >= 64;
 }
+// rays that share one workgroup of the fused form, hence one slot: rays of up to 128 samples run in pairs (shade_bwd.hip, 3.)
+static inline int ls2fm_wg_rays_per_slot(int n_samples) { return n_samples <= 128 ? 2 : 1; }
 static inline WgPartLayout make_wg_part_layout(int dual, int64_t n_rays, int n_samples) {
     WgPartLayout L;
     int64_t o = 0;
-    // per-ray slots (39 KB per ray, dual field) only where shade_bwd fills them (round-5 advisor: short rays, free points and A/B runs
-    // with the switch off carried them unused -- 2.5 GB at 64 k rays)
-    L.n_slots = ls2fm_fused_wgrad(n_samples) ? (int)n_rays : 0;
+    // per-workgroup slots (39 KB each, dual field) only where shade_bwd fills them (round-5 advisor: short rays, free points and A/B
+    // runs with the switch off carried them unused -- 2.5 GB at 64 k rays)
+    const int per_slot = ls2fm_wg_rays_per_slot(n_samples);
+    L.n_slots = ls2fm_fused_wgrad(n_samples) ? (int)((n_rays + per_slot - 1) / per_slot) : 0;
     L.l1_sdf = o; o += (int64_t)(kL1Seg + kWgradMlpBlocks) * kRegsSdf * 64;
     L.l1_geo = o; o += dual ? (int64_t)kWgradMlpBlocks * kRegsGeo * 64 : 0;
     L.dec = o; o += (int64_t)kWgradMlpBlocks * kRegsDec * 64;

@@ -436,7 +436,10 @@ ray_encode_kernel(LevelSet lv1, LevelSet lv2, FieldC fc, const float* __restrict
                                // here is live and so is its predecessor (live lanes are a prefix of the wave): the run flags
                                // are those the fill pass derives from the same cells
             const bool factored = ex.dual != 0 && l >= ex.n_explicit;        // the factored 32-byte dual item (fine levels)
-            const RunFlags rf = wave_runs(g, true, tid & 63, factored ? kMergeMinDual : kMergeMinSingle);
+            // (rays that share a wave are classified ray by ray, as the fill does: the same rule from the same two facts)
+            const int ray_len = ls2fm_ray_len_of_runs(ex.pts == nullptr, fc.n_samples);
+            const uint32_t n_in_ray = ray_len != 0 ? (uint32_t)i % (uint32_t)ray_len : 0u;
+            const RunFlags rf = wave_runs(g, true, tid & 63, factored ? kMergeMinDual : kMergeMinSingle, ray_len, n_in_ray);
             if (rf.head) {
                 const bool halves = factored && rf.merged;                    // a merged run of a factored pair: two half items
 #pragma unroll

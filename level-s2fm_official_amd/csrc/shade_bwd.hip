@@ -17,11 +17,17 @@
 //        dW0' += DA U^T + GJ V^T  (64 x 36)   dW1[1..16] += GF H^T  (16 x 64)   dW1[0] += gf0 H + S1 . Q   db1 += sum GF
 //      accumulate in 85 (68) registers per wave over the wave's 64 samples; the workgroup's waves are summed through LDS
 //      and leave ONE partial per workgroup slot (fixed-order sums downstream: wgrad_l1 + wgrad_tail, deterministic).
+//      Rays of 64 .. 128 samples run TWO to a workgroup (rays 2b and 2b + 1; `PAIRS` below): one staging of each field's weights
+//      and one partial per pair -- half the partial bytes written here and read back by the level-1 sums.  Order of the sum,
+//      with ray h's waves w0, w1:  (r0w0 + r0w1) + (r1w0 + r1w1)  (64-sample rays: r0w0 + r1w0; a last workgroup without a
+//      second ray adds exact zeros) -- a function of (ray index, wave) alone, each ray's own sum being the one-ray form's.
 //      No separate weight-gradient kernel re-derives the hidden layer (round 4: wgrad_mlp x 2, 95 us alone and 150 us beside
 //      the table scatter), and the v / gf / gf2 rows (36 MB) are never stored.  One 16-column tile at a time then (NC = 1):
 //      the accumulators take the registers the second tile's operands had.
 //      Without WG (point queries keep wgrad_mlp.hip) the small per-sample upstream vectors (v, gf, gf2, dz, p) are stored.
 // MFMA-ordered weights are staged into LDS once per workgroup.  fp32 MFMA: exact fp32 products / sums.
+#include <type_traits>
+
 #include "bin_items.h"
 
 namespace {
@@ -33,7 +39,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // priority raised around the MFMA clusters of the SDF field's hidden blocks and dropped for the VALU part between them, the wave
 // that gets to its MFMAs first keeps the matrix pipe and the other one's VALU work fills the gaps -- the pair falls out of step:
 // shade_bwd 111.4 -> 106.0 us at C2 (single field 72.8 -> 70.6, C3 832 -> 821), bit-identical.
-// The per-ray weight-gradient partials (39 KB per ray) leave with non-temporal stores (section 12).
+// The per-workgroup weight-gradient partials (39 KB each) leave with non-temporal stores (section 12).
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -135,8 +141,10 @@ __device__ __forceinline__ double wave_suffix_excl_f64(double v, int lane) {
 
 // (WG) end of a pass: this wave's accumulators in the partial's row order (wgrad_tail.h: reduce_partials_row), with the row sums
 // over the 16 sample lanes for dW1[0] / db1; the workgroup's waves are summed through `buf` (s_w: the pass is done with its
-// weights) in a fixed order, and wave 0 stores the ray's partial
-template <bool GEO>
+// weights) in a fixed order, and wave 0 stores the workgroup's partial.  `wave`: the wave's index in the workgroup, ray h's waves
+// being h * n_waves .. h * n_waves + n_waves - 1.  Order (header, 3.): every ray's waves are folded into its first one from the last
+// down, ray after ray, then the rays' sums from the last ray down -- (r0w0 + r0w1) + (r1w0 + r1w1) for a pair of 128-sample rays.
+template <bool GEO, int RAYS>
 __device__ __forceinline__ void wg_flush(const f32x4 (&acc0)[4][2], const f32x4 (&acc1)[4], const float (&pacc)[4][4],
                                          float w1p, float gs16, float g0s, float* __restrict__ buf,
                                          float* __restrict__ dst, int wave, int n_waves, int lane) {
@@ -188,28 +196,83 @@ __device__ __forceinline__ void wg_flush(const f32x4 (&acc0)[4][2], const f32x4 
             regs[(GEO ? 64 : 80) + t] = o == 0 ? v0 : x;
         }
     }
-    for (int wv = n_waves - 1; wv >= 1; --wv) {
-        __syncthreads();                     // (first trip: every wave is done with the pass's weights)
-        if (wave == wv) {
+    if constexpr (RAYS == 1) {
+        for (int wv = n_waves - 1; wv >= 1; --wv) {
+            __syncthreads();                     // (first trip: every wave is done with the pass's weights)
+            if (wave == wv) {
 #pragma unroll
-            for (int q = 0; q < R; ++q) buf[q * 64 + lane] = regs[q];
+                for (int q = 0; q < R; ++q) buf[q * 64 + lane] = regs[q];
+            }
+            __syncthreads();
+            if (wave == wv - 1) {
+#pragma unroll
+                for (int q = 0; q < R; ++q) regs[q] += buf[q * 64 + lane];
+            }
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) __builtin_nontemporal_store(regs[q], at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u));
+        }
+    } else {
+        // A pair (n_waves <= 2).  The rows are cut in two halves, A = [0, H) and B = [H, R), so that two waves move registers through
+        // the one buffer at a time (one wave after the other, as the one-ray form does it, the pair's flush took three times as long):
+        //   1. ray 0's second wave hands A to its first and ray 1's second wave hands B to ITS first; 2. the same with A and B swapped:
+        //      wave 0 holds ray 0's sum w0 + w1 and wave n_waves ray 1's, each the sum the one-ray form makes;
+        //   3. wave 0 hands B to wave n_waves and takes its A: the two store ray 0's sum + ray 1's sum, a half each.
+        // Every sum is a function of (ray, wave) alone.
+        constexpr int H = (R + 1) / 2;
+        auto put_a = [&] {
+#pragma unroll
+            for (int q = 0; q < H; ++q) buf[q * 64 + lane] = regs[q];
+        };
+        auto put_b = [&] {
+#pragma unroll
+            for (int q = H; q < R; ++q) buf[q * 64 + lane] = regs[q];
+        };
+        auto add_a = [&] {
+#pragma unroll
+            for (int q = 0; q < H; ++q) regs[q] += buf[q * 64 + lane];
+        };
+        auto add_b = [&] {
+#pragma unroll
+            for (int q = H; q < R; ++q) regs[q] += buf[q * 64 + lane];
+        };
+        if (n_waves == 2) {
+            __syncthreads();                     // (every wave is done with the pass's weights)
+            if (wave == 1) put_a();
+            if (wave == 3) put_b();
+            __syncthreads();
+            if (wave == 0) add_a();
+            if (wave == 2) add_b();
+            __syncthreads();
+            if (wave == 1) put_b();
+            if (wave == 3) put_a();
+            __syncthreads();
+            if (wave == 0) add_b();
+            if (wave == 2) add_a();
         }
         __syncthreads();
-        if (wave == wv - 1) {
+        if (wave == 0) put_b();
+        if (wave == n_waves) put_a();
+        __syncthreads();
+        if (wave == 0) {
+            add_a();
 #pragma unroll
-            for (int q = 0; q < R; ++q) regs[q] += buf[q * 64 + lane];
+            for (int q = 0; q < H; ++q) __builtin_nontemporal_store(regs[q], at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u));
         }
-    }
-    if (wave == 0) {
+        if (wave == n_waves) {
+            add_b();
 #pragma unroll
-        for (int q = 0; q < R; ++q) __builtin_nontemporal_store(regs[q], at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u));
+            for (int q = H; q < R; ++q) __builtin_nontemporal_store(regs[q], at_bytes<float>(dst, (uint32_t)lane * 4u + (uint32_t)q * 256u));
+        }
     }
 }
 
 // POSE: center / ray require gradients (BA "sfm_refine" with one camera, BA.py:153-154) -- the only case that needs the rows of
 // W0'^T DA that belong to the MLP's position inputs: 16 more MFMAs per hidden block and 8 more registers.
-// WG: weight gradients contracted here (header, 3.), one partial per ray.  MAXT = 128: rays of up to 128 samples, 4 workgroups
-// of 2 waves per CU.  (A workgroup walking several rays and keeping one partial was tried first: the loop-invariant kernel
+// WG: weight gradients contracted here (header, 3.), one partial per workgroup.  MAXT = 128: rays of up to 128 samples; without WG
+// 4 workgroups of 2 waves per CU, with WG 2 workgroups of 4 waves, two rays each (PAIRS below).  (A workgroup walking several
+// rays IN TURN and keeping one partial was tried first: the loop-invariant kernel
 // arguments it keeps in scalar registers across the loop spill into vector registers -- 92 .. 136 B of scratch per lane.)
 // (Rounds 5-6: this kernel had two run-time modes on MI355X -- 121-126 and 132-137 us at C2, 85 / 97 us single field -- set by the NUMA
 // node the host process initialised on.  Cause, found in round 6 (profiles/r06_notes.md section 6): its waves read the DISPATCH PACKET,
@@ -217,8 +280,15 @@ __device__ __forceinline__ void wg_flush(const f32x4 (&acc0)[4][2], const f32x4 
 // FULL: all 32 encoding channels of both grids are live (16-level grids: every shipped preset) -- known at compile time, the sixteen
 // per-channel predicates of a tile's operand loads, their exec-mask branches and the zero fills behind them are gone (round 6:
 // shade_bwd 115.0 -> 111.8 us, single field 74.8 -> 72.2; bit-identical).  Instantiated for the fused-weight-gradient form only.
+// PAIRS (WG and MAXT = 128: rays of 64 .. 128 samples): a workgroup works TWO rays, 2b and 2b + 1 -- waves [0, n_waves) the first,
+// [n_waves, 2 n_waves) the second -- as 2 workgroups of 4 waves per CU: the same eight waves, one staging of each field's weights
+// and ONE weight-gradient partial per pair.  Everything else is per ray as before (part 1, its scans and LDS rows, the transpose
+// tiles, the level bounds); the rays meet only at the barriers the one-ray form already had.  With an odd ray count the last
+// workgroup's second half has no ray: it walks part 1 on the pair's first ray with every store masked, skips the tile loops and
+// hands exact zeros to the flush.
+constexpr int bwd_rays(bool wg, int maxt) { return wg && maxt == 128 ? 2 : 1; }
 template <bool DUAL, int MAXT, bool POSE, bool WG, bool FULL = false>
-__global__ void __launch_bounds__(MAXT, WG ? LS2FM_BWD_WAVES_WG : 2)
+__global__ void __launch_bounds__(MAXT * bwd_rays(WG, MAXT), WG ? LS2FM_BWD_WAVES_WG : 2)
 shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout w, const Packed* __restrict__ pk,
                  const float* __restrict__ center, const float* __restrict__ ray, const float* __restrict__ fws,
                  Upstream up, float* __restrict__ out, ZeroJob zero, int64_t n_rays, float* __restrict__ slot_sdf,
@@ -234,25 +304,49 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
     // (TCC_EA0_RDREQ_IO_32B; every other kernel of the step: 0), one on every workgroup's critical path at the head of its MFMA part.
     // That is what made the kernel 123 us from the GPU's NUMA node and 135 us from the other socket (profiles/r06_notes.md section 6).
     const int ch1 = FULL ? 32 : ch1_arg, ch2 = FULL ? 32 : ch2_arg;
-    const int n_threads = (fc.n_samples + 63) / 64 * 64;
+    constexpr int kRays = bwd_rays(WG, MAXT);                 // rays per workgroup
+    const int n_threads = (fc.n_samples + 63) / 64 * 64;        // threads of ONE ray
+    const int wg_threads = kRays * n_threads;
     if ((int)blockIdx.x < zero.blocks) {
-        zero_job_run(zero, (int)blockIdx.x, (int)threadIdx.x, n_threads);
+        zero_job_run(zero, (int)blockIdx.x, (int)threadIdx.x, wg_threads);
         return;
     }
-    __shared__ float s_part[MAXT / 64][8];
-    __shared__ double s_db[MAXT / 64];
-    __shared__ double s_pd[MAXT / 64][2];        // fp64 twin of the composite scans (d beta): tau totals, sum of U w
-    __shared__ int s_bound[32];                  // per-level max of a single scatter contribution (bits of a float >= 0)
-    __shared__ float s_y[MAXT][8];               // per sample: dz(3), g_n(3), g_sdf
+    // per ray: ONE block per ray of the pair, so that a single scalar offset selects the ray's rows
+    struct RayLds {
+        double db[MAXT / 64];
+        double pd[MAXT / 64][2];          // fp64 twin of the composite scans (d beta): tau totals, sum of U w
+        float part[MAXT / 64][8];
+        int bound[32];                    // per-level max of a single scatter contribution (bits of a float >= 0)
+        float y[MAXT][8];                 // per sample: dz(3), g_n(3), g_sdf
+    };
+    __shared__ RayLds sh_ray[kRays];
+    // per workgroup
     __shared__ float s_wc[3][68];                // collapsed decoder (Packed::wc)
     __shared__ float s_w[WG ? kSwWg : kMfmaBwdSdfFloats];     // MFMA-ordered weights of the field being processed (26 KB; WG:
                                                  // 22 KB, W1[0] compact); WG: also the buffer of the cross-wave sum of the
                                                  // weight-gradient registers
-    __shared__ __attribute__((aligned(16))) float s_t[WG ? MAXT / 64 : 1][WG ? NC * kTRows * kTLd : 4];   // wave-private transpose tiles
+    __shared__ __attribute__((aligned(16))) float s_t[WG ? kRays * MAXT / 64 : 1][WG ? NC * kTRows * kTLd : 4];   // wave-private transpose tiles
     static_assert(kRegsSdf * 64 <= kSwWg && kRegsGeo * 64 <= kSwWg && kMfmaBwdGeoFloats <= kSwWg, "register sums / second field's weights fit in s_w");
     const int N = fc.n_samples;
-    const int n = threadIdx.x, lane = n & 63, wave = n >> 6, n_waves = n_threads >> 6;
-    const int64_t r = (int64_t)blockIdx.x - zero.blocks;
+    const int tid = threadIdx.x, lane = tid & 63, n_waves = n_threads >> 6;
+    // wg_wave: the wave's index in the workgroup; rh, wave, n: the ray of the pair, the wave and the thread within that ray.  In the
+    // paired form the wave index is made uniform by hand, so that the ray index -- and with it the ray's geometry and every per-ray
+    // address -- stays in scalar registers as it does where it comes from the workgroup index alone.
+    const int wg_wave = kRays > 1 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+    const int rh = kRays > 1 && wg_wave >= n_waves ? 1 : 0;
+    const int wave = wg_wave - rh * n_waves, n = tid - rh * n_threads;
+    // (pairs: the workgroup and ray indices are formed in 32 bits -- fewer scalar registers, which this kernel spills into vector ones)
+    typedef typename std::conditional<(kRays > 1), int, int64_t>::type wg_index;
+    const wg_index wg = (wg_index)blockIdx.x - zero.blocks;
+    // (a half without a ray keeps a valid ray index for its loads and stores nothing)
+    const bool present = kRays == 1 || wg * kRays + rh < (wg_index)n_rays;
+    const int64_t r = present ? wg * kRays + rh : (wg_index)n_rays - 1;
+    RayLds& ray_lds = sh_ray[rh];
+    float (&s_part)[MAXT / 64][8] = ray_lds.part;
+    double (&s_db)[MAXT / 64] = ray_lds.db;
+    double (&s_pd)[MAXT / 64][2] = ray_lds.pd;
+    int (&s_bound)[32] = ray_lds.bound;
+    float (&s_y)[MAXT][8] = ray_lds.y;
     const int jl = lane & 15, g = lane >> 4;
     const int64_t P = w.p_pad;
     const uint32_t P32 = (uint32_t)w.p_pad;
@@ -267,13 +361,13 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         const float4* src = reinterpret_cast<const float4*>(&pk->bs);
         float4* dst = reinterpret_cast<float4*>(s_w);
         constexpr int n_stage = WG ? kMfmaBwdSdfFloats - 4 * 4 * 64 : kMfmaBwdSdfFloats;       // (w10 is the last member)
-        for (int q = n; q < n_stage / 4; q += n_threads) dst[q] = src[q];
-        if (WG && n < 64) s_w[n_stage + n] = pk->bs.w10[n >> 4][n & 3][16 * ((n >> 2) & 3)];      // W1[0][hidden unit n]
+        for (int q = tid; q < n_stage / 4; q += wg_threads) dst[q] = src[q];
+        if (WG && tid < 64) s_w[n_stage + tid] = pk->bs.w10[tid >> 4][tid & 3][16 * ((tid >> 2) & 3)];      // W1[0][hidden unit tid]
     }
     if (n < 32) s_bound[n] = 0;
     // the decoder's feature columns, read per lane (o = 4t + g) in every tile: from LDS (one base register + immediate offsets;
     // as global loads the compiler kept fifteen 64-bit addresses alive across the tile loop -- and spilled them)
-    for (int q = n; q < 3 * 68; q += n_threads) (&s_wc[0][0])[q] = (&pk->wc[0][0])[q];
+    for (int q = tid; q < 3 * 68; q += wg_threads) (&s_wc[0][0])[q] = (&pk->wc[0][0])[q];
 
     // =========================================================================== 1. one thread per sample
     {
@@ -319,7 +413,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             if (lo.depth_ref != nullptr && (lo.mask_dc == nullptr || lo.mask_dc[r] != 0))
                 gd = gl_dc * ls2fm_smooth_l1_grad(lo.depth_ref[r] - rout[3 * w.r_pad + r]);
             g_dep -= gd;
-            if (n == 0 && lo.d_depth_ref != nullptr) lo.d_depth_ref[r] = gd;
+            if (n == 0 && present && lo.d_depth_ref != nullptr) lo.d_depth_ref[r] = gd;
         }
         // forward per-sample values saved by shade_fwd
         const float sdf = fws[w.sdfv + i];
@@ -460,18 +554,18 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         y[3] = gn[0]; y[4] = gn[1]; y[5] = gn[2];
         y[6] = g_sdf;
         __syncthreads();          // s_part, s_db, s_y, s_w, s_bound ready
-        if (n < 3) {
+        if (n < 3 && present) {
             float s = 0.f;
             for (int q = 0; q < n_waves; ++q) s += s_part[q][4 + n];
             out[w.dzr + n * w.r_pad + r] = s;
         }
-        if (n == 3) {
+        if (n == 3 && present) {
             double s = 0.0;
             for (int q = 0; q < n_waves; ++q) s += s_db[q];
             reinterpret_cast<double*>(out + w.dbeta)[r] = s;         // per-ray partial: no atomic, nothing to zero
         }
-        if (n < kView) out[w.renc + n * w.r_pad + r] = view_component(gm.d, n);
-        if (n == 4 && want_pose) {
+        if (n < kView && present) out[w.renc + n * w.r_pad + r] = view_component(gm.d, n);
+        if (n == 4 && want_pose && present) {
             float s = 0.f;
             for (int q = 0; q < n_waves; ++q) s += s_part[q][3];
             out[w.dlen + r] = s;
@@ -491,7 +585,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         __syncthreads();          // every wave is done with the SDF weights
         const float4* src = reinterpret_cast<const float4*>(&pk->bg);
         float4* dst = reinterpret_cast<float4*>(s_w);
-        for (int q = n; q < kMfmaBwdGeoFloats / 4; q += n_threads) dst[q] = src[q];
+        for (int q = tid; q < kMfmaBwdGeoFloats / 4; q += wg_threads) dst[q] = src[q];
         __syncthreads();          // second field's weights staged
     }
     // this lane's levels are the same in every half and column (l = 8 mk + 2 g + hv): keep the running maxima of the
@@ -511,9 +605,9 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             for (int a = 0; a < 4; ++a) pacc[m][a] = 0.f;
         }
     }
-    float* __restrict__ xt = s_t[WG ? wave : 0];
+    float* __restrict__ xt = s_t[WG ? wg_wave : 0];
 #pragma unroll 1
-    for (int half = 0; half < 4 / NC; ++half) {
+    for (int half = 0; half < (present ? 4 / NC : 0); ++half) {
         uint32_t is[NC];                  // point index (32-bit offsets: uniform base + VGPR offset addressing)
         bool live_c[NC];
         float pw[NC][3], xg[NC][3], dz[NC][3], gns[NC][3], gnk[NC][3], gsdf[NC];
@@ -941,14 +1035,23 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             if (2 * l < (pass == 0 ? ch1 : ch2)) atomicMax(&s_bound[16 * pass + l], __float_as_int(bnd[mk][hv]));
         }
     if constexpr (WG) {
-        float* __restrict__ dst = (pass == 0 ? slot_sdf : slot_geo) + r * ((pass == 0 ? kRegsSdf : kRegsGeo) * 64);      // the ray's slot (uniform); wg_flush adds the lane
-        if (pass == 0) wg_flush<false>(acc0, acc1, pacc, w1p, gs16, g0s, s_w, dst, wave, n_waves, lane);
-        else wg_flush<true>(acc0, acc1, pacc, w1p, gs16, g0s, s_w, dst, wave, n_waves, lane);
+        float* __restrict__ dst = (pass == 0 ? slot_sdf : slot_geo) + (int64_t)wg * ((pass == 0 ? kRegsSdf : kRegsGeo) * 64);      // the workgroup's slot (uniform); wg_flush adds the lane
+        if (pass == 0) wg_flush<false, kRays>(acc0, acc1, pacc, w1p, gs16, g0s, s_w, dst, wg_wave, n_waves, lane);
+        else wg_flush<true, kRays>(acc0, acc1, pacc, w1p, gs16, g0s, s_w, dst, wg_wave, n_waves, lane);
+        // pairs: this pass's bounds leave here, behind the barriers of the flush (a pair's flush has at least one) and while the
+        // address of the ray's LDS block is still at hand -- kept for a store behind the pass loop it was one register too many.
+        // A single field's second sixteen are the zeros they were set to.
+        if constexpr (kRays > 1) {
+            const int n_out = DUAL ? 16 : 32;
+            if (wave == 0 && lane < n_out && present) out[w.smax + (16 * pass + lane) * w.r_pad + r] = __int_as_float(s_bound[16 * pass + lane]);
+        }
     }
     }
     // per-ray bounds of the scatter contributions (max over the ray's samples), [level][ray]
-    __syncthreads();
-    if (n < 32) out[w.smax + n * w.r_pad + r] = __int_as_float(s_bound[n]);
+    if constexpr (kRays == 1) {
+        __syncthreads();
+        if (n < 32) out[w.smax + n * w.r_pad + r] = __int_as_float(s_bound[n]);
+    }
 }
 
 }  // namespace
@@ -972,11 +1075,14 @@ int ls2fm_launch_shade_bwd(const FieldC& fc, const LevelScales& lsc, int dual, i
     const WgPartLayout pl = make_wg_part_layout(dual, n_rays, fc.n_samples);
     float* slot_sdf = ws + w.mpart + pl.slot_sdf;
     float* slot_geo = ws + w.mpart + pl.slot_geo;
-    const unsigned grid = (unsigned)(n_rays + zero.blocks);
+    // the fused form's workgroups are the slots of the partials: one layout rule for the kernel, the workspace and the level-1 sums
+    const int wg_rays = fused_wgrad && threads <= 128 ? 2 : 1;
+    if (fused_wgrad && (wg_rays != ls2fm_wg_rays_per_slot(fc.n_samples) || pl.n_slots != (n_rays + wg_rays - 1) / wg_rays)) return LS2FM_ERR_WORKSPACE;
     const bool full = ch1 == 32 && (!dual || ch2 == 32);
 #define LS2FM_SHADE_BWD3(DUAL, MAXT, POSE, WG, FULL)                                                                                \
-    shade_bwd_kernel<DUAL, MAXT, POSE, WG, FULL><<<grid, threads, 0, s>>>(fc, lsc, ch1, ch2, w, pk, center, ray, ws, up, ws, zero, \
-                                                                         n_rays, slot_sdf, slot_geo)
+    shade_bwd_kernel<DUAL, MAXT, POSE, WG, FULL><<<(unsigned)((n_rays + bwd_rays(WG, MAXT) - 1) / bwd_rays(WG, MAXT) + zero.blocks), \
+                                                   threads * bwd_rays(WG, MAXT), 0, s>>>(fc, lsc, ch1, ch2, w, pk, center, ray, ws, up, \
+                                                                                           ws, zero, n_rays, slot_sdf, slot_geo)
 #define LS2FM_SHADE_BWD2(DUAL, MAXT, POSE, WG)                                                                                \
     do { if (WG && full) LS2FM_SHADE_BWD3(DUAL, MAXT, POSE, WG, WG); else LS2FM_SHADE_BWD3(DUAL, MAXT, POSE, WG, false); } while (0)
 #define LS2FM_SHADE_BWD(DUAL, MAXT)                                                                                          \

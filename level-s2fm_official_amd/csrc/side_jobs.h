@@ -1,7 +1,7 @@
 // Jobs of the backward's weight-gradient tail that can ride in ANOTHER kernel's launch (round 5).
 //
 // With the MLPs' weight gradients contracted inside shade_bwd, what is left of the side chain of rounds 2-4 is small: the decoder
-// columns (dz x [p n f f2 1], 21 MB of operands), the level-1 sums of shade_bwd's per-ray partials (40 MB), the fixed-order reduction
+// columns (dz x [p n f f2 1], 21 MB of operands), the level-1 sums of shade_bwd's per-workgroup partials (20 MB; 40 MB before rays were paired), the fixed-order reduction
 // and the seven finalize tasks -- 13 + 30 us as two launches on a side stream.  Having a side stream at all costs the step 26 - 28 us
 // (a round-5 timing probe without the side chain: 0.473 -> 0.445 ms replayed, 0.468 -> 0.443 eager): a cross-queue edge in front of scatter_fill,
 // a fork / join pair of barrier packets, a longer replay-to-replay gap (two queues to drain) and contention with the fill.  Here the
@@ -34,11 +34,12 @@ __device__ __forceinline__ float4 mask4(const float4 v, int64_t s, int64_t n, bo
     return make_float4((on && s < n) ? v.x : 0.f, (on && s + 1 < n) ? v.y : 0.f, (on && s + 2 < n) ? v.z : 0.f, (on && s + 3 < n) ? v.w : 0.f);
 }
 
-// Level 1 of the fixed-order sum of shade_bwd's per-ray weight-gradient partials (shade_bwd.hip, 3.): job (row k, segment sg)
-// adds row k of the rays [sg * per, (sg + 1) * per) -- wave v takes the rays v, v + 4, ... of the segment, eight loads in
-// flight, then the four waves' sums are added in order -- and leaves row k of segment sum sg.  The order of the additions is a
-// function of (n_rays, kL1Seg) alone: deterministic.
-// The per-ray partials are read with plain loads (non-temporal ones: profiles/r06_notes.md section 16).
+// Level 1 of the fixed-order sum of shade_bwd's per-workgroup weight-gradient partials (shade_bwd.hip, 3.: one slot per ray, or per
+// pair of rays of up to 128 samples -- WgPartLayout::n_slots): job (row k, segment sg) adds row k of the slots
+// [sg * per, (sg + 1) * per), per = ceil(n_slots / kL1Seg) -- wave v takes the slots v, v + 4, ... of the segment, eight loads
+// in flight, then the four waves' sums are added in order -- and leaves row k of segment sum sg.  The order of the additions is
+// a function of (n_slots, kL1Seg) alone: deterministic.  With paired rays a job reads half the rows it read with a slot per ray.
+// The partials are read with plain loads (non-temporal ones: profiles/r06_notes.md section 16).
 struct L1Job { const float* slot_sdf; const float* slot_geo; float* l1_sdf; float* l1_geo; int n_slots, dual; };
 
 template <bool WT>
