@@ -625,7 +625,7 @@ int ls2fm_camera_rays(const float* poses, const float* se3, const float* kinv_ho
  *   out[1] = sum_i |sdf_last_i| w_i (0 when sdf_last is NULL) ;  out[2] = sum(live)            (fp64 fixed-order sums)
  * center, ray, target [n,3], d, live, sdf_last [n] (device); out [3].  bwd: g_tl, g_sd: one float each, the upstreams of out[0]
  * and out[1] (device; NULL = that term has no upstream: zero) -> d_d [n], d_sdf [n] (NULL with sdf_last NULL); d |e| / d d at
- * e = 0 is 0, sign(0) = 0, as torch. */
+ * e = 0 is 0, sign(0) = 0, as torch.  No live row: out[0], out[1] are 0 / 0 = NaN and so is EVERY gradient entry, as torch's. */
 int ls2fm_tracing_term_fwd(const float* center, const float* ray, const float* d, const float* target, const float* live,
                            const float* sdf_last, int64_t n, float* out, void* stream);
 int ls2fm_tracing_term_bwd(const float* center, const float* ray, const float* d, const float* target, const float* live,

@@ -200,9 +200,10 @@ tracing_term_bwd_kernel(const float* __restrict__ center, const float* __restric
         q = fmaf(e[a], e[a], q);
     }
     const float len = sqrtf(q);
-    // d |e| / d d = -(e . ray) / |e|   (0 at e = 0, as torch's norm backward)
+    // d |e| / d d = -(e . ray) / |e|   (0 at e = 0, as torch's norm backward: upstream x 0, so a NaN upstream -- no live row,
+    // w = 0 / 0 -- stays NaN there as in every other row)
     const float dot = fmaf(e[2], ray[3 * i + 2], fmaf(e[1], ray[3 * i + 1], e[0] * ray[3 * i]));
-    d_d[i] = len > 0.f ? -(g0 * w) * dot / len : 0.f;
+    d_d[i] = len > 0.f ? -(g0 * w) * dot / len : (g0 * w) * 0.f;
     if (d_sdf) {
         const float s = sdf_last[i];
         d_sdf[i] = g1 * w * (s > 0.f ? 1.f : (s < 0.f ? -1.f : 0.f));
