@@ -925,6 +925,56 @@ int ls2fm_bundle_adjust_run(float* se3, float* points, const float* obs_uv, int3
                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Levenberg-Marquardt bundle adjustment with a Schur complement (csrc/bundle_adjust_lm.hip; additions, the library stays ABI 13):
+ * explicit points and [R | t] poses of V <= LS2FM_BA_LM_MAX_VIEWS picked views, one shared pinhole camera, all arithmetic fp64, no
+ * floating-point atomics, every sum in a fixed order.  tests/ba_lm_restate.py repeats every rule in numpy, by two routes.
+ *   model     x_c = R X + t ; r = (fx x/z + cx - u, fy y/z + cy - v), a plain division ; s = |r|^2 ; rho(s) with scale c:
+ *             loss 0 (trivial) rho = s ; 1 (soft_l1) rho = 2 c^2 (sqrt(1 + s / c^2) - 1) ; 2 (cauchy) rho = c^2 log(1 + s / c^2).
+ *             cost = 1/2 sum rho(s) over ALL observations.  IRLS weight w = rho'(s), no second-order correction.
+ *   step      pose perturbation (omega, dt): d x_c = -[x_c]x omega + dt, the update R <- exp([omega]x) R, t <- exp([omega]x) t + dt
+ *             (ls2fm_pose_refine's); J_c 2 x 6, J_p = J_proj R 2 x 3.  A constant view has J_c = 0; a point with fewer than
+ *             min_point_views observations among the picked views has J_p = 0 (its observations still constrain their cameras and
+ *             count in the cost).  U_v = sum w J_c^T J_c, g_v = sum w J_c^T r over the view's observations in list order; V_p, g_p
+ *             over the point's observations in list order; W_o = w J_c^T J_p.  Damping per block: B* = B + lambda diag(max(B_kk,
+ *             1e-12 max_k B_kk)).  Reduced system S_ij = [i = j] U_i* - sum_p W_ip V_p*^-1 W_jp^T, b_i = -(g_i - sum_p W_ip V_p*^-1
+ *             g_p), a constant view's block the identity with right-hand side 0; S delta_c = b by Cholesky (dense, 6-column
+ *             panels); delta_p = -V_p*^-1 (g_p + sum_o W_o^T delta_c[view(o)]), 0 for a constant point.
+ *   decision  the candidate (updated poses, X + delta_p) is accepted iff its cost < the current cost (strict: a non-finite
+ *             candidate is rejected): lambda <- max(0.1 lambda, 1e-16); otherwise, or after a non-positive Cholesky pivot (of S or
+ *             of a V_p*), lambda <- 10 lambda.  The loop stops (reason) when max |g| <= grad_tol (1; checked first, the state
+ *             stays), an accepted step has max |delta| <= step_tol (1 + max |parameter|) (2; parameters: the translations and the
+ *             observed points entering the iteration), or lambda > 1e32 (3).  After the stop the remaining launches return at once.
+ *   prepare   ls2fm_bundle_adjust_lm_prepare, ONCE per loop (it synchronises `stream`; not capturable): validates view_start and
+ *             obs_point exactly as ls2fm_bundle_adjust_prepare does, and view_constant [V] (uint8, device, required).  In
+ *             addition LS2FM_ERR_UNSUPPORTED for n_views > LS2FM_BA_LM_MAX_VIEWS and LS2FM_ERR_INVALID_ARGUMENT for a point seen
+ *             twice by one view or min_point_views < 1.  The point -> observations lists and the constant flags are the library's
+ *             own copies behind a magic header.  workspace: ls2fm_bundle_adjust_lm_workspace_bytes (negative when refused).
+ *   run       ls2fm_bundle_adjust_lm_run: n_iters iterations, six plain launches each and two more after the last, nothing read
+ *             back: capturable.  poses [V][12] row-major [R | t] world to camera and points [P][3] are updated in place (an
+ *             accepted candidate replaces them; a point no picked view observes keeps its bits).  intrinsic4_host: fx, fy, cx, cy
+ *             as 4 HOST doubles.  state [8] (device) is owned by the caller and zero before the first call: lambda, done,
+ *             iterations taken, current cost, stop reason, max |g| and max |delta| of the last iteration, its accepted flag --
+ *             so 2 calls of 3 and 4 iterations equal 1 call of 7 bit for bit, and a replayed graph continues the loop.
+ *             log [n_iters][6] (device): cost entering, candidate cost (NaN when a pivot rejected the step; the cost entering
+ *             on a gradient stop), lambda used, accepted (1 / 0; -1 for a row after the stop, whose other words are cost, cost,
+ *             lambda, 0, 0), max |g|, max |delta|.  LS2FM_ERR_INVALID_ARGUMENT: n_iters < 1, null buffers, loss outside 0..2,
+ *             loss_scale / initial_lambda not positive and finite, negative tolerances, sizes as above; LS2FM_ERR_WORKSPACE: null
+ *             workspace.  A workspace that prepare did not fill for these sizes moves nothing and logs NaN.
+ */
+#define LS2FM_BA_LM_MAX_VIEWS 128
+typedef struct {
+    int32_t loss;              /* 0 trivial, 1 soft_l1, 2 cauchy */
+    double loss_scale, initial_lambda, grad_tol, step_tol;
+    int32_t min_point_views;   /* prepare's argument decides; kept here for the record of a loop's options */
+} ls2fm_ba_lm_opts;
+int64_t ls2fm_bundle_adjust_lm_workspace_bytes(int32_t n_views, int64_t n_points, int64_t n_obs);
+int ls2fm_bundle_adjust_lm_prepare(const int32_t* view_start, int32_t n_views, const int32_t* obs_point, int64_t n_obs, int64_t n_points,
+                                   const uint8_t* view_constant, int32_t min_point_views, void* workspace, void* stream);
+int ls2fm_bundle_adjust_lm_run(double* poses, double* points, const double* obs_uv, int32_t n_views, int64_t n_points, int64_t n_obs,
+                               const double* intrinsic4_host, const ls2fm_ba_lm_opts* opts, int32_t n_iters, double* state,
+                               double* log, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Descriptor matching (csrc/match.hip; additions, the library stays ABI 13): the raw matches `colmap exhaustive_matcher` writes
  * into its `matches` table (preparation/main.py:98, read back at :30-37) -- COLMAP's CPU SIFT matcher with its defaults,
  * restated from the published algorithm -- for ALL image pairs in one call.  tests/match_restate.py repeats every rule in numpy.

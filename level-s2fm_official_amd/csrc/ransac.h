@@ -26,6 +26,7 @@
 #pragma once
 
 #include "ls2fm_device.h"
+#include "lm_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -266,32 +267,7 @@ __device__ __forceinline__ int32_t best_trial_of(unsigned long long best_key) {
 }
 
 // ---------------------------------------------------------------------------------------------------- workgroup reductions
-// fixed-order sum of a[N] over a workgroup of Threads: xor-shuffles inside each wave, then the waves in index order through
-// s_red [Threads / 64][N]; every thread receives the sums.  s_red is read last: a barrier before it is written again (the next
-// block_sum has its own)
-template <int N, int Threads>
-__device__ __forceinline__ void block_sum(double (&a)[N], double* s_red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double t = a[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        a[q] = t;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < N; ++q) s_red[(tid >> 6) * N + q] = a[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double t = s_red[q];
-#pragma unroll
-        for (int wv = 1; wv < Threads / 64; ++wv) t += s_red[wv * N + q];
-        a[q] = t;
-    }
-}
+using lm_math::block_sum;               // the fixed-order sum over a workgroup (lm_math.h)
 
 __device__ __forceinline__ int block_count(int c, int* s_int) {     // exact integer sum over the workgroup
     __syncthreads();

@@ -104,6 +104,12 @@ class PoseRansacOpts(Structure):
                 ("max_num_trials", c_int64), ("seed", ctypes.c_uint64), ("refine", c_int32)]
 
 
+class BALMOpts(Structure):
+    """ls2fm_ba_lm_opts"""
+    _fields_ = [("loss", c_int32), ("loss_scale", c_double), ("initial_lambda", c_double), ("grad_tol", c_double), ("step_tol", c_double),
+                ("min_point_views", c_int32)]
+
+
 class SiftOpts(Structure):
     """ls2fm_sift_opts"""
     _fields_ = [("first_octave", c_int32), ("num_octaves", c_int32), ("octave_resolution", c_int32), ("max_num_features", c_int32),
@@ -215,6 +221,10 @@ _SIGNATURES = {
     "ls2fm_bundle_adjust_prepare": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P, _P]),
     "ls2fm_bundle_adjust_run": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int64, POINTER(c_float), c_double, c_double, c_double, c_double,
                                           c_float, c_float, c_float, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "ls2fm_bundle_adjust_lm_workspace_bytes": (c_int64, [c_int32, c_int64, c_int64]),
+    "ls2fm_bundle_adjust_lm_prepare": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P, c_int32, _P, _P]),
+    "ls2fm_bundle_adjust_lm_run": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int64, POINTER(c_double), POINTER(BALMOpts), c_int32, _P, _P, _P,
+                                             _P]),
     "ls2fm_match_descriptors_workspace_bytes": (c_int64, [_P, c_int32, _P, c_int32]),
     "ls2fm_match_descriptors": (c_int32, [_P, _P, c_int32, _P, c_int32, c_double, c_double, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_sift_workspace_bytes": (c_int64, [_P, _P, c_int32, POINTER(SiftOpts)]),

@@ -26,7 +26,14 @@ max_H_inlier_ratio) of the relative pose's, the pair is planar or panoramic in C
 explained by the five-point model as a plane under a rotation and a translation, with every match an inlier and a large median
 angle, and only the homography tells.  COLMAP would still try such a pair with the pose of the homography; this mapper passes on.
 
-Deviations from COLMAP's mapper: Adam bundle adjustment (TradBALoop) instead of Ceres' Levenberg-Marquardt; no refinement of the
+Bundle adjustment: options.ba_solver = "adam" (the default) runs TradBALoop, the reference's loop; "lm" runs LMBALoop, Levenberg-
+Marquardt with a Schur complement (ls2fm_bundle_adjust_lm_run): the first registered view constant when it is picked, soft_l1 for the
+local adjustment and the plain squared error for the global one (COLMAP's choices), options.lm_iters iterations at most, the fp64
+poses and points written back as they are.  At most 128 views can be adjusted at once with "lm".
+
+Deviations from COLMAP's mapper: with "adam", Adam bundle adjustment instead of Ceres' Levenberg-Marquardt; with "lm", IRLS weights
+without Ceres' second-order correction of the loss, a dense reduced camera system instead of a sparse or iterative Schur solver,
+damping per block by its own diagonal; either way the error is in pixels and there is no refinement of the
 intrinsics (one shared pinhole camera, as the reference and TradBALoop assume); no merging of points; completion and filtering by
 pixel error (one threshold, options.tri_max_error_px) instead of angular error; tracks follow the conflict-dropping rule of
 ls2fm.tracks (a component with two key points in one image is dropped whole), so no track is split while triangulating; a view
@@ -178,7 +185,8 @@ def update_observations(tracks, obs_uv, poses, intrinsics, registered, X, track_
 @dataclasses.dataclass
 class MapperOptions:
     """The options of `reconstruct`; the names follow COLMAP's IncrementalMapperOptions where one exists.  lr_* are TradBALoop's
-    rates (its ExponentialLR runs from lr_sdf to lr_sdf_end over each loop's iterations)."""
+    rates (its ExponentialLR runs from lr_sdf to lr_sdf_end over each loop's iterations).  ba_solver: "adam" (TradBALoop with
+    local_ba_iters / global_ba_iters and the rates) or "lm" (LMBALoop with lm_iters and the lm_* choices; at most 128 views)."""
     init_min_num_inliers: int = 100
     init_min_tri_angle_deg: float = 16.0
     init_candidates: int = 16
@@ -199,6 +207,13 @@ class MapperOptions:
     lr_xyzs: float = 1e-2
     lr_sdf: float = 1e-4
     lr_sdf_end: float = 5e-5
+    ba_solver: str = "adam"
+    lm_iters: int = 50
+    lm_local_loss: str = "soft_l1"
+    lm_local_loss_scale: float = 1.0
+    lm_global_loss: str = "trivial"
+    lm_global_loss_scale: float = 1.0
+    lm_constant_first_view: bool = True
 
     def __post_init__(self):
         def refuse(name, why):
@@ -228,6 +243,19 @@ class MapperOptions:
             v = getattr(self, name)
             if not (isinstance(v, (int, float)) and 0.0 <= v <= 1.0):
                 refuse(name, "must lie in [0, 1]")
+        if self.ba_solver not in ("adam", "lm"):
+            refuse("ba_solver", 'must be "adam" or "lm"')
+        if isinstance(self.lm_iters, bool) or not isinstance(self.lm_iters, (int, np.integer)) or self.lm_iters < 0:
+            refuse("lm_iters", "must be an integer >= 0")
+        for name in ("lm_local_loss", "lm_global_loss"):
+            if getattr(self, name) not in ("trivial", "soft_l1", "cauchy"):
+                refuse(name, 'must be "trivial", "soft_l1" or "cauchy"')
+        for name in ("lm_local_loss_scale", "lm_global_loss_scale"):
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float)) and math.isfinite(v) and v > 0.0):
+                refuse(name, "must be positive and finite")
+        if not isinstance(self.lm_constant_first_view, bool):
+            refuse("lm_constant_first_view", "must be a bool")
 
     def ba_rates(self):
         return dict(lr_pose_r=self.lr_pose_r, lr_pose_t=self.lr_pose_t, lr_xyzs=self.lr_xyzs, lr_sdf=self.lr_sdf, lr_sdf_end=self.lr_sdf_end)
@@ -368,6 +396,7 @@ class _Mapper:
         self.K = torch.tensor([[self.k4[0], 0.0, self.k4[2]], [0.0, self.k4[1], self.k4[3]], [0.0, 0.0, 1.0]], dtype=torch.float64, device=dev)
         self.intr = torch.as_tensor(self.k4, device=dev)
         self.K_host = torch.tensor([[self.k4[0], 0.0, self.k4[2]], [0.0, self.k4[1], self.k4[3]], [0.0, 0.0, 1.0]], dtype=torch.float32)
+        self.K_host64 = torch.tensor([[self.k4[0], 0.0, self.k4[2]], [0.0, self.k4[1], self.k4[3]], [0.0, 0.0, 1.0]], dtype=torch.float64)
         V = self.V = len(n_views)
         image_start, edges = _tracks.edges_from_n_views(n_views)
         self.kp = [torch.as_tensor(np.asarray(t["kypts"], np.float64).reshape(len(t["kypts"]), -1)[:, :2], device=dev) for t in n_views]
@@ -474,11 +503,27 @@ class _Mapper:
         keep = self.obs_keep & self.track_valid[self.track_of]
         perm = torch.argsort(torch.where(keep, self.view, torch.full_like(self.view, self.V)) * self.n_obs + self.arange)
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        kps = [self.uv[perm[off[v]:off[v + 1]]].float() for v in range(self.V)]
         ids = [self.track_of[perm[off[v]:off[v + 1]]] for v in range(self.V)]
+        if self.opt.ba_solver == "lm":                              # fp64 as it is: no se(3) / fp32 round trip
+            return _BAViews(self.poses, self.K, self.K_host64, [self.uv[perm[off[v]:off[v + 1]]] for v in range(self.V)], ids, self.X)
+        kps = [self.uv[perm[off[v]:off[v + 1]]].float() for v in range(self.V)]
         from .utils import camera as _cam
         se3 = _cam.lie.SE3_to_se3(self.poses).float()
         return _BAViews(se3, self.K.float(), self.K_host, kps, ids, self.X.float())
+
+    def bundle_adjust_lm(self, views, pick, local):
+        """LMBALoop over the views `pick`; writes its fp64 poses and points back -> the mean pixel error at the end (0-d tensor)"""
+        from .stage import LMBALoop
+        opt = self.opt
+        loss, scale = (opt.lm_local_loss, opt.lm_local_loss_scale) if local else (opt.lm_global_loss, opt.lm_global_loss_scale)
+        loop = LMBALoop(views, cam_pick=pick, constant_views=self.order[:1] if opt.lm_constant_first_view else (), max_iter=opt.lm_iters,
+                        loss=loss, loss_scale=scale)
+        loop.run()
+        self.poses[torch.as_tensor(pick, device=self.dev)] = loop.poses
+        moved = torch.zeros(self.T, dtype=torch.bool, device=self.dev)
+        moved[loop.obs_point] = True
+        self.X = torch.where(moved[:, None], loop.xyzs_all, self.X)
+        return loop.mean_error()
 
     def bundle_adjust(self, views, pick, iters):
         """TradBALoop over the views `pick`; writes back what BA_Trad writes back -> that iteration's mean error (0-d tensor)"""
@@ -507,6 +552,8 @@ class _Mapper:
         h = torch.stack([per_view, shared]).cpu().numpy()                        # the bookkeeping read
         views = None
         err = torch.full((), float("nan"), dtype=torch.float64, device=self.dev)
+        if opt.ba_solver == "lm":
+            return self._adjust_lm(new_view, do_global, h, err)
         if new_view is not None and opt.local_ba_iters > 0 and h[0, new_view] > 0:
             others = [v for v in range(self.V) if v != new_view and self.reg_host[v] and h[1, v] > 0]
             others.sort(key=lambda v: (-int(h[1, v]), v))
@@ -519,6 +566,24 @@ class _Mapper:
             if pick:
                 views = self._ba_views(h[0])                                      # the local loop moved poses and points
                 err = self.bundle_adjust(views, pick, opt.global_ba_iters)
+        return err
+
+    def _adjust_lm(self, new_view, do_global, h, err):
+        """`adjust` with LMBALoop: the same picks; both adjustments run options.lm_iters iterations at most"""
+        opt = self.opt
+        if opt.lm_iters < 1:
+            return err
+        n_reg = int(self.reg_host.sum())
+        if new_view is not None and h[0, new_view] > 0:
+            others = [v for v in range(self.V) if v != new_view and self.reg_host[v] and h[1, v] > 0]
+            others.sort(key=lambda v: (-int(h[1, v]), v))
+            pick = [int(new_view)] + others[:opt.local_ba_views - 1]
+            if not (do_global and len(pick) == n_reg):                            # the global one covers it
+                err = self.bundle_adjust_lm(self._ba_views(h[0]), pick, True)
+        if do_global:
+            pick = [v for v in range(self.V) if self.reg_host[v] and h[0, v] > 0]
+            if pick:
+                err = self.bundle_adjust_lm(self._ba_views(h[0]), pick, False)      # the local loop moved poses and points
         return err
 
     # ---- one registration

@@ -9,6 +9,8 @@ reference's Camera / Point3D bookkeeping (COLMAP ids, feature tracks) stays with
 """
 from __future__ import annotations
 
+import ctypes
+import math
 import random
 
 import numpy as np
@@ -800,3 +802,260 @@ class TradBALoop:
         if self._err_last is None:
             raise RuntimeError("TradBALoop.written_back: no iteration has run yet")
         return self.se3_entering_last, self.xyzs_entering_last, self._err_last
+
+
+class LMBALoop:
+    """Levenberg-Marquardt bundle adjustment with a Schur complement over explicit 3-D points and [R | t] poses (include/ls2fm.h
+    states every rule: the pinhole residual in pixels, the loss `trivial` / `soft_l1` / `cauchy` as IRLS weights, per-block damping,
+    the reduced camera system, the strict accept rule and the stopping rules; tests/ba_lm_restate.py repeats them in numpy).  All
+    arithmetic is fp64.  The surface is TradBALoop's where that makes sense.
+
+    views: `TrackedViews` or the mapper's view container (its `images` are not read; `poses` may be [V,6] se(3) parameters or
+    [V,3,4]); cam_pick: the views to adjust, in this order (None: all; at most 128); constant_views: view indices (as in cam_pick)
+    whose pose does not move.  A point with fewer than min_point_views observations among the picked views does not move either
+    (its observations still constrain their cameras).  The intrinsic must be a pinhole K without skew.
+
+    On the device `run()` is ONE call of ls2fm_bundle_adjust_lm_run (six launches per iteration, nothing read back; it can be
+    captured into a graph, and a replay continues the loop); off the device the same iteration runs as torch fp64 ops (dense
+    per-block tensors, torch.linalg.cholesky) so that the bookkeeping is testable anywhere.
+
+    State after `run()` / `step()`: `poses` [V,3,4] and `xyzs_all` [M,3] (fp64; all points of the set, the ones no picked view
+    observes unchanged), `poses_se3()`, `cost()` (0-d tensor), `stopped()` -> (reason, iterations), a host read; reason is one of
+    "running", "gradient", "step", "lambda", "max_iter".
+    """
+    LOSSES = ("trivial", "soft_l1", "cauchy")
+    REASONS = ("running", "gradient", "step", "lambda")
+    MAX_VIEWS = 128                      # LS2FM_BA_LM_MAX_VIEWS
+    KEYS = ("cost", "cost_candidate", "lambda", "accepted", "grad_max", "step_max")
+
+    def __init__(self, views, cam_pick=None, constant_views=(), max_iter=50, loss="trivial", loss_scale=1.0, initial_lambda=1e-4,
+                 grad_tol=1e-10, step_tol=1e-10, min_point_views=2):
+        n_all = len(views.track_ids)
+        self.cam_pick = list(range(n_all)) if cam_pick is None else [int(c) for c in cam_pick]
+        if not self.cam_pick or any(c < 0 or c >= n_all for c in self.cam_pick) or len(set(self.cam_pick)) != len(self.cam_pick):
+            raise ValueError(f"cam_pick {self.cam_pick} does not select distinct views of 0..{n_all - 1}")
+        if len(self.cam_pick) > self.MAX_VIEWS:
+            raise ValueError(f"LMBALoop: {len(self.cam_pick)} picked views; the dense reduced camera system serves at most {self.MAX_VIEWS}")
+        if loss not in self.LOSSES:
+            raise ValueError(f"LMBALoop: loss {loss!r} is not one of {self.LOSSES}")
+        if int(max_iter) < 1 or int(min_point_views) < 1:
+            raise ValueError("LMBALoop: max_iter < 1 or min_point_views < 1")
+        for name, v, positive in (("loss_scale", loss_scale, True), ("initial_lambda", initial_lambda, True), ("grad_tol", grad_tol, False),
+                                  ("step_tol", step_tol, False)):
+            if not (math.isfinite(v) and (v > 0 if positive else v >= 0)):
+                raise ValueError(f"LMBALoop: {name} = {v!r} must be finite and {'positive' if positive else 'non-negative'}")
+        self.max_iter, self.it = int(max_iter), 0
+        self.loss, self.loss_scale, self.initial_lambda = loss, float(loss_scale), float(initial_lambda)
+        self.grad_tol, self.step_tol, self.min_point_views = float(grad_tol), float(step_tol), int(min_point_views)
+        self.views = views
+        dev = views.xyzs.device
+        k_host = getattr(views, "host_intrinsic", None)
+        k_host = (views.intrinsic.detach().cpu() if k_host is None else k_host).double()
+        if tuple(k_host.shape) != (3, 3) or not bool(torch.isfinite(k_host).all()):
+            raise ValueError(f"LMBALoop: the intrinsic must be a finite K [3, 3], got shape {tuple(k_host.shape)}")
+        if k_host[0, 1] != 0 or k_host[1, 0] != 0:
+            raise ValueError("LMBALoop: the intrinsic has skew; the solver serves a pinhole (fx, fy, cx, cy)")
+        if k_host[2].tolist() != [0.0, 0.0, 1.0]:
+            raise ValueError(f"LMBALoop: the intrinsic's last row is {k_host[2].tolist()}, not (0, 0, 1)")
+        self.k4 = [float(k_host[0, 0]), float(k_host[1, 1]), float(k_host[0, 2]), float(k_host[1, 2])]
+        p = views.poses.detach().to(dev).double()
+        p = _cam.lie.se3_to_SE3(p) if p.shape[-1] == 6 else p
+        self.poses = p[self.cam_pick].clone().contiguous()
+        self.xyzs_all = views.xyzs.detach().double().clone().contiguous()
+        self.obs_view, self.obs_point, obs_uv, self.view_start = TrackedViews.observations(views, dev, self.cam_pick)
+        self.obs_uv = obs_uv.double().contiguous()
+        if self.obs_point.numel() < 1 or any(views.track_ids[c].shape[0] < 1 for c in self.cam_pick):
+            raise ValueError("LMBALoop: a picked view has no observation")
+        const = {int(c) for c in constant_views}
+        self.view_constant = torch.tensor([1 if c in const else 0 for c in self.cam_pick], dtype=torch.uint8).to(dev)
+        self._stop_reason = None
+        if self.xyzs_all.is_cuda:
+            self._init_device()
+        else:
+            self._init_torch()
+
+    # ---- device path
+    def _init_device(self):
+        lib = _lib.load()
+        V, P, n, dev = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.poses.device
+        size = int(lib.ls2fm_bundle_adjust_lm_workspace_bytes(V, P, n))
+        if size < 0:
+            _lib.check(size, "ls2fm_bundle_adjust_lm_workspace_bytes")
+        self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
+        self._obs_point32 = self.obs_point.to(torch.int32).contiguous()
+        status = lib.ls2fm_bundle_adjust_lm_prepare(_lib.ptr(self.view_start), V, _lib.ptr(self._obs_point32), n, P, _lib.ptr(self.view_constant),
+                                                    self.min_point_views, _lib.ptr(self._ws), _lib.stream_ptr())
+        if status == -1:                 # the sizes were checked above: what is left of "invalid argument" is the lists' content
+            raise ValueError("LMBALoop: duplicate observations (a point observed twice by one view) or a point index outside the set")
+        _lib.check(status, "ls2fm_bundle_adjust_lm_prepare")
+        self._k_host = (ctypes.c_double * 4)(*self.k4)
+        self._opts = _lib.BALMOpts(self.LOSSES.index(self.loss), self.loss_scale, self.initial_lambda, self.grad_tol, self.step_tol,
+                                   self.min_point_views)
+        self._state = torch.zeros(8, dtype=torch.float64, device=dev)
+
+    def _run_device(self, n_iters):
+        lib = _lib.load()
+        V, P, n = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0]
+        log = torch.empty(n_iters, 6, dtype=torch.float64, device=self.poses.device)
+        _lib.check(lib.ls2fm_bundle_adjust_lm_run(_lib.ptr(self.poses), _lib.ptr(self.xyzs_all), _lib.ptr(self.obs_uv), V, P, n, self._k_host,
+                                                  ctypes.byref(self._opts), n_iters, _lib.ptr(self._state), _lib.ptr(log), _lib.ptr(self._ws),
+                                                  _lib.stream_ptr()), "ls2fm_bundle_adjust_lm_run")
+        return log
+
+    # ---- the same iteration as torch fp64 ops
+    def _init_torch(self):
+        key = self.obs_view * self.xyzs_all.shape[0] + self.obs_point
+        if torch.unique(key).numel() != key.numel():
+            raise ValueError("LMBALoop: duplicate observations (a point observed twice by one view)")
+        if int(self.obs_point.min()) < 0 or int(self.obs_point.max()) >= self.xyzs_all.shape[0]:
+            raise ValueError("LMBALoop: a point index outside the set")
+        self._state = torch.zeros(8, dtype=torch.float64)
+        self._point_const = torch.bincount(self.obs_point, minlength=self.xyzs_all.shape[0]) < self.min_point_views
+
+    def _residuals(self, poses, X):
+        fx, fy, cx, cy = self.k4
+        Pv = poses[self.obs_view]
+        xc = (Pv[:, :, :3] @ X[self.obs_point][:, :, None])[..., 0] + Pv[:, :, 3]
+        r = torch.stack([fx * xc[:, 0] / xc[:, 2] + cx - self.obs_uv[:, 0], fy * xc[:, 1] / xc[:, 2] + cy - self.obs_uv[:, 1]], dim=1)
+        s, c2 = (r * r).sum(1), self.loss_scale ** 2
+        if self.loss == "trivial":
+            rho, w = s, torch.ones_like(s)
+        elif self.loss == "soft_l1":
+            q = torch.sqrt(1.0 + s / c2)
+            rho, w = 2.0 * c2 * (q - 1.0), 1.0 / q
+        else:
+            rho, w = c2 * torch.log1p(s / c2), 1.0 / (1.0 + s / c2)
+        return xc, r, rho, w
+
+    @staticmethod
+    def _damp(B, lam):
+        d = torch.diagonal(B, dim1=-2, dim2=-1)
+        return B + torch.diag_embed(lam * torch.maximum(d, 1e-12 * d.max(dim=-1, keepdim=True).values))
+
+    @staticmethod
+    def _pose_update(P, d):
+        w = d[:, :3]
+        th2 = (w * w).sum(1)
+        big = th2 >= 1e-30
+        th = torch.sqrt(torch.where(big, th2, torch.ones_like(th2)))
+        A = torch.where(big, torch.sin(th) / th, torch.ones_like(th))
+        B = torch.where(big, (1.0 - torch.cos(th)) / torch.where(big, th2, torch.ones_like(th2)), torch.zeros_like(th))
+        K = torch.zeros(P.shape[0], 3, 3, dtype=P.dtype)
+        K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+        E = torch.eye(3, dtype=P.dtype) + A[:, None, None] * K + B[:, None, None] * (K @ K)
+        C = E @ P
+        C[:, :, 3] += d[:, 3:]
+        return C
+
+    def _iterate_torch(self):
+        st = self._state
+        lam = float(st[0]) if float(st[0]) > 0 else self.initial_lambda
+        if float(st[1]) != 0:
+            return torch.tensor([float(st[3]), float(st[3]), lam, -1.0, 0.0, 0.0], dtype=torch.float64)
+        V, P, ov, op = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_view, self.obs_point
+        vconst, pconst = self.view_constant.bool(), self._point_const
+        xc, r, rho, w = self._residuals(self.poses, self.xyzs_all)
+        fx, fy = self.k4[0], self.k4[1]
+        n = xc.shape[0]
+        x, y, z = xc[:, 0], xc[:, 1], xc[:, 2]
+        Jproj = torch.zeros(n, 2, 3, dtype=torch.float64)
+        Jproj[:, 0, 0], Jproj[:, 0, 2], Jproj[:, 1, 1], Jproj[:, 1, 2] = fx / z, -fx * x / (z * z), fy / z, -fy * y / (z * z)
+        skew = torch.zeros(n, 3, 3, dtype=torch.float64)
+        skew[:, 0, 1], skew[:, 0, 2], skew[:, 1, 0], skew[:, 1, 2], skew[:, 2, 0], skew[:, 2, 1] = -z, y, z, -x, -y, x
+        Jc = torch.cat([-(Jproj @ skew), Jproj], dim=2)
+        Jp = Jproj @ self.poses[ov][:, :, :3]
+        Jc[vconst[ov]] = 0.0
+        Jp[pconst[op]] = 0.0
+        U = torch.zeros(V, 6, 6, dtype=torch.float64).index_add_(0, ov, w[:, None, None] * (Jc.transpose(1, 2) @ Jc))
+        gc = torch.zeros(V, 6, dtype=torch.float64).index_add_(0, ov, w[:, None] * (Jc.transpose(1, 2) @ r[:, :, None])[..., 0])
+        Vp = torch.zeros(P, 3, 3, dtype=torch.float64).index_add_(0, op, w[:, None, None] * (Jp.transpose(1, 2) @ Jp))
+        gp = torch.zeros(P, 3, dtype=torch.float64).index_add_(0, op, w[:, None] * (Jp.transpose(1, 2) @ r[:, :, None])[..., 0])
+        W = w[:, None, None] * (Jc.transpose(1, 2) @ Jp)
+        cost = 0.5 * float(rho.sum())
+        free = ~pconst
+        gmax = max(float(gc.abs().max()), float(gp[free].abs().max()) if bool(free.any()) else 0.0)
+        pmax = max(float(self.poses[:, :, 3].abs().max()), float(self.xyzs_all[torch.unique(op)].abs().max()))
+        cand, dmax, acc, done, reason, new_lam = float("nan"), 0.0, 0.0, 0.0, 0.0, lam
+        if gmax <= self.grad_tol:
+            done, reason, cand = 1.0, 1.0, cost
+        else:
+            step = None
+            Vs, Us = self._damp(Vp, lam), self._damp(U, lam)
+            if bool(torch.isfinite(Vs).all() and torch.isfinite(Us).all() and torch.isfinite(W).all()):
+                eye3 = torch.eye(3, dtype=torch.float64).expand(P, 3, 3)
+                L, info = torch.linalg.cholesky_ex(torch.where(free[:, None, None], Vs, eye3))
+                if int(info.abs().max()) == 0:
+                    Vinv = torch.where(free[:, None, None], torch.cholesky_inverse(L), torch.zeros_like(Vs))
+                    S = torch.block_diag(*[torch.eye(6, dtype=torch.float64) if bool(vconst[v]) else Us[v] for v in range(V)])
+                    b = torch.where(vconst[:, None], torch.zeros_like(gc), -gc).reshape(-1)
+                    Wd = torch.zeros(V, 6, P, 3, dtype=torch.float64)          # dense [6 V, 3 P]: the CPU path is test-scale
+                    Wd[ov, :, op, :] = W
+                    Wd = Wd.reshape(6 * V, P, 3)
+                    Y = torch.einsum("apk,pkl->apl", Wd, Vinv)
+                    S = S - torch.einsum("apk,bpk->ab", Y, Wd)
+                    b = b + torch.einsum("apk,pk->a", Y, gp)
+                    Ls, info = torch.linalg.cholesky_ex(S)
+                    if int(info) == 0:
+                        dc = torch.cholesky_solve(b[:, None], Ls)[:, 0]
+                        dp = -(Vinv @ (gp + torch.einsum("apk,a->pk", Wd, dc))[:, :, None])[..., 0]
+                        step = (dc.reshape(V, 6), dp)
+            if step is None:
+                new_lam = lam * 10.0
+            else:
+                dc, dp = step
+                cp = torch.where(vconst[:, None, None], self.poses, self._pose_update(self.poses, dc))
+                cx = self.xyzs_all + dp
+                cand = 0.5 * float(self._residuals(cp, cx)[2].sum())
+                dmax = float(torch.fmax(dc.abs().max(), dp.abs().max()))
+                if cand < cost:
+                    acc, new_lam = 1.0, max(lam * 0.1, 1e-16)
+                    self.poses, self.xyzs_all = cp.contiguous(), cx.contiguous()
+                    if dmax <= self.step_tol * (1.0 + pmax):
+                        done, reason = 1.0, 2.0
+                else:
+                    new_lam = lam * 10.0
+        if not done and new_lam > 1e32:
+            done, reason = 1.0, 3.0
+        self._state = torch.tensor([new_lam, done, float(st[2]) + 1.0, cand if acc else cost, reason, gmax, dmax, acc], dtype=torch.float64)
+        return torch.tensor([cost, cand, lam, acc, gmax, dmax], dtype=torch.float64)
+
+    def _run_torch(self, n_iters):
+        return torch.stack([self._iterate_torch() for _ in range(n_iters)])
+
+    # ---- surface
+    def run(self, n_iters=None):
+        """the remaining iterations (or n_iters of them) -> the log's columns as tensors [n] on the loop's device: cost (entering),
+        cost_candidate, lambda, accepted (1 / 0; -1 for an iteration after the stop), grad_max, step_max"""
+        n_iters = self.max_iter - self.it if n_iters is None else int(n_iters)
+        if n_iters < 1:
+            raise ValueError(f"nothing to run: n_iters = {n_iters} (iteration {self.it} of {self.max_iter})")
+        log = self._run_device(n_iters) if self.xyzs_all.is_cuda else self._run_torch(n_iters)
+        self.it += n_iters
+        return {k: log[:, q] for q, k in enumerate(self.KEYS)}
+
+    def step(self):
+        """one iteration -> its log entries as 0-d tensors"""
+        return {k: v[0] for k, v in self.run(1).items()}
+
+    def poses_se3(self):
+        return _cam.lie.SE3_to_se3(self.poses)
+
+    def cost(self):
+        """the current cost, 1/2 sum rho (0-d tensor on the loop's device; before the first iteration: not yet evaluated, 0)"""
+        return self._state[3]
+
+    def mean_error(self):
+        """mean pixel error |r| over the loop's observations at the current state (0-d tensor, torch ops, nothing read back)"""
+        Pv = self.poses[self.obs_view]
+        xc = (Pv[:, :, :3] @ self.xyzs_all[self.obs_point][:, :, None])[..., 0] + Pv[:, :, 3]
+        u = self.k4[0] * xc[:, 0] / xc[:, 2] + self.k4[2] - self.obs_uv[:, 0]
+        v = self.k4[1] * xc[:, 1] / xc[:, 2] + self.k4[3] - self.obs_uv[:, 1]
+        return torch.sqrt(u * u + v * v).mean()
+
+    def stopped(self):
+        """(reason, iterations taken before the stop or so far) -- a host read"""
+        st = self._state.tolist()
+        reason = self.REASONS[int(st[4])]
+        if reason == "running" and self.it >= self.max_iter:
+            reason = "max_iter"
+        return reason, int(st[2])
