@@ -1242,6 +1242,45 @@ int ls2fm_update_observations(const double* poses, const double* intrinsics, con
                               int32_t* status, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact nearest neighbours between two point clouds (csrc/point_grid.hip behind ls2fm.metrics; additions, the library stays ABI
+ * 13): the primitive of the Chamfer distance of a mesh against ground truth.  The reference ships no evaluation.
+ * tests/metrics_restate.py repeats the distance rule in numpy.
+ *
+ * distance rule  of a query q and a reference r, in fp32: dx = q.x - r.x, dy and dz likewise, d2 = (dx dx + dy dy) + dz dz, every
+ *   operation rounded once, none contracted.  r QUALIFIES when d2 <= max_d2 and d2 < +inf.  The neighbour of q is the qualifying
+ *   reference of smallest d2, among equal d2 the one of lowest index: a pure function of the two clouds and max_d2, whatever
+ *   the grid, the batching of the queries or the order of the visits.  A query without a qualifying reference -- every query
+ *   with a NaN or infinite coordinate is one -- gets index -1 and d2 = +inf.  max_d2 = +inf is "no cut-off"; NaN or a negative
+ *   max_d2 is refused.
+ * grid  origin float [3], cell_size h > 0, inv_cell_size (the caller's fp32 1 / h) and dim int32 [3] describe a uniform grid of
+ *   dim[0] dim[1] dim[2] < 2^31 - 1 cells; the cell of p on an axis is clamp(floor((p - origin) * inv_cell_size), 0, dim - 1) in
+ *   fp32 (fminf / fmaxf before the conversion, so a NaN lands in a border cell), cell id = (cz dim[1] + cy) dim[0] + cx.  For
+ *   exact answers the caller makes origin the per-axis minimum of the references and dim at least that formula's cell of the
+ *   per-axis maximum plus one, so that no reference is clamped (ls2fm.metrics.PointGrid does); any other grid is still walked
+ *   without a read outside the arrays.
+ * build  ref float [n_points][3] (finite: the caller guarantees it) -> cell_start int32 [cells + 1], the exclusive prefix sum of
+ *   the cells' point counts, and sorted float [n_points][4], 16-byte aligned: the points in cell order as x, y, z and the BITS of
+ *   their int32 index in ref.  Counting and scattering use 32-bit integer atomics, so the order inside a cell may differ between
+ *   runs; no result of a query depends on it.  workspace: the size query's bytes (negative: refused sizes).  n_points = 0 zeroes
+ *   cell_start.  One memset and five launches, nothing read back.
+ * query  queries float [n_queries][3] -> idx int32 [n_queries] (index into ref, or -1), d2 float [n_queries].  One launch, one
+ *   query per lane: the query's own cell, then the Chebyshev rings 1, 2, ... around it.  After ring k every unvisited reference is
+ *   at least (k - slack) h away, slack = 2^-21 max(dim) covering the two fp32 roundings of the cell assignment, and the walk stops
+ *   when min(best d2, max_d2) < ((k - slack) h)^2 (1 - 2^-18), strictly, so that a tied reference of a later ring is still
+ *   visited; the factor covers the rounding of d2 itself.  The ring loop runs at most max(dim) + 1 times.  Nothing is read back:
+ *   the call can be captured into a graph.  n_queries = 0 returns at once; n_points = 0 fills -1 / +inf without a launch.
+ * No floating-point atomic anywhere.  Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL array, a
+ * negative count, n_points >= 2^31, a cell size or reciprocal that is not positive and finite, a dim below 1 or 2^31 - 1 cells or
+ * more, a misaligned sorted; LS2FM_ERR_WORKSPACE for a NULL workspace.
+ */
+int64_t ls2fm_point_grid_workspace_bytes(int64_t n_points, int64_t n_cells);
+int ls2fm_point_grid_build(const float* ref, int64_t n_points, const float* origin, float cell_size, float inv_cell_size,
+                           const int32_t* dim, int32_t* cell_start, float* sorted, void* workspace, void* stream);
+int ls2fm_point_grid_query(const float* queries, int64_t n_queries, const float* sorted, const int32_t* cell_start, int64_t n_points,
+                           const float* origin, float cell_size, float inv_cell_size, const int32_t* dim, float max_d2, int32_t* idx,
+                           float* d2, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

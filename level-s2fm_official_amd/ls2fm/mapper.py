@@ -370,6 +370,12 @@ class Reconstruction:
         out.views = views
         return out
 
+    def pose_errors(self, gt_poses, align=True, with_scale=True):
+        """ls2fm.metrics.pose_errors of the registered views' poses against ground truth [V, 3, 4] or [V, 4, 4]"""
+        from .metrics import pose_errors
+        return pose_errors(self.poses, gt_poses, align=align, with_scale=with_scale,
+                           registered=torch.as_tensor(np.asarray(self.registered, dtype=bool)))
+
 
 # ---------------------------------------------------------------------------------------------------------------- the loop
 def _intrinsic4(intrinsic):

@@ -1,0 +1,408 @@
+"""Reconstruction metrics on the device: how good a result is against ground truth.  The paper reports camera error after a
+similarity alignment (rotation in degrees, ATE) and the DTU Chamfer distance of the mesh (accuracy, completeness, their mean); the
+reference ships neither, and the usual CPU KD-tree evaluation of two DTU-sized clouds takes minutes per scan.
+
+  PointGrid / nearest_neighbors   exact nearest neighbours over a uniform grid (ls2fm_point_grid_*, csrc/point_grid.hip)
+  nearest_neighbors_bruteforce    the same rule as plain torch ops on any device: the timing baseline and the host tests' route
+  voxel_downsample                one point per voxel, the lowest index
+  chamfer / evaluate_mesh         accuracy, completeness, overall, precision / recall / F-score
+  align_sim3 / pose_errors        Umeyama's similarity alignment, rotation and centre errors, ATE
+
+The distance rule (include/ls2fm.h): dx = q.x - r.x, dy, dz likewise, d2 = (dx dx + dy dy) + dz dz, every operation one rounded
+fp32 operation; a reference qualifies when d2 <= max_d2 and d2 < +inf; the smallest d2 wins, among equal d2 the lowest index.  The
+result is a pure function of the two clouds: no grid, batch or visiting order shows in it, and tests/metrics_restate.py holds it bit
+for bit.  There is no CPU path for the grid: CPU tensors, a missing device or a missing library raise.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream_ptr
+
+# The automatic cell size (auto_cell_size): "surface" sizes the cells for points on a surface, "volume" for points filling the box.
+# Chosen by tools/time_metrics.py on 2 M x 2 M points of a sphere surface (profiles/metrics_time.json).
+AUTO_CELL_RULE = "surface"
+
+
+def _device(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("ls2fm.metrics: the point grid runs on MI355X only (got a CPU tensor); there is no CPU fallback -- "
+                               "nearest_neighbors_bruteforce is the explicit torch form")
+
+
+def _points(x, name):
+    x = torch.as_tensor(x)
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"ls2fm.metrics: {name} must be [n, 3], got shape {tuple(x.shape)}")
+    return x
+
+
+def _max_d2(max_dist):
+    """float32(max_dist) * float32(max_dist) as a numpy float32; +inf for None"""
+    if max_dist is None:
+        return np.float32(np.inf)
+    m = np.float32(max_dist)
+    if not m >= 0:
+        raise ValueError(f"ls2fm.metrics: max_dist {max_dist} must be >= 0 (None: no cut-off)")
+    with np.errstate(over="ignore"):
+        return np.float32(m * m)
+
+
+def _dims(extent32, inv_h):
+    """cells per axis that hold every reference: floor((max - origin) * inv_h) + 1 in the device's fp32 arithmetic (float64 [3])"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.floor((extent32 * inv_h).astype(np.float32)).astype(np.float64) + 1.0
+
+
+def auto_cell_size(lo, hi, n, max_cells=2 ** 25, rule=None):
+    """The automatic cell size of a cloud of n points inside the box [lo, hi] (host numbers).  Over the axes of non-zero extent e:
+      "surface"  three axes: sqrt(2 (ex ey + ey ez + ez ex) / n), about one point per cell that a surface through the box crosses;
+                 two axes: sqrt(e1 e2 / n); one axis: e1 / n
+      "volume"   (product of e / n) ^ (1 / axes): one point per cell of the box
+    a cloud without extent gets 1.  The size is then grown by 5 % at a time until the grid has at most max_cells cells, so it is
+    always positive and finite."""
+    rule = AUTO_CELL_RULE if rule is None else rule
+    if rule not in ("surface", "volume"):
+        raise ValueError(f"ls2fm.metrics.auto_cell_size: rule {rule!r} is neither 'surface' nor 'volume'")
+    lo32, hi32 = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    extent32 = (hi32 - lo32).astype(np.float32)
+    e = [float(v) for v in extent32 if v > 0]
+    n = max(int(n), 1)
+    if not e:
+        h = 1.0
+    elif rule == "volume" or len(e) < 3:
+        h = (math.prod(e) / n) ** (1.0 / len(e))
+    else:
+        h = math.sqrt(2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0]) / n)
+    h = max(h, max(e, default=1.0) * 2.0 ** -20, float(np.finfo(np.float32).tiny) * 2.0 ** 24)
+    while True:
+        h32 = np.float32(h)
+        if np.isfinite(h32) and h32 > 0 and float(np.prod(_dims(extent32, np.float32(1) / h32))) <= max_cells:
+            return float(h32)
+        h *= 1.05
+
+
+class PointGrid:
+    """A uniform grid over the reference cloud `ref` (float32 [N, 3] on the device, finite) for exact nearest-neighbour queries.
+    origin is the per-axis minimum; `cell_size` is honoured exactly (ValueError if the grid would have more than `max_cells`
+    cells), None takes auto_cell_size.  Building reads the bounding box on the host once; cell_start int32 [cells + 1], sorted_xyz
+    float32 [N, 3] and sorted_index int32 [N] (views of one [N, 4] array) are the grid."""
+
+    def __init__(self, ref, cell_size=None, max_cells=2 ** 25):
+        ref = _points(ref, "ref")
+        _device(ref)
+        lib = _lib.load()
+        self.ref = _lib.cf(ref)
+        self.n = int(self.ref.shape[0])
+        self.device = dev = self.ref.device
+        if self.n >= 1 << 31:
+            raise ValueError(f"ls2fm.metrics.PointGrid: {self.n} points, 2^31 or more")
+        if self.n:
+            box = torch.stack([self.ref.amin(dim=0), self.ref.amax(dim=0)]).cpu().numpy()          # the one host read
+            if not np.isfinite(box).all():
+                raise ValueError("ls2fm.metrics.PointGrid: the reference cloud holds a NaN or infinite coordinate")
+        else:
+            box = np.zeros((2, 3), np.float32)
+        lo, hi = box[0].astype(np.float32), box[1].astype(np.float32)
+        if cell_size is None:
+            h = np.float32(auto_cell_size(lo, hi, self.n, max_cells))
+        else:
+            h = np.float32(cell_size)
+            if not (np.isfinite(h) and h > 0):
+                raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {cell_size} must be positive and finite")
+        with np.errstate(over="ignore"):
+            inv_h = np.float32(1) / h
+        if not (np.isfinite(inv_h) and inv_h > 0):
+            raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {cell_size} has no finite fp32 reciprocal")
+        dims = _dims((hi - lo).astype(np.float32), inv_h)
+        cells = float(np.prod(dims))
+        if not np.isfinite(cells) or cells > max_cells or cells >= 2 ** 31 - 1:
+            raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {float(h)} gives {dims.astype(np.int64).tolist()} cells, "
+                             f"more than max_cells = {max_cells}")
+        self.origin, self.cell_size, self.inv_cell_size = lo, float(h), float(inv_h)
+        self.dim = tuple(int(d) for d in dims)
+        self.n_cells = int(cells)
+        self._origin = (ctypes.c_float * 3)(*[float(v) for v in lo])
+        self._dim = (ctypes.c_int32 * 3)(*self.dim)
+        with torch.cuda.device(dev):
+            self.cell_start = torch.empty(self.n_cells + 1, dtype=torch.int32, device=dev)
+            self.sorted = torch.empty(self.n, 4, dtype=torch.float32, device=dev)
+            ws_bytes = int(lib.ls2fm_point_grid_workspace_bytes(self.n, self.n_cells))
+            if ws_bytes < 0:
+                check(ws_bytes, "ls2fm_point_grid_workspace_bytes")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            check(lib.ls2fm_point_grid_build(ptr(self.ref), self.n, self._origin, self.cell_size, self.inv_cell_size, self._dim,
+                                             ptr(self.cell_start), ptr(self.sorted), ptr(ws), stream_ptr()), "ls2fm_point_grid_build")
+        self.sorted_xyz = self.sorted[:, :3]
+        self.sorted_index = self.sorted.view(torch.int32)[:, 3]
+
+    def _order(self, q):
+        """a permutation that walks the queries cell by cell (any order gives the same results: this one is for the caches)"""
+        o = torch.as_tensor(self.origin, device=q.device)
+        c = ((torch.nan_to_num(q, nan=0.0, posinf=0.0, neginf=0.0) - o) * self.inv_cell_size).floor()
+        c = torch.minimum(c.clamp_(min=0), torch.tensor([d - 1 for d in self.dim], dtype=torch.float32, device=q.device)).long()
+        return torch.argsort((c[:, 2] * self.dim[1] + c[:, 1]) * self.dim[0] + c[:, 0])
+
+    def query(self, q, max_dist=None, sort=None):
+        """(idx int32 [M], d2 float32 [M]) of the queries `q` (float32 [M, 3] on the grid's device): the index into `ref` of each
+        query's nearest reference by the distance rule and its fp32 squared distance; -1 and +inf where no reference lies within
+        `max_dist` (d2 <= float32(max_dist)^2; None: no cut-off) and for a NaN or infinite query.  Reads nothing back, so it can
+        be captured into a graph.  The queries are walked in the order of their cells and the results put back (measured faster by the
+        same tool; a torch sort, so not while a stream captures); sort=False walks them as given.  No result depends on it."""
+        q = _points(q, "q")
+        _device(q)
+        if q.device != self.device:
+            raise ValueError(f"ls2fm.metrics.PointGrid.query: queries on {q.device}, the grid on {self.device}")
+        q = _lib.cf(q)
+        max_d2 = _max_d2(max_dist)
+        m = int(q.shape[0])
+        with torch.cuda.device(self.device):
+            capturing = torch.cuda.is_current_stream_capturing()
+            perm = None
+            if (sort is None or sort) and not capturing and m > 1 and self.n:
+                perm = self._order(q)
+                q = q[perm]
+            idx = torch.empty(m, dtype=torch.int32, device=self.device)
+            d2 = torch.empty(m, dtype=torch.float32, device=self.device)
+            check(_lib.load().ls2fm_point_grid_query(ptr(q), m, ptr(self.sorted), ptr(self.cell_start), self.n, self._origin,
+                                                     self.cell_size, self.inv_cell_size, self._dim, float(max_d2), ptr(idx), ptr(d2),
+                                                     stream_ptr()), "ls2fm_point_grid_query")
+            if perm is not None:
+                idx, d2 = torch.empty_like(idx).index_copy_(0, perm, idx), torch.empty_like(d2).index_copy_(0, perm, d2)
+        return idx, d2
+
+
+def nearest_neighbors(q, ref, max_dist=None, cell_size=None):
+    """PointGrid(ref, cell_size).query(q, max_dist) in one call: (idx int32 [M], d2 float32 [M])"""
+    q, ref = _points(q, "q"), _points(ref, "ref")
+    _device(q, ref)
+    return PointGrid(ref, cell_size=cell_size).query(q, max_dist)
+
+
+def nearest_neighbors_bruteforce(q, ref, max_dist=None, chunk=None):
+    """The distance rule as plain torch ops, on whatever device the clouds are on: all M x N distances, `chunk` queries at a time
+    (default: 2^24 distances per chunk).  The column differences, the three products and the two sums are separate torch ops in
+    the stated order, so each rounds once; the minimum is taken first and the lowest index among the entries that equal it second
+    (torch.argmin does not promise the first).  -> (idx int32 [M], d2 float32 [M]).  The timing baseline of the grid and the CPU
+    route of the host tests; nothing in the library falls back to it."""
+    q, ref = _points(q, "q").float(), _points(ref, "ref").float()
+    dev = q.device
+    ref = ref.to(dev)
+    m, n = int(q.shape[0]), int(ref.shape[0])
+    max_d2 = float(_max_d2(max_dist))
+    idx = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    d2_out = torch.full((m,), float("inf"), dtype=torch.float32, device=dev)
+    if m == 0 or n == 0:
+        return idx, d2_out
+    chunk = max(1, (1 << 24) // n) if chunk is None else max(1, int(chunk))
+    rx, ry, rz = ref[:, 0][None, :], ref[:, 1][None, :], ref[:, 2][None, :]
+    index = torch.arange(n, device=dev)[None, :]
+    big = torch.iinfo(torch.int64).max
+    for s in range(0, m, chunk):
+        c = q[s:s + chunk]
+        dx, dy, dz = c[:, 0:1] - rx, c[:, 1:2] - ry, c[:, 2:3] - rz
+        d2 = (dx * dx + dy * dy) + dz * dz
+        ok = (d2 <= max_d2) & (d2 < float("inf"))
+        d2 = torch.where(ok, d2, torch.full_like(d2, float("inf")))
+        mn = d2.amin(dim=1)
+        first = torch.where((d2 == mn[:, None]) & ok, index, torch.full_like(index, big)).amin(dim=1)
+        idx[s:s + chunk] = torch.where(mn < float("inf"), first, torch.full_like(first, -1)).to(torch.int32)
+        d2_out[s:s + chunk] = mn
+    return idx, d2_out
+
+
+_VOXEL_BITS = 21
+
+
+def voxel_downsample(points, voxel):
+    """int64 indices, ascending, of the points kept when every voxel of side `voxel` keeps its lowest-index point.  Voxel
+    coordinates are floor(double(p) / voxel), each stored in 21 bits (so inside [-2^20, 2^20): ValueError beyond, and for a NaN or
+    infinite point) of one int64 key; torch ops on the points' device, one host read for that check.
+    A stated deviation: the usual DTU evaluation script thins a cloud by a sequential greedy radius rule (a point is dropped when
+    a kept point lies within the radius), which depends on the visiting order and keeps points up to sqrt(3) times sparser or denser
+    than this; one point per voxel is order-free up to the choice of the lowest index and runs as one sort."""
+    p = _points(points, "points")
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError(f"ls2fm.metrics.voxel_downsample: voxel {voxel} must be positive and finite")
+    if p.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int64, device=p.device)
+    v = torch.floor(p.to(torch.float64) / float(voxel))
+    half = float(1 << (_VOXEL_BITS - 1))
+    if not bool((torch.isfinite(v) & (v >= -half) & (v < half)).all()):
+        raise ValueError(f"ls2fm.metrics.voxel_downsample: a voxel coordinate does not fit in {_VOXEL_BITS} bits "
+                         f"(|p / voxel| up to 2^{_VOXEL_BITS - 1}), or a point is not finite")
+    c = v.to(torch.int64) + (1 << (_VOXEL_BITS - 1))
+    key = (c[:, 0] << (2 * _VOXEL_BITS)) | (c[:, 1] << _VOXEL_BITS) | c[:, 2]
+    key, order = torch.sort(key, stable=True)                     # stable: the first of a run of equal keys is its lowest index
+    first = torch.ones_like(key, dtype=torch.bool)
+    first[1:] = key[1:] != key[:-1]
+    return torch.sort(order[first]).values
+
+
+def _masked(x, mask, name):
+    x = _points(x, name)
+    if mask is None:
+        return x
+    mask = torch.as_tensor(mask, device=x.device)
+    if mask.dtype != torch.bool or mask.shape != (x.shape[0],):
+        raise ValueError(f"ls2fm.metrics: {name}_mask must be bool [{x.shape[0]}], got {mask.dtype} {tuple(mask.shape)}")
+    return x[mask]
+
+
+def _one_side(q, ref, max_dist, thresholds, brute_force):
+    """fp64 [2 + len(thresholds)] on the device: the number of queries with a neighbour, the mean of their distances, and per
+    threshold the fraction of ALL queries whose neighbour passes it"""
+    if brute_force:
+        idx, d2 = nearest_neighbors_bruteforce(q, ref, max_dist)
+    else:
+        idx, d2 = nearest_neighbors(q, ref, max_dist)
+    has = idx >= 0
+    n = has.sum().to(torch.float64)
+    dist = torch.sqrt(d2.to(torch.float64))
+    mean = torch.where(has, dist, torch.zeros_like(dist)).sum() / n                    # 0 / 0 = NaN for an empty side
+    m = torch.tensor(float(q.shape[0]), dtype=torch.float64, device=q.device)
+    rates = [(has & (d2 <= float(np.float32(t) * np.float32(t)))).sum().to(torch.float64) / m for t in thresholds]
+    return torch.stack([n, mean] + rates)
+
+
+def chamfer(pred, gt, max_dist, thresholds=(), pred_mask=None, gt_mask=None, brute_force=False):
+    """The DTU-style Chamfer figures of a predicted cloud against ground truth (both float32 [., 3], on the device unless
+    brute_force): a dict of
+      accuracy        mean distance from the points of `pred` to their nearest point of `gt`, over those with one inside max_dist
+      completeness    the same from `gt` to `pred`;  overall: the mean of the two
+      n_accuracy, n_completeness   how many points had such a neighbour (ints)
+      thresholds, precision, recall, fscore   per threshold tau (tuples in the order given): the fraction of pred (of gt) whose
+                      neighbour has d2 <= float32(tau)^2, and 2 p r / (p + r) (0 when both are 0)
+    Distances are sqrt(double(d2)) of the fp32 d2 of the distance rule, the means are fp64 sums on the device, and the dict costs
+    one host read.  pred_mask / gt_mask (bool) select the points that take part: visibility volumes and ground-plane filters
+    are the dataset's and stay with the caller.  An empty side gives NaN for its mean (and its rates) and 0 for its count.
+    brute_force=True takes nearest_neighbors_bruteforce instead of the grid (any device; for checks and small clouds)."""
+    pred, gt = _masked(pred, pred_mask, "pred"), _masked(gt, gt_mask, "gt")
+    thresholds = tuple(float(t) for t in thresholds)
+    if not brute_force:
+        _device(pred, gt)
+    if pred.device != gt.device:
+        raise ValueError(f"ls2fm.metrics.chamfer: pred on {pred.device}, gt on {gt.device}")
+    acc = _one_side(pred, gt, max_dist, thresholds, brute_force)
+    com = _one_side(gt, pred, max_dist, thresholds, brute_force)
+    a, c = torch.stack([acc, com]).cpu().tolist()                                     # the one host read
+    return _chamfer_dict(a, c, thresholds)
+
+
+def _chamfer_dict(a, c, thresholds):
+    prec, rec = tuple(a[2:]), tuple(c[2:])
+    f = tuple((2.0 * p * r / (p + r)) if p + r > 0 else (0.0 if p + r == 0 else float("nan")) for p, r in zip(prec, rec))
+    return dict(accuracy=a[1], completeness=c[1], overall=0.5 * (a[1] + c[1]), n_accuracy=int(a[0]), n_completeness=int(c[0]),
+                thresholds=thresholds, precision=prec, recall=rec, fscore=f)
+
+
+def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), generator=None, brute_force=False, return_points=False):
+    """The Chamfer figures of a mesh against a ground-truth cloud: ceil(area / density^2) points of ls2fm.mesh.sample_surface
+    (uniforms from `generator`), both clouds thinned by voxel_downsample at `density`, then `chamfer`.
+    -> the dict of chamfer plus n_pred and n_gt, the sizes of the two clouds compared (and, with return_points, pred_points and
+    gt_points themselves).  One host read for the area, one per thinning, one for the dict.  A dataset's masks need the sampled
+    points: such a caller runs these steps itself and passes the masks to `chamfer`."""
+    from . import mesh
+    verts, gt = _points(verts, "verts"), _points(gt_points, "gt_points")
+    _device(verts, faces, gt)
+    if not (np.isfinite(density) and density > 0):
+        raise ValueError(f"ls2fm.metrics.evaluate_mesh: density {density} must be positive and finite")
+    area = float(mesh._face_areas64(verts, faces).sum())
+    count = int(math.ceil(area / (float(density) * float(density))))
+    if count >= 1 << 31:
+        raise ValueError(f"ls2fm.metrics.evaluate_mesh: {count} samples (area {area} at density {density}), 2^31 or more")
+    pts = mesh.sample_surface(verts, faces, count, generator=generator) if count else verts.new_zeros((0, 3), dtype=torch.float32)
+    pts = pts[voxel_downsample(pts, density)]
+    gt = gt.float()
+    gt = gt[voxel_downsample(gt, density)]
+    out = chamfer(pts, gt, max_dist, thresholds=thresholds, brute_force=brute_force)
+    out.update(n_pred=int(pts.shape[0]), n_gt=int(gt.shape[0]))
+    if return_points:
+        out.update(pred_points=pts, gt_points=gt)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- camera poses
+def align_sim3(src, dst, with_scale=True):
+    """Umeyama's closed form: the similarity (s, R, t) that minimises sum |dst_i - (s R src_i + t)|^2 over [n, 3] point sets, in
+    fp64.  The means, the 3 x 3 covariance and the variance are torch ops on the inputs' device; the 3 x 3 SVD runs on the host
+    (no dependence on a device solver); a reflection is corrected through the sign of det(U) det(V).  with_scale=False fixes s = 1.
+    -> (s float, R fp64 [3, 3], t fp64 [3]; tensors on src's device)."""
+    src, dst = _points(src, "src"), _points(dst, "dst")
+    if src.shape != dst.shape or src.shape[0] < 1:
+        raise ValueError(f"ls2fm.metrics.align_sim3: {tuple(src.shape)} against {tuple(dst.shape)}")
+    dev = src.device
+    a, b = src.to(torch.float64), dst.to(device=dev, dtype=torch.float64)
+    n = a.shape[0]
+    mu_a, mu_b = a.sum(dim=0) / n, b.sum(dim=0) / n
+    xa, xb = a - mu_a, b - mu_b
+    cov = (xb.t() @ xa) / n
+    var_a = (xa * xa).sum() / n
+    host = torch.cat([cov.reshape(-1), var_a.reshape(1), mu_a, mu_b]).cpu().numpy()      # the one host read
+    cov_h, var_h, mu_ah, mu_bh = host[:9].reshape(3, 3), host[9], host[10:13], host[13:16]
+    U, D, Vt = np.linalg.svd(cov_h)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    R = (U * S) @ Vt
+    s = float((D * S).sum() / var_h) if with_scale and var_h > 0 else 1.0
+    t = mu_bh - s * (R @ mu_ah)
+    return s, torch.as_tensor(R, dtype=torch.float64, device=dev), torch.as_tensor(t, dtype=torch.float64, device=dev)
+
+
+def _rt(poses, name):
+    p = torch.as_tensor(poses)
+    if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"ls2fm.metrics.pose_errors: {name} must be [V, 3, 4] or [V, 4, 4], got {tuple(p.shape)}")
+    p = p.to(torch.float64)
+    return p[:, :3, :3], p[:, :3, 3]
+
+
+def pose_errors(poses_est, poses_gt, align=True, with_scale=True, registered=None):
+    """Camera errors of estimated poses against ground truth, both [R | t] world-to-camera ([V, 3, 4] or [V, 4, 4]; the mapper's
+    convention), in fp64.  The camera centres C = -R^T t of the estimate are aligned to the ground truth's by align_sim3 (align=
+    False compares them as they are), X_gt = s A X_est + a, and the estimated orientations are taken along: R_est A^T.
+    registered: bool [V] (read on the host) or None; views that are not registered are left out and counted.  -> dict of
+      rot_err_deg [V], centre_err [V]   per view (fp64 host tensors; NaN for a view left out): the angle of R_est A^T R_gt^T, taken as
+                      atan2(|axis part|, (trace - 1) / 2) so that it is accurate near 0, and |s A C_est + a - C_gt|
+      ate_rmse        sqrt(mean centre_err^2), the absolute trajectory error
+      rot_err_mean_deg, rot_err_max_deg, centre_err_mean, centre_err_max, scale, n_views (compared), n_unregistered
+    An alignment needs three views; fewer raise.  One host read for the alignment's SVD, one for the dict."""
+    Re, te = _rt(poses_est, "poses_est")
+    Rg, tg = _rt(poses_gt, "poses_gt")
+    dev = Re.device
+    Rg, tg = Rg.to(dev), tg.to(dev)
+    V = Re.shape[0]
+    if Rg.shape[0] != V:
+        raise ValueError(f"ls2fm.metrics.pose_errors: {V} estimated poses against {Rg.shape[0]}")
+    reg = torch.ones(V, dtype=torch.bool) if registered is None else torch.as_tensor(registered).cpu()      # the mapper keeps it on the host
+    if reg.dtype != torch.bool or reg.shape != (V,):
+        raise ValueError(f"ls2fm.metrics.pose_errors: registered must be bool [{V}]")
+    sel_host = torch.nonzero(reg).reshape(-1)
+    sel = sel_host.to(dev)
+    n = int(sel.numel())
+    if n < (3 if align else 1):
+        raise ValueError(f"ls2fm.metrics.pose_errors: {n} registered views; {'an alignment needs three' if align else 'none to compare'}")
+    Re, te, Rg, tg = Re[sel], te[sel], Rg[sel], tg[sel]
+    Ce = -(Re.transpose(1, 2) @ te[:, :, None])[:, :, 0]
+    Cg = -(Rg.transpose(1, 2) @ tg[:, :, None])[:, :, 0]
+    if align:
+        s, A, a = align_sim3(Ce, Cg, with_scale=with_scale)
+    else:
+        s, A, a = 1.0, torch.eye(3, dtype=torch.float64, device=dev), torch.zeros(3, dtype=torch.float64, device=dev)
+    centre = ((s * (Ce @ A.t()) + a) - Cg).norm(dim=1)
+    D = (Re @ A.t()) @ Rg.transpose(1, 2)
+    axis = torch.stack([D[:, 2, 1] - D[:, 1, 2], D[:, 0, 2] - D[:, 2, 0], D[:, 1, 0] - D[:, 0, 1]], dim=1).norm(dim=1) / 2
+    rot = torch.rad2deg(torch.atan2(axis, ((D[:, 0, 0] + D[:, 1, 1]) + D[:, 2, 2] - 1) / 2))
+    nan = torch.full((V,), float("nan"), dtype=torch.float64, device=dev)
+    out = torch.stack([nan.index_copy(0, sel, rot), nan.index_copy(0, sel, centre)]).cpu()          # the dict's host read
+    r, c = out[0][sel_host], out[1][sel_host]
+    return dict(rot_err_deg=out[0], centre_err=out[1], ate_rmse=float((c * c).mean().sqrt()),
+                rot_err_mean_deg=float(r.mean()), rot_err_max_deg=float(r.max()), centre_err_mean=float(c.mean()),
+                centre_err_max=float(c.max()), scale=float(s), n_views=n, n_unregistered=V - n)
