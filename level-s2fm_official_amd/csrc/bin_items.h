@@ -279,15 +279,6 @@ __device__ __forceinline__ int* scan_ticket_dev(const BinMeta& bm) { return rein
 // unit counter of the persistent slab_accumulate launch (bin_scatter.hip): zeroed by the scatter_fill launch in front of it
 __host__ __device__ __forceinline__ int* acc_claim(const BinMeta& bm) { return reinterpret_cast<int*>(bm.level_bound) + 50; }
 
-__device__ __forceinline__ int wave_scan_incl_i32(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // nt = workgroup size: a multiple of 64, 64 <= nt <= 512.  The job's [n_tiles][16] block of counts goes through LDS in
 // pieces of 512 tiles (the benchmark: one piece; coalesced, independent loads in flight together: a thread walking its column in global memory pays one
 // dependent ~1 us access per tile, 20+ us per job -- and these jobs share a launch with shade_fwd).
@@ -358,8 +349,7 @@ constexpr int kScanArenaInts = kScanTiles * kScanGroup + (512 / kScanGroup) * kS
                              ? __hip_atomic_load(&bm.count[lv * kBins + bb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
             tot += held[h][c];
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+        tot = wave_sum(tot);
         if (lane == 0 && lv < LS2FM_MAX_LEVELS) level_total[lv] = tot;
     }
     __syncthreads();
@@ -374,7 +364,7 @@ constexpr int kScanArenaInts = kScanTiles * kScanGroup + (512 / kScanGroup) * kS
         for (int c = 0; c < kChunks; ++c) {
             const int bb = 64 * c + lane;
             const int cnt = held[h][c];
-            const int incl = wave_scan_incl_i32(cnt, lane);
+            const int incl = wave_scan_incl(cnt, lane);
             if (bb < kBins) bm.start[lv * kBins + bb] = before + run2 + incl - cnt;
             run2 += __shfl(incl, 63, 64);
         }

@@ -214,7 +214,7 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
         for (int c = 0; c < (kBins + 63) / 64; ++c) {
             const int b = 64 * c + lane;
             const int cnt = b < kBins ? run_len[b] : 0;
-            const int incl = wave_scan_incl_i32(cnt, lane);
+            const int incl = wave_scan_incl(cnt, lane);
             if (b < kBins) lds_off[b] = run + incl - cnt;
             run += __shfl(incl, 63, 64);
         }
@@ -349,7 +349,7 @@ scatter_fill_kernel(LevelSet lv, FieldC fc, const float* __restrict__ center, co
             float b = 0.f;
             for (int64_t r = tid; r < n_rays; r += kFillThreads) b = fmaxf(b, ray_bound[(int64_t)(16 * which + l) * r_pad + r]);
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) b = fmaxf(b, __shfl_xor(b, o, 64));
+            for (int o = 32; o > 0; o >>= 1) b = fmaxf(b, __shfl_xor(b, o, 64));       // (wave_max(b) schedules scatter_fill_kernel differently)
             if (lane == 0) red[tid >> 6] = b;
             __syncthreads();
             if (tid == 0) {

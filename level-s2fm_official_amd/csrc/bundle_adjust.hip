@@ -19,20 +19,20 @@
 // The learning-rate dependent scalars of every iteration are formed on the host as torch forms them (adam.hip's header) from the
 // caller's step count: the rates by ExponentialLR's chained multiplication from step 0, so a loop split over several calls steps
 // exactly as one call does.
-#include <vector>
-
 #include "adam_element.h"
+#include "ba_index.h"
 #include "reproject_point.h"
 #include "se3_exp.h"
+#include "workspace.h"
 
 namespace {
+
+using ba_index::sizes_ok;
 
 constexpr int kBaThreads = 256;
 constexpr int32_t kBaMagic = 0x42415431;           // "BAT1": the workspace was filled by ls2fm_bundle_adjust_prepare for these sizes
 
-// Workspace: every array the kernels index through is the library's OWN validated copy (view_start, obs_point, the CSR), so a
-// caller's index can never take a kernel out of bounds after prepare has accepted it.
-struct BaWs {
+struct BaWs {                  // the index arrays: ba_index.h
     int32_t* header;           // [8]: magic, n_views, n_points, n_obs
     double* partial;           // [V][2]: sum robust, sum err of the view
     float* d_se3;              // [V][6]: gradient w.r.t. the se(3) parameters for weight 1
@@ -44,26 +44,20 @@ struct BaWs {
     int64_t bytes;
 };
 
-int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
-
 BaWs ba_layout(void* base, int64_t V, int64_t P, int64_t n) {
+    Workspace ws(base, 16);
     BaWs w;
-    char* p = (char*)base;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { char* q = p + at; at += align16(bytes); return q; };
-    w.header = (int32_t*)take(32);
-    w.partial = (double*)take(16 * V);
-    w.d_se3 = (float*)take(24 * V);
-    w.g_obs = (float*)take(12 * n);
-    w.view_start = (int32_t*)take(4 * (V + 1));
-    w.obs_point = (int32_t*)take(4 * n);
-    w.point_start = (int32_t*)take(4 * (P + 1));
-    w.point_obs = (int32_t*)take(4 * n);
-    w.bytes = at;
+    w.header = ws.take<int32_t>(8);
+    w.partial = ws.take<double>(2 * V);
+    w.d_se3 = ws.take<float>(6 * V);
+    w.g_obs = ws.take<float>(3 * n);
+    w.view_start = ws.take<int32_t>(V + 1);
+    w.obs_point = ws.take<int32_t>(n);
+    w.point_start = ws.take<int32_t>(P + 1);
+    w.point_obs = ws.take<int32_t>(n);
+    w.bytes = (int64_t)ws.bytes();
     return w;
 }
-
-bool sizes_ok(int64_t V, int64_t P, int64_t n) { return V >= 1 && V <= (1 << 20) && P >= 1 && P <= (1 << 28) && n >= 1 && n <= (1 << 28); }
 
 __device__ __forceinline__ bool header_ok(const BaWs& w, int V, int P, int n) {
     return w.header[0] == kBaMagic && w.header[1] == V && w.header[2] == P && w.header[3] == n;
@@ -205,29 +199,13 @@ extern "C" int ls2fm_bundle_adjust_prepare(const int32_t* view_start, int32_t n_
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t V = n_views, P = n_points, n = n_obs;
     const BaWs w = ba_layout(workspace, V, P, n);
-    // the index arrays are read back ONCE, here (loop construction, outside any iteration), checked, and the point -> observations
-    // CSR is built by a stable counting sort: point p's observations in list order
-    std::vector<int32_t> vs(V + 1), op(n), ps(P + 1, 0), po(n);
-    int32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyAsync(w.header, none, sizeof(none), hipMemcpyHostToDevice, stream) != hipSuccess ||       // not prepared until the end
-        hipMemcpyAsync(vs.data(), view_start, 4 * (V + 1), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(op.data(), obs_point, 4 * n, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
-        { (void)hipGetLastError(); return LS2FM_ERR_LAUNCH; }
-    LS2FM_CHECK_ARG(vs[0] == 0 && vs[V] == n);
-    for (int64_t v = 0; v < V; ++v) LS2FM_CHECK_ARG(vs[v + 1] > vs[v]);            // sorted by view, and no view without an observation
-    for (int64_t i = 0; i < n; ++i) LS2FM_CHECK_ARG(op[i] >= 0 && op[i] < P);
-    for (int64_t i = 0; i < n; ++i) ++ps[op[i] + 1];
-    for (int64_t p = 0; p < P; ++p) ps[p + 1] += ps[p];
-    {
-        std::vector<int32_t> cur(ps.begin(), ps.end() - 1);
-        for (int64_t i = 0; i < n; ++i) po[cur[op[i]]++] = (int32_t)i;
-    }
+    ba_index::Index ix;
+    if (!ba_index::clear_header(w.header, stream)) { (void)hipGetLastError(); return LS2FM_ERR_LAUNCH; }
+    const int st = ba_index::build(view_start, obs_point, V, P, n, stream, &ix);
+    if (st != LS2FM_OK) return st;
     const int32_t header[8] = {kBaMagic, (int32_t)V, (int32_t)P, (int32_t)n, 0, 0, 0, 0};
-    if (hipMemcpyAsync(w.view_start, vs.data(), 4 * (V + 1), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.obs_point, op.data(), 4 * n, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.point_start, ps.data(), 4 * (P + 1), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.point_obs, po.data(), 4 * n, hipMemcpyHostToDevice, stream) != hipSuccess ||
+    if (!ba_index::upload(w.view_start, ix.view_start, stream) || !ba_index::upload(w.obs_point, ix.obs_point, stream) ||
+        !ba_index::upload(w.point_start, ix.point_start, stream) || !ba_index::upload(w.point_obs, ix.point_obs, stream) ||
         hipMemcpyAsync(w.header, header, sizeof(header), hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess)                                  // (the host vectors die with this frame)
         { (void)hipGetLastError(); return LS2FM_ERR_LAUNCH; }

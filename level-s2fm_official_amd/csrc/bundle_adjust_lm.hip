@@ -7,7 +7,7 @@
 //                   the same words -- the caller's state, the candidate's cost partials in view order, the maxima --, workgroup 0
 //                   writes the log row and the iteration's record `it`); then r, w, J_c, J_p of every observation of the view at the
 //                   selected state (the candidate when it was accepted, else the current one) into the workspace, and U_v, g_v and
-//                   the view's cost by lm_math.h's fixed-order block sum.
+//                   the view's cost by wave_ops.h's fixed-order block sum.
 //   balm_points     one thread per point (+ V for the poses): commits the record to the caller's state, copies an accepted candidate
 //                   into the caller's poses / points, then V_p, g_p over the point's observations in CSR order, the damped 3 x 3
 //                   inverse by Cholesky and V_p*^-1 g_p.
@@ -23,14 +23,14 @@
 //   balm_cost       one workgroup per view: the candidate's cost partials.
 // After the last iteration of a call the decision runs once more on its own (balm_linearize on one workgroup + balm_points, both
 // told to stop after the decision), so the caller's poses, points and state are final when the call's launches end.
-#include <vector>
-
+#include "ba_index.h"
 #include "lm_math.h"
 #include "render_common.h"
+#include "workspace.h"
 
 namespace {
 
-using lm_math::block_sum;
+using ba_index::sizes_ok;
 using lm_math::pose_update;
 
 constexpr int kT = 256;                              // threads of every workgroup here
@@ -42,7 +42,7 @@ enum { kLambda = 0, kDone = 1, kIters = 2, kCost = 3, kReason = 4, kGmax = 5, kD
 // the summary words
 enum { sGmax = 0, sPmax = 1, sCost = 2, sDmaxC = 3, sFailed = 4 };
 
-struct Ws {                    // every array the kernels index through is the library's own validated copy
+struct Ws {                    // the index arrays: ba_index.h
     int32_t* header;           // [8]: magic, V, P, n
     double* it;                // [8]: the record of the running iteration (balm_linearize, workgroup 0)
     double* sum;               // [8]: balm_solve's summary
@@ -77,65 +77,47 @@ struct Ws {                    // every array the kernels index through is the l
 
 struct Prob { int V, P, n, nb, loss; double fx, fy, cx, cy, c2, lambda0, grad_tol, step_tol; };
 
-int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
 int64_t n_blocks(int64_t V, int64_t P) { return (P + V + kT - 1) / kT; }
 
 Ws layout(void* base, int64_t V, int64_t P, int64_t n) {
+    Workspace ws(base, 16);
     Ws w;
-    char* p = (char*)base;
-    int64_t at = 0;
     const int64_t nb = n_blocks(V, P), N = 6 * V;
-    auto take = [&](int64_t bytes) { char* q = p + at; at += align16(bytes); return q; };
-    w.header = (int32_t*)take(32);
-    w.it = (double*)take(64);
-    w.sum = (double*)take(64);
-    w.cost_part = (double*)take(8 * V);
-    w.gview = (double*)take(8 * V);
-    w.pview = (double*)take(8 * V);
-    w.cand_part = (double*)take(8 * V);
-    w.gblk = (double*)take(8 * nb);
-    w.fblk = (double*)take(8 * nb);
-    w.dblk = (double*)take(8 * nb);
-    w.U = (double*)take(8 * 21 * V);
-    w.g = (double*)take(8 * 6 * V);
-    w.Jc = (double*)take(8 * 12 * n);
-    w.Jp = (double*)take(8 * 6 * n);
-    w.rw = (double*)take(8 * 3 * n);
-    w.Vinv = (double*)take(8 * 6 * P);
-    w.Vg = (double*)take(8 * 3 * P);
-    w.gp = (double*)take(8 * 3 * P);
-    w.S = (double*)take(8 * N * N);
-    w.b = (double*)take(8 * N);
-    w.cand_poses = (double*)take(8 * 12 * V);
-    w.cand_points = (double*)take(8 * 3 * P);
-    w.view_start = (int32_t*)take(4 * (V + 1));
-    w.obs_point = (int32_t*)take(4 * n);
-    w.obs_view = (int32_t*)take(4 * n);
-    w.point_start = (int32_t*)take(4 * (P + 1));
-    w.point_obs = (int32_t*)take(4 * n);
-    w.view_const = (uint8_t*)take(V);
-    w.point_const = (uint8_t*)take(P);
-    w.bytes = at;
+    w.header = ws.take<int32_t>(8);
+    w.it = ws.take<double>(8);
+    w.sum = ws.take<double>(8);
+    w.cost_part = ws.take<double>(V);
+    w.gview = ws.take<double>(V);
+    w.pview = ws.take<double>(V);
+    w.cand_part = ws.take<double>(V);
+    w.gblk = ws.take<double>(nb);
+    w.fblk = ws.take<double>(nb);
+    w.dblk = ws.take<double>(nb);
+    w.U = ws.take<double>(21 * V);
+    w.g = ws.take<double>(6 * V);
+    w.Jc = ws.take<double>(12 * n);
+    w.Jp = ws.take<double>(6 * n);
+    w.rw = ws.take<double>(3 * n);
+    w.Vinv = ws.take<double>(6 * P);
+    w.Vg = ws.take<double>(3 * P);
+    w.gp = ws.take<double>(3 * P);
+    w.S = ws.take<double>(N * N);
+    w.b = ws.take<double>(N);
+    w.cand_poses = ws.take<double>(12 * V);
+    w.cand_points = ws.take<double>(3 * P);
+    w.view_start = ws.take<int32_t>(V + 1);
+    w.obs_point = ws.take<int32_t>(n);
+    w.obs_view = ws.take<int32_t>(n);
+    w.point_start = ws.take<int32_t>(P + 1);
+    w.point_obs = ws.take<int32_t>(n);
+    w.view_const = ws.take<uint8_t>(V);
+    w.point_const = ws.take<uint8_t>(P);
+    w.bytes = (int64_t)ws.bytes();
     return w;
 }
 
-bool sizes_ok(int64_t V, int64_t P, int64_t n) { return V >= 1 && V <= (1 << 20) && P >= 1 && P <= (1 << 28) && n >= 1 && n <= (1 << 28); }
-
 __device__ __forceinline__ bool header_ok(const Ws& w, const Prob& pb) {
     return w.header[0] == kMagic && w.header[1] == pb.V && w.header[2] == pb.P && w.header[3] == pb.n;
-}
-
-// max over the workgroup (order-free and exact); every thread receives it.  s_mx [kT / 64]
-__device__ __forceinline__ double block_max(double m, double* s_mx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = s_mx[0];
-#pragma unroll
-    for (int wv = 1; wv < kT / 64; ++wv) m = fmax(m, s_mx[wv]);
-    return m;
 }
 
 // one observation: camera point, residual, s = |r|^2 -> rho and the IRLS weight rho'(s)
@@ -274,7 +256,7 @@ balm_linearize(const double* __restrict__ poses, const double* __restrict__ poin
         a[27] += 0.5 * e.rho;
     }
     block_sum<28, kT>(a, s_red);
-    pm = block_max(pm, s_mx);
+    pm = block_max<kT>(pm, s_mx);
     if (tid == 0) {
 #pragma unroll
         for (int q = 0; q < 21; ++q) w.U[21 * v + q] = a[q];
@@ -362,8 +344,8 @@ balm_points(double* __restrict__ poses, double* __restrict__ points, Ws w, Prob 
 #pragma unroll
         for (int c = 0; c < 3; ++c) { w.Vg[3 * idx + c] = vg[c]; w.gp[3 * idx + c] = g[c]; }
     }
-    gm = block_max(gm, s_mx);
-    fail = block_max(fail, s_mx);
+    gm = block_max<kT>(gm, s_mx);
+    fail = block_max<kT>(fail, s_mx);
     if (threadIdx.x == 0) { w.gblk[blockIdx.x] = gm; w.fblk[blockIdx.x] = fail; }
 }
 
@@ -486,9 +468,9 @@ balm_solve(Ws w, Prob pb) {
     double gm = 0.0, pm = 0.0, fl = 0.0;
     for (int v = tid; v < V; v += kT) { gm = fmax(gm, w.gview[v]); pm = fmax(pm, w.pview[v]); }
     for (int k = tid; k < pb.nb; k += kT) { gm = fmax(gm, w.gblk[k]); fl = fmax(fl, w.fblk[k]); }
-    gm = block_max(gm, s_mx);
-    pm = block_max(pm, s_mx);
-    fl = block_max(fl, s_mx);
+    gm = block_max<kT>(gm, s_mx);
+    pm = block_max<kT>(pm, s_mx);
+    fl = block_max<kT>(fl, s_mx);
     if (tid == 0) {
         double c = 0.0;
         for (int v = 0; v < V; ++v) c += w.cost_part[v];
@@ -585,7 +567,7 @@ balm_solve(Ws w, Prob pb) {
     __syncthreads();
     double dm = 0.0;
     for (int q = tid; q < N; q += kT) { w.b[q] = s_z[q]; dm = fmax(dm, fabs(s_z[q])); }
-    dm = block_max(dm, s_mx);
+    dm = block_max<kT>(dm, s_mx);
     if (tid == 0) { w.sum[sDmaxC] = dm; w.sum[sFailed] = s_fail ? 1.0 : 0.0; }
 }
 
@@ -635,7 +617,7 @@ balm_backsub(const double* __restrict__ poses, const double* __restrict__ points
 #pragma unroll
         for (int q = 0; q < 12; ++q) w.cand_poses[12 * v + q] = C[q];
     }
-    dm = block_max(dm, s_mx);
+    dm = block_max<kT>(dm, s_mx);
     if (threadIdx.x == 0) w.dblk[blockIdx.x] = dm;
 }
 
@@ -679,42 +661,25 @@ extern "C" int ls2fm_bundle_adjust_lm_prepare(const int32_t* view_start, int32_t
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t V = n_views, P = n_points, n = n_obs;
     const Ws w = layout(workspace, V, P, n);
-    // the index arrays are read back ONCE, here, checked, and the point -> observations CSR is built by a stable counting sort:
-    // point p's observations in list order, which is rising view position
-    std::vector<int32_t> vs(V + 1), op(n), ov(n), ps(P + 1, 0), po(n);
+    // view_constant comes back with the index arrays, under ba_index::build's one synchronisation
+    ba_index::Index ix;
     std::vector<uint8_t> vc(V), pc(P);
-    int32_t none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyAsync(w.header, none, sizeof(none), hipMemcpyHostToDevice, stream) != hipSuccess ||       // not prepared until the end
-        hipMemcpyAsync(vs.data(), view_start, 4 * (V + 1), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(op.data(), obs_point, 4 * n, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(vc.data(), view_constant, V, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
+    if (!ba_index::clear_header(w.header, stream) ||
+        hipMemcpyAsync(vc.data(), view_constant, V, hipMemcpyDeviceToHost, stream) != hipSuccess)
         { (void)hipGetLastError(); return LS2FM_ERR_LAUNCH; }
-    LS2FM_CHECK_ARG(vs[0] == 0 && vs[V] == n);
-    for (int64_t v = 0; v < V; ++v) LS2FM_CHECK_ARG(vs[v + 1] > vs[v]);            // sorted by view, and no view without an observation
-    for (int64_t i = 0; i < n; ++i) LS2FM_CHECK_ARG(op[i] >= 0 && op[i] < P);
-    for (int64_t v = 0; v < V; ++v) {
-        vc[v] = vc[v] ? 1 : 0;
-        for (int64_t i = vs[v]; i < vs[v + 1]; ++i) ov[i] = (int32_t)v;
-    }
-    for (int64_t i = 0; i < n; ++i) ++ps[op[i] + 1];
-    for (int64_t p = 0; p < P; ++p) ps[p + 1] += ps[p];
-    {
-        std::vector<int32_t> cur(ps.begin(), ps.end() - 1);
-        for (int64_t i = 0; i < n; ++i) po[cur[op[i]]++] = (int32_t)i;
-    }
+    const int st = ba_index::build(view_start, obs_point, V, P, n, stream, &ix);
+    if (st != LS2FM_OK) return st;
+    for (int64_t v = 0; v < V; ++v) vc[v] = vc[v] ? 1 : 0;
+    const std::vector<int32_t>&ov = ix.obs_view, &ps = ix.point_start, &po = ix.point_obs;
     for (int64_t p = 0; p < P; ++p) {
         for (int64_t k = ps[p] + 1; k < ps[p + 1]; ++k) LS2FM_CHECK_ARG(ov[po[k]] != ov[po[k - 1]]);       // seen twice by one view
         pc[p] = ps[p + 1] - ps[p] < min_point_views ? 1 : 0;
     }
     const int32_t header[8] = {kMagic, (int32_t)V, (int32_t)P, (int32_t)n, 0, 0, 0, 0};
-    if (hipMemcpyAsync(w.view_start, vs.data(), 4 * (V + 1), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.obs_point, op.data(), 4 * n, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.obs_view, ov.data(), 4 * n, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.point_start, ps.data(), 4 * (P + 1), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.point_obs, po.data(), 4 * n, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.view_const, vc.data(), V, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(w.point_const, pc.data(), P, hipMemcpyHostToDevice, stream) != hipSuccess ||
+    if (!ba_index::upload(w.view_start, ix.view_start, stream) || !ba_index::upload(w.obs_point, ix.obs_point, stream) ||
+        !ba_index::upload(w.obs_view, ix.obs_view, stream) || !ba_index::upload(w.point_start, ix.point_start, stream) ||
+        !ba_index::upload(w.point_obs, ix.point_obs, stream) || !ba_index::upload(w.view_const, vc, stream) ||
+        !ba_index::upload(w.point_const, pc, stream) ||
         hipMemcpyAsync(w.header, header, sizeof(header), hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess)                                  // (the host vectors die with this frame)
         { (void)hipGetLastError(); return LS2FM_ERR_LAUNCH; }

@@ -1,41 +1,14 @@
 // The fp64 pieces of a Levenberg-Marquardt step that absolute_pose.hip (one pose), two_view.h and bundle_adjust_lm.hip (poses and
-// points) share: the fixed-order workgroup sum, the damped 6 x 6 Cholesky solve and the pose update.  Every routine is a fixed
-// sequence of fp64 operations (the library is built with -ffp-contract=off): the same bits in whichever file includes it.
+// points) share: the damped 6 x 6 Cholesky solve and the pose update; the fixed-order workgroup sum they go with (block_sum) is
+// wave_ops.h's, included here.  Every routine is a fixed sequence of fp64 operations (the library is built with
+// -ffp-contract=off): the same bits in whichever file includes it.
 #pragma once
-
-#include <hip/hip_runtime.h>
 
 #include <cmath>
 
-namespace lm_math {
+#include "wave_ops.h"
 
-// ---------------------------------------------------------------------------------------------------- workgroup reductions
-// fixed-order sum of a[N] over a workgroup of Threads: xor-shuffles inside each wave, then the waves in index order through
-// s_red [Threads / 64][N]; every thread receives the sums.  s_red is read last: a barrier before it is written again (the next
-// block_sum has its own)
-template <int N, int Threads>
-__device__ __forceinline__ void block_sum(double (&a)[N], double* s_red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double t = a[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        a[q] = t;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int q = 0; q < N; ++q) s_red[(tid >> 6) * N + q] = a[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double t = s_red[q];
-#pragma unroll
-        for (int wv = 1; wv < Threads / 64; ++wv) t += s_red[wv * N + q];
-        a[q] = t;
-    }
-}
+namespace lm_math {
 
 // solve (H + lam diag(dg)) x = -g by Cholesky; a: the 21-entry upper triangle of H (row-major), then g at a[21 .. 26]
 template <int N>

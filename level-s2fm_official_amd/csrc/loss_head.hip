@@ -76,9 +76,7 @@ loss_head_fwd_kernel(LossIn in, const float* __restrict__ weights, double* __res
     }
 #pragma unroll
     for (int k = 0; k < kSums; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const double v = wave_sum(s[k]);
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();
@@ -184,9 +182,7 @@ post_shade_kernel(ls2fm_loss_spec loss, const float* __restrict__ lpart, int64_t
     }
 #pragma unroll
     for (int k = 0; k < kSums; ++k) {
-        double v = s[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const double v = wave_sum(s[k]);
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();

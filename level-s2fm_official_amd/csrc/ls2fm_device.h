@@ -9,6 +9,7 @@
 #include <stdio.h>
 
 #include "../../include/ls2fm.h"
+#include "wave_ops.h"
 
 #define LS2FM_PRIME_Y 2654435761u
 #define LS2FM_PRIME_Z 805459861u
@@ -173,33 +174,4 @@ __device__ __forceinline__ void ray_box(const float o[3], const float d[3], cons
     hit = t2 > 0.0f;
     t_near = hit ? fmaxf(t1, 0.0f) : -1.0f;
     t_far = hit ? t2 : -1.0f;
-}
-
-// wave64 helpers -------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// inclusive prefix sum across the 64 lanes
-__device__ __forceinline__ float wave_scan_incl(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// exclusive suffix sum across the 64 lanes: sum of v over the lanes above this one
-__device__ __forceinline__ float wave_suffix_excl(float v, int lane) {
-    float s = __shfl_down(v, 1, 64);
-    if (lane == 63) s = 0.f;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_down(s, o, 64);
-        if (lane + o < 64) s += t;
-    }
-    return s;
 }

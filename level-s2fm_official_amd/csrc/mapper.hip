@@ -25,6 +25,7 @@
 //              workgroups.
 //   uo_final   one lane per track: tri_angle and track_valid.
 #include "track_geom.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -44,8 +45,6 @@ constexpr int kGrid = 64;                      // cells per side of the finest l
 constexpr int kLevels = 6;
 
 static_assert(kGrid == 64 && (1 << kLevels) == kGrid, "a view's mask is 64 rows of 64 bits, one row per lane of a wave");
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 bool below_2_31(int64_t x) { return x >= 0 && x < ((int64_t)1 << 31); }
 
@@ -69,14 +68,13 @@ struct VsWs {
 };
 
 size_t vs_layout(int64_t T, int32_t V, int64_t n_obs, char* base, VsWs* w, size_t* zeroed) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* m = take((size_t)V * kGrid * sizeof(unsigned long long));
-    char* s = take((size_t)(T ? T : 1));
-    if (zeroed) *zeroed = off;                                  // mask and seen start at zero
-    char* t = take((size_t)(n_obs ? n_obs : 1) * sizeof(int32_t));
-    if (w) *w = {(unsigned long long*)m, (uint8_t*)s, (int32_t*)t};
-    return off;
+    Workspace ws(base, 256);
+    unsigned long long* m = ws.take<unsigned long long>((size_t)V * kGrid);
+    uint8_t* s = ws.take<uint8_t>((size_t)(T ? T : 1));
+    if (zeroed) *zeroed = ws.bytes();                           // mask and seen start at zero
+    int32_t* t = ws.take<int32_t>((size_t)(n_obs ? n_obs : 1));
+    if (w) *w = {m, s, t};
+    return ws.bytes();
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -144,8 +142,7 @@ vs_reduce(VsWs w, const uint8_t* __restrict__ registered, int32_t V, int64_t* __
         const int cells = (lane & ((1 << s) - 1)) == 0 ? __popcll(m & corner[s]) : 0;
         sum += (long long)cells << (2 * (kLevels - s));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_sum(sum);
     if (lane == 0) score[v] = registered[v] ? 0ll : sum;
 }
 
@@ -172,14 +169,13 @@ struct UoWs {
 };
 
 size_t uo_layout(int64_t T, int32_t V, int64_t n_obs, char* base, UoWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* c = take((size_t)V * 3 * sizeof(double));
-    char* h = take(((size_t)T + 1) * sizeof(long long));
-    char* k = take((size_t)(T ? T : 1) * sizeof(unsigned long long));
-    char* kv = take((size_t)(n_obs ? n_obs : 1) * sizeof(int32_t));
-    if (w) *w = {(double*)c, (long long*)h, (unsigned long long*)k, (int32_t*)kv};
-    return off;
+    Workspace ws(base, 256);
+    double* c = ws.take<double>((size_t)V * 3);
+    long long* h = ws.take<long long>((size_t)T + 1);
+    unsigned long long* k = ws.take<unsigned long long>((size_t)(T ? T : 1));
+    int32_t* kv = ws.take<int32_t>((size_t)(n_obs ? n_obs : 1));
+    if (w) *w = {c, h, k, kv};
+    return ws.bytes();
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -209,12 +205,7 @@ uo_rank(UoIn in, UoWs w, const uint8_t* __restrict__ obs_keep, int32_t* __restri
     int64_t s0 = 0;
     int n = 0;
     if (have && !track_extent(in.track_start, in.n_obs, t, s0, n) && status && sub == 0) atomicOr(status, LS2FM_MAPPER_BAD_START);
-    int rounds = (n + kSub - 1) / kSub;                         // as many as the longest track of the wave needs
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int y = __shfl_xor(rounds, o, 64);
-        rounds = y > rounds ? y : rounds;
-    }
+    const int rounds = wave_max((n + kSub - 1) / kSub);         // as many as the longest track of the wave needs
     int seen = 0;
     for (int r = 0; r < rounds; ++r) {
         const int k = r * kSub + sub;
@@ -230,7 +221,6 @@ uo_rank(UoIn in, UoWs w, const uint8_t* __restrict__ obs_keep, int32_t* __restri
 
 __global__ void __launch_bounds__(kScanThreads)
 uo_scan(int64_t T, const int32_t* __restrict__ num_kept, UoWs w) {
-    __shared__ long long s_wave[kScanThreads / 64];
     const int tid = threadIdx.x;
     long long carry = 0;
     for (int64_t base = 0; base < T; base += kScanThreads) {
@@ -241,7 +231,7 @@ uo_scan(int64_t T, const int32_t* __restrict__ num_kept, UoWs w) {
             w.best[t] = 0ull;
         }
         long long sum;
-        const long long e = block_exclusive_scan<kScanThreads>(c, sum, s_wave);
+        const long long e = block_exclusive_scan<kScanThreads>(c, sum);
         if (t < T) w.pair_start[t] = carry + e;
         carry += sum;
     }

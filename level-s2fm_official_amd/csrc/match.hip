@@ -19,6 +19,7 @@
 // tile: by the instruction count the vector pipe is the longer of the two, a column reduction from the same tile costs the same three instructions per
 // product, and it would add a cross-workgroup merge of column partials; two sweeps share one code path and stay free of atomics.
 #include "ls2fm_device.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <cmath>
@@ -65,22 +66,17 @@ struct Ws {
     uint4* part;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t ws_layout(const Plan& p, int32_t n_pairs, char* base, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += align_up(bytes); return q; };
-    char* jobs = take(sizeof(Job) * (2 * (size_t)n_pairs + 1));
-    char* first = take(sizeof(int32_t) * ((size_t)n_pairs + 1));
-    char* bias = take(sizeof(int32_t) * (size_t)p.n_desc);
-    char* dbias = take((size_t)128 * (size_t)p.n_desc);
-    char* prop = take(sizeof(int32_t) * (size_t)p.n_rows);
-    char* part = take(sizeof(uint4) * (size_t)p.n_parts);
-    if (w) {
-        w->jobs = (Job*)jobs; w->first_start = (int32_t*)first; w->bias128 = (int32_t*)bias; w->dbias = (uint8_t*)dbias;
-        w->proposal = (int32_t*)prop; w->part = (uint4*)part;
-    }
-    return off;
+    Workspace ws(base, 256);
+    Ws t;
+    t.jobs = ws.take<Job>(2 * (size_t)n_pairs + 1);
+    t.first_start = ws.take<int32_t>((size_t)n_pairs + 1);
+    t.bias128 = ws.take<int32_t>((size_t)p.n_desc);
+    t.dbias = ws.take<uint8_t>((size_t)128 * (size_t)p.n_desc);
+    t.proposal = ws.take<int32_t>((size_t)p.n_rows);
+    t.part = ws.take<uint4>((size_t)p.n_parts);
+    if (w) *w = t;
+    return ws.bytes();
 }
 
 // host-side plan of a call; every size comes from image_start and pairs (host arrays)

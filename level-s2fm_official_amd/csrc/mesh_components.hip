@@ -25,6 +25,7 @@
 //   lc_emit_faces   kept faces in order, renumbered
 #include "ls2fm_device.h"
 #include "union_find.h"
+#include "workspace.h"
 
 namespace {
 
@@ -102,32 +103,6 @@ __device__ __forceinline__ int fixed_shift(const LcSlots* slots, uint32_t n_face
     int e = 0;
     frexp(amax, &e);                                         // amax < 2^e (e = 0 for amax = 0)
     return 63 - (32 - __clz(n_faces)) - e;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_max(T x) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        const T y = __shfl_xor(x, o, 64);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_min(T x) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        const T y = __shfl_xor(x, o, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -224,31 +199,6 @@ lc_select_face(const int32_t* __restrict__ labels, uint32_t n_verts, const unsig
     f = wave_min(f);
     if ((threadIdx.x & 63) == 0 && f != kNoFace)
         __hip_atomic_fetch_min(&slots->win_face, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Exclusive scan over the NT threads of the workgroup (wave64 shuffles, then the wave totals through LDS); `total` = the sum.
-template <int NT, typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T& total) {
-    __shared__ T wave_sum_lds[NT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const T y = __shfl_up(x, s, 64);
-        if (lane >= s) x += y;
-    }
-    if (lane == 63) wave_sum_lds[wave] = x;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const T s = wave_sum_lds[w];
-        before += w < wave ? s : T(0);
-        all += s;
-    }
-    __syncthreads();                                   // wave_sum_lds may be written again by the next scan
-    total = all;
-    return before + x - v;
 }
 
 __device__ __forceinline__ int32_t winner_label(const int32_t* __restrict__ faces, const int32_t* __restrict__ labels,
@@ -362,31 +312,31 @@ bool sizes_ok(int64_t n_verts, int64_t n_faces) {
 
 struct LcLayout {
     uint32_t nv, nf, tiles_v, tiles_f;
-    int64_t labels, comp_q, comp_first, new_id, tile_f, tile_v, off_f, off_v, slots, bytes;
+    int32_t* labels;
+    unsigned long long* comp_q;
+    int32_t *comp_first, *new_id;
+    uint32_t *tile_f, *tile_v, *off_f, *off_v;
+    LcSlots* slots;
+    int64_t bytes;
 };
 
-int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-void lc_layout(int64_t n_verts, int64_t n_faces, LcLayout& L) {
+void lc_layout(int64_t n_verts, int64_t n_faces, void* base, LcLayout& L) {
     L.nv = (uint32_t)n_verts;
     L.nf = (uint32_t)n_faces;
     L.tiles_v = (uint32_t)((n_verts + kTile - 1) / kTile);
     L.tiles_f = (uint32_t)((n_faces + kTile - 1) / kTile);
-    int64_t at = 0;
-    L.labels = at;     at += align256(4 * n_verts);
-    L.comp_q = at;     at += align256(8 * n_verts);
-    L.comp_first = at; at += align256(4 * n_verts);
-    L.new_id = at;     at += align256(4 * n_verts);
-    L.tile_f = at;     at += align256(4 * (int64_t)L.tiles_f);
-    L.tile_v = at;     at += align256(4 * (int64_t)L.tiles_v);
-    L.off_f = at;      at += align256(4 * (int64_t)L.tiles_f);
-    L.off_v = at;      at += align256(4 * (int64_t)L.tiles_v);
-    L.slots = at;      at += align256((int64_t)sizeof(LcSlots));
-    L.bytes = at;
+    Workspace ws(base, 256);
+    L.labels = ws.take<int32_t>(n_verts);
+    L.comp_q = ws.take<unsigned long long>(n_verts);
+    L.comp_first = ws.take<int32_t>(n_verts);
+    L.new_id = ws.take<int32_t>(n_verts);
+    L.tile_f = ws.take<uint32_t>(L.tiles_f);
+    L.tile_v = ws.take<uint32_t>(L.tiles_v);
+    L.off_f = ws.take<uint32_t>(L.tiles_f);
+    L.off_v = ws.take<uint32_t>(L.tiles_v);
+    L.slots = ws.take<LcSlots>(1);
+    L.bytes = (int64_t)ws.bytes();
 }
-
-template <typename T>
-T* at_offset(void* ws, int64_t off) { return (T*)((char*)ws + off); }
 
 uint32_t blocks_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 
@@ -395,7 +345,7 @@ uint32_t blocks_of(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 extern "C" int64_t ls2fm_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces) {
     if (!sizes_ok(n_verts, n_faces)) return (int64_t)LS2FM_ERR_INVALID_ARGUMENT;
     LcLayout L;
-    lc_layout(n_verts, n_faces, L);
+    lc_layout(n_verts, n_faces, nullptr, L);
     return L.bytes;
 }
 
@@ -418,27 +368,18 @@ extern "C" int ls2fm_mesh_largest_component_count(const float* verts, int64_t n_
     LS2FM_CHECK_ARG(sizes_ok(n_verts, n_faces) && ((verts && faces && counts) || n_faces == 0));
     if (n_faces == 0) return LS2FM_OK;
     LcLayout L;
-    lc_layout(n_verts, n_faces, L);
+    lc_layout(n_verts, n_faces, workspace, L);
     if (!workspace || workspace_bytes < L.bytes) return LS2FM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    int32_t* labels = at_offset<int32_t>(workspace, L.labels);
-    unsigned long long* comp_q = at_offset<unsigned long long>(workspace, L.comp_q);
-    int32_t* comp_first = at_offset<int32_t>(workspace, L.comp_first);
-    LcSlots* slots = at_offset<LcSlots>(workspace, L.slots);
-    const uint32_t face_tiles = L.tiles_f;
-    cc_init<<<blocks_of(L.nv), kThreads, 0, s>>>(labels, L.nv, comp_q, comp_first, slots);
-    cc_hook<<<blocks_of(L.nf), kThreads, 0, s>>>(faces, L.nf, labels);
-    cc_flatten<<<blocks_of(L.nv), kThreads, 0, s>>>(labels, L.nv);
-    lc_max_area<<<face_tiles, kThreads, 0, s>>>(verts, faces, L.nf, slots);
-    lc_accumulate<<<face_tiles, kThreads, 0, s>>>(verts, faces, L.nf, labels, slots, comp_q, comp_first);
-    lc_select_max<<<blocks_of(L.nv), kThreads, 0, s>>>(labels, L.nv, L.nf, comp_q, slots, areas);
-    lc_select_face<<<blocks_of(L.nv), kThreads, 0, s>>>(labels, L.nv, comp_q, comp_first, slots);
-    lc_count<<<L.tiles_f + L.tiles_v, kThreads, 0, s>>>(faces, L.nf, labels, L.nv, slots, L.tiles_f,
-                                                        at_offset<uint32_t>(workspace, L.tile_f),
-                                                        at_offset<uint32_t>(workspace, L.tile_v));
-    lc_scan<<<1, kScanThreads, 0, s>>>(at_offset<uint32_t>(workspace, L.tile_f), L.tiles_f, at_offset<uint32_t>(workspace, L.tile_v),
-                                       L.tiles_v, at_offset<uint32_t>(workspace, L.off_f), at_offset<uint32_t>(workspace, L.off_v),
-                                       counts);
+    cc_init<<<blocks_of(L.nv), kThreads, 0, s>>>(L.labels, L.nv, L.comp_q, L.comp_first, L.slots);
+    cc_hook<<<blocks_of(L.nf), kThreads, 0, s>>>(faces, L.nf, L.labels);
+    cc_flatten<<<blocks_of(L.nv), kThreads, 0, s>>>(L.labels, L.nv);
+    lc_max_area<<<L.tiles_f, kThreads, 0, s>>>(verts, faces, L.nf, L.slots);
+    lc_accumulate<<<L.tiles_f, kThreads, 0, s>>>(verts, faces, L.nf, L.labels, L.slots, L.comp_q, L.comp_first);
+    lc_select_max<<<blocks_of(L.nv), kThreads, 0, s>>>(L.labels, L.nv, L.nf, L.comp_q, L.slots, areas);
+    lc_select_face<<<blocks_of(L.nv), kThreads, 0, s>>>(L.labels, L.nv, L.comp_q, L.comp_first, L.slots);
+    lc_count<<<L.tiles_f + L.tiles_v, kThreads, 0, s>>>(faces, L.nf, L.labels, L.nv, L.slots, L.tiles_f, L.tile_f, L.tile_v);
+    lc_scan<<<1, kScanThreads, 0, s>>>(L.tile_f, L.tiles_f, L.tile_v, L.tiles_v, L.off_f, L.off_v, counts);
     return ls2fm_launch_status();
 }
 
@@ -448,15 +389,10 @@ extern "C" int ls2fm_mesh_largest_component_emit(const float* verts, int64_t n_v
     LS2FM_CHECK_ARG(sizes_ok(n_verts, n_faces) && ((verts && faces && out_verts && out_faces) || n_faces == 0));
     if (n_faces == 0) return LS2FM_OK;
     LcLayout L;
-    lc_layout(n_verts, n_faces, L);
+    lc_layout(n_verts, n_faces, workspace, L);
     if (!workspace || workspace_bytes < L.bytes) return LS2FM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int32_t* labels = at_offset<int32_t>(workspace, L.labels);
-    const LcSlots* slots = at_offset<LcSlots>(workspace, L.slots);
-    int32_t* new_id = at_offset<int32_t>(workspace, L.new_id);
-    lc_emit_verts<<<L.tiles_v, kThreads, 0, s>>>(verts, L.nv, faces, labels, slots, at_offset<uint32_t>(workspace, L.off_v), new_id,
-                                                 out_verts);
-    lc_emit_faces<<<L.tiles_f, kThreads, 0, s>>>(faces, L.nf, labels, slots, at_offset<uint32_t>(workspace, L.off_f), new_id,
-                                                 out_faces);
+    lc_emit_verts<<<L.tiles_v, kThreads, 0, s>>>(verts, L.nv, faces, L.labels, L.slots, L.off_v, L.new_id, out_verts);
+    lc_emit_faces<<<L.tiles_f, kThreads, 0, s>>>(faces, L.nf, L.labels, L.slots, L.off_f, L.new_id, out_faces);
     return ls2fm_launch_status();
 }

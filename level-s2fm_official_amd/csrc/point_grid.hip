@@ -15,6 +15,7 @@
 //                 The order inside a cell is the order the atomics arrived in; it cannot show, ties break on the stored index.
 // ls2fm_point_grid_query (one launch): pg_query, one query per lane -- its own cell, then Chebyshev rings 1, 2, ... (ring_bound).
 #include "ls2fm_device.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <climits>
@@ -62,53 +63,24 @@ pg_count(PgGrid g, const float* __restrict__ ref, int64_t n, int32_t* cursor) {
     atomicAdd(cursor + cell_of(g, ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), 1);
 }
 
-__device__ __forceinline__ int wave_scan_incl_i32(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// exclusive prefix sum of one value per thread over the kScanThreads threads of a workgroup; total: the sum over all of them
-__device__ __forceinline__ int block_scan_excl(int v, int tid, int* s_wave, int& total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int incl = wave_scan_incl_i32(v, lane);
-    __syncthreads();                                   // s_wave may still be read from the previous round
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const int t = s_wave[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    total = sum;
-    return before + incl - v;
-}
-
 __global__ void __launch_bounds__(kScanThreads)
 pg_scan_local(const int32_t* __restrict__ count, int64_t n_cells, int32_t* __restrict__ cell_start, int32_t* __restrict__ block_sum) {
-    __shared__ int s_wave[kScanThreads / 64];
     const int tid = threadIdx.x;
     const int64_t c = (int64_t)blockIdx.x * kScanThreads + tid;
     int total;
-    const int excl = block_scan_excl(c < n_cells ? count[c] : 0, tid, s_wave, total);
+    const int excl = block_exclusive_scan<kScanThreads>(c < n_cells ? count[c] : 0, total);
     if (c < n_cells) cell_start[c] = excl;
     if (tid == 0) block_sum[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(kScanThreads)
 pg_scan_sums(int32_t* block_sum, int64_t n_blocks, int32_t* __restrict__ cell_start_end) {
-    __shared__ int s_wave[kScanThreads / 64];
     const int tid = threadIdx.x;
     int carry = 0;
     for (int64_t base = 0; base < n_blocks; base += kScanThreads) {
         const int64_t b = base + tid;
         int total;
-        const int excl = block_scan_excl(b < n_blocks ? block_sum[b] : 0, tid, s_wave, total);
+        const int excl = block_exclusive_scan<kScanThreads>(b < n_blocks ? block_sum[b] : 0, total);
         if (b < n_blocks) block_sum[b] = carry + excl;
         carry += total;
     }
@@ -198,8 +170,6 @@ pg_query(PgGrid g, const float4* __restrict__ sorted, const int32_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 bool grid_ok(const float* origin, float h, float inv_h, const int32_t* dim, int64_t* n_cells) {
     if (!origin || !dim || !(h > 0.0f) || !std::isfinite(h) || !(inv_h > 0.0f) || !std::isfinite(inv_h)) return false;
     int64_t cells = 1;
@@ -219,12 +189,25 @@ PgGrid make_grid(const float* origin, float h, float inv_h, const int32_t* dim) 
 
 int64_t scan_blocks(int64_t n_cells) { return (n_cells + kScanThreads - 1) / kScanThreads; }
 
+struct PgWs {
+    int32_t* cursor;           // [n_cells]
+    int32_t* block_sum;        // [scan_blocks(n_cells)]
+};
+
+size_t pg_layout(int64_t n_cells, void* base, PgWs* w) {
+    Workspace ws(base, 256);
+    int32_t* cursor = ws.take<int32_t>((size_t)n_cells);
+    int32_t* block_sum = ws.take<int32_t>((size_t)scan_blocks(n_cells));
+    if (w) *w = {cursor, block_sum};
+    return ws.bytes();
+}
+
 }  // namespace
 
 extern "C" int64_t ls2fm_point_grid_workspace_bytes(int64_t n_points, int64_t n_cells) {
     if (n_points < 0 || n_points >= ((int64_t)1 << 31) || n_cells < 1 || n_cells >= ((int64_t)1 << 31) - 1)
         return (int64_t)LS2FM_ERR_INVALID_ARGUMENT;
-    return (int64_t)(align256((size_t)n_cells * sizeof(int32_t)) + align256((size_t)scan_blocks(n_cells) * sizeof(int32_t)));
+    return (int64_t)pg_layout(n_cells, nullptr, nullptr);
 }
 
 extern "C" int ls2fm_point_grid_build(const float* ref, int64_t n_points, const float* origin, float cell_size, float inv_cell_size,
@@ -239,16 +222,16 @@ extern "C" int ls2fm_point_grid_build(const float* ref, int64_t n_points, const 
         return LS2FM_OK;
     }
     const PgGrid g = make_grid(origin, cell_size, inv_cell_size, dim);
-    int32_t* cursor = (int32_t*)workspace;
-    int32_t* block_sum = (int32_t*)((char*)workspace + align256((size_t)n_cells * sizeof(int32_t)));
+    PgWs w;
+    pg_layout(n_cells, workspace, &w);
     const int64_t n_blocks = scan_blocks(n_cells);
     const unsigned point_blocks = (unsigned)((n_points + kThreads - 1) / kThreads);
-    if (hipMemsetAsync(cursor, 0, (size_t)n_cells * sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
-    pg_count<<<point_blocks, kThreads, 0, s>>>(g, ref, n_points, cursor);
-    pg_scan_local<<<(unsigned)n_blocks, kScanThreads, 0, s>>>(cursor, n_cells, cell_start, block_sum);
-    pg_scan_sums<<<1, kScanThreads, 0, s>>>(block_sum, n_blocks, cell_start + n_cells);
-    pg_scan_add<<<(unsigned)n_blocks, kScanThreads, 0, s>>>(cell_start, n_cells, block_sum, cursor);
-    pg_scatter<<<point_blocks, kThreads, 0, s>>>(g, ref, n_points, cell_start, cursor, (float4*)sorted);
+    if (hipMemsetAsync(w.cursor, 0, (size_t)n_cells * sizeof(int32_t), s) != hipSuccess) return ls2fm_launch_status();
+    pg_count<<<point_blocks, kThreads, 0, s>>>(g, ref, n_points, w.cursor);
+    pg_scan_local<<<(unsigned)n_blocks, kScanThreads, 0, s>>>(w.cursor, n_cells, cell_start, w.block_sum);
+    pg_scan_sums<<<1, kScanThreads, 0, s>>>(w.block_sum, n_blocks, cell_start + n_cells);
+    pg_scan_add<<<(unsigned)n_blocks, kScanThreads, 0, s>>>(cell_start, n_cells, w.block_sum, w.cursor);
+    pg_scatter<<<point_blocks, kThreads, 0, s>>>(g, ref, n_points, cell_start, w.cursor, (float4*)sorted);
     return ls2fm_launch_status();
 }
 

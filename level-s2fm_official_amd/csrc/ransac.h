@@ -27,6 +27,7 @@
 
 #include "ls2fm_device.h"
 #include "lm_math.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <cmath>
@@ -105,24 +106,21 @@ struct Ws {                     // workspace layout (ls2fm_*_pose_workspace_byte
     int32_t* tile_off;          // [G + 1]   first scoring tile of group g (ceil(n_g / kScoreTile) tiles each)
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <class M>
 inline size_t ws_layout(int32_t G, char* base, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* hyp = take((size_t)G * kRound * M::kMaxSol * M::kHypWords * sizeof(double));
-    char* valid = take((size_t)G * kRound * sizeof(int32_t));
-    char* counts = take((size_t)G * kRound * M::kMaxSol * sizeof(int32_t));
-    char* bk = take((size_t)G * sizeof(unsigned long long));
-    char* be = take((size_t)G * M::kHypWords * sizeof(double));
-    char* tr = take((size_t)G * sizeof(int32_t));
-    char* ac = take((size_t)G * sizeof(int32_t));
-    char* na = take(sizeof(int32_t));
-    char* to = take(((size_t)G + 1) * sizeof(int32_t));
-    if (w) *w = {(double*)hyp, (int32_t*)valid, (int32_t*)counts, (unsigned long long*)bk, (double*)be, (int32_t*)tr, (int32_t*)ac,
-                 (int32_t*)na, (int32_t*)to};
-    return off;
+    Workspace ws(base, 256);
+    Ws t;
+    t.hyp = ws.take<double>((size_t)G * kRound * M::kMaxSol * M::kHypWords);
+    t.valid = ws.take<int32_t>((size_t)G * kRound);
+    t.counts = ws.take<int32_t>((size_t)G * kRound * M::kMaxSol);
+    t.best_key = ws.take<unsigned long long>((size_t)G);
+    t.best = ws.take<double>((size_t)G * M::kHypWords);
+    t.trials = ws.take<int32_t>((size_t)G);
+    t.active = ws.take<int32_t>((size_t)G);
+    t.n_active = ws.take<int32_t>(1);
+    t.tile_off = ws.take<int32_t>((size_t)G + 1);
+    if (w) *w = t;
+    return ws.bytes();
 }
 
 // --------------------------------------------------------------------------------------------------------------- kernels
@@ -212,15 +210,6 @@ score_kernel(typename M::Input in, const int32_t* __restrict__ gs, int32_t G, Ws
     if (tid < kH && s_cnt[tid]) atomicAdd(&w.counts[kS * slot0 + tid], s_cnt[tid]);
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(k, o, 64);
-        k = t > k ? t : k;
-    }
-    return k;
-}
-
 template <class M>
 __global__ void __launch_bounds__(kGroupThreads)
 select_kernel(const int32_t* __restrict__ gs, double confidence, int64_t min_trials, int64_t max_trials, Ws w) {
@@ -241,7 +230,7 @@ select_kernel(const int32_t* __restrict__ gs, double confidence, int64_t min_tri
             best = key > best ? key : best;
         }
     }
-    best = wave_max_u64(best);
+    best = wave_max(best);
     if ((tid & 63) == 0) s_k[tid >> 6] = best;
     __syncthreads();
     if (tid != 0) return;
@@ -267,8 +256,7 @@ __device__ __forceinline__ int32_t best_trial_of(unsigned long long best_key) {
 }
 
 // ---------------------------------------------------------------------------------------------------- workgroup reductions
-using lm_math::block_sum;               // the fixed-order sum over a workgroup (lm_math.h)
-
+// (the fixed-order fp64 sum over a workgroup is wave_ops.h's block_sum)
 __device__ __forceinline__ int block_count(int c, int* s_int) {     // exact integer sum over the workgroup
     __syncthreads();
     if (threadIdx.x == 0) *s_int = 0;

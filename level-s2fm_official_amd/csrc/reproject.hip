@@ -146,15 +146,14 @@ namespace {
 
 constexpr int kTtThreads = 1024;
 
-__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int q = 0; q < kTtThreads / 64; ++q) t += red[q];
-    return t;
+// wave_ops.h's fixed-order block_sum of one value.  It sums the wave totals from the first total on, which gives the bits of a
+// sum that starts from 0.0 (as these terms were first written and recorded): 0.0 + x differs from x only for x = -0.0, and no
+// total here is -0.0 -- the accumulator of every lane of the three kernels that call this starts at +0.0, and a round-to-nearest
+// sum that starts at +0.0 is never -0.0, nor is a sum of such sums.
+__device__ __forceinline__ double block_total(double v, double* red) {
+    double a[1] = {v};
+    block_sum<1, kTtThreads>(a, red);
+    return a[0];
 }
 
 __global__ void __launch_bounds__(kTtThreads)
@@ -176,7 +175,7 @@ tracing_term_fwd_kernel(const float* __restrict__ center, const float* __restric
         s_tr += (double)(sqrtf(q) * lv);
         if (sdf_last) s_sd += (double)(fabsf(sdf_last[i]) * lv);
     }
-    const double tl = block_sum(s_live, red, tid), tt = block_sum(s_tr, red, tid), ts = block_sum(s_sd, red, tid);
+    const double tl = block_total(s_live, red), tt = block_total(s_tr, red), ts = block_total(s_sd, red);
     if (tid == 0) {
         out[0] = (float)(tt / tl);
         out[1] = (float)(ts / tl);
@@ -243,7 +242,7 @@ ba_terms_fwd_kernel(const float* __restrict__ reproj, const float* __restrict__ 
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int64_t i = tid; i < n; i += kTtThreads) s += (double)fabsf(sdfs[i]);
-    const double tot = block_sum(s, red, tid);
+    const double tot = block_total(s, red);
     if (tid == 0) {
         const float surf = (float)(tot / (double)n);
         const float r = reproj[0];
@@ -420,7 +419,7 @@ match_term_fwd_kernel(const float* __restrict__ center, const float* __restrict_
             s_err += (double)o.err;
             s_sdf += (double)fabsf(sg.s[seg][j]);
         }
-    const double te = block_sum(s_err, red, tid), ts = block_sum(s_sdf, red, tid);
+    const double te = block_total(s_err, red), ts = block_total(s_sdf, red);
     if (tid == 0) {
         const double cnt = (double)n_seg * (double)n;
         out[0] = (float)(te / cnt);

@@ -119,26 +119,6 @@ __device__ __forceinline__ float pos_col(float s, const float4& a_da, const floa
     return s;
 }
 
-// fp64 wave scans for the d beta path (below)
-__device__ __forceinline__ double wave_scan_incl_f64(double v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_suffix_excl_f64(double v, int lane) {
-    double s = __shfl_down(v, 1, 64);
-    if (lane == 63) s = 0.0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_down(s, o, 64);
-        if (lane + o < 64) s += t;
-    }
-    return s;
-}
-
 // (WG) end of a pass: this wave's accumulators in the partial's row order (wgrad_tail.h: reduce_partials_row), with the row sums
 // over the 16 sample lanes for dW1[0] / db1; the workgroup's waves are summed through `buf` (s_w: the pass is done with its
 // weights) in a fixed order, and wave 0 stores the workgroup's partial.  `wave`: the wave's index in the workgroup, ray h's waves
@@ -445,7 +425,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
         const double delta_d = ((double)t_next - (double)t) *
                                sqrt((double)gm.d[0] * (double)gm.d[0] + (double)gm.d[1] * (double)gm.d[1] + (double)gm.d[2] * (double)gm.d[2]);
         const double tau_d = interval ? sigma_d * delta_d : 0.0;
-        const double incl_d = wave_scan_incl_f64(tau_d, lane);
+        const double incl_d = wave_scan_incl(tau_d, lane);
         if (lane == 63) s_pd[wave][0] = incl_d;
         __syncthreads();
         float before = incl - tau;
@@ -479,7 +459,7 @@ shade_bwd_kernel(FieldC fc, LevelScales lsc, int ch1_arg, int ch2_arg, WsLayout 
             vb_d += (double)g_nm[c] * ((double)nrm[c] - (double)n_last[c]);
         }
         const double u_w_d = interval ? vb_d * wgt_d : 0.0;
-        const double sfx_d = wave_suffix_excl_f64(u_w_d, lane);
+        const double sfx_d = wave_suffix_excl(u_w_d, lane);
         {
             double tot = u_w_d;
 #pragma unroll

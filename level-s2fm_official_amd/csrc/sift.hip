@@ -21,6 +21,7 @@
 // the lanes arrive; everything else is per-thread arithmetic or a butterfly reduction in a fixed order.  A view's rows depend on
 // that view's pixels alone, so a rerun, another batch around it or another chunking return the same bits.
 #include "ls2fm_device.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <cmath>
@@ -85,29 +86,23 @@ struct Ws {
     float* planes;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t ws_layout(int n_img, int cap, int64_t floats, char* base, Ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += align_up(bytes); return q; };
+    Workspace ws(base, 256);
     const size_t rows = (size_t)n_img * (size_t)cap;
-    char* imgs = take(sizeof(Img) * (size_t)n_img);
-    char* taps = take(sizeof(float) * kLevels * kTapStride);
-    char* count = take(sizeof(int32_t) * (size_t)n_img);
-    char* raw = take(sizeof(Cand) * rows);
-    char* sorted = take(sizeof(Cand) * rows);
-    char* scale = take(sizeof(float) * rows);
-    char* n_ori = take(sizeof(int32_t) * rows);
-    char* angles = take(sizeof(float) * 2 * rows);
-    char* kept = take(sizeof(int32_t) * rows);
-    char* start = take(sizeof(int32_t) * rows);
-    char* planes = take(sizeof(float) * (size_t)floats);
-    if (w) {
-        w->imgs = (Img*)imgs; w->taps = (float*)taps; w->cand_count = (int32_t*)count; w->raw = (Cand*)raw; w->sorted = (Cand*)sorted;
-        w->scale = (float*)scale; w->n_ori = (int32_t*)n_ori; w->angles = (float*)angles; w->kept = (int32_t*)kept;
-        w->out_start = (int32_t*)start; w->planes = (float*)planes;
-    }
-    return off;
+    Ws t;
+    t.imgs = ws.take<Img>((size_t)n_img);
+    t.taps = ws.take<float>((size_t)kLevels * kTapStride);
+    t.cand_count = ws.take<int32_t>((size_t)n_img);
+    t.raw = ws.take<Cand>(rows);
+    t.sorted = ws.take<Cand>(rows);
+    t.scale = ws.take<float>(rows);
+    t.n_ori = ws.take<int32_t>(rows);
+    t.angles = ws.take<float>(2 * rows);
+    t.kept = ws.take<int32_t>(rows);
+    t.out_start = ws.take<int32_t>(rows);
+    t.planes = ws.take<float>((size_t)floats);
+    if (w) *w = t;
+    return ws.bytes();
 }
 
 int check_opts(const ls2fm_sift_opts* o) {
@@ -372,12 +367,6 @@ __global__ void __launch_bounds__(kThreads) sift_rank_kernel(const int32_t* __re
         for (int j = 0; j < m; ++j) rank += keys[j] < key ? 1 : 0;
     }
     if (i < n) sorted[(int64_t)blockIdx.y * cap + rank] = mine[i];
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // gradient of level L at (x, y), 1 <= x <= w - 2, 1 <= y <= h - 2 -> modulus and angle in [0, 2 pi)

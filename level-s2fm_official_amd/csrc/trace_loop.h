@@ -139,10 +139,4 @@ __device__ __forceinline__ void store_track_point(const TraceEnd& e, int64_t r, 
     if (track_sdf) track_sdf[r * (iters_max + 1) + k] = e.raw;
 }
 
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 }  // namespace

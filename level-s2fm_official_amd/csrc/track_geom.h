@@ -1,6 +1,6 @@
 // What tracks.hip (triangulation) and mapper.hip (the mapper's upkeep of observations and points) share: the extent of a track,
 // the numbering of the pairs of a track's first LS2FM_TRACK_HYP_OBS observations, the camera centre, the pixel error and depth of
-// an observation, the triangulation angle, and the workgroup scan that numbers all tracks' pairs in one flat range.  include/ls2fm.h
+// an observation, and the triangulation angle (wave_ops.h's workgroup scan numbers all tracks' pairs in one flat range).  include/ls2fm.h
 // states the rules ("Feature tracks and multi-view triangulation"); all geometry in fp64, every sum in the order written here.
 #pragma once
 #include "ls2fm_device.h"
@@ -47,29 +47,6 @@ __device__ __forceinline__ void pair_of(int q, int m, int& i, int& j) {
     }
     i = row;
     j = row + 1 + left;
-}
-
-template <int NT>
-__device__ __forceinline__ long long block_exclusive_scan(long long v, long long& total, long long* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long x = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const long long y = __shfl_up(x, s, 64);
-        if (lane >= s) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const long long s = s_wave[w];
-        before += w < wave ? s : 0ll;
-        all += s;
-    }
-    __syncthreads();                                   // s_wave is written again by the next round
-    total = all;
-    return before + x - v;
 }
 
 // centre C_k = -((R0k t0 + R1k t1) + R2k t2) of the pose P [12]

@@ -23,6 +23,7 @@
 #include "pose_math.h"
 #include "track_geom.h"
 #include "union_find.h"
+#include "workspace.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -104,16 +105,13 @@ struct TtWs {
     unsigned long long* best_key;   // [T]
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 size_t tt_layout(int64_t T, int32_t V, char* base, TtWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-    char* c = take((size_t)V * 3 * sizeof(double));
-    char* h = take(((size_t)T + 1) * sizeof(long long));
-    char* k = take((size_t)(T ? T : 1) * sizeof(unsigned long long));
-    if (w) *w = {(double*)c, (long long*)h, (unsigned long long*)k};
-    return off;
+    Workspace ws(base, 256);
+    double* c = ws.take<double>((size_t)V * 3);
+    long long* h = ws.take<long long>((size_t)T + 1);
+    unsigned long long* k = ws.take<unsigned long long>((size_t)(T ? T : 1));
+    if (w) *w = {c, h, k};
+    return ws.bytes();
 }
 
 // the extent of track t (track_geom.h): false (n = 0) when it is not inside [0, n_obs], runs backwards or is too long
@@ -123,7 +121,6 @@ __device__ __forceinline__ bool track_extent(const TtIn& in, int64_t t, int64_t&
 
 __global__ void __launch_bounds__(kScanThreads)
 tt_prepare(TtIn in, TtWs w, int32_t* __restrict__ status) {
-    __shared__ long long s_wave[kScanThreads / 64];
     __shared__ int s_status;
     const int tid = threadIdx.x;
     if (tid == 0) s_status = 0;
@@ -143,7 +140,7 @@ tt_prepare(TtIn in, TtWs w, int32_t* __restrict__ status) {
             w.best_key[t] = 0ull;
         }
         long long sum;
-        const long long e = block_exclusive_scan<kScanThreads>(c, sum, s_wave);
+        const long long e = block_exclusive_scan<kScanThreads>(c, sum);
         if (t < in.T) w.hyp_start[t] = carry + e;
         carry += sum;
     }
@@ -232,12 +229,7 @@ tt_final(TtIn in, TtWs w, double* __restrict__ Xout, uint8_t* __restrict__ inlie
     int n = 0;
     if (have) track_extent(in, t, s0, n);
     // rounds of eight observations: as many as the longest track of the wave needs
-    int rounds = (n + kSub - 1) / kSub;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int y = __shfl_xor(rounds, o, 64);
-        rounds = y > rounds ? y : rounds;
-    }
+    const int rounds = wave_max((n + kSub - 1) / kSub);
     const unsigned long long bk = have ? w.best_key[t] : 0ull;
     const int q = bk ? (int)(0xFFFFFFFFu - (uint32_t)(bk & 0xFFFFFFFFull)) : -1;
     double X[3] = {0.0, 0.0, 0.0};

@@ -278,6 +278,14 @@ def check(status: int, what: str) -> None:
         raise RuntimeError(f"{what} failed: {msg} (status {status})")
 
 
+def workspace(n_bytes: int, symbol: str, device, min_bytes: int = 0) -> torch.Tensor:
+    """the uint8 workspace for the byte count `symbol` (a *_workspace_bytes export) returned; a negative count is its status"""
+    n_bytes = int(n_bytes)
+    if n_bytes < 0:
+        check(n_bytes, symbol)
+    return torch.empty(max(n_bytes, min_bytes), dtype=torch.uint8, device=device)
+
+
 def ptr(t) -> c_void_p:
     """device pointer of a tensor (None -> NULL)"""
     if t is None:

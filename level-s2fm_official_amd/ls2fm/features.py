@@ -96,11 +96,8 @@ def _call(greys, opt, dev, debug=False, with_keys=False):
             levels = torch.empty(total, dtype=torch.float32, device=dev)
         keys = torch.zeros((V * opt.max_num_features, 2), dtype=torch.int32, device=dev) if with_keys else None
         c_opt = opt.c_struct(levels, keys)
-        ws_bytes = lib.ls2fm_sift_workspace_bytes(c_h, c_w, V, ctypes.byref(c_opt))
-        if ws_bytes < 0:
-            check(int(ws_bytes), "ls2fm_sift_workspace_bytes")
+        ws = _lib.workspace(lib.ls2fm_sift_workspace_bytes(c_h, c_w, V, ctypes.byref(c_opt)), "ls2fm_sift_workspace_bytes", dev, 256)
         pixels = torch.cat([g.reshape(-1) for g in greys])
-        ws = torch.empty(max(int(ws_bytes), 256), dtype=torch.uint8, device=dev)
         kp = torch.empty((V * opt.max_num_features, 4), dtype=torch.float32, device=dev)
         desc = torch.empty((V * opt.max_num_features, 128), dtype=torch.uint8, device=dev)
         counts = torch.empty(V, dtype=torch.int32, device=dev)

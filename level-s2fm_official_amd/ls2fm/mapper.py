@@ -120,10 +120,7 @@ def view_scores(tracks, obs_uv, obs_keep, track_valid, registered, image_size, v
     size = size.contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.ls2fm_view_scores_workspace_bytes(T, V, n_obs))
-        if ws_bytes < 0:
-            check(ws_bytes, "ls2fm_view_scores_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.ls2fm_view_scores_workspace_bytes(T, V, n_obs), "ls2fm_view_scores_workspace_bytes", dev)
         score = torch.empty(V, dtype=torch.int64, device=dev)
         num = torch.empty(V, dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -164,10 +161,7 @@ def update_observations(tracks, obs_uv, poses, intrinsics, registered, X, track_
     valid_in = _flags(track_valid, T, dev, "track_valid", "update_observations")
     lib = _lib.load()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.ls2fm_update_observations_workspace_bytes(T, V, n_obs))
-        if ws_bytes < 0:
-            check(ws_bytes, "ls2fm_update_observations_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.ls2fm_update_observations_workspace_bytes(T, V, n_obs), "ls2fm_update_observations_workspace_bytes", dev)
         keep = torch.empty(n_obs, dtype=torch.uint8, device=dev)
         valid = torch.empty(T, dtype=torch.uint8, device=dev)
         num = torch.empty(T, dtype=torch.int32, device=dev)

@@ -77,11 +77,9 @@ def match_descriptors(descriptors, pairs=None, max_ratio=0.8, max_distance=0.7, 
     lib = _lib.load()
     c_start = start.ctypes.data_as(ctypes.c_void_p)
     c_pairs = pairs.ctypes.data_as(ctypes.c_void_p)
-    ws_bytes = lib.ls2fm_match_descriptors_workspace_bytes(c_start, V, c_pairs, P)
-    if ws_bytes < 0:
-        check(int(ws_bytes), "ls2fm_match_descriptors_workspace_bytes")
     with torch.cuda.device(dev):
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.ls2fm_match_descriptors_workspace_bytes(c_start, V, c_pairs, P), "ls2fm_match_descriptors_workspace_bytes",
+                            dev, 16)
         index = torch.empty(int(first[-1]), dtype=torch.int32, device=dev)
         num = torch.empty(P, dtype=torch.int32, device=dev)
         raw = [torch.empty(int(rows[-1]), dtype=torch.int32, device=dev) for _ in range(3)] if return_scores else [None] * 3

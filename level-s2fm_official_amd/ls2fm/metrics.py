@@ -133,10 +133,7 @@ class PointGrid:
         with torch.cuda.device(dev):
             self.cell_start = torch.empty(self.n_cells + 1, dtype=torch.int32, device=dev)
             self.sorted = torch.empty(self.n, 4, dtype=torch.float32, device=dev)
-            ws_bytes = int(lib.ls2fm_point_grid_workspace_bytes(self.n, self.n_cells))
-            if ws_bytes < 0:
-                check(ws_bytes, "ls2fm_point_grid_workspace_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(lib.ls2fm_point_grid_workspace_bytes(self.n, self.n_cells), "ls2fm_point_grid_workspace_bytes", dev)
             check(lib.ls2fm_point_grid_build(ptr(self.ref), self.n, self._origin, self.cell_size, self.inv_cell_size, self._dim,
                                              ptr(self.cell_start), ptr(self.sorted), ptr(ws), stream_ptr()), "ls2fm_point_grid_build")
         self.sorted_xyz = self.sorted[:, :3]

@@ -66,10 +66,7 @@ def _ransac(symbol, a, b, starts, extra_in, model_out, max_error_px, confidence,
     lib = _lib.load()
     opts = _lib.PoseRansacOpts(float(max_error_px), float(confidence), float(min_inlier_ratio), int(min_num_trials),
                                int(max_num_trials), int(seed) & ((1 << 64) - 1), 1 if refine else 0)
-    ws_bytes = getattr(lib, symbol + "_workspace_bytes")(G, n)
-    if ws_bytes < 0:
-        check(int(ws_bytes), symbol + "_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(getattr(lib, symbol + "_workspace_bytes")(G, n), symbol + "_workspace_bytes", dev)
     inl = torch.empty(n, dtype=torch.uint8, device=dev)
     num, trials, best, succ = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(4))
     check(getattr(lib, symbol)(ptr(a), ptr(b), ptr(starts), G, *map(ptr, extra_in), ctypes.byref(opts), *map(ptr, model_out), ptr(inl),

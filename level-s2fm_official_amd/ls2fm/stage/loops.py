@@ -726,10 +726,7 @@ class TradBALoop:
     def _init_device(self):
         lib = _lib.load()
         V, P, n, dev = self.se3.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.se3.device
-        size = int(lib.ls2fm_bundle_adjust_workspace_bytes(V, P, n))
-        if size < 0:
-            _lib.check(size, "ls2fm_bundle_adjust_workspace_bytes")
-        self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
+        self._ws = _lib.workspace(lib.ls2fm_bundle_adjust_workspace_bytes(V, P, n), "ls2fm_bundle_adjust_workspace_bytes", dev)
         self._obs_point32 = self.obs_point.to(torch.int32).contiguous()
         _lib.check(lib.ls2fm_bundle_adjust_prepare(_lib.ptr(self.view_start), V, _lib.ptr(self._obs_point32), n, P, _lib.ptr(self._ws),
                                                    _lib.stream_ptr()), "ls2fm_bundle_adjust_prepare")
@@ -878,10 +875,7 @@ class LMBALoop:
     def _init_device(self):
         lib = _lib.load()
         V, P, n, dev = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.poses.device
-        size = int(lib.ls2fm_bundle_adjust_lm_workspace_bytes(V, P, n))
-        if size < 0:
-            _lib.check(size, "ls2fm_bundle_adjust_lm_workspace_bytes")
-        self._ws = torch.empty((size + 7) // 8, dtype=torch.int64, device=dev)
+        self._ws = _lib.workspace(lib.ls2fm_bundle_adjust_lm_workspace_bytes(V, P, n), "ls2fm_bundle_adjust_lm_workspace_bytes", dev)
         self._obs_point32 = self.obs_point.to(torch.int32).contiguous()
         status = lib.ls2fm_bundle_adjust_lm_prepare(_lib.ptr(self.view_start), V, _lib.ptr(self._obs_point32), n, P, _lib.ptr(self.view_constant),
                                                     self.min_point_views, _lib.ptr(self._ws), _lib.stream_ptr())

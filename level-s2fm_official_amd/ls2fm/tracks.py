@@ -201,10 +201,7 @@ def triangulate_tracks(tracks, keypoints, poses, intrinsics, max_error_px=4.0, m
         raise ValueError(f"ls2fm.tracks.triangulate_tracks: {uv.shape[0]} pixel rows for {n_obs} observations of {T} tracks")
     lib = _lib.load()
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.ls2fm_triangulate_tracks_workspace_bytes(T, V))
-        if ws_bytes < 0:
-            check(ws_bytes, "ls2fm_triangulate_tracks_workspace_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.ls2fm_triangulate_tracks_workspace_bytes(T, V), "ls2fm_triangulate_tracks_workspace_bytes", dev)
         X = torch.empty(T, 3, dtype=torch.float64, device=dev)
         inl = torch.empty(n_obs, dtype=torch.uint8, device=dev)
         num, succ, best = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(3))

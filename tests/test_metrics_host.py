@@ -124,6 +124,16 @@ def test_auto_cell_size_is_positive_for_every_extent():
                 assert np.prod(dims) <= 2 ** 25
 
 
+def test_surface_scene_at_a_quarter_cell_scans_in_two_rounds():
+    """pg_scan_sums scans 1024 block totals per round, each of 1024 cells: only a grid of more than 1024 x 1024 cells carries a
+    sum into a second round.  The GPU tests build that grid from the surface scene at a quarter of its automatic cell size."""
+    ref = S.scenes()["surface"]["ref"]
+    lo, hi = ref.min(axis=0), ref.max(axis=0)
+    h = np.float32(MT.auto_cell_size(lo, hi, len(ref)) / 4)
+    dims = MT._dims((hi - lo).astype(np.float32), np.float32(1) / h)
+    assert 1024 * 1024 < np.prod(dims) <= 2 ** 25
+
+
 @pytest.mark.parametrize("voxel", [0.05, 0.3, 7.0])
 def test_voxel_downsample_equals_restatement(voxel):
     rng = np.random.default_rng(5)
