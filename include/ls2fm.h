@@ -1281,6 +1281,67 @@ int ls2fm_point_grid_query(const float* queries, int64_t n_queries, const float*
                            float* d2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A triangle rasteriser with a z-buffer (csrc/rasterize.hip behind ls2fm.raster; additions, the library stays ABI 13): which
+ * faces of a mesh each camera sees, mesh depth maps, per-pixel face ids and barycentrics, and per-vertex mask votes -- the
+ * culling step in front of the DTU Chamfer figures.  The reference ships none.  tests/raster_restate.py repeats the rule in numpy.
+ *
+ * Inputs: verts float [V][3]; faces int32 [F][3]; poses float [N][3][4], world-to-camera [R | t]; intr float [N][4] =
+ * (fx, fy, cx, cy), on the device (skew is not modelled); height, width; near > 0.  Pixel (px, py) has its centre at
+ * (px + 0.5, py + 0.5).  The RASTERISATION RULE, for one view and one face (a, b, c):
+ *   camera point  of a vertex X, in fp32: for row r of the pose, c_r = ((P_r0 X_0 + P_r1 X_1) + P_r2 X_2) + P_r3, every
+ *     operation rounded once, none contracted.
+ *   projection    u = fx * (c_x / c_z) + cx, v = fy * (c_y / c_z) + cy, each operation one rounded fp32 operation.
+ *   usable vertex c_z is finite, c_z >= near, |u| <= 65536 and |v| <= 65536.  A NaN fails every one of these comparisons.
+ *   snap          U = (int) rintf(u * 256), V likewise: 8 sub-pixel bits, |U| <= 2^24.  Every integer below stays under 2^52,
+ *     so its conversion to double is exact.
+ *   drawn face    a face is drawn in a view if and only if its three indices lie in [0, V), all three vertices are usable,
+ *     and A = (U_b - U_a)(V_c - V_a) - (V_b - V_a)(U_c - U_a) (int64) is not 0.
+ *   no clipping   a face with an unusable vertex is simply not drawn in that view (a stated deviation: marching-cubes
+ *     triangles are voxel-sized, so what crosses the near plane is negligible).  No back-face culling: back faces occlude.
+ *   coverage      in exact integers.  s = sign(A), P = (256 px + 128, 256 py + 128).  For the edge p -> q,
+ *     E_pq(P) = (U_q - U_p)(P_y - V_p) - (V_q - V_p)(P_x - U_p).  w_a = s E_bc, w_b = s E_ca, w_c = s E_ab, so that
+ *     w_a + w_b + w_c = s A = |A|.  An edge OWNS its boundary when its normalised direction d = s (U_q - U_p, V_q - V_p) has
+ *     d_y > 0, or d_y == 0 and d_x > 0.  The pixel is covered if and only if each w_i > 0, or w_i == 0 and that edge owns its
+ *     boundary.  The two triangles on either side of a shared edge traverse it in opposite directions after normalisation, so
+ *     exactly one of them takes a pixel centre lying on the edge.
+ *   depth         camera z, perspective-correct, in fp64.  Per face r_i = 1.0 / (double) c_z,i.  Per pixel
+ *     num = ((double) w_a r_a + (double) w_b r_b) + (double) w_c r_c, z = (float)((double) |A| / num): one division per pixel,
+ *     every operation rounded once.  The barycentrics are beta_i = (float)(((double) w_i r_i) / num).
+ *   z-test        key = ((uint64) bits(z) << 32) | (uint32) f; the smallest key wins: the nearest depth, among equal depth
+ *     bits the lowest face index.  No visiting order, batching or path shows in the result.
+ *   empty pixel   face_id = -1, depth = +inf, barycentrics 0.
+ *
+ * ls2fm_rasterize  -> face_id int32 [N][H][W], depth float [N][H][W], bary float [N][H][W][3] (or NULL), and face_hits int32 [F]
+ *   (or NULL; caller-zeroed): face_hits[f] += the pixels face f won, over the N views (32-bit integer atomics: exact, so reruns
+ *   agree).  workspace: the uint64 z-buffer, 8 n_views height width bytes, 8-byte aligned (the size query; negative: refused
+ *   sizes).  Three launches -- the workspace cleared to all-ones (by a kernel: a captured memset node was seen not to be ordered
+ *   with the kernels after it on replay), the raster kernel, the resolve kernel; nothing is read back, nothing is allocated and
+ *   no stream is forked, so the call can be captured.  The raster kernel takes one lane per (view, face): it sets
+ *   the face up, clips the box of pixel centres inside the face's bounds to the image, and walks the box when it holds at most
+ *   LS2FM_RASTER_LANE_PIXELS pixels; the wave then takes its remaining faces one at a time, the set-up broadcast, all 64 lanes
+ *   striding the box.  Both paths evaluate the same integer and fp64 expressions per pixel.  Its only atomic is the 64-bit
+ *   unsigned minimum on the z-buffer (the key is read first and the atomic skipped when it would not lower it: keys only fall).
+ *   The resolve kernel unpacks face_id and depth and recomputes the winner's barycentrics from the rule.  No floating-point
+ *   atomic anywhere.  n_views = 0 returns at once; n_faces = 0 fills -1 / +inf (and barycentrics 0).
+ * ls2fm_mesh_mask_votes  masks uint8 [N][H][W] -> seen, inside int32 [V] (overwritten).  One lane per vertex, looping over the
+ *   views, no atomics; the same camera point, projection and usable rule.  The vertex is IN THE IMAGE when 0 <= u < width and
+ *   0 <= v < height, as fp32 comparisons; its pixel is (floor(u), floor(v)).  seen[v] counts the views where the vertex is
+ *   usable and in the image, inside[v] those of them whose mask byte is non-zero.  n_verts = 0 returns at once; n_views = 0
+ *   writes zeros.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL required array (bary and face_hits are optional;
+ * verts and faces are required when n_faces > 0), a negative count, n_faces >= 2^31, height or width outside [1, 32768], a
+ * near that is not positive and finite, n_views height width >= 2^40, a workspace that is not 8-byte aligned;
+ * LS2FM_ERR_WORKSPACE for a NULL workspace.
+ */
+#define LS2FM_RASTER_LANE_PIXELS 16   /* a face whose clipped box holds more pixels than this is walked by its whole wave */
+int64_t ls2fm_rasterize_workspace_bytes(int32_t n_views, int32_t height, int32_t width);
+int ls2fm_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* poses, const float* intr,
+                    int32_t n_views, int32_t height, int32_t width, float near, int32_t* face_id, float* depth, float* bary,
+                    int32_t* face_hits, void* workspace, void* stream);
+int ls2fm_mesh_mask_votes(const float* verts, int64_t n_verts, const float* poses, const float* intr, int32_t n_views, int32_t height,
+                          int32_t width, float near, const uint8_t* masks, int32_t* seen, int32_t* inside, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:
