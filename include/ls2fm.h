@@ -1281,6 +1281,57 @@ int ls2fm_point_grid_query(const float* queries, int64_t n_queries, const float*
                            float* d2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ICP registration of a moving cloud to a fixed one (csrc/icp.hip behind ls2fm.metrics.icp; additions, the library stays ABI
+ * 13): the step between the camera alignment and the Chamfer figures of a reconstruction in its own gauge.  The reference ships
+ * none.  tests/icp_restate.py repeats the rule in numpy.
+ *
+ * The fixed cloud is a built point grid (sorted, cell_start, n_dst and the grid description of ls2fm_point_grid_build); the
+ * moving cloud is src float [n_src][3].  The transform (s, R, t) lives in the caller's state, double [24]:
+ *   [0] s   [1 .. 9] R row-major   [10 .. 12] t   [13] cost of the last accumulate   [14] its pair count   [15] iterations done
+ *   [16] status: 0 running, 1 converged, 2 degenerate   [17 .. 23] reserved, written as 0
+ * The caller initialises s, R, t and sets [13 .. 23] to 0.  Because the state is the caller's, split calls (iters = a, then
+ * iters = b) continue bit for bit like one call of a + b.
+ * accumulate  per source point p = (x, y, z), widened to fp64: p'_i = s ((R_i0 x + R_i1 y) + R_i2 z) + t_i, every operation
+ *   rounded once in this association, none contracted; p' is then rounded once to fp32 and is the query of the grid walk under
+ *   the distance rule and max_d2 (above).  A p' that is not finite has no pair; a source point without a qualifying reference
+ *   has no pair.  For a pair (p', q), q the stored fp32 reference and p' the fp32 point, both widened to fp64, the Gauss-Newton
+ *   normal equations of the left perturbation xi = (omega, upsilon, lambda), p'' = e^lambda exp([omega]x) p' + upsilon:
+ *     point to point (dst_normals NULL)   r = p' - q (three rows),  J = [-[p']x, I, p']
+ *     point to plane (dst_normals float [n_dst][3], of the fixed cloud, read at the winner's index n)
+ *                                         r = (n.x d.x + n.y d.y) + n.z d.z, d = p' - q (one row),
+ *                                         J = [p' x n, n, (n.x p'.x + n.y p'.y) + n.z p'.z],  (p' x n).x = p'.y n.z - p'.z n.y, ...
+ *   A pair's term of H_ab is J_0a J_0b, with three rows (J_0a J_0b + J_1a J_1b) + J_2a J_2b; of g_a the same with r in place
+ *   of J_.b; of the cost the same with r twice.  The 36 sums: the 28 entries of the upper triangle of H row-major, g (7), the
+ *   cost.  No floating-point atomic: a lane adds its own points in index order (point i belongs to lane i mod the launch's
+ *   lanes), the lanes of a workgroup are added in the fixed order of the library's workgroup sum, and the workgroups' partial
+ *   rows are added in row order.  The launch shape and the rows depend on n_src alone: min(ceil(n_src / 512), 512) workgroups of
+ *   512 lanes.  The pair count is an exact integer.  pair_idx int32 [n_src] and pair_d2 float [n_src] (each may be NULL) receive
+ *   the winner's index and d2, -1 and +inf without a pair; sums double [36] (may be NULL) the sums of the last accumulate.
+ * solve  H delta = -g by Cholesky in fp64, 7 x 7 with with_scale != 0, else the leading 6 x 6 (lambda = 0).  E = exp([omega]x) by
+ *   Rodrigues' formula (below |omega|^2 = 1e-30: I + [omega]x), k = 1 + expm1(lambda) (e^lambda, evaluated so that its error scales
+ *   with |lambda|; 1 without scale); s <- k s, R <- E R, t <- k (E t) + upsilon, each entry (a b + c d) + e f.
+ *   A pivot <= 0, a delta that is not finite or fewer pairs than unknowns: status DEGENERATE, the transform unchanged bit for
+ *   bit, the iteration not counted.  Otherwise the update is applied and counted, and max(|omega_i|, |lambda|) <= tol_rot together
+ *   with max |upsilon_i| <= tol_trans sets status CONVERGED.
+ * Every kernel reads the status first and does nothing once it is not 0: a call on a converged or degenerate state changes
+ * nothing, neither the state nor the pair arrays nor sums.  iters >= 1: two launches per iteration (accumulate, solve), iters
+ * of them whatever the status becomes.  iters = 0: one accumulate and the reduction of its rows (the solve's kernel, which stops
+ * after writing cost, pair count and sums): cost, count and pairs at the state's transform, the transform, the iteration count
+ * and the status untouched.  Nothing is read back: the call can be captured into a graph.  n_src = 0 or n_dst = 0: no walk, cost
+ * and count 0, status DEGENERATE at once (n_dst = 0 fills the pair arrays with -1 / +inf first).  This takes precedence over
+ * iters = 0 leaving the status untouched: an empty side sets DEGENERATE whatever iters is.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL array that is needed, a negative count or one of
+ * 2^31 or more, iters < 0 or above LS2FM_ICP_MAX_ITERS, a NaN or negative max_d2, tol_rot or tol_trans, a grid description the
+ * query refuses, a misaligned sorted; LS2FM_ERR_WORKSPACE for a NULL workspace (ls2fm_icp_workspace_bytes(n_src) bytes).
+ */
+#define LS2FM_ICP_MAX_ITERS 65536
+int64_t ls2fm_icp_workspace_bytes(int64_t n_src);
+int ls2fm_icp_run(const float* src, int64_t n_src, const float* sorted, const int32_t* cell_start, int64_t n_dst, const float* origin,
+                  float cell_size, float inv_cell_size, const int32_t* dim, const float* dst_normals, float max_d2, int32_t with_scale,
+                  int32_t iters, double tol_rot, double tol_trans, double* state, double* sums, int32_t* pair_idx, float* pair_d2,
+                  void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A triangle rasteriser with a z-buffer (csrc/rasterize.hip behind ls2fm.raster; additions, the library stays ABI 13): which
  * faces of a mesh each camera sees, mesh depth maps, per-pixel face ids and barycentrics, and per-vertex mask votes -- the
  * culling step in front of the DTU Chamfer figures.  The reference ships none.  tests/raster_restate.py repeats the rule in numpy.

@@ -7,6 +7,8 @@ reference ships neither, and the usual CPU KD-tree evaluation of two DTU-sized c
   voxel_downsample                one point per voxel, the lowest index
   chamfer / evaluate_mesh         accuracy, completeness, overall, precision / recall / F-score
   align_sim3 / pose_errors        Umeyama's similarity alignment, rotation and centre errors, ATE
+  icp / IcpResult                 registration of a cloud to ground truth over the grid (ls2fm_icp_run, csrc/icp.hip); evaluate_mesh
+                                  takes it (init=, icp=) for a mesh in another gauge than the ground truth
 
 The distance rule (include/ls2fm.h): dx = q.x - r.x, dy, dz likewise, d2 = (dx dx + dy dy) + dz dz, every operation one rounded
 fp32 operation; a reference qualifies when d2 <= max_d2 and d2 < +inf; the smallest d2 wins, among equal d2 the lowest index.  The
@@ -126,6 +128,7 @@ class PointGrid:
             raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {float(h)} gives {dims.astype(np.int64).tolist()} cells, "
                              f"more than max_cells = {max_cells}")
         self.origin, self.cell_size, self.inv_cell_size = lo, float(h), float(inv_h)
+        self.box_max = hi
         self.dim = tuple(int(d) for d in dims)
         self.n_cells = int(cells)
         self._origin = (ctypes.c_float * 3)(*[float(v) for v in lo])
@@ -299,17 +302,28 @@ def _chamfer_dict(a, c, thresholds):
                 thresholds=thresholds, precision=prec, recall=rec, fscore=f)
 
 
-def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), generator=None, brute_force=False, return_points=False):
+def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), generator=None, brute_force=False, return_points=False,
+                  init=None, icp=None):
     """The Chamfer figures of a mesh against a ground-truth cloud: ceil(area / density^2) points of ls2fm.mesh.sample_surface
     (uniforms from `generator`), both clouds thinned by voxel_downsample at `density`, then `chamfer`.
     -> the dict of chamfer plus n_pred and n_gt, the sizes of the two clouds compared (and, with return_points, pred_points and
     gt_points themselves).  One host read for the area, one per thinning, one for the dict.  A dataset's masks need the sampled
-    points: such a caller runs these steps itself and passes the masks to `chamfer`."""
+    points: such a caller runs these steps itself and passes the masks to `chamfer`.
+    init, icp: for a mesh in another gauge than the ground truth (a reconstruction from estimated poses).  With both None nothing
+    changes.  Otherwise the vertices are first moved by init = (s, R, t) as align_sim3 returns it (None: the identity), x -> s R x +
+    t in fp64, rounded to fp32; the thinned sample is registered to the thinned ground truth by `icp` (the function below) with the
+    options of the dict `icp` (None: its defaults; max_dist defaults to this call's max_dist, brute_force to this call's), and
+    `chamfer` runs on the registered sample.  The dict gains s, R, t -- the whole transform from the mesh's frame, ICP after init,
+    fp64 device tensors -- and icp_rmse, icp_n_pairs, icp_iterations, icp_status (one more host read)."""
     from . import mesh
     verts, gt = _points(verts, "verts"), _points(gt_points, "gt_points")
     _device(verts, faces, gt)
     if not (np.isfinite(density) and density > 0):
         raise ValueError(f"ls2fm.metrics.evaluate_mesh: density {density} must be positive and finite")
+    register = init is not None or icp is not None
+    if register:
+        s0, R0, t0 = _sim3(init, verts.device)
+        verts = (s0 * (verts.to(torch.float64) @ R0.t()) + t0).float()
     area = float(mesh._face_areas64(verts, faces).sum())
     count = int(math.ceil(area / (float(density) * float(density))))
     if count >= 1 << 31:
@@ -318,8 +332,16 @@ def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), gen
     pts = pts[voxel_downsample(pts, density)]
     gt = gt.float()
     gt = gt[voxel_downsample(gt, density)]
+    if register:
+        options = dict(max_dist=max_dist, brute_force=brute_force)
+        options.update(icp or {})
+        reg = _icp(pts, gt, **options)
+        pts = reg.apply(pts).float()
     out = chamfer(pts, gt, max_dist, thresholds=thresholds, brute_force=brute_force)
     out.update(n_pred=int(pts.shape[0]), n_gt=int(gt.shape[0]))
+    if register:
+        out.update(s=reg.s * s0, R=reg.R @ R0, t=reg.s * (reg.R @ t0) + reg.t, icp_rmse=reg.rmse, icp_n_pairs=reg.n_pairs,
+                   icp_iterations=reg.iterations, icp_status=reg.status)
     if return_points:
         out.update(pred_points=pts, gt_points=gt)
     return out
@@ -403,3 +425,249 @@ def pose_errors(poses_est, poses_gt, align=True, with_scale=True, registered=Non
     return dict(rot_err_deg=out[0], centre_err=out[1], ate_rmse=float((c * c).mean().sqrt()),
                 rot_err_mean_deg=float(r.mean()), rot_err_max_deg=float(r.max()), centre_err_mean=float(c.mean()),
                 centre_err_max=float(c.max()), scale=float(s), n_views=n, n_unregistered=V - n)
+
+
+# ------------------------------------------------------------------------------------------------------------------- ICP
+ICP_RUNNING, ICP_CONVERGED, ICP_DEGENERATE = 0, 1, 2
+ICP_MAX_ITERS = 65536                     # LS2FM_ICP_MAX_ITERS
+ICP_TOL_ROT = 1e-9                        # the default tol_rot (radians; |lambda| too)
+ICP_TOL_TRANS_REL = 1e-9                  # the default tol_trans, as a fraction of the diagonal of the fixed cloud's box
+_S_COST, _S_PAIRS, _S_ITERS, _S_STATUS, _S_SIZE = 13, 14, 15, 16, 24
+
+
+def _sim3(init, device):
+    """(s fp64 0-dim, R fp64 [3, 3], t fp64 [3]) on `device` of an (s, R, t) as align_sim3 returns it; None: the identity"""
+    if init is None:
+        init = (1.0, torch.eye(3, dtype=torch.float64), torch.zeros(3, dtype=torch.float64))
+    s, R, t = init
+    s = torch.as_tensor(s, dtype=torch.float64).to(device).reshape(())
+    R = torch.as_tensor(R).to(device=device, dtype=torch.float64)
+    t = torch.as_tensor(t).to(device=device, dtype=torch.float64).reshape(-1)
+    if R.shape != (3, 3) or t.shape != (3,):
+        raise ValueError(f"ls2fm.metrics.icp: init must be (s, R [3, 3], t [3]), got R {tuple(R.shape)}, t {tuple(t.shape)}")
+    return s, R, t
+
+
+class IcpResult:
+    """What `icp` returns.  s (0-dim), R [3, 3], t [3]: fp64 tensors on the clouds' device, views of `state` (fp64 [24], the layout
+    of include/ls2fm.h; pass it back as icp(..., state=) to continue bit for bit).  rmse = sqrt(cost / n_pairs) and n_pairs come from
+    a closing evaluation at the returned transform (the cost is the sum of squared residuals: distances point to point, distances
+    along the normal point to plane; NaN without a pair); iterations and status (ICP_RUNNING: the iterations ran out,
+    ICP_CONVERGED, ICP_DEGENERATE) from the state.  With read=False these four are None and `evaluation`, the fp64 [24] state of
+    the closing evaluation (cost at 13, pair count at 14), holds them on the device.  pair_idx int32 [M] / pair_d2 float32 [M] (with
+    return_pairs): each source point's reference at the returned transform, -1 / +inf without one."""
+
+    def __init__(self, state, evaluation, pair_idx=None, pair_d2=None):
+        self.state, self.evaluation, self.pair_idx, self.pair_d2 = state, evaluation, pair_idx, pair_d2
+        self.s, self.R, self.t = state[0], state[1:10].view(3, 3), state[10:13]
+        self.rmse = self.n_pairs = self.iterations = self.status = None
+
+    def read(self):
+        """the one host read: fills rmse, n_pairs, iterations, status"""
+        cost, pairs, iterations, status = torch.cat([self.evaluation[_S_COST:_S_PAIRS + 1], self.state[_S_ITERS:_S_STATUS + 1]]).cpu().tolist()
+        self.n_pairs, self.iterations, self.status = int(pairs), int(iterations), int(status)
+        self.rmse = math.sqrt(cost / pairs) if pairs else float("nan")
+        return self
+
+    def apply(self, points):
+        """s R p + t of points [n, 3] in fp64 (on the state's device)"""
+        p = _points(points, "points").to(device=self.state.device, dtype=torch.float64)
+        return self.s * (p @ self.R.t()) + self.t
+
+
+def _icp_state(init, state, device):
+    if state is not None:
+        state = torch.as_tensor(state)
+        if state.dtype != torch.float64 or state.shape != (_S_SIZE,):
+            raise ValueError(f"ls2fm.metrics.icp: state must be float64 [{_S_SIZE}], got {state.dtype} {tuple(state.shape)}")
+        return state.to(device).clone()
+    s, R, t = _sim3(init, device)
+    out = torch.zeros(_S_SIZE, dtype=torch.float64, device=device)
+    out[0] = s
+    out[1:10] = R.reshape(-1)
+    out[10:13] = t
+    return out
+
+
+def _chol_solve(H, g):
+    """H x = -g by the Cholesky order of the device's solve (lm_math::chol_solve), so that the torch form calls the same systems
+    degenerate: None for a pivot <= 0 (a NaN included) or an x that is not finite"""
+    m = len(g)
+    L = [[0.0] * m for _ in range(m)]
+    for j in range(m):
+        d = float(H[j, j]) - sum(L[j][k] * L[j][k] for k in range(j))
+        if not d > 0.0:
+            return None
+        L[j][j] = math.sqrt(d)
+        for i in range(j + 1, m):
+            L[i][j] = (float(H[j, i]) - sum(L[i][k] * L[j][k] for k in range(j))) / L[j][j]
+    z, x = [0.0] * m, [0.0] * m
+    for i in range(m):
+        z[i] = (-float(g[i]) - sum(L[i][k] * z[k] for k in range(i))) / L[i][i]
+    for i in range(m - 1, -1, -1):
+        x[i] = (z[i] - sum(L[k][i] * x[k] for k in range(i + 1, m))) / L[i][i]
+    x = np.array(x)
+    return x if np.isfinite(x).all() else None
+
+
+def _icp_torch_step(src64, ref, normals, state, neighbours, with_scale, tol_rot, tol_trans, solve):
+    """one iteration of the rule as plain torch ops: the transform in the stated association, `neighbours` for the pairs, the
+    normal equations as masked fp64 reductions; with `solve` the 7 x 7 system goes to the host, is solved there (_chol_solve) and
+    the state updated.  -> (idx, d2)"""
+    s, R, t = state[0], state[1:10].view(3, 3), state[10:13]
+    x, y, z = src64[:, 0], src64[:, 1], src64[:, 2]
+    p = torch.stack([s * ((R[i, 0] * x + R[i, 1] * y) + R[i, 2] * z) + t[i] for i in range(3)], dim=1).float()
+    idx, d2 = neighbours(p)
+    has = idx >= 0
+    j = idx.clamp(min=0).long()
+    w = has.to(torch.float64)
+    p64 = torch.where(has[:, None], p.to(torch.float64), torch.zeros((), dtype=torch.float64, device=p.device))
+    if ref.shape[0] == 0:                                          # no reference: nothing to gather, no pair
+        ref, normals = ref.new_zeros((1, 3)), None if normals is None else normals.new_zeros((1, 3))
+    d = (p64 - ref[j].to(torch.float64)) * w[:, None]
+    px, py, pz = p64[:, 0], p64[:, 1], p64[:, 2]
+    zero = torch.zeros_like(px)
+    if normals is None:
+        J = torch.stack([torch.stack([zero, pz, -py, w, zero, zero, px], dim=1), torch.stack([-pz, zero, px, zero, w, zero, py], dim=1),
+                         torch.stack([py, -px, zero, zero, zero, w, pz], dim=1)], dim=1)
+        r = d
+    else:
+        n = normals[j].to(torch.float64) * w[:, None]
+        nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+        J = torch.stack([py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz, (nx * px + ny * py) + nz * pz], dim=1)[:, None, :]
+        r = ((nx * d[:, 0] + ny * d[:, 1]) + nz * d[:, 2])[:, None]
+    # the Gram matrix of [J | r], 4096 rows at a time as one batched product (a single product over millions of rows runs as one
+    # long dot product per entry): H, g and the cost are its blocks
+    A = torch.cat([J.reshape(-1, 7), r.reshape(-1, 1)], dim=1)
+    A = torch.nn.functional.pad(A, (0, 0, 0, -A.shape[0] % 4096)).view((A.shape[0] + 4095) // 4096, 4096, 8)
+    G = torch.bmm(A.transpose(1, 2), A).sum(dim=0)
+    H, g = G[:7, :7], G[:7, 7]
+    state[_S_COST] = G[7, 7]
+    state[_S_PAIRS] = w.sum()
+    if not solve:
+        return idx, d2
+    host = torch.cat([H.reshape(-1), g, state[:_S_SIZE]]).cpu().numpy()                # the iteration's host read
+    Hh, gh, st = host[:49].reshape(7, 7), host[49:56], host[56:].copy()
+    m = 7 if with_scale else 6
+    delta = None
+    if st[_S_PAIRS] >= m:
+        delta = _chol_solve(Hh[:m, :m], gh[:m])
+    if delta is None:
+        st[_S_STATUS] = ICP_DEGENERATE
+    else:
+        wv = delta[:3]
+        th2 = float(wv @ wv)
+        K = np.array([[0.0, -wv[2], wv[1]], [wv[2], 0.0, -wv[0]], [-wv[1], wv[0], 0.0]])
+        th = math.sqrt(th2)
+        E = np.eye(3) + K if th2 < 1e-30 else np.eye(3) + math.sin(th) / th * K + (1.0 - math.cos(th)) / th2 * (K @ K)
+        lam = float(delta[6]) if with_scale else 0.0
+        k = 1.0 + math.expm1(lam)
+        st[0] = k * st[0]
+        st[10:13] = k * (E @ st[10:13]) + delta[3:6]
+        st[1:10] = (E @ st[1:10].reshape(3, 3)).reshape(-1)
+        st[_S_ITERS] += 1
+        if max(np.abs(wv).max(), abs(lam)) <= tol_rot and np.abs(delta[3:6]).max() <= tol_trans:
+            st[_S_STATUS] = ICP_CONVERGED
+    state.copy_(torch.as_tensor(st).to(state.device))
+    return idx, d2
+
+
+def _icp_torch(src, ref, normals, state, neighbours, with_scale, iters, tol_rot, tol_trans):
+    """the loop of _icp_torch_step with the status rules (the status lives on the host here: one read per iteration)"""
+    src64 = src.to(torch.float64)
+    for _ in range(iters):
+        if int(state[_S_STATUS]) != ICP_RUNNING:
+            break
+        _icp_torch_step(src64, ref, normals, state, neighbours, with_scale, tol_rot, tol_trans, True)
+
+
+def icp(src, dst, init=None, dst_normals=None, max_dist=None, with_scale=False, iters=50, tol_rot=ICP_TOL_ROT, tol_trans=None,
+        return_pairs=False, brute_force=False, state=None, read=True):
+    """Registers the moving cloud `src` (float32 [M, 3]) to the fixed cloud `dst` (float32 [N, 3], or a PointGrid built over it: the
+    grid is then reused across calls and cut-off stages) by ICP -> IcpResult.  Each iteration pairs every moved source point
+    p' = s R p + t (fp64, rounded once to fp32) with its nearest point of dst by the distance rule, within max_dist (None: no
+    cut-off), and takes one Gauss-Newton step on the similarity (with_scale) or rigid transform for the point-to-point residual,
+    or, with dst_normals (float32 [N, 3], normals of the FIXED cloud), the point-to-plane residual.  include/ls2fm.h states the rule
+    (csrc/icp.hip: two launches per iteration, no host read, no floating-point atomic: a run is a pure function of its inputs);
+    tests/icp_restate.py repeats it in numpy.
+    init: the start, an (s, R, t) as align_sim3 returns it (None: the identity); state: an earlier result's state to continue from
+    instead.  The loop stops at `iters` iterations (at most ICP_MAX_ITERS), when a step has max(|omega|, |lambda|) <= tol_rot and
+    max |upsilon| <= tol_trans (status ICP_CONVERGED), or at a system that cannot be solved -- fewer pairs than unknowns, a pivot
+    <= 0 -- (ICP_DEGENERATE, the transform as it was).  The defaults are an interface choice, not a measurement: tol_rot = 1e-9
+    (ICP_TOL_ROT) and tol_trans = 1e-9 (ICP_TOL_TRANS_REL) times the diagonal of the fixed cloud's bounding box.
+    The only host read is the final one for rmse, n_pairs, iterations and status; read=False skips it, and the call can then be
+    captured into a graph (with dst a PointGrid: building one reads the box).  Deviations from the usual formulations: Gauss-Newton
+    on the linearisation for both residuals, where point to point has a closed form (one accumulate and one solve serve both, and
+    the camera alignment starts it close); normals on the fixed cloud only; no robust loss beyond the cut-off; a source point's
+    correspondence is its nearest reference only.
+    brute_force=True runs the same rule as plain torch ops on any device over nearest_neighbors_bruteforce, with the solve on the
+    host: the timing baseline and the CPU route of the host tests; nothing in the library falls back to it."""
+    src = _points(src, "src")
+    grid = dst if isinstance(dst, PointGrid) else None
+    ref = grid.ref if grid is not None else _points(dst, "dst")
+    if not brute_force:
+        _device(src, ref, dst_normals)
+    dev = src.device
+    if ref.device != dev:
+        raise ValueError(f"ls2fm.metrics.icp: src on {dev}, dst on {ref.device}")
+    iters = int(iters)
+    if not 0 <= iters <= ICP_MAX_ITERS:
+        raise ValueError(f"ls2fm.metrics.icp: iters {iters} must be in [0, {ICP_MAX_ITERS}]")
+    max_d2 = _max_d2(max_dist)
+    n = int(ref.shape[0])
+    normals = None
+    if dst_normals is not None:
+        normals = _points(dst_normals, "dst_normals")
+        if normals.shape[0] != n or normals.device != dev:
+            raise ValueError(f"ls2fm.metrics.icp: dst_normals {tuple(normals.shape)} on {normals.device} for {n} points on {dev}")
+        normals = _lib.cf(normals)
+    if tol_trans is None:
+        if grid is not None:
+            diagonal = float(np.linalg.norm(grid.box_max.astype(np.float64) - grid.origin.astype(np.float64)))
+        elif brute_force:
+            diagonal = float((ref.double().amax(dim=0) - ref.double().amin(dim=0)).norm()) if n else 0.0
+        else:
+            grid = PointGrid(ref)
+            diagonal = float(np.linalg.norm(grid.box_max.astype(np.float64) - grid.origin.astype(np.float64)))
+        tol_trans = ICP_TOL_TRANS_REL * diagonal
+    tol_rot, tol_trans = float(tol_rot), float(tol_trans)
+    if not (tol_rot >= 0 and tol_trans >= 0):
+        raise ValueError(f"ls2fm.metrics.icp: tol_rot {tol_rot} and tol_trans {tol_trans} must be >= 0")
+    src = _lib.cf(src)
+    m = int(src.shape[0])
+    if m >= 1 << 31:
+        raise ValueError(f"ls2fm.metrics.icp: {m} source points, 2^31 or more")
+    state = _icp_state(init, state, dev)
+    if brute_force:
+        ref = ref.float()
+        neighbours = lambda p: nearest_neighbors_bruteforce(p, ref, max_dist)      # noqa: E731
+        _icp_torch(src, ref, normals, state, neighbours, with_scale, iters, tol_rot, tol_trans)
+        evaluation = state.clone()
+        evaluation[_S_STATUS] = ICP_RUNNING
+        idx, d2 = _icp_torch_step(src.to(torch.float64), ref, normals, evaluation, neighbours, with_scale, tol_rot, tol_trans, False)
+        out = IcpResult(state, evaluation, *((idx, d2) if return_pairs else ()))
+        return out.read() if read else out
+    if grid is None:
+        grid = PointGrid(ref)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _lib.workspace(lib.ls2fm_icp_workspace_bytes(m), "ls2fm_icp_workspace_bytes", dev)
+        idx = torch.empty(m, dtype=torch.int32, device=dev) if return_pairs else None
+        d2 = torch.empty(m, dtype=torch.float32, device=dev) if return_pairs else None
+
+        def run(st, n_iters, pair_idx, pair_d2):
+            check(lib.ls2fm_icp_run(ptr(src), m, ptr(grid.sorted), ptr(grid.cell_start), grid.n, grid._origin, grid.cell_size,
+                                    grid.inv_cell_size, grid._dim, ptr(normals), float(max_d2), 1 if with_scale else 0, n_iters, tol_rot,
+                                    tol_trans, ptr(st), None, ptr(pair_idx), ptr(pair_d2), ptr(ws), stream_ptr()), "ls2fm_icp_run")
+
+        if iters:
+            run(state, iters, None, None)
+        # the closing evaluation: a copy of the state set to RUNNING, so that it runs whatever the status has become
+        evaluation = state.clone()
+        evaluation[_S_STATUS:_S_STATUS + 1].zero_()                 # ICP_RUNNING; a fill, not a host copy: capturable
+        run(evaluation, 0, idx, d2)
+    out = IcpResult(state, evaluation, idx, d2)
+    return out.read() if read else out
+
+
+_icp = icp          # evaluate_mesh has a parameter of this name
