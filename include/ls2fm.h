@@ -1393,6 +1393,51 @@ int ls2fm_mesh_mask_votes(const float* verts, int64_t n_verts, const float* pose
                           int32_t width, float near, const uint8_t* masks, int32_t* seen, int32_t* inside, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Image-quality metrics of rendered views against photographs (csrc/image_metrics.hip behind ls2fm.image_metrics; additions, the
+ * library stays ABI 13, the number the host tests of earlier additions pin): the squared error behind PSNR, and SSIM over the
+ * valid region, per view, in fp64.  The reference has only the training-time PSNR of the sampled rays (pipelines/Camera.py:534).
+ * tests/image_metrics_restate.py repeats the rule and the summation order in numpy.
+ *
+ * Inputs: a, b float [N][H][W][C], channel last (the layout of ls2fm_render_image's rgb), 1 <= C <= 4; mask uint8 [N][H][W] or
+ * NULL, non-zero = counted; taps double [n_taps] ON THE HOST, n odd, 1 <= n <= LS2FM_IMAGE_MAX_TAPS, used along both axes (the
+ * library evaluates no exp: a Gaussian and a uniform window are two tap arrays); c1, c2 doubles, >= 0 and finite.
+ * THE RULE, every operation one rounded fp64 operation, none contracted, x = (double) a, y = (double) b:
+ *   squared error  per pixel and channel (x - y)^2, over the pixels with mask != 0.  Per view: sse, and count = the number of
+ *     pixel-channels (int64).
+ *   SSIM  no padding: window (y, x), 0 <= y <= H - n, 0 <= x <= W - n, covers pixels (y .. y + n - 1, x .. x + n - 1); its centre
+ *     pixel is (y + r, x + r), r = (n - 1) / 2.  Per channel the five moments E[x], E[y], E[xx], E[yy], E[xy] are the images
+ *     x, y, x x, y y, x y blurred separably, along rows first:  R(y', x) = sum_k w[k] v(y', x + k),  then along columns:
+ *     M(y, x) = sum_k w[k] R(y + k, x);  each sum is  acc = w[0] v[0];  acc = acc + w[k] v[k]  for k = 1 .. n - 1 in tap order.
+ *     vx = E[xx] - mx mx,  vy = E[yy] - my my,  cxy = E[xy] - mx my,
+ *     ssim = (((2 mx) my + c1) (2 cxy + c2)) / (((mx mx + my my) + c1) ((vx + vy) + c2)),  one IEEE division.
+ *     Two identical images give exactly 1.0 at every window: numerator and denominator are the same operations.  Per view:
+ *     ssim_sum over the windows whose centre pixel has mask != 0, all channels, and ssim_count = their number times C (int64).
+ *   ssim_map  double [N][H - n + 1][W - n + 1][C] or NULL: every window's value, masked or not.
+ * SUMMATION ORDER (no floating-point atomic, nothing read back): the image is cut into tiles of T x T, T = LS2FM_IMAGE_TILE,
+ *   ceil(H / T) x ceil(W / T) of them; tile (ty, tx) owns the pixels (T ty + ly, T tx + lx) and the windows of the same indices,
+ *   0 <= ly, lx < T.  Lane T ly + lx of the tile's workgroup starts from 0.0 and adds its pixel's (its window's) terms in channel
+ *   order; a term that is not counted (outside the image, mask 0) is +0.0.  The T T = 256 lanes are added in the order of the
+ *   library's workgroup sum (csrc/wave_ops.h block_sum: the xor butterfly 32, 16, .. 1 inside each wave of 64 lanes, then the
+ *   four waves in index order).  A second launch adds a view's tiles in row-major tile order, starting from 0.0.  Neither the
+ *   tile size nor a pixel's place in its tile shows in ssim_map; the sums depend on T through this order alone.
+ * Views are independent: a non-finite pixel reaches the numbers of its own view only.  A view whose mask is empty gets sums
+ * and counts of 0.  Two launches per call (one more per 65535 views), no allocation, no stream forked: the call can be captured.
+ * workspace: ls2fm_image_compare_workspace_bytes(...) bytes (one partial row and two counts per view and tile); workspace_bytes
+ * is what the caller provides.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL required array (mask and ssim_map are optional),
+ * n_views < 1, channels outside 1 .. 4, n_taps even or outside 1 .. 33, height or width below n_taps, c1 or c2 negative or not
+ * finite, H W C >= 2^31; LS2FM_ERR_WORKSPACE for a NULL or short workspace.  The size query refuses the same shapes with the
+ * (negative) status as its result.
+ */
+#define LS2FM_IMAGE_TILE 16
+#define LS2FM_IMAGE_MAX_TAPS 33
+int64_t ls2fm_image_compare_workspace_bytes(int32_t n_views, int32_t height, int32_t width, int32_t channels, int32_t n_taps);
+int ls2fm_image_compare(const float* a, const float* b, const uint8_t* mask, int32_t n_views, int32_t height, int32_t width,
+                        int32_t channels, const double* taps, int32_t n_taps, double c1, double c2, double* sse, int64_t* count,
+                        double* ssim_sum, int64_t* ssim_count, double* ssim_map, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -239,6 +239,9 @@ _SIGNATURES = {
     "ls2fm_rasterize_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ls2fm_rasterize": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P]),
     "ls2fm_mesh_mask_votes": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P]),
+    "ls2fm_image_compare_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "ls2fm_image_compare": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(ctypes.c_double), c_int32, ctypes.c_double,
+                                      ctypes.c_double, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

@@ -16,6 +16,9 @@ ls2fm_trace_image (csrc/trace_image.hip) sphere-traces every pixel with the trip
 per-pixel outputs only -- no track, no re-evaluation of it, one normal query.  `get_depth` is the drop-in
 (Camera.get_depth = ls2fm.image.get_depth); with grad enabled, on CPU tensors, for bg_sdf or several poses it runs the reference's
 steps on this package's classes instead (get_center_and_ray, SDF.sphere_tracing, SDF.gradient).
+
+`evaluate_views` is render_image followed by ls2fm.image_metrics.compare_images on its rgb: the PSNR / SSIM of the rendered views
+against the photographs, per view, without leaving the device.
 """
 from __future__ import annotations
 
@@ -114,6 +117,20 @@ def render_img_by_slices(camera_obj, sdf_func, color_func, Renderer, pose_input=
     pose = camera_obj.get_pose() if pose_input is None else pose_input
     ret = render_image(Renderer, opt, sdf_func, color_func, pose, camera_obj.intrinsic, H=opt.H, W=opt.W)
     return Options(depth=ret.depth, norm=ret.norm, rgb=ret.rgb)
+
+
+@torch.no_grad()
+def evaluate_views(renderer, opt, sdf_field, rad_field, poses, intr, images, masks=None, H=None, W=None, return_render=False,
+                   **compare_kw):
+    """The PSNR / SSIM row of a results table without leaving the device: render_image on `poses`, then
+    ls2fm.image_metrics.compare_images of its rgb with `images` ([V, H, W, 3] or [V, HW, 3]; masks [V, H, W] or None;
+    compare_kw: data_range, window, k1, k2, full).  -> ImageScores, or (ImageScores, the render) with return_render=True."""
+    from . import image_metrics
+    H, W = _image_size(opt, H, W)
+    ret = render_image(renderer, opt, sdf_field, rad_field, poses, intr, H=H, W=W)
+    images = torch.as_tensor(images)
+    scores = image_metrics.compare_images(ret.rgb, images.reshape(ret.rgb.shape), mask=masks, H=H, W=W, **compare_kw)
+    return (scores, ret) if return_render else scores
 
 
 # ------------------------------------------------------------------------------------------------ depth and normal maps
