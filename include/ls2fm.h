@@ -1438,6 +1438,74 @@ int ls2fm_image_compare(const float* a, const float* b, const uint8_t* mask, int
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The radiance field at free points (csrc/radiance_points.hip behind ls2fm.mesh_colors.field_colors; an addition, the library
+ * stays ABI 13): the colour the trained field gives a mesh vertex.  The reference evaluates radiance along camera rays only.
+ *
+ * Inputs: points float [n][3] (world); view_dirs float [n][3] or NULL; field, sdf_grid, rad_grid and params as ls2fm_render_fwd
+ * takes them (rad_grid and the geo_* / rad_table parameters are read only with field->dual_field; n_samples and bgcolor are not
+ * read).  Per point p, what Renderer.forward_composed forms per sample (models/Renderer.py:105-117):
+ *   sdf, feats = SDF.infer_sdf(p, "ret_all");  g = SDF.gradient(p), the analytic normal, not normalised;
+ *   view = Embedder_Fourier(v), v = view_dirs[i], or v = -g / max(|g|, 1e-12) when view_dirs is NULL (the surface seen head-on:
+ *   -torch.nn.functional.normalize(g));  geo = feats[1:], with dual_field followed by Geometry_feat(p)[1:];
+ *   rgb = infer_app([p, g, view, geo]).
+ * Outputs: rgb float [n][3]; normal float [n][3] or NULL (g); sdf float [n] or NULL.  sdf and normal are bit for bit what
+ * ls2fm_sdf_eval returns for the same points: the kernel runs that call's evaluators (sdf_point.h, render_common.h).
+ * One lane per point, LS2FM_RADIANCE_POINTS_TILE points per workgroup; two launches (the weight preparation, the evaluation);
+ * no atomic, no allocation, nothing read back, no stream forked: the call can be captured.  n = 0 returns at once.
+ * workspace: ls2fm_radiance_points_workspace_bytes() bytes (the prepared weights).
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL descriptor, a grid descriptor the library does not
+ * serve, a NULL required parameter or array, n < 0; LS2FM_ERR_UNSUPPORTED for field->bg_sdf (the composed form serves it);
+ * LS2FM_ERR_WORKSPACE for a NULL workspace.
+ */
+#define LS2FM_RADIANCE_POINTS_TILE 256
+int64_t ls2fm_radiance_points_workspace_bytes(void);
+int ls2fm_radiance_points(const ls2fm_field_desc* field, const ls2fm_grid_desc* sdf_grid, const ls2fm_grid_desc* rad_grid,
+                          const ls2fm_params* params, const float* points, const float* view_dirs, int64_t n, float* rgb,
+                          float* normal, float* sdf, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Vertex colours of a mesh from photographs (csrc/mesh_colors.hip behind ls2fm.mesh_colors.photo_colors; additions, the library
+ * stays ABI 13): per vertex, a weighted blend of the views that see it, visibility decided against ls2fm_rasterize's depth maps
+ * of the same mesh.  The reference ships none.  tests/mesh_colors_restate.py repeats the rule in numpy.
+ *
+ * Inputs: verts float [V][3]; normals float [V][3] or NULL; poses float [N][3][4] and intr float [N][4] as for ls2fm_rasterize;
+ * images float [N][H][W][C], channel last, 1 <= C <= 4; depth float [N][H][W], ls2fm_rasterize's depth of the same mesh, views
+ * and near; masks uint8 [N][H][W] or NULL; near > 0; depth_tol >= 0; power, an integer 0 .. 8; and the caller-owned state
+ * sums double [V][C + 1], count int32 [V] (zeroed by the caller before the first call).
+ * THE VERTEX COLOUR RULE, per vertex and view, the views in index order:
+ *   1. pixel     camera point c, projection (u, v), usable and IN THE IMAGE by the RASTERISATION RULE and ls2fm_mesh_mask_votes'
+ *      rule above (csrc/raster_project.h holds the expressions for all three); the pixel is (floor u, floor v).  Otherwise the
+ *      view is skipped.
+ *   2. mask      a zero mask byte at the pixel skips the view.
+ *   3. visible   d = depth at the pixel.  The view counts if and only if d is finite and c_z <= d + depth_tol * d, in fp32, the
+ *      product and the sum each rounded once, not contracted.  An empty pixel (+inf) and a NaN fail.
+ *   4. weight    without normals w = 1.  With normals, in fp64 from the fp32 inputs, every operation rounded once: n_c = R n,
+ *      row r as ((R_r0 n_0 + R_r1 n_1) + R_r2 n_2);  dot = ((n_c0 c_0 + n_c1 c_1) + n_c2 c_2);  |n_c| = sqrt((n_c0 n_c0 +
+ *      n_c1 n_c1) + n_c2 n_c2), |c| likewise, correctly rounded roots;  cos = (-dot) / (|n_c| |c|).  cos <= 0 or not finite
+ *      skips the view.  w = 1, then w = w cos, `power` times.
+ *   5. sample    bilinear about the pixel centres, in fp64: x = (double) u - 0.5, x0 = floor(x), fx = x - x0, y likewise; the
+ *      columns x0, x0 + 1 and the rows y0, y0 + 1 clamped to the image; per channel r0 = a00 + fx (a10 - a00),
+ *      r1 = a01 + fx (a11 - a01), s = r0 + fy (r1 - r0), a_xy the tap at column x, row y.
+ *   6. accumulate  sums[v][c] += w s_c, sums[v][C] += w, count[v] += 1: the product rounded, then the sum.
+ * One lane takes one vertex (LS2FM_MESH_COLORS_THREADS per workgroup) and loads, extends and stores its state: no atomic, and a
+ * call over views 0 .. k followed by a call over views k + 1 .. N - 1 leaves the bits of one call over all of them.  A NaN pixel
+ * stays in the sums of the vertices that sampled it.  One launch; n_verts = 0 and n_views = 0 return at once.
+ * ls2fm_mesh_vertex_colors_finish  -> color float [V][C]: (float)(sums[v][c] / sums[v][C]) where count[v] > 0; elsewhere
+ *   fallback[v][c] when fallback (float [V][C], on the device) is given, otherwise fill[c] (`channels` floats ON THE HOST, read
+ *   before the call returns).  One launch.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL required array (normals, masks optional; one of
+ * fallback and fill is required), a negative count, height or width outside [1, 32768], n_views height width >= 2^40, channels
+ * outside 1 .. 4, power outside 0 .. 8, a near that is not positive and finite, a depth_tol that is negative or not finite.
+ */
+#define LS2FM_MESH_COLORS_THREADS 256
+int ls2fm_mesh_vertex_colors(const float* verts, const float* normals, int64_t n_verts, const float* poses, const float* intr,
+                             int32_t n_views, int32_t height, int32_t width, int32_t channels, const float* images,
+                             const float* depth, const uint8_t* masks, float near, float depth_tol, int32_t power, double* sums,
+                             int32_t* count, void* stream);
+int ls2fm_mesh_vertex_colors_finish(const double* sums, const int32_t* count, int64_t n_verts, int32_t channels,
+                                    const float* fallback, const float* fill, float* color, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -18,6 +18,7 @@
 //   raster_resolve  one lane per pixel: unpack face_id and depth, recompute the winner's barycentrics, count the face's pixels.
 // ls2fm_mesh_mask_votes (one launch): mask_votes, one lane per vertex, the views in a loop.
 #include "ls2fm_device.h"
+#include "raster_project.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,46 +29,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxViewBlocks = 65535;          // gridDim.y; further views are taken by the kernels' view loops
 constexpr int64_t kClearBlocks = 1 << 16;       // raster_clear strides the z-buffer with at most this many workgroups
 constexpr unsigned long long kEmptyKey = ~0ull;
-
-// pose rows and intrinsics of one view.  The view index is uniform over the wave wherever this is called, so these are scalar
-// loads into scalar registers.
-struct View {
-    float p[12];
-    float fx, fy, cx, cy;
-};
-
-__device__ __forceinline__ View load_view(const float* __restrict__ poses, const float* __restrict__ intr, int view) {
-    View w;
-    const float* p = poses + (int64_t)view * 12;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) w.p[k] = p[k];
-    const float* q = intr + (int64_t)view * 4;
-    w.fx = q[0]; w.fy = q[1]; w.cx = q[2]; w.cy = q[3];
-    return w;
-}
-
-struct Projected {
-    float z, u, v;         // camera z and the image point
-    bool usable;
-};
-
-// camera point, projection and the usable rule.  Spelled with the rounded-operation intrinsics and compiled with contraction
-// off for this function, so the result does not depend on the build's -ffp-contract flag.
-__device__ __forceinline__ Projected project(const View& w, float x, float y, float z, float near) {
-#pragma clang fp contract(off)
-    float c[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        c[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w.p[4 * r], x), __fmul_rn(w.p[4 * r + 1], y)), __fmul_rn(w.p[4 * r + 2], z)),
-                         w.p[4 * r + 3]);
-    Projected o;
-    o.z = c[2];
-    o.u = __fadd_rn(__fmul_rn(w.fx, __fdiv_rn(c[0], c[2])), w.cx);
-    o.v = __fadd_rn(__fmul_rn(w.fy, __fdiv_rn(c[1], c[2])), w.cy);
-    // every comparison is false for a NaN; c_z = +inf fails the first
-    o.usable = fabsf(c[2]) < INFINITY && c[2] >= near && fabsf(o.u) <= 65536.0f && fabsf(o.v) <= 65536.0f;
-    return o;
-}
 
 __device__ __forceinline__ int snap(float u) { return (int)rintf(__fmul_rn(u, 256.0f)); }
 
@@ -245,14 +206,12 @@ mask_votes(const float* __restrict__ verts, int64_t n_verts, const float* __rest
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n_verts) return;
     const float x = verts[3 * i], y = verts[3 * i + 1], z = verts[3 * i + 2];
-    const float fw = (float)width, fh = (float)height;          // exact: at most 32768
     int n_seen = 0, n_inside = 0;
     for (int view = 0; view < n_views; ++view) {
         const View w = load_view(poses, intr, view);
         const Projected p = project(w, x, y, z, near);
-        if (p.usable && p.u >= 0.0f && p.u < fw && p.v >= 0.0f && p.v < fh) {
-            // 0 <= u < width in fp32 and width is an fp32 integer: floor(u) lies in [0, width - 1]; v likewise
-            const int px = (int)floorf(p.u), py = (int)floorf(p.v);
+        int px, py;
+        if (pixel_of(p, height, width, px, py)) {
             ++n_seen;
             n_inside += masks[((int64_t)view * height + py) * width + px] != 0;
         }
@@ -261,12 +220,9 @@ mask_votes(const float* __restrict__ verts, int64_t n_verts, const float* __rest
     inside[i] = n_inside;
 }
 
-bool image_ok(int32_t n_views, int32_t height, int32_t width) {
-    return n_views >= 0 && height >= 1 && height <= 32768 && width >= 1 && width <= 32768 &&
-           (int64_t)n_views * height * width < ((int64_t)1 << 40);
-}
+bool image_ok(int32_t n_views, int32_t height, int32_t width) { return raster_image_ok(n_views, height, width); }
 
-bool near_ok(float near) { return near > 0.0f && std::isfinite(near); }
+bool near_ok(float near) { return raster_near_ok(near); }
 
 }  // namespace
 

@@ -567,6 +567,16 @@ int ls2fm_launch_prep_sdf(const ls2fm_params* params, int n_levels, Packed* out,
     return ls2fm_launch_status();
 }
 
+// weight-norm + packing of everything a render reads (the three tasks the gather pass runs in its leading workgroups), as a
+// launch of its own: the point evaluator of radiance_points.hip has no gather pass to ride in
+int ls2fm_launch_prep_render(const ls2fm_params* params, int n_levels, int n_levels2, int dual, Packed* out, hipStream_t stream) {
+    ls2fm_prof_begin(LS2FM_PROF_PREP, stream);
+    prep_weights_kernel<<<3, kPrepThreads, 0, stream>>>(*params, 3 + 2 * n_levels, 3 + 2 * n_levels2,
+                                                        3 + 3 + kView + LS2FM_FEAT * (dual ? 2 : 1), dual, 1, out, nullptr);
+    ls2fm_prof_end(LS2FM_PROF_PREP, stream);
+    return ls2fm_launch_status();
+}
+
 // ------------------------------------------------------------------------------------------- C ABI
 static bool render_config_ok(const ls2fm_field_desc* field, const ls2fm_grid_desc* g1, const ls2fm_grid_desc* g2) {
     if (!field || !grid_desc_ok(g1)) return false;

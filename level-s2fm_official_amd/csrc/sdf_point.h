@@ -7,6 +7,7 @@
 
 // weight preparation (render_fwd.hip) and the normal query on prepared weights (sdf_eval.hip), shared with trace_image.hip
 int ls2fm_launch_prep_sdf(const ls2fm_params* params, int n_levels, Packed* out, hipStream_t stream, int32_t* zero_word = nullptr);
+int ls2fm_launch_prep_render(const ls2fm_params* params, int n_levels, int n_levels2, int dual, Packed* out, hipStream_t stream);
 int ls2fm_launch_sdf_normals(const ls2fm_field_desc* field, const ls2fm_grid_desc* grid, const Packed* pk, const float* table,
                              const float* p, int64_t n, int64_t n_query, float* sdf, float* normal, hipStream_t s);
 
@@ -90,6 +91,38 @@ __device__ __forceinline__ float lane_sdf(const LevelSet& lv, const FieldC& fc, 
     geometry_forward<false>(rec, u, f, dummy);
     bool bg;
     return signed_sdf(fc, bg_sdf, bg_rad, f[0], p, &bg);
+}
+
+// One lane: the analytic normal d sdf / d p (SDF.gradient, not normalised) from r = W0^T (s' w1_0) of geometry_forward<true>: a
+// second gather pass contracting the hash Jacobian with r, levels and corners in index order; the background sphere's normal
+// where signed_sdf selected it.  These are the statements of sdf_eval_kernel<true> (sdf_eval.hip), which keeps them inline: called
+// from there, the same statements cost that kernel 18 more VGPRs (120 for 102), and nothing measured says that is free.
+// tests/test_hip_radiance_points.py holds the two to the same bits with the thread-per-point kernel forced.
+__device__ __forceinline__ void lane_normal(const LevelSet& lv, const FieldC& fc, const float* __restrict__ table, const float p[3],
+                                            const float (&rr)[kInMax], bool bg, float (&nrm)[3]) {
+    float acc[3] = {0.f, 0.f, 0.f};
+    float x[3];
+    unit_cube(fc, p, x);
+#pragma unroll
+    for (int l = 0; l < LS2FM_MAX_LEVELS; ++l) {
+        if (l < lv.n_levels) {
+            Cell c;
+            locate(x, lv.scale[l], lv.res[l], lv.size[l], lv.offset[l], lv.hashed[l], c);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float2 v = *reinterpret_cast<const float2*>(table + 2ull * c.idx[k]);
+                const float m = fmaf(v.x, rr[3 + 2 * l], v.y * rr[4 + 2 * l]) * lv.scale[l];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) acc[a] = fmaf(corner_dweight(c.w, k, a), m, acc[a]);
+            }
+        }
+    }
+    const float len = sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float n = fc.kappa * (rr[a] / fc.rescale + acc[a] * fc.inv_ext[a]);
+        nrm[a] = bg ? -p[a] / len : n;
+    }
 }
 
 // f += w[J] * (lane J of this lane's 16-lane row).h for J = 0 .. 15, one fmaf chain; the broadcast is a DPP row_share operand

@@ -242,6 +242,12 @@ _SIGNATURES = {
     "ls2fm_image_compare_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "ls2fm_image_compare": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(ctypes.c_double), c_int32, ctypes.c_double,
                                       ctypes.c_double, _P, _P, _P, _P, _P, _P, c_int64, _P]),
+    "ls2fm_radiance_points_workspace_bytes": (c_int64, []),
+    "ls2fm_radiance_points": (c_int32, [POINTER(FieldDesc), POINTER(GridDesc), POINTER(GridDesc), POINTER(Params), _P, _P, c_int64, _P,
+                                        _P, _P, _P, _P]),
+    "ls2fm_mesh_vertex_colors": (c_int32, [_P, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_float, c_float,
+                                           c_int32, _P, _P, _P]),
+    "ls2fm_mesh_vertex_colors_finish": (c_int32, [_P, _P, c_int64, c_int32, _P, POINTER(c_float), _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

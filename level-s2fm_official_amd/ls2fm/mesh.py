@@ -178,18 +178,35 @@ def _as_numpy(a, dtype):
     return np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(-1, 3))
 
 
-def ply_header(n_verts: int, n_faces: int) -> bytes:
-    """the header plyfile writes for extract_mesh's two elements (binary, little endian)"""
-    return ("ply\nformat binary_little_endian 1.0\n"
-            f"element vertex {n_verts}\nproperty float x\nproperty float y\nproperty float z\n"
+_COLOR_NAMES = ("red", "green", "blue", "alpha")
+
+
+def _n_color_channels(colors) -> int:
+    """0 for None; else the channel count of a colour array [V, 3 | 4], or an int 3 | 4 itself"""
+    if colors is None:
+        return 0
+    n = int(colors) if isinstance(colors, (int, np.integer)) else (int(colors.shape[1]) if getattr(colors, "ndim", 0) == 2 else -1)
+    if n not in (3, 4):
+        raise ValueError(f"ply colours must have 3 (red green blue) or 4 (+ alpha) channels, got {colors if n >= 0 else 'a wrong shape'}")
+    return n
+
+
+def _header(fmt: str, n_verts: int, n_faces: int, colors) -> bytes:
+    color_lines = "".join(f"property uchar {name}\n" for name in _COLOR_NAMES[:_n_color_channels(colors)])
+    return (f"ply\nformat {fmt} 1.0\n"
+            f"element vertex {n_verts}\nproperty float x\nproperty float y\nproperty float z\n{color_lines}"
             f"element face {n_faces}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
 
 
-def ply_header_ascii(n_verts: int, n_faces: int) -> bytes:
-    """the header of write_ply(encoding="ascii"): the same two elements as the binary layout"""
-    return ("ply\nformat ascii 1.0\n"
-            f"element vertex {n_verts}\nproperty float x\nproperty float y\nproperty float z\n"
-            f"element face {n_faces}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
+def ply_header(n_verts: int, n_faces: int, colors=None) -> bytes:
+    """the header plyfile writes for extract_mesh's two elements (binary, little endian); colors (an array [V, 3 | 4] or the
+    channel count) adds `property uchar red green blue (alpha)` to the vertex element"""
+    return _header("binary_little_endian", n_verts, n_faces, colors)
+
+
+def ply_header_ascii(n_verts: int, n_faces: int, colors=None) -> bytes:
+    """the header of write_ply(encoding="ascii"): the same elements as the binary layout"""
+    return _header("ascii", n_verts, n_faces, colors)
 
 
 _ASCII_BLOCK = 1 << 16          # rows formatted per string operation
@@ -201,66 +218,124 @@ def _ascii_rows(fh, rows, fmt):
         fh.write(((fmt * len(block)) % tuple(block.ravel().tolist())).encode("ascii"))
 
 
-def write_ply(path, verts, faces, encoding: str = "binary") -> None:
+def color_bytes(colors, n_verts: int) -> np.ndarray:
+    """vertex colours [V, 3 | 4] (tensor or array) as the bytes write_ply stores: a uint8 array as it is, anything else
+    round(clip(c, 0, 1) * 255) with halves to even (a NaN becomes 0)"""
+    if isinstance(colors, torch.Tensor):
+        colors = colors.detach().cpu().numpy()
+    c = np.asarray(colors)
+    if c.ndim != 2 or c.shape[1] not in (3, 4) or c.shape[0] != n_verts:
+        raise ValueError(f"write_ply: colors must be [{n_verts}, 3] or [{n_verts}, 4], got shape {tuple(c.shape)}")
+    if c.dtype == np.uint8:
+        return np.ascontiguousarray(c)
+    with np.errstate(invalid="ignore"):
+        return np.rint(np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def _vertex_dtype(n_channels: int) -> np.dtype:
+    """one packed row of the binary vertex element"""
+    return np.dtype([("xyz", "<f4", (3,))] + ([("rgb", "u1", (n_channels,))] if n_channels else []))
+
+
+_FACE_DTYPE = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])      # packed: 13 bytes per face
+
+
+def write_ply(path, verts, faces, encoding: str = "binary", colors=None) -> None:
     """write verts [V, 3] / faces [F, 3] (tensors or arrays).
     encoding="binary": the layout extract_mesh's plyfile branch writes: binary_little_endian 1.0, `element vertex` of float
     x/y/z, `element face` of `property list uchar int vertex_indices`.
     encoding="ascii": the same elements as text (get_surface_high_res_mesh's export_ply(encoding='ascii')): one `x y z` line
-    per vertex with 9 significant digits (a float32 round-trips), one `3 a b c` line per face"""
+    per vertex with 9 significant digits (a float32 round-trips), one `3 a b c` line per face.
+    colors [V, 3] or [V, 4] in [0, 1] (color_bytes): `uchar red green blue` per vertex, a fourth channel `alpha`, what
+    trimesh reads into mesh.visual.vertex_colors.  None: the bytes written without the argument."""
     if encoding not in ("binary", "ascii"):
         raise ValueError(f"write_ply: encoding must be 'binary' or 'ascii', got {encoding!r}")
     v = _as_numpy(verts, "<f4")
     f = _as_numpy(faces, "<i4")
+    c = None if colors is None else color_bytes(colors, len(v))
     if encoding == "ascii":
         with open(path, "wb") as fh:
-            fh.write(ply_header_ascii(len(v), len(f)))
-            _ascii_rows(fh, v.astype(np.float64), "%.9g %.9g %.9g\n")
+            fh.write(ply_header_ascii(len(v), len(f), c))
+            if c is None:
+                _ascii_rows(fh, v.astype(np.float64), "%.9g %.9g %.9g\n")
+            else:
+                rows = np.concatenate([v.astype(np.float64), c.astype(np.float64)], axis=1)
+                _ascii_rows(fh, rows, "%.9g %.9g %.9g" + " %d" * c.shape[1] + "\n")
             _ascii_rows(fh, f, "3 %d %d %d\n")
         return
-    rows = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))      # packed: 13 bytes per face
+    rows = np.empty(len(f), dtype=_FACE_DTYPE)
     rows["n"] = 3
     rows["idx"] = f
     with open(path, "wb") as fh:
-        fh.write(ply_header(len(v), len(f)))
-        fh.write(v.tobytes())
+        fh.write(ply_header(len(v), len(f), c))
+        if c is None:
+            fh.write(v.tobytes())
+        else:
+            vrows = np.empty(len(v), dtype=_vertex_dtype(c.shape[1]))
+            vrows["xyz"] = v
+            vrows["rgb"] = c
+            fh.write(vrows.tobytes())
         fh.write(rows.tobytes())
 
 
-def read_ply(path):
-    """parse back a file of write_ply's layout (triangles only) -> (verts float32 [V, 3], faces int32 [F, 3])"""
+def _split_header(path, header_of, what):
+    """(data, end of header, n_verts, n_faces, n colour channels) of a file whose header is header_of(V, F, colours)"""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     lines = data[:end].decode("ascii").split("\n")
     n_verts = int(next(ln for ln in lines if ln.startswith("element vertex")).split()[2])
     n_faces = int(next(ln for ln in lines if ln.startswith("element face")).split()[2])
-    if ply_header(n_verts, n_faces) != data[:end]:
-        raise ValueError(f"{path}: not the layout write_ply writes")
-    v = np.frombuffer(data, dtype="<f4", count=3 * n_verts, offset=end).reshape(n_verts, 3)
-    rows = np.frombuffer(data, dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), count=n_faces, offset=end + 12 * n_verts)
+    for n_channels in (0, 3, 4):
+        if header_of(n_verts, n_faces, n_channels or None) == data[:end]:
+            return data, end, n_verts, n_faces, n_channels
+    raise ValueError(f"{path}: not the layout {what} writes")
+
+
+def _read_binary(path):
+    data, end, n_verts, n_faces, n_channels = _split_header(path, ply_header, "write_ply")
+    vdt = _vertex_dtype(n_channels)
+    vrows = np.frombuffer(data, dtype=vdt, count=n_verts, offset=end)
+    rows = np.frombuffer(data, dtype=_FACE_DTYPE, count=n_faces, offset=end + vdt.itemsize * n_verts)
     if n_faces and not (rows["n"] == 3).all():
         raise ValueError(f"{path}: a face that is not a triangle")
-    return v.copy(), rows["idx"].astype(np.int32).reshape(n_faces, 3)
+    colors = vrows["rgb"].copy().reshape(n_verts, n_channels) if n_channels else None
+    return vrows["xyz"].copy().reshape(n_verts, 3), rows["idx"].astype(np.int32).reshape(n_faces, 3), colors
+
+
+def _read_ascii(path):
+    data, end, n_verts, n_faces, n_channels = _split_header(path, ply_header_ascii, "write_ply(encoding='ascii')")
+    body = data[end:].split(b"\n")
+    if len(body) != n_verts + n_faces + 1 or body[-1] != b"":
+        raise ValueError(f"{path}: {len(body) - 1} rows, expected {n_verts} + {n_faces}")
+    width = 3 + n_channels
+    v = np.array(b" ".join(body[:n_verts]).split(), dtype=np.float64)
+    rows = np.array(b" ".join(body[n_verts:n_verts + n_faces]).split(), dtype=np.int64)
+    if v.size != width * n_verts or rows.size != 4 * n_faces:
+        raise ValueError(f"{path}: a row without three coordinates or a face that is not a triangle")
+    v = v.reshape(n_verts, width)
+    rows = rows.reshape(n_faces, 4)
+    if n_faces and not (rows[:, 0] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    colors = v[:, 3:].astype(np.uint8) if n_channels else None
+    return v[:, :3].astype(np.float32), rows[:, 1:].astype(np.int32), colors
+
+
+def read_ply(path):
+    """parse back a file of write_ply's layout (triangles only) -> (verts float32 [V, 3], faces int32 [F, 3]); vertex colours,
+    if the file has them, are skipped (read_ply_colors returns them)"""
+    return _read_binary(path)[:2]
 
 
 def read_ply_ascii(path):
     """parse back a file of write_ply(encoding="ascii")'s layout (triangles only) -> (verts float32 [V, 3], faces int32 [F, 3])"""
+    return _read_ascii(path)[:2]
+
+
+def read_ply_colors(path):
+    """a file of either layout of write_ply -> (verts float32 [V, 3], faces int32 [F, 3], colors uint8 [V, 3 | 4] or None)"""
     with open(path, "rb") as fh:
-        data = fh.read()
-    end = data.index(b"end_header\n") + len(b"end_header\n")
-    lines = data[:end].decode("ascii").split("\n")
-    n_verts = int(next(ln for ln in lines if ln.startswith("element vertex")).split()[2])
-    n_faces = int(next(ln for ln in lines if ln.startswith("element face")).split()[2])
-    if ply_header_ascii(n_verts, n_faces) != data[:end]:
-        raise ValueError(f"{path}: not the layout write_ply(encoding='ascii') writes")
-    body = data[end:].split(b"\n")
-    if len(body) != n_verts + n_faces + 1 or body[-1] != b"":
-        raise ValueError(f"{path}: {len(body) - 1} rows, expected {n_verts} + {n_faces}")
-    v = np.array(b" ".join(body[:n_verts]).split(), dtype=np.float64).astype(np.float32)
-    rows = np.array(b" ".join(body[n_verts:n_verts + n_faces]).split(), dtype=np.int64)
-    if v.size != 3 * n_verts or rows.size != 4 * n_faces:
-        raise ValueError(f"{path}: a row without three coordinates or a face that is not a triangle")
-    rows = rows.reshape(n_faces, 4)
-    if n_faces and not (rows[:, 0] == 3).all():
-        raise ValueError(f"{path}: a face that is not a triangle")
-    return v.reshape(n_verts, 3), rows[:, 1:].astype(np.int32)
+        ascii_file = fh.read(64).startswith(b"ply\nformat ascii")
+    return _read_ascii(path) if ascii_file else _read_binary(path)
+
+

@@ -135,7 +135,7 @@ def _high_res_device(sdf, resolution, grid_boundary, level, take_components):
 
 
 def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), level=0, take_components=True, path=None,
-                              backend="auto"):
+                              backend="auto", colors=None, rad_field=None):
     """utils/plots.py:140-222, same arguments.  The two SDF sweeps are device passes (see module docstring).
     backend: "trimesh" = the reference's scikit-image + trimesh steps (ImportError without them; returns a Trimesh);
     "device" = ls2fm.mesh: marching cubes on the coarse volume, its largest component by area (take_components), 10 000
@@ -143,12 +143,19 @@ def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), le
     ls2fm.mesh.Mesh of device tensors, or None (nothing written) when the fitted volume has no crossing.  A coarse volume
     without a crossing raises ValueError (as skimage does), and so does a fitted lattice marching cubes refuses.
     "auto" = "trimesh" when both packages import, else "device".
+    colors (device backend): None = bare geometry, the bytes written without the argument; "field" = the radiance field
+    `rad_field` at the vertices, `sdf` being a method of its SDF field (ls2fm.mesh_colors.field_colors); a callable
+    (verts, faces) -> colours [V, 3 | 4] in [0, 1].  The colours go into the PLY at `path`.
     Intended differences of the device path: the surface samples come from torch's generator (reproducible under
     torch.manual_seed) instead of numpy's global one; marching cubes uses its own case table (ls2fm.mesh.marching_cubes);
     trimesh merges vertices on construction, which only differs where a lattice value equals `level` exactly; the PLY
     carries no normals, as the reference's (skimage's vertex normals land in Trimesh's face_normals argument)."""
     if backend not in ("auto", "device", "trimesh"):
         raise ValueError(f"get_surface_high_res_mesh: backend must be 'auto', 'device' or 'trimesh', got {backend!r}")
+    if colors is not None and backend == "trimesh":
+        raise ValueError("get_surface_high_res_mesh(colors=...) writes vertex colours on backend='device' only")
+    if backend == "auto" and colors is not None:
+        backend = "device"
     if backend == "auto":
         try:
             import skimage.measure  # noqa: F401
@@ -157,10 +164,12 @@ def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), le
         except ImportError:
             backend = "device"
     if backend == "device":
-        from .. import mesh
+        from .. import mesh, mesh_colors
         result, _ = _high_res_device(sdf, resolution, grid_boundary, level, take_components)
         if path is not None and result is not None:
-            mesh.write_ply(path, result.vertices, result.faces, encoding="ascii")
+            c = mesh_colors.resolve_colors(colors, result.vertices, result.faces, getattr(sdf, "__self__", None), rad_field,
+                                           "get_surface_high_res_mesh")
+            mesh.write_ply(path, result.vertices, result.faces, encoding="ascii", colors=c)
         return result
     try:
         from skimage import measure

@@ -53,17 +53,24 @@ def lattice_points(volume_size=2.0, N=512, bound_max=None, bound_min=None, first
 
 
 def extract_mesh(implicit_surface, log=None, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply",
-                 show_progress=True, chunk=16 * 1024, bound_max=None, bound_min=None, extra_info=None, backend="auto"):
+                 show_progress=True, chunk=16 * 1024, bound_max=None, bound_min=None, extra_info=None, backend="auto",
+                 colors=None, rad_field=None):
     """utils/util.py:392-425.  `chunk` and `show_progress` are accepted and unused (one device call).
     backend: "skimage" = the reference's scikit-image + plyfile branch (ImportError without them); "device" = ls2fm.mesh
     (marching cubes on the GPU, numpy PLY writer); "auto" = "skimage" when both packages import, else "device".  Both apply
-    the reference's spacing size / N (the lattice step is size / (N - 1)) and origin to the vertices.  Returns the volume."""
+    the reference's spacing size / N (the lattice step is size / (N - 1)) and origin to the vertices.  Returns the volume.
+    colors (device backend): None = bare geometry, the bytes written without the argument; "field" = the radiance field
+    `rad_field` at the vertices (ls2fm.mesh_colors.field_colors); a callable (verts, faces) -> colours [V, 3 | 4] in [0, 1]."""
     if backend not in ("auto", "device", "skimage"):
         raise ValueError(f"extract_mesh: backend must be 'auto', 'device' or 'skimage', got {backend!r}")
     if extra_info is not None:
         raise NotImplementedError("extract_mesh(extra_info=...): residual fields are outside the fused path")
+    if colors is not None and backend == "skimage":
+        raise ValueError("extract_mesh(colors=...) writes vertex colours on backend='device' only")
     vol = sdf_volume(implicit_surface, volume_size, N, bound_max, bound_min)
     _, _, origin, sizes = _lattice(volume_size, N, bound_max, bound_min)
+    if backend == "auto" and colors is not None:
+        backend = "device"
     if backend == "auto":
         try:
             import skimage.measure  # noqa: F401
@@ -72,9 +79,10 @@ def extract_mesh(implicit_surface, log=None, volume_size=2.0, level=0.0, N=512, 
         except ImportError:
             backend = "device"
     if backend == "device":
-        from .. import mesh
+        from .. import mesh, mesh_colors
         verts, faces = mesh.marching_cubes(vol, level=level, spacing=[float(v) / N for v in sizes], origin=origin)
-        mesh.write_ply(filepath, verts, faces)
+        mesh.write_ply(filepath, verts, faces,
+                       colors=mesh_colors.resolve_colors(colors, verts, faces, implicit_surface, rad_field, "extract_mesh"))
         if log is not None:
             log.info("saving mesh to %s" % str(filepath))
         return vol
