@@ -1506,6 +1506,46 @@ int ls2fm_mesh_vertex_colors_finish(const double* sums, const int32_t* count, in
                                     const float* fallback, const float* fill, float* color, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TSDF fusion of posed depth maps into a dense volume (csrc/tsdf_fusion.hip behind ls2fm.fusion.integrate; an addition, the
+ * library stays ABI 13): the way back from depth maps -- ls2fm_rasterize's, ls2fm_trace_image's, a sensor's -- to a surface.
+ * The reference ships none.  tests/fusion_restate.py repeats the rule in numpy.
+ *
+ * The volume: nx x ny x nz lattice points, row-major with axis 2 fastest, as ls2fm_marching_cubes_* takes it.  Lattice point i
+ * sits at X[a] = fl32(fl32((float) i[a] * voxel) + origin[a]): the vertex expression of ls2fm_marching_cubes_emit with
+ * spacing = (voxel, voxel, voxel), so the mesh extracted from the volume is in the depth maps' world frame as it stands.
+ * The caller owns the state tsdf float [nx][ny][nz] and weight float [nx][ny][nz], both zero for a fresh volume.
+ * Inputs: depth float [N][H][W], camera z pixel for pixel (the convention of ls2fm_rasterize's depth); poses float [N][3][4] and
+ * intr float [N][4] as for ls2fm_rasterize; view_weight float [N] or NULL (every view weighs 1); near, trunc, voxel > 0;
+ * max_depth > 0 and max_weight > 0, either may be +inf; origin: 3 floats in HOST memory, read before the call returns.
+ * THE FUSION RULE, per lattice point X and view v, the views in index order, every operation one rounded fp32 operation, none
+ * contracted:
+ *   1. pixel     camera point c, projection (u, v), usable and IN THE IMAGE by the RASTERISATION RULE and ls2fm_mesh_mask_votes'
+ *      rule above (csrc/raster_project.h): the point lands on the pixel (floor u, floor v) on which the rasteriser would put a
+ *      vertex at X.  Otherwise the view is skipped.
+ *   2. depth     d = depth[v][py][px]: the nearest pixel, no interpolation.  Skipped unless d is finite, d > 0 and
+ *      d <= max_depth: the rasteriser's empty pixels (+inf), a tracer's misses, a sensor's zeros and NaN all skip.
+ *   3. weight    w = view_weight[v], or 1.  Skipped unless w > 0 (false for a NaN).
+ *   4. distance  s = d - c_z: projective, along camera z, not along the ray.  Skipped if s < -trunc; s == -trunc counts.
+ *   5. value     val = fminf(1, s / trunc).
+ *   6. Wn = W + w;   7. T = ((W T) + (w val)) / Wn;   8. W = fminf(Wn, max_weight).
+ * One lane takes one lattice point (a workgroup a brick of LS2FM_TSDF_BRICK_X x _Y x _Z points, consecutive lanes along axis
+ * 2), loads its T and W once, walks the views and stores them once: no atomic, and a call over views 0 .. k followed by a call
+ * over views k + 1 .. N - 1 leaves the bits of one call over all of them; a rerun and a graph replay repeat the bits.  One
+ * launch, no workspace, no allocation, nothing read back, no stream forked: the call can be captured.  A volume with a side of
+ * 0 and n_views = 0 return at once.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL required array (view_weight is optional), a negative
+ * side or one above 2^24 (the index converts to fp32 exactly), 2^31 bricks or more, height or width outside [1, 32768],
+ * n_views height width >= 2^40, near, trunc or voxel not positive and finite, max_depth or max_weight not positive (a NaN is
+ * not), an origin that is not finite.
+ */
+#define LS2FM_TSDF_BRICK_X 2
+#define LS2FM_TSDF_BRICK_Y 2
+#define LS2FM_TSDF_BRICK_Z 64
+int ls2fm_tsdf_integrate(float* tsdf, float* weight, int64_t nx, int64_t ny, int64_t nz, const float* origin, float voxel,
+                         float trunc, const float* depth, const float* poses, const float* intr, const float* view_weight,
+                         int32_t n_views, int32_t height, int32_t width, float near, float max_depth, float max_weight, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -248,6 +248,8 @@ _SIGNATURES = {
     "ls2fm_mesh_vertex_colors": (c_int32, [_P, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_float, c_float,
                                            c_int32, _P, _P, _P]),
     "ls2fm_mesh_vertex_colors_finish": (c_int32, [_P, _P, c_int64, c_int32, _P, POINTER(c_float), _P, _P]),
+    "ls2fm_tsdf_integrate": (c_int32, [_P, _P, c_int64, c_int64, c_int64, POINTER(c_float), c_float, c_float, _P, _P, _P, _P, c_int32,
+                                       c_int32, c_int32, c_float, c_float, c_float, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

@@ -1,0 +1,251 @@
+"""TSDF fusion on the device: from a set of posed depth maps back to a surface.
+
+  TsdfVolume   a dense truncated-signed-distance volume and its weights, owned by the caller
+  integrate    fuse depth maps [V, H, W] into a volume (ls2fm_tsdf_integrate, csrc/tsdf_fusion.hip): one launch, no host read
+  extract      the mesh of the volume's zero level over the observed lattice points (ls2fm.mesh.marching_cubes)
+  fuse_mesh    ls2fm.raster.rasterize -> integrate -> extract: the re-fusion step of the ScanNet protocol of the neural-surface
+               papers (Manhattan-SDF, MonoSDF, NeuRIS).  The predicted mesh is rendered to depth at every test camera, the depth
+               maps are fused and the re-fused mesh goes into ls2fm.metrics.evaluate_mesh: what no camera observes is removed,
+               by the same rule on both sides.  ls2fm.raster.clean_mesh(visibility=True) is the DTU counterpart.
+  fuse_field   the same from ls2fm.image.trace_image's depth of the SDF field, to set beside extract_mesh
+
+The three producers of depth maps in the library -- raster.rasterize, image.trace_image and the sensor depth a ScanNet loader
+reads -- share one convention: camera z, pixel for pixel (see raster.rasterize).  THE FUSION RULE is stated in include/ls2fm.h and
+restated in numpy in tests/fusion_restate.py: a lattice point lands on the pixel on which the rasteriser would put a vertex there
+(csrc/raster_project.h), takes that pixel's depth d, and with s = d - c_z >= -trunc extends its running average by
+min(1, s / trunc) at the view's weight; every operation is one rounded fp32 operation, the views go in index order, one lane per
+lattice point and no atomics.  So views split over several calls leave the bits of one call, and a rerun or a replay of a
+captured graph repeats them.
+
+Deviations from what fusion packages (Open3D, KinectFusion and their kin) do, on purpose: the distance is projective along camera
+z, not along the ray; the depth is the nearest pixel's, not interpolated; the volume is dense (no hashing, no sparse bricks: 8
+bytes per lattice point); and extract keeps the faces of a cell with an unobserved corner whose three vertices lie on observed
+edges, where Open3D drops such cells whole.  Masks are the caller's business: one torch.where that writes +inf into the depth.
+Colour is not part of the volume: ls2fm.mesh_colors.photo_colors colours any mesh from the photographs, the fused one included.
+
+There is no CPU path: CPU tensors, a missing device or a missing library raise, as in ls2fm.raster.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from . import _lib, mesh, raster
+from ._lib import check, ptr, stream_ptr
+
+TRUNC_VOXELS = 3.0          # the default truncation distance, in voxels
+
+
+class TsdfVolume:
+    """A dense TSDF volume: tsdf and weight float32 [nx, ny, nz] on `device`, zero when fresh.  Lattice point i sits at
+    (float32) i * voxel + origin per axis -- marching cubes' vertex expression with spacing = (voxel,) * 3 -- so the extracted
+    mesh is in the depth maps' world frame.  shape: three ints, each >= 2 for extract; origin: three floats; voxel and trunc
+    positive and finite."""
+
+    def __init__(self, shape, origin, voxel, trunc, device):
+        shape = tuple(int(s) for s in shape)
+        origin = tuple(float(v) for v in origin)
+        voxel, trunc = float(voxel), float(trunc)
+        if len(shape) != 3 or min(shape) < 0 or max(shape) > 2 ** 24:
+            raise ValueError(f"ls2fm.fusion.TsdfVolume: shape {shape} must be three sides in [0, 2^24]")
+        if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+            raise ValueError(f"ls2fm.fusion.TsdfVolume: origin {origin} must be three finite floats")
+        if not (0.0 < voxel < math.inf and 0.0 < trunc < math.inf):
+            raise ValueError(f"ls2fm.fusion.TsdfVolume: voxel {voxel} and trunc {trunc} must be positive and finite")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ls2fm.fusion: TSDF fusion runs on MI355X only (got a CPU device); there is no CPU fallback")
+        self.shape, self.origin, self.voxel, self.trunc = shape, origin, voxel, trunc
+        self.tsdf = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.weight = torch.zeros(shape, dtype=torch.float32, device=device)
+
+    @property
+    def device(self):
+        return self.tsdf.device
+
+
+def _depth_maps(depth, n, H, W):
+    depth = torch.as_tensor(depth)
+    raster._device(depth)
+    if depth.dim() == 3 and depth.shape[2] == 1 and H is not None and W is not None and depth.shape[1] == int(H) * int(W):
+        depth = depth.reshape(depth.shape[0], int(H), int(W))               # [V, H W, 1], as ls2fm.image.trace_image returns it
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3 or depth.shape[0] != n or (H is not None and int(H) != depth.shape[1]) or (W is not None and int(W) != depth.shape[2]):
+        raise ValueError(f"ls2fm.fusion.integrate: depth must be [{n}, H, W] (or [{n}, H W, 1] with H= and W=), got {tuple(depth.shape)}")
+    return _lib.cf(depth.detach())
+
+
+@torch.no_grad()
+def integrate(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=math.inf, view_weight=None, max_weight=math.inf,
+              H=None, W=None):
+    """Fuse V depth maps into `volume` in place (THE FUSION RULE of include/ls2fm.h) -> volume.
+      depth        float32 [V, H, W], camera z pixel for pixel; [V, H W, 1] as ls2fm.image.trace_image returns it is taken too,
+                   with H= and W=.  A pixel that is not finite, not positive or above max_depth is not used: the rasteriser's
+                   empty pixels (+inf), a tracer's misses, a sensor's zeros.  Masks: torch.where(mask, depth, inf) by the caller.
+      pose, intr   [V, 3, 4] world-to-camera and [3, 3] or [V, 3, 3], as ls2fm.raster.rasterize
+      view_weight  float [V] or None (every view weighs 1); a view whose weight is not > 0 is skipped
+      max_weight   the weight saturates there: later views then move the average at 1 / max_weight at least
+    One launch, no host read and no allocation beyond the argument conversions: the call can be captured.  The views of several
+    calls, in order, leave the bits of one call over all of them."""
+    lib = _lib.load()
+    poses, k4 = raster._views(pose, intr, "integrate")
+    n = int(poses.shape[0])
+    d = _depth_maps(depth, n, H, W)
+    dev = volume.device
+    vw = None
+    if view_weight is not None:
+        vw = torch.as_tensor(view_weight)
+        raster._device(vw)
+        vw = _lib.cf(vw.detach().reshape(-1))
+        if vw.shape[0] != n:
+            raise ValueError(f"ls2fm.fusion.integrate: {vw.shape[0]} view weights for {n} views")
+    for t in (poses, d, vw):
+        if t is not None and t.device != dev:
+            raise ValueError(f"ls2fm.fusion.integrate: the volume on {dev}, another argument on {t.device}")
+    near = raster._near(near, "integrate")
+    max_depth, max_weight = float(max_depth), float(max_weight)
+    if not (max_depth > 0.0 and max_weight > 0.0):
+        raise ValueError(f"ls2fm.fusion.integrate: max_depth {max_depth} and max_weight {max_weight} must be positive (inf is allowed)")
+    if not (volume.tsdf.is_contiguous() and volume.weight.is_contiguous() and volume.tsdf.dtype == volume.weight.dtype == torch.float32
+            and tuple(volume.tsdf.shape) == tuple(volume.weight.shape) == volume.shape):
+        raise ValueError("ls2fm.fusion.integrate: the volume's tsdf and weight must be contiguous float32 of the volume's shape")
+    origin = (ctypes.c_float * 3)(*volume.origin)
+    with torch.cuda.device(dev):
+        check(lib.ls2fm_tsdf_integrate(ptr(volume.tsdf), ptr(volume.weight), *volume.shape, origin, volume.voxel, volume.trunc, ptr(d),
+                                       ptr(poses), ptr(k4), ptr(vw), n, int(d.shape[1]), int(d.shape[2]), near, max_depth, max_weight,
+                                       stream_ptr()), "ls2fm_tsdf_integrate")
+    return volume
+
+
+@torch.no_grad()
+def integrate_torch(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=math.inf, view_weight=None, max_weight=math.inf):
+    """THE FUSION RULE as plain torch ops on the volume's device, vectorised over the lattice points, the views in a loop: the
+    same operations in the same order, each a separate op, so each rounds once.  It reads and writes the whole volume once per
+    view and per op.  The timing baseline (tools/time_fusion.py) and a check of the kernel; nothing in the library falls back
+    to it.  view_weight: a sequence of floats or None.  -> volume"""
+    dev = volume.device
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(dev)
+    n = int(P.shape[0])
+    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3).float().to(dev).expand(n, 3, 3)
+    depth = torch.as_tensor(depth).detach().float().to(dev)
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    axes = [torch.arange(s, device=dev).float() * volume.voxel + o for s, o in zip(volume.shape, volume.origin)]
+    x, y, z = (t.reshape(-1) for t in torch.meshgrid(*axes, indexing="ij"))
+    T, Wt = volume.tsdf.view(-1), volume.weight.view(-1)
+    # 0-dim device tensors: a division by a Python scalar would be a multiplication by its reciprocal
+    scalar = lambda t: torch.tensor(float(t), dtype=torch.float32, device=dev)
+    trunc, one, max_w = scalar(volume.trunc), scalar(1.0), scalar(max_weight)
+    for i in range(n):
+        w = 1.0 if view_weight is None else float(view_weight[i])
+        if not w > 0.0:
+            continue
+        w = scalar(w)
+        c = [((P[i, r, 0] * x + P[i, r, 1] * y) + P[i, r, 2] * z) + P[i, r, 3] for r in range(3)]
+        u = K[i, 0, 0] * (c[0] / c[2]) + K[i, 0, 2]
+        v = K[i, 1, 1] * (c[1] / c[2]) + K[i, 1, 2]
+        ok = torch.isfinite(c[2]) & (c[2] >= near) & (u.abs() <= 65536.0) & (v.abs() <= 65536.0)
+        ok = ok & (u >= 0) & (u < W) & (v >= 0) & (v < H)
+        px = torch.where(ok, u.floor(), torch.zeros_like(u)).long()
+        py = torch.where(ok, v.floor(), torch.zeros_like(v)).long()
+        d = depth[i].reshape(-1)[py * W + px]
+        ok = ok & torch.isfinite(d) & (d > 0) & (d <= max_depth)
+        s = d - c[2]
+        ok = ok & ~(s < -trunc)
+        val = torch.fmin(one, s / trunc)
+        Wn = Wt + w
+        Tn = (Wt * T + w * val) / Wn
+        T.copy_(torch.where(ok, Tn, T))
+        Wt.copy_(torch.where(ok, torch.fmin(Wn, max_w), Wt))
+    return volume
+
+
+@torch.no_grad()
+def extract(volume: TsdfVolume, min_weight=1.0) -> mesh.Mesh:
+    """The mesh of the volume's zero level -> ls2fm.mesh.Mesh, in the depth maps' world frame, normals toward the cameras.
+    A lattice point of weight < min_weight is unobserved: its value becomes NaN, which marching cubes' rule reads as "not below",
+    so an edge from a below corner to an unobserved one gets a NaN vertex.  Every face with a non-finite vertex coordinate is
+    dropped, then the vertices no face uses, both in their order, with torch ops.  A cell with an unobserved corner keeps the faces
+    whose three vertices lie on observed edges (Open3D drops such cells whole).  Host reads: marching cubes' counts, and the sizes
+    of the result."""
+    with torch.cuda.device(volume.device):
+        vol = torch.where(volume.weight >= float(min_weight), volume.tsdf, torch.full_like(volume.tsdf, math.nan))
+        verts, faces = mesh.marching_cubes(vol, 0.0, spacing=(volume.voxel,) * 3, origin=volume.origin)
+        good = torch.isfinite(verts).all(dim=1)
+        keep = good[faces.long()].all(dim=1) if faces.shape[0] else torch.zeros(0, dtype=torch.bool, device=verts.device)
+        return mesh.select_faces(verts, faces, keep)
+
+
+def volume_for(bounds, voxel, trunc=None, device="cuda") -> TsdfVolume:
+    """a fresh volume whose lattice covers bounds = ((x0, y0, z0), (x1, y1, z1)): origin at the low corner, per axis
+    ceil((high - low) / voxel) + 1 points, at least 2.  trunc defaults to TRUNC_VOXELS = 3 voxels."""
+    lo, hi = ([float(v) for v in b] for b in bounds)
+    voxel = float(voxel)
+    if not 0.0 < voxel < math.inf or not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError(f"ls2fm.fusion: voxel {voxel} must be positive and finite, and the bounds {lo} .. {hi} finite")
+    shape = [max(2, int(math.ceil((h - l) / voxel)) + 1) for l, h in zip(lo, hi)]
+    return TsdfVolume(shape, lo, voxel, TRUNC_VOXELS * voxel if trunc is None else trunc, device)
+
+
+def _intr_of(K, s, e):
+    return K if K.shape[0] == 1 else K[s:e]
+
+
+@torch.no_grad()
+def fuse_mesh(verts, faces, pose, intr, H, W, voxel, trunc=None, bounds=None, near=1e-3, max_depth=math.inf, min_weight=1.0,
+              max_weight=math.inf, max_workspace_bytes=2 ** 28, return_volume=False):
+    """Render a mesh to depth at every camera, fuse the depth maps and extract: ls2fm.raster.rasterize -> integrate -> extract.
+    The re-fusion step of the ScanNet evaluation protocol; the result goes straight into ls2fm.metrics.evaluate_mesh.
+      verts, faces, pose, intr, H, W, near   as ls2fm.raster.rasterize
+      voxel        the lattice spacing;  trunc  the truncation distance, default 3 voxels (TRUNC_VOXELS)
+      bounds       ((x0, y0, z0), (x1, y1, z1)) of the volume; default: the mesh's box grown by trunc, which costs one host
+                   read (the box) -- give bounds to avoid it
+    The views go in chunks whose z-buffer stays within max_workspace_bytes (at least one view per chunk), one rasterisation and
+    one ls2fm_tsdf_integrate launch per chunk; the chunking does not show in the result.
+    -> ls2fm.mesh.Mesh, with return_volume (Mesh, TsdfVolume)."""
+    v, f = raster._mesh(verts, faces, "fuse_mesh")
+    poses, _ = raster._views(pose, intr, "fuse_mesh")
+    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3)
+    H, W, voxel = int(H), int(W), float(voxel)
+    trunc = TRUNC_VOXELS * voxel if trunc is None else float(trunc)
+    if bounds is None:
+        if not v.shape[0]:
+            raise ValueError("ls2fm.fusion.fuse_mesh: an empty mesh has no box; give bounds")
+        lo, hi = (t.tolist() for t in torch.stack([v.amin(dim=0), v.amax(dim=0)]).cpu())
+        bounds = ([t - trunc for t in lo], [t + trunc for t in hi])
+    volume = volume_for(bounds, voxel, trunc, v.device)
+    n = int(poses.shape[0])
+    per_chunk = max(1, int(max_workspace_bytes) // (8 * H * W))
+    for s in range(0, n, per_chunk):
+        e = min(s + per_chunk, n)
+        k = _intr_of(K, s, e)
+        depth = raster.rasterize(v, f, poses[s:e], k, H, W, near=near, max_workspace_bytes=max_workspace_bytes).depth
+        integrate(volume, depth, poses[s:e], k, near=near, max_depth=max_depth, max_weight=max_weight)
+    out = extract(volume, min_weight)
+    return (out, volume) if return_volume else out
+
+
+@torch.no_grad()
+def fuse_field(sdf_field, pose, intr, H, W, voxel, bounds, trunc=None, near=1e-3, max_depth=math.inf, min_weight=1.0,
+               max_weight=math.inf, max_workspace_bytes=2 ** 28, return_volume=False):
+    """fuse_mesh's steps from the SDF field's own depth: ls2fm.image.trace_image -> integrate -> extract, a cross-check of the
+    field against its depth maps to set beside extract_mesh.  A pixel whose ray did not `finish` (no surface found) is set to
+    +inf and so not used.  pose [V, 3, 4], intr [3, 3] as trace_image takes them; bounds is required (a field has no box of its
+    own here).  The views go in chunks whose traced maps (40 bytes per pixel) stay within max_workspace_bytes.
+    -> ls2fm.mesh.Mesh, with return_volume (Mesh, TsdfVolume)."""
+    from . import image
+    poses = torch.as_tensor(pose).reshape(-1, 3, 4)
+    raster._device(poses)
+    H, W = int(H), int(W)
+    volume = volume_for(bounds, voxel, trunc, poses.device)
+    n = int(poses.shape[0])
+    per_chunk = max(1, int(max_workspace_bytes) // (40 * H * W))
+    for s in range(0, n, per_chunk):
+        e = min(s + per_chunk, n)
+        t = image.trace_image(sdf_field, poses[s:e], intr, H, W)
+        depth = torch.where(t.finish, t.depth[..., 0], torch.full_like(t.depth[..., 0], math.inf)).view(e - s, H, W)
+        integrate(volume, depth, poses[s:e], intr, near=near, max_depth=max_depth, max_weight=max_weight)
+    out = extract(volume, min_weight)
+    return (out, volume) if return_volume else out

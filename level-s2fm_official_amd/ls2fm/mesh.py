@@ -55,6 +55,16 @@ class Mesh(NamedTuple):
     faces: torch.Tensor
 
 
+def select_faces(verts: torch.Tensor, faces: torch.Tensor, keep: torch.Tensor) -> Mesh:
+    """the faces with keep (bool [F]) set, the vertices no kept face uses dropped and the faces re-indexed, both in their order,
+    with torch ops: the compaction that ends ls2fm.raster.clean_mesh and ls2fm.fusion.extract"""
+    kept = faces.long()[keep]
+    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+    used[kept.reshape(-1)] = True
+    renumber = torch.cumsum(used.to(torch.int64), dim=0) - 1
+    return Mesh(verts[used], renumber[kept].to(torch.int32))
+
+
 def _check_mesh(verts, faces, what):
     """device-only and [., 3] shapes"""
     if not faces.is_cuda or (verts is not None and not verts.is_cuda):

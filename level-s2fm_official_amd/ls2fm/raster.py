@@ -205,11 +205,7 @@ def clean_mesh(verts, faces, pose, intr, masks=None, H=None, W=None, dilate=0, m
             if H is None or W is None:
                 raise ValueError("ls2fm.raster.clean_mesh: visibility needs the image size (H, W) when no masks give it")
             keep_f = keep_f & (rasterize(v, f, pose, intr, H, W, near=near, hits=True).face_hits >= int(min_pixels))
-        kept = idx[keep_f]
-        used = torch.zeros(v.shape[0], dtype=torch.bool, device=dev)
-        used[kept.reshape(-1)] = True
-        renumber = torch.cumsum(used.to(torch.int64), dim=0) - 1
-        out = mesh.Mesh(v[used], renumber[kept].to(torch.int32))
+        out = mesh.select_faces(v, f, keep_f)
         if keep_largest:
             out = mesh.largest_component(out.vertices, out.faces)
     return out, keep_f
