@@ -332,6 +332,27 @@ def require_device(*tensors) -> None:
             raise RuntimeError(f"ls2fm: unsupported dtype {t.dtype}")
 
 
+def require_device_tensors(module: str, *tensors, phrase: str = ": runs on MI355X only", more: str = "") -> None:
+    """the guard of a module without a CPU path, in its own words ("ls2fm.pose" + phrase ... + more); None entries are skipped"""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{module}{phrase} (got a CPU tensor); there is no CPU fallback{more}")
+
+
+def find_device(module: str, items=()) -> torch.device:
+    """the device of the first device tensor among `items`, else the current device; without any device the module refuses"""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{module}: runs on MI355X only (no device found); there is no CPU fallback")
+    return next((i.device for i in items if torch.is_tensor(i) and i.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+
+
+def raise_status(status, prefix: str, table: dict) -> None:
+    """the status word a device call left (int32 [1]; one host read): ValueError naming every bit of `table` that is set"""
+    code = int(status.item())
+    if code:
+        raise ValueError(f"{prefix}: " + "; ".join(msg for bit, msg in table.items() if code & bit))
+
+
 def cf(t: torch.Tensor) -> torch.Tensor:
     """contiguous float32 view/copy"""
     if t.dtype != torch.float32:

@@ -65,12 +65,6 @@ def _grey(image, dev):
     return t.contiguous()
 
 
-def _device(images):
-    if not torch.cuda.is_available():
-        raise RuntimeError("ls2fm.features: runs on MI355X only (no device found); there is no CPU fallback")
-    return next((i.device for i in images if torch.is_tensor(i) and i.is_cuda), torch.device("cuda", torch.cuda.current_device()))
-
-
 def _call(greys, opt, dev, debug=False, with_keys=False):
     """one ls2fm_sift_extract call -> (keypoints [V * max,4], descriptors [V * max,128], counts [V] on the device, levels or None,
     packed keys [V * max,2] or None)"""
@@ -122,7 +116,7 @@ def extract(images, options=None, return_keys=False):
     if len(images) == 0:
         raise ValueError("ls2fm.features: no images")
     opt = options or SiftOptions()
-    dev = _device(images)
+    dev = _lib.find_device("ls2fm.features", images)
     greys = [_grey(i, dev) for i in images]
     step = len(greys) if not opt.chunk_views else max(int(opt.chunk_views), 1)
     parts = [_call(greys[a:a + step], opt, dev, with_keys=return_keys) for a in range(0, len(greys), step)]
@@ -147,7 +141,7 @@ def extract(images, options=None, return_keys=False):
 def gaussian_levels(image, options=None):
     """debug entry: the Gaussian levels the extraction of ONE image builds -> list over octaves of float32 [6,h,w] device tensors"""
     opt = options or SiftOptions()
-    dev = _device([image])
+    dev = _lib.find_device("ls2fm.features", [image])
     return _call([_grey(image, dev)], opt, dev, debug=True)[3]
 
 

@@ -28,14 +28,16 @@ There is no CPU path: CPU tensors, a missing device or a missing library raise, 
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 
 import torch
 
-from . import _lib, mesh, raster
+from . import _lib, _posed, mesh, raster
 from ._lib import check, ptr, stream_ptr
 
 TRUNC_VOXELS = 3.0          # the default truncation distance, in voxels
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.fusion", phrase=": TSDF fusion runs on MI355X only")
 
 
 class TsdfVolume:
@@ -67,8 +69,6 @@ class TsdfVolume:
 
 
 def _depth_maps(depth, n, H, W):
-    depth = torch.as_tensor(depth)
-    raster._device(depth)
     if depth.dim() == 3 and depth.shape[2] == 1 and H is not None and W is not None and depth.shape[1] == int(H) * int(W):
         depth = depth.reshape(depth.shape[0], int(H), int(W))               # [V, H W, 1], as ls2fm.image.trace_image returns it
     if depth.dim() == 2:
@@ -90,22 +90,26 @@ def integrate(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=math.i
       max_weight   the weight saturates there: later views then move the average at 1 / max_weight at least
     One launch, no host read and no allocation beyond the argument conversions: the call can be captured.  The views of several
     calls, in order, leave the bits of one call over all of them."""
-    lib = _lib.load()
-    poses, k4 = raster._views(pose, intr, "integrate")
+    depth, vw = torch.as_tensor(depth), None if view_weight is None else torch.as_tensor(view_weight)
+    _device(depth, vw)
+    poses, k4 = _posed.views(pose, intr, "ls2fm.fusion.integrate")
     n = int(poses.shape[0])
     d = _depth_maps(depth, n, H, W)
-    dev = volume.device
-    vw = None
-    if view_weight is not None:
-        vw = torch.as_tensor(view_weight)
-        raster._device(vw)
+    if vw is not None:
         vw = _lib.cf(vw.detach().reshape(-1))
         if vw.shape[0] != n:
             raise ValueError(f"ls2fm.fusion.integrate: {vw.shape[0]} view weights for {n} views")
+    return _integrate(volume, d, poses, k4, vw, near, max_depth, max_weight)
+
+
+def _integrate(volume, d, poses, k4, vw, near, max_depth, max_weight):
+    """integrate on converted arguments: d [n, H, W], poses [n, 3, 4], k4 [n, 4] and vw [n] or None, contiguous float32"""
+    lib = _lib.load()
+    n, dev = int(poses.shape[0]), volume.device
     for t in (poses, d, vw):
         if t is not None and t.device != dev:
             raise ValueError(f"ls2fm.fusion.integrate: the volume on {dev}, another argument on {t.device}")
-    near = raster._near(near, "integrate")
+    near = _posed.near_plane(near, "ls2fm.fusion.integrate")
     max_depth, max_weight = float(max_depth), float(max_weight)
     if not (max_depth > 0.0 and max_weight > 0.0):
         raise ValueError(f"ls2fm.fusion.integrate: max_depth {max_depth} and max_weight {max_weight} must be positive (inf is allowed)")
@@ -143,13 +147,7 @@ def integrate_torch(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=
         if not w > 0.0:
             continue
         w = scalar(w)
-        c = [((P[i, r, 0] * x + P[i, r, 1] * y) + P[i, r, 2] * z) + P[i, r, 3] for r in range(3)]
-        u = K[i, 0, 0] * (c[0] / c[2]) + K[i, 0, 2]
-        v = K[i, 1, 1] * (c[1] / c[2]) + K[i, 1, 2]
-        ok = torch.isfinite(c[2]) & (c[2] >= near) & (u.abs() <= 65536.0) & (v.abs() <= 65536.0)
-        ok = ok & (u >= 0) & (u < W) & (v >= 0) & (v < H)
-        px = torch.where(ok, u.floor(), torch.zeros_like(u)).long()
-        py = torch.where(ok, v.floor(), torch.zeros_like(v)).long()
+        c, _, _, _, ok, px, py = _posed.project_torch(P[i], K[i], x, y, z, near, H, W)
         d = depth[i].reshape(-1)[py * W + px]
         ok = ok & torch.isfinite(d) & (d > 0) & (d <= max_depth)
         s = d - c[2]
@@ -189,10 +187,6 @@ def volume_for(bounds, voxel, trunc=None, device="cuda") -> TsdfVolume:
     return TsdfVolume(shape, lo, voxel, TRUNC_VOXELS * voxel if trunc is None else trunc, device)
 
 
-def _intr_of(K, s, e):
-    return K if K.shape[0] == 1 else K[s:e]
-
-
 @torch.no_grad()
 def fuse_mesh(verts, faces, pose, intr, H, W, voxel, trunc=None, bounds=None, near=1e-3, max_depth=math.inf, min_weight=1.0,
               max_weight=math.inf, max_workspace_bytes=2 ** 28, return_volume=False):
@@ -205,9 +199,8 @@ def fuse_mesh(verts, faces, pose, intr, H, W, voxel, trunc=None, bounds=None, ne
     The views go in chunks whose z-buffer stays within max_workspace_bytes (at least one view per chunk), one rasterisation and
     one ls2fm_tsdf_integrate launch per chunk; the chunking does not show in the result.
     -> ls2fm.mesh.Mesh, with return_volume (Mesh, TsdfVolume)."""
-    v, f = raster._mesh(verts, faces, "fuse_mesh")
-    poses, _ = raster._views(pose, intr, "fuse_mesh")
-    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3)
+    v, f = _posed.mesh_arrays(verts, faces, "ls2fm.fusion.fuse_mesh")
+    poses, k4 = _posed.views(pose, intr, "ls2fm.fusion.fuse_mesh")
     H, W, voxel = int(H), int(W), float(voxel)
     trunc = TRUNC_VOXELS * voxel if trunc is None else float(trunc)
     if bounds is None:
@@ -216,13 +209,9 @@ def fuse_mesh(verts, faces, pose, intr, H, W, voxel, trunc=None, bounds=None, ne
         lo, hi = (t.tolist() for t in torch.stack([v.amin(dim=0), v.amax(dim=0)]).cpu())
         bounds = ([t - trunc for t in lo], [t + trunc for t in hi])
     volume = volume_for(bounds, voxel, trunc, v.device)
-    n = int(poses.shape[0])
-    per_chunk = max(1, int(max_workspace_bytes) // (8 * H * W))
-    for s in range(0, n, per_chunk):
-        e = min(s + per_chunk, n)
-        k = _intr_of(K, s, e)
-        depth = raster.rasterize(v, f, poses[s:e], k, H, W, near=near, max_workspace_bytes=max_workspace_bytes).depth
-        integrate(volume, depth, poses[s:e], k, near=near, max_depth=max_depth, max_weight=max_weight)
+    for s, e in _posed.chunks(int(poses.shape[0]), 8, H, W, max_workspace_bytes):
+        depth = raster.rasterize_prepared(v, f, poses[s:e], k4[s:e], H, W, near, max_workspace_bytes=max_workspace_bytes).depth
+        _integrate(volume, depth, poses[s:e], k4[s:e], None, near, max_depth, max_weight)
     out = extract(volume, min_weight)
     return (out, volume) if return_volume else out
 
@@ -237,13 +226,10 @@ def fuse_field(sdf_field, pose, intr, H, W, voxel, bounds, trunc=None, near=1e-3
     -> ls2fm.mesh.Mesh, with return_volume (Mesh, TsdfVolume)."""
     from . import image
     poses = torch.as_tensor(pose).reshape(-1, 3, 4)
-    raster._device(poses)
+    _posed.device(poses)
     H, W = int(H), int(W)
     volume = volume_for(bounds, voxel, trunc, poses.device)
-    n = int(poses.shape[0])
-    per_chunk = max(1, int(max_workspace_bytes) // (40 * H * W))
-    for s in range(0, n, per_chunk):
-        e = min(s + per_chunk, n)
+    for s, e in _posed.chunks(int(poses.shape[0]), 40, H, W, max_workspace_bytes):
         t = image.trace_image(sdf_field, poses[s:e], intr, H, W)
         depth = torch.where(t.finish, t.depth[..., 0], torch.full_like(t.depth[..., 0], math.inf)).view(e - s, H, W)
         integrate(volume, depth, poses[s:e], intr, near=near, max_depth=max_depth, max_weight=max_weight)

@@ -44,6 +44,7 @@ There is no CPU path for the device calls: CPU tensors, a missing device or a mi
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
 
 import numpy as np
@@ -57,16 +58,7 @@ _STATUS = {1: f"track_start does not rise inside [0, n_obs] or a track has more 
            2: "an obs_view outside [0, n_views)", 4: "a counting observation with a non-finite pixel"}
 
 
-def _device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ls2fm.mapper: runs on MI355X only (got a CPU tensor); there is no CPU fallback")
-
-
-def _raise_status(status, what):
-    code = int(status.item())
-    if code:
-        raise ValueError(f"ls2fm.mapper.{what}: " + "; ".join(msg for bit, msg in _STATUS.items() if code & bit))
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.mapper")
 
 
 def _table(tracks, obs_uv, what):
@@ -127,7 +119,7 @@ def view_scores(tracks, obs_uv, obs_keep, track_valid, registered, image_size, v
         check(lib.ls2fm_view_scores(ptr(ts), T, ptr(view), ptr(uv), n_obs, ptr(keep), ptr(valid), ptr(reg), ptr(size), V, ptr(score),
                                     ptr(num), ptr(status), ptr(ws), stream_ptr()), "ls2fm_view_scores")
         if validate and not torch.cuda.is_current_stream_capturing():
-            _raise_status(status, "view_scores")
+            _lib.raise_status(status, "ls2fm.mapper.view_scores", _STATUS)
     return score, num, status
 
 
@@ -171,7 +163,7 @@ def update_observations(tracks, obs_uv, poses, intrinsics, registered, X, track_
                                             float(max_error_px), float(min_tri_angle_deg), ptr(keep), ptr(valid), ptr(num), ptr(ang),
                                             ptr(status), ptr(ws), stream_ptr()), "ls2fm_update_observations")
         if validate and not torch.cuda.is_current_stream_capturing():
-            _raise_status(status, "update_observations")
+            _lib.raise_status(status, "ls2fm.mapper.update_observations", _STATUS)
     return dict(obs_keep=keep.view(torch.bool), track_valid=valid.view(torch.bool), num_kept=num, tri_angle=ang, status=status)
 
 
@@ -646,8 +638,7 @@ def reconstruct(n_views, intrinsic, H, W, options=None, device="cuda"):
         raise TypeError("ls2fm.mapper.reconstruct: options must be a MapperOptions")
     if len(n_views) < 2:
         raise ValueError(f"ls2fm.mapper.reconstruct: {len(n_views)} views; two are needed")
-    if not torch.cuda.is_available():
-        raise RuntimeError("ls2fm.mapper: runs on MI355X only (no device found); there is no CPU fallback")
+    _lib.find_device("ls2fm.mapper")             # called for its refusal: without a device the mapper raises here
     m = _Mapper(n_views, intrinsic, H, W, opt, device)
     with torch.cuda.device(m.dev):
         m.initialise()

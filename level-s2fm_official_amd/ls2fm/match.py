@@ -54,12 +54,10 @@ def match_descriptors(descriptors, pairs=None, max_ratio=0.8, max_distance=0.7, 
     -> list of int64 [M_p,2] tensors (row of the first image, row of the second; increasing first), on the device.
     return_scores=True: (matches, scores) with scores a list of dicts best_ab / best_j_ab / second_ab [n_a] and best_ba /
     best_j_ba / second_ba [n_b] (int32): the raw integers of both directions."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("ls2fm.match: runs on MI355X only (no device found); there is no CPU fallback")
     descriptors = list(descriptors)
+    dev = _lib.find_device("ls2fm.match", descriptors)
     if len(descriptors) == 0:
         raise ValueError("ls2fm.match: no images")
-    dev = next((torch.as_tensor(d).device for d in descriptors if torch.is_tensor(d) and d.is_cuda), torch.device("cuda", torch.cuda.current_device()))
     flat, start = _descriptor_array(descriptors, dev)
     V = len(descriptors)
     if pairs is None:

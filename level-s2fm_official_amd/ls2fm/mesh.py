@@ -25,8 +25,7 @@ def marching_cubes(volume: torch.Tensor, level: float = 0.0, spacing=(1.0, 1.0, 
     lib = _lib.load()
     if volume.dim() != 3:
         raise ValueError(f"marching_cubes: a 3-d volume is needed, got shape {tuple(volume.shape)}")
-    if not volume.is_cuda:
-        raise RuntimeError("ls2fm.mesh.marching_cubes runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    _lib.require_device_tensors("ls2fm.mesh.marching_cubes", volume, phrase=" runs on the GPU only")
     vol = _lib.cf(volume)
     nx, ny, nz = (int(s) for s in vol.shape)
     dev = vol.device
@@ -67,8 +66,7 @@ def select_faces(verts: torch.Tensor, faces: torch.Tensor, keep: torch.Tensor) -
 
 def _check_mesh(verts, faces, what):
     """device-only and [., 3] shapes"""
-    if not faces.is_cuda or (verts is not None and not verts.is_cuda):
-        raise RuntimeError(f"ls2fm.mesh.{what} runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    _lib.require_device_tensors(f"ls2fm.mesh.{what}", faces, verts, phrase=" runs on the GPU only")
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"{what}: faces must be [F, 3], got shape {tuple(faces.shape)}")
     if verts is not None and (verts.dim() != 2 or verts.shape[1] != 3):

@@ -23,7 +23,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, fused, raster
+from . import _lib, _posed, fused, raster
 from ._lib import check, ptr, stream_ptr
 
 
@@ -183,13 +183,7 @@ def photo_colors_torch(verts, pose, intr, images, depth, masks=None, normals=Non
     x, y, z = v[:, 0], v[:, 1], v[:, 2]
     tol = torch.tensor(depth_tol, dtype=torch.float32, device=dev)
     for i in range(n):
-        c = [((P[i, r, 0] * x + P[i, r, 1] * y) + P[i, r, 2] * z) + P[i, r, 3] for r in range(3)]
-        u = K[i, 0, 0] * (c[0] / c[2]) + K[i, 0, 2]
-        w = K[i, 1, 1] * (c[1] / c[2]) + K[i, 1, 2]
-        ok = torch.isfinite(c[2]) & (c[2] >= near) & (u.abs() <= 65536.0) & (w.abs() <= 65536.0)
-        ok = ok & (u >= 0) & (u < W) & (w >= 0) & (w < H)
-        px = torch.where(ok, u.floor(), torch.zeros_like(u)).long()
-        py = torch.where(ok, w.floor(), torch.zeros_like(w)).long()
+        c, u, w, _, ok, px, py = _posed.project_torch(P[i], K[i], x, y, z, near, H, W)
         at = py * W + px
         if masks is not None:
             ok = ok & (masks[i].reshape(-1)[at] != 0)
@@ -256,16 +250,15 @@ def photo_colors(verts, faces, pose, intr, images, masks=None, normals=None, nea
             raise RuntimeError("ls2fm.mesh_colors.photo_colors: CPU tensors need the depth maps (depth=...): the rasteriser runs "
                                "on MI355X only")
         return photo_colors_torch(verts, pose, intr, images, depth, masks, normals, near, depth_tol, power, fill, fallback)
-    v, f = raster._mesh(verts, faces, "photo_colors")
-    poses, k4 = raster._views(pose, intr, "photo_colors")
-    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3)
+    v, f = _posed.mesh_arrays(verts, faces, "ls2fm.mesh_colors.photo_colors")
+    poses, k4 = _posed.views(pose, intr, "ls2fm.mesh_colors.photo_colors")
     n, dev = int(poses.shape[0]), v.device
     img = _images(images, n, "photo_colors")
     H, W, C = int(img.shape[1]), int(img.shape[2]), int(img.shape[3])
-    m = None if masks is None else raster._masks(masks, n, "photo_colors")
+    m = None if masks is None else _posed.masks(masks, n, "ls2fm.mesh_colors.photo_colors")
     if m is not None and tuple(m.shape[1:]) != (H, W):
         raise ValueError(f"ls2fm.mesh_colors.photo_colors: masks of {tuple(m.shape[1:])} for images of {(H, W)}")
-    near = raster._near(near, "photo_colors")
+    near = _posed.near_plane(near, "ls2fm.mesh_colors.photo_colors")
     nrm = None
     if normals is not None:
         nrm = _lib.cf(torch.as_tensor(normals).detach())
@@ -278,12 +271,10 @@ def photo_colors(verts, faces, pose, intr, images, masks=None, normals=None, nea
     for t in (poses, img, m, nrm, depth):
         if t is not None and t.device != dev:
             raise ValueError(f"ls2fm.mesh_colors.photo_colors: verts on {dev}, another argument on {t.device}")
-    per_chunk = max(1, (2 ** 28) // (8 * H * W)) if view_chunk is None else max(1, int(view_chunk))
     with torch.cuda.device(dev):
         state = (torch.zeros(v.shape[0], C + 1, dtype=torch.float64, device=dev), torch.zeros(v.shape[0], dtype=torch.int32, device=dev))
-        for s in range(0, n, per_chunk):
-            e = min(s + per_chunk, n)
-            d = depth[s:e] if depth is not None else raster.rasterize(v, f, poses[s:e], K if K.shape[0] == 1 else K[s:e], H, W, near=near).depth
+        for s, e in _posed.chunks(n, 8, H, W, 2 ** 28, view_chunk):
+            d = depth[s:e] if depth is not None else raster.rasterize_prepared(v, f, poses[s:e], k4[s:e], H, W, near).depth
             accumulate_views(state, v, (poses[s:e], k4[s:e]), img[s:e], d, None if m is None else m[s:e], nrm, near, depth_tol, power)
         colors = finish_colors(state, C, fill, fallback)
     return VertexColors(colors, state[0][:, C].clone(), state[1])

@@ -18,6 +18,7 @@ for bit.  There is no CPU path for the grid: CPU tensors, a missing device or a 
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -31,11 +32,8 @@ from ._lib import check, ptr, stream_ptr
 AUTO_CELL_RULE = "surface"
 
 
-def _device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ls2fm.metrics: the point grid runs on MI355X only (got a CPU tensor); there is no CPU fallback -- "
-                               "nearest_neighbors_bruteforce is the explicit torch form")
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.metrics", phrase=": the point grid runs on MI355X only",
+                            more=" -- nearest_neighbors_bruteforce is the explicit torch form")
 
 
 def _points(x, name):

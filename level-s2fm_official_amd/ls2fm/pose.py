@@ -17,6 +17,7 @@ absolute_pose_estimation defaults as we read them.  There is no CPU path: CPU te
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -25,10 +26,7 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr
 
 
-def _device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ls2fm.pose: runs on MI355X only (got a CPU tensor); there is no CPU fallback")
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.pose")
 
 
 def _f64(t, shape_tail, what):

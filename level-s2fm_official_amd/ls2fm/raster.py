@@ -18,51 +18,10 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, _posed
 from ._lib import check, ptr, stream_ptr
+from ._posed import device as _device, masks as _masks, mesh_arrays as _mesh, near_plane as _near, views as _views
 from .options import Options
-
-
-def _device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ls2fm.raster: the rasteriser runs on MI355X only (got a CPU tensor); there is no CPU fallback")
-
-
-def _views(pose, intr, name):
-    """poses float32 [N, 3, 4] and intrinsics float32 [N, 4] = (fx, fy, cx, cy), both contiguous on the pose's device.  Only
-    K[0,0], K[1,1], K[0,2] and K[1,2] are taken, with torch ops on the device: no host read."""
-    pose, intr = torch.as_tensor(pose), torch.as_tensor(intr)
-    _device(pose, intr)
-    if pose.dim() not in (2, 3) or tuple(pose.shape[-2:]) != (3, 4):
-        raise ValueError(f"ls2fm.raster.{name}: pose must be [3, 4] or [V, 3, 4], got {tuple(pose.shape)}")
-    poses = _lib.cf(pose.detach().reshape(-1, 3, 4))
-    n = int(poses.shape[0])
-    if intr.dim() not in (2, 3) or tuple(intr.shape[-2:]) != (3, 3):
-        raise ValueError(f"ls2fm.raster.{name}: intr must be [3, 3] or [V, 3, 3], got {tuple(intr.shape)}")
-    K = intr.detach().reshape(-1, 3, 3).to(device=poses.device, dtype=torch.float32)
-    if K.shape[0] not in (1, n):
-        raise ValueError(f"ls2fm.raster.{name}: {K.shape[0]} intrinsics for {n} poses")
-    k4 = torch.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], dim=1).expand(n, 4).contiguous()
-    return poses, k4
-
-
-def _mesh(verts, faces, name):
-    verts, faces = torch.as_tensor(verts), torch.as_tensor(faces)
-    _device(verts, faces)
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError(f"ls2fm.raster.{name}: verts must be [V, 3], got shape {tuple(verts.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"ls2fm.raster.{name}: faces must be [F, 3], got shape {tuple(faces.shape)}")
-    f = faces if faces.dtype == torch.int32 and faces.is_contiguous() else faces.to(torch.int32).contiguous()
-    return _lib.cf(verts.detach()), f
-
-
-def _near(near, name):
-    near = float(near)
-    if not (0.0 < near < float("inf")):
-        raise ValueError(f"ls2fm.raster.{name}: near {near} must be positive and finite")
-    return near
 
 
 @torch.no_grad()
@@ -82,42 +41,38 @@ def rasterize(verts, faces, pose, intr, H, W, near=1e-3, bary=False, hits=False,
     The views are rasterised in chunks so that the 8-byte-per-pixel z-buffer stays within max_workspace_bytes (at least one view
     per chunk); views are independent, so the chunking does not show in the result.  Nothing is read back to the host, so a call
     can be captured into a graph."""
+    v, f = _mesh(verts, faces, "ls2fm.raster.rasterize")
+    poses, k4 = _views(pose, intr, "ls2fm.raster.rasterize")
+    return rasterize_prepared(v, f, poses, k4, H, W, near, bary, hits, max_workspace_bytes)
+
+
+@torch.no_grad()
+def rasterize_prepared(v, f, poses, k4, H, W, near=1e-3, bary=False, hits=False, max_workspace_bytes=2 ** 28):
+    """Internal to the package, not part of the API: rasterize on converted arguments (_posed.mesh_arrays, _posed.views or a
+    chunk [s:e] of its pair), for the chunk loops of ls2fm.mesh_colors and ls2fm.fusion: the intrinsics are converted once."""
     lib = _lib.load()
-    v, f = _mesh(verts, faces, "rasterize")
-    poses, k4 = _views(pose, intr, "rasterize")
     if poses.device != v.device or f.device != v.device:
         raise ValueError(f"ls2fm.raster.rasterize: verts on {v.device}, faces on {f.device}, poses on {poses.device}")
-    H, W, near = int(H), int(W), _near(near, "rasterize")
+    H, W, near = int(H), int(W), _near(near, "ls2fm.raster.rasterize")
     if not (1 <= H <= 32768 and 1 <= W <= 32768):
         raise ValueError(f"ls2fm.raster.rasterize: image size {H} x {W} outside [1, 32768]")
     n, dev = int(poses.shape[0]), v.device
     n_f = int(f.shape[0])
     if n_f >= 1 << 31:
         raise ValueError(f"ls2fm.raster.rasterize: {n_f} faces, 2^31 or more")
-    per_chunk = max(1, int(max_workspace_bytes) // (8 * H * W))
+    ranges = _posed.chunks(n, 8, H, W, max_workspace_bytes)
     with torch.cuda.device(dev):
         face_id = torch.empty(n, H, W, dtype=torch.int32, device=dev)
         depth = torch.empty(n, H, W, dtype=torch.float32, device=dev)
         bc = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev) if bary else None
         face_hits = torch.zeros(n_f, dtype=torch.int32, device=dev) if hits else None
         if n:
-            ws = _lib.workspace(lib.ls2fm_rasterize_workspace_bytes(min(per_chunk, n), H, W), "ls2fm_rasterize_workspace_bytes", dev)
-        for s in range(0, n, per_chunk):
-            e = min(s + per_chunk, n)
+            ws = _lib.workspace(lib.ls2fm_rasterize_workspace_bytes(ranges[0][1], H, W), "ls2fm_rasterize_workspace_bytes", dev)
+        for s, e in ranges:
             check(lib.ls2fm_rasterize(ptr(v), int(v.shape[0]), ptr(f), n_f, ptr(poses[s:e]), ptr(k4[s:e]), e - s, H, W, near,
                                       ptr(face_id[s:e]), ptr(depth[s:e]), ptr(bc[s:e]) if bary else ptr(None), ptr(face_hits),
                                       ptr(ws), stream_ptr()), "ls2fm_rasterize")
     return Options(face_id=face_id, depth=depth, bary=bc, face_hits=face_hits)
-
-
-def _masks(masks, n, name):
-    masks = torch.as_tensor(masks)
-    _device(masks)
-    if masks.dim() == 2:
-        masks = masks[None]
-    if masks.dim() != 3 or masks.shape[0] != n or masks.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"ls2fm.raster.{name}: masks must be bool or uint8 [{n}, H, W], got {masks.dtype} {tuple(masks.shape)}")
-    return masks.contiguous().view(torch.uint8)
 
 
 @torch.no_grad()
@@ -131,12 +86,12 @@ def mask_votes(verts, pose, intr, masks, near=1e-3):
     if verts.dim() != 2 or verts.shape[1] != 3:
         raise ValueError(f"ls2fm.raster.mask_votes: verts must be [n, 3], got shape {tuple(verts.shape)}")
     v = _lib.cf(verts.detach())
-    poses, k4 = _views(pose, intr, "mask_votes")
+    poses, k4 = _views(pose, intr, "ls2fm.raster.mask_votes")
     n = int(poses.shape[0])
-    m = _masks(masks, n, "mask_votes")
+    m = _masks(masks, n, "ls2fm.raster.mask_votes")
     if poses.device != v.device or m.device != v.device:
         raise ValueError(f"ls2fm.raster.mask_votes: verts on {v.device}, poses on {poses.device}, masks on {m.device}")
-    H, W, near = int(m.shape[1]), int(m.shape[2]), _near(near, "mask_votes")
+    H, W, near = int(m.shape[1]), int(m.shape[2]), _near(near, "ls2fm.raster.mask_votes")
     with torch.cuda.device(v.device):
         seen = torch.empty(v.shape[0], dtype=torch.int32, device=v.device)
         inside = torch.empty(v.shape[0], dtype=torch.int32, device=v.device)
@@ -158,13 +113,7 @@ def mask_votes_torch(verts, pose, intr, masks, near=1e-3):
     inside = torch.zeros_like(seen)
     x, y, z = v[:, 0], v[:, 1], v[:, 2]
     for i in range(P.shape[0]):
-        c = [((P[i, r, 0] * x + P[i, r, 1] * y) + P[i, r, 2] * z) + P[i, r, 3] for r in range(3)]
-        u = K[i, 0, 0] * (c[0] / c[2]) + K[i, 0, 2]
-        w = K[i, 1, 1] * (c[1] / c[2]) + K[i, 1, 2]
-        ok = torch.isfinite(c[2]) & (c[2] >= near) & (u.abs() <= 65536.0) & (w.abs() <= 65536.0)
-        ok = ok & (u >= 0) & (u < W) & (w >= 0) & (w < H)
-        px = torch.where(ok, u.floor(), torch.zeros_like(u)).long()
-        py = torch.where(ok, w.floor(), torch.zeros_like(w)).long()
+        _, _, _, _, ok, px, py = _posed.project_torch(P[i], K[i], x, y, z, near, H, W)
         seen += ok.to(torch.int32)
         inside += (ok & (masks[i].view(-1)[py * W + px] != 0)).to(torch.int32)
     return seen, inside
@@ -184,14 +133,14 @@ def clean_mesh(verts, faces, pose, intr, masks=None, H=None, W=None, dilate=0, m
     re-indexed, both in their order, with torch ops.  kept_faces is this selection; keep_largest then hands the result to
     ls2fm.mesh.largest_component.  Face indices are checked (one host read), the sizes of the result are another."""
     from . import mesh
-    v, f = _mesh(verts, faces, "clean_mesh")
+    v, f = _mesh(verts, faces, "ls2fm.raster.clean_mesh")
     mesh._faces_i32(f, int(v.shape[0]), "ls2fm.raster.clean_mesh")
     dev = v.device
     with torch.cuda.device(dev):
         keep_v = torch.ones(v.shape[0], dtype=torch.bool, device=dev)
         if masks is not None:
-            poses, _ = _views(pose, intr, "clean_mesh")
-            m = _masks(masks, int(poses.shape[0]), "clean_mesh")
+            poses, _ = _views(pose, intr, "ls2fm.raster.clean_mesh")
+            m = _masks(masks, int(poses.shape[0]), "ls2fm.raster.clean_mesh")
             if int(dilate) > 0:
                 d = int(dilate)
                 m = torch.nn.functional.max_pool2d(m[:, None].float(), kernel_size=2 * d + 1, stride=1, padding=d)[:, 0].to(torch.uint8)

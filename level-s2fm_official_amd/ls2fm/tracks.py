@@ -14,6 +14,8 @@ There is no CPU path for the two device calls: CPU tensors, a missing device or 
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 import torch
 
@@ -27,16 +29,7 @@ _TRACK_STATUS = {1: f"track_start does not rise inside [0, n_obs] or a track has
                  2: "an obs_view outside [0, n_views)"}
 
 
-def _device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("ls2fm.tracks: runs on MI355X only (got a CPU tensor); there is no CPU fallback")
-
-
-def _raise_status(status, table, what):
-    code = int(status.item())
-    if code:
-        raise ValueError(f"ls2fm.tracks.{what}: " + "; ".join(msg for bit, msg in table.items() if code & bit))
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.tracks")
 
 
 def edges_from_n_views(n_views):
@@ -115,7 +108,7 @@ def track_labels(image_start, edges, return_status=False):
               "ls2fm_track_labels")
     if return_status:
         return labels, status
-    _raise_status(status, _EDGE_STATUS, "track_labels")
+    _lib.raise_status(status, "ls2fm.tracks.track_labels", _EDGE_STATUS)
     return labels
 
 
@@ -211,7 +204,7 @@ def triangulate_tracks(tracks, keypoints, poses, intrinsics, max_error_px=4.0, m
                                            float(min_tri_angle_deg), ptr(X), ptr(inl), ptr(num), ptr(succ), ptr(ang), ptr(err), ptr(best),
                                            ptr(status), ptr(ws), stream_ptr()), "ls2fm_triangulate_tracks")
         if validate and not torch.cuda.is_current_stream_capturing():
-            _raise_status(status, _TRACK_STATUS, "triangulate_tracks")
+            _lib.raise_status(status, "ls2fm.tracks.triangulate_tracks", _TRACK_STATUS)
     return dict(X=X, inliers=inl.view(torch.bool), num_inliers=num, success=succ.bool(), tri_angle=ang, mean_error_px=err,
                 best_pair=best, status=status, obs_uv=uv)
 

@@ -2,6 +2,7 @@
 GPU tests (tests/test_hip_fusion.py) can be exact comparisons against that restatement; and ls2fm.fusion.extract's face filter."""
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -167,9 +168,36 @@ def test_extract_drops_exactly_the_faces_on_an_unobserved_corner_s_crossing_edge
         assert (np.abs(v[:, 0] - 0.125) < 1e-7).all()                # what is left lies on the plane
 
 
+def _cpu_volume(sc):
+    """TsdfVolume refuses CPU devices: a plain object with its attributes, for the torch form"""
+    import torch
+    return types.SimpleNamespace(shape=tuple(sc["shape"]), origin=tuple(sc["origin"]), voxel=sc["voxel"], trunc=sc["trunc"],
+                                 device=torch.device("cpu"), tsdf=torch.zeros(*sc["shape"]), weight=torch.zeros(*sc["shape"]))
+
+
+@pytest.mark.parametrize("shape,H,W,nan_pose", [((5, 4, 67), 9, 11, False), ((3, 3, 130), 7, 5, True)])
+def test_integrate_torch_on_the_cpu_leaves_the_restatement_s_bits(shape, H, W, nan_pose):
+    """ls2fm.fusion.integrate_torch, the torch form the GPU tests and tools/time_fusion.py hold the kernel against, on CPU tensors
+    against FR.fuse on the edge scene with its near, max_depth, view weights and max_weight: tsdf and weight equal as bits at
+    every lattice point"""
+    import torch
+    from ls2fm import fusion
+    sc = S.edge_scene(shape, H, W, nan_pose=nan_pose)
+    want = fuse(sc, weighted=True)
+    vol = fusion.integrate_torch(_cpu_volume(sc), torch.from_numpy(sc["depth"]), torch.from_numpy(np.asarray(sc["poses"], F32)),
+                                 torch.from_numpy(np.asarray(sc["intr"], F32)), near=sc["near"], max_depth=sc["max_depth"],
+                                 view_weight=[float(w) for w in sc["view_weight"]], max_weight=sc["max_weight"])
+    assert want[1].any() and (want[1] == 0).any()
+    for got, ref in ((vol.tsdf, want[0]), (vol.weight, want[1])):
+        assert np.array_equal(got.numpy().view(np.uint32), np.asarray(ref, F32).view(np.uint32))
+
+
 def test_public_entry_points_refuse_cpu_tensors():
     import torch
     from ls2fm import fusion
+    # fusion's own arguments are refused in fusion's name, before the views are looked at
+    with pytest.raises(RuntimeError, match=r"ls2fm\.fusion.*no CPU fallback"):
+        fusion.integrate(types.SimpleNamespace(device=torch.device("cpu")), torch.ones(1, 8, 8), torch.zeros(1, 3, 4), torch.eye(3))
     with pytest.raises(RuntimeError):
         fusion.TsdfVolume((4, 4, 4), (0.0, 0.0, 0.0), 0.25, 0.5, "cpu")
     for bad in (dict(voxel=0.0), dict(trunc=float("inf")), dict(voxel=float("nan")), dict(origin=(0.0, float("nan"), 0.0)), dict(shape=(4, 4))):

@@ -216,8 +216,8 @@ def test_refusals_and_empty_calls(FU):
     sc = S.edge_scene((BX + 1, BY + 1, 4), 5, 7)
     tsdf = torch.zeros(sc["shape"], device=DEV)
     weight = torch.zeros(sc["shape"], device=DEV)
-    from ls2fm import raster
-    poses, k4 = raster._views(dev(sc["poses"]), dev(sc["intr"]), "test")
+    from ls2fm import _posed
+    poses, k4 = _posed.views(dev(sc["poses"]), dev(sc["intr"]), "test")
     depth = dev(sc["depth"])
     p, s = _lib.ptr, _lib.stream_ptr()
     origin = (3 * _lib.c_float)(*sc["origin"])

@@ -7,7 +7,7 @@ import torch
 
 import mesh_colors_restate as MR
 import mesh_colors_scenes as S
-from ls2fm import mesh_colors, raster
+from ls2fm import _posed, mesh_colors
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -40,7 +40,7 @@ def same(got, ref, what):
 def device_state(sc, V, views, with_normals, power, with_masks=True, state=None):
     """accumulate the views `views` of an edge scene's first V points on the device -> (sums, count)"""
     pts = dev(sc["points"][:V])
-    pose4 = raster._views(dev(sc["poses"][views]), dev(sc["intr"][views]), "test")
+    pose4 = _posed.views(dev(sc["poses"][views]), dev(sc["intr"][views]), "test")
     img = dev(sc["images"][views])
     C = img.shape[3]
     if state is None:
@@ -150,7 +150,7 @@ def test_refusals_and_empty_calls():
     sc = S.edge_scene(5, 7, 3)
     V = 8
     pts, img, depth = dev(sc["points"][:V]), dev(sc["images"]), dev(sc["depth"])
-    poses, k4 = raster._views(dev(sc["poses"]), dev(sc["intr"]), "test")
+    poses, k4 = _posed.views(dev(sc["poses"]), dev(sc["intr"]), "test")
     sums = torch.zeros(V, 4, dtype=torch.float64, device=DEV)
     count = torch.zeros(V, dtype=torch.int32, device=DEV)
     p, s = _lib.ptr, _lib.stream_ptr()

@@ -182,6 +182,35 @@ def test_votes_scene_holds_the_image_borders_and_the_unusable():
     assert (inside <= seen).all() and set(np.unique(seen).tolist()) == {0, 1, 2} and (inside == 2).any() and ((seen == 2) & (inside == 0)).any()
 
 
+def test_the_library_s_torch_projection_is_the_restatement_s():
+    """ls2fm._posed.project_torch, the one torch statement of the projection under the three *_torch forms, against R.project on
+    the votes scene (the image borders and every unusable clause), view by view: the flags equal, camera z, u and v equal as
+    bits (NaN by its pattern); then mask_votes_torch on CPU tensors against R.mask_votes"""
+    import torch
+    from ls2fm import _posed, raster
+    vs = S.votes_scene()
+    (H, W), n = vs["masks"].shape[1:], len(vs["poses"])
+    bits = lambda a: np.asarray(a, F32).view(np.uint32)
+    v = torch.from_numpy(vs["verts"])
+    P = torch.from_numpy(np.asarray(vs["poses"], F32))
+    K = torch.from_numpy(np.asarray(vs["intr"], F32)).reshape(-1, 3, 3).expand(n, 3, 3)
+    for i in range(n):
+        z, u, w, usable = R.project(vs["verts"], vs["poses"][i], R.intr4(vs["intr"], n)[i], vs["near"])
+        with np.errstate(all="ignore"):
+            in_image = usable & (u >= 0) & (u < W) & (w >= 0) & (w < H)
+        assert usable.any() and (~usable).any() and in_image.any() and (usable & ~in_image).any()
+        c, tu, tw, t_usable, ok, px, py = _posed.project_torch(P[i], K[i], v[:, 0], v[:, 1], v[:, 2], vs["near"], H, W)
+        assert np.array_equal(t_usable.numpy(), usable) and np.array_equal(ok.numpy(), in_image)
+        for got, want in ((c[2], z), (tu, u), (tw, w)):
+            assert np.array_equal(bits(got.numpy()), bits(want))
+        with np.errstate(all="ignore"):
+            assert np.array_equal(px.numpy(), np.where(in_image, np.floor(u), 0).astype(np.int64))
+            assert np.array_equal(py.numpy(), np.where(in_image, np.floor(w), 0).astype(np.int64))
+    seen, inside = raster.mask_votes_torch(v, P, torch.from_numpy(np.asarray(vs["intr"], F32)), torch.from_numpy(vs["masks"]), vs["near"])
+    want = R.mask_votes(vs["verts"], vs["poses"], vs["intr"], vs["masks"], vs["near"])
+    assert np.array_equal(seen.numpy(), want[0]) and np.array_equal(inside.numpy(), want[1])
+
+
 def test_dilation_is_a_max_pool():
     import torch
     m = (np.random.default_rng(2).uniform(size=(2, 13, 17)) < 0.08).astype(np.uint8)

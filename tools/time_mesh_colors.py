@@ -48,7 +48,7 @@ def main():
     a = ap.parse_args()
     import torch
     from time_raster import alternated, scene
-    from ls2fm import mesh_colors as MC, raster
+    from ls2fm import _posed, mesh_colors as MC, raster
     dev = "cuda:0"
     H, W, N = a.height, a.width, a.views
     verts, faces, poses, K = scene(a.res, N, H, W, dev)
@@ -80,7 +80,7 @@ def main():
                photo_colors_equal_torch=True, field_rgb_gap_kernel_vs_composition=gap)
     del got, ref, comp, close
     state = lambda: (torch.zeros(n_v, 4, dtype=torch.float64, device=dev), torch.zeros(n_v, dtype=torch.int32, device=dev))
-    pose4 = raster._views(poses, K, "time")
+    pose4 = _posed.views(poses, K, "time")
 
     def kernel_alone():
         st = state()
