@@ -1546,6 +1546,93 @@ int ls2fm_tsdf_integrate(float* tsdf, float* weight, int64_t nx, int64_t ny, int
                          int32_t n_views, int32_t height, int32_t width, float near, float max_depth, float max_weight, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering with quadric error metrics (csrc/mesh_simplify.hip behind ls2fm.simplify; additions,
+ * the library stays ABI 13): a mesh at marching-cubes density made small enough for a viewer, on the device.  Lindstrom's
+ * out-of-core simplification (2000): one pass, order-free, a pure function of its inputs.  The reference ships none.
+ * tests/simplify_restate.py repeats the rule in numpy.
+ *
+ * Inputs: verts float [V][3]; faces int32 [F][3], every index in [0, V) (the caller's duty: ls2fm.simplify checks it); cell, a
+ * positive finite float; placement LS2FM_SIMPLIFY_QUADRIC or LS2FM_SIMPLIFY_MEAN; reg >= 0, finite (ls2fm.simplify: 2^-2);
+ * colors float [V][C], 1 <= C <= 4, or NULL with C = 0.  THE CLUSTERING RULE.  All arithmetic is fp64 of the fp32 inputs, every
+ * operation rounded once, none contracted.
+ *   1. cell of a vertex   k_a = floor((double) v_a / (double) cell) per axis.  A vertex with a coordinate that is not finite is
+ *      INVALID.  A finite vertex with a k_a outside [-2^20, 2^20) is BAD: it is counted (ls2fm.simplify raises ValueError from
+ *      the count, the refusal of ls2fm.metrics.voxel_downsample) and otherwise treated as invalid.  key = x << 42 | y << 21 | z of
+ *      the coordinates k_a + 2^20, as voxel_downsample packs them, so 0 <= key < 2^63; an invalid vertex has key -1.  The cell's centre is
+ *      g_a = ((double) k_a + 0.5) * (double) cell: the sum is exact, the product rounds once.  The lattice is absolute: anchored
+ *      at 0, not at the mesh's box.
+ *   2. faces   a face is VALID iff its three vertices are valid (class 1), and SURVIVES iff it is valid and its three keys are
+ *      pairwise distinct (class 2); class 0 otherwise.
+ *   3. quadrics   corner k of a valid face CONTRIBUTES to its cell unless an earlier corner k' < k of the same face has the same
+ *      key: a face adds its quadric once per distinct cell it touches.  For a contributing corner, with g its cell's centre and
+ *      (a, b, c) the face's vertices in the face's order: p_i = (double) v_i - g;  u = p_b - p_a, w = p_c - p_a;
+ *      n = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x), unnormalised (Lindstrom's area-squared weighting: no
+ *      division, no square root);  d = (n_x p_a.x + n_y p_a.y) + n_z p_a.z.  The cell gains ten terms, sums 0 .. 9:
+ *      n_x n_x, n_x n_y, n_x n_z, n_y n_y, n_y n_z, n_z n_z (A, upper triangle row-major), d n_x, d n_y, d n_z (b), d d.
+ *   4. per-cell vertex sums   over the cell's valid vertices: the count m, p = (double) v - g per axis (sums 10 .. 12) and
+ *      (double) colour per channel (sums 13 .. 12 + C).
+ *   5. order of summation   the cell's vertices in ascending index and its contributing corners in ascending 3 f + k each form
+ *      a SEGMENT, entries e_0, e_1, ...  One wave of 64 lanes sums a segment: lane l adds e_l, e_(l + 64), e_(l + 128), ... in
+ *      that order into a running sum per quantity that starts at +0 (a lane without entries keeps +0); then the six
+ *      butterfly steps o = 32, 16, 8, 4, 2, 1 replace every lane's sum s_l by s_l + s_(l xor o) (the library's wave_sum).  The
+ *      result is lane 0's.  A segment of at most 64 entries is thus a balanced tree over its entries padded with +0 to 64.
+ *   6. placement   mean_a = sum_p_a / (double) m.  t = (A00 + A11) + A22, lambda = reg * t;  (A + lambda I) x = b + lambda mean
+ *      by the library's Cholesky solve (csrc/lm_math.h chol_solve at size 3: the matrix entries A_ij, the diagonal
+ *      A_ii + lambda * 1, its g_i = -(b_i + lambda * mean_i); a pivot <= 0 or an x that is not finite fails).
+ *      x = mean when placement is MEAN, when t is 0 or not finite, when the solve fails, or when any |x_a| > (double) cell / 2
+ *      (false for no finite x_a).  The output vertex is (float) (g_a + x_a): one fp64 sum, one rounding to fp32, which may put
+ *      it an ulp outside its cell.  The output colour is (float) (sum_c / (double) m).
+ *   7. output   vertices: the cells that hold at least one corner of a surviving face, in ascending key order.  Faces: the
+ *      surviving faces in input order, corner order kept, re-indexed to cell ranks; then every face that equals an earlier one
+ *      as an oriented triangle (equal after rotating the smallest index to the front) is removed: the lowest input index stays
+ *      (ls2fm.simplify does this with sorts of the triples; the library emits the faces it is told to keep).  vertex_map int32
+ *      [V]: the output index of each input vertex's cell, -1 for an invalid vertex or a cell that is not output.
+ * Stated, not fixed: clustering can create non-manifold edges and fold-overs; opposite-oriented duplicates both stay; no boundary
+ * or feature-edge preservation beyond what the quadrics give; no texture coordinates; the absolute lattice (a translated mesh
+ * simplifies differently).
+ *
+ * The calls, on one stream, with the caller's stable sorts and prefix sums between them; `workspace`
+ * (ls2fm_mesh_simplify_workspace_bytes(V, F) bytes) carries state from mark to index to place and must not be touched between:
+ *   keys   vert_key int64 [V], face_class uint8 [F] (may be NULL), counts int64 [2] = (surviving faces, bad vertices); counts
+ *          is zeroed by the call.  With face_class NULL this is the whole of a face count.
+ *   mark   sorted_key / sorted_vert int64 [V]: vert_key sorted ascending by a STABLE sort and the permutation.  Writes
+ *          corner_head int32 [3F]: per corner 3 f + k the position in the sorted list of its cell's first vertex, 2^31 - 1 for a
+ *          corner that does not contribute; head_used int32 [V]: 1 at the first sorted position of every output cell, else 0.
+ *   index  head_rank int32 [V]: the inclusive prefix sum of head_used (its last entry is the number of output cells n_out).
+ *          Writes vertex_map int32 [V] and face_index int32 [F][3]: a surviving face in output indices, (-1, -1, -1) otherwise.
+ *   place  sorted_corner_head int32 [3F] / sorted_corner int64 [3F]: corner_head sorted ascending by a STABLE sort and the
+ *          permutation.  stages: LS2FM_SIMPLIFY_STAGE_SUMS writes sums double [n_out][13 + C] and count int32 [n_out] (ONE WAVE
+ *          per output cell), LS2FM_SIMPLIFY_STAGE_SOLVE reads them and writes out_verts float [n_out][3] and out_colors float
+ *          [n_out][C]; both bits: both, in that order.
+ *   emit   keep uint8 [F], keep_rank int32 [F] its inclusive prefix sum, n_kept its last entry: out_faces int32 [n_kept][3].
+ * Nothing is read back by any call.  Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL array that is
+ * needed, V < 0 or V >= 2^31, F < 0 or 3 F >= 2^31, a cell that is not positive and finite, C outside [0, 4] or C = 0 with colors
+ * or C > 0 without, a placement or stages value not listed, a reg that is negative or not finite, n_out outside [0, V], n_kept
+ * outside [0, F]; LS2FM_ERR_WORKSPACE for a NULL workspace or workspace_bytes below ls2fm_mesh_simplify_workspace_bytes(V, F).
+ */
+#define LS2FM_SIMPLIFY_SUMS 13
+#define LS2FM_SIMPLIFY_QUADRIC 0
+#define LS2FM_SIMPLIFY_MEAN 1
+#define LS2FM_SIMPLIFY_STAGE_SUMS 1
+#define LS2FM_SIMPLIFY_STAGE_SOLVE 2
+int64_t ls2fm_mesh_simplify_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int ls2fm_mesh_simplify_keys(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, float cell,
+                             int64_t* vert_key, uint8_t* face_class, int64_t* counts, void* stream);
+int ls2fm_mesh_simplify_mark(const int64_t* sorted_key, const int64_t* sorted_vert, int64_t n_verts, const int32_t* faces,
+                             int64_t n_faces, const uint8_t* face_class, int32_t* corner_head, int32_t* head_used,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int ls2fm_mesh_simplify_index(const int32_t* head_used, const int32_t* head_rank, int64_t n_verts, const int32_t* faces,
+                              int64_t n_faces, const uint8_t* face_class, int32_t* vertex_map, int32_t* face_index,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int ls2fm_mesh_simplify_place(const float* verts, const float* colors, int32_t channels, int64_t n_verts, const int32_t* faces,
+                              int64_t n_faces, float cell, int32_t placement, double reg, const int64_t* sorted_key,
+                              const int64_t* sorted_vert, const int32_t* sorted_corner_head, const int64_t* sorted_corner,
+                              int64_t n_out, int32_t stages, double* sums, int32_t* count, float* out_verts, float* out_colors,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int ls2fm_mesh_simplify_emit(const int32_t* face_index, const uint8_t* keep, const int32_t* keep_rank, int64_t n_faces,
+                             int64_t n_kept, int32_t* out_faces, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -135,7 +135,7 @@ def _high_res_device(sdf, resolution, grid_boundary, level, take_components):
 
 
 def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), level=0, take_components=True, path=None,
-                              backend="auto", colors=None, rad_field=None):
+                              backend="auto", colors=None, rad_field=None, simplify=None):
     """utils/plots.py:140-222, same arguments.  The two SDF sweeps are device passes (see module docstring).
     backend: "trimesh" = the reference's scikit-image + trimesh steps (ImportError without them; returns a Trimesh);
     "device" = ls2fm.mesh: marching cubes on the coarse volume, its largest component by area (take_components), 10 000
@@ -146,6 +146,9 @@ def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), le
     colors (device backend): None = bare geometry, the bytes written without the argument; "field" = the radiance field
     `rad_field` at the vertices, `sdf` being a method of its SDF field (ls2fm.mesh_colors.field_colors); a callable
     (verts, faces) -> colours [V, 3 | 4] in [0, 1].  The colours go into the PLY at `path`.
+    simplify (device backend): None = the mesh as it is, the bytes written without the argument; a number = the cell size in world
+    units of ls2fm.simplify.simplify; {"faces": n} = ls2fm.simplify.simplify_to_faces.  Applied to the fitted mesh (after the
+    component step) and before the colours; the simplified mesh is what is returned and written.
     Intended differences of the device path: the surface samples come from torch's generator (reproducible under
     torch.manual_seed) instead of numpy's global one; marching cubes uses its own case table (ls2fm.mesh.marching_cubes);
     trimesh merges vertices on construction, which only differs where a lattice value equals `level` exactly; the PLY
@@ -154,7 +157,9 @@ def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), le
         raise ValueError(f"get_surface_high_res_mesh: backend must be 'auto', 'device' or 'trimesh', got {backend!r}")
     if colors is not None and backend == "trimesh":
         raise ValueError("get_surface_high_res_mesh(colors=...) writes vertex colours on backend='device' only")
-    if backend == "auto" and colors is not None:
+    if simplify is not None and backend == "trimesh":
+        raise ValueError("get_surface_high_res_mesh(simplify=...) simplifies the mesh on backend='device' only")
+    if backend == "auto" and (colors is not None or simplify is not None):
         backend = "device"
     if backend == "auto":
         try:
@@ -166,6 +171,9 @@ def get_surface_high_res_mesh(sdf, resolution=100, grid_boundary=(-2.0, 2.0), le
     if backend == "device":
         from .. import mesh, mesh_colors
         result, _ = _high_res_device(sdf, resolution, grid_boundary, level, take_components)
+        if simplify is not None and result is not None:
+            from ..simplify import apply as apply_simplify
+            result = mesh.Mesh(*apply_simplify(result.vertices, result.faces, simplify, "get_surface_high_res_mesh"))
         if path is not None and result is not None:
             c = mesh_colors.resolve_colors(colors, result.vertices, result.faces, getattr(sdf, "__self__", None), rad_field,
                                            "get_surface_high_res_mesh")

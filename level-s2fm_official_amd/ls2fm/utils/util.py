@@ -54,22 +54,27 @@ def lattice_points(volume_size=2.0, N=512, bound_max=None, bound_min=None, first
 
 def extract_mesh(implicit_surface, log=None, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply",
                  show_progress=True, chunk=16 * 1024, bound_max=None, bound_min=None, extra_info=None, backend="auto",
-                 colors=None, rad_field=None):
+                 colors=None, rad_field=None, simplify=None):
     """utils/util.py:392-425.  `chunk` and `show_progress` are accepted and unused (one device call).
     backend: "skimage" = the reference's scikit-image + plyfile branch (ImportError without them); "device" = ls2fm.mesh
     (marching cubes on the GPU, numpy PLY writer); "auto" = "skimage" when both packages import, else "device".  Both apply
     the reference's spacing size / N (the lattice step is size / (N - 1)) and origin to the vertices.  Returns the volume.
     colors (device backend): None = bare geometry, the bytes written without the argument; "field" = the radiance field
-    `rad_field` at the vertices (ls2fm.mesh_colors.field_colors); a callable (verts, faces) -> colours [V, 3 | 4] in [0, 1]."""
+    `rad_field` at the vertices (ls2fm.mesh_colors.field_colors); a callable (verts, faces) -> colours [V, 3 | 4] in [0, 1].
+    simplify (device backend): None = the mesh as marching cubes gives it, the bytes written without the argument; a number = the
+    cell size in world units of ls2fm.simplify.simplify; {"faces": n} = ls2fm.simplify.simplify_to_faces.  Applied before the
+    colours, which are evaluated on the simplified mesh."""
     if backend not in ("auto", "device", "skimage"):
         raise ValueError(f"extract_mesh: backend must be 'auto', 'device' or 'skimage', got {backend!r}")
     if extra_info is not None:
         raise NotImplementedError("extract_mesh(extra_info=...): residual fields are outside the fused path")
     if colors is not None and backend == "skimage":
         raise ValueError("extract_mesh(colors=...) writes vertex colours on backend='device' only")
+    if simplify is not None and backend == "skimage":
+        raise ValueError("extract_mesh(simplify=...) simplifies the mesh on backend='device' only")
     vol = sdf_volume(implicit_surface, volume_size, N, bound_max, bound_min)
     _, _, origin, sizes = _lattice(volume_size, N, bound_max, bound_min)
-    if backend == "auto" and colors is not None:
+    if backend == "auto" and (colors is not None or simplify is not None):
         backend = "device"
     if backend == "auto":
         try:
@@ -81,6 +86,9 @@ def extract_mesh(implicit_surface, log=None, volume_size=2.0, level=0.0, N=512, 
     if backend == "device":
         from .. import mesh, mesh_colors
         verts, faces = mesh.marching_cubes(vol, level=level, spacing=[float(v) / N for v in sizes], origin=origin)
+        if simplify is not None:
+            from ..simplify import apply as apply_simplify
+            verts, faces = apply_simplify(verts, faces, simplify, "extract_mesh")
         mesh.write_ply(filepath, verts, faces,
                        colors=mesh_colors.resolve_colors(colors, verts, faces, implicit_surface, rad_field, "extract_mesh"))
         if log is not None:
