@@ -1633,6 +1633,78 @@ int ls2fm_mesh_simplify_emit(const int32_t* face_index, const uint8_t* keep, con
                              int64_t n_kept, int32_t* out_faces, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Plane-sweep multi-view stereo and the geometric-consistency filter of its depth maps (csrc/mvs_sweep.hip behind
+ * ls2fm.mvs.plane_sweep and ls2fm.mvs.filter_depths; additions, the library stays ABI 13): from posed photographs to the depth
+ * maps ls2fm_tsdf_integrate fuses, the classical dense baseline (COLMAP's patch_match_stereo and stereo_fusion) in its simplest
+ * form.  The reference shells out to colmap for its sparse stage only and ships no dense stage.  tests/mvs_restate.py repeats
+ * both rules in numpy, ls2fm.mvs.plane_sweep_torch and filter_depths_torch as torch ops; the three agree bit for bit.
+ *
+ * Conventions are the rasteriser's: poses world -> camera [3][4], intr float [V][4] = (fx, fy, cx, cy), pixel (px, py) has its
+ * centre at u = px + 0.5, depth is camera z.  All views of a call share one image size H x W.
+ * Inputs of the sweep: images float [V][H][W] (grey); refs int32 [R], the view index of each reference; sources int32 [R][S], an
+ * entry outside [0, V) (-1 by convention) skips that source; depths float [R][D], the plane depths of each reference, formed by
+ * the caller (the rule never forms them); rel float [R][S][3][4], P_rs = P_s o P_r^-1 formed in fp64 and rounded once by the
+ * caller (entries of skipped sources are not read); half_width w in [1, LS2FM_MVS_MAX_HALF_WIDTH], n = (2 w + 1)^2 taps; near;
+ * min_var >= 0; min_sources in [1, S].  A reference outside [0, V) has every pixel invalid.
+ * THE SWEEP RULE, per reference r and pixel (px, py).  Every operation is one rounded fp32 operation, none contracted; division
+ * and square root are correctly rounded; every sum starts at +0 and goes in the stated order.
+ *   1. reference window   a pixel with px < w, px > W - 1 - w, py < w or py > H - 1 - w is INVALID.  Otherwise the taps a_i are
+ *      the pixels (px + dx, py + dy), dy = -w .. w outer, dx = -w .. w inner (row-major).  ma = (sum a_i) / (float) n;
+ *      va = sum (a_i - ma)^2.  The pixel is invalid if any tap is not finite or va < min_var (false for a NaN).  The
+ *      mean-subtracted two-pass form is the rule: E[xx] - E[x]^2 cancels in fp32.
+ *   2. warp   per tap pixel q = (qx, qy), plane k and source s: xn = (((float) qx + 0.5) - cx_r) / fx_r, yn likewise; the camera
+ *      point of the reference is (xn d_k, yn d_k, d_k): the plane is fronto-parallel.  Its projection into s is the camera
+ *      point / projection / usable part of the RASTERISATION RULE with the view (P_rs, intr_s) and `near`.
+ *   3. sample   bilinear about pixel centres: x = u - 0.5, x0 = floor(x), tx = x - x0; y, y0, ty likewise.  The tap is valid
+ *      iff usable and 0 <= x0, x0 <= W - 2, 0 <= y0, y0 <= H - 2 (fp32 comparisons; no clamping).  With b00, b10, b01, b11 the
+ *      source pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1): r0 = b00 + tx (b10 - b00), r1 = b01 + tx (b11 - b01),
+ *      b = r0 + ty (r1 - r0).
+ *   4. NCC   if any of the n taps is invalid or its b is not finite, (pixel, k, s) is invalid.  Otherwise mb and vb as in 1. and
+ *      cov = sum (a_i - ma) (b_i - mb), all three in tap order.  Invalid if vb < min_var.  ncc = cov / sqrt(va vb).
+ *   5. aggregate   score_k = (sum of ncc over the valid sources, in source order) / (float) count; invalid (NaN) if
+ *      count < min_sources.
+ *   6. select   the plane with the largest score; ties go to the lowest k; a NaN score never wins.  Without one the pixel is
+ *      invalid.
+ *   7. refine   with 0 < k < D - 1, s- = score_(k-1) and s+ = score_(k+1) both not NaN and den = (s- - 2 s0) + s+ < 0:
+ *      off = (0.5 (s- - s+)) / den;  depth = d_k + off (d_(k+1) - d_k) for off >= 0, d_k + off (d_k - d_(k-1)) otherwise.  In
+ *      every other case depth = d_k.
+ * Outputs: depth float [R][H][W] (NaN where invalid), score float [R][H][W] (the winning score; NaN where invalid), plane int32
+ * [R][H][W] (-1 where invalid).  One workgroup of 256 lanes per (reference, LS2FM_MVS_TILE x LS2FM_MVS_TILE tile); a pixel's
+ * result depends on nothing but the rule, so references split over several calls leave the bits of one call.
+ *
+ * THE CONSISTENCY RULE (ls2fm_mvs_filter), one lane per (view r, pixel), same arithmetic.  Inputs: depth float [V][H][W];
+ * sources int32 [V][S] (entries outside [0, V) skip); rel float [V][S][3][4] = P_rs and rel_back float [V][S][3][4] = P_sr, both
+ * formed in fp64 and rounded once; max_reproj >= 0 (pixels), rel_depth >= 0, min_consistent >= 0.  For a pixel whose depth d is
+ * finite and positive, and each source s in order:
+ *   1. lift the pixel centre: uc = (float) px + 0.5, vc likewise; X = ((uc - cx_r) / fx_r) d, Y likewise; the point (X, Y, d)
+ *   2. project it with the view (P_rs, intr_s) and `near`;  3. IN THE IMAGE by the rasteriser's floor rule gives the pixel
+ *      (sx, sy), otherwise s is not consistent; d_s = depth[s][sy][sx]
+ *   4. d_s finite and positive, otherwise not consistent
+ *   5. lift (sx, sy)'s centre at d_s with intr_s as in 1.;  6. project it with the view (P_sr, intr_r): (u', v', z'), usable
+ *   7. consistent iff du = u' - uc, dv = v' - vc, (du du) + (dv dv) <= max_reproj max_reproj, and |z' - d| <= rel_depth d.
+ * Outputs: count uint8 [V][H][W], the number of consistent sources (0 for a pixel without a finite positive depth); filtered
+ * float [V][H][W], the input depth where count >= min_consistent and NaN elsewhere.
+ *
+ * Both calls: one launch, no workspace, no atomics, nothing read back, no stream forked; they can be captured, and a rerun or a
+ * replay repeats the bits.  n_refs = 0 (sweep) and n_views = 0 (filter) return at once.  Refused before anything is enqueued:
+ * LS2FM_ERR_INVALID_ARGUMENT for a NULL array, height or width outside [1, 32768], views height width >= 2^40, S outside
+ * [1, LS2FM_MVS_MAX_SOURCES], D outside [1, LS2FM_MVS_MAX_PLANES], a half width outside [1, LS2FM_MVS_MAX_HALF_WIDTH], near not
+ * positive and finite, min_var, max_reproj or rel_depth negative or not finite, min_sources outside [1, S], a negative
+ * min_consistent, 2^31 workgroups or more.
+ */
+#define LS2FM_MVS_TILE 16
+#define LS2FM_MVS_MAX_HALF_WIDTH 5
+#define LS2FM_MVS_MAX_SOURCES 64
+#define LS2FM_MVS_MAX_PLANES 65536
+int ls2fm_mvs_sweep(const float* images, int32_t n_views, int32_t height, int32_t width, const int32_t* refs, int32_t n_refs,
+                    const int32_t* sources, int32_t n_sources, const float* depths, int32_t n_planes, const float* rel,
+                    const float* intr, int32_t half_width, float near, float min_var, int32_t min_sources, float* depth,
+                    float* score, int32_t* plane, void* stream);
+int ls2fm_mvs_filter(const float* depth, int32_t n_views, int32_t height, int32_t width, const int32_t* sources, int32_t n_sources,
+                     const float* rel, const float* rel_back, const float* intr, float near, float max_reproj, float rel_depth,
+                     int32_t min_consistent, uint8_t* count, float* filtered, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -1,0 +1,489 @@
+"""Plane-sweep multi-view stereo on the device: from posed photographs to depth maps, and through ls2fm.fusion to a surface.
+
+  to_grey, select_sources, depth_range_from_points, depth_planes, relative_poses   the inputs of the sweep, as torch ops
+  plane_sweep     per reference view the depth, score and plane of every pixel (ls2fm_mvs_sweep, csrc/mvs_sweep.hip): normalised
+                  cross-correlation of a (2 w + 1)^2 window against S source views over D fronto-parallel planes
+  filter_depths   the geometric-consistency filter of a set of depth maps (ls2fm_mvs_filter): a pixel stays when enough source
+                  views hold a depth that projects back onto it
+  dense_reconstruct   plane_sweep -> filter_depths -> fusion.volume_for -> fusion.integrate -> fusion.extract: the classical dense
+                  baseline row of the neural-surface tables (COLMAP's patch_match_stereo and stereo_fusion), in its simplest
+                  form; its mesh goes into ls2fm.mesh_colors.photo_colors and ls2fm.metrics.evaluate_mesh as it stands
+  plane_sweep_torch, filter_depths_torch   the same rules as separate torch ops, on CPU tensors as well: the checks of the kernels
+                  and the timing baseline (tools/time_mvs.py); nothing in the library falls back to them
+
+THE SWEEP RULE and THE CONSISTENCY RULE are stated in include/ls2fm.h and restated in numpy in tests/mvs_restate.py; the kernels,
+the torch forms and the restatement agree bit for bit.  Conventions are the rasteriser's (ls2fm.raster.rasterize): poses world ->
+camera [V, 3, 4], intr [3, 3] or [V, 3, 3], pixel (px, py) has its centre at px + 0.5, depth is camera z.  All views of a call
+share one image size.  Each kernel call is one launch without host read or atomics: it can be captured, a rerun repeats its bits,
+and the chunking of the reference views does not show in them.
+
+Deviations from COLMAP's dense stage, on purpose: the planes are fronto-parallel to the reference (no per-pixel normals); the
+score of a plane is the mean NCC over the valid sources, not the best K of them; there is no PatchMatch propagation -- every pixel
+tries every plane; one image size per call; grey images only; no gradients.
+
+There is no CPU path for the kernels: CPU tensors, a missing device or a missing library raise, as in ls2fm.fusion.
+"""
+from __future__ import annotations
+
+import dataclasses
+import functools
+import math
+
+import torch
+
+from . import _lib, _posed, fusion
+from ._lib import check, ptr, stream_ptr
+
+TILE = 16                   # LS2FM_MVS_TILE
+MAX_HALF_WIDTH = 5          # LS2FM_MVS_MAX_HALF_WIDTH
+MAX_SOURCES = 64            # LS2FM_MVS_MAX_SOURCES
+MAX_PLANES = 65536          # LS2FM_MVS_MAX_PLANES
+_device = functools.partial(_lib.require_device_tensors, "ls2fm.mvs", phrase=": multi-view stereo runs on MI355X only")
+
+
+@dataclasses.dataclass
+class MvsOptions:
+    """The settings of dense_reconstruct; plane_sweep and filter_depths take the same names as keywords."""
+    half_width: int = 3             # w: the window has (2 w + 1)^2 taps
+    near: float = 1e-3
+    min_var: float = 1e-6           # a window whose summed squared deviation is below it carries no texture
+    min_sources: int = 1
+    n_sources: int = 4              # select_sources
+    min_angle: float = 3.0          # degrees
+    max_angle: float = 45.0
+    n_planes: int = 128             # depth_planes
+    inverse_depth: bool = True
+    margin: float = 0.05            # depth_range_from_points
+    max_reproj: float = 1.0         # pixels
+    rel_depth: float = 0.01
+    min_consistent: int = 2
+    max_workspace_bytes: int = 2 ** 28
+
+    def sweep(self):
+        return dict(half_width=self.half_width, near=self.near, min_var=self.min_var, min_sources=self.min_sources,
+                    max_workspace_bytes=self.max_workspace_bytes)
+
+    def filter(self):
+        return dict(near=self.near, max_reproj=self.max_reproj, rel_depth=self.rel_depth, min_consistent=self.min_consistent)
+
+
+# --------------------------------------------------------------------------------------------------------- inputs, as torch ops
+def to_grey(images):
+    """images [V, H, W, 3] (or [H, W, 3]) -> float32 [V, H, W]: (0.299 r + 0.587 g) + 0.114 b; [V, H, W] passes through"""
+    images = torch.as_tensor(images)
+    if images.dim() == 3 and images.shape[-1] != 3:
+        return _lib.cf(images.detach())
+    if images.dim() == 3:
+        images = images[None]
+    if images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"ls2fm.mvs.to_grey: images must be [V, H, W, 3] or [V, H, W], got {tuple(images.shape)}")
+    c = images.detach().float()
+    return ((0.299 * c[..., 0] + 0.587 * c[..., 1]) + 0.114 * c[..., 2]).contiguous()
+
+
+def _compose(pa, pb):
+    """P_a o P_b^-1 of fp64 [..., 3, 4] arrays as elementwise fp64 operations in a stated order (no matrix product: the result
+    does not depend on the device's GEMM):  R_ij = (Ra_i0 Rb_j0 + Ra_i1 Rb_j1) + Ra_i2 Rb_j2;
+    t_i = ta_i - ((R_i0 tb_0 + R_i1 tb_1) + R_i2 tb_2)"""
+    Ra, ta, Rb, tb = pa[..., :3], pa[..., 3], pb[..., :3], pb[..., 3]
+    p = Ra[..., :, None, :] * Rb[..., None, :, :]
+    R = (p[..., 0] + p[..., 1]) + p[..., 2]
+    q = R * tb[..., None, :]
+    t = ta - ((q[..., 0] + q[..., 1]) + q[..., 2])
+    return torch.cat([R, t[..., None]], dim=-1)
+
+
+def relative_poses(pose, refs, sources, back=False):
+    """P_rs = P_s o P_r^-1 per (reference, source) -> float32 [R, S, 3, 4], formed in fp64 with elementwise torch ops on the pose's
+    device and rounded once; with back=True P_sr = P_r o P_s^-1.  pose [V, 3, 4]; refs int [R]; sources int [R, S], whose entries
+    outside [0, V) give an entry that no rule reads."""
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).double()
+    refs = torch.as_tensor(refs, device=P.device).long().reshape(-1)
+    sources = torch.as_tensor(sources, device=P.device).long().reshape(refs.shape[0], -1)
+    V = P.shape[0]
+    Pr = P[refs.clamp(0, V - 1)][:, None]
+    Ps = P[sources.clamp(0, V - 1)]
+    return (_compose(Pr, Ps) if back else _compose(Ps, Pr)).float().contiguous()
+
+
+def depth_planes(near, far, D, inverse=True):
+    """The plane depths of the sweep -> float32 [R, D]: D planes from near to far, uniform in inverse depth (the default, uniform
+    in disparity) or in depth, formed in fp64 and rounded once.  near and far: floats or [R] tensors; D = 1 gives near."""
+    near, far = torch.as_tensor(near), torch.as_tensor(far)
+    dev = near.device if near.is_cuda else far.device
+    near, far = near.double().to(dev).reshape(-1), far.double().to(dev).reshape(-1)
+    D = int(D)
+    if D < 1:
+        raise ValueError(f"ls2fm.mvs.depth_planes: D {D} must be at least 1")
+    t = torch.arange(D, dtype=torch.float64, device=dev) / max(D - 1, 1)
+    if inverse:
+        d = 1.0 / (1.0 / near[:, None] + t * (1.0 / far[:, None] - 1.0 / near[:, None]))
+    else:
+        d = near[:, None] + t * (far[:, None] - near[:, None])
+    return d.float().contiguous()
+
+
+def depth_range_from_points(points, pose, margin=0.05):
+    """Per view the range of camera z of the points in front of it -> (near, far) float32 [V] each: the minimum times 1 - margin
+    and the maximum times 1 + margin, as torch ops; a view with no point in front of it gets NaN.  points: [N, 3], or an
+    ls2fm.mapper.Reconstruction (its valid tracks' X)."""
+    if hasattr(points, "X") and hasattr(points, "track_valid"):
+        points = points.X[points.track_valid]
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).double()
+    X = torch.as_tensor(points).detach().reshape(-1, 3).double().to(P.device)
+    cz = ((P[:, None, 2, 0] * X[None, :, 0] + P[:, None, 2, 1] * X[None, :, 1]) + P[:, None, 2, 2] * X[None, :, 2]) + P[:, None, 2, 3]
+    front = torch.isfinite(cz) & (cz > 0)
+    inf = torch.full_like(cz, math.inf)
+    lo = torch.where(front, cz, inf).amin(dim=1) if X.shape[0] else inf[:, 0]
+    hi = torch.where(front, cz, -inf).amax(dim=1) if X.shape[0] else -inf[:, 0]
+    nan = torch.full_like(lo, math.nan)
+    some = front.any(dim=1)
+    return (torch.where(some, lo * (1.0 - margin), nan).float(), torch.where(some, hi * (1.0 + margin), nan).float())
+
+
+def select_sources(pose, n, min_angle=3.0, max_angle=45.0, centre=None):
+    """Per view its n source views -> int32 [V, n], -1 where fewer qualify; torch ops, no host read.  The other views are ranked
+    by the angle at the scene centre between the two viewing rays (camera centre to scene centre), the smallest first, inside
+    the band [min_angle, max_angle] (degrees); equal angles go to the longer baseline, then to the lower index.  centre: three
+    floats, by default the point nearest to all optical axes in least squares."""
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).double()
+    V, n = int(P.shape[0]), int(n)
+    R, t = P[:, :, :3], P[:, :, 3]
+    C = -(R.transpose(1, 2) @ t[:, :, None])[:, :, 0]
+    if centre is None:
+        z = R[:, 2]
+        M = torch.eye(3, dtype=torch.float64, device=P.device)[None] - z[:, :, None] * z[:, None, :]
+        A, b = M.sum(dim=0), (M @ C[:, :, None]).sum(dim=0)
+        c = (torch.linalg.inv_ex(A).inverse @ b)[:, 0]                 # inv_ex: no status read back
+    else:
+        c = torch.as_tensor(centre, dtype=torch.float64, device=P.device).reshape(3)
+    ray = c[None] - C
+    ray = ray / ray.norm(dim=1, keepdim=True)
+    angle = torch.rad2deg(torch.acos((ray @ ray.T).clamp(-1.0, 1.0)))
+    baseline = (C[:, None] - C[None]).norm(dim=2)
+    ok = (angle >= float(min_angle)) & (angle <= float(max_angle)) & ~torch.eye(V, dtype=torch.bool, device=P.device)
+    key = torch.where(ok, angle, torch.full_like(angle, math.inf))
+    first = torch.argsort(-baseline, dim=1, stable=True)
+    order = torch.gather(first, 1, torch.argsort(torch.gather(key, 1, first), dim=1, stable=True))
+    picked = torch.where(torch.gather(ok, 1, order), order, torch.full_like(order, -1))
+    out = torch.full((V, n), -1, dtype=torch.int64, device=P.device)
+    out[:, :min(n, V)] = picked[:, :n]
+    return out.to(torch.int32)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the kernels
+def _check_sweep(half_width, min_var, min_sources, S, D, who):
+    half_width, min_var, min_sources = int(half_width), float(min_var), int(min_sources)
+    if not 1 <= half_width <= MAX_HALF_WIDTH:
+        raise ValueError(f"{who}: half_width {half_width} must be in [1, {MAX_HALF_WIDTH}]")
+    if not 0.0 <= min_var < math.inf:
+        raise ValueError(f"{who}: min_var {min_var} must be finite and not negative")
+    if not 1 <= S <= MAX_SOURCES or not 1 <= D <= MAX_PLANES:
+        raise ValueError(f"{who}: {S} sources per reference (1 to {MAX_SOURCES}) and {D} planes (1 to {MAX_PLANES})")
+    if not 1 <= min_sources <= S:
+        raise ValueError(f"{who}: min_sources {min_sources} must be in [1, {S}]")
+    return half_width, min_var, min_sources
+
+
+def _check_filter(max_reproj, rel_depth, min_consistent, S, who):
+    max_reproj, rel_depth, min_consistent = float(max_reproj), float(rel_depth), int(min_consistent)
+    if not (0.0 <= max_reproj < math.inf and 0.0 <= rel_depth < math.inf) or min_consistent < 0:
+        raise ValueError(f"{who}: max_reproj {max_reproj} and rel_depth {rel_depth} must be finite and not negative, min_consistent "
+                         f"{min_consistent} not negative")
+    if not 1 <= S <= MAX_SOURCES:
+        raise ValueError(f"{who}: {S} sources per view (1 to {MAX_SOURCES})")
+    return max_reproj, rel_depth, min_consistent
+
+
+def _index_arrays(refs, sources, depths, V, dev, who):
+    refs = torch.arange(V, device=dev) if refs is None else torch.as_tensor(refs, device=dev).reshape(-1)
+    R = int(refs.shape[0])
+    sources = torch.as_tensor(sources, device=dev)
+    if sources.dim() != 2 or sources.shape[0] != R:
+        raise ValueError(f"{who}: sources must be [{R}, S], one row per reference, got {tuple(sources.shape)}")
+    if depths is not None:
+        depths = torch.as_tensor(depths, device=dev)
+        if depths.dim() == 1:
+            depths = depths[None].expand(R, -1)
+        if depths.dim() != 2 or depths.shape[0] != R:
+            raise ValueError(f"{who}: depths must be [D] or [{R}, D], got {tuple(depths.shape)}")
+        depths = depths.detach().float().contiguous()
+    return refs.to(torch.int32).contiguous(), sources.to(torch.int32).contiguous(), depths
+
+
+def _grey(images, n, who):
+    images = torch.as_tensor(images)
+    if images.dim() != 3 or images.shape[0] != n:
+        raise ValueError(f"{who}: images must be grey float [{n}, H, W] (see to_grey), got {tuple(images.shape)}")
+    return _lib.cf(images.detach())
+
+
+@torch.no_grad()
+def plane_sweep(images, pose, intr, sources, depths, refs=None, half_width=3, near=1e-3, min_var=1e-6, min_sources=1,
+                max_workspace_bytes=2 ** 28):
+    """THE SWEEP RULE of include/ls2fm.h -> (depth float32 [R, H, W], score float32 [R, H, W], plane int32 [R, H, W]); an
+    invalid pixel has NaN, NaN and -1.
+      images     grey float32 [V, H, W] (to_grey)
+      pose, intr [V, 3, 4] world-to-camera and [3, 3] or [V, 3, 3], as ls2fm.raster.rasterize
+      refs       int [R], the reference views; default every view
+      sources    int [R, S], per reference its source views; -1 skips (select_sources)
+      depths     float [R, D] or [D], the plane depths (depth_planes)
+    The references go in chunks whose outputs (12 bytes per pixel) stay within max_workspace_bytes, one launch per chunk; the
+    chunking does not show in the bits.  No host read."""
+    who = "ls2fm.mvs.plane_sweep"
+    images = torch.as_tensor(images)
+    _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
+    poses, k4 = _posed.views(pose, intr, who)
+    V, dev = int(poses.shape[0]), poses.device
+    img = _grey(images, V, who)
+    refs, sources, depths = _index_arrays(refs, sources, depths, V, dev, who)
+    R, S, D, H, W = int(refs.shape[0]), int(sources.shape[1]), int(depths.shape[1]), int(img.shape[1]), int(img.shape[2])
+    half_width, min_var, min_sources = _check_sweep(half_width, min_var, min_sources, S, D, who)
+    near = _posed.near_plane(near, who)
+    if img.device != dev:
+        raise ValueError(f"{who}: the poses on {dev}, the images on {img.device}")
+    rel = relative_poses(poses, refs, sources)
+    depth = torch.empty((R, H, W), dtype=torch.float32, device=dev)
+    score = torch.empty((R, H, W), dtype=torch.float32, device=dev)
+    plane = torch.empty((R, H, W), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        for s, e in _posed.chunks(R, 12, H, W, max_workspace_bytes):
+            check(lib.ls2fm_mvs_sweep(ptr(img), V, H, W, ptr(refs[s:e]), e - s, ptr(sources[s:e]), S, ptr(depths[s:e]), D, ptr(rel[s:e]),
+                                      ptr(k4), half_width, near, min_var, min_sources, ptr(depth[s:e]), ptr(score[s:e]), ptr(plane[s:e]),
+                                      stream_ptr()), "ls2fm_mvs_sweep")
+    return depth, score, plane
+
+
+@torch.no_grad()
+def filter_depths(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_depth=0.01, min_consistent=2):
+    """THE CONSISTENCY RULE of include/ls2fm.h -> (filtered float32 [V, H, W], count uint8 [V, H, W]): count is the number of
+    source views whose depth map agrees with the pixel's depth (it projects back within max_reproj pixels and rel_depth d); filtered
+    is the depth where count >= min_consistent and NaN elsewhere -- what ls2fm.fusion.integrate skips.
+      depth      float32 [V, H, W], one map per view (plane_sweep with refs=None); pixels that are not finite and positive count 0
+      sources    int [V, S]; -1 skips
+    One launch, no host read."""
+    who = "ls2fm.mvs.filter_depths"
+    depth = torch.as_tensor(depth)
+    _device(depth, torch.as_tensor(pose), torch.as_tensor(intr))
+    poses, k4 = _posed.views(pose, intr, who)
+    V, dev = int(poses.shape[0]), poses.device
+    d = _grey(depth, V, who)
+    refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
+    S, H, W = int(sources.shape[1]), int(d.shape[1]), int(d.shape[2])
+    max_reproj, rel_depth, min_consistent = _check_filter(max_reproj, rel_depth, min_consistent, S, who)
+    near = _posed.near_plane(near, who)
+    if d.device != dev:
+        raise ValueError(f"{who}: the poses on {dev}, the depth maps on {d.device}")
+    rel, back = relative_poses(poses, refs, sources), relative_poses(poses, refs, sources, back=True)
+    count = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().ls2fm_mvs_filter(ptr(d), V, H, W, ptr(sources), S, ptr(rel), ptr(back), ptr(k4), near, max_reproj, rel_depth,
+                                           min_consistent, ptr(count), ptr(out), stream_ptr()), "ls2fm_mvs_filter")
+    return out, count
+
+
+# -------------------------------------------------------------------------------------------------------------- the torch forms
+def _torch_views(pose, intr, dev):
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(dev)
+    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3).float().to(dev).expand(P.shape[0], 3, 3)
+    return P, K
+
+
+def _taps(Z, w):
+    """the (2 w + 1)^2 shifted views of Z [H, W] in row-major window order; a tap outside the image reads NaN"""
+    H, W = Z.shape
+    pad = torch.full((H + 2 * w, W + 2 * w), math.nan, dtype=Z.dtype, device=Z.device)
+    pad[w:w + H, w:w + W] = Z
+    return [pad[i:i + H, j:j + W] for i in range(2 * w + 1) for j in range(2 * w + 1)]
+
+
+def _tap_sum(taps):
+    total = torch.zeros_like(taps[0])
+    for t in taps:
+        total = total + t
+    return total
+
+
+def _sqrt_rn(t):
+    """the correctly rounded fp32 square root: torch.sqrt of a float32 tensor is not correctly rounded on every backend (the CPU's
+    vectorised one is not); the fp64 root rounded to fp32 is, since 53 >= 2 * 24 + 2 bits leave no double rounding"""
+    return torch.sqrt(t.double()).float()
+
+
+def _lift(K, H, W, dev):
+    """xn [1, W] and yn [H, 1] of every pixel centre"""
+    xn = ((torch.arange(W, device=dev).float() + 0.5) - K[0, 2]) / K[0, 0]
+    yn = ((torch.arange(H, device=dev).float() + 0.5) - K[1, 2]) / K[1, 1]
+    return xn[None, :], yn[:, None]
+
+
+@torch.no_grad()
+def plane_sweep_torch(images, pose, intr, sources, depths, refs=None, half_width=3, near=1e-3, min_var=1e-6, min_sources=1):
+    """THE SWEEP RULE as plain torch ops on the images' device (a CPU works), vectorised over the pixels of one reference, the
+    references, planes, sources and taps in loops: the same operations in the same order, each a separate op, so each rounds
+    once.  A non-finite or invalid sample is a NaN, and a window's sum is NaN exactly when one of its taps is.  Reads `refs` and
+    `sources` on the host.  -> (depth, score, plane) as plane_sweep."""
+    who = "ls2fm.mvs.plane_sweep_torch"
+    img = torch.as_tensor(images).detach().float()
+    dev = img.device
+    P, K = _torch_views(pose, intr, dev)
+    V = int(P.shape[0])
+    img = _grey(img, V, who)
+    refs, sources, depths = _index_arrays(refs, sources, depths, V, dev, who)
+    R, S, D, H, W = int(refs.shape[0]), int(sources.shape[1]), int(depths.shape[1]), int(img.shape[1]), int(img.shape[2])
+    w, min_var, min_sources = _check_sweep(half_width, min_var, min_sources, S, D, who)
+    rel = relative_poses(P, refs, sources)
+    # 0-dim device tensors: a division by a Python scalar would be a multiplication by its reciprocal
+    scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
+    n, near, min_var = scalar((2 * w + 1) ** 2), scalar(_posed.near_plane(near, who)), scalar(min_var)
+    nan = torch.full((H, W), math.nan, dtype=torch.float32, device=dev)
+    finite = lambda t: torch.where(torch.isfinite(t), t, nan)
+    out_d, out_s = nan.repeat(R, 1, 1), nan.repeat(R, 1, 1)
+    out_k = torch.full((R, H, W), -1, dtype=torch.int32, device=dev)
+    last = H * W - 1
+    for r, (rv, srcs) in enumerate(zip(refs.tolist(), sources.tolist())):
+        if not 0 <= rv < V:
+            continue
+        # 1. the reference window
+        a = _taps(finite(img[rv]), w)
+        sa = _tap_sum(a)
+        ma = sa / n
+        da = [t - ma for t in a]
+        va = torch.zeros_like(sa)
+        for t in da:
+            va = va + t * t
+        pixel_ok = ~torch.isnan(sa) & ~(va < min_var)
+        xn, yn = _lift(K[rv], H, W, dev)
+        best, before, after, previous = nan, nan, nan, nan
+        best_k = torch.full((H, W), -1, dtype=torch.int64, device=dev)
+        for k in range(D):
+            d = depths[r, k]
+            total, count = torch.zeros_like(sa), torch.zeros((H, W), dtype=torch.int64, device=dev)
+            for s, sv in enumerate(srcs):
+                if not 0 <= sv < V:
+                    continue
+                # 2. warp, 3. sample
+                x, y = (xn * d).expand(H, W).reshape(-1), (yn * d).expand(H, W).reshape(-1)
+                _, u, v, usable, _, _, _ = _posed.project_torch(rel[r, s], K[sv], x, y, d.expand(H * W), near, H, W)
+                fx, fy = u - 0.5, v - 0.5
+                x0, y0 = fx.floor(), fy.floor()
+                tx, ty = fx - x0, fy - y0
+                ok = usable & (x0 >= 0) & (x0 <= W - 2) & (y0 >= 0) & (y0 <= H - 2)
+                zero = torch.zeros_like(x0)
+                at = torch.where(ok, y0, zero).long() * W + torch.where(ok, x0, zero).long()
+                src = img[sv].reshape(-1)
+                b00, b10 = src[at], src[(at + 1).clamp(max=last)]
+                b01, b11 = src[(at + W).clamp(max=last)], src[(at + W + 1).clamp(max=last)]
+                r0 = b00 + tx * (b10 - b00)
+                r1 = b01 + tx * (b11 - b01)
+                b = r0 + ty * (r1 - r0)
+                b = torch.where(ok & torch.isfinite(b), b, nan.reshape(-1)).reshape(H, W)
+                # 4. NCC
+                bt = _taps(b, w)
+                sb = _tap_sum(bt)
+                mb = sb / n
+                vb, cov = torch.zeros_like(sb), torch.zeros_like(sb)
+                for ai, t in zip(da, bt):
+                    db = t - mb
+                    vb = vb + db * db
+                    cov = cov + ai * db
+                valid = pixel_ok & ~torch.isnan(sb) & ~(vb < min_var)
+                ncc = cov / _sqrt_rn(va * vb)
+                total = torch.where(valid, total + ncc, total)
+                count = count + valid
+            # 5. aggregate, 6. select
+            score = torch.where(count >= min_sources, total / count.float(), nan)
+            better = ~torch.isnan(score) & ((best_k < 0) | (score > best))
+            follows = ~better & (best_k + 1 == k)
+            before = torch.where(better, previous, before)
+            after = torch.where(better, nan, torch.where(follows, score, after))
+            best = torch.where(better, score, best)
+            best_k = torch.where(better, torch.full_like(best_k, k), best_k)
+            previous = score
+        # 7. refine
+        dr = depths[r]
+        d0, dn, dp = dr[best_k.clamp(0, D - 1)], dr[(best_k + 1).clamp(0, D - 1)], dr[(best_k - 1).clamp(0, D - 1)]
+        den = (before - 2.0 * best) + after
+        off = (0.5 * (before - after)) / den
+        step = torch.where(off >= 0, dn - d0, d0 - dp)
+        refined = torch.where((best_k > 0) & (best_k < D - 1) & (den < 0), d0 + off * step, d0)
+        out_d[r] = torch.where(best_k >= 0, refined, nan)
+        out_s[r] = best
+        out_k[r] = best_k.to(torch.int32)
+    return out_d, out_s, out_k
+
+
+@torch.no_grad()
+def filter_depths_torch(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_depth=0.01, min_consistent=2):
+    """THE CONSISTENCY RULE as plain torch ops on the depth maps' device (a CPU works), vectorised over the pixels of one view.
+    Reads `sources` on the host.  -> (filtered, count) as filter_depths."""
+    who = "ls2fm.mvs.filter_depths_torch"
+    depth = torch.as_tensor(depth).detach().float()
+    dev = depth.device
+    P, K = _torch_views(pose, intr, dev)
+    V = int(P.shape[0])
+    depth = _grey(depth, V, who)
+    refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
+    S, H, W = int(sources.shape[1]), int(depth.shape[1]), int(depth.shape[2])
+    max_reproj, rel_depth, min_consistent = _check_filter(max_reproj, rel_depth, min_consistent, S, who)
+    rel, back = relative_poses(P, refs, sources), relative_poses(P, refs, sources, back=True)
+    scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
+    near, max_reproj, rel_depth = scalar(_posed.near_plane(near, who)), scalar(max_reproj), scalar(rel_depth)
+    reproj2 = max_reproj * max_reproj
+    count = torch.zeros((V, H * W), dtype=torch.int64, device=dev)
+    centre = lambda n: torch.arange(n, device=dev).float() + 0.5
+    uc, vc = centre(W)[None, :].expand(H, W).reshape(-1), centre(H)[:, None].expand(H, W).reshape(-1)
+    for r, srcs in enumerate(sources.tolist()):
+        d = depth[r].reshape(-1)
+        has = torch.isfinite(d) & (d > 0)
+        X, Y = ((uc - K[r, 0, 2]) / K[r, 0, 0]) * d, ((vc - K[r, 1, 2]) / K[r, 1, 1]) * d
+        dz = rel_depth * d
+        for s, sv in enumerate(srcs):
+            if not 0 <= sv < V:
+                continue
+            _, _, _, _, ok, sx, sy = _posed.project_torch(rel[r, s], K[sv], X, Y, d, near, H, W)
+            ds = depth[sv].reshape(-1)[sy * W + sx]
+            ok = has & ok & torch.isfinite(ds) & (ds > 0)
+            Xs = (((sx.float() + 0.5) - K[sv, 0, 2]) / K[sv, 0, 0]) * ds
+            Ys = (((sy.float() + 0.5) - K[sv, 1, 2]) / K[sv, 1, 1]) * ds
+            c, u, v, usable, _, _, _ = _posed.project_torch(back[r, s], K[r], Xs, Ys, ds, near, H, W)
+            du, dv = u - uc, v - vc
+            e = du * du + dv * dv
+            count[r] += ok & usable & (e <= reproj2) & ((c[2] - d).abs() <= dz)
+    flat = depth.reshape(V, -1)
+    out = torch.where(count >= min_consistent, flat, torch.full_like(flat, math.nan))
+    return out.reshape(V, H, W), count.to(torch.uint8).reshape(V, H, W)
+
+
+# ------------------------------------------------------------------------------------------------------------------ end to end
+@torch.no_grad()
+def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=None, points=None, options=None, trunc=None,
+                      min_weight=1.0, return_depth=False):
+    """Photographs to a surface: plane_sweep over every view -> filter_depths -> ls2fm.fusion.volume_for(bounds, voxel, trunc) ->
+    fusion.integrate -> fusion.extract -> ls2fm.mesh.Mesh, in the poses' world frame.
+      images     [V, H, W, 3] colour (to_grey) or grey [V, H, W]
+      sources    int [V, S]; default select_sources(pose, options.n_sources, options.min_angle, options.max_angle)
+      depths     float [V, D]; default depth_planes over depth_range_from_points of `points` (an [N, 3] cloud or an
+                 ls2fm.mapper.Reconstruction), or of the eight corners of `bounds` when there are none
+      options    MvsOptions
+    Host reads: those of fusion.extract.  With return_depth: (Mesh, filtered depth [V, H, W], count uint8 [V, H, W])."""
+    opt = MvsOptions() if options is None else options
+    images = torch.as_tensor(images)
+    _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
+    grey = to_grey(images)
+    if sources is None:
+        sources = select_sources(pose, opt.n_sources, opt.min_angle, opt.max_angle)
+    if depths is None:
+        if points is None:
+            lo, hi = ([float(v) for v in b] for b in bounds)
+            points = torch.tensor([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=torch.float64)
+        near, far = depth_range_from_points(points, pose, opt.margin)
+        depths = depth_planes(near, far, opt.n_planes, opt.inverse_depth)
+    depth, _, _ = plane_sweep(grey, pose, intr, sources, depths, **opt.sweep())
+    filtered, count = filter_depths(depth, pose, intr, sources, **opt.filter())
+    volume = fusion.volume_for(bounds, voxel, trunc, grey.device)
+    fusion.integrate(volume, filtered, pose, intr, near=opt.near)
+    out = fusion.extract(volume, min_weight)
+    return (out, filtered, count) if return_depth else out
