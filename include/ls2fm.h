@@ -1281,6 +1281,49 @@ int ls2fm_point_grid_query(const float* queries, int64_t n_queries, const float*
                            float* d2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The k nearest neighbours of a query and the normals of a cloud (csrc/point_grid.hip, csrc/cloud_normals.hip behind
+ * ls2fm.metrics.PointGrid.knn and ls2fm.cloud; additions, the library stays ABI 13).  The reference ships none.
+ * tests/cloud_restate.py repeats both rules in numpy.
+ *
+ * K-NEIGHBOUR RULE  under the distance rule and its qualification (d2 <= max_d2 and d2 < +inf, above) the neighbours of a query
+ *   are its qualifying references ordered by (d2, index) ascending, the first k of them, 1 <= k <= 32.  idx int32 [n_queries][k]
+ *   holds their indices and -1 in the slots without a neighbour, d2 float [n_queries][k] their d2 and +inf in those slots,
+ *   count int32 [n_queries] how many slots are filled.  A NaN or infinite query has none.  With skip_own != 0 query t ignores the
+ *   reference whose original index is t: the caller promises that the queries are the references in their order, and the call is
+ *   refused unless n_queries == n_points; a duplicate of point t at another index stays a neighbour at d2 = 0.  The result is a
+ *   pure function of the two clouds, k, max_d2 and the flag: no grid, batch, visiting order or list capacity shows in it.
+ * knn  one launch, one query per lane, the rings of the query above with a sorted list of the k best in registers (capacities 8,
+ *   16 and 32 are instantiated; the smallest that holds k runs).  After ring r the walk stops when
+ *   min(d2 of the k-th entry -- +inf while there are fewer than k --, max_d2) < ring bound of r, strictly, for the reason given
+ *   above; the whole-grid exit is unchanged.  Nothing is read back: the call can be captured into a graph.  n_queries = 0 returns
+ *   at once; n_points = 0 fills -1 / +inf / 0 without a launch.  Refused as the query refuses, and for k outside 1 .. 32.
+ *
+ * NORMAL RULE  of points float [n_points][3] and a neighbour list idx int32 [n_queries][k] (k >= 1; rows of the knn above, or any
+ *   other list).  Per query, over the n entries with 0 <= idx < n_points in list order (any other entry is no neighbour),
+ *   everything in fp64 of the fp32 inputs, every operation rounded once, none contracted:
+ *     mean        m = (((p0 + p1) + p2) + ...) / n
+ *     covariance  d_j = p_j - m;  C_ab = (((d_0a d_0b + d_1a d_1b) + d_2a d_2b) + ...) / n, the six entries xx xy xz yy yz zz
+ *     eigen       the cyclic Jacobi of the symmetric 3 x 3 (pose_math.h's jacobi3_sym: the threshold, sweep cap and rotation
+ *                 formulas of jacobi4); lambda_i is the diagonal after it.  The normal is the eigenvector of the smallest
+ *                 lambda, the lowest index among equals, divided by its length sqrt((v.x v.x + v.y v.y) + v.z v.z);
+ *                 curvature = that lambda / ((lambda_0 + lambda_1) + lambda_2)
+ *     n < 3, or a trace (C_xx + C_yy) + C_zz that is zero or NaN: NaN for the normal and the curvature (cov is still C; NaN for
+ *                 n = 0)
+ *     orientation with toward float [1 or n_queries][3] and queries float [n_queries][3]: the normal is negated when
+ *                 (v.x t.x + v.y t.y) + v.z t.z < 0, t = toward - query in fp64 (zero keeps the sign).  Without toward: negated
+ *                 when its component of largest magnitude, the lowest axis among equals, is negative.
+ *   -> normal double [n_queries][3], curvature double [n_queries], cov double [n_queries][6] (may be NULL).
+ * normals  one launch, one query per lane, k gathers from points (twice: mean, covariance); no atomics, no workspace, nothing
+ *   read back.  Refused: a NULL array that is needed, a negative count, n_points >= 2^31, k < 1, toward without queries or with
+ *   n_toward neither 1 nor n_queries.
+ */
+int ls2fm_point_grid_knn(const float* queries, int64_t n_queries, const float* sorted, const int32_t* cell_start, int64_t n_points,
+                         const float* origin, float cell_size, float inv_cell_size, const int32_t* dim, int32_t k, float max_d2,
+                         int32_t skip_own, int32_t* idx, float* d2, int32_t* count, void* stream);
+int ls2fm_cloud_normals(const float* points, int64_t n_points, const int32_t* idx, int64_t n_queries, int32_t k, const float* queries,
+                        const float* toward, int64_t n_toward, double* normal, double* curvature, double* cov, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP registration of a moving cloud to a fixed one (csrc/icp.hip behind ls2fm.metrics.icp; additions, the library stays ABI
  * 13): the step between the camera alignment and the Chamfer figures of a reconstruction in its own gauge.  The reference ships
  * none.  tests/icp_restate.py repeats the rule in numpy.

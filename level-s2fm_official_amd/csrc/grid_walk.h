@@ -1,5 +1,6 @@
-// The walk of the uniform point grid, stated once for point_grid.hip (pg_query) and icp.hip (icp_accumulate): the grid's
-// description, the cell assignment, the distance rule, the ring bound and the ring loop.  include/ls2fm.h states the rules;
+// The walk of the uniform point grid, stated once for point_grid.hip (pg_query, pg_knn) and icp.hip (icp_accumulate): the grid's
+// description, the cell assignment, the distance rule, the ring bound and the ring loops -- nearest for the one nearest
+// reference, k_nearest for the k nearest in a register-resident sorted list.  include/ls2fm.h states the rules;
 // tests/metrics_restate.py repeats the distance rule in numpy.  Every routine is a fixed sequence of fp32 operations, so the
 // winner, its d2 and its coordinates are the same bits in whichever file includes it.
 #pragma once
@@ -98,6 +99,91 @@ __device__ __forceinline__ Best nearest(const PgGrid& g, const float4* __restric
         if (cx - k <= 0 && cx + k >= g.nx - 1 && cy - k <= 0 && cy + k >= g.ny - 1 && cz - k <= 0 && cz + k >= g.nz - 1) break;   // the whole grid
     }
     return b;
+}
+
+// ------------------------------------------------------------------------------------------------------------- k nearest
+// The K-NEIGHBOUR RULE (include/ls2fm.h): the qualifying references ordered by (d2, index) ascending, the first k of them.
+// KList is that list in registers: CAP slots kept sorted, an empty slot being (+inf, INT_MAX), which every qualifying candidate
+// precedes.  Every index into it is a compile-time one (full unrolling): a runtime index would send it to scratch or to LDS.
+// The runtime k is the WORST SLOT: (wd2, wi) is a copy of slot k - 1, a candidate enters only when it precedes that, and the
+// walk stops on wd2 -- +inf while fewer than k are held.  Slots k .. CAP - 1 would only ever receive what slot k - 1 sheds; they
+// are never read and the insertion skips them, so the capacity shows neither in the result nor in the insertion's length.
+template <int CAP>
+struct KList {
+    float d2[CAP];
+    int32_t i[CAP];
+    float wd2;
+    int32_t wi;
+};
+
+template <int CAP>
+__device__ __forceinline__ void klist_init(KList<CAP>& l) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) { l.d2[j] = INFINITY; l.i[j] = INT_MAX; }
+    l.wd2 = INFINITY;
+    l.wi = INT_MAX;
+}
+
+__device__ __forceinline__ bool precedes(float d2, int32_t i, float e_d2, int32_t e_i) { return d2 < e_d2 || (d2 == e_d2 && i < e_i); }
+
+// compare-and-shift: slot j takes its left neighbour when the candidate precedes that one, the candidate when it precedes only
+// slot j itself, and keeps its entry otherwise (slots are updated from the right, so slot j - 1 is still the old one)
+template <int CAP>
+__device__ __forceinline__ void klist_insert(KList<CAP>& l, int k, float d2, int32_t i) {
+#pragma unroll
+    for (int j = CAP - 1; j >= 1; --j) {
+        if (j >= k) continue;                                   // never read; k is uniform, so this is a scalar branch
+        const bool left = precedes(d2, i, l.d2[j - 1], l.i[j - 1]);
+        const bool here = precedes(d2, i, l.d2[j], l.i[j]);
+        l.d2[j] = left ? l.d2[j - 1] : (here ? d2 : l.d2[j]);
+        l.i[j] = left ? l.i[j - 1] : (here ? i : l.i[j]);
+    }
+    if (precedes(d2, i, l.d2[0], l.i[0])) { l.d2[0] = d2; l.i[0] = i; }
+#pragma unroll
+    for (int j = 0; j < CAP; ++j)
+        if (j == k - 1) { l.wd2 = l.d2[j]; l.wi = l.i[j]; }
+}
+
+// skip: the original index that is not a neighbour (skip_own), -1 for none
+template <int CAP>
+__device__ __forceinline__ void visit_k(const float4* __restrict__ sorted, int32_t s, int32_t e, float qx, float qy, float qz,
+                                        float max_d2, int32_t skip, int k, KList<CAP>& l) {
+    for (int32_t p = s; p < e; ++p) {
+        const float4 r = sorted[p];
+        const float d2 = d2_rule(qx, qy, qz, r.x, r.y, r.z);
+        const int32_t i = __float_as_int(r.w);
+        if (d2 <= max_d2 && d2 < INFINITY && i != skip && precedes(d2, i, l.wd2, l.wi)) klist_insert(l, k, d2, i);
+    }
+}
+
+// nearest's ring loop with the list in Best's place.  A row of the shell is one range of cell_start, a row through its inside
+// two single cells; both go through the one visit_k below, so that the unrolled insertion is instantiated once.
+template <int CAP>
+__device__ __forceinline__ void k_nearest(const PgGrid& g, const float4* __restrict__ sorted, const int32_t* __restrict__ cell_start,
+                                          float qx, float qy, float qz, float max_d2, int32_t skip, int k, int max_rings, KList<CAP>& l) {
+    klist_init(l);
+    const int cx = cell_axis(qx, g.ox, g.inv_h, g.nx), cy = cell_axis(qy, g.oy, g.inv_h, g.ny), cz = cell_axis(qz, g.oz, g.inv_h, g.nz);
+    const bool finite = isfinite(qx) && isfinite(qy) && isfinite(qz);
+    for (int r = 0; finite && r < max_rings; ++r) {
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
+        for (int z = z0; z <= z1; ++z) {
+            const bool z_face = z == cz - r || z == cz + r;
+            for (int y = y0; y <= y1; ++y) {
+                const int64_t row = ((int64_t)z * g.ny + y) * g.nx;
+                const bool whole = z_face || y == cy - r || y == cy + r;
+                for (int part = 0; part < (whole ? 1 : 2); ++part) {
+                    const int xa = whole ? x0 : (part == 0 ? cx - r : cx + r);
+                    const int xb = whole ? x1 : xa;
+                    if (xa < 0 || xb >= g.nx) continue;                      // that side of the shell lies outside the grid
+                    visit_k(sorted, cell_start[row + xa], cell_start[row + xb + 1], qx, qy, qz, max_d2, skip, k, l);
+                }
+            }
+        }
+        if (fminf(l.wd2, max_d2) < ring_bound(g, r)) break;
+        if (cx - r <= 0 && cx + r >= g.nx - 1 && cy - r <= 0 && cy + r >= g.ny - 1 && cz - r <= 0 && cz + r >= g.nz - 1) break;   // the whole grid
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host

@@ -14,7 +14,9 @@
 //   pg_scatter    one lane per reference point: slot = cell_start[cell] + cursor[cell]++, sorted[slot] = (x, y, z, bits of index).
 //                 The order inside a cell is the order the atomics arrived in; it cannot show, ties break on the stored index.
 // ls2fm_point_grid_query (one launch): pg_query, one query per lane -- its own cell, then Chebyshev rings 1, 2, ... (ring_bound).
-// The walk itself -- cells, distance rule, ring bound, ring loop -- is grid_walk.h's, shared with icp.hip.
+// ls2fm_point_grid_knn (one launch): pg_knn<8 | 16 | 32>, one query per lane, the K-NEIGHBOUR RULE: the same rings with a sorted
+// list of the k best in registers (KList, k_nearest), the instantiation the smallest capacity >= k.
+// The walk itself -- cells, distance rule, ring bound, ring loops -- is grid_walk.h's, shared with icp.hip.
 #include "grid_walk.h"
 #include "ls2fm_device.h"
 #include "workspace.h"
@@ -90,6 +92,34 @@ pg_query(PgGrid g, const float4* __restrict__ sorted, const int32_t* __restrict_
     d2_out[t] = b.d2;
 }
 
+// KList and the ring loop (k_nearest): grid_walk.h.  Row t of idx / d2 is the list's first k slots; only compile-time slots.
+template <int CAP>
+__global__ void __launch_bounds__(kThreads)
+pg_knn(PgGrid g, const float4* __restrict__ sorted, const int32_t* __restrict__ cell_start, const float* __restrict__ q, int64_t m, int k,
+       float max_d2, int skip_own, int max_rings, int32_t* __restrict__ idx, float* __restrict__ d2_out, int32_t* __restrict__ count) {
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t >= m) return;
+    KList<CAP> l;
+    k_nearest<CAP>(g, sorted, cell_start, q[3 * t], q[3 * t + 1], q[3 * t + 2], max_d2, skip_own ? (int32_t)t : -1, k, max_rings, l);
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+        if (j < k) {
+            const bool has = l.d2[j] < INFINITY;
+            idx[t * k + j] = has ? l.i[j] : -1;
+            d2_out[t * k + j] = l.d2[j];
+            n += has ? 1 : 0;
+        }
+    }
+    count[t] = n;
+}
+
+template <int CAP>
+void launch_knn(unsigned blocks, hipStream_t s, const PgGrid& g, const float* sorted, const int32_t* cell_start, const float* q, int64_t m,
+                int k, float max_d2, int skip_own, int max_rings, int32_t* idx, float* d2, int32_t* count) {
+    pg_knn<CAP><<<blocks, kThreads, 0, s>>>(g, (const float4*)sorted, cell_start, q, m, k, max_d2, skip_own, max_rings, idx, d2, count);
+}
+
 // ------------------------------------------------------------------------------------------------------------------- host
 // grid_ok, make_grid and max_rings: grid_walk.h
 int64_t scan_blocks(int64_t n_cells) { return (n_cells + kScanThreads - 1) / kScanThreads; }
@@ -159,5 +189,32 @@ extern "C" int ls2fm_point_grid_query(const float* queries, int64_t n_queries, c
     const int64_t blocks = (n_queries + kThreads - 1) / kThreads;
     LS2FM_CHECK_ARG(blocks < ((int64_t)1 << 31));
     pg_query<<<(unsigned)blocks, kThreads, 0, s>>>(g, (const float4*)sorted, cell_start, queries, n_queries, max_d2, max_rings(dim), idx, d2);
+    return ls2fm_launch_status();
+}
+
+extern "C" int ls2fm_point_grid_knn(const float* queries, int64_t n_queries, const float* sorted, const int32_t* cell_start,
+                                    int64_t n_points, const float* origin, float cell_size, float inv_cell_size, const int32_t* dim,
+                                    int32_t k, float max_d2, int32_t skip_own, int32_t* idx, float* d2, int32_t* count, void* stream) {
+    int64_t n_cells = 0;
+    LS2FM_CHECK_ARG(n_queries >= 0 && n_points >= 0 && n_points < ((int64_t)1 << 31) && grid_ok(origin, cell_size, inv_cell_size, dim, &n_cells));
+    LS2FM_CHECK_ARG(!(max_d2 != max_d2) && max_d2 >= 0.0f && k >= 1 && k <= 32);
+    LS2FM_CHECK_ARG(!skip_own || n_queries == n_points);
+    if (n_queries == 0) return LS2FM_OK;
+    LS2FM_CHECK_ARG(queries && idx && d2 && count);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_points == 0) {                       // no reference: every slot is empty
+        if (hipMemsetD32Async((hipDeviceptr_t)idx, -1, (size_t)n_queries * k, s) != hipSuccess) return ls2fm_launch_status();
+        if (hipMemsetD32Async((hipDeviceptr_t)d2, 0x7f800000, (size_t)n_queries * k, s) != hipSuccess) return ls2fm_launch_status();
+        if (hipMemsetD32Async((hipDeviceptr_t)count, 0, (size_t)n_queries, s) != hipSuccess) return ls2fm_launch_status();
+        return LS2FM_OK;
+    }
+    LS2FM_CHECK_ARG(sorted && cell_start && ((uintptr_t)sorted & 15) == 0);
+    const PgGrid g = make_grid(origin, cell_size, inv_cell_size, dim);
+    const int64_t blocks = (n_queries + kThreads - 1) / kThreads;
+    LS2FM_CHECK_ARG(blocks < ((int64_t)1 << 31));
+    const int rings = max_rings(dim);
+    if (k <= 8) launch_knn<8>((unsigned)blocks, s, g, sorted, cell_start, queries, n_queries, k, max_d2, skip_own, rings, idx, d2, count);
+    else if (k <= 16) launch_knn<16>((unsigned)blocks, s, g, sorted, cell_start, queries, n_queries, k, max_d2, skip_own, rings, idx, d2, count);
+    else launch_knn<32>((unsigned)blocks, s, g, sorted, cell_start, queries, n_queries, k, max_d2, skip_own, rings, idx, d2, count);
     return ls2fm_launch_status();
 }

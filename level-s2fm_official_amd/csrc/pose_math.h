@@ -244,4 +244,52 @@ HD inline void jacobi4(double (&a)[10], double (&V)[4][4]) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------- symmetric Jacobi, 3 x 3
+// jacobi4's rules at size 3 (cloud_normals.hip: the covariance of a neighbourhood): a = upper triangle row-major (00 01 02 11 12
+// 22); on return its diagonal entries are the eigenvalues and V[k] the eigenvector of eigenvalue k
+constexpr int sidx3(int i, int j) { return i <= j ? i * 3 - (i * (i - 1)) / 2 + (j - i) : j * 3 - (j * (j - 1)) / 2 + (i - j); }
+
+HD inline void jacobi3_sym(double (&a)[6], double (&V)[3][3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) V[k][r] = k == r ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        double off = 0.0, dia = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            dia += a[sidx3(i, i)] * a[sidx3(i, i)];
+#pragma unroll
+            for (int j = i + 1; j < 3; ++j) off += a[sidx3(i, j)] * a[sidx3(i, j)];
+        }
+        if (!(off > 1e-30 * dia)) break;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = a[sidx3(p, q)];
+                if (apq == 0.0) continue;
+                const double theta = (a[sidx3(q, q)] - a[sidx3(p, p)]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (k == p || k == q) continue;
+                    const double akp = a[sidx3(k, p)], akq = a[sidx3(k, q)];
+                    a[sidx3(k, p)] = c * akp - s * akq;
+                    a[sidx3(k, q)] = s * akp + c * akq;
+                }
+                a[sidx3(p, p)] = a[sidx3(p, p)] - t * apq;
+                a[sidx3(q, q)] = a[sidx3(q, q)] + t * apq;
+                a[sidx3(p, q)] = 0.0;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double vp = V[p][r], vq = V[q][r];
+                    V[p][r] = c * vp - s * vq;
+                    V[q][r] = s * vp + c * vq;
+                }
+            }
+    }
+}
+
 }  // namespace pose_math

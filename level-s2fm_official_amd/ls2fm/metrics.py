@@ -2,7 +2,9 @@
 similarity alignment (rotation in degrees, ATE) and the DTU Chamfer distance of the mesh (accuracy, completeness, their mean); the
 reference ships neither, and the usual CPU KD-tree evaluation of two DTU-sized clouds takes minutes per scan.
 
-  PointGrid / nearest_neighbors   exact nearest neighbours over a uniform grid (ls2fm_point_grid_*, csrc/point_grid.hip)
+  PointGrid / nearest_neighbors   exact nearest neighbours over a uniform grid (ls2fm_point_grid_*, csrc/point_grid.hip);
+                                  PointGrid.knn: the k nearest (ls2fm.cloud builds normals and outlier filters on it)
+  normal_consistency              mean |n . n'| over the nearest-neighbour pairs, both directions
   nearest_neighbors_bruteforce    the same rule as plain torch ops on any device: the timing baseline and the host tests' route
   voxel_downsample                one point per voxel, the lowest index
   chamfer / evaluate_mesh         accuracy, completeness, overall, precision / recall / F-score
@@ -175,6 +177,48 @@ class PointGrid:
                 idx, d2 = torch.empty_like(idx).index_copy_(0, perm, idx), torch.empty_like(d2).index_copy_(0, perm, d2)
         return idx, d2
 
+    def knn(self, q, k, max_dist=None, skip_own=False, sort=None):
+        """(idx int32 [M, k], d2 float32 [M, k], count int32 [M]) of the queries `q`: each query's qualifying references ordered by
+        (d2, index), the first k of them (1 <= k <= KNN_MAX_K; the K-NEIGHBOUR RULE of include/ls2fm.h), -1 / +inf in the slots
+        without one and the number of filled slots.  skip_own: query t ignores reference t -- `q` must be the grid's own cloud
+        in its order (M == N is checked, the rest is the caller's promise); a duplicate at another index stays a neighbour.
+        One launch (ls2fm_point_grid_knn), nothing read back; the cell-order walk, its put-back and `sort` are `query`'s."""
+        q = _points(q, "q")
+        _device(q)
+        if q.device != self.device:
+            raise ValueError(f"ls2fm.metrics.PointGrid.knn: queries on {q.device}, the grid on {self.device}")
+        k = _knn_k(k)
+        q = _lib.cf(q)
+        max_d2 = _max_d2(max_dist)
+        m = int(q.shape[0])
+        if skip_own and m != self.n:
+            raise ValueError(f"ls2fm.metrics.PointGrid.knn: skip_own needs the grid's own cloud as queries, got {m} queries for {self.n} points")
+        with torch.cuda.device(self.device):
+            capturing = torch.cuda.is_current_stream_capturing()
+            perm = None
+            # skip_own identifies a query by its position: those are walked as given
+            if (sort is None or sort) and not capturing and not skip_own and m > 1 and self.n:
+                perm = self._order(q)
+                q = q[perm]
+            idx = torch.empty(m, k, dtype=torch.int32, device=self.device)
+            d2 = torch.empty(m, k, dtype=torch.float32, device=self.device)
+            count = torch.empty(m, dtype=torch.int32, device=self.device)
+            check(_lib.load().ls2fm_point_grid_knn(ptr(q), m, ptr(self.sorted), ptr(self.cell_start), self.n, self._origin,
+                                                   self.cell_size, self.inv_cell_size, self._dim, k, float(max_d2), 1 if skip_own else 0,
+                                                   ptr(idx), ptr(d2), ptr(count), stream_ptr()), "ls2fm_point_grid_knn")
+            if perm is not None:
+                idx, d2, count = (torch.empty_like(x).index_copy_(0, perm, x) for x in (idx, d2, count))
+        return idx, d2, count
+
+
+KNN_MAX_K = 32                            # the largest list capacity ls2fm_point_grid_knn instantiates
+
+
+def _knn_k(k):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError(f"ls2fm.metrics: k {k} must be an integer in [1, {KNN_MAX_K}]")
+    return int(k)
+
 
 def nearest_neighbors(q, ref, max_dist=None, cell_size=None):
     """PointGrid(ref, cell_size).query(q, max_dist) in one call: (idx int32 [M], d2 float32 [M])"""
@@ -298,6 +342,37 @@ def _chamfer_dict(a, c, thresholds):
     f = tuple((2.0 * p * r / (p + r)) if p + r > 0 else (0.0 if p + r == 0 else float("nan")) for p, r in zip(prec, rec))
     return dict(accuracy=a[1], completeness=c[1], overall=0.5 * (a[1] + c[1]), n_accuracy=int(a[0]), n_completeness=int(c[0]),
                 thresholds=thresholds, precision=prec, recall=rec, fscore=f)
+
+
+def _consistency_side(q, qn, ref, refn, max_dist):
+    """fp64 [2] on the device: the number of queries with a reference inside max_dist and the mean of |n_q . n_ref| over them"""
+    idx, _ = nearest_neighbors(q, ref, max_dist)
+    has = idx >= 0
+    a, b = qn.to(torch.float64), refn.to(torch.float64)[idx.clamp(min=0).long()]
+    dot = ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]).abs()
+    n = has.sum().to(torch.float64)
+    return torch.stack([n, torch.where(has, dot, torch.zeros_like(dot)).sum() / n])
+
+
+def normal_consistency(pred_points, pred_normals, gt_points, gt_normals, max_dist):
+    """The normal consistency the neural-surface papers report beside Chamfer (MonoSDF, NeuRIS), in both directions: a dict of
+      accuracy        the fp64 mean of |n_pred . n_gt| over the points of `pred` paired with their nearest point of `gt` inside max_dist
+      completeness    the same from `gt` to `pred`;  overall: the mean of the two
+      n_accuracy, n_completeness   the numbers of pairs (ints)
+    (and, empty, the threshold entries of `chamfer`'s dict).  The pairs are PointGrid.query's; the absolute value is there because
+    estimated normals (ls2fm.cloud.estimate_normals) are unoriented.  Normals are taken as given, not normalised.  A side without
+    a pair gives NaN.  Torch ops on two queries, one host read."""
+    pred, gt = _points(pred_points, "pred_points"), _points(gt_points, "gt_points")
+    pn, gn = _points(pred_normals, "pred_normals"), _points(gt_normals, "gt_normals")
+    _device(pred, gt, pn, gn)
+    if pn.shape[0] != pred.shape[0] or gn.shape[0] != gt.shape[0]:
+        raise ValueError(f"ls2fm.metrics.normal_consistency: {pn.shape[0]} normals for {pred.shape[0]} points, {gn.shape[0]} for {gt.shape[0]}")
+    if len({t.device for t in (pred, gt, pn, gn)}) != 1:
+        raise ValueError("ls2fm.metrics.normal_consistency: the four tensors are not on one device")
+    a = _consistency_side(pred, pn, gt, gn, max_dist) if gt.shape[0] else pred.new_tensor([0.0, float("nan")], dtype=torch.float64)
+    c = _consistency_side(gt, gn, pred, pn, max_dist) if pred.shape[0] else pred.new_tensor([0.0, float("nan")], dtype=torch.float64)
+    a, c = torch.stack([a, c]).cpu().tolist()                                         # the one host read
+    return _chamfer_dict(a, c, ())
 
 
 def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), generator=None, brute_force=False, return_points=False,
@@ -585,7 +660,9 @@ def icp(src, dst, init=None, dst_normals=None, max_dist=None, with_scale=False, 
     grid is then reused across calls and cut-off stages) by ICP -> IcpResult.  Each iteration pairs every moved source point
     p' = s R p + t (fp64, rounded once to fp32) with its nearest point of dst by the distance rule, within max_dist (None: no
     cut-off), and takes one Gauss-Newton step on the similarity (with_scale) or rigid transform for the point-to-point residual,
-    or, with dst_normals (float32 [N, 3], normals of the FIXED cloud), the point-to-plane residual.  include/ls2fm.h states the rule
+    or, with dst_normals (float32 [N, 3], normals of the FIXED cloud), the point-to-plane residual; a cloud that brings none (a
+    scan, the mapper's points, a back-projected depth map) gets them from ls2fm.cloud.estimate_normals(dst), whose sign does not
+    matter here.  include/ls2fm.h states the rule
     (csrc/icp.hip: two launches per iteration, no host read, no floating-point atomic: a run is a pure function of its inputs);
     tests/icp_restate.py repeats it in numpy.
     init: the start, an (s, R, t) as align_sim3 returns it (None: the identity); state: an earlier result's state to continue from
