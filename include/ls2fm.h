@@ -1324,6 +1324,58 @@ int ls2fm_cloud_normals(const float* points, int64_t n_points, const int32_t* id
                         const float* toward, int64_t n_toward, double* normal, double* curvature, double* cov, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The implicit surface of an oriented point cloud on a dense lattice (csrc/cloud_implicit.hip behind ls2fm.cloud_mesh; an
+ * addition, the library stays ABI 13): what marching cubes needs to mesh a scan, a filtered MVS cloud or the mapper's points.
+ * The reference ships none.  tests/cloud_mesh_restate.py repeats the rule in numpy.
+ *
+ * THE IMPLICIT RULE  of points float [n_points][3] (finite: the caller's promise, as for ls2fm_point_grid_build), normals float
+ *   [n_points][3], a point grid built over the points, a lattice nx x ny x nz with origin float [3] and voxel, k in 1 .. 32,
+ *   max_d2 finite and > 0 (+inf is refused: the weight needs it) and min_neighbors >= 1.  Lattice point i sits at
+ *   X[a] = fl32(fl32((float) i[a] * voxel) + origin[a]), the expression of ls2fm_tsdf_integrate and ls2fm_marching_cubes_emit;
+ *   axis 2 is the fastest.  Its neighbours are the list of the K-NEIGHBOUR RULE for the query X with k and max_d2, no skip_own:
+ *   entries (d2_j, i_j), j = 0 .. n - 1, in list order.  Then in fp64 of the fp32 inputs, every operation rounded once, none
+ *   contracted, P = points[i_j], N = normals[i_j]:
+ *     t_j = 1 - (double) d2_j / (double) max_d2
+ *     w_j = (t_j t_j) t_j
+ *     s_j = (N.x (X.x - P.x) + N.y (X.y - P.y)) + N.z (X.z - P.z)
+ *     den = ((w_0 + w_1) + w_2) + ...            num = ((w_0 s_0 + w_1 s_1) + w_2 s_2) + ...     both start from their first term
+ *     value   = fl32(num / den)  when n >= min_neighbors and den > 0, NaN otherwise
+ *     support = fl32(den)        (0 when n = 0)
+ *   A non-finite normal makes value NaN at every lattice point that lists its point (ls2fm.cloud_mesh removes such points
+ *   first); a neighbour at exactly d2 == max_d2 has weight 0; the value is positive on the side the normals point to, the sign of
+ *   the FUSION RULE, so marching cubes' faces come out oriented like ls2fm.fusion.extract's.  value and support are float
+ *   [nx][ny][nz]; support may be NULL.  The value is a pure function of the cloud, the normals, the lattice, k, max_d2 and
+ *   min_neighbors: neither the grid's cell size, the brick nor the order of the visits shows in it.
+ * implicit  one launch, one lane per lattice point: the lane forms X, runs the k-nearest walk with the list in registers
+ *   (capacities 8, 16, 32; the smallest that holds k) and sums over the finished list.  No atomics, no workspace, nothing read
+ *   back: the call can be captured.  n_points = 0 fills NaN / 0 without a walk.  ls2fm_cloud_implicit_plan is the same call
+ *   with the launch plan chosen: brick 0 is LS2FM_CLOUD_IMPLICIT_BRICK0_X x _Y x _Z lattice points per workgroup (a wave along
+ *   axis 2), brick 1 is ..._BRICK1_X x _Y x _Z (a wave a cube of 4 x 4 x 4); with empty_test = 1 a workgroup whose brick, grown
+ *   by the radius, overlaps no occupied grid cell writes NaN / 0 without walking.  No plan shows in a bit of the result;
+ *   ls2fm_cloud_implicit runs LS2FM_CLOUD_IMPLICIT_BRICK and LS2FM_CLOUD_IMPLICIT_EMPTY_TEST, the measured fastest.
+ *   Refused before anything is enqueued, LS2FM_ERR_INVALID_ARGUMENT: a NULL array that is needed, a negative count, n_points >=
+ *   2^31, a lattice side below 1 or above 2^24 or a lattice of 2^31 points or more, a voxel that is not positive and finite, a
+ *   non-finite origin, k outside 1 .. 32, max_d2 not finite or <= 0, min_neighbors < 1, a plan that is neither 0 nor 1, and
+ *   what ls2fm_point_grid_knn refuses of the grid.
+ */
+#define LS2FM_CLOUD_IMPLICIT_BRICK0_X 2
+#define LS2FM_CLOUD_IMPLICIT_BRICK0_Y 2
+#define LS2FM_CLOUD_IMPLICIT_BRICK0_Z 64
+#define LS2FM_CLOUD_IMPLICIT_BRICK1_X 8
+#define LS2FM_CLOUD_IMPLICIT_BRICK1_Y 8
+#define LS2FM_CLOUD_IMPLICIT_BRICK1_Z 4
+#define LS2FM_CLOUD_IMPLICIT_BRICK 1
+#define LS2FM_CLOUD_IMPLICIT_EMPTY_TEST 1
+int ls2fm_cloud_implicit(const float* points, const float* normals, int64_t n_points, const float* sorted, const int32_t* cell_start,
+                         const float* origin, float cell_size, float inv_cell_size, const int32_t* dim, int64_t nx, int64_t ny, int64_t nz,
+                         const float* lattice_origin, float voxel, int32_t k, float max_d2, int32_t min_neighbors, float* value,
+                         float* support, void* stream);
+int ls2fm_cloud_implicit_plan(const float* points, const float* normals, int64_t n_points, const float* sorted, const int32_t* cell_start,
+                              const float* origin, float cell_size, float inv_cell_size, const int32_t* dim, int64_t nx, int64_t ny,
+                              int64_t nz, const float* lattice_origin, float voxel, int32_t k, float max_d2, int32_t min_neighbors,
+                              int32_t brick, int32_t empty_test, float* value, float* support, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP registration of a moving cloud to a fixed one (csrc/icp.hip behind ls2fm.metrics.icp; additions, the library stays ABI
  * 13): the step between the camera alignment and the Chamfer figures of a reconstruction in its own gauge.  The reference ships
  * none.  tests/icp_restate.py repeats the rule in numpy.

@@ -236,6 +236,10 @@ _SIGNATURES = {
     "ls2fm_point_grid_knn": (c_int32, [_P, c_int64, _P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int32,
                                        c_float, c_int32, _P, _P, _P, _P]),
     "ls2fm_cloud_normals": (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P]),
+    "ls2fm_cloud_implicit": (c_int32, [_P, _P, c_int64, _P, _P, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int64, c_int64,
+                                       c_int64, POINTER(c_float), c_float, c_int32, c_float, c_int32, _P, _P, _P]),
+    "ls2fm_cloud_implicit_plan": (c_int32, [_P, _P, c_int64, _P, _P, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int64, c_int64,
+                                            c_int64, POINTER(c_float), c_float, c_int32, c_float, c_int32, c_int32, c_int32, _P, _P, _P]),
     "ls2fm_icp_workspace_bytes": (c_int64, [c_int64]),
     "ls2fm_icp_run": (c_int32, [_P, c_int64, _P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), _P, c_float, c_int32,
                                 c_int32, c_double, c_double, _P, _P, _P, _P, _P, _P]),

@@ -6,6 +6,8 @@ they are scored, meshed or registered.
                          metrics.icp's point-to-plane residual and metrics.normal_consistency want from a cloud that brings none
   statistical_outliers   Open3D's rule: drop the points whose mean neighbour distance lies std_ratio deviations above the mean
   radius_outliers        drop the points with fewer than min_neighbors others inside a radius
+  depths_to_cloud        back-project posed depth maps into a cloud and each point's camera centre (torch ops), the input of
+                         estimate_normals(toward=...) and of ls2fm.cloud_mesh.mesh_from_cloud
 
 include/ls2fm.h states the K-NEIGHBOUR RULE and the NORMAL RULE; both make the result a pure function of the inputs, and
 tests/cloud_restate.py repeats them in numpy.  _knn_torch and _normals_torch are the same rules as plain torch ops on whatever
@@ -290,3 +292,46 @@ def radius_outliers(points, radius, min_neighbors):
     _max_d2(radius)
     _, count = _self_neighbours(points, int(min_neighbors), radius)
     return count == int(min_neighbors)
+
+
+@torch.no_grad()
+def depths_to_cloud(depth, pose, intr, stride=1, max_depth=float("inf")):
+    """Back-project depth maps into one cloud -> (points float32 [M, 3], centers float32 [M, 3]).
+      depth        float [V, H, W] or [H, W], camera z pixel for pixel (the convention of raster.rasterize, image.trace_image,
+                   mvs and fusion.integrate).  A pixel that is not finite, not positive or above max_depth gives no point.
+      pose, intr   [V, 3, 4] (or [3, 4]) world-to-camera [R | t] and [3, 3] or [V, 3, 3], as ls2fm/_posed.py takes them
+      stride       every stride-th row and column
+    Pixel (px, py) of depth d is the world point R^T (((px + 0.5 - cx) / fx d, (py + 0.5 - cy) / fy d, d) - t): the pixel's centre,
+    which the rasteriser's projection puts back on (px + 0.5, py + 0.5) at c_z = d.  centers holds each point's camera centre
+    -R^T t: the per-point `toward` of estimate_normals.  The points come view by view, row by row.  torch ops only, in fp64 and
+    rounded once to float32, on the depth's device; the size of the result is a host read."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() == 2:
+        depth = depth[None]
+    dev = depth.device
+    P = torch.as_tensor(pose).detach().to(dev)
+    if depth.dim() != 3 or P.dim() not in (2, 3) or tuple(P.shape[-2:]) != (3, 4):
+        raise ValueError(f"ls2fm.cloud.depths_to_cloud: depth must be [V, H, W] and pose [V, 3, 4], got {tuple(depth.shape)} and {tuple(P.shape)}")
+    P = P.reshape(-1, 3, 4).to(torch.float64)
+    n, H, W = (int(s) for s in depth.shape)
+    K = torch.as_tensor(intr).detach().to(dev)
+    if K.dim() not in (2, 3) or tuple(K.shape[-2:]) != (3, 3) or K.reshape(-1, 3, 3).shape[0] not in (1, n) or P.shape[0] != n:
+        raise ValueError(f"ls2fm.cloud.depths_to_cloud: {P.shape[0]} poses and intr {tuple(K.shape)} for {n} depth maps")
+    K = K.reshape(-1, 3, 3).to(torch.float64).expand(n, 3, 3)
+    if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+        raise ValueError(f"ls2fm.cloud.depths_to_cloud: stride {stride} must be an integer >= 1")
+    max_depth = float(max_depth)
+    if not max_depth > 0.0:
+        raise ValueError(f"ls2fm.cloud.depths_to_cloud: max_depth {max_depth} must be positive (inf is allowed)")
+    py, px = torch.arange(0, H, int(stride), device=dev), torch.arange(0, W, int(stride), device=dev)
+    d = depth.detach()[:, py][:, :, px].to(torch.float64)                              # [V, h, w]
+    ok = torch.isfinite(d) & (d > 0) & (d <= max_depth)
+    u = (px.to(torch.float64) + 0.5)[None, None, :]
+    v = (py.to(torch.float64) + 0.5)[None, :, None]
+    fx, fy, cx, cy = (K[:, a, b][:, None, None] for a, b in ((0, 0), (1, 1), (0, 2), (1, 2)))
+    cam = torch.stack([(u - cx) / fx * d, (v - cy) / fy * d, d], dim=-1)               # [V, h, w, 3]
+    R, t = P[:, :, :3], P[:, :, 3]
+    world = torch.einsum("vji,vhwj->vhwi", R, cam - t[:, None, None, :])               # R^T (c - t)
+    centre = -torch.einsum("vji,vj->vi", R, t)
+    centers = centre[:, None, None, :].expand_as(world)
+    return world[ok].float(), centers[ok].float()

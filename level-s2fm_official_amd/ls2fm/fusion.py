@@ -171,9 +171,7 @@ def extract(volume: TsdfVolume, min_weight=1.0) -> mesh.Mesh:
     with torch.cuda.device(volume.device):
         vol = torch.where(volume.weight >= float(min_weight), volume.tsdf, torch.full_like(volume.tsdf, math.nan))
         verts, faces = mesh.marching_cubes(vol, 0.0, spacing=(volume.voxel,) * 3, origin=volume.origin)
-        good = torch.isfinite(verts).all(dim=1)
-        keep = good[faces.long()].all(dim=1) if faces.shape[0] else torch.zeros(0, dtype=torch.bool, device=verts.device)
-        return mesh.select_faces(verts, faces, keep)
+        return mesh.finite_faces(verts, faces)
 
 
 def volume_for(bounds, voxel, trunc=None, device="cuda") -> TsdfVolume:

@@ -64,6 +64,14 @@ def select_faces(verts: torch.Tensor, faces: torch.Tensor, keep: torch.Tensor) -
     return Mesh(verts[used], renumber[kept].to(torch.int32))
 
 
+def finite_faces(verts: torch.Tensor, faces: torch.Tensor) -> Mesh:
+    """the faces whose three vertices are finite, then select_faces' compaction: the tail of ls2fm.fusion.extract and
+    ls2fm.cloud_mesh.extract, where marching cubes puts a NaN vertex on every edge into an undefined lattice point"""
+    good = torch.isfinite(verts).all(dim=1)
+    keep = good[faces.long()].all(dim=1) if faces.shape[0] else torch.zeros(0, dtype=torch.bool, device=verts.device)
+    return select_faces(verts, faces, keep)
+
+
 def _check_mesh(verts, faces, what):
     """device-only and [., 3] shapes"""
     _lib.require_device_tensors(f"ls2fm.mesh.{what}", faces, verts, phrase=" runs on the GPU only")

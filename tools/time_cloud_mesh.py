@@ -1,0 +1,147 @@
+#!/usr/bin/env python
+"""Times ls2fm.cloud_mesh on the 2 M-point sphere cloud of tools/time_metrics.py (radius 100) with its analytic normals, into a
+512^3 lattice at a radius of 3 voxels and k = 16, and writes profiles/cloud_mesh_time.json:
+  kernel   ls2fm_cloud_implicit alone on a built grid at its four launch plans (brick 2 x 2 x 64 or 8 x 8 x 4, with and without the
+           empty-brick test; first checked to leave the same bits), implicit_from_cloud (on a built grid, and building its own),
+           extract, mesh_from_cloud end to end, and the share of lattice points that walk at all (a neighbour inside the radius).
+           HIP events around windows of --calls calls, the forms ALTERNATED inside every repetition, median over the windows.
+  torch    _implicit_torch (PointGrid.knn over the lattice points in chunks plus torch sums: the route a user has without the
+           kernel) on the same GPU, on growing cubes of the lattice about a point of the surface, each checked bit-equal against the
+           kernel first, up to the largest a forecast (eight times the last) fits into the step's budget
+Every step is a child process under its own time limit; a step that fails or runs out ends the run (the record says which).
+    python tools/time_cloud_mesh.py [--n 2000000] [--side 512] [--reps 5] [--steps kernel,torch]"""
+import argparse, json, os, subprocess, sys, tempfile, time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "level-s2fm_official_amd"), ROOT, os.path.dirname(os.path.abspath(__file__))):
+    sys.path.insert(0, p)
+
+from time_metrics import RADIUS, alternated, sphere          # noqa: E402  the cloud and the timing loop of tools/time_metrics.py
+
+LIMITS = dict(kernel=420, torch=300)                         # seconds per step
+TORCH_BUDGET_S = 40.0
+K, MIN_NEIGHBORS, RADIUS_VOXELS = 16, 3, 3.0
+
+
+def workload(a):
+    """the cloud, its normals and the lattice: `side` points per axis, centred, the sphere and the radius inside it"""
+    import torch
+    pts = sphere(a.n, RADIUS, 1)
+    nrm = (pts.astype(np.float64) / np.linalg.norm(pts.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+    voxel = 2.0 * RADIUS / (a.side - 1 - 2 * RADIUS_VOXELS - 1)
+    half = 0.5 * (a.side - 1) * voxel
+    bounds = ((-half,) * 3, (half,) * 3)
+    return torch.from_numpy(pts).to("cuda:0"), torch.from_numpy(nrm).to("cuda:0"), voxel, bounds
+
+
+def same_bits(x, y):
+    import torch
+    return all(bool(torch.equal(a.view(torch.int32), b.view(torch.int32))) for a, b in zip(x, y))
+
+
+def step_kernel(a):
+    import torch
+    from ls2fm import cloud_mesh as CM, metrics as MT
+    p, n, voxel, bounds = workload(a)
+    shape, origin = CM._lattice(bounds, voxel)
+    radius = RADIUS_VOXELS * voxel
+    max_d2 = MT._max_d2(radius)
+    g = MT.PointGrid(p)
+    res = dict(n=a.n, sphere_radius=RADIUS, lattice=list(shape), voxel=voxel, radius=radius, k=K, min_neighbors=MIN_NEIGHBORS,
+               cell_size=g.cell_size, grid_dim=list(g.dim), default_plan=CM.DEFAULT_PLAN)
+    plans = {f"kernel_brick{b}_{'empty_test' if e else 'no_test'}": dict(brick=b, empty_test=e) for b in (0, 1) for e in (False, True)}
+    run = lambda plan: CM._implicit_device(p, n, g, shape, origin, voxel, K, max_d2, MIN_NEIGHBORS, plan)       # noqa: E731
+    first = run(None)
+    for name, plan in plans.items():
+        if not same_bits(run(plan), first):
+            raise SystemExit(f"{name} leaves other bits than the default plan")
+    res["plans_leave_the_same_bits"] = True
+    total = first[0].numel()
+    res["share_walking"] = float((first[1] > 0).sum()) / total
+    res["share_defined"] = float(torch.isfinite(first[0]).sum()) / total
+    res["knn16_floor_ms"] = res["share_walking"] * total * 3.01 / 2e6        # knn(16) costs 3.01 ms per 2 M queries here
+    volume = CM.ImplicitVolume(first[0], first[1], origin, voxel, radius)
+    out = CM.extract(volume)
+    res["mesh"] = dict(vertices=int(out.vertices.shape[0]), faces=int(out.faces.shape[0]))
+    del first
+    forms = {name: (lambda plan=plan: run(plan)) for name, plan in plans.items()}
+    forms["implicit_from_cloud_on_a_grid"] = lambda: CM.implicit_from_cloud(p, n, voxel, bounds=bounds, grid=g)
+    forms["implicit_from_cloud"] = lambda: CM.implicit_from_cloud(p, n, voxel, bounds=bounds)
+    forms["extract"] = lambda: CM.extract(volume)
+    forms["mesh_from_cloud"] = lambda: CM.mesh_from_cloud(p, n, voxel=voxel, bounds=bounds)
+    res["forms"] = alternated(forms, a.reps, calls=a.calls)
+    return res
+
+
+def step_torch(a):
+    import torch
+    from ls2fm import cloud_mesh as CM, metrics as MT
+    p, n, voxel, _ = workload(a)
+    radius = RADIUS_VOXELS * voxel
+    g = MT.PointGrid(p)
+    res, side = dict(sizes=[]), 32
+    while side <= a.side:
+        shape = (side,) * 3
+        origin = (RADIUS - 0.5 * (side - 1) * voxel, -0.5 * (side - 1) * voxel, -0.5 * (side - 1) * voxel)     # the surface runs through it
+        want = CM._implicit_device(p, n, g, shape, origin, voxel, K, MT._max_d2(radius), MIN_NEIGHBORS)
+        t0 = time.perf_counter()
+        got = CM._implicit_torch(p, n, shape, origin, voxel, radius, K, MIN_NEIGHBORS, grid=g)
+        torch.cuda.synchronize()
+        first_s = time.perf_counter() - t0
+        nan = torch.isnan(want[0])
+        if not (torch.equal(torch.isnan(got[0]), nan) and same_bits((got[0][~nan], got[1]), (want[0][~nan], want[1]))):
+            raise SystemExit(f"the torch form and the kernel differ at a lattice of {side}^3")
+        t = alternated({"implicit_torch": lambda: CM._implicit_torch(p, n, shape, origin, voxel, radius, K, MIN_NEIGHBORS, grid=g),
+                        "kernel": lambda: CM._implicit_device(p, n, g, shape, origin, voxel, K, MT._max_d2(radius), MIN_NEIGHBORS)},
+                       3 if first_s < 5 else 1)
+        res["sizes"].append(dict(side=side, equal=True, share_walking=float((want[1] > 0).sum()) / want[1].numel(), **t))
+        print(json.dumps(res["sizes"][-1]), flush=True)
+        if 8 * t["implicit_torch"]["median_ms"] / 1e3 * (4 if first_s < 5 else 2) > TORCH_BUDGET_S:   # the next size: eight times the work
+            break
+        side *= 2
+    res["largest_side"] = res["sizes"][-1]["side"]
+    return res
+
+
+STEPS = dict(kernel=step_kernel, torch=step_torch)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=2_000_000)
+    ap.add_argument("--side", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=1, help="calls per timed window of the kernel step's forms")
+    ap.add_argument("--steps", default="kernel,torch")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cloud_mesh_time.json"))
+    ap.add_argument("--step", help="(internal) run one step in this process and write its record to --step-out")
+    ap.add_argument("--step-out")
+    a = ap.parse_args()
+    if a.step:
+        rec = STEPS[a.step](a)
+        with open(a.step_out, "w") as f:
+            json.dump(rec, f)
+        return
+    res = dict(n=a.n, side=a.side, reps=a.reps)
+    for name in a.steps.split(","):
+        with tempfile.NamedTemporaryFile(suffix=".json") as tmp:
+            cmd = ["timeout", "-k", "10", str(LIMITS[name]), sys.executable, os.path.abspath(__file__), "--n", str(a.n), "--side", str(a.side),
+                   "--reps", str(a.reps), "--calls", str(a.calls), "--step", name, "--step-out", tmp.name]
+            t0 = time.perf_counter()
+            rc = subprocess.run(cmd).returncode
+            if rc != 0:
+                res[name] = dict(failed=True, returncode=rc, limit_s=LIMITS[name])
+                print(f"step {name} ended with status {rc}: nothing further is started", file=sys.stderr)
+                break
+            res[name] = json.load(open(tmp.name))
+            res[name]["step_wall_s"] = time.perf_counter() - t0
+    print(json.dumps(res, indent=1))
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    sys.exit(1 if any(isinstance(v, dict) and v.get("failed") for v in res.values()) else 0)
+
+
+if __name__ == "__main__":
+    main()
