@@ -1,7 +1,7 @@
 // The implicit surface of an oriented point cloud on a dense lattice (ls2fm_cloud_implicit): the primitive under
 // ls2fm.cloud_mesh.implicit_from_cloud.  include/ls2fm.h states THE IMPLICIT RULE; tests/cloud_mesh_restate.py repeats it in numpy.
 //
-// One launch, one lane per lattice point.  The lane forms its own position X (the lattice expression of tsdf_fusion.hip and
+// One launch, one lane per lattice point.  The lane forms its own position X (the lattice expression of lattice.h and
 // marching_cubes.hip), runs grid_walk.h's k_nearest with the list in registers (capacities 8 / 16 / 32, the smallest that holds
 // k), then walks the finished list with compile-time indices, gathers points[i] and normals[i] and forms the two fp64 sums in list
 // order.  No atomics, no workspace, nothing read back: the value is a pure function of the cloud, the normals, the lattice, k,
@@ -15,6 +15,7 @@
 //           without a walk.  The range is a superset of every cell a qualifying reference of any of the brick's lattice points can
 //           lie in (empty_reach), so the test only ever skips walks that would have found nothing: the bits are the same.
 #include "grid_walk.h"
+#include "lattice.h"
 #include "ls2fm_device.h"
 
 #include <cmath>
@@ -45,13 +46,7 @@ static_assert(Brick<0>::X == LS2FM_CLOUD_IMPLICIT_BRICK0_X && Brick<0>::Y == LS2
               Brick<0>::Z == LS2FM_CLOUD_IMPLICIT_BRICK0_Z && Brick<1>::X == LS2FM_CLOUD_IMPLICIT_BRICK1_X &&
               Brick<1>::Y == LS2FM_CLOUD_IMPLICIT_BRICK1_Y && Brick<1>::Z == LS2FM_CLOUD_IMPLICIT_BRICK1_Z, "the header states the bricks");
 
-struct Lattice {
-    int nx, ny, nz;
-    float origin[3];
-    float voxel;
-};
-
-__device__ __forceinline__ float lattice_coord(int i, float voxel, float origin) { return __fadd_rn(__fmul_rn((float)i, voxel), origin); }
+struct Lattice { int nx, ny, nz; LatticeFrame frame; };
 
 // Whether the cells [cell of (lo - reach), cell of (hi + reach)] per axis hold any point, lo / hi being the brick's lowest and
 // highest lattice coordinates.  A reference that qualifies for a lattice point X has fp32 d2 <= max_d2, so |X.a - p.a| <=
@@ -62,9 +57,9 @@ template <int BRICK>
 __device__ __forceinline__ bool brick_occupied(const PgGrid& g, const int32_t* __restrict__ cell_start, const Lattice& lat, int bx, int by, int bz,
                                                float reach, int t) {
     using B = Brick<BRICK>;
-    const float lx = lattice_coord(bx * B::X, lat.voxel, lat.origin[0]), hx = lattice_coord(min(bx * B::X + B::X - 1, lat.nx - 1), lat.voxel, lat.origin[0]);
-    const float ly = lattice_coord(by * B::Y, lat.voxel, lat.origin[1]), hy = lattice_coord(min(by * B::Y + B::Y - 1, lat.ny - 1), lat.voxel, lat.origin[1]);
-    const float lz = lattice_coord(bz * B::Z, lat.voxel, lat.origin[2]), hz = lattice_coord(min(bz * B::Z + B::Z - 1, lat.nz - 1), lat.voxel, lat.origin[2]);
+    const float lx = lattice_coord(bx * B::X, lat.frame, 0), hx = lattice_coord(min(bx * B::X + B::X - 1, lat.nx - 1), lat.frame, 0);
+    const float ly = lattice_coord(by * B::Y, lat.frame, 1), hy = lattice_coord(min(by * B::Y + B::Y - 1, lat.ny - 1), lat.frame, 1);
+    const float lz = lattice_coord(bz * B::Z, lat.frame, 2), hz = lattice_coord(min(bz * B::Z + B::Z - 1, lat.nz - 1), lat.frame, 2);
     const int x0 = cell_axis(nextafterf(__fsub_rn(lx, reach), -INFINITY), g.ox, g.inv_h, g.nx);
     const int x1 = cell_axis(nextafterf(__fadd_rn(hx, reach), INFINITY), g.ox, g.inv_h, g.nx);
     const int y0 = cell_axis(nextafterf(__fsub_rn(ly, reach), -INFINITY), g.oy, g.inv_h, g.ny);
@@ -106,9 +101,7 @@ ci_implicit(PgGrid g, const float4* __restrict__ sorted, const int32_t* __restri
         if (support) support[at] = 0.0f;
         return;
     }
-    // every side is at most 2^24, so the index converts exactly
-    const float x = lattice_coord(ix, lat.voxel, lat.origin[0]), y = lattice_coord(iy, lat.voxel, lat.origin[1]),
-                z = lattice_coord(iz, lat.voxel, lat.origin[2]);
+    const float x = lattice_coord(ix, lat.frame, 0), y = lattice_coord(iy, lat.frame, 1), z = lattice_coord(iz, lat.frame, 2);
     KList<CAP> l;
     k_nearest<CAP>(g, sorted, cell_start, x, y, z, max_d2, -1, k, max_rings, l);
     // the list in its order: filled slots come first, so slot 0 starts both sums
@@ -153,20 +146,13 @@ extern "C" int ls2fm_cloud_implicit_plan(const float* points, const float* norma
                                          int32_t k, float max_d2, int32_t min_neighbors, int32_t brick, int32_t empty_test, float* value,
                                          float* support, void* stream) {
     int64_t n_cells = 0;
-    const int64_t side = (int64_t)1 << 24;
     LS2FM_CHECK_ARG(n_points >= 0 && n_points < ((int64_t)1 << 31) && grid_ok(origin, cell_size, inv_cell_size, dim, &n_cells));
-    LS2FM_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && nx <= side && ny <= side && nz <= side && nx * ny < ((int64_t)1 << 31) &&
-                    nx * ny * nz < ((int64_t)1 << 31));
-    LS2FM_CHECK_ARG(voxel > 0.0f && voxel < INFINITY && k >= 1 && k <= 32 && max_d2 > 0.0f && max_d2 < INFINITY && min_neighbors >= 1);
+    LS2FM_CHECK_ARG(lattice_ok(nx, ny, nz, 1, voxel) && nx * ny < ((int64_t)1 << 31) && nx * ny * nz < ((int64_t)1 << 31));
+    LS2FM_CHECK_ARG(k >= 1 && k <= 32 && max_d2 > 0.0f && max_d2 < INFINITY && min_neighbors >= 1);
     LS2FM_CHECK_ARG((brick == 0 || brick == 1) && (empty_test == 0 || empty_test == 1));
-    LS2FM_CHECK_ARG(lattice_origin && value);
     Lattice lat;
-    for (int a = 0; a < 3; ++a) {
-        LS2FM_CHECK_ARG(fabsf(lattice_origin[a]) < INFINITY);           // on the host: three floats, read before the call returns
-        lat.origin[a] = lattice_origin[a];
-    }
+    LS2FM_CHECK_ARG(value && lattice_frame(lattice_origin, voxel, &lat.frame));
     lat.nx = (int)nx; lat.ny = (int)ny; lat.nz = (int)nz;
-    lat.voxel = voxel;
     hipStream_t s = (hipStream_t)stream;
     const size_t total = (size_t)(nx * ny * nz);
     if (n_points == 0) {                       // no cloud: every lattice point is undefined, without a walk

@@ -8,6 +8,7 @@
 // over the wave: its pose and intrinsics are scalar loads.  The camera point, the projection, the usable rule and the pixel are
 // the expressions of csrc/raster_project.h, the ones ls2fm_rasterize draws its depth maps with.  A wave whose 64 points all miss
 // a view's image (or lie behind its near plane) leaves that view at the branch after the projection.
+#include "lattice.h"
 #include "ls2fm_device.h"
 #include "raster_project.h"
 
@@ -22,14 +23,9 @@ static_assert(kBrickX == LS2FM_TSDF_BRICK_X && kBrickY == LS2FM_TSDF_BRICK_Y && 
               "the header states the brick");
 static_assert(kBrickZ == 64, "one wave per row of the brick");
 
-struct Lattice {
-    float origin[3];
-    float voxel;
-};
-
 __global__ void __launch_bounds__(kThreads)
 tsdf_integrate(float* __restrict__ tsdf, float* __restrict__ weight, int64_t nx, int64_t ny, int64_t nz, int64_t bricks_y,
-               int64_t bricks_z, Lattice lat, float trunc, const float* __restrict__ depth, const float* __restrict__ poses,
+               int64_t bricks_z, LatticeFrame lat, float trunc, const float* __restrict__ depth, const float* __restrict__ poses,
                const float* __restrict__ intr, const float* __restrict__ view_weight, int n_views, int height, int width, float near,
                float max_depth, float max_weight) {
 #pragma clang fp contract(off)
@@ -41,10 +37,7 @@ tsdf_integrate(float* __restrict__ tsdf, float* __restrict__ weight, int64_t nx,
     const int64_t ix = bx * kBrickX + t / (kBrickZ * kBrickY);
     if (ix >= nx || iy >= ny || iz >= nz) return;
     const int64_t at = (ix * ny + iy) * nz + iz;
-    // every side is at most 2^24, so the index converts exactly
-    const float x = __fadd_rn(__fmul_rn((float)ix, lat.voxel), lat.origin[0]);
-    const float y = __fadd_rn(__fmul_rn((float)iy, lat.voxel), lat.origin[1]);
-    const float z = __fadd_rn(__fmul_rn((float)iz, lat.voxel), lat.origin[2]);
+    const float x = lattice_coord(ix, lat, 0), y = lattice_coord(iy, lat, 1), z = lattice_coord(iz, lat, 2);
     float T = tsdf[at], W = weight[at];
     const int64_t hw = (int64_t)height * width;
     for (int view = 0; view < n_views; ++view) {
@@ -67,28 +60,20 @@ tsdf_integrate(float* __restrict__ tsdf, float* __restrict__ weight, int64_t nx,
     weight[at] = W;
 }
 
-bool positive_finite(float v) { return v > 0.0f && v < INFINITY; }
-
 }  // namespace
 
 extern "C" int ls2fm_tsdf_integrate(float* tsdf, float* weight, int64_t nx, int64_t ny, int64_t nz, const float* origin, float voxel,
                                     float trunc, const float* depth, const float* poses, const float* intr, const float* view_weight,
                                     int32_t n_views, int32_t height, int32_t width, float near, float max_depth, float max_weight,
                                     void* stream) {
-    const int64_t side = (int64_t)1 << 24;
-    LS2FM_CHECK_ARG(nx >= 0 && ny >= 0 && nz >= 0 && nx <= side && ny <= side && nz <= side && raster_image_ok(n_views, height, width) &&
-                    raster_near_ok(near) && positive_finite(voxel) && positive_finite(trunc) && max_depth > 0.0f && max_weight > 0.0f);
+    LS2FM_CHECK_ARG(lattice_ok(nx, ny, nz, 0, voxel) && raster_image_ok(n_views, height, width) && raster_near_ok(near) &&
+                    trunc > 0.0f && trunc < INFINITY && max_depth > 0.0f && max_weight > 0.0f);
     if (nx == 0 || ny == 0 || nz == 0 || n_views == 0) return LS2FM_OK;
     const int64_t bricks_x = (nx + kBrickX - 1) / kBrickX, bricks_y = (ny + kBrickY - 1) / kBrickY, bricks_z = (nz + kBrickZ - 1) / kBrickZ;
     // the three factors are at most 2^23 each: the products below stay in int64
     LS2FM_CHECK_ARG(bricks_x * bricks_y < ((int64_t)1 << 31) && bricks_x * bricks_y * bricks_z < ((int64_t)1 << 31));
-    LS2FM_CHECK_ARG(tsdf && weight && origin && depth && poses && intr);
-    Lattice lat;
-    for (int a = 0; a < 3; ++a) {
-        LS2FM_CHECK_ARG(fabsf(origin[a]) < INFINITY);               // on the host: three floats, read before the call returns
-        lat.origin[a] = origin[a];
-    }
-    lat.voxel = voxel;
+    LatticeFrame lat;
+    LS2FM_CHECK_ARG(tsdf && weight && depth && poses && intr && lattice_frame(origin, voxel, &lat));
     tsdf_integrate<<<(unsigned)(bricks_x * bricks_y * bricks_z), kThreads, 0, (hipStream_t)stream>>>(
         tsdf, weight, nx, ny, nz, bricks_y, bricks_z, lat, trunc, depth, poses, intr, view_weight, n_views, height, width, near, max_depth,
         max_weight);

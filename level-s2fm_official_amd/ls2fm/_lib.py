@@ -118,6 +118,9 @@ class SiftOpts(Structure):
 
 
 _P = c_void_p
+# PointGrid.c_args: sorted, cell_start, n, origin, cell_size, inv_cell_size, dim; ls2fm_cloud_implicit* take n ahead of sorted
+_GRID = [_P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32)]
+_GRID_N_FIRST = [c_int64, _P, _P] + _GRID[3:]
 _SIGNATURES = {
     # name: (restype, argtypes)        -- must list every symbol include/ls2fm.h declares
     "ls2fm_abi_version": (c_int32, []),
@@ -231,18 +234,14 @@ _SIGNATURES = {
     "ls2fm_sift_extract": (c_int32, [_P, _P, _P, _P, c_int32, POINTER(SiftOpts), _P, _P, _P, _P, _P]),
     "ls2fm_point_grid_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "ls2fm_point_grid_build": (c_int32, [_P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), _P, _P, _P, _P]),
-    "ls2fm_point_grid_query": (c_int32, [_P, c_int64, _P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_float,
-                                         _P, _P, _P]),
-    "ls2fm_point_grid_knn": (c_int32, [_P, c_int64, _P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int32,
-                                       c_float, c_int32, _P, _P, _P, _P]),
+    "ls2fm_point_grid_query": (c_int32, [_P, c_int64, *_GRID, c_float, _P, _P, _P]),
+    "ls2fm_point_grid_knn": (c_int32, [_P, c_int64, *_GRID, c_int32, c_float, c_int32, _P, _P, _P, _P]),
     "ls2fm_cloud_normals": (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P]),
-    "ls2fm_cloud_implicit": (c_int32, [_P, _P, c_int64, _P, _P, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int64, c_int64,
-                                       c_int64, POINTER(c_float), c_float, c_int32, c_float, c_int32, _P, _P, _P]),
-    "ls2fm_cloud_implicit_plan": (c_int32, [_P, _P, c_int64, _P, _P, POINTER(c_float), c_float, c_float, POINTER(c_int32), c_int64, c_int64,
-                                            c_int64, POINTER(c_float), c_float, c_int32, c_float, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "ls2fm_cloud_implicit": (c_int32, [_P, _P, *_GRID_N_FIRST, *[c_int64] * 3, POINTER(c_float), c_float, c_int32, c_float, c_int32, _P, _P, _P]),
+    "ls2fm_cloud_implicit_plan": (c_int32, [_P, _P, *_GRID_N_FIRST, *[c_int64] * 3, POINTER(c_float), c_float, c_int32, c_float, *[c_int32] * 3,
+                                            _P, _P, _P]),
     "ls2fm_icp_workspace_bytes": (c_int64, [c_int64]),
-    "ls2fm_icp_run": (c_int32, [_P, c_int64, _P, _P, c_int64, POINTER(c_float), c_float, c_float, POINTER(c_int32), _P, c_float, c_int32,
-                                c_int32, c_double, c_double, _P, _P, _P, _P, _P, _P]),
+    "ls2fm_icp_run": (c_int32, [_P, c_int64, *_GRID, _P, c_float, c_int32, c_int32, c_double, c_double, _P, _P, _P, _P, _P, _P]),
     "ls2fm_rasterize_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "ls2fm_rasterize": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P]),
     "ls2fm_mesh_mask_votes": (c_int32, [_P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P]),

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .metrics import KNN_MAX_K, PointGrid, _knn_k, _max_d2, _points
+from .point_grid import KNN_MAX_K, PointGrid, knn_k, points3, squared_cutoff
 
 _JACOBI_SWEEPS = 30                        # pose_math.h's kJacobiSweeps
 
@@ -32,14 +32,14 @@ def _knn_torch(q, ref, k, max_dist=None, skip_own=False, chunk=None):
     """The K-NEIGHBOUR RULE as plain torch ops: all M x N distances of the distance rule, `chunk` queries at a time (default: 2^24
     distances per chunk), the entries that do not qualify set to +inf, then a two-key sort on (d2, index): a stable sort of d2 over
     columns that stand in index order.  -> (idx int32 [M, k], d2 float32 [M, k], count int32 [M])"""
-    q, ref = _points(q, "q").float(), _points(ref, "ref").float()
-    k = _knn_k(k)
+    q, ref = points3(q, "q").float(), points3(ref, "ref").float()
+    k = knn_k(k)
     dev = q.device
     ref = ref.to(dev)
     m, n = int(q.shape[0]), int(ref.shape[0])
     if skip_own and m != n:
         raise ValueError(f"ls2fm.cloud: skip_own needs the reference cloud as queries, got {m} queries for {n} points")
-    max_d2 = float(_max_d2(max_dist))
+    max_d2 = float(squared_cutoff(max_dist))
     inf = float("inf")
     idx = torch.full((m, k), -1, dtype=torch.int32, device=dev)
     d2_out = torch.full((m, k), inf, dtype=torch.float32, device=dev)
@@ -105,7 +105,7 @@ def _normals_torch(points, idx, queries=None, toward=None):
     """The NORMAL RULE as plain torch ops in fp64: the mean and the covariance accumulated over the list's columns in a Python
     loop, so that each add rounds once, the Jacobi as masked batch operations.
     -> (normal fp64 [M, 3], curvature fp64 [M], cov fp64 [M, 6])"""
-    points = _points(points, "points").float()
+    points = points3(points, "points").float()
     idx = torch.as_tensor(idx).to(points.device)
     m, k = int(idx.shape[0]), int(idx.shape[1])
     n_points = int(points.shape[0])
@@ -143,7 +143,7 @@ def _normals_torch(points, idx, queries=None, toward=None):
     length = torch.sqrt((vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2])
     vec = [x / length for x in vec]
     if toward is not None:
-        t = _toward(toward, m, points.device).to(torch.float64) - _points(queries, "queries").float().to(torch.float64)
+        t = _toward(toward, m, points.device).to(torch.float64) - points3(queries, "queries").float().to(torch.float64)
         flip = (vec[0] * t[:, 0] + vec[1] * t[:, 1]) + vec[2] * t[:, 2] < 0.0
     else:
         big = vec[0]
@@ -171,16 +171,16 @@ def knn(q, ref, k, max_dist=None, exclude_self=False, cell_size=None):
     """(idx int32 [M, k], d2 float32 [M, k], count int32 [M]): the k nearest references of every query by the K-NEIGHBOUR RULE
     (1 <= k <= 32; -1 / +inf in the slots without a neighbour inside max_dist).  exclude_self: the queries ARE the references
     (`q is ref` is required) and a point is not its own neighbour; a duplicate at another index still is.  `ref` may be a
-    metrics.PointGrid, which is then reused (exclude_self: pass its cloud, grid.ref, as q).  Device tensors go through the grid,
+    point_grid.PointGrid, which is then reused (exclude_self: pass its cloud, grid.ref, as q).  Device tensors go through the grid,
     CPU tensors through _knn_torch."""
     grid = ref if isinstance(ref, PointGrid) else None
     if exclude_self and q is not (grid.ref if grid is not None else ref):
         raise ValueError("ls2fm.cloud.knn: exclude_self needs the references themselves as queries (q is ref)")
-    q = _points(q, "q")
-    k = _knn_k(k)
-    _max_d2(max_dist)
+    q = points3(q, "q")
+    k = knn_k(k)
+    squared_cutoff(max_dist)
     if grid is None:
-        ref = _points(ref, "ref")
+        ref = points3(ref, "ref")
         if ref.device != q.device:
             raise ValueError(f"ls2fm.cloud.knn: q on {q.device}, ref on {ref.device}")
         if not q.is_cuda:
@@ -194,7 +194,7 @@ def normals_from_neighbors(points, idx, queries=None, toward=None, return_cov=Fa
     and, with return_cov, cov fp64 [M, 6] (xx xy xz yy yz zz).  toward ([3], [1, 3] or [M, 3]) orients the normals toward that
     position as seen from `queries` [M, 3] (needed with toward); without it the largest component is made positive.  One launch
     (ls2fm_cloud_normals), nothing read back; CPU tensors go through _normals_torch."""
-    points = _points(points, "points")
+    points = points3(points, "points")
     idx = torch.as_tensor(idx)
     if idx.dim() != 2 or idx.shape[1] < 1 or idx.dtype != torch.int32:
         raise ValueError(f"ls2fm.cloud: idx must be int32 [M, k >= 1], got {idx.dtype} {tuple(idx.shape)}")
@@ -202,7 +202,7 @@ def normals_from_neighbors(points, idx, queries=None, toward=None, return_cov=Fa
     if toward is not None:
         if queries is None:
             raise ValueError("ls2fm.cloud: toward needs the queries' positions")
-        queries = _points(queries, "queries")
+        queries = points3(queries, "queries")
         if queries.shape[0] != m:
             raise ValueError(f"ls2fm.cloud: {queries.shape[0]} queries for {m} neighbour lists")
         toward = _toward(toward, m, points.device)
@@ -229,9 +229,9 @@ def estimate_normals(points, k=16, max_dist=None, toward=None, grid=None, return
     the smallest eigenvalue of the covariance of the point's k nearest neighbours inside max_dist, the point itself among them
     (k counts it, as Open3D's KNN search does); fewer than 3 neighbours or a neighbourhood without extent give NaN.  toward (a
     position [3] / [1, 3], e.g. the camera or scanner, or one per point [N, 3]) orients them; without it the largest component is
-    positive, which is consistent across a smooth patch but not a global orientation.  grid: a metrics.PointGrid over `points` to
+    positive, which is consistent across a smooth patch but not a global orientation.  grid: a point_grid.PointGrid over `points` to
     reuse.  Two launches on the device (knn, normals), nothing read back once the grid exists."""
-    points = _points(points, "points")
+    points = points3(points, "points")
     if grid is not None and grid.n != points.shape[0]:
         raise ValueError(f"ls2fm.cloud.estimate_normals: the grid holds {grid.n} points, the cloud {points.shape[0]}")
     if points.is_cuda:
@@ -255,7 +255,7 @@ def _self_neighbours(points, k, max_dist):
     if n < 2:
         _, d2, count = PointGrid(points).knn(points, k, max_dist, skip_own=True)
         return d2, count
-    perm = PointGrid(points)._order(points)
+    perm = PointGrid(points).cell_order(points)
     moved = points[perm]
     _, d2, count = PointGrid(moved).knn(moved, k, max_dist, skip_own=True)
     return torch.empty_like(d2).index_copy_(0, perm, d2), torch.empty_like(count).index_copy_(0, perm, count)
@@ -265,10 +265,10 @@ def statistical_outliers(points, k=20, std_ratio=2.0):
     """(keep bool [N], mean_dist fp64 [N]) by Open3D's statistical rule: mean_dist is the fp64 mean of sqrt(double(d2)) over a
     point's k nearest OTHER points (fewer when the cloud is smaller; NaN without any, and such a point is dropped), mu and sigma
     the mean and the population deviation of the finite mean_dist, and a point is kept when mean_dist <= mu + std_ratio sigma."""
-    points = _points(points, "points")
+    points = points3(points, "points")
     if not (np.isfinite(std_ratio) and std_ratio >= 0):
         raise ValueError(f"ls2fm.cloud.statistical_outliers: std_ratio {std_ratio} must be finite and >= 0")
-    d2, count = _self_neighbours(points, _knn_k(k), None)
+    d2, count = _self_neighbours(points, knn_k(k), None)
     dist = torch.sqrt(d2.to(torch.float64))
     dist = torch.where(d2 < float("inf"), dist, torch.zeros_like(dist))
     mean = dist.sum(dim=1) / count.to(torch.float64)                              # 0 / 0 = NaN: no neighbour
@@ -284,12 +284,12 @@ def statistical_outliers(points, k=20, std_ratio=2.0):
 def radius_outliers(points, radius, min_neighbors):
     """keep bool [N]: the points with at least min_neighbors OTHER points within `radius` (d2 <= float32(radius)^2), 1 <=
     min_neighbors <= 32.  One knn with k = min_neighbors: a point is kept when its list came back full, exact in integers."""
-    points = _points(points, "points")
+    points = points3(points, "points")
     if isinstance(min_neighbors, bool) or int(min_neighbors) != min_neighbors or not 1 <= int(min_neighbors) <= KNN_MAX_K:
         raise ValueError(f"ls2fm.cloud.radius_outliers: min_neighbors {min_neighbors} must be an integer in [1, {KNN_MAX_K}]")
     if radius is None:
         raise ValueError("ls2fm.cloud.radius_outliers: radius None is no radius")
-    _max_d2(radius)
+    squared_cutoff(radius)
     _, count = _self_neighbours(points, int(min_neighbors), radius)
     return count == int(min_neighbors)
 

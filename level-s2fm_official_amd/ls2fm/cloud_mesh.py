@@ -27,9 +27,9 @@ import math
 
 import torch
 
-from . import _lib, cloud, mesh
+from . import _lib, cloud, lattice, mesh
 from ._lib import check, ptr, stream_ptr
-from .metrics import PointGrid, _knn_k, _max_d2, _points
+from .point_grid import PointGrid, knn_k, points3, squared_cutoff
 
 RADIUS_VOXELS = 3.0         # the default support radius, in voxels
 # the launch plans of ls2fm_cloud_implicit_plan (include/ls2fm.h: LS2FM_CLOUD_IMPLICIT_BRICK0_* / _BRICK1_*) and the default one
@@ -38,10 +38,9 @@ DEFAULT_PLAN = dict(brick=1, empty_test=True)
 
 
 class ImplicitVolume:
-    """value and support float32 [nx, ny, nz] of THE IMPLICIT RULE on one device.  Lattice point i sits at (float32) i * voxel +
-    origin per axis -- marching cubes' vertex expression with spacing = (voxel,) * 3, TsdfVolume's layout -- so the extracted mesh
-    is in the cloud's frame.  value is NaN where the rule defines none; support is the sum of the weights (0 without a neighbour).
-    radius is the support radius the volume was made with."""
+    """value and support float32 [nx, ny, nz] of THE IMPLICIT RULE on one device, on the lattice of ls2fm/lattice.py (TsdfVolume's
+    layout), so the extracted mesh is in the cloud's frame.  value is NaN where the rule defines none; support is the sum of the
+    weights (0 without a neighbour).  radius is the support radius the volume was made with."""
 
     def __init__(self, value, support, origin, voxel, radius):
         self.value, self.support = value, support
@@ -54,15 +53,10 @@ class ImplicitVolume:
 
 
 def _lattice(bounds, voxel):
-    """(shape, origin) as fusion.volume_for shapes a lattice over bounds: origin at the low corner, per axis
-    ceil((high - low) / voxel) + 1 points, at least 2"""
-    lo, hi = ([float(v) for v in b] for b in bounds)
-    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(v) for v in lo + hi):
-        raise ValueError(f"ls2fm.cloud_mesh: the bounds {lo} .. {hi} must be two finite corners")
-    shape = tuple(max(2, int(math.ceil((h - l) / voxel)) + 1) for l, h in zip(lo, hi))
+    shape, origin = lattice.shape_for(bounds, voxel, "ls2fm.cloud_mesh: the bounds {lo} .. {hi} must be two finite corners")
     if max(shape) > 2 ** 24 or math.prod(shape) >= 2 ** 31:
         raise ValueError(f"ls2fm.cloud_mesh: a lattice of {shape} points, a side above 2^24 or 2^31 points or more")
-    return shape, tuple(lo)
+    return shape, origin
 
 
 def _options(voxel, radius, k, min_neighbors):
@@ -70,19 +64,13 @@ def _options(voxel, radius, k, min_neighbors):
     if not 0.0 < voxel < math.inf:
         raise ValueError(f"ls2fm.cloud_mesh: voxel {voxel} must be positive and finite")
     radius = RADIUS_VOXELS * voxel if radius is None else float(radius)
-    max_d2 = _max_d2(radius)
+    max_d2 = squared_cutoff(radius)
     if not 0.0 < float(max_d2) < math.inf:
         raise ValueError(f"ls2fm.cloud_mesh: radius {radius} must have a positive finite fp32 square (the weight needs it)")
-    k = _knn_k(k)
+    k = knn_k(k)
     if isinstance(min_neighbors, bool) or int(min_neighbors) != min_neighbors or int(min_neighbors) < 1:
         raise ValueError(f"ls2fm.cloud_mesh: min_neighbors {min_neighbors} must be an integer >= 1")
     return voxel, radius, max_d2, k, int(min_neighbors)
-
-
-def _lattice_points(shape, origin, voxel, device):
-    """float32 [nx ny nz, 3]: the lattice expression, axis 2 fastest"""
-    axes = [torch.arange(s, device=device).float() * voxel + o for s, o in zip(shape, origin)]
-    return torch.stack([t.reshape(-1) for t in torch.meshgrid(*axes, indexing="ij")], dim=1)
 
 
 @torch.no_grad()
@@ -90,7 +78,7 @@ def _implicit_torch(points, normals, shape, origin, voxel, radius, k=16, min_nei
     """THE IMPLICIT RULE as plain torch ops on the points' device -> (value, support) float32 [nx, ny, nz].  The lattice points go
     in chunks through PointGrid.knn (device tensors; `grid` is reused) or cloud._knn_torch (CPU tensors); the two sums are then
     accumulated over the list's columns in a Python loop, so that each add rounds once, both starting from their first term."""
-    points, normals = _points(points, "points").float(), _points(normals, "normals").float()
+    points, normals = points3(points, "points").float(), points3(normals, "normals").float()
     voxel, radius, max_d2, k, min_neighbors = _options(voxel, radius, k, min_neighbors)
     dev = points.device
     n_points = int(points.shape[0])
@@ -99,7 +87,7 @@ def _implicit_torch(points, normals, shape, origin, voxel, radius, k=16, min_nei
     support = torch.zeros(total, dtype=torch.float32, device=dev)
     if n_points == 0 or total == 0:
         return value.view(shape), support.view(shape)
-    X = _lattice_points(shape, origin, voxel, dev)
+    X = torch.stack(lattice.points(shape, origin, voxel, dev), dim=1)
     p64, n64 = points.to(torch.float64), normals.to(torch.float64)
     lim = torch.tensor(float(max_d2), dtype=torch.float64, device=dev)      # a tensor: a Python scalar would divide by its reciprocal
     if points.is_cuda and grid is None:
@@ -139,8 +127,7 @@ def _implicit_device(points, normals, grid, shape, origin, voxel, k, max_d2, min
     with torch.cuda.device(dev):
         value = torch.empty(shape, dtype=torch.float32, device=dev)
         support = torch.empty(shape, dtype=torch.float32, device=dev)
-        head = (ptr(points), ptr(normals), grid.n, ptr(grid.sorted), ptr(grid.cell_start), grid._origin, grid.cell_size, grid.inv_cell_size,
-                grid._dim, *shape, og, voxel, k, float(max_d2), min_neighbors)
+        head = (ptr(points), ptr(normals), *grid.c_args(n_first=True), *shape, og, voxel, k, float(max_d2), min_neighbors)
         if plan is None:
             check(lib.ls2fm_cloud_implicit(*head, ptr(value), ptr(support), stream_ptr()), "ls2fm_cloud_implicit")
         else:
@@ -155,12 +142,12 @@ def implicit_from_cloud(points, normals, voxel, radius=None, k=16, min_neighbors
       voxel          the lattice spacing;  radius  the support radius, default 3 voxels (RADIUS_VOXELS); a lattice point farther
                      than that from every point stays undefined (NaN)
       k              neighbours per lattice point, 1 .. 32;  min_neighbors  fewer neighbours inside the radius leave NaN
-      bounds         ((x0, y0, z0), (x1, y1, z1)) of the lattice, shaped as fusion.volume_for shapes it; default: the cloud's box
+      bounds         ((x0, y0, z0), (x1, y1, z1)) of the lattice, shaped as lattice.shape_for shapes it; default: the cloud's box
                      grown by the radius, which costs one host read (the box) -- give bounds to avoid it
-      grid           a metrics.PointGrid over `points` to reuse; it is used when no point had to be dropped
+      grid           a point_grid.PointGrid over `points` to reuse; it is used when no point had to be dropped
     Points with a non-finite coordinate or normal are dropped first, with torch ops (the count of the rest is a host read, as is
     the box of a grid built here).  One launch on the device; CPU tensors go through _implicit_torch."""
-    points, normals = _points(points, "points"), _points(normals, "normals")
+    points, normals = points3(points, "points"), points3(normals, "normals")
     if points.shape[0] != normals.shape[0] or points.device != normals.device:
         raise ValueError(f"ls2fm.cloud_mesh.implicit_from_cloud: {points.shape[0]} points on {points.device}, "
                          f"{normals.shape[0]} normals on {normals.device}")
@@ -176,8 +163,7 @@ def implicit_from_cloud(points, normals, voxel, radius=None, k=16, min_neighbors
     if bounds is None:
         if not points.shape[0]:
             raise ValueError("ls2fm.cloud_mesh.implicit_from_cloud: a cloud without a finite point has no box; give bounds")
-        lo, hi = (t.tolist() for t in torch.stack([points.amin(dim=0), points.amax(dim=0)]).cpu())
-        bounds = ([t - radius for t in lo], [t + radius for t in hi])
+        bounds = lattice.grown_box(points, radius)
     shape, origin = _lattice(bounds, voxel)
     if not points.is_cuda:
         value, support = _implicit_torch(points, normals, shape, origin, voxel, radius, k, min_neighbors)
@@ -190,15 +176,10 @@ def implicit_from_cloud(points, normals, voxel, radius=None, k=16, min_neighbors
 @torch.no_grad()
 def extract(volume: ImplicitVolume, min_support=0.0) -> mesh.Mesh:
     """The mesh of the volume's zero level -> ls2fm.mesh.Mesh in the cloud's frame, faces oriented along the normals (as
-    fusion.extract's toward the cameras).  A lattice point of support < min_support becomes NaN like the undefined ones, which
-    marching cubes' rule reads as "not below"; every face with a non-finite vertex is then dropped and the vertices no face uses,
-    both in their order (mesh.finite_faces, the tail of fusion.extract).  Host reads: marching cubes' counts and the sizes of the
-    result."""
+    fusion.extract's toward the cameras).  A lattice point of support < min_support takes no part (lattice.zero_level), like the
+    undefined ones, whose value is NaN already.  Host reads: marching cubes' counts and the sizes of the result."""
     _lib.require_device_tensors("ls2fm.cloud_mesh.extract", volume.value, volume.support, phrase=": marching cubes runs on MI355X only")
-    with torch.cuda.device(volume.device):
-        vol = torch.where(volume.support >= float(min_support), volume.value, torch.full_like(volume.value, math.nan))
-        verts, faces = mesh.marching_cubes(vol, 0.0, spacing=(volume.voxel,) * 3, origin=volume.origin)
-        return mesh.finite_faces(verts, faces)
+    return lattice.zero_level(volume.value, volume.support >= float(min_support), volume.voxel, volume.origin)
 
 
 @torch.no_grad()
@@ -212,7 +193,7 @@ def mesh_from_cloud(points, normals=None, voxel=None, toward=None, normals_k=16,
       voxel       the lattice spacing (required);  **implicit: radius, k, min_neighbors, bounds, grid as implicit_from_cloud"""
     if voxel is None:
         raise ValueError("ls2fm.cloud_mesh.mesh_from_cloud: voxel, the lattice spacing, is required")
-    points = _points(points, "points")
+    points = points3(points, "points")
     if normals is None:
         if toward is None:
             raise ValueError("ls2fm.cloud_mesh.mesh_from_cloud: without normals, toward is required: estimated normals have no "

@@ -33,7 +33,7 @@ import math
 
 import torch
 
-from . import _lib, _posed, mesh, raster
+from . import _lib, _posed, lattice, mesh, raster
 from ._lib import check, ptr, stream_ptr
 
 TRUNC_VOXELS = 3.0          # the default truncation distance, in voxels
@@ -41,10 +41,9 @@ _device = functools.partial(_lib.require_device_tensors, "ls2fm.fusion", phrase=
 
 
 class TsdfVolume:
-    """A dense TSDF volume: tsdf and weight float32 [nx, ny, nz] on `device`, zero when fresh.  Lattice point i sits at
-    (float32) i * voxel + origin per axis -- marching cubes' vertex expression with spacing = (voxel,) * 3 -- so the extracted
-    mesh is in the depth maps' world frame.  shape: three ints, each >= 2 for extract; origin: three floats; voxel and trunc
-    positive and finite."""
+    """A dense TSDF volume: tsdf and weight float32 [nx, ny, nz] on `device`, zero when fresh, on the lattice of ls2fm/lattice.py,
+    so the extracted mesh is in the depth maps' world frame.  shape: three ints, each >= 2 for extract; origin: three floats;
+    voxel and trunc positive and finite."""
 
     def __init__(self, shape, origin, voxel, trunc, device):
         shape = tuple(int(s) for s in shape)
@@ -136,8 +135,7 @@ def integrate_torch(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=
     K = torch.as_tensor(intr).detach().reshape(-1, 3, 3).float().to(dev).expand(n, 3, 3)
     depth = torch.as_tensor(depth).detach().float().to(dev)
     H, W = int(depth.shape[1]), int(depth.shape[2])
-    axes = [torch.arange(s, device=dev).float() * volume.voxel + o for s, o in zip(volume.shape, volume.origin)]
-    x, y, z = (t.reshape(-1) for t in torch.meshgrid(*axes, indexing="ij"))
+    x, y, z = lattice.points(volume.shape, volume.origin, volume.voxel, dev)
     T, Wt = volume.tsdf.view(-1), volume.weight.view(-1)
     # 0-dim device tensors: a division by a Python scalar would be a multiplication by its reciprocal
     scalar = lambda t: torch.tensor(float(t), dtype=torch.float32, device=dev)
@@ -163,26 +161,16 @@ def integrate_torch(volume: TsdfVolume, depth, pose, intr, near=1e-3, max_depth=
 @torch.no_grad()
 def extract(volume: TsdfVolume, min_weight=1.0) -> mesh.Mesh:
     """The mesh of the volume's zero level -> ls2fm.mesh.Mesh, in the depth maps' world frame, normals toward the cameras.
-    A lattice point of weight < min_weight is unobserved: its value becomes NaN, which marching cubes' rule reads as "not below",
-    so an edge from a below corner to an unobserved one gets a NaN vertex.  Every face with a non-finite vertex coordinate is
-    dropped, then the vertices no face uses, both in their order, with torch ops.  A cell with an unobserved corner keeps the faces
-    whose three vertices lie on observed edges (Open3D drops such cells whole).  Host reads: marching cubes' counts, and the sizes
-    of the result."""
-    with torch.cuda.device(volume.device):
-        vol = torch.where(volume.weight >= float(min_weight), volume.tsdf, torch.full_like(volume.tsdf, math.nan))
-        verts, faces = mesh.marching_cubes(vol, 0.0, spacing=(volume.voxel,) * 3, origin=volume.origin)
-        return mesh.finite_faces(verts, faces)
+    A lattice point of weight < min_weight is unobserved and takes no part (lattice.zero_level): a cell with such a corner keeps the
+    faces whose three vertices lie on observed edges (Open3D drops it whole).  Host reads: marching cubes' counts, the result's sizes."""
+    return lattice.zero_level(volume.tsdf, volume.weight >= float(min_weight), volume.voxel, volume.origin)
 
 
 def volume_for(bounds, voxel, trunc=None, device="cuda") -> TsdfVolume:
-    """a fresh volume whose lattice covers bounds = ((x0, y0, z0), (x1, y1, z1)): origin at the low corner, per axis
-    ceil((high - low) / voxel) + 1 points, at least 2.  trunc defaults to TRUNC_VOXELS = 3 voxels."""
-    lo, hi = ([float(v) for v in b] for b in bounds)
-    voxel = float(voxel)
-    if not 0.0 < voxel < math.inf or not all(math.isfinite(v) for v in lo + hi):
-        raise ValueError(f"ls2fm.fusion: voxel {voxel} must be positive and finite, and the bounds {lo} .. {hi} finite")
-    shape = [max(2, int(math.ceil((h - l) / voxel)) + 1) for l, h in zip(lo, hi)]
-    return TsdfVolume(shape, lo, voxel, TRUNC_VOXELS * voxel if trunc is None else trunc, device)
+    """a fresh volume whose lattice covers bounds = ((x0, y0, z0), (x1, y1, z1)) as lattice.shape_for shapes it: origin at the low
+    corner, per axis ceil((high - low) / voxel) + 1 points, at least 2.  trunc defaults to TRUNC_VOXELS = 3 voxels."""
+    shape, origin = lattice.shape_for(bounds, voxel, "ls2fm.fusion: voxel {voxel} must be positive and finite, and the bounds {lo} .. {hi} finite")
+    return TsdfVolume(shape, origin, voxel, TRUNC_VOXELS * float(voxel) if trunc is None else trunc, device)
 
 
 @torch.no_grad()
@@ -204,8 +192,7 @@ def fuse_mesh(verts, faces, pose, intr, H, W, voxel, trunc=None, bounds=None, ne
     if bounds is None:
         if not v.shape[0]:
             raise ValueError("ls2fm.fusion.fuse_mesh: an empty mesh has no box; give bounds")
-        lo, hi = (t.tolist() for t in torch.stack([v.amin(dim=0), v.amax(dim=0)]).cpu())
-        bounds = ([t - trunc for t in lo], [t + trunc for t in hi])
+        bounds = lattice.grown_box(v, trunc)
     volume = volume_for(bounds, voxel, trunc, v.device)
     for s, e in _posed.chunks(int(poses.shape[0]), 8, H, W, max_workspace_bytes):
         depth = raster.rasterize_prepared(v, f, poses[s:e], k4[s:e], H, W, near, max_workspace_bytes=max_workspace_bytes).depth

@@ -2,25 +2,18 @@
 similarity alignment (rotation in degrees, ATE) and the DTU Chamfer distance of the mesh (accuracy, completeness, their mean); the
 reference ships neither, and the usual CPU KD-tree evaluation of two DTU-sized clouds takes minutes per scan.
 
-  PointGrid / nearest_neighbors   exact nearest neighbours over a uniform grid (ls2fm_point_grid_*, csrc/point_grid.hip);
-                                  PointGrid.knn: the k nearest (ls2fm.cloud builds normals and outlier filters on it)
+  PointGrid / nearest_neighbors   exact nearest neighbours over a uniform grid: ls2fm/point_grid.py, re-exported here
   normal_consistency              mean |n . n'| over the nearest-neighbour pairs, both directions
-  nearest_neighbors_bruteforce    the same rule as plain torch ops on any device: the timing baseline and the host tests' route
   voxel_downsample                one point per voxel, the lowest index
   chamfer / evaluate_mesh         accuracy, completeness, overall, precision / recall / F-score
   align_sim3 / pose_errors        Umeyama's similarity alignment, rotation and centre errors, ATE
   icp / IcpResult                 registration of a cloud to ground truth over the grid (ls2fm_icp_run, csrc/icp.hip); evaluate_mesh
                                   takes it (init=, icp=) for a mesh in another gauge than the ground truth
 
-The distance rule (include/ls2fm.h): dx = q.x - r.x, dy, dz likewise, d2 = (dx dx + dy dy) + dz dz, every operation one rounded
-fp32 operation; a reference qualifies when d2 <= max_d2 and d2 < +inf; the smallest d2 wins, among equal d2 the lowest index.  The
-result is a pure function of the two clouds: no grid, batch or visiting order shows in it, and tests/metrics_restate.py holds it bit
-for bit.  There is no CPU path for the grid: CPU tensors, a missing device or a missing library raise.
+ls2fm/point_grid.py states the distance rule.  There is no CPU path for the grid: CPU tensors, a missing device or a missing library raise.
 """
 from __future__ import annotations
 
-import ctypes
-import functools
 import math
 
 import numpy as np
@@ -28,235 +21,9 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-
-# The automatic cell size (auto_cell_size): "surface" sizes the cells for points on a surface, "volume" for points filling the box.
-# Chosen by tools/time_metrics.py on 2 M x 2 M points of a sphere surface (profiles/metrics_time.json).
-AUTO_CELL_RULE = "surface"
-
-
-_device = functools.partial(_lib.require_device_tensors, "ls2fm.metrics", phrase=": the point grid runs on MI355X only",
-                            more=" -- nearest_neighbors_bruteforce is the explicit torch form")
-
-
-def _points(x, name):
-    x = torch.as_tensor(x)
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"ls2fm.metrics: {name} must be [n, 3], got shape {tuple(x.shape)}")
-    return x
-
-
-def _max_d2(max_dist):
-    """float32(max_dist) * float32(max_dist) as a numpy float32; +inf for None"""
-    if max_dist is None:
-        return np.float32(np.inf)
-    m = np.float32(max_dist)
-    if not m >= 0:
-        raise ValueError(f"ls2fm.metrics: max_dist {max_dist} must be >= 0 (None: no cut-off)")
-    with np.errstate(over="ignore"):
-        return np.float32(m * m)
-
-
-def _dims(extent32, inv_h):
-    """cells per axis that hold every reference: floor((max - origin) * inv_h) + 1 in the device's fp32 arithmetic (float64 [3])"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.floor((extent32 * inv_h).astype(np.float32)).astype(np.float64) + 1.0
-
-
-def auto_cell_size(lo, hi, n, max_cells=2 ** 25, rule=None):
-    """The automatic cell size of a cloud of n points inside the box [lo, hi] (host numbers).  Over the axes of non-zero extent e:
-      "surface"  three axes: sqrt(2 (ex ey + ey ez + ez ex) / n), about one point per cell that a surface through the box crosses;
-                 two axes: sqrt(e1 e2 / n); one axis: e1 / n
-      "volume"   (product of e / n) ^ (1 / axes): one point per cell of the box
-    a cloud without extent gets 1.  The size is then grown by 5 % at a time until the grid has at most max_cells cells, so it is
-    always positive and finite."""
-    rule = AUTO_CELL_RULE if rule is None else rule
-    if rule not in ("surface", "volume"):
-        raise ValueError(f"ls2fm.metrics.auto_cell_size: rule {rule!r} is neither 'surface' nor 'volume'")
-    lo32, hi32 = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
-    extent32 = (hi32 - lo32).astype(np.float32)
-    e = [float(v) for v in extent32 if v > 0]
-    n = max(int(n), 1)
-    if not e:
-        h = 1.0
-    elif rule == "volume" or len(e) < 3:
-        h = (math.prod(e) / n) ** (1.0 / len(e))
-    else:
-        h = math.sqrt(2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0]) / n)
-    h = max(h, max(e, default=1.0) * 2.0 ** -20, float(np.finfo(np.float32).tiny) * 2.0 ** 24)
-    while True:
-        h32 = np.float32(h)
-        if np.isfinite(h32) and h32 > 0 and float(np.prod(_dims(extent32, np.float32(1) / h32))) <= max_cells:
-            return float(h32)
-        h *= 1.05
-
-
-class PointGrid:
-    """A uniform grid over the reference cloud `ref` (float32 [N, 3] on the device, finite) for exact nearest-neighbour queries.
-    origin is the per-axis minimum; `cell_size` is honoured exactly (ValueError if the grid would have more than `max_cells`
-    cells), None takes auto_cell_size.  Building reads the bounding box on the host once; cell_start int32 [cells + 1], sorted_xyz
-    float32 [N, 3] and sorted_index int32 [N] (views of one [N, 4] array) are the grid."""
-
-    def __init__(self, ref, cell_size=None, max_cells=2 ** 25):
-        ref = _points(ref, "ref")
-        _device(ref)
-        lib = _lib.load()
-        self.ref = _lib.cf(ref)
-        self.n = int(self.ref.shape[0])
-        self.device = dev = self.ref.device
-        if self.n >= 1 << 31:
-            raise ValueError(f"ls2fm.metrics.PointGrid: {self.n} points, 2^31 or more")
-        if self.n:
-            box = torch.stack([self.ref.amin(dim=0), self.ref.amax(dim=0)]).cpu().numpy()          # the one host read
-            if not np.isfinite(box).all():
-                raise ValueError("ls2fm.metrics.PointGrid: the reference cloud holds a NaN or infinite coordinate")
-        else:
-            box = np.zeros((2, 3), np.float32)
-        lo, hi = box[0].astype(np.float32), box[1].astype(np.float32)
-        if cell_size is None:
-            h = np.float32(auto_cell_size(lo, hi, self.n, max_cells))
-        else:
-            h = np.float32(cell_size)
-            if not (np.isfinite(h) and h > 0):
-                raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {cell_size} must be positive and finite")
-        with np.errstate(over="ignore"):
-            inv_h = np.float32(1) / h
-        if not (np.isfinite(inv_h) and inv_h > 0):
-            raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {cell_size} has no finite fp32 reciprocal")
-        dims = _dims((hi - lo).astype(np.float32), inv_h)
-        cells = float(np.prod(dims))
-        if not np.isfinite(cells) or cells > max_cells or cells >= 2 ** 31 - 1:
-            raise ValueError(f"ls2fm.metrics.PointGrid: cell_size {float(h)} gives {dims.astype(np.int64).tolist()} cells, "
-                             f"more than max_cells = {max_cells}")
-        self.origin, self.cell_size, self.inv_cell_size = lo, float(h), float(inv_h)
-        self.box_max = hi
-        self.dim = tuple(int(d) for d in dims)
-        self.n_cells = int(cells)
-        self._origin = (ctypes.c_float * 3)(*[float(v) for v in lo])
-        self._dim = (ctypes.c_int32 * 3)(*self.dim)
-        with torch.cuda.device(dev):
-            self.cell_start = torch.empty(self.n_cells + 1, dtype=torch.int32, device=dev)
-            self.sorted = torch.empty(self.n, 4, dtype=torch.float32, device=dev)
-            ws = _lib.workspace(lib.ls2fm_point_grid_workspace_bytes(self.n, self.n_cells), "ls2fm_point_grid_workspace_bytes", dev)
-            check(lib.ls2fm_point_grid_build(ptr(self.ref), self.n, self._origin, self.cell_size, self.inv_cell_size, self._dim,
-                                             ptr(self.cell_start), ptr(self.sorted), ptr(ws), stream_ptr()), "ls2fm_point_grid_build")
-        self.sorted_xyz = self.sorted[:, :3]
-        self.sorted_index = self.sorted.view(torch.int32)[:, 3]
-
-    def _order(self, q):
-        """a permutation that walks the queries cell by cell (any order gives the same results: this one is for the caches)"""
-        o = torch.as_tensor(self.origin, device=q.device)
-        c = ((torch.nan_to_num(q, nan=0.0, posinf=0.0, neginf=0.0) - o) * self.inv_cell_size).floor()
-        c = torch.minimum(c.clamp_(min=0), torch.tensor([d - 1 for d in self.dim], dtype=torch.float32, device=q.device)).long()
-        return torch.argsort((c[:, 2] * self.dim[1] + c[:, 1]) * self.dim[0] + c[:, 0])
-
-    def query(self, q, max_dist=None, sort=None):
-        """(idx int32 [M], d2 float32 [M]) of the queries `q` (float32 [M, 3] on the grid's device): the index into `ref` of each
-        query's nearest reference by the distance rule and its fp32 squared distance; -1 and +inf where no reference lies within
-        `max_dist` (d2 <= float32(max_dist)^2; None: no cut-off) and for a NaN or infinite query.  Reads nothing back, so it can
-        be captured into a graph.  The queries are walked in the order of their cells and the results put back (measured faster by the
-        same tool; a torch sort, so not while a stream captures); sort=False walks them as given.  No result depends on it."""
-        q = _points(q, "q")
-        _device(q)
-        if q.device != self.device:
-            raise ValueError(f"ls2fm.metrics.PointGrid.query: queries on {q.device}, the grid on {self.device}")
-        q = _lib.cf(q)
-        max_d2 = _max_d2(max_dist)
-        m = int(q.shape[0])
-        with torch.cuda.device(self.device):
-            capturing = torch.cuda.is_current_stream_capturing()
-            perm = None
-            if (sort is None or sort) and not capturing and m > 1 and self.n:
-                perm = self._order(q)
-                q = q[perm]
-            idx = torch.empty(m, dtype=torch.int32, device=self.device)
-            d2 = torch.empty(m, dtype=torch.float32, device=self.device)
-            check(_lib.load().ls2fm_point_grid_query(ptr(q), m, ptr(self.sorted), ptr(self.cell_start), self.n, self._origin,
-                                                     self.cell_size, self.inv_cell_size, self._dim, float(max_d2), ptr(idx), ptr(d2),
-                                                     stream_ptr()), "ls2fm_point_grid_query")
-            if perm is not None:
-                idx, d2 = torch.empty_like(idx).index_copy_(0, perm, idx), torch.empty_like(d2).index_copy_(0, perm, d2)
-        return idx, d2
-
-    def knn(self, q, k, max_dist=None, skip_own=False, sort=None):
-        """(idx int32 [M, k], d2 float32 [M, k], count int32 [M]) of the queries `q`: each query's qualifying references ordered by
-        (d2, index), the first k of them (1 <= k <= KNN_MAX_K; the K-NEIGHBOUR RULE of include/ls2fm.h), -1 / +inf in the slots
-        without one and the number of filled slots.  skip_own: query t ignores reference t -- `q` must be the grid's own cloud
-        in its order (M == N is checked, the rest is the caller's promise); a duplicate at another index stays a neighbour.
-        One launch (ls2fm_point_grid_knn), nothing read back; the cell-order walk, its put-back and `sort` are `query`'s."""
-        q = _points(q, "q")
-        _device(q)
-        if q.device != self.device:
-            raise ValueError(f"ls2fm.metrics.PointGrid.knn: queries on {q.device}, the grid on {self.device}")
-        k = _knn_k(k)
-        q = _lib.cf(q)
-        max_d2 = _max_d2(max_dist)
-        m = int(q.shape[0])
-        if skip_own and m != self.n:
-            raise ValueError(f"ls2fm.metrics.PointGrid.knn: skip_own needs the grid's own cloud as queries, got {m} queries for {self.n} points")
-        with torch.cuda.device(self.device):
-            capturing = torch.cuda.is_current_stream_capturing()
-            perm = None
-            # skip_own identifies a query by its position: those are walked as given
-            if (sort is None or sort) and not capturing and not skip_own and m > 1 and self.n:
-                perm = self._order(q)
-                q = q[perm]
-            idx = torch.empty(m, k, dtype=torch.int32, device=self.device)
-            d2 = torch.empty(m, k, dtype=torch.float32, device=self.device)
-            count = torch.empty(m, dtype=torch.int32, device=self.device)
-            check(_lib.load().ls2fm_point_grid_knn(ptr(q), m, ptr(self.sorted), ptr(self.cell_start), self.n, self._origin,
-                                                   self.cell_size, self.inv_cell_size, self._dim, k, float(max_d2), 1 if skip_own else 0,
-                                                   ptr(idx), ptr(d2), ptr(count), stream_ptr()), "ls2fm_point_grid_knn")
-            if perm is not None:
-                idx, d2, count = (torch.empty_like(x).index_copy_(0, perm, x) for x in (idx, d2, count))
-        return idx, d2, count
-
-
-KNN_MAX_K = 32                            # the largest list capacity ls2fm_point_grid_knn instantiates
-
-
-def _knn_k(k):
-    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNN_MAX_K:
-        raise ValueError(f"ls2fm.metrics: k {k} must be an integer in [1, {KNN_MAX_K}]")
-    return int(k)
-
-
-def nearest_neighbors(q, ref, max_dist=None, cell_size=None):
-    """PointGrid(ref, cell_size).query(q, max_dist) in one call: (idx int32 [M], d2 float32 [M])"""
-    q, ref = _points(q, "q"), _points(ref, "ref")
-    _device(q, ref)
-    return PointGrid(ref, cell_size=cell_size).query(q, max_dist)
-
-
-def nearest_neighbors_bruteforce(q, ref, max_dist=None, chunk=None):
-    """The distance rule as plain torch ops, on whatever device the clouds are on: all M x N distances, `chunk` queries at a time
-    (default: 2^24 distances per chunk).  The column differences, the three products and the two sums are separate torch ops in
-    the stated order, so each rounds once; the minimum is taken first and the lowest index among the entries that equal it second
-    (torch.argmin does not promise the first).  -> (idx int32 [M], d2 float32 [M]).  The timing baseline of the grid and the CPU
-    route of the host tests; nothing in the library falls back to it."""
-    q, ref = _points(q, "q").float(), _points(ref, "ref").float()
-    dev = q.device
-    ref = ref.to(dev)
-    m, n = int(q.shape[0]), int(ref.shape[0])
-    max_d2 = float(_max_d2(max_dist))
-    idx = torch.full((m,), -1, dtype=torch.int32, device=dev)
-    d2_out = torch.full((m,), float("inf"), dtype=torch.float32, device=dev)
-    if m == 0 or n == 0:
-        return idx, d2_out
-    chunk = max(1, (1 << 24) // n) if chunk is None else max(1, int(chunk))
-    rx, ry, rz = ref[:, 0][None, :], ref[:, 1][None, :], ref[:, 2][None, :]
-    index = torch.arange(n, device=dev)[None, :]
-    big = torch.iinfo(torch.int64).max
-    for s in range(0, m, chunk):
-        c = q[s:s + chunk]
-        dx, dy, dz = c[:, 0:1] - rx, c[:, 1:2] - ry, c[:, 2:3] - rz
-        d2 = (dx * dx + dy * dy) + dz * dz
-        ok = (d2 <= max_d2) & (d2 < float("inf"))
-        d2 = torch.where(ok, d2, torch.full_like(d2, float("inf")))
-        mn = d2.amin(dim=1)
-        first = torch.where((d2 == mn[:, None]) & ok, index, torch.full_like(index, big)).amin(dim=1)
-        idx[s:s + chunk] = torch.where(mn < float("inf"), first, torch.full_like(first, -1)).to(torch.int32)
-        d2_out[s:s + chunk] = mn
-    return idx, d2_out
+from .point_grid import (AUTO_CELL_RULE, KNN_MAX_K, PointGrid, auto_cell_size, cell_dims, knn_k, nearest_neighbors,  # noqa: F401
+                         nearest_neighbors_bruteforce, points3, require_device, squared_cutoff)
+_points, _max_d2, _knn_k, _dims = points3, squared_cutoff, knn_k, cell_dims          # the names they had while they lived here
 
 
 _VOXEL_BITS = 21
@@ -269,7 +36,7 @@ def voxel_downsample(points, voxel):
     A stated deviation: the usual DTU evaluation script thins a cloud by a sequential greedy radius rule (a point is dropped when
     a kept point lies within the radius), which depends on the visiting order and keeps points up to sqrt(3) times sparser or denser
     than this; one point per voxel is order-free up to the choice of the lowest index and runs as one sort."""
-    p = _points(points, "points")
+    p = points3(points, "points")
     if not (np.isfinite(voxel) and voxel > 0):
         raise ValueError(f"ls2fm.metrics.voxel_downsample: voxel {voxel} must be positive and finite")
     if p.shape[0] == 0:
@@ -288,7 +55,7 @@ def voxel_downsample(points, voxel):
 
 
 def _masked(x, mask, name):
-    x = _points(x, name)
+    x = points3(x, name)
     if mask is None:
         return x
     mask = torch.as_tensor(mask, device=x.device)
@@ -328,7 +95,7 @@ def chamfer(pred, gt, max_dist, thresholds=(), pred_mask=None, gt_mask=None, bru
     pred, gt = _masked(pred, pred_mask, "pred"), _masked(gt, gt_mask, "gt")
     thresholds = tuple(float(t) for t in thresholds)
     if not brute_force:
-        _device(pred, gt)
+        require_device(pred, gt)
     if pred.device != gt.device:
         raise ValueError(f"ls2fm.metrics.chamfer: pred on {pred.device}, gt on {gt.device}")
     acc = _one_side(pred, gt, max_dist, thresholds, brute_force)
@@ -362,9 +129,9 @@ def normal_consistency(pred_points, pred_normals, gt_points, gt_normals, max_dis
     (and, empty, the threshold entries of `chamfer`'s dict).  The pairs are PointGrid.query's; the absolute value is there because
     estimated normals (ls2fm.cloud.estimate_normals) are unoriented.  Normals are taken as given, not normalised.  A side without
     a pair gives NaN.  Torch ops on two queries, one host read."""
-    pred, gt = _points(pred_points, "pred_points"), _points(gt_points, "gt_points")
-    pn, gn = _points(pred_normals, "pred_normals"), _points(gt_normals, "gt_normals")
-    _device(pred, gt, pn, gn)
+    pred, gt = points3(pred_points, "pred_points"), points3(gt_points, "gt_points")
+    pn, gn = points3(pred_normals, "pred_normals"), points3(gt_normals, "gt_normals")
+    require_device(pred, gt, pn, gn)
     if pn.shape[0] != pred.shape[0] or gn.shape[0] != gt.shape[0]:
         raise ValueError(f"ls2fm.metrics.normal_consistency: {pn.shape[0]} normals for {pred.shape[0]} points, {gn.shape[0]} for {gt.shape[0]}")
     if len({t.device for t in (pred, gt, pn, gn)}) != 1:
@@ -389,8 +156,8 @@ def evaluate_mesh(verts, faces, gt_points, max_dist, density, thresholds=(), gen
     `chamfer` runs on the registered sample.  The dict gains s, R, t -- the whole transform from the mesh's frame, ICP after init,
     fp64 device tensors -- and icp_rmse, icp_n_pairs, icp_iterations, icp_status (one more host read)."""
     from . import mesh
-    verts, gt = _points(verts, "verts"), _points(gt_points, "gt_points")
-    _device(verts, faces, gt)
+    verts, gt = points3(verts, "verts"), points3(gt_points, "gt_points")
+    require_device(verts, faces, gt)
     if not (np.isfinite(density) and density > 0):
         raise ValueError(f"ls2fm.metrics.evaluate_mesh: density {density} must be positive and finite")
     register = init is not None or icp is not None
@@ -426,7 +193,7 @@ def align_sim3(src, dst, with_scale=True):
     fp64.  The means, the 3 x 3 covariance and the variance are torch ops on the inputs' device; the 3 x 3 SVD runs on the host
     (no dependence on a device solver); a reflection is corrected through the sign of det(U) det(V).  with_scale=False fixes s = 1.
     -> (s float, R fp64 [3, 3], t fp64 [3]; tensors on src's device)."""
-    src, dst = _points(src, "src"), _points(dst, "dst")
+    src, dst = points3(src, "src"), points3(dst, "dst")
     if src.shape != dst.shape or src.shape[0] < 1:
         raise ValueError(f"ls2fm.metrics.align_sim3: {tuple(src.shape)} against {tuple(dst.shape)}")
     dev = src.device
@@ -544,7 +311,7 @@ class IcpResult:
 
     def apply(self, points):
         """s R p + t of points [n, 3] in fp64 (on the state's device)"""
-        p = _points(points, "points").to(device=self.state.device, dtype=torch.float64)
+        p = points3(points, "points").to(device=self.state.device, dtype=torch.float64)
         return self.s * (p @ self.R.t()) + self.t
 
 
@@ -677,22 +444,22 @@ def icp(src, dst, init=None, dst_normals=None, max_dist=None, with_scale=False, 
     correspondence is its nearest reference only.
     brute_force=True runs the same rule as plain torch ops on any device over nearest_neighbors_bruteforce, with the solve on the
     host: the timing baseline and the CPU route of the host tests; nothing in the library falls back to it."""
-    src = _points(src, "src")
+    src = points3(src, "src")
     grid = dst if isinstance(dst, PointGrid) else None
-    ref = grid.ref if grid is not None else _points(dst, "dst")
+    ref = grid.ref if grid is not None else points3(dst, "dst")
     if not brute_force:
-        _device(src, ref, dst_normals)
+        require_device(src, ref, dst_normals)
     dev = src.device
     if ref.device != dev:
         raise ValueError(f"ls2fm.metrics.icp: src on {dev}, dst on {ref.device}")
     iters = int(iters)
     if not 0 <= iters <= ICP_MAX_ITERS:
         raise ValueError(f"ls2fm.metrics.icp: iters {iters} must be in [0, {ICP_MAX_ITERS}]")
-    max_d2 = _max_d2(max_dist)
+    max_d2 = squared_cutoff(max_dist)
     n = int(ref.shape[0])
     normals = None
     if dst_normals is not None:
-        normals = _points(dst_normals, "dst_normals")
+        normals = points3(dst_normals, "dst_normals")
         if normals.shape[0] != n or normals.device != dev:
             raise ValueError(f"ls2fm.metrics.icp: dst_normals {tuple(normals.shape)} on {normals.device} for {n} points on {dev}")
         normals = _lib.cf(normals)
@@ -731,9 +498,8 @@ def icp(src, dst, init=None, dst_normals=None, max_dist=None, with_scale=False, 
         d2 = torch.empty(m, dtype=torch.float32, device=dev) if return_pairs else None
 
         def run(st, n_iters, pair_idx, pair_d2):
-            check(lib.ls2fm_icp_run(ptr(src), m, ptr(grid.sorted), ptr(grid.cell_start), grid.n, grid._origin, grid.cell_size,
-                                    grid.inv_cell_size, grid._dim, ptr(normals), float(max_d2), 1 if with_scale else 0, n_iters, tol_rot,
-                                    tol_trans, ptr(st), None, ptr(pair_idx), ptr(pair_d2), ptr(ws), stream_ptr()), "ls2fm_icp_run")
+            check(lib.ls2fm_icp_run(ptr(src), m, *grid.c_args(), ptr(normals), float(max_d2), 1 if with_scale else 0, n_iters, tol_rot, tol_trans,
+                                    ptr(st), None, ptr(pair_idx), ptr(pair_d2), ptr(ws), stream_ptr()), "ls2fm_icp_run")
 
         if iters:
             run(state, iters, None, None)

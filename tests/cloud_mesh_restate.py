@@ -5,14 +5,9 @@ import numpy as np
 
 import cloud_restate as R
 import metrics_restate as MR
+from fusion_restate import lattice as lattice_points       # float32 [nx ny nz, 3], axis 2 fastest: the one restatement of the lattice
 
 F32 = np.float32
-
-
-def lattice_points(shape, origin, voxel):
-    """float32 [nx ny nz, 3]: X[a] = fl32(fl32((float) i * voxel) + origin[a]), axis 2 fastest"""
-    axes = [(np.arange(s).astype(F32) * F32(voxel)).astype(F32) + F32(o) for s, o in zip(shape, origin)]
-    return np.stack([g.reshape(-1) for g in np.meshgrid(*axes, indexing="ij")], axis=1).astype(F32)
 
 
 def neighbours(points, shape, origin, voxel, radius, k=32):

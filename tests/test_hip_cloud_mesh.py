@@ -43,7 +43,7 @@ def host(*tensors):
 def kernel(CM, MT, points, normals, shape, origin, voxel, radius, k=S.K, least=S.MIN_NEIGHBORS, cell_size=None, plan=None, grid=None):
     p, n = dev(points), dev(normals)
     grid = MT.PointGrid(p, cell_size=cell_size) if grid is None else grid
-    return CM._implicit_device(p, n, grid, tuple(shape), tuple(origin), float(voxel), k, MT._max_d2(radius), least, plan)
+    return CM._implicit_device(p, n, grid, tuple(shape), tuple(origin), float(voxel), k, MT.squared_cutoff(radius), least, plan)
 
 
 def same(got, exp):
@@ -88,9 +88,8 @@ def test_support_may_be_null(CM, MT):
     grid = MT.PointGrid(p)
     value = torch.empty(sc["shape"], dtype=torch.float32, device=DEV)
     og = (ctypes.c_float * 3)(*sc["origin"])
-    _lib.check(_lib.load().ls2fm_cloud_implicit(_lib.ptr(p), _lib.ptr(n), grid.n, _lib.ptr(grid.sorted), _lib.ptr(grid.cell_start), grid._origin,
-                                                grid.cell_size, grid.inv_cell_size, grid._dim, *sc["shape"], og, sc["voxel"], S.K,
-                                                float(MT._max_d2(sc["radius"])), S.MIN_NEIGHBORS, _lib.ptr(value), None, _lib.stream_ptr()),
+    _lib.check(_lib.load().ls2fm_cloud_implicit(_lib.ptr(p), _lib.ptr(n), *grid.c_args(n_first=True), *sc["shape"], og, sc["voxel"], S.K,
+                                                float(MT.squared_cutoff(sc["radius"])), S.MIN_NEIGHBORS, _lib.ptr(value), None, _lib.stream_ptr()),
                "ls2fm_cloud_implicit")
     assert CR.same_bits(host(value)[0], S.expected("duplicates")[0])
 
@@ -167,7 +166,7 @@ def test_reruns_and_graph_replay_repeat_the_bits(CM, MT):
     exp = S.expected("sphere")
     p, n = dev(sc["points"]), dev(sc["normals"])
     grid = MT.PointGrid(p)
-    run = lambda: CM._implicit_device(p, n, grid, sc["shape"], sc["origin"], sc["voxel"], S.K, MT._max_d2(sc["radius"]), S.MIN_NEIGHBORS)   # noqa: E731
+    run = lambda: CM._implicit_device(p, n, grid, sc["shape"], sc["origin"], sc["voxel"], S.K, MT.squared_cutoff(sc["radius"]), S.MIN_NEIGHBORS)   # noqa: E731
     assert same(run(), exp) and same(run(), exp)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())

@@ -58,8 +58,8 @@ class Device:
         idx = torch.full((self.m,), -7, dtype=torch.int32, device=DEV) if pairs else None
         d2 = torch.full((self.m,), -1.0, dtype=torch.float32, device=DEV) if pairs else None
         out = torch.full((36,), float("nan"), dtype=torch.float64, device=DEV) if sums else None
-        _lib.check(lib.ls2fm_icp_run(_lib.ptr(self.src), self.m, _lib.ptr(g.sorted), _lib.ptr(g.cell_start), g.n, g._origin, g.cell_size,
-                                     g.inv_cell_size, g._dim, _lib.ptr(self.normals), float(self.MT._max_d2(sc["max_dist"])),
+        _lib.check(lib.ls2fm_icp_run(_lib.ptr(self.src), self.m, *g.c_args(), _lib.ptr(self.normals),
+                                     float(self.MT.squared_cutoff(sc["max_dist"])),
                                      1 if sc["with_scale"] else 0, iters, sc["tol_rot"], sc["tol_trans"], _lib.ptr(state), _lib.ptr(out),
                                      _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(ws), _lib.stream_ptr()), "ls2fm_icp_run")
         return idx, d2, out
@@ -254,8 +254,10 @@ def test_refusals(MT):
     ws = _lib.workspace(lib.ls2fm_icp_workspace_bytes(d.m), "ls2fm_icp_workspace_bytes", DEV)
 
     def run(src=d.src, m=d.m, sorted_=g.sorted, cell_size=g.cell_size, max_d2=1.0, iters=1, tol=1e-9, st=state, work=ws):
-        return lib.ls2fm_icp_run(_lib.ptr(src), m, _lib.ptr(sorted_), _lib.ptr(g.cell_start), g.n, g._origin, cell_size, g.inv_cell_size, g._dim,
-                                 None, max_d2, 0, iters, tol, 1e-9, _lib.ptr(st), None, None, None, _lib.ptr(work), _lib.stream_ptr())
+        grid = list(g.c_args())
+        grid[0], grid[4] = _lib.ptr(sorted_), cell_size                      # sorted and cell_size are what the refusals vary
+        return lib.ls2fm_icp_run(_lib.ptr(src), m, *grid, None, max_d2, 0, iters, tol, 1e-9, _lib.ptr(st), None, None, None, _lib.ptr(work),
+                                 _lib.stream_ptr())
 
     assert run() == 0
     torch.cuda.synchronize()

@@ -120,7 +120,7 @@ def test_auto_cell_size_is_positive_for_every_extent():
             for n in (0, 1, 257, 2_000_000):
                 h = MT.auto_cell_size(lo, hi, n, rule=rule)
                 assert np.isfinite(h) and h > 0
-                dims = MT._dims((np.asarray(hi, np.float32) - np.asarray(lo, np.float32)), np.float32(1) / np.float32(h))
+                dims = MT.cell_dims((np.asarray(hi, np.float32) - np.asarray(lo, np.float32)), np.float32(1) / np.float32(h))
                 assert np.prod(dims) <= 2 ** 25
 
 
@@ -130,7 +130,7 @@ def test_surface_scene_at_a_quarter_cell_scans_in_two_rounds():
     ref = S.scenes()["surface"]["ref"]
     lo, hi = ref.min(axis=0), ref.max(axis=0)
     h = np.float32(MT.auto_cell_size(lo, hi, len(ref)) / 4)
-    dims = MT._dims((hi - lo).astype(np.float32), np.float32(1) / h)
+    dims = MT.cell_dims((hi - lo).astype(np.float32), np.float32(1) / h)
     assert 1024 * 1024 < np.prod(dims) <= 2 ** 25
 
 

@@ -47,7 +47,7 @@ def step_kernel(a):
     p, n, voxel, bounds = workload(a)
     shape, origin = CM._lattice(bounds, voxel)
     radius = RADIUS_VOXELS * voxel
-    max_d2 = MT._max_d2(radius)
+    max_d2 = MT.squared_cutoff(radius)
     g = MT.PointGrid(p)
     res = dict(n=a.n, sphere_radius=RADIUS, lattice=list(shape), voxel=voxel, radius=radius, k=K, min_neighbors=MIN_NEIGHBORS,
                cell_size=g.cell_size, grid_dim=list(g.dim), default_plan=CM.DEFAULT_PLAN)
@@ -85,7 +85,7 @@ def step_torch(a):
     while side <= a.side:
         shape = (side,) * 3
         origin = (RADIUS - 0.5 * (side - 1) * voxel, -0.5 * (side - 1) * voxel, -0.5 * (side - 1) * voxel)     # the surface runs through it
-        want = CM._implicit_device(p, n, g, shape, origin, voxel, K, MT._max_d2(radius), MIN_NEIGHBORS)
+        want = CM._implicit_device(p, n, g, shape, origin, voxel, K, MT.squared_cutoff(radius), MIN_NEIGHBORS)
         t0 = time.perf_counter()
         got = CM._implicit_torch(p, n, shape, origin, voxel, radius, K, MIN_NEIGHBORS, grid=g)
         torch.cuda.synchronize()
@@ -94,7 +94,7 @@ def step_torch(a):
         if not (torch.equal(torch.isnan(got[0]), nan) and same_bits((got[0][~nan], got[1]), (want[0][~nan], want[1]))):
             raise SystemExit(f"the torch form and the kernel differ at a lattice of {side}^3")
         t = alternated({"implicit_torch": lambda: CM._implicit_torch(p, n, shape, origin, voxel, radius, K, MIN_NEIGHBORS, grid=g),
-                        "kernel": lambda: CM._implicit_device(p, n, g, shape, origin, voxel, K, MT._max_d2(radius), MIN_NEIGHBORS)},
+                        "kernel": lambda: CM._implicit_device(p, n, g, shape, origin, voxel, K, MT.squared_cutoff(radius), MIN_NEIGHBORS)},
                        3 if first_s < 5 else 1)
         res["sizes"].append(dict(side=side, equal=True, share_walking=float((want[1] > 0).sum()) / want[1].numel(), **t))
         print(json.dumps(res["sizes"][-1]), flush=True)

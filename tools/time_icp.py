@@ -36,13 +36,12 @@ def step(a):
     for order in ("as_given", "cell_order"):
         src = torch.from_numpy(src_h).to(dev)
         if order == "cell_order":
-            src = src[grid._order(src)].contiguous()
+            src = src[grid.cell_order(src)].contiguous()
         src64 = src.to(torch.float64)
         state = state0.clone()
 
         def run(st, iters, idx=None, d2=None, src=src):
-            _lib.check(lib.ls2fm_icp_run(_lib.ptr(src), a.n, _lib.ptr(grid.sorted), _lib.ptr(grid.cell_start), grid.n, grid._origin,
-                                         grid.cell_size, grid.inv_cell_size, grid._dim, None, float("inf"), 0, iters, MT.ICP_TOL_ROT, tol_trans,
+            _lib.check(lib.ls2fm_icp_run(_lib.ptr(src), a.n, *grid.c_args(), None, float("inf"), 0, iters, MT.ICP_TOL_ROT, tol_trans,
                                          _lib.ptr(st), None, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(ws), _lib.stream_ptr()), "ls2fm_icp_run")
 
         def neighbours(p):
