@@ -1800,6 +1800,77 @@ int ls2fm_mvs_filter(const float* depth, int32_t n_views, int32_t height, int32_
                      int32_t min_consistent, uint8_t* count, float* filtered, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PatchMatch stereo with slanted planes (csrc/mvs_patchmatch.hip behind ls2fm.mvs.plane_score, patch_match_step and patch_match;
+ * additions, the library stays ABI 13): per pixel of a reference a plane hypothesis (d, n) -- d the camera z at the pixel centre,
+ * n its normal in the reference camera's frame, not necessarily of unit length -- scored by the sweep's NCC over a window warped
+ * along that plane, and improved by red-black propagation and random refinement (COLMAP's patch_match_stereo, Gipuma, ACMH).  The
+ * state is depth float [R][H][W], normal float [R][H][W][3], score float [R][H][W].  tests/patchmatch_restate.py repeats both rules
+ * in numpy, ls2fm.mvs.plane_score_torch and patch_match_step_torch as torch ops; the three agree bit for bit.
+ *
+ * Conventions, images, refs, sources, rel = P_rs, intr, half_width w, near, min_var and min_sources are the sweep's, and so is the
+ * arithmetic: every operation is one rounded fp32 operation, none contracted; division is correctly rounded; a square root is
+ * taken in fp64 of the fp32 argument and rounded to fp32; every sum starts at +0 and goes in tap / source order.
+ * The window has a tap step t in {1, 2}: dx and dy take the values -w, -w + t, ... <= w, dy outer and dx inner, n = (2 w / t + 1)^2
+ * taps (integer division).  t = 1 is the sweep's window.
+ *
+ * THE PLANE SCORE of the hypothesis (d, n) at pixel p = (px, py) of reference r:
+ *   0. reference window   step 1 of THE SWEEP RULE over the taps of the step t: ma, va, and the pixel INVALID as there.
+ *   1. lift   xn_p = (((float) px + 0.5) - cx_r) / fx_r, yn_p likewise;  g_p = ((n_x xn_p) + (n_y yn_p)) + n_z.
+ *   2. the hypothesis is INVALID unless d is finite and d > 0, n_x, n_y and n_z are finite, and g_p < 0 (the plane faces the
+ *      camera; false for a NaN).
+ *   3. h = g_p d.
+ *   4. per tap q: xn_q, yn_q and g_q as in 1.; d_q = h / g_q.  The tap is invalid unless g_q < 0 and d_q is finite.
+ *   5. the tap's camera point is (xn_q d_q, yn_q d_q, d_q).
+ *   6. steps 2 (its projection with the view (P_rs, intr_s) and `near`), 3 (sample), 4 (NCC over the n taps) and 5 (aggregate) of
+ *      THE SWEEP RULE follow unchanged: score, NaN when invalid or count < min_sources.
+ * With n = (0, 0, -1) and t = 1, g = -1 and d_q = d exactly: the score at d_k is the sweep's score_k by its bits.
+ *
+ * THE DRAWS.  mix(x), on 32-bit unsigned integers that wrap:  x ^= x >> 16;  x *= LS2FM_MVS_MIX_A;  x ^= x >> 15;
+ * x *= LS2FM_MVS_MIX_B;  x ^= x >> 15.  key = mix(mix(mix(mix(seed + LS2FM_MVS_MIX_SALT) + view) + iteration) + (py W + px)), with
+ * `view` the VIEW index refs[r], so that chunks of references do not show in the bits;  u_j = (float) (mix(key + j) >> 8) 2^-24,
+ * exact, in [0, 1), j = 0 .. 8.  normalise(x, y, z): s = ((x x) + (y y)) + (z z), root = sqrt(s), (x / root, y / root, z / root).
+ *
+ * THE PATCHMATCH STEP (colour, iteration) updates, in place, the pixels with (px + py) & 1 == colour that have a window (step 1 of
+ * THE SWEEP RULE's bounds).  The incumbent is the pixel's stored (d, n, score); its score is not evaluated again.  A candidate
+ * replaces the incumbent iff its PLANE SCORE is not NaN and either the incumbent's score is NaN or the candidate's is strictly
+ * larger.  The candidates, in this order:
+ *   1. the eight neighbours m = p + (0,-1), (-1,0), (1,0), (0,1), (0,-3), (-3,0), (3,0), (0,3) (dx, dy): all at odd Manhattan
+ *      distance, so every pixel read has the other colour and the step is free of races in place and independent of the order the
+ *      lanes run in.  A neighbour outside the image, or whose depth is not finite and positive, is skipped.  With g_m formed from
+ *      m's normal at m's own lift, and g = ((n_mx xn_p) + (n_my yn_p)) + n_mz at p's: the candidate ((g_m d_m) / g, n_m).
+ *   2. perturbed depth   (d (1 + rho_d ((2 u_0) - 1)), n), about the incumbent at that moment (as are 3. and 4.)
+ *   3. perturbed normal  (d, normalise(n_x + rho_n ((2 u_1) - 1), n_y + rho_n ((2 u_2) - 1), n_z))
+ *   4. both              the depth of 2. with u_3, the normal of 3. with u_4 and u_5
+ *   5. a fresh hypothesis   d = 1 / (i0 + u_6 (i1 - i0)), i0 = 1 / d_min[r], i1 = 1 / d_max[r];
+ *      n = normalise(sigma ((2 u_7) - 1), sigma ((2 u_8) - 1), -1)
+ * 2. to 4. are skipped while the incumbent's score is NaN (there is no hypothesis to perturb).  rho_d, rho_n (already scaled by
+ * the caller's schedule rho 2^-iteration, formed in fp64 and rounded once), sigma = max_slope, d_min and d_max float [R] arrive
+ * as fp32.  A reference outside [0, V) is left as it is by the step and gets NaN scores from ls2fm_mvs_plane_score.
+ *
+ * ls2fm_mvs_plane_score writes THE PLANE SCORE of a given state at every pixel (NaN for a pixel without a window);
+ * ls2fm_mvs_patchmatch_step is one half-sweep of one colour.  One workgroup of 256 lanes per (reference, tile of
+ * LS2FM_MVS_PM_TILE_H x LS2FM_MVS_PM_TILE_W pixels), one lane per pixel of a colour.  Both calls: one launch, no workspace, no
+ * atomics, nothing read back, no stream forked; they can be captured, and a rerun of the same state repeats the bits.  n_refs = 0
+ * returns at once.  Refused before anything is enqueued (LS2FM_ERR_INVALID_ARGUMENT): what ls2fm_mvs_sweep refuses, a tap step
+ * outside {1, 2}, a colour outside {0, 1}, a negative iteration, rho_d, rho_n or sigma negative or not finite.
+ */
+#define LS2FM_MVS_PM_TILE_H 16
+#define LS2FM_MVS_PM_TILE_W 32
+#define LS2FM_MVS_PM_DRAWS 9
+#define LS2FM_MVS_MIX_A 0x21F0AAADu
+#define LS2FM_MVS_MIX_B 0x735A2D97u
+#define LS2FM_MVS_MIX_SALT 0x9E3779B9u
+int ls2fm_mvs_plane_score(const float* images, int32_t n_views, int32_t height, int32_t width, const int32_t* refs, int32_t n_refs,
+                          const int32_t* sources, int32_t n_sources, const float* rel, const float* intr, int32_t half_width,
+                          int32_t tap_step, float near, float min_var, int32_t min_sources, const float* depth, const float* normal,
+                          float* score, void* stream);
+int ls2fm_mvs_patchmatch_step(const float* images, int32_t n_views, int32_t height, int32_t width, const int32_t* refs,
+                              int32_t n_refs, const int32_t* sources, int32_t n_sources, const float* rel, const float* intr,
+                              int32_t half_width, int32_t tap_step, float near, float min_var, int32_t min_sources, int32_t colour,
+                              int32_t iteration, uint32_t seed, float rho_d, float rho_n, float sigma, const float* d_min,
+                              const float* d_max, float* depth, float* normal, float* score, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -5,21 +5,29 @@
                   cross-correlation of a (2 w + 1)^2 window against S source views over D fronto-parallel planes
   filter_depths   the geometric-consistency filter of a set of depth maps (ls2fm_mvs_filter): a pixel stays when enough source
                   views hold a depth that projects back onto it
-  dense_reconstruct   plane_sweep -> filter_depths -> fusion.volume_for -> fusion.integrate -> fusion.extract: the classical dense
-                  baseline row of the neural-surface tables (COLMAP's patch_match_stereo and stereo_fusion), in its simplest
-                  form; its mesh goes into ls2fm.mesh_colors.photo_colors and ls2fm.metrics.evaluate_mesh as it stands
-  plane_sweep_torch, filter_depths_torch   the same rules as separate torch ops, on CPU tensors as well: the checks of the kernels
-                  and the timing baseline (tools/time_mvs.py); nothing in the library falls back to them
+  plane_score, patch_match_step   PatchMatch stereo with slanted planes (ls2fm_mvs_plane_score, ls2fm_mvs_patchmatch_step,
+                  csrc/mvs_patchmatch.hip): the NCC of a per-pixel plane (depth, normal), and one red-black half-sweep of
+                  propagation and random refinement, in place on the state (depth, normal, score)
+  patch_match     a coarse plane_sweep (or a caller's state) refined by `iterations` red-black sweeps -> depth, normal, score
+  normals_to_world   camera-frame normal maps into the poses' world frame, elementwise
+  dense_reconstruct   plane_sweep or patch_match -> filter_depths -> fusion.volume_for -> fusion.integrate -> fusion.extract: the
+                  classical dense baseline row of the neural-surface tables (COLMAP's patch_match_stereo and stereo_fusion); its
+                  mesh goes into ls2fm.mesh_colors.photo_colors and ls2fm.metrics.evaluate_mesh as it stands
+  plane_sweep_torch, filter_depths_torch, plane_score_torch, patch_match_step_torch   the same rules as separate torch ops, on
+                  CPU tensors as well: the checks of the kernels and the timing baselines (tools/time_mvs.py,
+                  tools/time_patchmatch.py); nothing in the library falls back to them
 
-THE SWEEP RULE and THE CONSISTENCY RULE are stated in include/ls2fm.h and restated in numpy in tests/mvs_restate.py; the kernels,
-the torch forms and the restatement agree bit for bit.  Conventions are the rasteriser's (ls2fm.raster.rasterize): poses world ->
+THE SWEEP RULE, THE CONSISTENCY RULE, THE PLANE SCORE and THE PATCHMATCH STEP are stated in include/ls2fm.h and restated in numpy
+in tests/mvs_restate.py and tests/patchmatch_restate.py; the kernels, the torch forms and the restatements agree bit for bit.  Conventions are the rasteriser's (ls2fm.raster.rasterize): poses world ->
 camera [V, 3, 4], intr [3, 3] or [V, 3, 3], pixel (px, py) has its centre at px + 0.5, depth is camera z.  All views of a call
 share one image size.  Each kernel call is one launch without host read or atomics: it can be captured, a rerun repeats its bits,
 and the chunking of the reference views does not show in them.
 
-Deviations from COLMAP's dense stage, on purpose: the planes are fronto-parallel to the reference (no per-pixel normals); the
-score of a plane is the mean NCC over the valid sources, not the best K of them; there is no PatchMatch propagation -- every pixel
-tries every plane; one image size per call; grey images only; no gradients.
+Deviations of plane_sweep from COLMAP's dense stage, on purpose: the planes are fronto-parallel to the reference (no per-pixel
+normals) and every pixel tries every plane (no propagation) -- patch_match lifts both.  Deviations of both: the score of a plane
+is the mean NCC over the valid sources, not the best K of them or a per-pixel view selection; the window's taps weigh the same (no
+bilateral weights); the cost holds no geometric-consistency term (filter_depths runs afterwards); one scale and one image size per
+call; grey images only; no gradients.
 
 There is no CPU path for the kernels: CPU tensors, a missing device or a missing library raise, as in ls2fm.fusion.
 """
@@ -38,6 +46,10 @@ TILE = 16                   # LS2FM_MVS_TILE
 MAX_HALF_WIDTH = 5          # LS2FM_MVS_MAX_HALF_WIDTH
 MAX_SOURCES = 64            # LS2FM_MVS_MAX_SOURCES
 MAX_PLANES = 65536          # LS2FM_MVS_MAX_PLANES
+PM_TILE_H, PM_TILE_W = 16, 32   # LS2FM_MVS_PM_TILE_H, LS2FM_MVS_PM_TILE_W
+PM_DRAWS = 9                # LS2FM_MVS_PM_DRAWS
+MIX_A, MIX_B, MIX_SALT = 0x21F0AAAD, 0x735A2D97, 0x9E3779B9    # LS2FM_MVS_MIX_A, LS2FM_MVS_MIX_B, LS2FM_MVS_MIX_SALT
+NEIGHBOURS = ((0, -1), (-1, 0), (1, 0), (0, 1), (0, -3), (-3, 0), (3, 0), (0, 3))     # (dx, dy), THE PATCHMATCH STEP's order
 _device = functools.partial(_lib.require_device_tensors, "ls2fm.mvs", phrase=": multi-view stereo runs on MI355X only")
 
 
@@ -58,6 +70,17 @@ class MvsOptions:
     rel_depth: float = 0.01
     min_consistent: int = 2
     max_workspace_bytes: int = 2 ** 28
+    iterations: int = 5             # patch_match (dense_reconstruct with stereo="patchmatch")
+    seed: int = 0
+    depth_perturb: float = 0.02     # relative; halves with every iteration
+    normal_perturb: float = 0.5
+    max_slope: float = 1.0
+    tap_step: int = 1
+    patchmatch_planes: int = 32     # the planes of the initial sweep when dense_reconstruct forms them
+
+    def patchmatch(self):
+        return dict(self.sweep(), iterations=self.iterations, seed=self.seed, depth_perturb=self.depth_perturb,
+                    normal_perturb=self.normal_perturb, max_slope=self.max_slope, tap_step=self.tap_step)
 
     def sweep(self):
         return dict(half_width=self.half_width, near=self.near, min_var=self.min_var, min_sources=self.min_sources,
@@ -284,6 +307,185 @@ def filter_depths(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_dep
     return out, count
 
 
+# -------------------------------------------------------------------------------------------------------------------- PatchMatch
+def _check_tap_step(tap_step, who):
+    tap_step = int(tap_step)
+    if tap_step not in (1, 2):
+        raise ValueError(f"{who}: tap_step {tap_step} must be 1 or 2")
+    return tap_step
+
+
+def _check_step(colour, iteration, depth_perturb, normal_perturb, max_slope, who):
+    """-> colour, iteration, rho_d, rho_n, sigma: the perturbations on the schedule rho 2^-iteration, formed in fp64 (the float
+    argument of the call, or the float32 tensor of the torch form, rounds them once)"""
+    colour, iteration = int(colour), int(iteration)
+    if colour not in (0, 1) or iteration < 0:
+        raise ValueError(f"{who}: colour {colour} must be 0 or 1, iteration {iteration} not negative")
+    rho = [float(depth_perturb), float(normal_perturb), float(max_slope)]
+    if not all(0.0 <= v < math.inf for v in rho):
+        raise ValueError(f"{who}: depth_perturb {rho[0]}, normal_perturb {rho[1]} and max_slope {rho[2]} must be finite and not negative")
+    return colour, iteration, rho[0] * 2.0 ** -iteration, rho[1] * 2.0 ** -iteration, rho[2]
+
+
+def _state(depth, normal, score, R, H, W, dev, who, in_place):
+    """the state's arrays as float32 [R, H, W], [R, H, W, 3], [R, H, W] on dev; what is updated in place must be so already"""
+    out = []
+    for name, t, shape in (("depth", depth, (R, H, W)), ("normal", normal, (R, H, W, 3)), ("score", score, (R, H, W))):
+        if t is None:
+            out.append(None)
+            continue
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{who}: {name} must be {list(shape)}, got {tuple(t.shape)}")
+        if in_place and not (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"{who}: {name} is updated in place: it must be a contiguous float32 tensor on {dev}")
+        out.append(t if in_place else _lib.cf(t.detach().to(dev)))
+    return out
+
+
+class _Inputs:
+    """what plane_score and patch_match_step share: the checked inputs of one set of references"""
+
+    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who):
+        images = torch.as_tensor(images)
+        _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
+        poses, self.k4 = _posed.views(pose, intr, who)
+        self.V, self.dev = int(poses.shape[0]), poses.device
+        self.img = _grey(images, self.V, who)
+        self.refs, self.sources, _ = _index_arrays(refs, sources, None, self.V, self.dev, who)
+        self.R, self.S, self.H, self.W = int(self.refs.shape[0]), int(self.sources.shape[1]), int(self.img.shape[1]), int(self.img.shape[2])
+        self.w, self.min_var, self.min_sources = _check_sweep(half_width, min_var, min_sources, self.S, 1, who)
+        self.t = _check_tap_step(tap_step, who)
+        self.near = _posed.near_plane(near, who)
+        if self.img.device != self.dev:
+            raise ValueError(f"{who}: the poses on {self.dev}, the images on {self.img.device}")
+        self.rel = relative_poses(poses, self.refs, self.sources)
+
+    def head(self, s, e):
+        """the arguments both entry points begin with, for the references s .. e"""
+        return (ptr(self.img), self.V, self.H, self.W, ptr(self.refs[s:e]), e - s, ptr(self.sources[s:e]), self.S, ptr(self.rel[s:e]),
+                ptr(self.k4), self.w, self.t, self.near, self.min_var, self.min_sources)
+
+    def score(self, depth, normal, score, budget):
+        lib = _lib.load()
+        with torch.cuda.device(self.dev):
+            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
+                check(lib.ls2fm_mvs_plane_score(*self.head(s, e), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]), stream_ptr()),
+                      "ls2fm_mvs_plane_score")
+
+    def step(self, depth, normal, score, colour, iteration, seed, rho_d, rho_n, sigma, d_min, d_max, budget):
+        lib = _lib.load()
+        with torch.cuda.device(self.dev):
+            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
+                check(lib.ls2fm_mvs_patchmatch_step(*self.head(s, e), colour, iteration, int(seed) & 0xFFFFFFFF, rho_d, rho_n, sigma,
+                                                    ptr(d_min[s:e]), ptr(d_max[s:e]), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]),
+                                                    stream_ptr()), "ls2fm_mvs_patchmatch_step")
+
+
+def _range(d_min, d_max, R, dev, who):
+    out = []
+    for name, t in (("d_min", d_min), ("d_max", d_max)):
+        t = torch.as_tensor(t, device=dev).detach().float().reshape(-1)
+        if t.shape[0] == 1:
+            t = t.expand(R)
+        if t.shape[0] != R:
+            raise ValueError(f"{who}: {name} must be a float or [{R}], got {tuple(t.shape)}")
+        out.append(t.contiguous())
+    return out
+
+
+@torch.no_grad()
+def plane_score(images, pose, intr, sources, depth, normal, refs=None, half_width=3, tap_step=1, near=1e-3, min_var=1e-6, min_sources=1,
+                max_workspace_bytes=2 ** 28):
+    """THE PLANE SCORE of include/ls2fm.h at every pixel of a state -> score float32 [R, H, W], NaN where the pixel, the
+    hypothesis or too many sources are invalid.
+      depth      float [R, H, W]: camera z at the pixel centre
+      normal     float [R, H, W, 3]: the plane's normal in the reference camera's frame (any length); it must face the camera
+      tap_step   1, or 2 for every other tap of the window in both axes
+    The other arguments are plane_sweep's.  One launch per chunk of references (20 bytes per pixel within max_workspace_bytes); no
+    host read."""
+    who = "ls2fm.mvs.plane_score"
+    a = _Inputs(images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who)
+    depth, normal, _ = _state(depth, normal, None, a.R, a.H, a.W, a.dev, who, False)
+    score = torch.empty((a.R, a.H, a.W), dtype=torch.float32, device=a.dev)
+    a.score(depth, normal, score, max_workspace_bytes)
+    return score
+
+
+@torch.no_grad()
+def patch_match_step(images, pose, intr, sources, depth, normal, score, colour, iteration, d_min, d_max, refs=None, seed=0,
+                     depth_perturb=0.02, normal_perturb=0.5, max_slope=1.0, half_width=3, tap_step=1, near=1e-3, min_var=1e-6,
+                     min_sources=1, max_workspace_bytes=2 ** 28):
+    """THE PATCHMATCH STEP of include/ls2fm.h: one half-sweep over the pixels with (px + py) & 1 == colour, in place on the state
+    depth [R, H, W], normal [R, H, W, 3], score [R, H, W] (contiguous float32 device tensors; score as plane_score leaves it)
+    -> the same three tensors.  Each such pixel tries the planes of eight neighbours of the other colour, a perturbed depth, a
+    perturbed normal, both, and a fresh hypothesis between d_min and d_max (floats or [R]) with a slope up to max_slope, and keeps
+    what scores strictly higher.  depth_perturb and normal_perturb are the values of iteration 0: the step halves them `iteration`
+    times.  The draws depend on (seed, view, iteration, pixel) alone.  One launch per chunk of references; no host read."""
+    who = "ls2fm.mvs.patch_match_step"
+    a = _Inputs(images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who)
+    colour, iteration, rho_d, rho_n, sigma = _check_step(colour, iteration, depth_perturb, normal_perturb, max_slope, who)
+    depth, normal, score = _state(depth, normal, score, a.R, a.H, a.W, a.dev, who, True)
+    d_min, d_max = _range(d_min, d_max, a.R, a.dev, who)
+    a.step(depth, normal, score, colour, iteration, seed, rho_d, rho_n, sigma, d_min, d_max, max_workspace_bytes)
+    return depth, normal, score
+
+
+@torch.no_grad()
+def patch_match(images, pose, intr, sources, depths, refs=None, iterations=5, init=None, seed=0, depth_perturb=0.02, normal_perturb=0.5,
+                max_slope=1.0, tap_step=1, half_width=3, near=1e-3, min_var=1e-6, min_sources=1, max_workspace_bytes=2 ** 28):
+    """PatchMatch stereo -> (depth float32 [R, H, W], normal float32 [R, H, W, 3] in each reference camera's frame, score float32
+    [R, H, W]); depth and normal are NaN where the final score is.
+      depths     float [R, D] or [D]: the planes of the initial sweep (a coarse D, 16 to 32, is the intended use); the ends of each
+                 row are the range d_min, d_max of the fresh hypotheses
+      init       None: plane_sweep over `depths`, its depth with the normal (0, 0, -1); or a caller's (depth, normal)
+      iterations each runs colour 0, then colour 1, with depth_perturb and normal_perturb halved from one to the next
+    plane_score turns the initial state into scores; then 2 `iterations` launches of patch_match_step per chunk of references, chunked
+    as plane_sweep chunks them.  No host read; a rerun repeats the bits."""
+    who = "ls2fm.mvs.patch_match"
+    a = _Inputs(images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"{who}: iterations {iterations} must not be negative")
+    _check_step(0, 0, depth_perturb, normal_perturb, max_slope, who)
+    _, _, depths = _index_arrays(a.refs, a.sources, depths, a.V, a.dev, who)
+    d_min, d_max = depths[:, 0].contiguous(), depths[:, -1].contiguous()
+    if init is None:
+        depth = plane_sweep(a.img, pose, intr, a.sources, depths, refs=a.refs, half_width=half_width, near=near, min_var=min_var,
+                            min_sources=min_sources, max_workspace_bytes=max_workspace_bytes)[0]
+        normal = torch.zeros((a.R, a.H, a.W, 3), dtype=torch.float32, device=a.dev)
+        normal[..., 2] = -1.0
+    else:
+        depth, normal, _ = _state(init[0], init[1], None, a.R, a.H, a.W, a.dev, who, False)
+        depth, normal = depth.clone(), normal.clone()
+    score = torch.empty((a.R, a.H, a.W), dtype=torch.float32, device=a.dev)
+    a.score(depth, normal, score, max_workspace_bytes)
+    for it in range(iterations):
+        _, _, rho_d, rho_n, sigma = _check_step(0, it, depth_perturb, normal_perturb, max_slope, who)
+        for colour in (0, 1):
+            a.step(depth, normal, score, colour, it, seed, rho_d, rho_n, sigma, d_min, d_max, max_workspace_bytes)
+    dead = torch.isnan(score)
+    depth.masked_fill_(dead, math.nan)
+    normal.masked_fill_(dead[..., None], math.nan)
+    return depth, normal, score
+
+
+def normals_to_world(normal, pose, refs=None):
+    """Camera-frame normal maps [R, H, W, 3] of the views refs (default: every view, R = V) -> the same in the world frame of
+    pose [V, 3, 4]: n_w = R^T n_c as elementwise torch ops, (R_0j n_0 + R_1j n_1) + R_2j n_2 -- no GEMM, so the device's matrix
+    product does not show in the bits.  Any device."""
+    normal = torch.as_tensor(normal).detach().float()
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(normal.device)
+    if normal.dim() != 4 or normal.shape[-1] != 3:
+        raise ValueError(f"ls2fm.mvs.normals_to_world: normal must be [R, H, W, 3], got {tuple(normal.shape)}")
+    refs = torch.arange(P.shape[0], device=normal.device) if refs is None else torch.as_tensor(refs, device=normal.device).long().reshape(-1)
+    if refs.shape[0] != normal.shape[0]:
+        raise ValueError(f"ls2fm.mvs.normals_to_world: {normal.shape[0]} normal maps for {refs.shape[0]} references")
+    Rm = P[refs.clamp(0, P.shape[0] - 1), :, :3][:, None, None]                    # [R, 1, 1, 3, 3]
+    n = normal[..., :, None]                                                       # [R, H, W, 3, 1]
+    return (Rm[..., 0, :] * n[..., 0, :] + Rm[..., 1, :] * n[..., 1, :]) + Rm[..., 2, :] * n[..., 2, :]
+
+
 # -------------------------------------------------------------------------------------------------------------- the torch forms
 def _torch_views(pose, intr, dev):
     P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(dev)
@@ -457,19 +659,215 @@ def filter_depths_torch(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, r
     return out.reshape(V, H, W), count.to(torch.uint8).reshape(V, H, W)
 
 
+def _mix(x):
+    """mix of THE DRAWS on int64 tensors that hold 32-bit values: both constants are below 2^31, so no product leaves 63 bits"""
+    m = 0xFFFFFFFF
+    x = x & m
+    x = x ^ (x >> 16)
+    x = (x * MIX_A) & m
+    x = x ^ (x >> 15)
+    x = (x * MIX_B) & m
+    return x ^ (x >> 15)
+
+
+def _draws(seed, view, iteration, pixel):
+    """u_0 .. u_8 float32 of the pixels `pixel` (int64, py W + px) of view `view`"""
+    h = _mix(torch.full_like(pixel[:1], (int(seed) + MIX_SALT) & 0xFFFFFFFF))
+    h = _mix(_mix(h + int(view)) + int(iteration))
+    key = _mix(h + pixel)
+    return [(_mix(key + j) >> 8).float() * 2.0 ** -24 for j in range(PM_DRAWS)]
+
+
+def _normalise(x, y, z):
+    root = _sqrt_rn((x * x + y * y) + z * z)
+    return torch.stack([x / root, y / root, z / root], dim=1)
+
+
+class _TorchScene:
+    """the inputs of plane_score_torch and patch_match_step_torch, and per reference what no hypothesis changes"""
+
+    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who):
+        img = torch.as_tensor(images).detach().float()
+        self.dev = dev = img.device
+        self.P, self.K = _torch_views(pose, intr, dev)
+        self.V = int(self.P.shape[0])
+        self.img = _grey(img, self.V, who)
+        refs, sources, _ = _index_arrays(refs, sources, None, self.V, dev, who)
+        self.R, self.S, self.H, self.W = int(refs.shape[0]), int(sources.shape[1]), int(self.img.shape[1]), int(self.img.shape[2])
+        self.w, min_var, self.min_sources = _check_sweep(half_width, min_var, min_sources, self.S, 1, who)
+        self.t = _check_tap_step(tap_step, who)
+        self.rel = relative_poses(self.P, refs, sources)
+        self.refs, self.sources = refs.tolist(), sources.tolist()
+        self.scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
+        side = range(0, 2 * self.w + 1, self.t)
+        self.offsets = [(j - self.w, i - self.w) for i in side for j in side]
+        self.picked = [i * (2 * self.w + 1) + j for i in side for j in side]
+        self.n, self.near, self.min_var = self.scalar(len(self.offsets)), self.scalar(_posed.near_plane(near, who)), self.scalar(min_var)
+        self.cache = {}
+
+    def reference(self, r):
+        rv = self.refs[r]
+        if not 0 <= rv < self.V:
+            return None
+        if r not in self.cache:
+            nan = torch.full((self.H, self.W), math.nan, dtype=torch.float32, device=self.dev)
+            img = torch.where(torch.isfinite(self.img[rv]), self.img[rv], nan)
+            every = _taps(img, self.w)
+            a = [every[i] for i in self.picked]
+            sa = _tap_sum(a)
+            ma = sa / self.n
+            va = torch.zeros_like(sa)
+            for t in a:
+                va = va + (t - ma) * (t - ma)
+            xn, yn = _lift(self.K[rv], self.H, self.W, self.dev)
+            self.cache[r] = dict(rv=rv, img=img, ma=ma, va=va, pixel_ok=~torch.isnan(sa) & ~(va < self.min_var), xn=xn[0], yn=yn[:, 0])
+        return self.cache[r]
+
+    def sample(self, r, s, sv, X, Y, Z):
+        """steps 2 and 3 of THE SWEEP RULE at the camera points (X, Y, Z) of reference r: NaN where not valid"""
+        H, W = self.H, self.W
+        _, u, v, usable, _, _, _ = _posed.project_torch(self.rel[r, s], self.K[sv], X, Y, Z, self.near, H, W)
+        fx, fy = u - 0.5, v - 0.5
+        x0, y0 = fx.floor(), fy.floor()
+        tx, ty = fx - x0, fy - y0
+        ok = usable & (x0 >= 0) & (x0 <= W - 2) & (y0 >= 0) & (y0 <= H - 2)
+        zero = torch.zeros_like(x0)
+        at = torch.where(ok, y0, zero).long() * W + torch.where(ok, x0, zero).long()
+        src, last = self.img[sv].reshape(-1), H * W - 1
+        b00, b10 = src[at], src[(at + 1).clamp(max=last)]
+        b01, b11 = src[(at + W).clamp(max=last)], src[(at + W + 1).clamp(max=last)]
+        r0 = b00 + tx * (b10 - b00)
+        r1 = b01 + tx * (b11 - b01)
+        b = r0 + ty * (r1 - r0)
+        return torch.where(ok & torch.isfinite(b), b, torch.full_like(b, math.nan))
+
+    def score(self, r, py, px, d, n):
+        """THE PLANE SCORE of (d [N], n [N, 3]) at the pixels (px, py) (int64 [N]) of reference r -> float32 [N]"""
+        nan = torch.full(py.shape, math.nan, dtype=torch.float32, device=self.dev)
+        ref = self.reference(r)
+        if ref is None:
+            return nan
+        nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+        gp = (nx * ref["xn"][px] + ny * ref["yn"][py]) + nz
+        ok = ref["pixel_ok"][py, px] & torch.isfinite(d) & (d > 0) & torch.isfinite(nx) & torch.isfinite(ny) & torch.isfinite(nz) & (gp < 0)
+        h = gp * d
+        a, pts = [], []
+        for dx, dy in self.offsets:
+            qx, qy = (px + dx).clamp(0, self.W - 1), (py + dy).clamp(0, self.H - 1)
+            xq, yq = ref["xn"][qx], ref["yn"][qy]
+            gq = (nx * xq + ny * yq) + nz
+            dq = h / gq
+            a.append(ref["img"][qy, qx])
+            pts.append((xq * dq, yq * dq, dq, (gq < 0) & torch.isfinite(dq)))
+        ma, va = ref["ma"][py, px], ref["va"][py, px]
+        total, count = torch.zeros_like(nan), torch.zeros(py.shape, dtype=torch.int64, device=self.dev)
+        for s, sv in enumerate(self.sources[r]):
+            if not 0 <= sv < self.V:
+                continue
+            b = [torch.where(tap_ok, self.sample(r, s, sv, X, Y, Z), nan) for X, Y, Z, tap_ok in pts]
+            sb = _tap_sum(b)
+            mb = sb / self.n
+            vb, cov = torch.zeros_like(sb), torch.zeros_like(sb)
+            for ai, bi in zip(a, b):
+                db = bi - mb
+                vb = vb + db * db
+                cov = cov + (ai - ma) * db
+            valid = ok & ~torch.isnan(sb) & ~(vb < self.min_var)
+            ncc = cov / _sqrt_rn(va * vb)
+            total = torch.where(valid, total + ncc, total)
+            count = count + valid
+        return torch.where(ok & (count >= self.min_sources), total / count.float(), nan)
+
+
+@torch.no_grad()
+def plane_score_torch(images, pose, intr, sources, depth, normal, refs=None, half_width=3, tap_step=1, near=1e-3, min_var=1e-6,
+                      min_sources=1):
+    """THE PLANE SCORE as plain torch ops on the images' device (a CPU works), vectorised over the pixels of one reference, the
+    references, sources and taps in loops: the same operations in the same order, each a separate op.  Reads `refs` and `sources`
+    on the host.  -> score as plane_score."""
+    who = "ls2fm.mvs.plane_score_torch"
+    sc = _TorchScene(images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who)
+    depth, normal, _ = _state(depth, normal, None, sc.R, sc.H, sc.W, sc.dev, who, False)
+    yy, xx = torch.meshgrid(torch.arange(sc.H, device=sc.dev), torch.arange(sc.W, device=sc.dev), indexing="ij")
+    py, px = yy.reshape(-1), xx.reshape(-1)
+    return torch.stack([sc.score(r, py, px, depth[r].reshape(-1), normal[r].reshape(-1, 3)).reshape(sc.H, sc.W) for r in range(sc.R)])
+
+
+@torch.no_grad()
+def patch_match_step_torch(images, pose, intr, sources, depth, normal, score, colour, iteration, d_min, d_max, refs=None, seed=0,
+                           depth_perturb=0.02, normal_perturb=0.5, max_slope=1.0, half_width=3, tap_step=1, near=1e-3, min_var=1e-6,
+                           min_sources=1):
+    """THE PATCHMATCH STEP as plain torch ops on the images' device (a CPU works), the hash in int64 ops masked to 32 bits; in place
+    on contiguous float32 tensors like patch_match_step.  Every candidate is scored at every pixel of the colour and masked.  Reads
+    `refs` and `sources` on the host.  -> (depth, normal, score)."""
+    who = "ls2fm.mvs.patch_match_step_torch"
+    sc = _TorchScene(images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who)
+    colour, iteration, rho_d, rho_n, sigma = _check_step(colour, iteration, depth_perturb, normal_perturb, max_slope, who)
+    rho_d, rho_n, sigma = sc.scalar(rho_d), sc.scalar(rho_n), sc.scalar(sigma)
+    depth, normal, score = _state(depth, normal, score, sc.R, sc.H, sc.W, sc.dev, who, True)
+    d_min, d_max = _range(d_min, d_max, sc.R, sc.dev, who)
+    H, W, w = sc.H, sc.W, sc.w
+    yy, xx = torch.meshgrid(torch.arange(w, H - w, device=sc.dev), torch.arange(w, W - w, device=sc.dev), indexing="ij")
+    yy, xx = yy.reshape(-1), xx.reshape(-1)
+    mine = ((xx + yy) & 1) == colour
+    py, px = yy[mine], xx[mine]
+    if py.numel() == 0:
+        return depth, normal, score
+    one = sc.scalar(1.0)
+    for r in range(sc.R):
+        ref = sc.reference(r)
+        if ref is None:
+            continue
+        best = [depth[r][py, px], normal[r][py, px], score[r][py, px]]
+        u = _draws(seed, ref["rv"], iteration, py * W + px)
+        xp, yp = ref["xn"][px], ref["yn"][py]
+
+        def consider(cd, cn, active):
+            s = sc.score(r, py, px, cd, cn)
+            better = active & ~torch.isnan(s) & (torch.isnan(best[2]) | (s > best[2]))
+            best[0] = torch.where(better, cd, best[0])
+            best[1] = torch.where(better[:, None], cn, best[1])
+            best[2] = torch.where(better, s, best[2])
+
+        for dx, dy in NEIGHBOURS:
+            mx, my = px + dx, py + dy
+            inside = (mx >= 0) & (mx < W) & (my >= 0) & (my < H)
+            mx, my = mx.clamp(0, W - 1), my.clamp(0, H - 1)
+            dm, nm = depth[r][my, mx], normal[r][my, mx]
+            gm = (nm[:, 0] * ref["xn"][mx] + nm[:, 1] * ref["yn"][my]) + nm[:, 2]
+            g = (nm[:, 0] * xp + nm[:, 1] * yp) + nm[:, 2]
+            consider((gm * dm) / g, nm, inside & torch.isfinite(dm) & (dm > 0))
+        have = ~torch.isnan(best[2])
+        deeper = lambda j: best[0] * (one + rho_d * (2.0 * u[j] - 1.0))
+        turned = lambda j: _normalise(best[1][:, 0] + rho_n * (2.0 * u[j] - 1.0), best[1][:, 1] + rho_n * (2.0 * u[j + 1] - 1.0), best[1][:, 2])
+        consider(deeper(0), best[1], have)
+        consider(best[0], turned(1), have)
+        consider(deeper(3), turned(4), have)
+        lo, hi = one / d_min[r], one / d_max[r]
+        fresh = _normalise(sigma * (2.0 * u[7] - 1.0), sigma * (2.0 * u[8] - 1.0), torch.full_like(u[7], -1.0))
+        consider(one / (lo + u[6] * (hi - lo)), fresh, torch.ones_like(have))
+        depth[r][py, px], normal[r][py, px], score[r][py, px] = best
+    return depth, normal, score
+
+
 # ------------------------------------------------------------------------------------------------------------------ end to end
 @torch.no_grad()
 def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=None, points=None, options=None, trunc=None,
-                      min_weight=1.0, return_depth=False):
-    """Photographs to a surface: plane_sweep over every view -> filter_depths -> ls2fm.fusion.volume_for(bounds, voxel, trunc) ->
-    fusion.integrate -> fusion.extract -> ls2fm.mesh.Mesh, in the poses' world frame.
+                      min_weight=1.0, return_depth=False, stereo="sweep"):
+    """Photographs to a surface: plane_sweep (stereo="sweep", the default) or patch_match (stereo="patchmatch") over every view ->
+    filter_depths -> ls2fm.fusion.volume_for(bounds, voxel, trunc) -> fusion.integrate -> fusion.extract -> ls2fm.mesh.Mesh, in the
+    poses' world frame.
       images     [V, H, W, 3] colour (to_grey) or grey [V, H, W]
       sources    int [V, S]; default select_sources(pose, options.n_sources, options.min_angle, options.max_angle)
       depths     float [V, D]; default depth_planes over depth_range_from_points of `points` (an [N, 3] cloud or an
-                 ls2fm.mapper.Reconstruction), or of the eight corners of `bounds` when there are none
+                 ls2fm.mapper.Reconstruction), or of the eight corners of `bounds` when there are none; options.n_planes of them
+                 for the sweep, options.patchmatch_planes for patch_match's initial sweep
       options    MvsOptions
-    Host reads: those of fusion.extract.  With return_depth: (Mesh, filtered depth [V, H, W], count uint8 [V, H, W])."""
+    Host reads: those of fusion.extract.  With return_depth: (Mesh, filtered depth [V, H, W], count uint8 [V, H, W]), and with
+    stereo="patchmatch" a fourth entry, the world normals [V, H, W, 3] (normals_to_world), NaN where the filter dropped the pixel."""
     opt = MvsOptions() if options is None else options
+    if stereo not in ("sweep", "patchmatch"):
+        raise ValueError(f"ls2fm.mvs.dense_reconstruct: stereo {stereo!r} must be 'sweep' or 'patchmatch'")
     images = torch.as_tensor(images)
     _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
     grey = to_grey(images)
@@ -480,10 +878,18 @@ def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=No
             lo, hi = ([float(v) for v in b] for b in bounds)
             points = torch.tensor([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])], dtype=torch.float64)
         near, far = depth_range_from_points(points, pose, opt.margin)
-        depths = depth_planes(near, far, opt.n_planes, opt.inverse_depth)
-    depth, _, _ = plane_sweep(grey, pose, intr, sources, depths, **opt.sweep())
+        depths = depth_planes(near, far, opt.n_planes if stereo == "sweep" else opt.patchmatch_planes, opt.inverse_depth)
+    if stereo == "sweep":
+        depth, _, _ = plane_sweep(grey, pose, intr, sources, depths, **opt.sweep())
+    else:
+        depth, normal, _ = patch_match(grey, pose, intr, sources, depths, **opt.patchmatch())
     filtered, count = filter_depths(depth, pose, intr, sources, **opt.filter())
     volume = fusion.volume_for(bounds, voxel, trunc, grey.device)
     fusion.integrate(volume, filtered, pose, intr, near=opt.near)
     out = fusion.extract(volume, min_weight)
-    return (out, filtered, count) if return_depth else out
+    if not return_depth:
+        return out
+    if stereo == "sweep":
+        return out, filtered, count
+    world = normals_to_world(normal, pose)
+    return out, filtered, count, world.masked_fill(torch.isnan(filtered)[..., None], math.nan)
