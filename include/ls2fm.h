@@ -1376,6 +1376,78 @@ int ls2fm_cloud_implicit_plan(const float* points, const float* normals, int64_t
                               int32_t brick, int32_t empty_test, float* value, float* support, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Screened Poisson reconstruction of an oriented point cloud on the dense lattice (csrc/poisson.hip behind
+ * ls2fm.cloud_mesh.poisson_from_cloud; additions, the library stays ABI 13): a global solve, so holes close by one stated rule
+ * where the implicit rule above leaves them open.  The reference ships none.  tests/poisson_restate.py repeats the rule in numpy.
+ *
+ * THE POISSON RULE  The unknown chi lives on the lattice n0 x n1 x n2 (every side >= 2, axis 2 fastest), lattice point i at
+ *   fl32(fl32((float) i * voxel) + origin).  All lattice arithmetic is fp32; every operation below is ONE rounded operation in
+ *   the stated order, none contracted, division correctly rounded.  fl() is that rounding.
+ *   1 splat   For point P with normal N (fp32), per axis a: u = fl(fl(P_a - origin_a) / voxel), i_a = floor(u), f_a = u - i_a
+ *     (exact).  The point takes part when 0 <= u < n_a - 1 on every axis and P and N are finite; otherwise it adds nothing.  The
+ *     weight at corner (dx, dy, dz) of its cell is w = fl(fl(wx wy) wz), w_a = f_a at the upper corner and fl(1 - f_a) at the
+ *     lower.  The corner receives w into the density W and w N_a into V_a, each term as rint((double) w (double) N_a 2^32), an
+ *     int64 (the product is exact in fp64; the conversion goes through the double's mantissa and is rint while the term stays
+ *     below 2^51, i. e. |N_a| < 2^19), added with 64-bit INTEGER atomics into four accumulators per lattice point: no order
+ *     shows.  Then V_a = (float) ((double) sum 2^-32), W likewise.  Exactness needs, per lattice point, sum |w N_a| < 2^30: with
+ *     unit normals (ls2fm.cloud_mesh normalises them) that is a bound of 2^30 on the points around one lattice point.
+ *   2 right-hand side   g(i, i + e_a) = fl(0.5 fl(V_a[i] + V_a[i + e_a])) on every lattice edge;  t_a = fl(g(i - e_a, i) -
+ *     g(i, i + e_a)), a missing edge counted as 0;  b_i = fl(fl(t_0 + t_1) + t_2).  These are the normal equations of
+ *     sum over edges (chi_j - chi_i - g_ij)^2 + screen sum_i W_i chi_i^2: a graph Laplacian with natural boundaries plus a
+ *     lumped screening term.  Summed, they give sum W_i chi_i = 0: the surface is the ZERO level, no isovalue is reduced;
+ *     outward normals make chi positive outside, the sign of the FUSION RULE.
+ *   3 operator at level l   s = 4^-l (exact), a = screen (fp32).  N_i is the sum of the existing neighbours in the order -0, +0,
+ *     -1, +1, -2, +2, starting from the first that exists; deg_i their count;  D_i = fl(fl(s deg_i) + fl(a W_i)).
+ *     smoother: red-black Gauss-Seidel in place, colour (i0 + i1 + i2) & 1 == 0 first:  chi_i <- fl(fl(b_i + fl(s N_i)) / D_i)
+ *     residual: r_i = fl(b_i - fl(fl(s fl(fl(deg_i chi_i) - N_i)) + fl(fl(a W_i) chi_i)))
+ *   4 levels   a coarse side is nc = (n + 1) / 2, coarse I on fine 2 I; level l + 1 exists while level l has its smallest side
+ *     >= 4 and its largest >= 5.  Prolongation along an axis: even i copies e[i / 2], odd i takes fl(0.5 fl(e[(i - 1) / 2] +
+ *     e[min((i + 1) / 2, nc - 1)])); in three dimensions the axes in the order 0, 1, 2; the correction is chi <- fl(chi + P e).
+ *     Restriction is its transpose, halved per axis: acc = fl(0.5 r[2 I]), + fl(0.25 r[2 I - 1]) if that point exists, + fl(c
+ *     r[2 I + 1]) if that point exists, c = 0.5 when 2 I + 2 == n (the last point of an even side) and 0.25 otherwise; the axes
+ *     in the order 0, 1, 2; no renormalisation at the boundary.  W_{l+1} = R W_l by the same restriction.
+ *   5 cycle   cycle(l) on the coarsest level is 32 sweeps from the chi it is given; on any other level 2 sweeps, then gamma
+ *     times { r; b_{l+1} = R r; chi_{l+1} = 0; cycle(l + 1); chi_l += P chi_{l+1} }, then 2 sweeps.  The solve is `cycles` calls
+ *     of cycle(0) from chi = 0: a fixed count, no stopping test, nothing read on the host.
+ * ls2fm_poisson_solve  splat -> finish and right-hand side -> W of the levels -> the cycles, launched in a fixed order on `stream`
+ *   and capturable; value (chi) and density (W of level 0) are float [nx][ny][nz].  n_points = 0 gives chi = 0 and W = 0.  From
+ *   the first level of at most LS2FM_POISSON_TAIL_POINTS points downward one launch of one workgroup runs the whole sub-cycle in
+ *   LDS, with the device functions of the per-level kernels: the same bits.  ls2fm_poisson_solve_plan chooses tail_points = 0
+ *   (every level by its own launches) or LS2FM_POISSON_TAIL_POINTS; no plan shows in a bit.  The sweep kernel's brick is
+ *   LS2FM_POISSON_BRICK_X x _Y x _Z lattice points per workgroup.  The workspace (256-byte aligned,
+ *   ls2fm_poisson_workspace_bytes; -1 for a lattice that is refused) holds the accumulators, whose bytes the coarse levels take
+ *   over once the finish has read them, and b of level 0.
+ *   Refused before anything is enqueued, LS2FM_ERR_INVALID_ARGUMENT: a side below 2 or above 2^24, nx ny or the lattice 2^31
+ *   points or more, a voxel that is not positive and finite, a non-finite origin, n_points < 0 or >= 2^31, cycles < 0, gamma
+ *   not 1 or 2, screen not finite and positive, tail_points neither 0 nor LS2FM_POISSON_TAIL_POINTS, a NULL array that is
+ *   needed, a workspace that is NULL, misaligned or too small.
+ * The stages one at a time, with the kernels of the solve (the tests hold each to the restatement): ls2fm_poisson_splat (splat,
+ *   finish and right-hand side: V float [3][nx][ny][nz] or NULL, b, density; workspace of 32 bytes a lattice point),
+ *   ls2fm_poisson_sweep_colour (one colour of one sweep at scale s, in place), ls2fm_poisson_restrict (coarse = R r of chi, b,
+ *   density at scale s; with b and density NULL coarse = R chi; coarse is float [(nx + 1) / 2][(ny + 1) / 2][(nz + 1) / 2]) and
+ *   ls2fm_poisson_prolong (chi += P coarse).
+ */
+#define LS2FM_POISSON_BRICK_X 2
+#define LS2FM_POISSON_BRICK_Y 2
+#define LS2FM_POISSON_BRICK_Z 128
+#define LS2FM_POISSON_TAIL_POINTS 4096
+int64_t ls2fm_poisson_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int ls2fm_poisson_solve(const float* points, const float* normals, int64_t n_points, int64_t nx, int64_t ny, int64_t nz,
+                        const float* origin, float voxel, float screen, int32_t cycles, int32_t gamma, float* value, float* density,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int ls2fm_poisson_solve_plan(const float* points, const float* normals, int64_t n_points, int64_t nx, int64_t ny, int64_t nz,
+                             const float* origin, float voxel, float screen, int32_t cycles, int32_t gamma, int32_t tail_points,
+                             float* value, float* density, void* workspace, int64_t workspace_bytes, void* stream);
+int ls2fm_poisson_splat(const float* points, const float* normals, int64_t n_points, int64_t nx, int64_t ny, int64_t nz,
+                        const float* origin, float voxel, float* V, float* b, float* density, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int ls2fm_poisson_sweep_colour(float* chi, const float* b, const float* density, int64_t nx, int64_t ny, int64_t nz, float scale,
+                               float screen, int32_t colour, void* stream);
+int ls2fm_poisson_restrict(const float* chi, const float* b, const float* density, int64_t nx, int64_t ny, int64_t nz, float scale,
+                           float screen, float* coarse, void* stream);
+int ls2fm_poisson_prolong(float* chi, int64_t nx, int64_t ny, int64_t nz, const float* coarse, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP registration of a moving cloud to a fixed one (csrc/icp.hip behind ls2fm.metrics.icp; additions, the library stays ABI
  * 13): the step between the camera alignment and the Chamfer figures of a reconstruction in its own gauge.  The reference ships
  * none.  tests/icp_restate.py repeats the rule in numpy.

@@ -240,6 +240,14 @@ _SIGNATURES = {
     "ls2fm_cloud_implicit": (c_int32, [_P, _P, *_GRID_N_FIRST, *[c_int64] * 3, POINTER(c_float), c_float, c_int32, c_float, c_int32, _P, _P, _P]),
     "ls2fm_cloud_implicit_plan": (c_int32, [_P, _P, *_GRID_N_FIRST, *[c_int64] * 3, POINTER(c_float), c_float, c_int32, c_float, *[c_int32] * 3,
                                             _P, _P, _P]),
+    "ls2fm_poisson_workspace_bytes": (c_int64, [c_int64] * 3),
+    "ls2fm_poisson_solve": (c_int32, [_P, _P, *[c_int64] * 4, POINTER(c_float), c_float, c_float, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
+    "ls2fm_poisson_solve_plan": (c_int32, [_P, _P, *[c_int64] * 4, POINTER(c_float), c_float, c_float, *[c_int32] * 3, _P, _P, _P, c_int64,
+                                           _P]),
+    "ls2fm_poisson_splat": (c_int32, [_P, _P, *[c_int64] * 4, POINTER(c_float), c_float, _P, _P, _P, _P, c_int64, _P]),
+    "ls2fm_poisson_sweep_colour": (c_int32, [_P, _P, _P, *[c_int64] * 3, c_float, c_float, c_int32, _P]),
+    "ls2fm_poisson_restrict": (c_int32, [_P, _P, _P, *[c_int64] * 3, c_float, c_float, _P, _P]),
+    "ls2fm_poisson_prolong": (c_int32, [_P, *[c_int64] * 3, _P, _P]),
     "ls2fm_icp_workspace_bytes": (c_int64, [c_int64]),
     "ls2fm_icp_run": (c_int32, [_P, c_int64, *_GRID, _P, c_float, c_int32, c_int32, c_double, c_double, _P, _P, _P, _P, _P, _P]),
     "ls2fm_rasterize_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
