@@ -55,7 +55,7 @@ __device__ __forceinline__ void fill_tile(Tile<HW, T>& s, const float* __restric
         const int hy = h / L::kCols, hx = h % L::kCols;
         const int qx = x0 - HW + hx, qy = y0 - HW + hy;
         const bool live = qx >= 0 && qx < width && qy >= 0 && qy < height;
-        s.ref[hy * L::kRow + hx] = live ? pm_finite_or_nan(ref_img[(int64_t)qy * width + qx]) : NAN;
+        s.ref[hy * L::kRow + hx] = live ? finite_or_nan(ref_img[(int64_t)qy * width + qx]) : NAN;
     }
     if (t < L::kCols) s.xn[t] = __fdiv_rn(__fsub_rn(__fadd_rn((float)(x0 - HW + t), 0.5f), k[2]), k[0]);
     if (t >= 64 && t < 64 + L::kRows) s.yn[t - 64] = __fdiv_rn(__fsub_rn(__fadd_rn((float)(y0 - HW + t - 64), 0.5f), k[3]), k[1]);
@@ -98,7 +98,7 @@ __device__ __forceinline__ float plane_score(const Scene& sc, Tile<HW, T>& s, in
     for (int src = 0; src < sc.n_sources; ++src) {
         const int sv = sc.sources[src];
         if (sv < 0 || sv >= sc.n_views) continue;
-        const View cam = pm_load_pair(sc.rel, src, sc.intr, sv);
+        const View cam = load_pair(sc.rel, src, sc.intr, sv);
         const float* src_img = sc.images + (int64_t)sv * hw;
         float sum = 0.0f;
         for (int i = 0; i < L::kAxis; ++i) {
@@ -110,8 +110,8 @@ __device__ __forceinline__ float plane_score(const Scene& sc, Tile<HW, T>& s, in
                 const float xq = xn_win[j * T];
                 const float g_q = pm_g(n, xq, yq);
                 const float d_q = __fdiv_rn(h, g_q);
-                row[j] = pm_sample(src_img, sc.height, sc.width, project(cam, __fmul_rn(xq, d_q), __fmul_rn(yq, d_q), d_q, sc.near),
-                                   g_q < 0.0f && fabsf(d_q) < INFINITY);
+                row[j] = sample<false>(src_img, sc.height, sc.width, project(cam, __fmul_rn(xq, d_q), __fmul_rn(yq, d_q), d_q, sc.near),
+                                       g_q < 0.0f && fabsf(d_q) < INFINITY);
             }
 #pragma unroll
             for (int j = 0; j < L::kAxis; ++j) {
@@ -130,7 +130,7 @@ __device__ __forceinline__ float plane_score(const Scene& sc, Tile<HW, T>& s, in
                     cov = __fadd_rn(cov, __fmul_rn(da, db));
                 }
             if (!(vb < sc.min_var)) {
-                total = __fadd_rn(total, __fdiv_rn(cov, pm_sqrt_rn(__fmul_rn(va, vb))));
+                total = __fadd_rn(total, __fdiv_rn(cov, sqrt_rn(__fmul_rn(va, vb))));
                 ++count;
             }
         }
@@ -271,16 +271,6 @@ mvs_patchmatch_step(Args a, int colour, uint32_t iteration, uint32_t seed, float
 typedef void (*ScoreKernel)(Args, const float*, const float*, float*);
 typedef void (*StepKernel)(Args, int, uint32_t, uint32_t, float, float, float, const float*, const float*, float*, float*, float*);
 
-bool finite_not_negative(float v) { return v >= 0.0f && v < INFINITY; }
-
-// what both entry points refuse before n_refs = 0 returns, as ls2fm_mvs_sweep does
-bool shape_ok(int32_t n_views, int32_t height, int32_t width, int32_t n_refs, int32_t n_sources, int32_t half_width, int32_t tap_step,
-              float near, float min_var, int32_t min_sources) {
-    return raster_image_ok(n_views, height, width) && raster_image_ok(n_refs, height, width) && raster_near_ok(near) && n_sources >= 1 &&
-           n_sources <= LS2FM_MVS_MAX_SOURCES && half_width >= 1 && half_width <= LS2FM_MVS_MAX_HALF_WIDTH &&
-           (tap_step == 1 || tap_step == 2) && finite_not_negative(min_var) && min_sources >= 1 && min_sources <= n_sources;
-}
-
 }  // namespace
 
 #define PM_KERNELS(name) \
@@ -290,7 +280,8 @@ extern "C" int ls2fm_mvs_plane_score(const float* images, int32_t n_views, int32
                                      int32_t n_refs, const int32_t* sources, int32_t n_sources, const float* rel, const float* intr,
                                      int32_t half_width, int32_t tap_step, float near, float min_var, int32_t min_sources,
                                      const float* depth, const float* normal, float* score, void* stream) {
-    LS2FM_CHECK_ARG(shape_ok(n_views, height, width, n_refs, n_sources, half_width, tap_step, near, min_var, min_sources));
+    LS2FM_CHECK_ARG(mvs_shape_ok(n_views, height, width, n_refs, n_sources, half_width, near, min_var, min_sources) &&
+                    (tap_step == 1 || tap_step == 2));
     if (n_refs == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(n_views >= 1 && images && refs && sources && rel && intr && depth && normal && score);
     const int64_t tiles_x = (width + kTileW - 1) / kTileW, tiles_y = (height + kTileH - 1) / kTileH;
@@ -308,9 +299,9 @@ extern "C" int ls2fm_mvs_patchmatch_step(const float* images, int32_t n_views, i
                                          int32_t colour, int32_t iteration, uint32_t seed, float rho_d, float rho_n, float sigma,
                                          const float* d_min, const float* d_max, float* depth, float* normal, float* score,
                                          void* stream) {
-    LS2FM_CHECK_ARG(shape_ok(n_views, height, width, n_refs, n_sources, half_width, tap_step, near, min_var, min_sources) &&
-                    (colour == 0 || colour == 1) && iteration >= 0 && finite_not_negative(rho_d) && finite_not_negative(rho_n) &&
-                    finite_not_negative(sigma));
+    LS2FM_CHECK_ARG(mvs_shape_ok(n_views, height, width, n_refs, n_sources, half_width, near, min_var, min_sources) &&
+                    (tap_step == 1 || tap_step == 2) && (colour == 0 || colour == 1) && iteration >= 0 && finite_not_negative(rho_d) &&
+                    finite_not_negative(rho_n) && finite_not_negative(sigma));
     if (n_refs == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(n_views >= 1 && images && refs && sources && rel && intr && d_min && d_max && depth && normal && score);
     const int64_t tiles_x = (width + kTileW - 1) / kTileW, tiles_y = (height + kTileH - 1) / kTileH;

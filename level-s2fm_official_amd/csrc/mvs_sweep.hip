@@ -5,17 +5,15 @@
 // Sweep: one workgroup of 256 lanes takes one (reference, 16 x 16 tile).  The reference tile with its halo of w pixels goes to LDS
 // once, and every pixel's window mean and variance are formed once, before the plane and source loops.  Per (plane, source) the
 // lanes share out the (16 + 2 w)^2 halo pixels: each warps its pixels onto the plane, projects them into the source
-// (csrc/raster_project.h, unchanged) and samples it bilinearly into LDS -- a warped sample is formed once per tile, not once per
-// window that holds it.  After a barrier every lane runs its own window from LDS.  A sample that is invalid or not finite is
-// stored as NaN: a window's sum in tap order is NaN exactly when one of its taps is (finite taps can overflow to an infinity,
-// never to a NaN), so "any tap invalid" costs one comparison per window.  The LDS rows are kRow = 48 floats apart: a 32-lane half of
-// a wave reads two tile rows of 16 consecutive floats, and 48 = 16 mod 32 puts them on disjoint banks.  The running best score,
-// the scores before and after it and its plane stay in registers over the planes.  The pose P_rs, the intrinsics and the plane
-// depth are uniform over the workgroup: scalar loads.  No atomics, no workspace, nothing read back.
-#include "ls2fm_device.h"
-#include "raster_project.h"
-
-#include <cmath>
+// (csrc/raster_project.h, unchanged) and samples it bilinearly (csrc/mvs_sample.h, the one statement csrc/mvs_patchmatch.hip
+// uses too) into LDS -- a warped sample is formed once per tile, not once per window that holds it.  After a barrier every lane
+// runs its own window from LDS.  A sample that is invalid or not finite is stored as NaN: a window's sum in tap order is NaN
+// exactly when one of its taps is (finite taps can overflow to an infinity, never to a NaN), so "any tap invalid" costs one
+// comparison per window.  The LDS rows are kRow = 48 floats apart: a 32-lane half of a wave reads two tile rows of 16 consecutive
+// floats, and 48 = 16 mod 32 puts them on disjoint banks.  The running best score, the scores before and after it and its plane
+// stay in registers over the planes.  The pose P_rs, the intrinsics and the plane depth are uniform over the workgroup: scalar
+// loads.  No atomics, no workspace, nothing read back.
+#include "mvs_sample.h"
 
 namespace {
 
@@ -28,38 +26,6 @@ static_assert(kTile == LS2FM_MVS_TILE, "the header states the tile");
 static_assert(kRow >= kTile + 2 * LS2FM_MVS_MAX_HALF_WIDTH && kRow % 32 == 16, "rows of a half-wave on disjoint banks");
 
 typedef float Pair __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float finite_or_nan(float v) { return fabsf(v) < INFINITY ? v : NAN; }
-
-// the correctly rounded fp32 square root.  __fsqrt_rn lowers to the bare v_sqrt_f32 here (1 ulp), so the root is taken in fp64
-// (correctly rounded: csrc/mesh_colors.hip relies on it too) and rounded to fp32: 53 >= 2 * 24 + 2 bits leave no double rounding
-__device__ __forceinline__ float sqrt_rn(float v) { return (float)__dsqrt_rn((double)v); }
-
-// the pose of entry `pair` of a [.., 3, 4] array with the intrinsics of view `view`: uniform over the wave, scalar loads
-__device__ __forceinline__ View load_pair(const float* __restrict__ rel, int64_t pair, const float* __restrict__ intr, int view) {
-    View w;
-    const float* p = rel + pair * 12;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) w.p[k] = p[k];
-    const float* q = intr + (int64_t)view * 4;
-    w.fx = q[0]; w.fy = q[1]; w.cx = q[2]; w.cy = q[3];
-    return w;
-}
-
-// STEP 3 of THE SWEEP RULE: the bilinear sample of one image at the projection p, NaN when it is invalid or not finite
-__device__ __forceinline__ float sample(const float* __restrict__ img, int height, int width, const Projected& p) {
-#pragma clang fp contract(off)
-    const float x = __fsub_rn(p.u, 0.5f), y = __fsub_rn(p.v, 0.5f);
-    const float x0 = floorf(x), y0 = floorf(y);
-    // every comparison is false for a NaN; |u|, |v| <= 65536 by usable, so x0 and y0 convert
-    if (!(p.usable && x0 >= 0.0f && x0 <= (float)(width - 2) && y0 >= 0.0f && y0 <= (float)(height - 2))) return NAN;
-    const float tx = __fsub_rn(x, x0), ty = __fsub_rn(y, y0);
-    const float* q = img + (int64_t)(int)y0 * width + (int)x0;
-    const float b00 = q[0], b10 = q[1], b01 = q[width], b11 = q[width + 1];
-    const float r0 = __fadd_rn(b00, __fmul_rn(tx, __fsub_rn(b10, b00)));
-    const float r1 = __fadd_rn(b01, __fmul_rn(tx, __fsub_rn(b11, b01)));
-    return finite_or_nan(__fadd_rn(r0, __fmul_rn(ty, __fsub_rn(r1, r0))));
-}
 
 template <int HW>
 __global__ void __launch_bounds__(kThreads)
@@ -143,7 +109,7 @@ mvs_sweep(const float* __restrict__ images, int n_views, int height, int width, 
                 const int h = t + j * kThreads;
                 if (h < kHalo) {
                     float b = NAN;
-                    if (live[j]) b = sample(src_img, height, width, project(cam, __fmul_rn(xn[j], d), __fmul_rn(yn[j], d), d, near));
+                    if (live[j]) b = sample<true>(src_img, height, width, project(cam, __fmul_rn(xn[j], d), __fmul_rn(yn[j], d), d, near));
                     src_t[(h / kSide) * kRow + h % kSide] = b;
                 }
             }
@@ -254,10 +220,8 @@ extern "C" int ls2fm_mvs_sweep(const float* images, int32_t n_views, int32_t hei
                                const int32_t* sources, int32_t n_sources, const float* depths, int32_t n_planes, const float* rel,
                                const float* intr, int32_t half_width, float near, float min_var, int32_t min_sources, float* depth,
                                float* score, int32_t* plane, void* stream) {
-    LS2FM_CHECK_ARG(raster_image_ok(n_views, height, width) && raster_image_ok(n_refs, height, width) && raster_near_ok(near) &&
-                    n_sources >= 1 && n_sources <= LS2FM_MVS_MAX_SOURCES && n_planes >= 1 && n_planes <= LS2FM_MVS_MAX_PLANES &&
-                    half_width >= 1 && half_width <= LS2FM_MVS_MAX_HALF_WIDTH && min_var >= 0.0f && min_var < INFINITY &&
-                    min_sources >= 1 && min_sources <= n_sources);
+    LS2FM_CHECK_ARG(mvs_shape_ok(n_views, height, width, n_refs, n_sources, half_width, near, min_var, min_sources) && n_planes >= 1 &&
+                    n_planes <= LS2FM_MVS_MAX_PLANES);
     if (n_refs == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(n_views >= 1 && images && refs && sources && depths && rel && intr && depth && score && plane);
     const int64_t tiles_x = (width + kTile - 1) / kTile, tiles_y = (height + kTile - 1) / kTile;
@@ -274,8 +238,8 @@ extern "C" int ls2fm_mvs_filter(const float* depth, int32_t n_views, int32_t hei
                                 float max_reproj, float rel_depth, int32_t min_consistent, uint8_t* count, float* filtered,
                                 void* stream) {
     LS2FM_CHECK_ARG(raster_image_ok(n_views, height, width) && raster_near_ok(near) && n_sources >= 1 &&
-                    n_sources <= LS2FM_MVS_MAX_SOURCES && max_reproj >= 0.0f && max_reproj < INFINITY && rel_depth >= 0.0f &&
-                    rel_depth < INFINITY && min_consistent >= 0);
+                    n_sources <= LS2FM_MVS_MAX_SOURCES && finite_not_negative(max_reproj) && finite_not_negative(rel_depth) &&
+                    min_consistent >= 0);
     if (n_views == 0) return LS2FM_OK;
     LS2FM_CHECK_ARG(depth && sources && rel && rel_back && intr && count && filtered);
     const int64_t blocks_per_view = ((int64_t)height * width + kFilterThreads - 1) / kFilterThreads;

@@ -241,6 +241,79 @@ def _grey(images, n, who):
     return _lib.cf(images.detach())
 
 
+def _check_tap_step(tap_step, who):
+    tap_step = int(tap_step)
+    if tap_step not in (1, 2):
+        raise ValueError(f"{who}: tap_step {tap_step} must be 1 or 2")
+    return tap_step
+
+
+class _Checked:
+    """the checked inputs of one set of references, as the kernels (_Inputs) and the torch forms (_TorchScene) take them"""
+
+    def gather(self, img, poses, sources, refs, depths, half_width, tap_step, min_var, min_sources, who):
+        self.V, self.dev = int(poses.shape[0]), poses.device
+        self.img = _grey(img, self.V, who)
+        self.refs, self.sources, self.depths = _index_arrays(refs, sources, depths, self.V, self.dev, who)
+        self.R, self.S, self.H, self.W = int(self.refs.shape[0]), int(self.sources.shape[1]), int(self.img.shape[1]), int(self.img.shape[2])
+        self.D = 1 if depths is None else int(self.depths.shape[1])
+        self.w, self.min_var, self.min_sources = _check_sweep(half_width, min_var, min_sources, self.S, self.D, who)
+        self.t = _check_tap_step(tap_step, who)
+        self.rel = relative_poses(poses, self.refs, self.sources)
+
+
+def _device_views(maps, pose, intr, who):
+    """-> the maps as given, the poses [V, 3, 4] and k4 [V, 4] of a call that runs on the device"""
+    maps = torch.as_tensor(maps)
+    _device(maps, torch.as_tensor(pose), torch.as_tensor(intr))
+    return (maps,) + _posed.views(pose, intr, who)
+
+
+class _Inputs(_Checked):
+    """what plane_sweep, plane_score, patch_match_step and patch_match share: the checked inputs of one set of references"""
+
+    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who, depths=None):
+        images, poses, self.k4 = _device_views(images, pose, intr, who)
+        self.gather(images, poses, sources, refs, depths, half_width, tap_step, min_var, min_sources, who)
+        self.near = _posed.near_plane(near, who)
+        if self.img.device != self.dev:
+            raise ValueError(f"{who}: the poses on {self.dev}, the images on {self.img.device}")
+
+    def head(self, s, e, depths=None):
+        """the arguments every entry point begins with, for the references s .. e: the sweep has its planes before the poses and
+        no tap step"""
+        planes, taps = ((), (self.t,)) if depths is None else ((ptr(depths[s:e]), int(depths.shape[1])), ())
+        return (ptr(self.img), self.V, self.H, self.W, ptr(self.refs[s:e]), e - s, ptr(self.sources[s:e]), self.S, *planes,
+                ptr(self.rel[s:e]), ptr(self.k4), self.w, *taps, self.near, self.min_var, self.min_sources)
+
+    def sweep(self, depths, budget):
+        """ls2fm_mvs_sweep over the checked planes depths [R, D] -> depth, score, plane"""
+        depth = torch.empty((self.R, self.H, self.W), dtype=torch.float32, device=self.dev)
+        score = torch.empty((self.R, self.H, self.W), dtype=torch.float32, device=self.dev)
+        plane = torch.empty((self.R, self.H, self.W), dtype=torch.int32, device=self.dev)
+        lib = _lib.load()
+        with torch.cuda.device(self.dev):
+            for s, e in _posed.chunks(self.R, 12, self.H, self.W, budget):
+                check(lib.ls2fm_mvs_sweep(*self.head(s, e, depths), ptr(depth[s:e]), ptr(score[s:e]), ptr(plane[s:e]), stream_ptr()),
+                      "ls2fm_mvs_sweep")
+        return depth, score, plane
+
+    def score(self, depth, normal, score, budget):
+        lib = _lib.load()
+        with torch.cuda.device(self.dev):
+            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
+                check(lib.ls2fm_mvs_plane_score(*self.head(s, e), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]), stream_ptr()),
+                      "ls2fm_mvs_plane_score")
+
+    def step(self, depth, normal, score, colour, iteration, seed, rho_d, rho_n, sigma, d_min, d_max, budget):
+        lib = _lib.load()
+        with torch.cuda.device(self.dev):
+            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
+                check(lib.ls2fm_mvs_patchmatch_step(*self.head(s, e), colour, iteration, int(seed) & 0xFFFFFFFF, rho_d, rho_n, sigma,
+                                                    ptr(d_min[s:e]), ptr(d_max[s:e]), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]),
+                                                    stream_ptr()), "ls2fm_mvs_patchmatch_step")
+
+
 @torch.no_grad()
 def plane_sweep(images, pose, intr, sources, depths, refs=None, half_width=3, near=1e-3, min_var=1e-6, min_sources=1,
                 max_workspace_bytes=2 ** 28):
@@ -253,29 +326,8 @@ def plane_sweep(images, pose, intr, sources, depths, refs=None, half_width=3, ne
       depths     float [R, D] or [D], the plane depths (depth_planes)
     The references go in chunks whose outputs (12 bytes per pixel) stay within max_workspace_bytes, one launch per chunk; the
     chunking does not show in the bits.  No host read."""
-    who = "ls2fm.mvs.plane_sweep"
-    images = torch.as_tensor(images)
-    _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
-    poses, k4 = _posed.views(pose, intr, who)
-    V, dev = int(poses.shape[0]), poses.device
-    img = _grey(images, V, who)
-    refs, sources, depths = _index_arrays(refs, sources, depths, V, dev, who)
-    R, S, D, H, W = int(refs.shape[0]), int(sources.shape[1]), int(depths.shape[1]), int(img.shape[1]), int(img.shape[2])
-    half_width, min_var, min_sources = _check_sweep(half_width, min_var, min_sources, S, D, who)
-    near = _posed.near_plane(near, who)
-    if img.device != dev:
-        raise ValueError(f"{who}: the poses on {dev}, the images on {img.device}")
-    rel = relative_poses(poses, refs, sources)
-    depth = torch.empty((R, H, W), dtype=torch.float32, device=dev)
-    score = torch.empty((R, H, W), dtype=torch.float32, device=dev)
-    plane = torch.empty((R, H, W), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        for s, e in _posed.chunks(R, 12, H, W, max_workspace_bytes):
-            check(lib.ls2fm_mvs_sweep(ptr(img), V, H, W, ptr(refs[s:e]), e - s, ptr(sources[s:e]), S, ptr(depths[s:e]), D, ptr(rel[s:e]),
-                                      ptr(k4), half_width, near, min_var, min_sources, ptr(depth[s:e]), ptr(score[s:e]), ptr(plane[s:e]),
-                                      stream_ptr()), "ls2fm_mvs_sweep")
-    return depth, score, plane
+    a = _Inputs(images, pose, intr, sources, refs, half_width, 1, near, min_var, min_sources, "ls2fm.mvs.plane_sweep", depths)
+    return a.sweep(a.depths, max_workspace_bytes)
 
 
 @torch.no_grad()
@@ -287,9 +339,7 @@ def filter_depths(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_dep
       sources    int [V, S]; -1 skips
     One launch, no host read."""
     who = "ls2fm.mvs.filter_depths"
-    depth = torch.as_tensor(depth)
-    _device(depth, torch.as_tensor(pose), torch.as_tensor(intr))
-    poses, k4 = _posed.views(pose, intr, who)
+    depth, poses, k4 = _device_views(depth, pose, intr, who)
     V, dev = int(poses.shape[0]), poses.device
     d = _grey(depth, V, who)
     refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
@@ -308,13 +358,6 @@ def filter_depths(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_dep
 
 
 # -------------------------------------------------------------------------------------------------------------------- PatchMatch
-def _check_tap_step(tap_step, who):
-    tap_step = int(tap_step)
-    if tap_step not in (1, 2):
-        raise ValueError(f"{who}: tap_step {tap_step} must be 1 or 2")
-    return tap_step
-
-
 def _check_step(colour, iteration, depth_perturb, normal_perturb, max_slope, who):
     """-> colour, iteration, rho_d, rho_n, sigma: the perturbations on the schedule rho 2^-iteration, formed in fp64 (the float
     argument of the call, or the float32 tensor of the torch form, rounds them once)"""
@@ -341,45 +384,6 @@ def _state(depth, normal, score, R, H, W, dev, who, in_place):
             raise ValueError(f"{who}: {name} is updated in place: it must be a contiguous float32 tensor on {dev}")
         out.append(t if in_place else _lib.cf(t.detach().to(dev)))
     return out
-
-
-class _Inputs:
-    """what plane_score and patch_match_step share: the checked inputs of one set of references"""
-
-    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who):
-        images = torch.as_tensor(images)
-        _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
-        poses, self.k4 = _posed.views(pose, intr, who)
-        self.V, self.dev = int(poses.shape[0]), poses.device
-        self.img = _grey(images, self.V, who)
-        self.refs, self.sources, _ = _index_arrays(refs, sources, None, self.V, self.dev, who)
-        self.R, self.S, self.H, self.W = int(self.refs.shape[0]), int(self.sources.shape[1]), int(self.img.shape[1]), int(self.img.shape[2])
-        self.w, self.min_var, self.min_sources = _check_sweep(half_width, min_var, min_sources, self.S, 1, who)
-        self.t = _check_tap_step(tap_step, who)
-        self.near = _posed.near_plane(near, who)
-        if self.img.device != self.dev:
-            raise ValueError(f"{who}: the poses on {self.dev}, the images on {self.img.device}")
-        self.rel = relative_poses(poses, self.refs, self.sources)
-
-    def head(self, s, e):
-        """the arguments both entry points begin with, for the references s .. e"""
-        return (ptr(self.img), self.V, self.H, self.W, ptr(self.refs[s:e]), e - s, ptr(self.sources[s:e]), self.S, ptr(self.rel[s:e]),
-                ptr(self.k4), self.w, self.t, self.near, self.min_var, self.min_sources)
-
-    def score(self, depth, normal, score, budget):
-        lib = _lib.load()
-        with torch.cuda.device(self.dev):
-            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
-                check(lib.ls2fm_mvs_plane_score(*self.head(s, e), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]), stream_ptr()),
-                      "ls2fm_mvs_plane_score")
-
-    def step(self, depth, normal, score, colour, iteration, seed, rho_d, rho_n, sigma, d_min, d_max, budget):
-        lib = _lib.load()
-        with torch.cuda.device(self.dev):
-            for s, e in _posed.chunks(self.R, 20, self.H, self.W, budget):
-                check(lib.ls2fm_mvs_patchmatch_step(*self.head(s, e), colour, iteration, int(seed) & 0xFFFFFFFF, rho_d, rho_n, sigma,
-                                                    ptr(d_min[s:e]), ptr(d_max[s:e]), ptr(depth[s:e]), ptr(normal[s:e]), ptr(score[s:e]),
-                                                    stream_ptr()), "ls2fm_mvs_patchmatch_step")
 
 
 def _range(d_min, d_max, R, dev, who):
@@ -451,8 +455,9 @@ def patch_match(images, pose, intr, sources, depths, refs=None, iterations=5, in
     _, _, depths = _index_arrays(a.refs, a.sources, depths, a.V, a.dev, who)
     d_min, d_max = depths[:, 0].contiguous(), depths[:, -1].contiguous()
     if init is None:
-        depth = plane_sweep(a.img, pose, intr, a.sources, depths, refs=a.refs, half_width=half_width, near=near, min_var=min_var,
-                            min_sources=min_sources, max_workspace_bytes=max_workspace_bytes)[0]
+        # the inputs are checked already; what the sweep adds is its plane count, refused in plane_sweep's name as before
+        _check_sweep(a.w, a.min_var, a.min_sources, a.S, int(depths.shape[1]), "ls2fm.mvs.plane_sweep")
+        depth = a.sweep(depths, max_workspace_bytes)[0]
         normal = torch.zeros((a.R, a.H, a.W, 3), dtype=torch.float32, device=a.dev)
         normal[..., 2] = -1.0
     else:
@@ -487,10 +492,17 @@ def normals_to_world(normal, pose, refs=None):
 
 
 # -------------------------------------------------------------------------------------------------------------- the torch forms
-def _torch_views(pose, intr, dev):
-    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(dev)
-    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3).float().to(dev).expand(P.shape[0], 3, 3)
-    return P, K
+def _torch_views(maps, pose, intr):
+    """-> the maps as float32, P [V, 3, 4] and K [V, 3, 3] on the maps' device"""
+    maps = torch.as_tensor(maps).detach().float()
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).float().to(maps.device)
+    K = torch.as_tensor(intr).detach().reshape(-1, 3, 3).float().to(maps.device).expand(P.shape[0], 3, 3)
+    return maps, P, K
+
+
+def _scalar(v, dev):
+    """a 0-dim float32 tensor on dev: a division by a Python scalar would be a multiplication by its reciprocal"""
+    return torch.tensor(float(v), dtype=torch.float32, device=dev)
 
 
 def _taps(Z, w):
@@ -521,82 +533,132 @@ def _lift(K, H, W, dev):
     return xn[None, :], yn[:, None]
 
 
+class _TorchScene(_Checked):
+    """the inputs of plane_sweep_torch, plane_score_torch and patch_match_step_torch, and per reference what no plane changes"""
+
+    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who, depths=None):
+        img, P, self.K = _torch_views(images, pose, intr)
+        self.gather(img, P, sources, refs, depths, half_width, tap_step, min_var, min_sources, who)
+        self.refs, self.sources = self.refs.tolist(), self.sources.tolist()
+        self.scalar = functools.partial(_scalar, dev=self.dev)
+        side = range(0, 2 * self.w + 1, self.t)
+        self.offsets = [(j - self.w, i - self.w) for i in side for j in side]
+        self.picked = [i * (2 * self.w + 1) + j for i in side for j in side]
+        self.n, self.near, self.min_var = self.scalar(len(self.offsets)), self.scalar(_posed.near_plane(near, who)), self.scalar(self.min_var)
+        self.cache = {}
+
+    def reference(self, r):
+        """step 1 of THE SWEEP RULE over the window's picked taps `a`, and the lift xn [W], yn [H]; None for a view outside [0, V)"""
+        rv = self.refs[r]
+        if not 0 <= rv < self.V:
+            return None
+        if r not in self.cache:
+            nan = torch.full((self.H, self.W), math.nan, dtype=torch.float32, device=self.dev)
+            img = torch.where(torch.isfinite(self.img[rv]), self.img[rv], nan)
+            every = _taps(img, self.w)
+            a = [every[i] for i in self.picked]
+            sa = _tap_sum(a)
+            ma = sa / self.n
+            va = torch.zeros_like(sa)
+            for t in a:
+                va = va + (t - ma) * (t - ma)
+            xn, yn = _lift(self.K[rv], self.H, self.W, self.dev)
+            self.cache[r] = dict(rv=rv, img=img, a=a, ma=ma, va=va, pixel_ok=~torch.isnan(sa) & ~(va < self.min_var), xn=xn[0], yn=yn[:, 0])
+        return self.cache[r]
+
+    def sample(self, r, s, sv, X, Y, Z):
+        """steps 2 and 3 of THE SWEEP RULE at the camera points (X, Y, Z) of reference r: NaN where not valid"""
+        H, W = self.H, self.W
+        _, u, v, usable, _, _, _ = _posed.project_torch(self.rel[r, s], self.K[sv], X, Y, Z, self.near, H, W)
+        fx, fy = u - 0.5, v - 0.5
+        x0, y0 = fx.floor(), fy.floor()
+        tx, ty = fx - x0, fy - y0
+        ok = usable & (x0 >= 0) & (x0 <= W - 2) & (y0 >= 0) & (y0 <= H - 2)
+        zero = torch.zeros_like(x0)
+        at = torch.where(ok, y0, zero).long() * W + torch.where(ok, x0, zero).long()
+        src, last = self.img[sv].reshape(-1), H * W - 1
+        b00, b10 = src[at], src[(at + 1).clamp(max=last)]
+        b01, b11 = src[(at + W).clamp(max=last)], src[(at + W + 1).clamp(max=last)]
+        r0 = b00 + tx * (b10 - b00)
+        r1 = b01 + tx * (b11 - b01)
+        b = r0 + ty * (r1 - r0)
+        return torch.where(ok & torch.isfinite(b), b, torch.full_like(b, math.nan))
+
+    def correlate(self, total, count, da, b, va, ok):
+        """step 4 of THE SWEEP RULE and a source's share of step 5: the NCC of the samples b against the a_i - ma `da` -- both in tap
+        order; da a list that the sweep forms once, or a generator that subtracts per tap -- joins (total, count) where it is valid"""
+        sb = _tap_sum(b)
+        mb = sb / self.n
+        vb, cov = torch.zeros_like(sb), torch.zeros_like(sb)
+        for dai, bi in zip(da, b):
+            db = bi - mb
+            vb = vb + db * db
+            cov = cov + dai * db
+        valid = ok & ~torch.isnan(sb) & ~(vb < self.min_var)
+        ncc = cov / _sqrt_rn(va * vb)
+        return torch.where(valid, total + ncc, total), count + valid
+
+    def score(self, r, py, px, d, n):
+        """THE PLANE SCORE of (d [N], n [N, 3]) at the pixels (px, py) (int64 [N]) of reference r -> float32 [N]"""
+        nan = torch.full(py.shape, math.nan, dtype=torch.float32, device=self.dev)
+        ref = self.reference(r)
+        if ref is None:
+            return nan
+        nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+        gp = (nx * ref["xn"][px] + ny * ref["yn"][py]) + nz
+        ok = ref["pixel_ok"][py, px] & torch.isfinite(d) & (d > 0) & torch.isfinite(nx) & torch.isfinite(ny) & torch.isfinite(nz) & (gp < 0)
+        h = gp * d
+        a, pts = [], []
+        for dx, dy in self.offsets:
+            qx, qy = (px + dx).clamp(0, self.W - 1), (py + dy).clamp(0, self.H - 1)
+            xq, yq = ref["xn"][qx], ref["yn"][qy]
+            gq = (nx * xq + ny * yq) + nz
+            dq = h / gq
+            a.append(ref["img"][qy, qx])
+            pts.append((xq * dq, yq * dq, dq, (gq < 0) & torch.isfinite(dq)))
+        ma, va = ref["ma"][py, px], ref["va"][py, px]
+        total, count = torch.zeros_like(nan), torch.zeros(py.shape, dtype=torch.int64, device=self.dev)
+        for s, sv in enumerate(self.sources[r]):
+            if not 0 <= sv < self.V:
+                continue
+            b = [torch.where(tap_ok, self.sample(r, s, sv, X, Y, Z), nan) for X, Y, Z, tap_ok in pts]
+            total, count = self.correlate(total, count, (ai - ma for ai in a), b, va, ok)
+        return torch.where(ok & (count >= self.min_sources), total / count.float(), nan)
+
+
 @torch.no_grad()
 def plane_sweep_torch(images, pose, intr, sources, depths, refs=None, half_width=3, near=1e-3, min_var=1e-6, min_sources=1):
     """THE SWEEP RULE as plain torch ops on the images' device (a CPU works), vectorised over the pixels of one reference, the
     references, planes, sources and taps in loops: the same operations in the same order, each a separate op, so each rounds
     once.  A non-finite or invalid sample is a NaN, and a window's sum is NaN exactly when one of its taps is.  Reads `refs` and
     `sources` on the host.  -> (depth, score, plane) as plane_sweep."""
-    who = "ls2fm.mvs.plane_sweep_torch"
-    img = torch.as_tensor(images).detach().float()
-    dev = img.device
-    P, K = _torch_views(pose, intr, dev)
-    V = int(P.shape[0])
-    img = _grey(img, V, who)
-    refs, sources, depths = _index_arrays(refs, sources, depths, V, dev, who)
-    R, S, D, H, W = int(refs.shape[0]), int(sources.shape[1]), int(depths.shape[1]), int(img.shape[1]), int(img.shape[2])
-    w, min_var, min_sources = _check_sweep(half_width, min_var, min_sources, S, D, who)
-    rel = relative_poses(P, refs, sources)
-    # 0-dim device tensors: a division by a Python scalar would be a multiplication by its reciprocal
-    scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
-    n, near, min_var = scalar((2 * w + 1) ** 2), scalar(_posed.near_plane(near, who)), scalar(min_var)
+    sc = _TorchScene(images, pose, intr, sources, refs, half_width, 1, near, min_var, min_sources, "ls2fm.mvs.plane_sweep_torch", depths)
+    R, D, H, W, dev, depths = sc.R, sc.D, sc.H, sc.W, sc.dev, sc.depths
     nan = torch.full((H, W), math.nan, dtype=torch.float32, device=dev)
-    finite = lambda t: torch.where(torch.isfinite(t), t, nan)
     out_d, out_s = nan.repeat(R, 1, 1), nan.repeat(R, 1, 1)
     out_k = torch.full((R, H, W), -1, dtype=torch.int32, device=dev)
-    last = H * W - 1
-    for r, (rv, srcs) in enumerate(zip(refs.tolist(), sources.tolist())):
-        if not 0 <= rv < V:
+    for r in range(R):
+        ref = sc.reference(r)
+        if ref is None:
             continue
-        # 1. the reference window
-        a = _taps(finite(img[rv]), w)
-        sa = _tap_sum(a)
-        ma = sa / n
-        da = [t - ma for t in a]
-        va = torch.zeros_like(sa)
-        for t in da:
-            va = va + t * t
-        pixel_ok = ~torch.isnan(sa) & ~(va < min_var)
-        xn, yn = _lift(K[rv], H, W, dev)
+        # 1. the reference window: a_i - ma once for all planes and sources
+        da = [t - ref["ma"] for t in ref["a"]]
+        xn, yn = ref["xn"][None, :], ref["yn"][:, None]
         best, before, after, previous = nan, nan, nan, nan
         best_k = torch.full((H, W), -1, dtype=torch.int64, device=dev)
         for k in range(D):
             d = depths[r, k]
-            total, count = torch.zeros_like(sa), torch.zeros((H, W), dtype=torch.int64, device=dev)
-            for s, sv in enumerate(srcs):
-                if not 0 <= sv < V:
+            total, count = torch.zeros_like(nan), torch.zeros((H, W), dtype=torch.int64, device=dev)
+            # 2. warp: every pixel of the reference is a tap
+            X, Y, Z = (xn * d).expand(H, W).reshape(-1), (yn * d).expand(H, W).reshape(-1), d.expand(H * W)
+            for s, sv in enumerate(sc.sources[r]):
+                if not 0 <= sv < sc.V:
                     continue
-                # 2. warp, 3. sample
-                x, y = (xn * d).expand(H, W).reshape(-1), (yn * d).expand(H, W).reshape(-1)
-                _, u, v, usable, _, _, _ = _posed.project_torch(rel[r, s], K[sv], x, y, d.expand(H * W), near, H, W)
-                fx, fy = u - 0.5, v - 0.5
-                x0, y0 = fx.floor(), fy.floor()
-                tx, ty = fx - x0, fy - y0
-                ok = usable & (x0 >= 0) & (x0 <= W - 2) & (y0 >= 0) & (y0 <= H - 2)
-                zero = torch.zeros_like(x0)
-                at = torch.where(ok, y0, zero).long() * W + torch.where(ok, x0, zero).long()
-                src = img[sv].reshape(-1)
-                b00, b10 = src[at], src[(at + 1).clamp(max=last)]
-                b01, b11 = src[(at + W).clamp(max=last)], src[(at + W + 1).clamp(max=last)]
-                r0 = b00 + tx * (b10 - b00)
-                r1 = b01 + tx * (b11 - b01)
-                b = r0 + ty * (r1 - r0)
-                b = torch.where(ok & torch.isfinite(b), b, nan.reshape(-1)).reshape(H, W)
-                # 4. NCC
-                bt = _taps(b, w)
-                sb = _tap_sum(bt)
-                mb = sb / n
-                vb, cov = torch.zeros_like(sb), torch.zeros_like(sb)
-                for ai, t in zip(da, bt):
-                    db = t - mb
-                    vb = vb + db * db
-                    cov = cov + ai * db
-                valid = pixel_ok & ~torch.isnan(sb) & ~(vb < min_var)
-                ncc = cov / _sqrt_rn(va * vb)
-                total = torch.where(valid, total + ncc, total)
-                count = count + valid
+                # 3. sample, 4. NCC
+                bt = _taps(sc.sample(r, s, sv, X, Y, Z).reshape(H, W), sc.w)
+                total, count = sc.correlate(total, count, da, bt, ref["va"], ref["pixel_ok"])
             # 5. aggregate, 6. select
-            score = torch.where(count >= min_sources, total / count.float(), nan)
+            score = torch.where(count >= sc.min_sources, total / count.float(), nan)
             better = ~torch.isnan(score) & ((best_k < 0) | (score > best))
             follows = ~better & (best_k + 1 == k)
             before = torch.where(better, previous, before)
@@ -614,6 +676,7 @@ def plane_sweep_torch(images, pose, intr, sources, depths, refs=None, half_width
         out_d[r] = torch.where(best_k >= 0, refined, nan)
         out_s[r] = best
         out_k[r] = best_k.to(torch.int32)
+        sc.cache.clear()                                               # a reference comes once: its taps need not outlive it
     return out_d, out_s, out_k
 
 
@@ -622,16 +685,14 @@ def filter_depths_torch(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, r
     """THE CONSISTENCY RULE as plain torch ops on the depth maps' device (a CPU works), vectorised over the pixels of one view.
     Reads `sources` on the host.  -> (filtered, count) as filter_depths."""
     who = "ls2fm.mvs.filter_depths_torch"
-    depth = torch.as_tensor(depth).detach().float()
-    dev = depth.device
-    P, K = _torch_views(pose, intr, dev)
-    V = int(P.shape[0])
+    depth, P, K = _torch_views(depth, pose, intr)
+    V, dev = int(P.shape[0]), depth.device
     depth = _grey(depth, V, who)
     refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
     S, H, W = int(sources.shape[1]), int(depth.shape[1]), int(depth.shape[2])
     max_reproj, rel_depth, min_consistent = _check_filter(max_reproj, rel_depth, min_consistent, S, who)
     rel, back = relative_poses(P, refs, sources), relative_poses(P, refs, sources, back=True)
-    scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
+    scalar = functools.partial(_scalar, dev=dev)
     near, max_reproj, rel_depth = scalar(_posed.near_plane(near, who)), scalar(max_reproj), scalar(rel_depth)
     reproj2 = max_reproj * max_reproj
     count = torch.zeros((V, H * W), dtype=torch.int64, device=dev)
@@ -681,102 +742,6 @@ def _draws(seed, view, iteration, pixel):
 def _normalise(x, y, z):
     root = _sqrt_rn((x * x + y * y) + z * z)
     return torch.stack([x / root, y / root, z / root], dim=1)
-
-
-class _TorchScene:
-    """the inputs of plane_score_torch and patch_match_step_torch, and per reference what no hypothesis changes"""
-
-    def __init__(self, images, pose, intr, sources, refs, half_width, tap_step, near, min_var, min_sources, who):
-        img = torch.as_tensor(images).detach().float()
-        self.dev = dev = img.device
-        self.P, self.K = _torch_views(pose, intr, dev)
-        self.V = int(self.P.shape[0])
-        self.img = _grey(img, self.V, who)
-        refs, sources, _ = _index_arrays(refs, sources, None, self.V, dev, who)
-        self.R, self.S, self.H, self.W = int(refs.shape[0]), int(sources.shape[1]), int(self.img.shape[1]), int(self.img.shape[2])
-        self.w, min_var, self.min_sources = _check_sweep(half_width, min_var, min_sources, self.S, 1, who)
-        self.t = _check_tap_step(tap_step, who)
-        self.rel = relative_poses(self.P, refs, sources)
-        self.refs, self.sources = refs.tolist(), sources.tolist()
-        self.scalar = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)
-        side = range(0, 2 * self.w + 1, self.t)
-        self.offsets = [(j - self.w, i - self.w) for i in side for j in side]
-        self.picked = [i * (2 * self.w + 1) + j for i in side for j in side]
-        self.n, self.near, self.min_var = self.scalar(len(self.offsets)), self.scalar(_posed.near_plane(near, who)), self.scalar(min_var)
-        self.cache = {}
-
-    def reference(self, r):
-        rv = self.refs[r]
-        if not 0 <= rv < self.V:
-            return None
-        if r not in self.cache:
-            nan = torch.full((self.H, self.W), math.nan, dtype=torch.float32, device=self.dev)
-            img = torch.where(torch.isfinite(self.img[rv]), self.img[rv], nan)
-            every = _taps(img, self.w)
-            a = [every[i] for i in self.picked]
-            sa = _tap_sum(a)
-            ma = sa / self.n
-            va = torch.zeros_like(sa)
-            for t in a:
-                va = va + (t - ma) * (t - ma)
-            xn, yn = _lift(self.K[rv], self.H, self.W, self.dev)
-            self.cache[r] = dict(rv=rv, img=img, ma=ma, va=va, pixel_ok=~torch.isnan(sa) & ~(va < self.min_var), xn=xn[0], yn=yn[:, 0])
-        return self.cache[r]
-
-    def sample(self, r, s, sv, X, Y, Z):
-        """steps 2 and 3 of THE SWEEP RULE at the camera points (X, Y, Z) of reference r: NaN where not valid"""
-        H, W = self.H, self.W
-        _, u, v, usable, _, _, _ = _posed.project_torch(self.rel[r, s], self.K[sv], X, Y, Z, self.near, H, W)
-        fx, fy = u - 0.5, v - 0.5
-        x0, y0 = fx.floor(), fy.floor()
-        tx, ty = fx - x0, fy - y0
-        ok = usable & (x0 >= 0) & (x0 <= W - 2) & (y0 >= 0) & (y0 <= H - 2)
-        zero = torch.zeros_like(x0)
-        at = torch.where(ok, y0, zero).long() * W + torch.where(ok, x0, zero).long()
-        src, last = self.img[sv].reshape(-1), H * W - 1
-        b00, b10 = src[at], src[(at + 1).clamp(max=last)]
-        b01, b11 = src[(at + W).clamp(max=last)], src[(at + W + 1).clamp(max=last)]
-        r0 = b00 + tx * (b10 - b00)
-        r1 = b01 + tx * (b11 - b01)
-        b = r0 + ty * (r1 - r0)
-        return torch.where(ok & torch.isfinite(b), b, torch.full_like(b, math.nan))
-
-    def score(self, r, py, px, d, n):
-        """THE PLANE SCORE of (d [N], n [N, 3]) at the pixels (px, py) (int64 [N]) of reference r -> float32 [N]"""
-        nan = torch.full(py.shape, math.nan, dtype=torch.float32, device=self.dev)
-        ref = self.reference(r)
-        if ref is None:
-            return nan
-        nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
-        gp = (nx * ref["xn"][px] + ny * ref["yn"][py]) + nz
-        ok = ref["pixel_ok"][py, px] & torch.isfinite(d) & (d > 0) & torch.isfinite(nx) & torch.isfinite(ny) & torch.isfinite(nz) & (gp < 0)
-        h = gp * d
-        a, pts = [], []
-        for dx, dy in self.offsets:
-            qx, qy = (px + dx).clamp(0, self.W - 1), (py + dy).clamp(0, self.H - 1)
-            xq, yq = ref["xn"][qx], ref["yn"][qy]
-            gq = (nx * xq + ny * yq) + nz
-            dq = h / gq
-            a.append(ref["img"][qy, qx])
-            pts.append((xq * dq, yq * dq, dq, (gq < 0) & torch.isfinite(dq)))
-        ma, va = ref["ma"][py, px], ref["va"][py, px]
-        total, count = torch.zeros_like(nan), torch.zeros(py.shape, dtype=torch.int64, device=self.dev)
-        for s, sv in enumerate(self.sources[r]):
-            if not 0 <= sv < self.V:
-                continue
-            b = [torch.where(tap_ok, self.sample(r, s, sv, X, Y, Z), nan) for X, Y, Z, tap_ok in pts]
-            sb = _tap_sum(b)
-            mb = sb / self.n
-            vb, cov = torch.zeros_like(sb), torch.zeros_like(sb)
-            for ai, bi in zip(a, b):
-                db = bi - mb
-                vb = vb + db * db
-                cov = cov + (ai - ma) * db
-            valid = ok & ~torch.isnan(sb) & ~(vb < self.min_var)
-            ncc = cov / _sqrt_rn(va * vb)
-            total = torch.where(valid, total + ncc, total)
-            count = count + valid
-        return torch.where(ok & (count >= self.min_sources), total / count.float(), nan)
 
 
 @torch.no_grad()

@@ -39,15 +39,29 @@ def taps(Z, w):
     return [pad[i:i + H, j:j + W] for i in range(2 * w + 1) for j in range(2 * w + 1)]
 
 
-def window(Z, w):
-    """per pixel: the taps, whether all are finite (False where the pixel has no window), their sum in tap order"""
+def window(Z, w, picked=None):
+    """per pixel of Z [H, W]: the window's taps (every one, or those at the places `picked` of taps), whether all are finite
+    (False where the pixel has no window), their sum in tap order"""
     t = taps(Z, w)
+    if picked is not None:
+        t = [t[i] for i in picked]
     total, finite = np.zeros(Z.shape, F32), np.ones(Z.shape, bool)
     for a in t:
         total = total + a
         finite &= np.isfinite(a)
     assert total.dtype == F32
     return t, finite, total
+
+
+def window_stats(Z, w, picked=None):
+    """step 1 per pixel of the reference Z: the taps a, whether all are finite, ma and va over them"""
+    a, finite, sa = window(Z, w, picked)
+    ma = sa / F32(len(a))
+    va = np.zeros(Z.shape, F32)
+    for t in a:
+        va = va + (t - ma) * (t - ma)
+    assert va.dtype == F32
+    return a, finite, ma, va
 
 
 def lift(k4, H, W):
@@ -59,12 +73,11 @@ def lift(k4, H, W):
     return xn[None, :], yn[:, None]
 
 
-def warp_sample(src, P, k4, xn, yn, d, near, stats=None):
-    """steps 2 and 3 for every pixel of the reference as a tap: b float32 [H, W] and its validity"""
+def sample(src, P, k4, X, Y, Z, near, stats=None):
+    """steps 2 and 3 for the camera points (X, Y, Z) of the reference, float32 [N] each: b float32 [N], NaN where not valid"""
     H, W = src.shape
-    X = np.broadcast_to(xn * d, (H, W)).reshape(-1)
-    Y = np.broadcast_to(yn * d, (H, W)).reshape(-1)
-    Z = np.full(H * W, d, F32)
+    if H < 2 or W < 2:
+        return np.full(len(X), NAN, F32)
     cz, u, v, usable = R.project(np.stack([X, Y, Z], axis=1), P, k4, near)
     x, y = u - F32(0.5), v - F32(0.5)
     x0, y0 = np.floor(x), np.floor(y)
@@ -72,10 +85,7 @@ def warp_sample(src, P, k4, xn, yn, d, near, stats=None):
     inside = (x0 >= 0) & (x0 <= F32(W - 2)) & (y0 >= 0) & (y0 <= F32(H - 2))
     ok = usable & inside
     ix, iy = np.where(ok, x0, 0).astype(np.int64), np.where(ok, y0, 0).astype(np.int64)
-    if H < 2 or W < 2:
-        return np.full((H, W), NAN, F32), np.zeros((H, W), bool)
-    b00, b10, b01, b11 = src[iy, ix], src[iy, np.minimum(ix + 1, W - 1)], src[np.minimum(iy + 1, H - 1), ix], \
-        src[np.minimum(iy + 1, H - 1), np.minimum(ix + 1, W - 1)]
+    b00, b10, b01, b11 = src[iy, ix], src[iy, ix + 1], src[iy + 1, ix], src[iy + 1, ix + 1]
     r0 = b00 + tx * (b10 - b00)
     r1 = b01 + tx * (b11 - b01)
     b = r0 + ty * (r1 - r0)
@@ -95,7 +105,15 @@ def warp_sample(src, P, k4, xn, yn, d, near, stats=None):
         note("plane behind the source", cz < 0)
         note("c_z is NaN", np.isnan(cz))
         note("source sample not finite", ok & ~np.isfinite(b))
-    return np.where(ok, b, NAN).reshape(H, W), ok.reshape(H, W)
+    return np.where(ok & np.isfinite(b), b, NAN)
+
+
+def warp_sample(src, P, k4, xn, yn, d, near, stats=None):
+    """steps 2 and 3 for every pixel of the reference as a tap on the fronto-parallel plane d: b float32 [H, W]"""
+    H, W = src.shape
+    X = np.broadcast_to(xn * d, (H, W)).reshape(-1)
+    Y = np.broadcast_to(yn * d, (H, W)).reshape(-1)
+    return sample(src, P, k4, X, Y, np.full(H * W, d, F32), near, stats).reshape(H, W)
 
 
 def sweep(images, poses, intr, sources, depths, refs=None, half_width=3, near=1e-3, min_var=1e-6, min_sources=1, stats=None,
@@ -124,12 +142,8 @@ def sweep(images, poses, intr, sources, depths, refs=None, half_width=3, near=1e
             if not 0 <= rv < V:
                 continue
             # 1. reference window
-            a, a_finite, sa = window(img[rv], w)
+            a, a_finite, ma, va = window_stats(img[rv], w)
             assert not (a_finite & ~has_window).any()
-            ma = sa / n
-            va = np.zeros((H, W), F32)
-            for t in a:
-                va = va + (t - ma) * (t - ma)
             pixel_ok = has_window & a_finite & ~(va < mv)
             if note:
                 note("reference tap not finite", has_window & ~a_finite)
@@ -149,7 +163,7 @@ def sweep(images, poses, intr, sources, depths, refs=None, half_width=3, near=1e
                     if note:
                         note("a view is reference and source", np.isin(sv, refs))
                     # 2. warp, 3. sample
-                    b, _ = warp_sample(img[sv], rel[r, s], k4[sv], xn, yn, d, near, stats)
+                    b = warp_sample(img[sv], rel[r, s], k4[sv], xn, yn, d, near, stats)
                     # 4. NCC
                     bt, b_finite, sb = window(b, w)
                     mb = sb / n

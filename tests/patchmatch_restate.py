@@ -1,7 +1,7 @@
 """THE PLANE SCORE and THE PATCHMATCH STEP of include/ls2fm.h (ls2fm_mvs_plane_score, ls2fm_mvs_patchmatch_step) restated in plain
 numpy for this project: float32 arrays over a set of pixels of one reference view, the references, candidates, sources and window
-taps in loops, so that every fp32 operation rounds once, in the order the header gives.  The lift, the relative poses and the
-window's tap order are mvs_restate's, the camera point, projection and usable rule raster_restate's.  Test infrastructure only."""
+taps in loops, so that every fp32 operation rounds once, in the order the header gives.  The lift, the relative poses, the
+window's sums and the sample of a camera point are mvs_restate's, the camera point, projection and usable rule raster_restate's.  Test infrastructure only."""
 import numpy as np
 
 import mvs_restate as MR
@@ -79,17 +79,7 @@ class Scene:
                 self.per_ref[r] = None
                 return None
             with np.errstate(all="ignore"):
-                every = MR.taps(self.img[rv], self.w)
-                a = [every[i] for i in self.picked]
-                total, finite = np.zeros((self.H, self.W), F32), np.ones((self.H, self.W), bool)
-                for t in a:
-                    total = total + t
-                    finite &= np.isfinite(t)
-                ma = total / self.n
-                va = np.zeros((self.H, self.W), F32)
-                for t in a:
-                    va = va + (t - ma) * (t - ma)
-                assert va.dtype == F32
+                _, finite, ma, va = MR.window_stats(self.img[rv], self.w, self.picked)
                 xn, yn = MR.lift(self.k4[rv], self.H, self.W)
             self.per_ref[r] = dict(rv=rv, xn=xn[0], yn=yn[:, 0], ma=ma, va=va, pixel_ok=self.has_window & finite & ~(va < self.mv))
         return self.per_ref[r]
@@ -99,25 +89,6 @@ def _note(stats):
     if stats is None:
         return lambda name, m: None
     return lambda name, m: stats.__setitem__(name, stats.get(name, 0) + int(np.count_nonzero(m)))
-
-
-def sample(src, P, k4, X, Y, Z, near):
-    """steps 2 and 3 of THE SWEEP RULE for the camera points (X, Y, Z) of the reference: b float32 [N], NaN where not valid"""
-    H, W = src.shape
-    cz, u, v, usable = R.project(np.stack([X, Y, Z], axis=1), P, k4, near)
-    x, y = u - F32(0.5), v - F32(0.5)
-    x0, y0 = np.floor(x), np.floor(y)
-    tx, ty = x - x0, y - y0
-    ok = usable & (x0 >= 0) & (x0 <= F32(W - 2)) & (y0 >= 0) & (y0 <= F32(H - 2))
-    if H < 2 or W < 2:
-        return np.full(len(X), NAN, F32)
-    ix, iy = np.where(ok, x0, 0).astype(np.int64), np.where(ok, y0, 0).astype(np.int64)
-    b00, b10, b01, b11 = src[iy, ix], src[iy, ix + 1], src[iy + 1, ix], src[iy + 1, ix + 1]
-    r0 = b00 + tx * (b10 - b00)
-    r1 = b01 + tx * (b11 - b01)
-    b = r0 + ty * (r1 - r0)
-    assert b.dtype == F32 and tx.dtype == F32
-    return np.where(ok & np.isfinite(b), b, NAN)
 
 
 # --------------------------------------------------------------------------------------------------------------- THE PLANE SCORE
@@ -162,7 +133,7 @@ def score_pixels(sc, r, py, px, d, n, stats=None):
             sv = int(sc.sources[r, s])
             if not 0 <= sv < sc.V:
                 continue
-            b = [np.where(tap_ok, sample(sc.img[sv], sc.rel[r, s], sc.k4[sv], X, Y, Z, sc.near), NAN) for X, Y, Z, tap_ok in pts]
+            b = [np.where(tap_ok, MR.sample(sc.img[sv], sc.rel[r, s], sc.k4[sv], X, Y, Z, sc.near), NAN) for X, Y, Z, tap_ok in pts]
             sb, finite = np.zeros(N, F32), np.ones(N, bool)
             for bi in b:
                 sb = sb + bi

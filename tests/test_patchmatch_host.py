@@ -259,6 +259,24 @@ def test_the_torch_forms_on_the_cpu_leave_the_restatement_s_bits(H, W, w, t, nan
             assert same_bits(g.numpy(), r)
 
 
+@pytest.mark.parametrize("H,W,w", [(4, 5, 2), (17, 33, 2)])
+def test_the_torch_sweep_and_the_torch_plane_score_share_one_scene(H, W, w):
+    """both torch forms run on one scene object: at one plane, n = (0, 0, -1) and t = 1 the sweep's score is the plane score by
+    its bits, at an image smaller than the window (no pixel has one) and at one above the tiles"""
+    import torch
+    from ls2fm import mvs
+    sc = S.grid_scene(H, W, w, D=1)
+    v = tuple(_torch(sc[k]) for k in ("images", "poses", "intr", "sources"))
+    refs, depths = _torch(sc["refs"]), _torch(sc["depths"])
+    swept = mvs.plane_sweep_torch(*v, depths, refs=refs, **sweep_kw(sc))[1]
+    normal = torch.zeros(len(refs), H, W, 3)
+    normal[..., 2] = -1
+    scored = mvs.plane_score_torch(*v, depths[:, 0, None, None].expand(-1, H, W), normal, refs=refs, tap_step=1, **sweep_kw(sc))
+    assert same_bits(swept.numpy(), scored.numpy())
+    assert np.isnan(swept.numpy()).all() if H < 2 * w + 1 else np.isfinite(swept.numpy()).any()
+    assert same_bits(swept.numpy(), MR.sweep(sc["images"], sc["poses"], sc["intr"], sc["sources"], sc["depths"], refs=sc["refs"], **sweep_kw(sc))[1])
+
+
 def test_normals_to_world_against_numpy():
     import torch
     from ls2fm import mvs
