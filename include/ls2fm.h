@@ -1943,6 +1943,67 @@ int ls2fm_mvs_patchmatch_step(const float* images, int32_t n_views, int32_t heig
                               const float* d_max, float* depth, float* normal, float* score, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fusion of per-view depth and normal maps into one oriented, coloured cloud (csrc/mvs_fuse.hip behind ls2fm.mvs.fuse_depths;
+ * additions, the library stays ABI 13): COLMAP's stereo_fusion, the stage between patch_match_stereo and poisson_mesher.
+ * tests/fuse_restate.py repeats the rule in numpy, ls2fm.mvs.fuse_depths_torch as torch ops; the three agree bit for bit.
+ *
+ * Conventions are those of THE CONSISTENCY RULE.  Inputs: depth float [V][H][W], meant to be ls2fm_mvs_filter's output (any value
+ * that is not finite and positive is "no depth"); normal float [V][H][W][3] in each camera's frame, of any length, or NULL; colour
+ * float [V][H][W][C], C in [1, 4], or NULL with C = 0; sources int32 [V][S], rel = P_rs, rel_back = P_sr, intr, near, max_reproj
+ * and rel_depth exactly as ls2fm_mvs_filter takes them; cos2 in [0, 1], the squared cosine of the largest angle between the normals
+ * of a pixel and a partner, formed by the caller; cam_to_world float [V][3][4] = P_v^-1, formed in fp64 and rounded once by the
+ * caller; a range of views [view_begin, view_end).
+ * THE FUSION RULE, per view r of the range and pixel (px, py) whose depth d is finite and positive:
+ *   1. partners   each source s in order; an entry outside [0, V) and an entry equal to r are skipped, a view listed twice counts
+ *      twice.  Steps 1 to 7 of THE CONSISTENCY RULE, unchanged, give the partner pixel (sx, sy) of view s with its depth d_s, and
+ *      whether it is consistent.  With normals it must pass one more test: with n_r the pixel's normal, n_s the partner pixel's and
+ *      B = P_sr, n'_i = ((B_i0 n_sx) + (B_i1 n_sy)) + B_i2 n_sz;  a = ((n_rx n'_x) + (n_ry n'_y)) + n_rz n'_z;  rr = ((n_rx n_rx) +
+ *      (n_ry n_ry)) + n_rz n_rz, ss likewise of n'; consistent only if a > 0 and a a >= cos2 (rr ss).  Every operation is one
+ *      rounded fp32 operation, none contracted; every comparison is false for a NaN.
+ *   2. ownership   the pixel gives a point iff no consistent partner has a view index below r.  support = 1 + the number of
+ *      consistent partners for a pixel that gives a point and 0 for every other pixel.  The maps are filtered already, so a consistent
+ *      partner pixel is one that itself survived: a surface element seen by several views is emitted by the lowest of them and the
+ *      others are folded into its mean -- no visited mask, no atomics, no dependence on an order.
+ *   3. the point   the mean over the contributors: the pixel itself, then its consistent partners in source order.  A contributor's
+ *      camera point (X, Y, d) is that of its own pixel centre, the fp32 values of step 1 (the pixel) or 5 (a partner) of THE
+ *      CONSISTENCY RULE.  With M = cam_to_world of the contributor's own view, in fp64 of the fp32 values and never contracted:
+ *      w_i = ((M_i0 X + M_i1 Y) + M_i2 d) + M_i3.  The sums start at +0; point_i = (float) (sum_i / (double) support).
+ *      The normal: per contributor g_i = (M_i0 n_x + M_i1 n_y) + M_i2 n_z in fp64, l = sqrt((g_0 g_0 + g_1 g_1) + g_2 g_2), the
+ *      unit vector g_i / l; their sum t in the same order; normal_i = (float) (t_i / sqrt((t_0 t_0 + t_1 t_1) + t_2 t_2)).  A zero
+ *      or NaN sum gives a NaN normal in its own row and nothing else.  Division and root are correctly rounded.  A normal that faces
+ *      its camera keeps facing it: M's rotation is R^T, as in ls2fm.mvs.normals_to_world.
+ *      The colour: per channel the fp64 sum of the contributors' own pixels, divided by (double) support and rounded once.
+ * Outputs: support uint8 [V][H][W], written for the views of the range only; rows in (view, py, px) order: points float [M][3],
+ * normals float [M][3] (with normals), colours float [M][C] (with colours), pixel int64 [M] = (v H + py) W + px of the owner.
+ * Deviations from COLMAP's stereo_fusion, on purpose: a mean, not a median; partners come from the source lists alone, there is no
+ * traversal beyond one hop; the nearest pixel, not an interpolated one; no min_num_pixels inside the rule, the caller thresholds
+ * support; near-duplicates remain where consistency is not mutual.
+ *
+ * ls2fm_mvs_fuse_mark writes support.  The caller forms row int64 [view_end - view_begin][H][W], the exclusive prefix sum of
+ * support > 0 over the pixels of the range in (view, py, px) order plus the number of rows of the views before the range, and
+ * ls2fm_mvs_fuse_emit repeats the walk of every pixel with support > 0 and writes its row; a row outside [0, n_rows) is not
+ * written.  Both: one launch, one lane per pixel, a workgroup of 256 lanes takes one tile of LS2FM_MVS_FUSE_TILE_W x
+ * LS2FM_MVS_FUSE_TILE_H pixels of one view (a wave is two rows of 32 pixels), no workspace, no atomics, nothing read back, no stream forked; they can be captured, a rerun or a replay repeats the bits, and the view ranges of several
+ * calls leave the bits of one.  n_views = 0, an empty range and (emit) n_rows = 0 return at once.  Refused before anything is
+ * enqueued (LS2FM_ERR_INVALID_ARGUMENT): what ls2fm_mvs_filter refuses of the arguments they share, a NULL array, normals without
+ * normal (emit) or the reverse, colours without colour or the reverse, C outside [1, 4] with colour or not 0 without, a view range
+ * outside [0, V] or with its end before its begin, cos2 outside [0, 1] or not finite, a negative n_rows, 2^31 workgroups or more.
+ */
+#define LS2FM_MVS_FUSE_MAX_CHANNELS 4
+#define LS2FM_MVS_FUSE_TILE_W 32
+#define LS2FM_MVS_FUSE_TILE_H 8
+int ls2fm_mvs_fuse_mark(const float* depth, const float* normal, int32_t n_views, int32_t height, int32_t width,
+                        const int32_t* sources, int32_t n_sources, const float* rel, const float* rel_back, const float* intr,
+                        float near, float max_reproj, float rel_depth, float cos2, int32_t view_begin, int32_t view_end,
+                        uint8_t* support, void* stream);
+int ls2fm_mvs_fuse_emit(const float* depth, const float* normal, const float* colour, int32_t n_channels, int32_t n_views,
+                        int32_t height, int32_t width, const int32_t* sources, int32_t n_sources, const float* rel,
+                        const float* rel_back, const float* intr, const float* cam_to_world, float near, float max_reproj,
+                        float rel_depth, float cos2, int32_t view_begin, int32_t view_end, const uint8_t* support,
+                        const int64_t* row, int64_t n_rows, float* points, float* normals, float* colours, int64_t* pixel,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

@@ -280,6 +280,10 @@ _SIGNATURES = {
     "ls2fm_mvs_patchmatch_step": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, c_int32, c_int32, c_float,
                                             c_float, c_int32, c_int32, c_int32, ctypes.c_uint32, c_float, c_float, c_float, _P, _P, _P, _P,
                                             _P, _P]),
+    "ls2fm_mvs_fuse_mark": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, c_float, c_float, c_float,
+                                      c_int32, c_int32, _P, _P]),
+    "ls2fm_mvs_fuse_emit": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, c_float, c_float,
+                                      c_float, c_float, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),

@@ -10,15 +10,20 @@
                   propagation and random refinement, in place on the state (depth, normal, score)
   patch_match     a coarse plane_sweep (or a caller's state) refined by `iterations` red-black sweeps -> depth, normal, score
   normals_to_world   camera-frame normal maps into the poses' world frame, elementwise
+  fuse_depths     the depth (and normal) maps of all views as one deduplicated, oriented, coloured cloud -> FusedCloud
+                  (ls2fm_mvs_fuse_mark, ls2fm_mvs_fuse_emit, csrc/mvs_fuse.hip; COLMAP's stereo_fusion): a pixel gives a point
+                  unless a lower view holds a consistent partner of it, and the point is the mean over its consistent partners
   dense_reconstruct   plane_sweep or patch_match -> filter_depths -> fusion.volume_for -> fusion.integrate -> fusion.extract: the
                   classical dense baseline row of the neural-surface tables (COLMAP's patch_match_stereo and stereo_fusion); its
-                  mesh goes into ls2fm.mesh_colors.photo_colors and ls2fm.metrics.evaluate_mesh as it stands
-  plane_sweep_torch, filter_depths_torch, plane_score_torch, patch_match_step_torch   the same rules as separate torch ops, on
-                  CPU tensors as well: the checks of the kernels and the timing baselines (tools/time_mvs.py,
-                  tools/time_patchmatch.py); nothing in the library falls back to them
+                  mesh goes into ls2fm.mesh_colors.photo_colors and ls2fm.metrics.evaluate_mesh as it stands.  With
+                  surface="poisson" or "mls": filter_depths -> fuse_depths -> ls2fm.cloud_mesh.mesh_from_cloud instead of the volume
+  plane_sweep_torch, filter_depths_torch, plane_score_torch, patch_match_step_torch, fuse_depths_torch   the same rules as separate
+                  torch ops, on CPU tensors as well: the checks of the kernels and the timing baselines (tools/time_mvs.py,
+                  tools/time_patchmatch.py, tools/time_fuse.py); nothing in the library falls back to them
 
-THE SWEEP RULE, THE CONSISTENCY RULE, THE PLANE SCORE and THE PATCHMATCH STEP are stated in include/ls2fm.h and restated in numpy
-in tests/mvs_restate.py and tests/patchmatch_restate.py; the kernels, the torch forms and the restatements agree bit for bit.  Conventions are the rasteriser's (ls2fm.raster.rasterize): poses world ->
+THE SWEEP RULE, THE CONSISTENCY RULE, THE PLANE SCORE, THE PATCHMATCH STEP and THE FUSION RULE are stated in include/ls2fm.h and
+restated in numpy in tests/mvs_restate.py, tests/patchmatch_restate.py and tests/fuse_restate.py; the kernels, the torch forms and
+the restatements agree bit for bit.  Conventions are the rasteriser's (ls2fm.raster.rasterize): poses world ->
 camera [V, 3, 4], intr [3, 3] or [V, 3, 3], pixel (px, py) has its centre at px + 0.5, depth is camera z.  All views of a call
 share one image size.  Each kernel call is one launch without host read or atomics: it can be captured, a rerun repeats its bits,
 and the chunking of the reference views does not show in them.
@@ -27,7 +32,10 @@ Deviations of plane_sweep from COLMAP's dense stage, on purpose: the planes are 
 normals) and every pixel tries every plane (no propagation) -- patch_match lifts both.  Deviations of both: the score of a plane
 is the mean NCC over the valid sources, not the best K of them or a per-pixel view selection; the window's taps weigh the same (no
 bilateral weights); the cost holds no geometric-consistency term (filter_depths runs afterwards); one scale and one image size per
-call; grey images only; no gradients.
+call; grey images only; no gradients.  Deviations of fuse_depths from COLMAP's stereo_fusion: a mean over the contributors, not a
+median; the partners of a pixel come from its view's source list alone, no traversal beyond one hop; the nearest pixel of a
+partner, not an interpolated one; no min_num_pixels inside the rule (min_support thresholds afterwards); near-duplicates remain
+where consistency is not mutual.  fuse_depths makes one host read, the row count.
 
 There is no CPU path for the kernels: CPU tensors, a missing device or a missing library raise, as in ls2fm.fusion.
 """
@@ -49,6 +57,8 @@ MAX_PLANES = 65536          # LS2FM_MVS_MAX_PLANES
 PM_TILE_H, PM_TILE_W = 16, 32   # LS2FM_MVS_PM_TILE_H, LS2FM_MVS_PM_TILE_W
 PM_DRAWS = 9                # LS2FM_MVS_PM_DRAWS
 MIX_A, MIX_B, MIX_SALT = 0x21F0AAAD, 0x735A2D97, 0x9E3779B9    # LS2FM_MVS_MIX_A, LS2FM_MVS_MIX_B, LS2FM_MVS_MIX_SALT
+FUSE_MAX_CHANNELS = 4       # LS2FM_MVS_FUSE_MAX_CHANNELS
+FUSE_TILE_W, FUSE_TILE_H = 32, 8    # LS2FM_MVS_FUSE_TILE_W, LS2FM_MVS_FUSE_TILE_H
 NEIGHBOURS = ((0, -1), (-1, 0), (1, 0), (0, 1), (0, -3), (-3, 0), (3, 0), (0, 3))     # (dx, dy), THE PATCHMATCH STEP's order
 _device = functools.partial(_lib.require_device_tensors, "ls2fm.mvs", phrase=": multi-view stereo runs on MI355X only")
 
@@ -77,6 +87,8 @@ class MvsOptions:
     max_slope: float = 1.0
     tap_step: int = 1
     patchmatch_planes: int = 32     # the planes of the initial sweep when dense_reconstruct forms them
+    max_normal_angle: float = 60.0  # degrees: fuse_depths (dense_reconstruct with surface="poisson" or "mls")
+    min_support: int = 1
 
     def patchmatch(self):
         return dict(self.sweep(), iterations=self.iterations, seed=self.seed, depth_perturb=self.depth_perturb,
@@ -88,6 +100,10 @@ class MvsOptions:
 
     def filter(self):
         return dict(near=self.near, max_reproj=self.max_reproj, rel_depth=self.rel_depth, min_consistent=self.min_consistent)
+
+    def fuse(self):
+        return dict(near=self.near, max_reproj=self.max_reproj, rel_depth=self.rel_depth, max_normal_angle=self.max_normal_angle,
+                    min_support=self.min_support, max_workspace_bytes=self.max_workspace_bytes)
 
 
 # --------------------------------------------------------------------------------------------------------- inputs, as torch ops
@@ -355,6 +371,140 @@ def filter_depths(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, rel_dep
         check(_lib.load().ls2fm_mvs_filter(ptr(d), V, H, W, ptr(sources), S, ptr(rel), ptr(back), ptr(k4), near, max_reproj, rel_depth,
                                            min_consistent, ptr(count), ptr(out), stream_ptr()), "ls2fm_mvs_filter")
     return out, count
+
+
+# ------------------------------------------------------------------------------------------------------------------------ fusion
+@dataclasses.dataclass
+class FusedCloud:
+    """What fuse_depths returns: M rows in (view, py, px) order of their owners."""
+    points: torch.Tensor            # float32 [M, 3], world
+    normals: torch.Tensor           # float32 [M, 3], world, of unit length, toward the cameras; None without normal maps
+    colors: torch.Tensor            # float32 [M, C]; None without images
+    support: torch.Tensor           # uint8 [M]: 1 + the consistent partners folded into the row
+    view: torch.Tensor              # int64 [M]: the owner's view
+    pixel: torch.Tensor             # int64 [M]: (view H + py) W + px of the owner
+    centers: torch.Tensor           # float32 [M, 3]: the owner's camera centre (estimate_normals' `toward`)
+
+
+def cam_to_world(pose):
+    """P^-1 per view -> float32 [V, 3, 4]: formed in fp64 with elementwise torch ops in relative_poses' order (the identity
+    composed with P^-1) on the pose's device and rounded once; its last column is the camera centre."""
+    P = torch.as_tensor(pose).detach().reshape(-1, 3, 4).double()
+    eye = torch.eye(3, 4, dtype=torch.float64, device=P.device).expand(P.shape)
+    return _compose(eye, P).float().contiguous()
+
+
+def _check_fuse(max_normal_angle, min_support, max_reproj, rel_depth, S, who):
+    """-> max_reproj, rel_depth, cos2 (fp64; the float argument of the call, or the float32 tensor of the torch form, rounds it
+    once), min_support"""
+    max_reproj, rel_depth, _ = _check_filter(max_reproj, rel_depth, 0, S, who)
+    angle, min_support = float(max_normal_angle), int(min_support)
+    if not 0.0 <= angle <= 90.0:
+        raise ValueError(f"{who}: max_normal_angle {angle} must be in [0, 90] degrees")
+    if min_support < 1:
+        raise ValueError(f"{who}: min_support {min_support} must be at least 1 (the pixel itself)")
+    return max_reproj, rel_depth, math.cos(math.radians(angle)) ** 2, min_support
+
+
+def _fuse_maps(normal, images, V, H, W, dev, who):
+    """the optional maps as contiguous float32 [V, H, W, 3] and [V, H, W, C] on dev, or None"""
+    if normal is not None:
+        normal = torch.as_tensor(normal)
+        if tuple(normal.shape) != (V, H, W, 3):
+            raise ValueError(f"{who}: normal must be [{V}, {H}, {W}, 3], got {tuple(normal.shape)}")
+        normal = _lib.cf(normal.detach())
+    if images is not None:
+        images = torch.as_tensor(images)
+        if images.dim() == 3:
+            images = images[..., None]
+        if images.dim() != 4 or tuple(images.shape[:3]) != (V, H, W) or not 1 <= images.shape[3] <= FUSE_MAX_CHANNELS:
+            raise ValueError(f"{who}: images must be [{V}, {H}, {W}] or [{V}, {H}, {W}, C] with C in 1 .. {FUSE_MAX_CHANNELS}, got "
+                             f"{tuple(images.shape)}")
+        images = _lib.cf(images.detach())
+    for name, t in (("normal", normal), ("images", images)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: the poses on {dev}, {name} on {t.device}")
+    return normal, images
+
+
+def _no_cloud(normal, colour, dev):
+    """the FusedCloud of no views"""
+    rows = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+    return FusedCloud(rows(0, 3), None if normal is None else rows(0, 3), None if colour is None else rows(0, int(colour.shape[3])),
+                      rows(0, dtype=torch.uint8), rows(0, dtype=torch.int64), rows(0, dtype=torch.int64), rows(0, 3))
+
+
+def _fused_cloud(points, normals, colours, support, pixel, to_world, H, W, min_support):
+    """the rows as a FusedCloud, those with support >= min_support (torch ops)"""
+    if min_support > 1:
+        keep = support >= min_support
+        points, support, pixel = points[keep], support[keep], pixel[keep]
+        normals = None if normals is None else normals[keep]
+        colours = None if colours is None else colours[keep]
+    view = torch.div(pixel, H * W, rounding_mode="floor")
+    return FusedCloud(points, normals, colours, support, view, pixel, to_world[:, :, 3][view])
+
+
+@torch.no_grad()
+def fuse_depths(depth, pose, intr, sources, normal=None, images=None, near=1e-3, max_reproj=1.0, rel_depth=0.01, max_normal_angle=60.0,
+                min_support=1, max_workspace_bytes=2 ** 28):
+    """THE FUSION RULE of include/ls2fm.h -> FusedCloud: the depth (and normal) maps of all views as one deduplicated, oriented,
+    coloured cloud in the poses' world frame.  A pixel with a depth gives a point unless a lower view holds a consistent partner of
+    it; the point, normal and colour are the means over the pixel and its consistent partners.
+      depth      float32 [V, H, W], filter_depths' output: pixels that are not finite and positive give nothing
+      sources    int [V, S]; -1 skips; the partners of a pixel come from its view's row alone
+      normal     float [V, H, W, 3] in each camera's frame (patch_match's), any length; a partner whose normal is further than
+                 max_normal_angle degrees from the pixel's is not consistent.  None: no normal test, FusedCloud.normals is None
+      images     float [V, H, W, C] or [V, H, W], C in 1 .. 4: the colours to average.  None: FusedCloud.colors is None
+      min_support   rows with a lower support are dropped afterwards, with torch ops
+    The views go in chunks whose workspace (the row index and its prefix sum, 24 bytes per pixel) stays within max_workspace_bytes:
+    ls2fm_mvs_fuse_mark per chunk, the row count (the one host read), then torch's prefix sum and ls2fm_mvs_fuse_emit per chunk;
+    the chunking does not show in the bits."""
+    who = "ls2fm.mvs.fuse_depths"
+    depth, poses, k4 = _device_views(depth, pose, intr, who)
+    V, dev = int(poses.shape[0]), poses.device
+    d = _grey(depth, V, who)
+    refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
+    S, H, W = int(sources.shape[1]), int(d.shape[1]), int(d.shape[2])
+    max_reproj, rel_depth, cos2, min_support = _check_fuse(max_normal_angle, min_support, max_reproj, rel_depth, S, who)
+    near = _posed.near_plane(near, who)
+    if d.device != dev:
+        raise ValueError(f"{who}: the poses on {dev}, the depth maps on {d.device}")
+    for name, t in (("normal", normal), ("images", images)):
+        if t is not None:
+            _device(torch.as_tensor(t))
+    normal, colour = _fuse_maps(normal, images, V, H, W, dev, who)
+    C = 0 if colour is None else int(colour.shape[3])
+    if V == 0:
+        return _no_cloud(normal, colour, dev)
+    rel, back = relative_poses(poses, refs, sources), relative_poses(poses, refs, sources, back=True)
+    to_world = cam_to_world(poses)
+    support = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    shared = (ptr(sources), S, ptr(rel), ptr(back), ptr(k4))
+    chunks = _posed.chunks(V, 24, H, W, max_workspace_bytes)
+    with torch.cuda.device(dev):
+        for s, e in chunks:
+            check(lib.ls2fm_mvs_fuse_mark(ptr(d), ptr(normal), V, H, W, *shared, near, max_reproj, rel_depth, cos2, s, e, ptr(support),
+                                          stream_ptr()), "ls2fm_mvs_fuse_mark")
+        per_view = (support > 0).reshape(V, -1).sum(dim=1)
+        before = per_view.cumsum(dim=0) - per_view                      # int64 [V]: the rows of the views before each
+        M = int(per_view.sum()) if V else 0                             # the one host read
+        points = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        normals = None if normal is None else torch.empty((M, 3), dtype=torch.float32, device=dev)
+        colours = None if colour is None else torch.empty((M, C), dtype=torch.float32, device=dev)
+        pixel = torch.empty((M,), dtype=torch.int64, device=dev)
+        for s, e in chunks if M else ():
+            gives = support[s:e].reshape(-1).clamp(max=1)
+            row = gives.cumsum(dim=0, dtype=torch.int64)                # made exclusive and global in place
+            row -= gives
+            row += before[s]
+            check(lib.ls2fm_mvs_fuse_emit(ptr(d), ptr(normal), ptr(colour), C, V, H, W, *shared, ptr(to_world), near, max_reproj,
+                                          rel_depth, cos2, s, e, ptr(support), ptr(row), M, ptr(points), ptr(normals), ptr(colours),
+                                          ptr(pixel), stream_ptr()), "ls2fm_mvs_fuse_emit")
+            del gives, row
+    rows = support.reshape(-1)[pixel]
+    return _fused_cloud(points, normals, colours, rows, pixel, to_world, H, W, min_support)
 
 
 # -------------------------------------------------------------------------------------------------------------------- PatchMatch
@@ -720,6 +870,106 @@ def filter_depths_torch(depth, pose, intr, sources, near=1e-3, max_reproj=1.0, r
     return out.reshape(V, H, W), count.to(torch.uint8).reshape(V, H, W)
 
 
+def _dot3(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+@torch.no_grad()
+def fuse_depths_torch(depth, pose, intr, sources, normal=None, images=None, near=1e-3, max_reproj=1.0, rel_depth=0.01,
+                      max_normal_angle=60.0, min_support=1):
+    """THE FUSION RULE as plain torch ops on the depth maps' device (a CPU works), vectorised over the pixels of one view: the walk
+    in float32, the sums in float64, each operation a separate op.  Reads `sources` and the owners on the host.  -> FusedCloud as
+    fuse_depths."""
+    who = "ls2fm.mvs.fuse_depths_torch"
+    depth, P, K = _torch_views(depth, pose, intr)
+    V, dev = int(P.shape[0]), depth.device
+    depth = _grey(depth, V, who)
+    refs, sources, _ = _index_arrays(None, sources, None, V, dev, who)
+    S, H, W = int(sources.shape[1]), int(depth.shape[1]), int(depth.shape[2])
+    max_reproj, rel_depth, cos2, min_support = _check_fuse(max_normal_angle, min_support, max_reproj, rel_depth, S, who)
+    normal, colour = _fuse_maps(normal, images, V, H, W, dev, who)
+    if V == 0:
+        return _no_cloud(normal, colour, dev)
+    rel, back = relative_poses(P, refs, sources), relative_poses(P, refs, sources, back=True)
+    to_world = cam_to_world(P)
+    M64 = to_world.double()
+    scalar = functools.partial(_scalar, dev=dev)
+    near, max_reproj, rel_depth, cos2 = scalar(_posed.near_plane(near, who)), scalar(max_reproj), scalar(rel_depth), scalar(cos2)
+    reproj2 = max_reproj * max_reproj
+    centre = lambda n: torch.arange(n, device=dev).float() + 0.5
+    uc, vc = centre(W)[None, :].expand(H, W).reshape(-1), centre(H)[:, None].expand(H, W).reshape(-1)
+    flat = depth.reshape(V, -1)
+    nflat = None if normal is None else normal.reshape(V, H * W, 3)
+    cflat = None if colour is None else colour.reshape(V, H * W, -1)
+
+    def world(v, X, Y, d):
+        m, X, Y, d = M64[v], X.double(), Y.double(), d.double()
+        return [((m[i, 0] * X + m[i, 1] * Y) + m[i, 2] * d) + m[i, 3] for i in range(3)]
+
+    def unit(v, n):
+        m, n = M64[v], n.double()
+        g = [(m[i, 0] * n[:, 0] + m[i, 1] * n[:, 1]) + m[i, 2] * n[:, 2] for i in range(3)]
+        length = torch.sqrt(_dot3(g, g))
+        return [gi / length for gi in g]
+
+    rows = dict(points=[], normals=[], colours=[], support=[], pixel=[])
+    for r, srcs in enumerate(sources.tolist()):
+        d = flat[r]
+        has = torch.isfinite(d) & (d > 0)
+        X, Y = ((uc - K[r, 0, 2]) / K[r, 0, 0]) * d, ((vc - K[r, 1, 2]) / K[r, 1, 1]) * d
+        dz = rel_depth * d
+        count, lower = torch.zeros(H * W, dtype=torch.int64, device=dev), torch.zeros(H * W, dtype=torch.bool, device=dev)
+        point = [torch.zeros(H * W, dtype=torch.float64, device=dev) + w for w in world(r, X, Y, d)]
+        if nflat is not None:
+            nr = [nflat[r][:, j] for j in range(3)]
+            rr = _dot3(nr, nr)
+            nsum = [torch.zeros(H * W, dtype=torch.float64, device=dev) + g for g in unit(r, nflat[r])]
+        if cflat is not None:
+            csum = torch.zeros_like(cflat[r], dtype=torch.float64) + cflat[r].double()
+        for s, sv in enumerate(srcs):
+            if not 0 <= sv < V or sv == r:
+                continue
+            _, _, _, _, ok, sx, sy = _posed.project_torch(rel[r, s], K[sv], X, Y, d, near, H, W)
+            at = sy * W + sx
+            ds = flat[sv][at]
+            ok = has & ok & torch.isfinite(ds) & (ds > 0)
+            Xs = (((sx.float() + 0.5) - K[sv, 0, 2]) / K[sv, 0, 0]) * ds
+            Ys = (((sy.float() + 0.5) - K[sv, 1, 2]) / K[sv, 1, 1]) * ds
+            c, u, v, usable, _, _, _ = _posed.project_torch(back[r, s], K[r], Xs, Ys, ds, near, H, W)
+            du, dv = u - uc, v - vc
+            e = du * du + dv * dv
+            good = ok & usable & (e <= reproj2) & ((c[2] - d).abs() <= dz)
+            if nflat is not None:
+                ns, B = nflat[sv][at], back[r, s]
+                turned = [(B[i, 0] * ns[:, 0] + B[i, 1] * ns[:, 1]) + B[i, 2] * ns[:, 2] for i in range(3)]
+                a = _dot3(nr, turned)
+                good = good & (a > 0) & (a * a >= cos2 * (rr * _dot3(turned, turned)))
+            count += good
+            lower |= good & (sv < r)
+            for i, w in enumerate(world(sv, Xs, Ys, ds)):
+                point[i] = torch.where(good, point[i] + w, point[i])
+            if nflat is not None:
+                for i, g in enumerate(unit(sv, nflat[sv][at])):
+                    nsum[i] = torch.where(good, nsum[i] + g, nsum[i])
+            if cflat is not None:
+                csum = torch.where(good[:, None], csum + cflat[sv][at].double(), csum)
+        owner = has & ~lower
+        n = (1 + count[owner]).double()
+        rows["support"].append((1 + count[owner]).to(torch.uint8))
+        rows["points"].append(torch.stack([p[owner] / n for p in point], dim=1).float())
+        if nflat is not None:
+            t = [g[owner] for g in nsum]
+            length = torch.sqrt(_dot3(t, t))
+            rows["normals"].append(torch.stack([ti / length for ti in t], dim=1).float())
+        if cflat is not None:
+            rows["colours"].append((csum[owner] / n[:, None]).float())
+        rows["pixel"].append(r * H * W + torch.nonzero(owner)[:, 0])
+    cat = lambda name, shape, dtype: (torch.cat(rows[name]) if rows[name] else torch.zeros(0, dtype=dtype, device=dev)).reshape(shape)
+    return _fused_cloud(cat("points", (-1, 3), torch.float32), None if nflat is None else cat("normals", (-1, 3), torch.float32),
+                        None if cflat is None else cat("colours", (-1, cflat.shape[2]), torch.float32),
+                        cat("support", (-1,), torch.uint8), cat("pixel", (-1,), torch.int64), to_world, H, W, min_support)
+
+
 def _mix(x):
     """mix of THE DRAWS on int64 tensors that hold 32-bit values: both constants are below 2^31, so no product leaves 63 bits"""
     m = 0xFFFFFFFF
@@ -818,10 +1068,13 @@ def patch_match_step_torch(images, pose, intr, sources, depth, normal, score, co
 # ------------------------------------------------------------------------------------------------------------------ end to end
 @torch.no_grad()
 def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=None, points=None, options=None, trunc=None,
-                      min_weight=1.0, return_depth=False, stereo="sweep"):
+                      min_weight=1.0, return_depth=False, stereo="sweep", surface="tsdf"):
     """Photographs to a surface: plane_sweep (stereo="sweep", the default) or patch_match (stereo="patchmatch") over every view ->
     filter_depths -> ls2fm.fusion.volume_for(bounds, voxel, trunc) -> fusion.integrate -> fusion.extract -> ls2fm.mesh.Mesh, in the
-    poses' world frame.
+    poses' world frame.  With surface="poisson" or "mls" the depth maps go through the cloud instead of the volume: filter_depths ->
+    fuse_depths -> ls2fm.cloud_mesh.mesh_from_cloud(method=surface, voxel=voxel, bounds=bounds), with patch_match's normals, or for
+    the sweep, which has none, with normals estimated toward each point's camera; trunc and min_weight are the volume's and unused;
+    with return_depth the FusedCloud is appended to the result.
       images     [V, H, W, 3] colour (to_grey) or grey [V, H, W]
       sources    int [V, S]; default select_sources(pose, options.n_sources, options.min_angle, options.max_angle)
       depths     float [V, D]; default depth_planes over depth_range_from_points of `points` (an [N, 3] cloud or an
@@ -833,6 +1086,8 @@ def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=No
     opt = MvsOptions() if options is None else options
     if stereo not in ("sweep", "patchmatch"):
         raise ValueError(f"ls2fm.mvs.dense_reconstruct: stereo {stereo!r} must be 'sweep' or 'patchmatch'")
+    if surface not in ("tsdf", "poisson", "mls"):
+        raise ValueError(f"ls2fm.mvs.dense_reconstruct: surface {surface!r} must be 'tsdf', 'poisson' or 'mls'")
     images = torch.as_tensor(images)
     _device(images, torch.as_tensor(pose), torch.as_tensor(intr))
     grey = to_grey(images)
@@ -849,12 +1104,21 @@ def dense_reconstruct(images, pose, intr, bounds, voxel, sources=None, depths=No
     else:
         depth, normal, _ = patch_match(grey, pose, intr, sources, depths, **opt.patchmatch())
     filtered, count = filter_depths(depth, pose, intr, sources, **opt.filter())
-    volume = fusion.volume_for(bounds, voxel, trunc, grey.device)
-    fusion.integrate(volume, filtered, pose, intr, near=opt.near)
-    out = fusion.extract(volume, min_weight)
+    fused = ()
+    if surface == "tsdf":
+        volume = fusion.volume_for(bounds, voxel, trunc, grey.device)
+        fusion.integrate(volume, filtered, pose, intr, near=opt.near)
+        out = fusion.extract(volume, min_weight)
+    else:
+        from . import cloud_mesh
+        cloud = fuse_depths(filtered, pose, intr, sources, normal=None if stereo == "sweep" else normal,
+                            images=images if images.dim() == 4 else grey, **opt.fuse())
+        out = cloud_mesh.mesh_from_cloud(cloud.points, normals=cloud.normals, toward=cloud.centers, voxel=voxel, method=surface,
+                                         bounds=bounds)
+        fused = (cloud,)
     if not return_depth:
         return out
     if stereo == "sweep":
-        return out, filtered, count
+        return (out, filtered, count) + fused
     world = normals_to_world(normal, pose)
-    return out, filtered, count, world.masked_fill(torch.isnan(filtered)[..., None], math.nan)
+    return (out, filtered, count, world.masked_fill(torch.isnan(filtered)[..., None], math.nan)) + fused
