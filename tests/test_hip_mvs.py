@@ -65,11 +65,14 @@ def check(got, ref, what=""):
 
 
 # H, W, w, S, R, D, nan_pose, patches: an image smaller than a tile and its halo, one pixel past a tile in each axis, whole tiles;
-# every w, S, R and D of the lists, each with every image size
+# every w from 1 to 5 (each instantiation of the kernel; w = 4 is the first with three halo pixels per lane) with every image size,
+# S, R, D and nan_pose varied across them
 CASES = [(15, 16, 1, 1, 1, 1, False, False), (15, 16, 2, 3, 2, 2, False, False), (15, 16, 5, 5, 3, 17, False, False),
          (17, 33, 1, 5, 3, 17, False, True), (17, 33, 2, 3, 3, 3, True, False), (17, 33, 5, 1, 3, 17, False, False),
          (17, 33, 1, 5, 3, 17, True, False), (32, 48, 1, 5, 1, 2, False, False), (32, 48, 2, 3, 3, 17, False, True),
-         (32, 48, 5, 5, 2, 3, True, False)]
+         (32, 48, 5, 5, 2, 3, True, False),
+         (15, 16, 3, 3, 3, 3, True, False), (15, 16, 4, 5, 2, 17, False, False), (17, 33, 3, 5, 3, 17, False, False),
+         (17, 33, 4, 1, 1, 2, False, False), (32, 48, 3, 5, 2, 17, True, False), (32, 48, 4, 3, 3, 3, False, False)]
 
 
 @pytest.mark.parametrize("H,W,w,S_,R,D,nan_pose,patches", CASES)

@@ -81,7 +81,11 @@ def restated_steps(args, t, first, iteration, seed):
 CASES = [(15, 31, 1, 1, 1, 1, False, 0, 0, 0), (15, 31, 2, 3, 3, 2, False, 1, 3, 1), (15, 31, 5, 5, 3, 1, True, 0, 0, 1),
          (16, 32, 1, 5, 3, 2, False, 1, 3, 0), (16, 32, 2, 1, 1, 1, True, 0, 0, 1), (16, 32, 5, 3, 3, 2, False, 0, 3, 1),
          (17, 33, 1, 3, 1, 1, False, 1, 3, 1), (17, 33, 2, 5, 3, 1, True, 0, 0, 0), (17, 33, 5, 1, 3, 2, False, 1, 3, 0),
-         (32, 48, 1, 5, 3, 1, True, 1, 0, 1), (32, 48, 2, 3, 1, 2, False, 0, 3, 0), (32, 48, 5, 1, 3, 1, False, 0, 0, 0)]
+         (32, 48, 1, 5, 3, 1, True, 1, 0, 1), (32, 48, 2, 3, 1, 2, False, 0, 3, 0), (32, 48, 5, 1, 3, 1, False, 0, 0, 0),
+         # w = 3 (the default) and w = 4 with both tap steps, each at two of the sizes; (3, 2) is the one pattern without a centre tap
+         (15, 31, 3, 5, 3, 1, False, 0, 0, 0), (17, 33, 3, 3, 3, 1, True, 1, 3, 1), (16, 32, 3, 3, 1, 2, False, 1, 3, 0),
+         (32, 48, 3, 5, 3, 2, False, 0, 0, 1), (15, 31, 4, 5, 3, 1, False, 1, 0, 1), (32, 48, 4, 1, 3, 1, False, 0, 3, 0),
+         (16, 32, 4, 5, 3, 2, True, 0, 3, 1), (17, 33, 4, 3, 2, 2, False, 1, 0, 0)]
 
 
 @pytest.mark.parametrize("H,W,w,S_,R,t,nan_pose,first,iteration,seed", CASES)
@@ -117,6 +121,34 @@ def test_plane_score_alone_on_a_swept_state(MV):
         torch.cuda.synchronize()
         same(got, want, f"plane_score, tap step {t}")
         assert np.isfinite(want).any()
+
+
+def test_the_default_half_width_is_three(MV):
+    """plane_sweep, plane_score, patch_match_step and patch_match called without half_width, against the restatements at 3"""
+    import mvs_restate as MR
+    args = (17, 33, 3, 5, 3, 17, False, False)
+    sc = S.grid_scene(*args)
+    kw = dict(near=sc["near"], min_var=sc["min_var"], min_sources=sc["min_sources"])
+    v, refs = views(sc)
+    swept = MV.plane_sweep(*v, dev(sc["depths"]), refs=refs, **kw)
+    want = MR.sweep(sc["images"], sc["poses"], sc["intr"], sc["sources"], sc["depths"], refs=sc["refs"], half_width=3, **kw)
+    torch.cuda.synchronize()
+    for name, g, r in zip(("depth", "score"), swept, want):
+        same(g, r, f"{name} of the default sweep")
+    assert np.array_equal(host(swept[2]), want[2]) and (want[2] >= 0).any()
+    ref = restated_steps(args, 1, 0, 0, 0)
+    depth, normal = (dev(a) for a in PS.edge_state(sc))
+    score = MV.plane_score(*v, depth, normal, refs=refs, **kw)
+    check((depth, normal, score), ref[0], "default plane_score")
+    assert np.isfinite(ref[0][2]).any()
+    lo, hi = (dev(a) for a in d_range(sc))
+    for i, colour in enumerate((0, 1)):
+        check(MV.patch_match_step(*v, depth, normal, score, colour, 0, lo, hi, refs=refs, seed=0, **PERTURB, **kw), ref[1 + i],
+              f"default step, colour {colour}")
+    loop = PR.patch_match(sc["images"], sc["poses"], sc["intr"], sc["sources"], sc["depths"], refs=sc["refs"], iterations=1, seed=2,
+                          half_width=3, **PERTURB, **kw)
+    check(MV.patch_match(*v, dev(sc["depths"]), refs=refs, iterations=1, seed=2, **PERTURB, **kw), loop, "default patch_match")
+    assert np.isfinite(loop[2]).any()
 
 
 def test_two_iterations_from_the_edge_state(MV):

@@ -146,7 +146,8 @@ def _torch(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
-@pytest.mark.parametrize("H,W,w,nan_pose,patches", [(17, 33, 1, False, True), (15, 16, 2, True, False)])
+@pytest.mark.parametrize("H,W,w,nan_pose,patches", [(17, 33, 1, False, True), (15, 16, 2, True, False), (17, 33, 3, True, False),
+                                                    (15, 16, 3, False, False), (17, 33, 4, False, False), (15, 16, 4, True, False)])
 def test_plane_sweep_torch_on_the_cpu_leaves_the_restatement_s_bits(H, W, w, nan_pose, patches):
     from ls2fm import mvs
     sc = S.grid_scene(H, W, w, nan_pose=nan_pose, patches=patches)

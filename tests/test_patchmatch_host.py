@@ -157,6 +157,19 @@ def test_the_edge_states_meet_every_edge_of_both_rules():
     assert same_bits(d1[kept], flat_d[kept]) and kept.any()
 
 
+def test_the_edge_state_meets_every_edge_without_a_centre_tap():
+    """w = 3, t = 2: the taps at -3, -1, 1, 3, the one pattern that leaves the window's centre out -- every edge both rules name
+    still occurs on the state the GPU tests compare at that pattern, but for one that no w >= 3 can meet: "neighbour outside the
+    image".  The step visits the pixels that have a window, at least w from every border, and its farthest neighbour is 3 away."""
+    sc, ps, states, stats = edge_run(17, 33, 3, 2)
+    assert (0, 0) not in ps.offsets and len(ps.offsets) == 16
+    assert max(max(abs(dx), abs(dy)) for dx, dy in PR.NEIGHBOURS) == 3 and stats["neighbour outside the image"] == 0
+    for name in EDGES:
+        if name != "neighbour outside the image":
+            assert stats.get(name, 0) > 0, name
+    assert np.isfinite(states[0][2]).any() and np.isnan(states[0][2]).any()
+
+
 def test_the_draws():
     pixel = np.arange(4096)
     u = np.stack([PR.draw(3, 2, 1, pixel, j) for j in range(PR.N_DRAWS)])
@@ -238,7 +251,8 @@ def _torch(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
-@pytest.mark.parametrize("H,W,w,t,nan_pose", [(15, 16, 1, 1, False), (17, 33, 2, 2, True)])
+@pytest.mark.parametrize("H,W,w,t,nan_pose", [(15, 16, 1, 1, False), (17, 33, 2, 2, True), (15, 16, 3, 1, False), (17, 33, 3, 2, False),
+                                              (17, 33, 4, 2, True)])
 def test_the_torch_forms_on_the_cpu_leave_the_restatement_s_bits(H, W, w, t, nan_pose):
     from ls2fm import mvs
     sc = S.grid_scene(H, W, w, nan_pose=nan_pose)
