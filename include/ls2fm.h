@@ -2004,6 +2004,76 @@ int ls2fm_mvs_fuse_emit(const float* depth, const float* normal, const float* co
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Texture atlases of a mesh (csrc/mesh_texture.hip behind ls2fm.texture; additions, the library stays ABI 13): the map from
+ * texels to surface points, where ls2fm_mesh_vertex_colors and ls2fm_radiance_points put colour, and the render of a textured
+ * mesh from ls2fm_rasterize's face ids and barycentrics.  The reference ships none.  tests/texture_restate.py repeats both
+ * rules in numpy.
+ *
+ * THE ATLAS RULE.  The atlas is a square of S x S texels, S a power of two in [4, 32768]; texel (x, y) has its centre at
+ * (x + 0.5, y + 0.5).  Every face gets a right-isosceles chart; two charts share one square cell of pitch p = 2^k texels.  With the
+ * gutter g >= 0 the admissible classes are the k with 2 g + 4 <= 2^k <= the largest pitch (256 by default), and L = p - 2 g - 3.
+ *   corners   a face's corners are its vertices; a face with an index outside [0, V) has NaN corners.
+ *   rotation  e_i = the squared length of the edge opposite corner i: the fp32 differences of the two other corners, component by
+ *     component, converted to fp64, then ((dx dx + dy dy) + dz dz) in fp64.  r = 0; r = 1 if e_1 > e_0; r = 2 if e_2 > max so far:
+ *     the corner opposite the longest edge, ties to the lowest index, a NaN never greater.  The chart's corners a, b, c are the
+ *     face's corners r, r + 1, r + 2 (mod 3): the orientation is kept, a sits on the right angle.
+ *   class     l2 = the larger of the two e_i other than e_r (the legs at a).  The class is the smallest admissible k with
+ *     l2 <= T_k, T_k = ((2^k - 2 g - 3) texel)^2 formed on the host in doubles (the product, then its square); the largest
+ *     admissible k if there is none (the face is undersampled); the smallest if a corner is not finite.  Only fp64 sums, products
+ *     and comparisons: torch ops on the device and numpy give the same classes.
+ *   packing   order[slot] = face: the faces sorted stably by class, descending.  Slots 2 c and 2 c + 1 of a class's slots share
+ *     cell c of that class.  A cell's Morton offset is the sum of p^2 over all earlier cells (sizes are powers of four in
+ *     descending order, so the sum is a multiple of the cell's own p^2); the cell's origin (x0, y0) is that offset de-interleaved,
+ *     bit 2 b of the offset to bit b of x0, bit 2 b + 1 to bit b of y0.  The atlas holds the mesh iff the cells' total area is at
+ *     most S^2.
+ *   in a cell  with i = x - x0, j = y - y0: the texel belongs to chart A (the even slot) iff i + j <= p - 1, otherwise to chart B
+ *     (the odd slot), which is A turned by 180 degrees about the cell's centre: i' = p - 1 - i, j' = p - 1 - j (for A i' = i,
+ *     j' = j).  A's corners a, b, c sit on the centres of the texels (i', j') = (g, g), (g + L, g), (g, g + L).  A texel of a cell
+ *     behind the last, of chart B of an odd last slot, or whose order entry lies outside [0, F) is unowned.
+ *     For every point of the closed chart triangle every bilinear tap of non-zero weight is a texel owned by that face
+ *     (tests/test_texture_host.py proves it for every admissible p <= 64 and g <= 3): colour never bleeds between charts.
+ *   surface   fp32, every operation rounded once, none contracted: s = (float)(i' - g) / (float) L, t likewise from j'; per
+ *     component X = (a + s (b - a)) + t (c - a); gutter texels extrapolate (s or t negative, or s + t > 1).  The normal is
+ *     n = (b - a) x (c - a), n_x = d1_y d2_z - d1_z d2_y and cyclically with d1 = b - a, d2 = c - a, not normalised.  Unowned
+ *     texels get face = -1 and NaN point and normal; so does, for point and normal, an owned texel of a face with an index
+ *     outside [0, V).
+ * ls2fm_texture_texels  the rows [row_begin, row_end) of the atlas -> face int32 [rows][S], point float [rows][S][3], normal
+ *   float [rows][S][3], and uv float [F][3][2] (or NULL): the texel that sits on a chart corner writes that corner's texel
+ *   coordinates (its own centre: half-integers) at the face's own corner index (r + q) mod 3; the other entries are not
+ *   touched.  Inputs: verts, faces as for ls2fm_rasterize; order int32 [F]; rot int32 [F] (taken into [0, 2]);
+ *   class_log2_pitch int32 [n_classes] and class_count int64 [n_classes] ON THE HOST, read before the call returns: the classes'
+ *   k, strictly descending, and how many faces each holds (0 allowed).  One lane per texel in LS2FM_TEXTURE_TILE-square tiles
+ *   aligned to the atlas; the lane forms its Morton code, finds its class against the at most LS2FM_TEXTURE_MAX_CLASSES class
+ *   starts (kernel arguments), its cell by a shift, its slot by the half of the cell.  One launch, no atomic, no workspace,
+ *   nothing read back: the call can be captured; bands leave the bits of one call.  row_begin = row_end returns at once.
+ *
+ * THE TEXTURE RENDER RULE, per pixel with face f = face_id and barycentrics (w0, w1, w2), exactly as ls2fm_rasterize writes them:
+ *   f < 0 or f >= F gives the background.  Otherwise, in fp32, every operation rounded once, none contracted, with (x_i, y_i) =
+ *   uv[f][i]:  x = ((w0 x0 + w1 x1) + w2 x2), y likewise.  The sample is step 3 of THE SWEEP RULE about the texel centres with
+ *   clamped taps in place of the validity test: sx = x - 0.5, u0 = floor(sx), tx = sx - u0; u0 is taken into [-1, S] as a float
+ *   (a NaN becomes -1) and converted; the columns u0, u0 + 1 and the rows likewise are clamped to [0, S - 1]; per channel
+ *   r0 = b00 + tx (b10 - b00), r1 = b01 + tx (b11 - b01), out = r0 + ty (r1 - r0).  A NaN texel stays in the pixels that tap it.
+ * ls2fm_texture_render  face_id int32 [N][H][W], bary float [N][H][W][3], uv float [F][3][2], texture float [S][S][C], 1 <= C <= 4,
+ *   background float [C] ON THE HOST (read before the call returns) -> out float [N][H][W][C].  One lane per pixel, one launch,
+ *   no atomic: the call can be captured.  n_views = 0 returns at once.
+ * Refused before anything is enqueued: LS2FM_ERR_INVALID_ARGUMENT for a NULL required array (uv of ls2fm_texture_texels is
+ * optional; verts, faces, order, rot and uv are required only when there are vertices / faces), a negative count, n_faces >= 2^31,
+ * S that is not a power of two in [4, 32768], a band that is not 0 <= row_begin <= row_end <= S, channels outside 1 .. 4, height
+ * or width outside [1, 32768], n_views height width >= 2^40, a gutter outside [0, 64], n_classes outside
+ * [1, LS2FM_TEXTURE_MAX_CLASSES], a class table that is not strictly descending, holds a k outside [2, 15] or with
+ * 2^k < 2 g + 4, whose counts do not add up to n_faces, or whose cells do not fit S^2.
+ */
+#define LS2FM_TEXTURE_TILE 16
+#define LS2FM_TEXTURE_MAX_CLASSES 8
+int ls2fm_texture_texels(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* order,
+                         const int32_t* rot, int32_t n_classes, const int32_t* class_log2_pitch, const int64_t* class_count,
+                         int32_t gutter, int32_t size, int32_t row_begin, int32_t row_end, int32_t* face, float* point,
+                         float* normal, float* uv, void* stream);
+int ls2fm_texture_render(const int32_t* face_id, const float* bary, int32_t n_views, int32_t height, int32_t width, const float* uv,
+                         int64_t n_faces, const float* texture, int32_t size, int32_t channels, const float* background, float* out,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

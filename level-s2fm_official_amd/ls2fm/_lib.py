@@ -284,6 +284,9 @@ _SIGNATURES = {
                                       c_int32, c_int32, _P, _P]),
     "ls2fm_mvs_fuse_emit": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, c_float, c_float,
                                       c_float, c_float, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "ls2fm_texture_texels": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int32, POINTER(c_int32), POINTER(c_int64), c_int32, c_int32,
+                                       c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "ls2fm_texture_render": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int32, c_int32, POINTER(c_float), _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),
