@@ -2074,6 +2074,94 @@ int ls2fm_texture_render(const int32_t* face_id, const float* bary, int32_t n_vi
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lens-distortion camera models and image undistortion (csrc/camera_model.h, csrc/undistort.hip behind ls2fm.undistort; additions,
+ * the library stays ABI 13): COLMAP's image_undistorter, the stage between mapper and patch_match_stereo.  Every other stage knows
+ * the pinhole camera intr = (fx, fy, cx, cy) alone; these two calls are the adapter in front of them.  tests/undistort_restate.py
+ * repeats both rules in numpy, ls2fm.undistort._undistort_images_torch and _camera_points_torch as torch ops; the three agree bit
+ * for bit.
+ *
+ * A camera is LS2FM_CAMERA_PARAMS = 12 numbers (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6): OpenCV's rational model, COLMAP's
+ * FULL_OPENCV.  SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL and OPENCV are the same rule with zeros.
+ * THE DISTORTION RULE, from an undistorted normalised point (x, y) to the distorted image, in the precision T of the call (fp32 or
+ * fp64), every operation rounded once, none contracted, division correctly rounded:
+ *   r2  = (x x) + (y y)
+ *   num = 1 + r2 (k1 + r2 (k2 + r2 k3))            Horner, innermost first
+ *   den = 1 + r2 (k4 + r2 (k5 + r2 k6))
+ *   rad = num / den
+ *   xy  = x y
+ *   xd  = (x rad) + ( ((2 p1) xy) + (p2 (r2 + (2 x) x)) )
+ *   yd  = (y rad) + ( (p1 (r2 + (2 y) y)) + ((2 p2) xy) )
+ *   u   = (fx xd) + cx ;  v = (fy yd) + cy
+ * Its Jacobian J = d(xd, yd)/d(x, y) = [a b; c d], analytic, in the same precision and with the same r2, den and rad:
+ *   dnum = k1 + r2 ((2 k2) + r2 (3 k3)) ;  dden = k4 + r2 ((2 k5) + r2 (3 k6))
+ *   g   = (dnum - (rad dden)) / den               d rad / d r2
+ *   gx  = (2 x) g ;  gy = (2 y) g
+ *   a   = ((rad + (x gx)) + ((2 p1) y)) + (p2 (6 x))
+ *   b   = ((x gy) + ((2 p1) x)) + (p2 (2 y))
+ *   c   = ((y gx) + (p1 (2 x))) + ((2 p2) y)
+ *   d   = ((rad + (y gy)) + (p1 (6 y))) + ((2 p2) x)
+ * Deviations from COLMAP, on purpose: no fisheye, FOV or thin-prism models (atan is not a correctly rounded operation and the rule
+ * would lose its bits); no guard against a rational model that folds over (rad not monotone in r): such a camera maps several
+ * undistorted points to one photograph pixel and the rule takes it at its word.
+ *
+ * ls2fm_undistort_images  images float [V][Hs][Ws][C], channel last, 1 <= C <= 4, the photographs; cam float [V][12] their cameras;
+ *   out_intr float [V][4] the pinhole cameras of the outputs; the output size H x W, which need not be the source's; mode
+ *   LS2FM_UNDISTORT_BILINEAR or LS2FM_UNDISTORT_NEAREST; fill float [C] ON THE HOST, read before the call returns (NaN is the useful
+ *   value: ls2fm_mvs_sweep and PatchMatch treat a non-finite tap as invalid) -> out float [V][H][W][C] and valid uint8 [V][H][W] (or
+ *   NULL).  THE UNDISTORTION RULE, per view and output pixel (px, py), fp32, every operation rounded once, none contracted:
+ *   1. xn = (((float) px + 0.5) - cx_o) / fx_o, yn = (((float) py + 0.5) - cy_o) / fy_o with (fx_o, fy_o, cx_o, cy_o) = out_intr.
+ *   2. (u, v) by THE DISTORTION RULE with the view's cam.
+ *   3. the pixel is valid iff u and v are finite and IN THE IMAGE of the source by the rasteriser's comparisons, 0 <= u < Ws and
+ *      0 <= v < Hs in fp32.  Otherwise it takes fill and valid = 0.  A NaN or infinite camera word, or den == 0, makes u or v
+ *      non-finite (or NaN) and the pixel takes fill.
+ *   4. bilinear: x = u - 0.5, x0 = floor(x), tx = x - x0, rows likewise from v; the columns x0, x0 + 1 and the rows y0, y0 + 1
+ *      are clamped to the image as in step 5 of THE VERTEX COLOUR RULE; per channel r0 = a00 + tx (a10 - a00),
+ *      r1 = a01 + tx (a11 - a01), out = r0 + ty (r1 - r0), a_xy the tap at column x, row y.  A NaN source pixel stays in the pixels
+ *      that tap it (also with weight 0).
+ *   5. nearest: the source pixel (floor u, floor v), copied.  For depth maps and masks: a blend of depths across an edge invents
+ *      surfaces.
+ *   One lane per output pixel; a workgroup of 256 lanes takes one tile of LS2FM_UNDISTORT_TILE_W x LS2FM_UNDISTORT_TILE_H output
+ *   pixels of one view, so the view's 16 camera words are scalar loads.  One launch, no workspace, no atomics, nothing read back:
+ *   the call can be captured, a rerun or a replay repeats the bits, and the views of several calls leave the bits of one.
+ *   n_views = 0 returns at once.
+ *
+ * ls2fm_camera_points  key points, both directions, fp64, every operation rounded once, none contracted.  uv double [N][2];
+ *   view_start int32 [V + 1], non-decreasing, 0 <= view_start[0], view_start[V] <= N: the points of view v are the rows
+ *   view_start[v] .. view_start[v + 1] - 1 (the convention of ls2fm_absolute_pose); cam double [V][12]; out_intr double [V][4];
+ *   iters in [0, LS2FM_CAMERA_MAX_ITERS] -> uv_out double [N][2] and residual double [N] (or NULL).  A row outside
+ *   [view_start[0], view_start[V]) is not written.  One lane per point finds its view by bisection of view_start (the last v
+ *   with view_start[v] <= row): a table that is not monotone makes no access outside the arrays, only rows of unspecified views.
+ *   direction = LS2FM_CAMERA_DISTORT:  (x, y) = ((u - cx_o) / fx_o, (v - cy_o) / fy_o), the pinhole out_intr undone; uv_out = THE
+ *     DISTORTION RULE's (u, v) with cam; residual = 0.
+ *   direction = LS2FM_CAMERA_UNDISTORT:  xd = (u - cx) / fx, yd = (v - cy) / fy with cam's own words; start at (x, y) = (xd, yd);
+ *     exactly `iters` Newton steps: (fx_, fy_) = the rule's (xd, yd) at (x, y) with its Jacobian, e_x = fx_ - xd, e_y = fy_ - yd,
+ *     det = (a d) - (b c), x = x - (((d e_x) - (b e_y)) / det), y = y - (((a e_y) - (c e_x)) / det).  A step whose det is zero or
+ *     not finite is skipped, along with all later ones; the trip count is `iters` for every lane, nothing is read back.
+ *     uv_out = ((fx_o x) + cx_o, (fy_o y) + cy_o);  residual = ((fx e_x)(fx e_x)) + ((fy e_y)(fy e_y)) with e of the final iterate:
+ *     the squared pixel distance in the photograph, for the caller to drop what did not converge.
+ *   One launch of LS2FM_CAMERA_POINTS_THREADS lanes per workgroup, no workspace, no atomics: capturable; chunks of rows with the
+ *   same tables, a rerun and a replay leave the same bits.  n_points = 0 returns at once.
+ * Refused before anything is enqueued (LS2FM_ERR_INVALID_ARGUMENT): a NULL required array (valid and residual are optional), a
+ * negative count, a height or width of the source or the output outside [1, 32768], V Hs Ws or V H W >= 2^40, C outside 1 .. 4, an
+ * unknown mode or direction, iters outside [0, LS2FM_CAMERA_MAX_ITERS], n_points >= 2^31, n_views < 1 with points, 2^31 workgroups
+ * or more.
+ */
+#define LS2FM_CAMERA_PARAMS 12
+#define LS2FM_CAMERA_MAX_ITERS 32
+#define LS2FM_CAMERA_DISTORT 0
+#define LS2FM_CAMERA_UNDISTORT 1
+#define LS2FM_CAMERA_POINTS_THREADS 256
+#define LS2FM_UNDISTORT_BILINEAR 0
+#define LS2FM_UNDISTORT_NEAREST 1
+#define LS2FM_UNDISTORT_TILE_W 32
+#define LS2FM_UNDISTORT_TILE_H 8
+int ls2fm_undistort_images(const float* images, int32_t n_views, int32_t src_height, int32_t src_width, int32_t channels,
+                           const float* cam, const float* out_intr, int32_t height, int32_t width, int32_t mode, const float* fill,
+                           float* out, uint8_t* valid, void* stream);
+int ls2fm_camera_points(const double* uv, int64_t n_points, const int32_t* view_start, int32_t n_views, const double* cam,
+                        const double* out_intr, int32_t direction, int32_t iters, double* uv_out, double* residual, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * How the table-gradient scatter (inside ls2fm_render_bwd / ls2fm_sdf_points_bwd) finishes the few coarse levels whose slabs
  * are split over several workgroups.  Process-wide; takes effect for the calls enqueued afterwards.
  *   1 (default; env LS2FM_SCATTER_MODE)  every part's 64-bit fixed-point partial sums are combined by one more small launch:

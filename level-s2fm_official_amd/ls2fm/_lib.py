@@ -287,6 +287,9 @@ _SIGNATURES = {
     "ls2fm_texture_texels": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int32, POINTER(c_int32), POINTER(c_int64), c_int32, c_int32,
                                        c_int32, c_int32, _P, _P, _P, _P, _P]),
     "ls2fm_texture_render": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int32, c_int32, POINTER(c_float), _P, _P]),
+    "ls2fm_undistort_images": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, POINTER(c_float), _P, _P,
+                                         _P]),
+    "ls2fm_camera_points": (c_int32, [_P, c_int64, _P, c_int32, _P, _P, c_int32, c_int32, _P, _P, _P]),
     "ls2fm_set_scatter_mode": (c_int32, [c_int32]),
     "ls2fm_get_scatter_mode": (c_int32, []),
     "ls2fm_profile_enable": (c_int32, [c_int32]),
