@@ -974,6 +974,45 @@ int ls2fm_bundle_adjust_lm_run(double* poses, double* points, const double* obs_
                                const double* intrinsic4_host, const ls2fm_ba_lm_opts* opts, int32_t n_iters, double* state,
                                double* log, void* workspace, void* stream);
 
+/* THE CAMERA BLOCK (additions, the library stays ABI 13): the same loop with the shared camera's LS2FM_CAMERA_PARAMS = 12 words
+ * c = (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) as a 12-parameter block beside the poses and the points.  All arithmetic fp64,
+ * every sum in a fixed order, no floating-point atomics.  tests/ba_lm_camera_restate.py repeats every rule in numpy, by two routes.
+ *   model     x_c = R X + t ; x = X_c / Z_c, y = Y_c / Z_c (plain divisions) ; (xd, yd) by THE DISTORTION RULE in fp64 ;
+ *             r = (fx xd + cx - u, fy yd + cy - v) with (u, v) the key point IN THE PHOTOGRAPH AS TAKEN.  Loss and IRLS weight as above.
+ *   Jacobians J_proj = diag(fx, fy) J_dist [[1/z, 0, -x/z], [0, 1/z, -y/z]], J_dist the rule's Jacobian; J_c and J_p from J_proj as
+ *             above.  J_k (2 x 12) by columns: fx (xd, 0) ; fy (0, yd) ; cx (1, 0) ; cy (0, 1) ; k1..k3 (fx x, fy y) r2^j / den ;
+ *             k4..k6 -(fx x, fy y) rad r2^j / den ; p1 (fx 2xy, fy (r2 + 2y^2)) ; p2 (fx (r2 + 2x^2), fy 2xy).
+ *   words     refine_mask has 12 bits, bit k = word k moves.  An unrefined word has a zero column of J_k; its row and column of the
+ *             camera block are the identity's with right-hand side 0 (a constant view's rule, per word).  tie_focal (needs bit 0
+ *             set and bit 1 clear): the fx column is col_fx + aspect col_fy, and after an update fy = aspect fx, rounded once;
+ *             aspect = fy / fx is formed ONCE by the caller when the loop is built.
+ *   system    per observation G += w J_k^T J_k, g_k += w J_k^T r, H_i += w J_c^T J_k (6 x 12, per view), Y_p += w J_k^T J_p (12 x 3,
+ *             per point, in the point's list order).  The camera block is damped as ONE 12-block: C* = C + lambda diag(max(C_kk,
+ *             1e-12 max_k C_kk)).  The reduced system has 6 V + 12 rows, the camera last:
+ *                 S_ik = H_i - sum_{o in view i} w_o J_c,o^T J_p,o V_p*^-1 Y_p^T       S_kk = C* - sum_p Y_p V_p*^-1 Y_p^T
+ *                 b_k  = -(g_k - sum_p Y_p V_p*^-1 g_p)      delta_p = -V_p*^-1 (g_p + sum_o W_o^T delta_c[view(o)] + Y_p^T delta_k)
+ *             The sums over p are formed as sums over the observations (sum_p Y_p V_p*^-1 Y_p^T = sum_o J_k,o^T F_o with F_o = w_o
+ *             J_p,o V_p*^-1 Y_p^T), per view in list order, the views added in view order.  The camera's rows are two more
+ *             6-column panels of the same Cholesky: V <= LS2FM_BA_LM_MAX_VIEWS - 2 = 126, LS2FM_ERR_UNSUPPORTED above.
+ *   decision  unchanged (strict cost decrease, pivot failure, the lambda rule), with: max |g| includes the refined g_k; max |delta|
+ *             includes |delta_k| / (1 + |c_k|) per refined word (a focal length of 1000 px must not loosen the step test of points
+ *             of size 1); max |parameter| unchanged.  The candidate camera is accepted or rejected with the poses and points.
+ *   run       ls2fm_bundle_adjust_lm_run_camera: prepare is shared (ls2fm_bundle_adjust_lm_prepare on the larger workspace of
+ *             ls2fm_bundle_adjust_lm_camera_workspace_bytes, which holds the pinhole layout first).  THE CALLER MUST ALLOCATE THAT
+ *             LARGER SIZE: prepare does not know the allocation, its header records V, P and n only, and a workspace of
+ *             ls2fm_bundle_adjust_lm_workspace_bytes passed here is written past its end.  camera [12] is DEVICE state,
+ *             updated in place like poses: split calls continue bit for bit, a captured call replays, nothing is read back.  Seven
+ *             launches per iteration (the border has its own) and two after the last.  refine_mask = 0 is legal: only the residual
+ *             model changes.  LS2FM_ERR_INVALID_ARGUMENT: mask bits >= 12, tie_focal with a wrong mask, a non-finite aspect, what
+ *             ls2fm_bundle_adjust_lm_run refuses.  A non-finite or zero fx / fy is found on the device: the run moves nothing and
+ *             logs NaN, as with an unprepared workspace.
+ */
+int64_t ls2fm_bundle_adjust_lm_camera_workspace_bytes(int32_t n_views, int64_t n_points, int64_t n_obs);
+int ls2fm_bundle_adjust_lm_run_camera(double* poses, double* points, double* camera, const double* obs_uv, int32_t n_views,
+                                      int64_t n_points, int64_t n_obs, uint32_t refine_mask, int32_t tie_focal, double aspect,
+                                      const ls2fm_ba_lm_opts* opts, int32_t n_iters, double* state, double* log, void* workspace,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Descriptor matching (csrc/match.hip; additions, the library stays ABI 13): the raw matches `colmap exhaustive_matcher` writes
  * into its `matches` table (preparation/main.py:98, read back at :30-37) -- COLMAP's CPU SIFT matcher with its defaults,

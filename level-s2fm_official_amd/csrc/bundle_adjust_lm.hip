@@ -23,7 +23,19 @@
 //   balm_cost       one workgroup per view: the candidate's cost partials.
 // After the last iteration of a call the decision runs once more on its own (balm_linearize on one workgroup + balm_points, both
 // told to stop after the decision), so the caller's poses, points and state are final when the call's launches end.
+//
+// THE CAMERA BLOCK (ls2fm_bundle_adjust_lm_run_camera): the kernels are instantiated over `bool CAMERA`; false is the pinhole loop above,
+// word for word.  true reads the 12-word camera from the device, puts THE DISTORTION RULE (camera_model.h, fp64) between the
+// division and the focal lengths, and borders the reduced system with the camera's 12 rows, two more panels of the same Cholesky:
+//   balm_linearize  also J_k (2 x 12, masked and tied) of every observation into the workspace
+//   balm_points     also Y_p = sum w J_k^T J_p over the point's list, and the accepted candidate camera into the caller's
+//   balm_border     one more launch, one workgroup per (view, pair of camera words): the view's part of G, g_k, H_i and of the three
+//                   sums that eliminate the points from the border, all as sums over the view's observations (F_o = w J_p V_p*^-1
+//                   Y_p^T is shared by them) -- 76 sums per thread instead of the 500 a single pass would hold
+//   balm_solve      adds the views' parts in view order into rows 6 V .. 6 V + 11, damps C as one block, V + 2 panels
+//   balm_backsub    adds Y_p^T delta_k, forms the candidate camera;  balm_cost evaluates the candidate under it
 #include "ba_index.h"
+#include "camera_model.h"
 #include "lm_math.h"
 #include "render_common.h"
 #include "workspace.h"
@@ -35,6 +47,10 @@ using lm_math::pose_update;
 
 constexpr int kT = 256;                              // threads of every workgroup here
 constexpr int kMaxN = 6 * LS2FM_BA_LM_MAX_VIEWS;     // rows of the reduced system
+constexpr int kK = LS2FM_CAMERA_PARAMS;              // the camera's words = its rows of the bordered system
+constexpr int kMaxCamViews = LS2FM_BA_LM_MAX_VIEWS - 2;
+constexpr int kBorderCols = 2, kBorderSums = 38 * kBorderCols;       // balm_border: camera words per workgroup, sums per thread
+using Cam = camera_model::Camera<double>;
 constexpr int32_t kMagic = 0x424c4d31;               // "BLM1": filled by ls2fm_bundle_adjust_lm_prepare for these sizes
 
 // the record of an iteration = the caller's state [8]
@@ -72,16 +88,31 @@ struct Ws {                    // the index arrays: ba_index.h
     int32_t* point_obs;        // [n]: observations of point p in list order (= rising view position)
     uint8_t* view_const;       // [V]
     uint8_t* point_const;      // [P]: fewer than min_point_views observations
+    // THE CAMERA BLOCK's part (ls2fm_bundle_adjust_lm_camera_workspace_bytes), behind the layout above; S and b then point here
+    double* cam_ok;            // [1]: the caller's fx, fy are finite and not 0 (balm_linearize, workgroup 0)
+    double* cand_cam;          // [12]
+    double* Jk;                // [n][2][12]
+    double* Yp;                // [P][12][3]
+    double* Gv;                // [V][12][12]: the view's sum of w J_k^T J_k
+    double* Zv;                // [V][12][12]:                  J_k^T F_o
+    double* Hv;                // [V][6][12]:                   w J_c^T J_k
+    double* Zh;                // [V][6][12]:                   J_c^T F_o
+    double* gkv;               // [V][12]:                      w J_k^T r
+    double* ekv;               // [V][12]:                      J_k^T (w J_p V_p*^-1 g_p)
     int64_t bytes;
 };
 
-struct Prob { int V, P, n, nb, loss; double fx, fy, cx, cy, c2, lambda0, grad_tol, step_tol; };
+struct Prob {
+    int V, P, n, nb, loss;
+    double fx, fy, cx, cy, c2, lambda0, grad_tol, step_tol;
+    uint32_t mask; int tie; double aspect;           // THE CAMERA BLOCK: the refined words, fy = aspect * fx
+};
 
 int64_t n_blocks(int64_t V, int64_t P) { return (P + V + kT - 1) / kT; }
 
-Ws layout(void* base, int64_t V, int64_t P, int64_t n) {
+Ws layout(void* base, int64_t V, int64_t P, int64_t n, bool camera = false) {
     Workspace ws(base, 16);
-    Ws w;
+    Ws w = {};
     const int64_t nb = n_blocks(V, P), N = 6 * V;
     w.header = ws.take<int32_t>(8);
     w.it = ws.take<double>(8);
@@ -112,6 +143,21 @@ Ws layout(void* base, int64_t V, int64_t P, int64_t n) {
     w.point_obs = ws.take<int32_t>(n);
     w.view_const = ws.take<uint8_t>(V);
     w.point_const = ws.take<uint8_t>(P);
+    if (camera) {
+        const int64_t Nc = N + kK;
+        w.cam_ok = ws.take<double>(1);
+        w.cand_cam = ws.take<double>(kK);
+        w.Jk = ws.take<double>(2 * kK * n);
+        w.Yp = ws.take<double>(3 * kK * P);
+        w.Gv = ws.take<double>(kK * kK * V);
+        w.Zv = ws.take<double>(kK * kK * V);
+        w.Hv = ws.take<double>(6 * kK * V);
+        w.Zh = ws.take<double>(6 * kK * V);
+        w.gkv = ws.take<double>(kK * V);
+        w.ekv = ws.take<double>(kK * V);
+        w.S = ws.take<double>(Nc * Nc);
+        w.b = ws.take<double>(Nc);
+    }
     w.bytes = (int64_t)ws.bytes();
     return w;
 }
@@ -120,18 +166,38 @@ __device__ __forceinline__ bool header_ok(const Ws& w, const Prob& pb) {
     return w.header[0] == kMagic && w.header[1] == pb.V && w.header[2] == pb.P && w.header[3] == pb.n;
 }
 
+__device__ __forceinline__ bool focal_ok(double f) { return f != 0.0 && fabs(f) <= 1.7976931348623157e308; }     // finite, not 0
+
+// what every launch but balm_linearize asks before it touches anything
+template <bool CAMERA>
+__device__ __forceinline__ bool ready(const Ws& w, const Prob& pb) {
+    if constexpr (CAMERA) return header_ok(w, pb) && w.cam_ok[0] != 0.0;
+    else return header_ok(w, pb);
+}
+
 // one observation: camera point, residual, s = |r|^2 -> rho and the IRLS weight rho'(s)
 struct ObsEval { double X, Y, Z, iz, r0, r1, rho, wgt; };
+// THE CAMERA BLOCK's part of it: the normalised point before and after THE DISTORTION RULE, and what the rule's Jacobians share
+struct Lens { double x, y, xd, yd; camera_model::Radial<double> o; };
 
+template <bool CAMERA>
 __device__ __forceinline__ ObsEval eval_obs(const double* __restrict__ P, const double* __restrict__ x, const double* __restrict__ uv,
-                                            const Prob& pb) {
+                                            const Prob& pb, const Cam& cam, Lens& L) {
     ObsEval e;
     e.X = ((P[0] * x[0] + P[1] * x[1]) + P[2] * x[2]) + P[3];
     e.Y = ((P[4] * x[0] + P[5] * x[1]) + P[6] * x[2]) + P[7];
     e.Z = ((P[8] * x[0] + P[9] * x[1]) + P[10] * x[2]) + P[11];
     e.iz = 1.0 / e.Z;
-    e.r0 = (pb.fx * (e.X * e.iz) + pb.cx) - uv[0];
-    e.r1 = (pb.fy * (e.Y * e.iz) + pb.cy) - uv[1];
+    if constexpr (CAMERA) {
+        L.x = e.X / e.Z;
+        L.y = e.Y / e.Z;
+        L.o = camera_model::distort<double>(cam, L.x, L.y, L.xd, L.yd);
+        e.r0 = (cam.fx * L.xd + cam.cx) - uv[0];
+        e.r1 = (cam.fy * L.yd + cam.cy) - uv[1];
+    } else {
+        e.r0 = (pb.fx * (e.X * e.iz) + pb.cx) - uv[0];
+        e.r1 = (pb.fy * (e.Y * e.iz) + pb.cy) - uv[1];
+    }
     const double s = e.r0 * e.r0 + e.r1 * e.r1;
     if (pb.loss == 0) {
         e.rho = s;
@@ -192,12 +258,19 @@ __device__ inline void decide(const Ws& w, const Prob& pb, const double* __restr
 }
 
 // grid: V workgroups (finish: 1)
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
-balm_linearize(const double* __restrict__ poses, const double* __restrict__ points, const double* __restrict__ obs_uv, Ws w, Prob pb,
-               const double* __restrict__ state, int pending, int finish, double* __restrict__ log_row) {
+balm_linearize(const double* __restrict__ poses, const double* __restrict__ points, const double* __restrict__ camera,
+               const double* __restrict__ obs_uv, Ws w, Prob pb, const double* __restrict__ state, int pending, int finish,
+               double* __restrict__ log_row) {
     const int v = blockIdx.x, tid = threadIdx.x;
     __shared__ double s_rec[8], s_red[(kT / 64) * 28], s_mx[kT / 64];
-    if (!header_ok(w, pb)) {                         // an unprepared workspace: nothing moves, the log says so
+    bool ok = header_ok(w, pb);
+    if constexpr (CAMERA) {                          // nobody writes the caller's camera during this launch
+        ok = ok && focal_ok(camera[0]) && focal_ok(camera[1]);
+        if (v == 0 && tid == 0 && header_ok(w, pb)) w.cam_ok[0] = ok ? 1.0 : 0.0;
+    }
+    if (!ok) {                                       // an unprepared workspace: nothing moves, the log says so
         if (v == 0 && tid < 6 && log_row) log_row[tid] = __builtin_nan("");
         return;
     }
@@ -217,6 +290,8 @@ balm_linearize(const double* __restrict__ poses, const double* __restrict__ poin
     double P[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) P[q] = acc ? w.cand_poses[12 * v + q] : poses[12 * v + q];
+    Cam cam = {};
+    if constexpr (CAMERA) cam = camera_model::load_camera<double>(acc ? w.cand_cam : camera, 0);
     const bool vconst = w.view_const[v] != 0;
     double a[28];
 #pragma unroll
@@ -225,13 +300,47 @@ balm_linearize(const double* __restrict__ poses, const double* __restrict__ poin
     for (int i = w.view_start[v] + tid; i < w.view_start[v + 1]; i += kT) {
         const int p = w.obs_point[i];
         const double* __restrict__ x = X + 3 * (int64_t)p;
-        const ObsEval e = eval_obs(P, x, obs_uv + 2 * (int64_t)i, pb);
+        Lens L;
+        const ObsEval e = eval_obs<CAMERA>(P, x, obs_uv + 2 * (int64_t)i, pb, cam, L);
         pm = fmax(pm, fmax(fmax(fabs(x[0]), fabs(x[1])), fabs(x[2])));
-        const double ju0 = pb.fx * e.iz, ju2 = -pb.fx * e.X * e.iz * e.iz;
-        const double jv1 = pb.fy * e.iz, jv2 = -pb.fy * e.Y * e.iz * e.iz;
-        // d x_c = -[x_c]x omega + dt
-        double Ju[6] = {e.Y * ju2, e.Z * ju0 - e.X * ju2, -e.Y * ju0, ju0, 0.0, ju2};
-        double Jv[6] = {e.Y * jv2 - e.Z * jv1, -e.X * jv2, e.X * jv1, 0.0, jv1, jv2};
+        // d x_c = -[x_c]x omega + dt ; J_p = J_proj R
+        double Ju[6], Jv[6], Pu[3], Pv[3];
+        if constexpr (CAMERA) {
+            // J_proj = diag(fx, fy) J_dist [[1/z, 0, -x/z], [0, 1/z, -y/z]], its rows ju and jv
+            double da, db, dc, dd;
+            camera_model::jacobian<double>(cam, L.o, L.x, L.y, da, db, dc, dd);
+            const double ju[3] = {cam.fx * (da * e.iz), cam.fx * (db * e.iz), -(cam.fx * ((da * L.x + db * L.y) * e.iz))};
+            const double jv[3] = {cam.fy * (dc * e.iz), cam.fy * (dd * e.iz), -(cam.fy * ((dc * L.x + dd * L.y) * e.iz))};
+            Ju[0] = ju[2] * e.Y - ju[1] * e.Z; Ju[1] = ju[0] * e.Z - ju[2] * e.X; Ju[2] = ju[1] * e.X - ju[0] * e.Y;
+            Jv[0] = jv[2] * e.Y - jv[1] * e.Z; Jv[1] = jv[0] * e.Z - jv[2] * e.X; Jv[2] = jv[1] * e.X - jv[0] * e.Y;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Ju[3 + c] = ju[c]; Jv[3 + c] = jv[c];
+                Pu[c] = (ju[0] * P[c] + ju[1] * P[4 + c]) + ju[2] * P[8 + c];
+                Pv[c] = (jv[0] * P[c] + jv[1] * P[4 + c]) + jv[2] * P[8 + c];
+            }
+            // J_k, the unrefined words' columns 0, the tied focal length's column col_fx + aspect col_fy
+            double ku[kK], kv[kK];
+            camera_model::jacobian_k<double>(cam, L.o, L.x, L.y, L.xd, L.yd, ku, kv);
+            if (pb.tie) { ku[0] = ku[0] + pb.aspect * ku[1]; kv[0] = kv[0] + pb.aspect * kv[1]; }
+            double* __restrict__ jk = w.Jk + 2 * kK * (int64_t)i;
+#pragma unroll
+            for (int k = 0; k < kK; ++k) {
+                const bool on = (pb.mask >> k) & 1u;
+                jk[k] = on ? ku[k] : 0.0;
+                jk[kK + k] = on ? kv[k] : 0.0;
+            }
+        } else {
+            const double ju0 = pb.fx * e.iz, ju2 = -pb.fx * e.X * e.iz * e.iz;
+            const double jv1 = pb.fy * e.iz, jv2 = -pb.fy * e.Y * e.iz * e.iz;
+            Ju[0] = e.Y * ju2; Ju[1] = e.Z * ju0 - e.X * ju2; Ju[2] = -e.Y * ju0; Ju[3] = ju0; Ju[4] = 0.0; Ju[5] = ju2;
+            Jv[0] = e.Y * jv2 - e.Z * jv1; Jv[1] = -e.X * jv2; Jv[2] = e.X * jv1; Jv[3] = 0.0; Jv[4] = jv1; Jv[5] = jv2;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Pu[c] = ju0 * P[c] + ju2 * P[8 + c];
+                Pv[c] = jv1 * P[4 + c] + jv2 * P[8 + c];
+            }
+        }
         if (vconst)
 #pragma unroll
             for (int q = 0; q < 6; ++q) { Ju[q] = 0.0; Jv[q] = 0.0; }
@@ -241,9 +350,9 @@ balm_linearize(const double* __restrict__ poses, const double* __restrict__ poin
 #pragma unroll
         for (int q = 0; q < 6; ++q) { jc[q] = Ju[q]; jc[6 + q] = Jv[q]; }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {                // J_p = J_proj R
-            jp[c] = pconst ? 0.0 : ju0 * P[c] + ju2 * P[8 + c];
-            jp[3 + c] = pconst ? 0.0 : jv1 * P[4 + c] + jv2 * P[8 + c];
+        for (int c = 0; c < 3; ++c) {
+            jp[c] = pconst ? 0.0 : Pu[c];
+            jp[3 + c] = pconst ? 0.0 : Pv[c];
         }
         w.rw[3 * (int64_t)i] = e.r0; w.rw[3 * (int64_t)i + 1] = e.r1; w.rw[3 * (int64_t)i + 2] = e.wgt;
         int q = 0;
@@ -270,10 +379,12 @@ balm_linearize(const double* __restrict__ poses, const double* __restrict__ poin
 }
 
 // grid: nb workgroups: thread = point, then view
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
-balm_points(double* __restrict__ poses, double* __restrict__ points, Ws w, Prob pb, double* __restrict__ state, int finish) {
+balm_points(double* __restrict__ poses, double* __restrict__ points, double* __restrict__ camera, Ws w, Prob pb,
+            double* __restrict__ state, int finish) {
     __shared__ double s_mx[kT / 64];
-    if (!header_ok(w, pb)) return;
+    if (!ready<CAMERA>(w, pb)) return;
     const int64_t idx = (int64_t)blockIdx.x * kT + threadIdx.x;
     const bool done = w.it[kDone] != 0.0, acc = w.it[kAccepted] != 0.0;
     if (idx == 0)
@@ -287,6 +398,10 @@ balm_points(double* __restrict__ poses, double* __restrict__ points, Ws w, Prob 
             const int v = (int)(idx - pb.P);
 #pragma unroll
             for (int q = 0; q < 12; ++q) poses[12 * v + q] = w.cand_poses[12 * v + q];
+            if constexpr (CAMERA)
+                if (v == 0)
+#pragma unroll
+                    for (int k = 0; k < kK; ++k) camera[k] = w.cand_cam[k];
         }
     }
     if (finish || done) return;
@@ -343,6 +458,23 @@ balm_points(double* __restrict__ poses, double* __restrict__ points, Ws w, Prob 
         for (int q = 0; q < 6; ++q) w.Vinv[6 * idx + q] = Vi[q];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { w.Vg[3 * idx + c] = vg[c]; w.gp[3 * idx + c] = g[c]; }
+        if constexpr (CAMERA) {                      // Y_p = sum w J_k^T J_p in the point's list order (J_p = 0: a constant point)
+            double Y[3 * kK];
+#pragma unroll
+            for (int q = 0; q < 3 * kK; ++q) Y[q] = 0.0;
+            for (int k = w.point_start[idx]; k < w.point_start[idx + 1]; ++k) {
+                const int64_t o = w.point_obs[k];
+                const double* __restrict__ jp = w.Jp + 6 * o;
+                const double* __restrict__ jk = w.Jk + 2 * kK * o;
+                const double wt = w.rw[3 * o + 2];
+#pragma unroll
+                for (int r = 0; r < kK; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) Y[3 * r + c] += wt * (jk[r] * jp[c]) + wt * (jk[kK + r] * jp[3 + c]);
+            }
+#pragma unroll
+            for (int q = 0; q < 3 * kK; ++q) w.Yp[3 * kK * idx + q] = Y[q];
+        }
     }
     gm = block_max<kT>(gm, s_mx);
     fail = block_max<kT>(fail, s_mx);
@@ -350,10 +482,11 @@ balm_points(double* __restrict__ poses, double* __restrict__ points, Ws w, Prob 
 }
 
 // grid: V (V + 1) / 2 workgroups: pair (i, j), i <= j, row by row
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
 balm_schur(Ws w, Prob pb) {
     __shared__ double s_red[(kT / 64) * 42];
-    if (!header_ok(w, pb) || w.it[kDone] != 0.0) return;
+    if (!ready<CAMERA>(w, pb) || w.it[kDone] != 0.0) return;
     int i = 0, rem = blockIdx.x;
     while (rem >= pb.V - i) { rem -= pb.V - i; ++i; }
     const int j = i + rem, tid = threadIdx.x;
@@ -413,7 +546,7 @@ balm_schur(Ws w, Prob pb) {
     }
     block_sum<42, kT>(a, s_red);
     if (tid != 0) return;
-    const int N = 6 * pb.V;
+    const int N = 6 * pb.V + (CAMERA ? kK : 0);      // S's row length
     double* __restrict__ S = w.S;
     if (i != j) {
 #pragma unroll
@@ -456,18 +589,104 @@ balm_schur(Ws w, Prob pb) {
     for (int r = 0; r < 6; ++r) w.b[6 * i + r] = -(w.g[6 * i + r] - a[36 + r]);
 }
 
+// THE CAMERA BLOCK.  grid: (V, kK / kBorderCols) workgroups: view v and the camera words k0, k0 + 1.  Per observation o of the view,
+// with E = w J_p V_p*^-1 (2 x 3), F = E Y_p^T (2 x 12, its columns k0..) and e = E g_p:
+//   Gv[r][k] += w J_k[:, r] . J_k[:, k]     Zv[r][k] += J_k[:, r] . F[:, k]      (r: the 12 words)
+//   Hv[r][k] += w J_c[:, r] . J_k[:, k]     Zh[r][k] += J_c[:, r] . F[:, k]      (r: the view's 6 pose parameters)
+//   gkv[k]   += w J_k[:, k] . r             ekv[k]   += J_k[:, k] . e
+// so that C = sum_v Gv, sum_p Y_p V_p*^-1 Y_p^T = sum_v Zv, sum_p Y_p V_p*^-1 g_p = sum_v ekv (a point's sum over its observations,
+// regrouped by view) and S_ik = Hv - Zh.  balm_solve adds the views in view order.
+__global__ void __launch_bounds__(kT)
+balm_border(Ws w, Prob pb) {
+    __shared__ double s_red[(kT / 64) * kBorderSums];
+    if (!ready<true>(w, pb) || w.it[kDone] != 0.0) return;
+    constexpr int C = kBorderCols;
+    const int v = blockIdx.x, k0 = C * blockIdx.y, tid = threadIdx.x;
+    double a[kBorderSums];
+#pragma unroll
+    for (int q = 0; q < kBorderSums; ++q) a[q] = 0.0;
+    for (int o = w.view_start[v] + tid; o < w.view_start[v + 1]; o += kT) {
+        const int p = w.obs_point[o];
+        const double* __restrict__ jk = w.Jk + 2 * kK * (int64_t)o;
+        const double* __restrict__ jc = w.Jc + 12 * (int64_t)o;
+        const double* __restrict__ jp = w.Jp + 6 * (int64_t)o;
+        const double* __restrict__ vi = w.Vinv + 6 * (int64_t)p;
+        const double* __restrict__ vg = w.Vg + 3 * (int64_t)p;
+        const double* __restrict__ yp = w.Yp + 3 * kK * (int64_t)p + 3 * k0;
+        const double r0 = w.rw[3 * (int64_t)o], r1 = w.rw[3 * (int64_t)o + 1], wt = w.rw[3 * (int64_t)o + 2];
+        double E[2][3], F[2][C], e[2], ku[C], kv[C];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            E[k][0] = wt * ((jp[3 * k] * vi[0] + jp[3 * k + 1] * vi[1]) + jp[3 * k + 2] * vi[2]);
+            E[k][1] = wt * ((jp[3 * k] * vi[1] + jp[3 * k + 1] * vi[3]) + jp[3 * k + 2] * vi[4]);
+            E[k][2] = wt * ((jp[3 * k] * vi[2] + jp[3 * k + 1] * vi[4]) + jp[3 * k + 2] * vi[5]);
+            e[k] = wt * ((jp[3 * k] * vg[0] + jp[3 * k + 1] * vg[1]) + jp[3 * k + 2] * vg[2]);
+#pragma unroll
+            for (int m = 0; m < C; ++m) F[k][m] = (E[k][0] * yp[3 * m] + E[k][1] * yp[3 * m + 1]) + E[k][2] * yp[3 * m + 2];
+        }
+#pragma unroll
+        for (int m = 0; m < C; ++m) { ku[m] = jk[k0 + m]; kv[m] = jk[kK + k0 + m]; }
+#pragma unroll
+        for (int r = 0; r < kK; ++r)
+#pragma unroll
+            for (int m = 0; m < C; ++m) {
+                a[C * r + m] += wt * (jk[r] * ku[m]) + wt * (jk[kK + r] * kv[m]);
+                a[C * (kK + r) + m] += jk[r] * F[0][m] + jk[kK + r] * F[1][m];
+            }
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int m = 0; m < C; ++m) {
+                a[C * (2 * kK + r) + m] += wt * (jc[r] * ku[m]) + wt * (jc[6 + r] * kv[m]);
+                a[C * (2 * kK + 6 + r) + m] += jc[r] * F[0][m] + jc[6 + r] * F[1][m];
+            }
+#pragma unroll
+        for (int m = 0; m < C; ++m) {
+            a[C * 36 + m] += wt * (ku[m] * r0) + wt * (kv[m] * r1);
+            a[C * 37 + m] += ku[m] * e[0] + kv[m] * e[1];
+        }
+    }
+    block_sum<kBorderSums, kT>(a, s_red);
+    if (tid != 0) return;
+#pragma unroll
+    for (int m = 0; m < C; ++m) {
+#pragma unroll
+        for (int r = 0; r < kK; ++r) {
+            w.Gv[kK * (kK * v + r) + k0 + m] = a[C * r + m];
+            w.Zv[kK * (kK * v + r) + k0 + m] = a[C * (kK + r) + m];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            w.Hv[kK * (6 * v + r) + k0 + m] = a[C * (2 * kK + r) + m];
+            w.Zh[kK * (6 * v + r) + k0 + m] = a[C * (2 * kK + 6 + r) + m];
+        }
+        w.gkv[kK * v + k0 + m] = a[C * 36 + m];
+        w.ekv[kK * v + k0 + m] = a[C * 37 + m];
+    }
+}
+
 // grid: ONE workgroup
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
 balm_solve(Ws w, Prob pb) {
     __shared__ double s_panel[kMaxN * 6];            // the panel's columns of L, row-major [row][6]
     __shared__ double s_z[kMaxN];                    // the right-hand side: one more row of the matrix
     __shared__ double s_d[36], s_mx[kT / 64];
+    __shared__ double s_c[CAMERA ? 2 * kK * kK : 1]; // C and the sum it loses to the points
     __shared__ int s_fail;
-    if (!header_ok(w, pb) || w.it[kDone] != 0.0) return;
-    const int tid = threadIdx.x, V = pb.V, N = 6 * V;
+    if (!ready<CAMERA>(w, pb) || w.it[kDone] != 0.0) return;
+    const int tid = threadIdx.x, V = pb.V, N = 6 * V + (CAMERA ? kK : 0), NP = V + (CAMERA ? kK / 6 : 0);
     double gm = 0.0, pm = 0.0, fl = 0.0;
     for (int v = tid; v < V; v += kT) { gm = fmax(gm, w.gview[v]); pm = fmax(pm, w.pview[v]); }
     for (int k = tid; k < pb.nb; k += kT) { gm = fmax(gm, w.gblk[k]); fl = fmax(fl, w.fblk[k]); }
+    if constexpr (CAMERA)
+        if (tid < kK) {                              // g_k and what the points take from it, the views' parts in view order
+            double gk = 0.0, ek = 0.0;
+            for (int v = 0; v < V; ++v) { gk += w.gkv[kK * v + tid]; ek += w.ekv[kK * v + tid]; }
+            const bool on = (pb.mask >> tid) & 1u;
+            s_z[6 * V + tid] = on ? -(gk - ek) : 0.0;
+            if (on) gm = fmax(gm, fabs(gk));
+        }
     gm = block_max<kT>(gm, s_mx);
     pm = block_max<kT>(pm, s_mx);
     fl = block_max<kT>(fl, s_mx);
@@ -477,9 +696,36 @@ balm_solve(Ws w, Prob pb) {
         w.sum[sGmax] = gm; w.sum[sPmax] = pm; w.sum[sCost] = c;
         s_fail = fl != 0.0 ? 1 : 0;
     }
-    for (int q = tid; q < N; q += kT) s_z[q] = w.b[q];
+    for (int q = tid; q < 6 * V; q += kT) s_z[q] = w.b[q];
     double* __restrict__ S = w.S;
-    for (int k = 0; k < V; ++k) {
+    if constexpr (CAMERA) {                          // the camera's rows 6 V .. of S (and their mirror)
+        const double lam = w.it[kLambda];
+        const int c6 = 6 * V;
+        if (tid < kK * kK) {
+            double c = 0.0, z = 0.0;
+            for (int v = 0; v < V; ++v) { c += w.Gv[kK * kK * v + tid]; z += w.Zv[kK * kK * v + tid]; }
+            s_c[tid] = c; s_c[kK * kK + tid] = z;
+        }
+        __syncthreads();
+        if (tid < kK * kK && tid % kK <= tid / kK) { // C* as ONE block; an unrefined word: the identity's row and column
+            const int k = tid / kK, l = tid % kK;
+            double dmx = 0.0;
+#pragma unroll
+            for (int q = 0; q < kK; ++q) dmx = fmax(dmx, s_c[(kK + 1) * q]);
+            double val = k == l ? 1.0 : 0.0;
+            if (((pb.mask >> k) & 1u) && ((pb.mask >> l) & 1u))
+                val = (s_c[tid] + (k == l ? lam * fmax(s_c[tid], 1e-12 * dmx) : 0.0)) - s_c[kK * kK + tid];
+            S[(int64_t)(c6 + k) * N + c6 + l] = val;
+            S[(int64_t)(c6 + l) * N + c6 + k] = val;
+        }
+        for (int q = tid; q < kK * c6; q += kT) {    // S_ki = (H_i - its eliminated part)^T
+            const int k = q / c6, col = q % c6;
+            const double val = w.Hv[kK * col + k] - w.Zh[kK * col + k];
+            S[(int64_t)(c6 + k) * N + col] = val;
+            S[(int64_t)col * N + c6 + k] = val;
+        }
+    }
+    for (int k = 0; k < NP; ++k) {
         const int c0 = 6 * k;
         __syncthreads();
         if (tid < 36) s_d[tid] = S[(int64_t)(c0 + tid / 6) * N + c0 + tid % 6];
@@ -544,7 +790,7 @@ balm_solve(Ws w, Prob pb) {
         }
     }
     // back substitution L^T x = z, by panels from the last
-    for (int k = V - 1; k >= 0; --k) {
+    for (int k = NP - 1; k >= 0; --k) {
         const int c0 = 6 * k;
         __syncthreads();
         if (tid < 36) s_d[tid] = S[(int64_t)(c0 + tid / 6) * N + c0 + tid % 6];
@@ -566,16 +812,20 @@ balm_solve(Ws w, Prob pb) {
     }
     __syncthreads();
     double dm = 0.0;
-    for (int q = tid; q < N; q += kT) { w.b[q] = s_z[q]; dm = fmax(dm, fabs(s_z[q])); }
+    for (int q = tid; q < N; q += kT) {              // (delta_k enters max |delta| scaled, in balm_backsub)
+        w.b[q] = s_z[q];
+        if (q < 6 * V) dm = fmax(dm, fabs(s_z[q]));
+    }
     dm = block_max<kT>(dm, s_mx);
     if (tid == 0) { w.sum[sDmaxC] = dm; w.sum[sFailed] = s_fail ? 1.0 : 0.0; }
 }
 
 // grid: nb workgroups: thread = point, then view
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
-balm_backsub(const double* __restrict__ poses, const double* __restrict__ points, Ws w, Prob pb) {
+balm_backsub(const double* __restrict__ poses, const double* __restrict__ points, const double* __restrict__ camera, Ws w, Prob pb) {
     __shared__ double s_mx[kT / 64];
-    if (!header_ok(w, pb) || w.it[kDone] != 0.0 || w.sum[sFailed] != 0.0) return;
+    if (!ready<CAMERA>(w, pb) || w.it[kDone] != 0.0 || w.sum[sFailed] != 0.0) return;
     const int64_t idx = (int64_t)blockIdx.x * kT + threadIdx.x;
     double dm = 0.0;
     if (idx < pb.P) {
@@ -593,6 +843,17 @@ balm_backsub(const double* __restrict__ poses, const double* __restrict__ points
                 const double wt = w.rw[3 * o + 2];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) s[c] += wt * (jp[c] * e0 + jp[3 + c] * e1);
+            }
+            if constexpr (CAMERA) {                  // + Y_p^T delta_k
+                const double* __restrict__ dk = w.b + 6 * pb.V;
+                const double* __restrict__ yp = w.Yp + 3 * kK * idx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int k = 0; k < kK; ++k) t += yp[3 * k + c] * dk[k];
+                    s[c] += t;
+                }
             }
             const double* __restrict__ vi = w.Vinv + 6 * idx;
             const double d[3] = {-((vi[0] * s[0] + vi[1] * s[1]) + vi[2] * s[2]), -((vi[1] * s[0] + vi[3] * s[1]) + vi[4] * s[2]),
@@ -616,23 +877,41 @@ balm_backsub(const double* __restrict__ poses, const double* __restrict__ points
         }
 #pragma unroll
         for (int q = 0; q < 12; ++q) w.cand_poses[12 * v + q] = C[q];
+        if constexpr (CAMERA)
+            if (v == 0) {                            // the candidate camera; its step enters max |delta| relative to the word
+                double cc[kK];
+#pragma unroll
+                for (int k = 0; k < kK; ++k) {
+                    const double ck = camera[k], dk = w.b[6 * pb.V + k];
+                    const bool on = (pb.mask >> k) & 1u;
+                    cc[k] = on ? ck + dk : ck;
+                    if (on) dm = fmax(dm, fabs(dk) / (1.0 + fabs(ck)));
+                }
+                if (pb.tie) cc[1] = pb.aspect * cc[0];
+#pragma unroll
+                for (int k = 0; k < kK; ++k) w.cand_cam[k] = cc[k];
+            }
     }
     dm = block_max<kT>(dm, s_mx);
     if (threadIdx.x == 0) w.dblk[blockIdx.x] = dm;
 }
 
 // grid: V workgroups
+template <bool CAMERA>
 __global__ void __launch_bounds__(kT)
 balm_cost(const double* __restrict__ obs_uv, Ws w, Prob pb) {
     __shared__ double s_red[kT / 64];
-    if (!header_ok(w, pb) || w.it[kDone] != 0.0 || w.sum[sFailed] != 0.0) return;
+    if (!ready<CAMERA>(w, pb) || w.it[kDone] != 0.0 || w.sum[sFailed] != 0.0) return;
     const int v = blockIdx.x, tid = threadIdx.x;
     double P[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) P[q] = w.cand_poses[12 * v + q];
+    Cam cam = {};
+    if constexpr (CAMERA) cam = camera_model::load_camera<double>(w.cand_cam, 0);
     double a[1] = {0.0};
     for (int i = w.view_start[v] + tid; i < w.view_start[v + 1]; i += kT) {
-        const ObsEval e = eval_obs(P, w.cand_points + 3 * (int64_t)w.obs_point[i], obs_uv + 2 * (int64_t)i, pb);
+        Lens L;
+        const ObsEval e = eval_obs<CAMERA>(P, w.cand_points + 3 * (int64_t)w.obs_point[i], obs_uv + 2 * (int64_t)i, pb, cam, L);
         a[0] += 0.5 * e.rho;
     }
     block_sum<1, kT>(a, s_red);
@@ -642,6 +921,34 @@ balm_cost(const double* __restrict__ obs_uv, Ws w, Prob pb) {
 bool opts_ok(const ls2fm_ba_lm_opts* o) {
     return o && o->loss >= 0 && o->loss <= 2 && o->loss_scale > 0.0 && std::isfinite(o->loss_scale) && o->initial_lambda > 0.0 &&
            std::isfinite(o->initial_lambda) && o->grad_tol >= 0.0 && o->step_tol >= 0.0 && o->min_point_views >= 1;
+}
+
+// the launches of a call, shared by the two entry points: pb is filled but for the sizes and the options
+template <bool CAMERA>
+int run(double* poses, double* points, double* camera, const double* obs_uv, int32_t n_views, int64_t n_points, int64_t n_obs, Prob pb,
+        const ls2fm_ba_lm_opts* opts, int32_t n_iters, double* state, double* log, void* workspace, hipStream_t stream) {
+    const Ws w = layout(workspace, n_views, n_points, n_obs, CAMERA);
+    pb.V = n_views; pb.P = (int)n_points; pb.n = (int)n_obs; pb.nb = (int)n_blocks(n_views, n_points); pb.loss = opts->loss;
+    pb.c2 = opts->loss_scale * opts->loss_scale;
+    pb.lambda0 = opts->initial_lambda; pb.grad_tol = opts->grad_tol; pb.step_tol = opts->step_tol;
+    const unsigned V = (unsigned)n_views, nb = (unsigned)pb.nb, pairs = V * (V + 1) / 2;
+    // (the opt-in event pairs of profile.hip bracket every launch: tools/time_ba_lm.py reads the kernels' shares from them)
+    auto span = [&](int id, auto&& launch) { ls2fm_prof_begin(id, stream); launch(); ls2fm_prof_end(id, stream); };
+    for (int32_t it = 0; it < n_iters; ++it) {
+        double* log_prev = it > 0 ? log + 6 * (int64_t)(it - 1) : nullptr;
+        span(LS2FM_PROF_BALM_LINEARIZE, [&] { balm_linearize<CAMERA><<<V, kT, 0, stream>>>(poses, points, camera, obs_uv, w, pb, state, it > 0 ? 1 : 0, 0, log_prev); });
+        span(LS2FM_PROF_BALM_POINTS, [&] { balm_points<CAMERA><<<nb, kT, 0, stream>>>(poses, points, camera, w, pb, state, 0); });
+        span(LS2FM_PROF_BALM_SCHUR, [&] { balm_schur<CAMERA><<<pairs, kT, 0, stream>>>(w, pb); });
+        if constexpr (CAMERA)
+            span(LS2FM_PROF_BALM_BORDER, [&] { balm_border<<<dim3(V, kK / kBorderCols), kT, 0, stream>>>(w, pb); });
+        span(LS2FM_PROF_BALM_SOLVE, [&] { balm_solve<CAMERA><<<1, kT, 0, stream>>>(w, pb); });
+        span(LS2FM_PROF_BALM_BACKSUB, [&] { balm_backsub<CAMERA><<<nb, kT, 0, stream>>>(poses, points, camera, w, pb); });
+        span(LS2FM_PROF_BALM_COST, [&] { balm_cost<CAMERA><<<V, kT, 0, stream>>>(obs_uv, w, pb); });
+    }
+    // the decision on the last iteration: the caller's poses, points (and camera) and state are final when these two end
+    balm_linearize<CAMERA><<<1, kT, 0, stream>>>(poses, points, camera, obs_uv, w, pb, state, 1, 1, log + 6 * (int64_t)(n_iters - 1));
+    balm_points<CAMERA><<<nb, kT, 0, stream>>>(poses, points, camera, w, pb, state, 1);
+    return ls2fm_launch_status();
 }
 
 }  // namespace
@@ -695,27 +1002,30 @@ extern "C" int ls2fm_bundle_adjust_lm_run(double* poses, double* points, const d
     for (int q = 0; q < 4; ++q) LS2FM_CHECK_ARG(std::isfinite(intrinsic4_host[q]));
     LS2FM_CHECK_ARG(intrinsic4_host[0] != 0.0 && intrinsic4_host[1] != 0.0);
     if (!workspace) return LS2FM_ERR_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    const Ws w = layout(workspace, n_views, n_points, n_obs);
-    Prob pb;
-    pb.V = n_views; pb.P = (int)n_points; pb.n = (int)n_obs; pb.nb = (int)n_blocks(n_views, n_points); pb.loss = opts->loss;
+    Prob pb = {};
     pb.fx = intrinsic4_host[0]; pb.fy = intrinsic4_host[1]; pb.cx = intrinsic4_host[2]; pb.cy = intrinsic4_host[3];
-    pb.c2 = opts->loss_scale * opts->loss_scale;
-    pb.lambda0 = opts->initial_lambda; pb.grad_tol = opts->grad_tol; pb.step_tol = opts->step_tol;
-    const unsigned V = (unsigned)n_views, nb = (unsigned)pb.nb, pairs = V * (V + 1) / 2;
-    // (the opt-in event pairs of profile.hip bracket every launch: tools/time_ba_lm.py reads the kernels' shares from them)
-    auto span = [&](int id, auto&& launch) { ls2fm_prof_begin(id, stream); launch(); ls2fm_prof_end(id, stream); };
-    for (int32_t it = 0; it < n_iters; ++it) {
-        double* log_prev = it > 0 ? log + 6 * (int64_t)(it - 1) : nullptr;
-        span(LS2FM_PROF_BALM_LINEARIZE, [&] { balm_linearize<<<V, kT, 0, stream>>>(poses, points, obs_uv, w, pb, state, it > 0 ? 1 : 0, 0, log_prev); });
-        span(LS2FM_PROF_BALM_POINTS, [&] { balm_points<<<nb, kT, 0, stream>>>(poses, points, w, pb, state, 0); });
-        span(LS2FM_PROF_BALM_SCHUR, [&] { balm_schur<<<pairs, kT, 0, stream>>>(w, pb); });
-        span(LS2FM_PROF_BALM_SOLVE, [&] { balm_solve<<<1, kT, 0, stream>>>(w, pb); });
-        span(LS2FM_PROF_BALM_BACKSUB, [&] { balm_backsub<<<nb, kT, 0, stream>>>(poses, points, w, pb); });
-        span(LS2FM_PROF_BALM_COST, [&] { balm_cost<<<V, kT, 0, stream>>>(obs_uv, w, pb); });
-    }
-    // the decision on the last iteration: the caller's poses, points and state are final when these two end
-    balm_linearize<<<1, kT, 0, stream>>>(poses, points, obs_uv, w, pb, state, 1, 1, log + 6 * (int64_t)(n_iters - 1));
-    balm_points<<<nb, kT, 0, stream>>>(poses, points, w, pb, state, 1);
-    return ls2fm_launch_status();
+    return run<false>(poses, points, nullptr, obs_uv, n_views, n_points, n_obs, pb, opts, n_iters, state, log, workspace,
+                      (hipStream_t)stream_);
+}
+
+extern "C" int64_t ls2fm_bundle_adjust_lm_camera_workspace_bytes(int32_t n_views, int64_t n_points, int64_t n_obs) {
+    if (!sizes_ok(n_views, n_points, n_obs)) return LS2FM_ERR_INVALID_ARGUMENT;
+    if (n_views > kMaxCamViews) return LS2FM_ERR_UNSUPPORTED;
+    return layout(nullptr, n_views, n_points, n_obs, true).bytes;
+}
+
+extern "C" int ls2fm_bundle_adjust_lm_run_camera(double* poses, double* points, double* camera, const double* obs_uv, int32_t n_views,
+                                                 int64_t n_points, int64_t n_obs, uint32_t refine_mask, int32_t tie_focal, double aspect,
+                                                 const ls2fm_ba_lm_opts* opts, int32_t n_iters, double* state, double* log,
+                                                 void* workspace, void* stream_) {
+    LS2FM_CHECK_ARG(sizes_ok(n_views, n_points, n_obs) && n_iters >= 1 && n_iters <= (1 << 20));
+    if (n_views > kMaxCamViews) return LS2FM_ERR_UNSUPPORTED;             // the camera's rows are two of the Cholesky's panels
+    LS2FM_CHECK_ARG(poses && points && camera && obs_uv && state && log && opts_ok(opts));
+    LS2FM_CHECK_ARG(refine_mask < (1u << kK) && std::isfinite(aspect));
+    LS2FM_CHECK_ARG(!tie_focal || ((refine_mask & 1u) && !(refine_mask & 2u)));
+    if (!workspace) return LS2FM_ERR_WORKSPACE;
+    Prob pb = {};
+    pb.mask = refine_mask; pb.tie = tie_focal ? 1 : 0; pb.aspect = aspect;
+    return run<true>(poses, points, camera, obs_uv, n_views, n_points, n_obs, pb, opts, n_iters, state, log, workspace,
+                     (hipStream_t)stream_);
 }

@@ -76,4 +76,27 @@ __device__ __forceinline__ void jacobian(const Camera<T>& c, const Radial<T>& o,
     jd = add(add(add(o.rad, mul(y, gy)), mul(c.p1, mul(six, y))), mul(p2_2, x));
 }
 
+// J_k = d(fx xd + cx, fy yd + cy)/d(the 12 words) at the point whose Radial is o and whose distorted point is (xd, yd): row u into
+// ju, row v into jv, the words in the camera's order (THE CAMERA BLOCK of include/ls2fm.h)
+template <class T>
+__device__ __forceinline__ void jacobian_k(const Camera<T>& c, const Radial<T>& o, T x, T y, T xd, T yd, T (&ju)[12], T (&jv)[12]) {
+#pragma clang fp contract(off)
+    const T zero = (T)0, one = (T)1, two = (T)2;
+    const T fxx = mul(c.fx, x), fyy = mul(c.fy, y), xy2 = mul(two, mul(x, y));
+    const T q1 = quot(o.r2, o.den), q2 = mul(q1, o.r2), q3 = mul(q2, o.r2);                 // r2^j / den
+    const T n1 = sub(zero, mul(o.rad, q1)), n2 = sub(zero, mul(o.rad, q2)), n3 = sub(zero, mul(o.rad, q3));
+    ju[0] = xd;   jv[0] = zero;
+    ju[1] = zero; jv[1] = yd;
+    ju[2] = one;  jv[2] = zero;
+    ju[3] = zero; jv[3] = one;
+    ju[4] = mul(fxx, q1); jv[4] = mul(fyy, q1);
+    ju[5] = mul(fxx, q2); jv[5] = mul(fyy, q2);
+    ju[6] = mul(c.fx, xy2); jv[6] = mul(c.fy, add(o.r2, mul(mul(two, y), y)));
+    ju[7] = mul(c.fx, add(o.r2, mul(mul(two, x), x))); jv[7] = mul(c.fy, xy2);
+    ju[8] = mul(fxx, q3); jv[8] = mul(fyy, q3);
+    ju[9] = mul(fxx, n1); jv[9] = mul(fyy, n1);
+    ju[10] = mul(fxx, n2); jv[10] = mul(fyy, n2);
+    ju[11] = mul(fxx, n3); jv[11] = mul(fyy, n3);
+}
+
 }  // namespace camera_model

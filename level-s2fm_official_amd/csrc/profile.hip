@@ -13,7 +13,7 @@ const char* const kNames[LS2FM_PROF_COUNT] = {
     "prep_weights", "ray_encode_sdf", "ray_encode_rad", "shade_fwd", "shade_bwd", "wgrad_mlp_geo", "wgrad_dec",
     "slab_accumulate", "scatter_fill", "reduce_finalize", "sdf_eval", "sphere_trace", "post_shade", "loss_head_fwd",
     "loss_head_bwd", "wgrad_mlp_sdf", "pose_grad", "ray_encode_pair", "balm_linearize", "balm_points", "balm_schur", "balm_solve",
-    "balm_backsub", "balm_cost"};
+    "balm_backsub", "balm_cost", "balm_border"};
 
 struct Span { int id; hipEvent_t a, b; };
 

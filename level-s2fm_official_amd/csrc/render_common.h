@@ -16,7 +16,7 @@ enum ls2fm_prof_id {
     LS2FM_PROF_SDF_EVAL, LS2FM_PROF_SPHERE_TRACE, LS2FM_PROF_BIN, LS2FM_PROF_LOSS_FWD,
     LS2FM_PROF_LOSS_BWD, LS2FM_PROF_WGRAD_MLP, LS2FM_PROF_POSE, LS2FM_PROF_ENCODE_PAIR,
     LS2FM_PROF_BALM_LINEARIZE, LS2FM_PROF_BALM_POINTS, LS2FM_PROF_BALM_SCHUR, LS2FM_PROF_BALM_SOLVE, LS2FM_PROF_BALM_BACKSUB,
-    LS2FM_PROF_BALM_COST, LS2FM_PROF_COUNT
+    LS2FM_PROF_BALM_COST, LS2FM_PROF_BALM_BORDER, LS2FM_PROF_COUNT
 };
 bool ls2fm_prof_enabled();
 void ls2fm_prof_begin(int id, hipStream_t stream);      // bracket one kernel launch on the stream it is enqueued on

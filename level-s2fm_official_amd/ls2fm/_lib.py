@@ -228,6 +228,9 @@ _SIGNATURES = {
     "ls2fm_bundle_adjust_lm_prepare": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P, c_int32, _P, _P]),
     "ls2fm_bundle_adjust_lm_run": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int64, POINTER(c_double), POINTER(BALMOpts), c_int32, _P, _P, _P,
                                              _P]),
+    "ls2fm_bundle_adjust_lm_camera_workspace_bytes": (c_int64, [c_int32, c_int64, c_int64]),
+    "ls2fm_bundle_adjust_lm_run_camera": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int64, c_uint32, c_int32, c_double, POINTER(BALMOpts),
+                                                    c_int32, _P, _P, _P, _P]),
     "ls2fm_match_descriptors_workspace_bytes": (c_int64, [_P, c_int32, _P, c_int32]),
     "ls2fm_match_descriptors": (c_int32, [_P, _P, c_int32, _P, c_int32, c_double, c_double, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "ls2fm_sift_workspace_bytes": (c_int64, [_P, _P, c_int32, POINTER(SiftOpts)]),

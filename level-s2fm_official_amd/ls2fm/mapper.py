@@ -654,3 +654,44 @@ def reconstruct(n_views, intrinsic, H, W, options=None, device="cuda"):
                 break
         m.init["new_points"] = int(m.init["new_points"])
         return m.finish()
+
+
+def refine_camera(rec, camera=None, refine=("f", "k1", "k2"), max_iter=50, loss="cauchy", loss_scale=2.0):
+    """Estimate the shared camera's words from a finished `Reconstruction`: ONE global ls2fm.stage.LMBALoop over the registered
+    views with THE CAMERA BLOCK of include/ls2fm.h, the first registered view constant -> (camera fp64 [12] on rec's device,
+    Reconstruction).  camera: the starting 12 words of ls2fm.undistort (None: the pinhole rec.intrinsic with zero distortion);
+    refine: the words that move, as LMBALoop takes them.  The photographs' own key points are
+    distort_points(rec.obs_uv, camera, out_intr=rec.intrinsic); the returned reconstruction carries the new poses and points, those
+    key points undistorted under the refined camera's pinhole, and that pinhole (K fp64 [3, 3], host) as its intrinsic.
+    `reconstruct` itself still registers under fixed intrinsics: re-running it under a moving camera is not done here."""
+    from . import undistort as _und
+    from .stage import LMBALoop
+    dev = rec.X.device
+    k4 = torch.as_tensor(_intrinsic4(rec.intrinsic), dtype=torch.float64)
+    if camera is None:
+        camera = torch.cat([k4, torch.zeros(_und.CAMERA_PARAMS - 4, dtype=torch.float64)])
+    camera = torch.as_tensor(camera).detach().to(device=dev, dtype=torch.float64)
+    raw = _und.distort_points(rec.obs_uv.to(dev), camera, out_intr=k4)[0]
+    views = [v for v in range(len(rec.registered)) if rec.registered[v]]
+    if not views:
+        raise ValueError("ls2fm.mapper.refine_camera: no registered view")
+    ts = rec.tracks["track_start"].long()
+    n_obs = rec.tracks["obs_view"].numel()
+    track_of = torch.bucketize(torch.arange(n_obs, device=ts.device), ts[1:], right=True)
+    keep = rec.obs_keep & rec.track_valid[track_of]
+    new_id = torch.cumsum(rec.track_valid.long(), 0) - 1
+    view = rec.tracks["obs_view"].long()
+    sels = [keep & (view == v) for v in views]
+    ba = _BAViews(rec.poses[views].double(), None, None, [raw[s] for s in sels], [new_id[track_of[s]] for s in sels],
+                  rec.X[rec.track_valid].double())
+    loop = LMBALoop(ba, constant_views=(views.index(rec.order[0]),) if rec.order else (0,), max_iter=max_iter, loss=loss,
+                    loss_scale=loss_scale, camera=camera, refine=refine)
+    loop.run()
+    poses, X = rec.poses.clone(), rec.X.clone()
+    poses[views] = loop.poses.to(poses.dtype)
+    X[rec.track_valid] = loop.xyzs_all.to(X.dtype)
+    out_cam = loop.camera.detach().clone()
+    K = _und.intrinsic_matrices(out_cam[None, :4].cpu())[0]
+    obs_uv = _und.undistort_points(raw, out_cam)[0].to(rec.obs_uv.dtype)
+    return out_cam, Reconstruction(rec.order, rec.registered, poses, X, rec.track_valid, rec.obs_keep, rec.tracks, obs_uv, K, rec.H, rec.W,
+                                   rec.init, rec.log)

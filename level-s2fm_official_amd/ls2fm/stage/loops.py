@@ -20,6 +20,7 @@ from .. import _lib
 from .. import dist as _dist
 from .. import fused as _fused
 from ..optim import FusedAdam
+from ..undistort import _distort_torch, _jacobian_k_torch, _jacobian_torch
 from ..utils import camera as _cam
 from .step import RenderStage, _EarlyTrace, _capture_step, _point_side, _weight_factor, _weight_lookup
 from .terms import _BATerms, _MatchTerm, _TracingTerm, _weighted_pair, host_intrinsic, reprojection_term
@@ -819,20 +820,41 @@ class LMBALoop:
     State after `run()` / `step()`: `poses` [V,3,4] and `xyzs_all` [M,3] (fp64; all points of the set, the ones no picked view
     observes unchanged), `poses_se3()`, `cost()` (0-d tensor), `stopped()` -> (reason, iterations), a host read; reason is one of
     "running", "gradient", "step", "lambda", "max_iter".
+
+    camera: THE CAMERA BLOCK of include/ls2fm.h.  The [12] vector of ls2fm.undistort (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5,
+    k6) shared by all views; the views' key points are then positions in the photographs AS TAKEN and `views.intrinsic` is not
+    read.  refine: the words that move, names of CAMERA_WORDS; "f" moves fx with fy tied to it at the starting aspect fy / fx and
+    excludes "fx" / "fy"; () only changes the residual model.  At most 126 views.  After `run()`, `camera` (fp64 [12] on the
+    loop's device) holds the result.  One more launch per iteration (ls2fm_bundle_adjust_lm_run_camera).
     """
     LOSSES = ("trivial", "soft_l1", "cauchy")
     REASONS = ("running", "gradient", "step", "lambda")
     MAX_VIEWS = 128                      # LS2FM_BA_LM_MAX_VIEWS
+    MAX_VIEWS_CAMERA = 126               # the camera's rows are two of the Cholesky's panels
     KEYS = ("cost", "cost_candidate", "lambda", "accepted", "grad_max", "step_max")
+    CAMERA_WORDS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")
 
     def __init__(self, views, cam_pick=None, constant_views=(), max_iter=50, loss="trivial", loss_scale=1.0, initial_lambda=1e-4,
-                 grad_tol=1e-10, step_tol=1e-10, min_point_views=2):
+                 grad_tol=1e-10, step_tol=1e-10, min_point_views=2, camera=None, refine=()):
         n_all = len(views.track_ids)
         self.cam_pick = list(range(n_all)) if cam_pick is None else [int(c) for c in cam_pick]
         if not self.cam_pick or any(c < 0 or c >= n_all for c in self.cam_pick) or len(set(self.cam_pick)) != len(self.cam_pick):
             raise ValueError(f"cam_pick {self.cam_pick} does not select distinct views of 0..{n_all - 1}")
         if len(self.cam_pick) > self.MAX_VIEWS:
             raise ValueError(f"LMBALoop: {len(self.cam_pick)} picked views; the dense reduced camera system serves at most {self.MAX_VIEWS}")
+        refine = (refine,) if isinstance(refine, str) else tuple(refine)
+        if camera is None and refine:
+            raise ValueError("LMBALoop: refine names camera words but no camera is given")
+        if camera is not None and len(self.cam_pick) > self.MAX_VIEWS_CAMERA:
+            raise ValueError(f"LMBALoop: {len(self.cam_pick)} picked views; with a camera the reduced system serves at most "
+                             f"{self.MAX_VIEWS_CAMERA}")
+        unknown = [r for r in refine if r != "f" and r not in self.CAMERA_WORDS]
+        if unknown:
+            raise ValueError(f"LMBALoop: refine names {unknown}; the words are 'f' and {self.CAMERA_WORDS}")
+        self.tie_focal = "f" in refine
+        if self.tie_focal and ("fx" in refine or "fy" in refine):
+            raise ValueError("LMBALoop: refine has 'f' (fy tied to fx) together with 'fx' / 'fy'")
+        self.refine_mask = sum({1 << (0 if r == "f" else self.CAMERA_WORDS.index(r)) for r in refine})
         if loss not in self.LOSSES:
             raise ValueError(f"LMBALoop: loss {loss!r} is not one of {self.LOSSES}")
         if int(max_iter) < 1 or int(min_point_views) < 1:
@@ -846,15 +868,17 @@ class LMBALoop:
         self.grad_tol, self.step_tol, self.min_point_views = float(grad_tol), float(step_tol), int(min_point_views)
         self.views = views
         dev = views.xyzs.device
-        k_host = getattr(views, "host_intrinsic", None)
-        k_host = (views.intrinsic.detach().cpu() if k_host is None else k_host).double()
-        if tuple(k_host.shape) != (3, 3) or not bool(torch.isfinite(k_host).all()):
-            raise ValueError(f"LMBALoop: the intrinsic must be a finite K [3, 3], got shape {tuple(k_host.shape)}")
-        if k_host[0, 1] != 0 or k_host[1, 0] != 0:
-            raise ValueError("LMBALoop: the intrinsic has skew; the solver serves a pinhole (fx, fy, cx, cy)")
-        if k_host[2].tolist() != [0.0, 0.0, 1.0]:
-            raise ValueError(f"LMBALoop: the intrinsic's last row is {k_host[2].tolist()}, not (0, 0, 1)")
-        self.k4 = [float(k_host[0, 0]), float(k_host[1, 1]), float(k_host[0, 2]), float(k_host[1, 2])]
+        self.camera = None
+        if camera is not None:
+            cam_host = torch.as_tensor(camera).detach().cpu().double()       # ONE host read when the loop is built: the aspect
+            if tuple(cam_host.shape) != (len(self.CAMERA_WORDS),) or not bool(torch.isfinite(cam_host).all()) or \
+                    float(cam_host[0]) == 0 or float(cam_host[1]) == 0:
+                raise ValueError("LMBALoop: camera must be 12 finite words (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6), fx, fy != 0")
+            self.aspect = float(cam_host[1]) / float(cam_host[0])
+            self.camera = cam_host.to(dev).contiguous()
+            self.k4 = None
+        else:
+            self._init_pinhole(views)
         p = views.poses.detach().to(dev).double()
         p = _cam.lie.se3_to_SE3(p) if p.shape[-1] == 6 else p
         self.poses = p[self.cam_pick].clone().contiguous()
@@ -871,18 +895,33 @@ class LMBALoop:
         else:
             self._init_torch()
 
+    def _init_pinhole(self, views):
+        k_host = getattr(views, "host_intrinsic", None)
+        k_host = (views.intrinsic.detach().cpu() if k_host is None else k_host).double()
+        if tuple(k_host.shape) != (3, 3) or not bool(torch.isfinite(k_host).all()):
+            raise ValueError(f"LMBALoop: the intrinsic must be a finite K [3, 3], got shape {tuple(k_host.shape)}")
+        if k_host[0, 1] != 0 or k_host[1, 0] != 0:
+            raise ValueError("LMBALoop: the intrinsic has skew; the solver serves a pinhole (fx, fy, cx, cy)")
+        if k_host[2].tolist() != [0.0, 0.0, 1.0]:
+            raise ValueError(f"LMBALoop: the intrinsic's last row is {k_host[2].tolist()}, not (0, 0, 1)")
+        self.k4 = [float(k_host[0, 0]), float(k_host[1, 1]), float(k_host[0, 2]), float(k_host[1, 2])]
+
     # ---- device path
     def _init_device(self):
         lib = _lib.load()
         V, P, n, dev = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0], self.poses.device
-        self._ws = _lib.workspace(lib.ls2fm_bundle_adjust_lm_workspace_bytes(V, P, n), "ls2fm_bundle_adjust_lm_workspace_bytes", dev)
+        if self.camera is not None:
+            self._ws = _lib.workspace(lib.ls2fm_bundle_adjust_lm_camera_workspace_bytes(V, P, n),
+                                      "ls2fm_bundle_adjust_lm_camera_workspace_bytes", dev)
+        else:
+            self._ws = _lib.workspace(lib.ls2fm_bundle_adjust_lm_workspace_bytes(V, P, n), "ls2fm_bundle_adjust_lm_workspace_bytes", dev)
         self._obs_point32 = self.obs_point.to(torch.int32).contiguous()
         status = lib.ls2fm_bundle_adjust_lm_prepare(_lib.ptr(self.view_start), V, _lib.ptr(self._obs_point32), n, P, _lib.ptr(self.view_constant),
                                                     self.min_point_views, _lib.ptr(self._ws), _lib.stream_ptr())
         if status == -1:                 # the sizes were checked above: what is left of "invalid argument" is the lists' content
             raise ValueError("LMBALoop: duplicate observations (a point observed twice by one view) or a point index outside the set")
         _lib.check(status, "ls2fm_bundle_adjust_lm_prepare")
-        self._k_host = (ctypes.c_double * 4)(*self.k4)
+        self._k_host = (ctypes.c_double * 4)(*self.k4) if self.camera is None else None
         self._opts = _lib.BALMOpts(self.LOSSES.index(self.loss), self.loss_scale, self.initial_lambda, self.grad_tol, self.step_tol,
                                    self.min_point_views)
         self._state = torch.zeros(8, dtype=torch.float64, device=dev)
@@ -891,6 +930,12 @@ class LMBALoop:
         lib = _lib.load()
         V, P, n = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_point.shape[0]
         log = torch.empty(n_iters, 6, dtype=torch.float64, device=self.poses.device)
+        if self.camera is not None:
+            _lib.check(lib.ls2fm_bundle_adjust_lm_run_camera(_lib.ptr(self.poses), _lib.ptr(self.xyzs_all), _lib.ptr(self.camera),
+                                                             _lib.ptr(self.obs_uv), V, P, n, self.refine_mask, int(self.tie_focal), self.aspect,
+                                                             ctypes.byref(self._opts), n_iters, _lib.ptr(self._state), _lib.ptr(log),
+                                                             _lib.ptr(self._ws), _lib.stream_ptr()), "ls2fm_bundle_adjust_lm_run_camera")
+            return log
         _lib.check(lib.ls2fm_bundle_adjust_lm_run(_lib.ptr(self.poses), _lib.ptr(self.xyzs_all), _lib.ptr(self.obs_uv), V, P, n, self._k_host,
                                                   ctypes.byref(self._opts), n_iters, _lib.ptr(self._state), _lib.ptr(log), _lib.ptr(self._ws),
                                                   _lib.stream_ptr()), "ls2fm_bundle_adjust_lm_run")
@@ -906,11 +951,15 @@ class LMBALoop:
         self._state = torch.zeros(8, dtype=torch.float64)
         self._point_const = torch.bincount(self.obs_point, minlength=self.xyzs_all.shape[0]) < self.min_point_views
 
-    def _residuals(self, poses, X):
-        fx, fy, cx, cy = self.k4
+    def _residuals(self, poses, X, camera=None):
         Pv = poses[self.obs_view]
         xc = (Pv[:, :, :3] @ X[self.obs_point][:, :, None])[..., 0] + Pv[:, :, 3]
-        r = torch.stack([fx * xc[:, 0] / xc[:, 2] + cx - self.obs_uv[:, 0], fy * xc[:, 1] / xc[:, 2] + cy - self.obs_uv[:, 1]], dim=1)
+        if camera is not None:
+            xd, yd, _ = _distort_torch(camera.unbind(0), xc[:, 0] / xc[:, 2], xc[:, 1] / xc[:, 2])
+            r = torch.stack([camera[0] * xd + camera[2] - self.obs_uv[:, 0], camera[1] * yd + camera[3] - self.obs_uv[:, 1]], dim=1)
+        else:
+            fx, fy, cx, cy = self.k4
+            r = torch.stack([fx * xc[:, 0] / xc[:, 2] + cx - self.obs_uv[:, 0], fy * xc[:, 1] / xc[:, 2] + cy - self.obs_uv[:, 1]], dim=1)
         s, c2 = (r * r).sum(1), self.loss_scale ** 2
         if self.loss == "trivial":
             rho, w = s, torch.ones_like(s)
@@ -941,6 +990,21 @@ class LMBALoop:
         C[:, :, 3] += d[:, 3:]
         return C
 
+    @staticmethod
+    def _camera_jacobians(cam, xc):
+        """THE CAMERA BLOCK's Jacobians at camera points xc [n, 3]: J_proj = diag(fx, fy) J_dist [[1/z, 0, -x/z], [0, 1/z, -y/z]]
+        [n, 2, 3] and J_k [n, 2, 12], all twelve columns (the caller masks and ties them)"""
+        c = cam.unbind(0)
+        z = xc[:, 2]
+        xn, yn, iz = xc[:, 0] / z, xc[:, 1] / z, 1.0 / z
+        xd, yd, shared = _distort_torch(c, xn, yn)
+        ja, jb, jc_, jd = _jacobian_torch(c, shared, xn, yn)
+        Jproj = torch.zeros(xc.shape[0], 2, 3, dtype=torch.float64)
+        Jproj[:, 0, 0], Jproj[:, 0, 1], Jproj[:, 0, 2] = c[0] * (ja * iz), c[0] * (jb * iz), -(c[0] * ((ja * xn + jb * yn) * iz))
+        Jproj[:, 1, 0], Jproj[:, 1, 1], Jproj[:, 1, 2] = c[1] * (jc_ * iz), c[1] * (jd * iz), -(c[1] * ((jc_ * xn + jd * yn) * iz))
+        ku, kv = _jacobian_k_torch(c, shared, xn, yn, xd, yd)
+        return Jproj, torch.stack([torch.stack(ku, dim=1), torch.stack(kv, dim=1)], dim=1)
+
     def _iterate_torch(self):
         st = self._state
         lam = float(st[0]) if float(st[0]) > 0 else self.initial_lambda
@@ -948,12 +1012,20 @@ class LMBALoop:
             return torch.tensor([float(st[3]), float(st[3]), lam, -1.0, 0.0, 0.0], dtype=torch.float64)
         V, P, ov, op = self.poses.shape[0], self.xyzs_all.shape[0], self.obs_view, self.obs_point
         vconst, pconst = self.view_constant.bool(), self._point_const
-        xc, r, rho, w = self._residuals(self.poses, self.xyzs_all)
-        fx, fy = self.k4[0], self.k4[1]
+        cam = self.camera
+        xc, r, rho, w = self._residuals(self.poses, self.xyzs_all, cam)
         n = xc.shape[0]
         x, y, z = xc[:, 0], xc[:, 1], xc[:, 2]
         Jproj = torch.zeros(n, 2, 3, dtype=torch.float64)
-        Jproj[:, 0, 0], Jproj[:, 0, 2], Jproj[:, 1, 1], Jproj[:, 1, 2] = fx / z, -fx * x / (z * z), fy / z, -fy * y / (z * z)
+        if cam is not None:                    # THE CAMERA BLOCK: J_proj through the rule's Jacobian, and J_k masked and tied
+            kmask = torch.tensor([bool(self.refine_mask >> k & 1) for k in range(12)])
+            Jproj, Jk = self._camera_jacobians(cam, xc)
+            if self.tie_focal:
+                Jk[:, :, 0] = Jk[:, :, 0] + self.aspect * Jk[:, :, 1]
+            Jk[:, :, ~kmask] = 0.0
+        else:
+            fx, fy = self.k4[0], self.k4[1]
+            Jproj[:, 0, 0], Jproj[:, 0, 2], Jproj[:, 1, 1], Jproj[:, 1, 2] = fx / z, -fx * x / (z * z), fy / z, -fy * y / (z * z)
         skew = torch.zeros(n, 3, 3, dtype=torch.float64)
         skew[:, 0, 1], skew[:, 0, 2], skew[:, 1, 0], skew[:, 1, 2], skew[:, 2, 0], skew[:, 2, 1] = -z, y, z, -x, -y, x
         Jc = torch.cat([-(Jproj @ skew), Jproj], dim=2)
@@ -968,6 +1040,13 @@ class LMBALoop:
         cost = 0.5 * float(rho.sum())
         free = ~pconst
         gmax = max(float(gc.abs().max()), float(gp[free].abs().max()) if bool(free.any()) else 0.0)
+        if cam is not None:
+            G = torch.einsum("n,nki,nkj->ij", w, Jk, Jk)
+            gk = torch.einsum("n,nki,nk->i", w, Jk, r)
+            Hd = torch.zeros(V, 6, 12, dtype=torch.float64).index_add_(0, ov, w[:, None, None] * (Jc.transpose(1, 2) @ Jk)).reshape(6 * V, 12)
+            Yd = torch.zeros(P, 12, 3, dtype=torch.float64).index_add_(0, op, w[:, None, None] * (Jk.transpose(1, 2) @ Jp))
+            if bool(kmask.any()):
+                gmax = max(gmax, float(gk[kmask].abs().max()))
         pmax = max(float(self.poses[:, :, 3].abs().max()), float(self.xyzs_all[torch.unique(op)].abs().max()))
         cand, dmax, acc, done, reason, new_lam = float("nan"), 0.0, 0.0, 0.0, 0.0, lam
         if gmax <= self.grad_tol:
@@ -975,7 +1054,10 @@ class LMBALoop:
         else:
             step = None
             Vs, Us = self._damp(Vp, lam), self._damp(U, lam)
-            if bool(torch.isfinite(Vs).all() and torch.isfinite(Us).all() and torch.isfinite(W).all()):
+            finite = torch.isfinite(Vs).all() and torch.isfinite(Us).all() and torch.isfinite(W).all()
+            if cam is not None:
+                finite = finite and torch.isfinite(G).all() and torch.isfinite(Hd).all() and torch.isfinite(Yd).all()
+            if bool(finite):
                 eye3 = torch.eye(3, dtype=torch.float64).expand(P, 3, 3)
                 L, info = torch.linalg.cholesky_ex(torch.where(free[:, None, None], Vs, eye3))
                 if int(info.abs().max()) == 0:
@@ -985,25 +1067,41 @@ class LMBALoop:
                     Wd = torch.zeros(V, 6, P, 3, dtype=torch.float64)          # dense [6 V, 3 P]: the CPU path is test-scale
                     Wd[ov, :, op, :] = W
                     Wd = Wd.reshape(6 * V, P, 3)
+                    if cam is not None:    # the border: 12 more rows, the camera block damped as ONE block
+                        S = torch.block_diag(S, self._damp(G, lam))
+                        S[:6 * V, 6 * V:], S[6 * V:, :6 * V] = Hd, Hd.T
+                        b = torch.cat([b, -gk])
+                        Wd = torch.cat([Wd, Yd.transpose(0, 1)])
                     Y = torch.einsum("apk,pkl->apl", Wd, Vinv)
                     S = S - torch.einsum("apk,bpk->ab", Y, Wd)
                     b = b + torch.einsum("apk,pk->a", Y, gp)
+                    if cam is not None:    # an unrefined word: the identity's row and column, right-hand side 0
+                        off = 6 * V + torch.nonzero(~kmask)[:, 0]
+                        S[off, :], S[:, off], b[off] = 0.0, 0.0, 0.0
+                        S[off, off] = 1.0
                     Ls, info = torch.linalg.cholesky_ex(S)
                     if int(info) == 0:
                         dc = torch.cholesky_solve(b[:, None], Ls)[:, 0]
                         dp = -(Vinv @ (gp + torch.einsum("apk,a->pk", Wd, dc))[:, :, None])[..., 0]
-                        step = (dc.reshape(V, 6), dp)
+                        step = (dc[:6 * V].reshape(V, 6), dp, dc[6 * V:])
             if step is None:
                 new_lam = lam * 10.0
             else:
-                dc, dp = step
+                dc, dp, dk = step
                 cp = torch.where(vconst[:, None, None], self.poses, self._pose_update(self.poses, dc))
                 cx = self.xyzs_all + dp
-                cand = 0.5 * float(self._residuals(cp, cx)[2].sum())
+                ck = None
+                if cam is not None:
+                    ck = torch.where(kmask, cam + dk, cam)
+                    if self.tie_focal:
+                        ck[1] = self.aspect * ck[0]
+                cand = 0.5 * float(self._residuals(cp, cx, ck)[2].sum())
                 dmax = float(torch.fmax(dc.abs().max(), dp.abs().max()))
+                if cam is not None and bool(kmask.any()):
+                    dmax = max(dmax, float((dk.abs() / (1.0 + cam.abs()))[kmask].max()))
                 if cand < cost:
                     acc, new_lam = 1.0, max(lam * 0.1, 1e-16)
-                    self.poses, self.xyzs_all = cp.contiguous(), cx.contiguous()
+                    self.poses, self.xyzs_all, self.camera = cp.contiguous(), cx.contiguous(), ck
                     if dmax <= self.step_tol * (1.0 + pmax):
                         done, reason = 1.0, 2.0
                 else:
@@ -1042,6 +1140,11 @@ class LMBALoop:
         """mean pixel error |r| over the loop's observations at the current state (0-d tensor, torch ops, nothing read back)"""
         Pv = self.poses[self.obs_view]
         xc = (Pv[:, :, :3] @ self.xyzs_all[self.obs_point][:, :, None])[..., 0] + Pv[:, :, 3]
+        if self.camera is not None:
+            xd, yd, _ = _distort_torch(self.camera.unbind(0), xc[:, 0] / xc[:, 2], xc[:, 1] / xc[:, 2])
+            u = self.camera[0] * xd + self.camera[2] - self.obs_uv[:, 0]
+            v = self.camera[1] * yd + self.camera[3] - self.obs_uv[:, 1]
+            return torch.sqrt(u * u + v * v).mean()
         u = self.k4[0] * xc[:, 0] / xc[:, 2] + self.k4[2] - self.obs_uv[:, 0]
         v = self.k4[1] * xc[:, 1] / xc[:, 2] + self.k4[3] - self.obs_uv[:, 1]
         return torch.sqrt(u * u + v * v).mean()

@@ -157,6 +157,21 @@ def _jacobian_torch(c, shared, x, y):
     return a, b, cc, d
 
 
+def _jacobian_k_torch(c, shared, x, y, xd, yd):
+    """d(fx xd + cx, fy yd + cy)/d(the 12 words), THE CAMERA BLOCK of include/ls2fm.h -> (row u [12 tensors], row v [12 tensors])"""
+    fx, fy = c[0], c[1]
+    r2, den, rad = shared
+    zero, one = torch.zeros_like(x), torch.ones_like(x)
+    fxx, fyy, xy2 = fx * x, fy * y, 2 * (x * y)
+    q1 = r2 / den
+    q2 = q1 * r2
+    q3 = q2 * r2
+    n1, n2, n3 = 0 - (rad * q1), 0 - (rad * q2), 0 - (rad * q3)
+    ju = [xd, zero, one, zero, fxx * q1, fxx * q2, fx * xy2, fx * (r2 + (2 * x) * x), fxx * q3, fxx * n1, fxx * n2, fxx * n3]
+    jv = [zero, yd, zero, one, fyy * q1, fyy * q2, fy * (r2 + (2 * y) * y), fy * xy2, fyy * q3, fyy * n1, fyy * n2, fyy * n3]
+    return ju, jv
+
+
 def _views_of_rows(view_start, n):
     """per row its view (the last v with view_start[v] <= row) and whether the row belongs to any"""
     vs = view_start.long()
